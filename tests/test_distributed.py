@@ -200,8 +200,19 @@ def test_no_rank_outlives_a_parent_that_is_killed(how):
                               cwd=ROOT, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
 
     def ranks():
-        out = subprocess.run(["ps", "-eo", "pid,ppid,args"], capture_output=True, text=True).stdout.splitlines()
-        return [int(ln.split()[0]) for ln in out if len(ln.split()) > 2 and ln.split()[1] == str(parent.pid) and "bench.py" in ln]
+        # read /proc directly: `ps` cuts its args column to $COLUMNS, which can drop "bench.py" from a long command line
+        found = []
+        for entry in os.listdir("/proc"):
+            if not entry.isdigit():
+                continue
+            try:
+                ppid = int(open("/proc/%s/stat" % entry).read().rsplit(")", 1)[1].split()[1])
+                args = open("/proc/%s/cmdline" % entry, "rb").read().split(b"\0")
+            except (OSError, IndexError, ValueError):
+                continue  # gone in the meantime
+            if ppid == parent.pid and any(a.endswith(b"bench.py") for a in args):
+                found.append(int(entry))
+        return found
 
     deadline = time.time() + 60
     kids = []

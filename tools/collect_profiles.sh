@@ -14,10 +14,10 @@ find_csv() { find "$1" -name "*$2" | head -1; }
 
 # round 4: the command is the headline itself -- sessions of the camt53 guest over the trace circuit (one session in flight, so that the
 # per-kernel table is one session's; --profile-mode leaves the synthetic secondary runs out)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 5 --warmup 2 --cpu-po2 0 --contexts 1 --profile-mode > $DST/${TAG}_bench_under_rocprof.json 2> $OUT/stats.err || exit 11
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 5 --warmup 2 --cpu-po2 0 --contexts 1 --profile-mode --full > $DST/${TAG}_bench_under_rocprof.json 2> $OUT/stats.err || exit 11
 cp "$(find_csv $OUT/stats kernel_stats.csv)" $DST/${TAG}_kernel_stats.csv || exit 12
 
-CMD="python3 bench.py --steps 1 --warmup 1 --cpu-po2 0 --contexts 1 --profile-mode"
+CMD="python3 bench.py --steps 1 --warmup 1 --cpu-po2 0 --contexts 1 --profile-mode --full"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -- $CMD > $OUT/fetch.out 2> $OUT/fetch.err || exit 21
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -- $CMD > $OUT/write.out 2> $OUT/write.err || exit 22
 python3 tools/summarize_pmc.py "$(find_csv $OUT/fetch counter_collection.csv)" "$(find_csv $OUT/write counter_collection.csv)" $DST/pmc_traffic.json \
