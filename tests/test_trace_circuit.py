@@ -22,16 +22,13 @@ from conftest import circuit_path
 from test_rv32im import _guest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-from gen_circuit import OPCODES, TRACE_COLUMNS, check_trace_rows  # noqa: E402
+from gen_circuit import TRACE_COLUMNS, check_trace_rows  # noqa: E402
 import trace_circuit as tc  # noqa: E402
 import session_by_hand as sbh  # noqa: E402
+from trace_corners import COL, F, P, PRIMARY, R_INV, STAMP, canonical, expand, montgomery  # noqa: E402
 
-COL = {name: i for i, name in enumerate(TRACE_COLUMNS)}
-P = 2013265921
 REG = r0.REG_BASE
 PO2 = r0.TRACE_MIN_PO2
-F = dict(cycle=0, pc=1, insn=2, next_pc=3, rs1=4, rs2=5, rd=6, rd_before=7, rd_after=8, mem_kind=9, mem_addr=10, mem_before=11, mem_after=12, prev=13)
-STAMP = {0: 2, 1: 3, 2: 4, 3: 5, 4: 1}  # access (x[rs1], x[rs2], x[rd], memory, fetch) -> its place in the cycle
 
 
 def _run(n_loop=60, po2=20):
@@ -42,94 +39,6 @@ def _run(n_loop=60, po2=20):
     vm.set_input([7, 0x01020304])
     assert vm.run(segment_po2=po2, keep_trace=True, boundary_rows=True) == (0, 0)
     return vm, base
-
-
-PRIMARY = (["live", "bnd", "cycle", "pc", "next_pc"] + ["opc_" + n for n, _ in OPCODES[:-1]] + ["f3_%d" % k for k in range(1, 8)]
-           + ["rd0", "rdA", "rdB", "r10", "r1A", "r1B", "r20", "r2A", "r2B", "b25", "f7A", "f7B", "b30", "b31"]
-           + ["rs1_lo", "rs1_hi", "dl0", "dh0", "rs2_lo", "rs2_hi", "dl1", "dh1", "zrd", "inv_rd", "act2", "old_lo", "old_hi", "dl2", "dh2"]
-           + ["mem_wr", "top", "addr3", "before_lo", "before_hi", "after_lo", "after_hi", "p3", "dl4", "dh4", "fimg"])
-
-
-def expand(rows, bounds, po2, number=1, closing=True):
-    """The columns of the DATA group that come straight from the compact rows (PRIMARY), as canonical integers, [column, row]: the
-    specification of include/r0hip.h (r0h_preflight_row, r0h_preflight_bound, the trace-circuit paragraph) written out with numpy.
-    (Access 3's timestamp limbs are left out: rows that multiply keep a carry there.)"""
-    n, nr, nb = 1 << po2, len(rows), len(bounds)
-    m = np.zeros((len(TRACE_COLUMNS), n), dtype=np.int64)
-    inv = lambda v: pow(int(v) % P, P - 2, P)
-    r = rows.astype(np.int64)
-    L = slice(0, nr)
-    insn, cyc = r[:, F["insn"]], r[:, F["cycle"]]
-    m[COL["live"], L] = 1
-    m[COL["cycle"], L] = cyc
-    m[COL["pc"], L] = r[:, F["pc"]]
-    m[COL["next_pc"], L] = r[:, F["next_pc"]]
-    for name, code in OPCODES[:-1]:  # (FENCE, the last of the list, has no column: it is `live` minus the others)
-        m[COL["opc_" + name], L] = (insn & 0x7F) == code
-    for k in range(1, 8):            # (funct3 = 0 likewise: one minus the others)
-        m[COL["f3_%d" % k], L] = ((insn >> 12) & 7) == k
-    for stem, shift in (("rd", 7), ("r1", 15), ("r2", 20)):
-        idx = (insn >> shift) & 31
-        m[COL[stem + "0"] if stem != "rd" else COL["rd0"], L] = idx & 1
-        m[COL[stem + "A"], L] = (idx >> 1) & 3
-        m[COL[stem + "B"], L] = idx >> 3
-    m[COL["b25"], L], m[COL["f7A"], L], m[COL["f7B"], L], m[COL["b30"], L], m[COL["b31"], L] = (insn >> 25) & 1, (insn >> 26) & 3, (insn >> 28) & 3, (insn >> 30) & 1, insn >> 31
-    small = np.array([0] + [inv(i) for i in range(1, 32)], dtype=np.int64)
-    for k, (lo, hi, dl, dh, val) in enumerate((("rs1_lo", "rs1_hi", "dl0", "dh0", "rs1"), ("rs2_lo", "rs2_hi", "dl1", "dh1", "rs2"))):
-        m[COL[lo], L] = r[:, F[val]] & 0xFFFF          # every cycle reads two registers, x0 included
-        m[COL[hi], L] = r[:, F[val]] >> 16
-        diff = 5 * cyc + STAMP[k] - r[:, F["prev"] + k] - 1
-        assert (diff >= 0).all() and (diff < 1 << 24).all()
-        m[COL[dl], L], m[COL[dh], L] = diff & 0xFFFF, diff >> 16
-    m[COL["zrd"]] = 1
-    m[COL["zrd"], L] = ((insn >> 7) & 31) == 0
-    m[COL["inv_rd"], L] = small[(insn >> 7) & 31]
-    wr = r[:, F["rd"]] != 0
-    m[COL["act2"], L] = wr
-    m[COL["old_lo"], L] = np.where(wr, r[:, F["rd_before"]] & 0xFFFF, 0)
-    m[COL["old_hi"], L] = np.where(wr, r[:, F["rd_before"]] >> 16, 0)
-    diff = np.where(wr, 5 * cyc + STAMP[2] - r[:, F["prev"] + 2] - 1, 0)
-    m[COL["dl2"], L], m[COL["dh2"], L] = diff & 0xFFFF, diff >> 16
-    mem = r[:, F["mem_kind"]] != 0
-    m[COL["mem_wr"], L] = r[:, F["mem_kind"]] == r0.MEM_WRITE
-    m[COL["addr3"], L] = np.where(mem, r[:, F["mem_addr"]] >> 2, 0)
-    for name, f in (("before", "mem_before"), ("after", "mem_after")):
-        m[COL[name + "_lo"], L] = np.where(mem, r[:, F[f]] & 0xFFFF, 0)
-        m[COL[name + "_hi"], L] = np.where(mem, r[:, F[f]] >> 16, 0)
-    m[COL["p3"], L] = np.where(mem, r[:, F["prev"] + 3], 0)
-    diff = 5 * cyc + STAMP[4] - r[:, F["prev"] + 4] - 1
-    m[COL["dl4"], L], m[COL["dh4"], L] = diff & 0xFFFF, diff >> 16
-    if nb:
-        bb = bounds.astype(np.int64)
-        B = slice(nr, nr + nb)
-        m[COL["bnd"], B] = 1
-        m[COL["addr3"], B] = bb[:, 0]
-        m[COL["after_lo"], B], m[COL["after_hi"], B] = bb[:, 1] & 0xFFFF, bb[:, 1] >> 16     # written: the value found, timestamp 0
-        m[COL["before_lo"], B], m[COL["before_hi"], B] = bb[:, 2] & 0xFFFF, bb[:, 2] >> 16   # read: the value left, at its last timestamp
-        m[COL["p3"], B] = bb[:, 3]
-        assert (bb[:, 0] < (1 << 28) + 32).all()
-        top = bb[:, 0] >> 28                                                                 # the address: two limbs and the register bit
-        low = bb[:, 0] - (top << 28)
-        m[COL["top"], B] = top
-        m[COL["dl0"], B], m[COL["dl1"], B] = low & 0xFFFF, low >> 16
-        m[COL["dh0"], B] = np.where(top == 1, 8 * (low & 0xFFFF), 0)
-        m[COL["dl2"], B] = number - bb[:, 4] - 1                                             # the segment that held the address before: an earlier one
-        if closing:
-            m[COL["old_lo"], B], m[COL["old_hi"], B] = bb[:, 5] & 0xFFFF, bb[:, 5] >> 16     # the address's initial value
-            m[COL["fimg"], B] = bb[:, 6] & 1
-    return m
-
-
-def montgomery(m):
-    return ((m.astype(object) << 32) % P).astype(np.uint32)
-
-
-R_INV = pow(1 << 32, P - 2, P)
-
-
-def canonical(words, po2):
-    """witness words (Montgomery form, column-major) -> [column, row] canonical integers"""
-    return (words.reshape(len(TRACE_COLUMNS), 1 << po2).astype(np.int64) * R_INV) % P
 
 
 def broken(vm, k, po2=PO2, edits=(), session_extra=None):
@@ -754,9 +663,8 @@ def test_the_device_expands_and_proves_an_execution_trace_word_for_word_like_the
     assert np.array_equal(dglob, glob)
     got = dev.to_host()
     assert np.array_equal(got, data)
-    if po2 <= 16:
-        primary = [COL[c_] for c_ in PRIMARY]
-        assert np.array_equal(got.reshape(r0.TRACE_COLUMNS, -1)[primary], montgomery(expand(rows, bounds, po2))[primary])
+    primary = [COL[c_] for c_ in PRIMARY]
+    assert np.array_equal(got.reshape(r0.TRACE_COLUMNS, -1)[primary], montgomery(expand(rows, bounds, po2)[primary]))
     ocode, _, _ = c.witgen(po2, 0)
     assert np.array_equal(ocode, code.to_host())
     rng = np.random.default_rng(po2)
