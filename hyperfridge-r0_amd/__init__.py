@@ -1311,6 +1311,12 @@ class Hal:
         _check(lib().r0h_logup_totals(self.ctx, circuit.handle, po2, code.handle, data.handle, g.ctypes.data_as(_vp)))
         return g
 
+    def logup_multiplicities(self, circuit, po2, data, glob):
+        """fill the lookup tables' multiplicity columns of the DATA group `data` (Buf) from the lookups its rows make
+        (r0h_logup_multiplicities)"""
+        g = np.ascontiguousarray(glob if len(glob) else [0], dtype=np.uint32)
+        _check(lib().r0h_logup_multiplicities(self.ctx, circuit.handle, po2, data.handle, g.ctypes.data_as(_vp)))
+
     def prefix_sums(self, io, n):
         _check(lib().r0h_prefix_sums(self.ctx, io.handle, n))
 

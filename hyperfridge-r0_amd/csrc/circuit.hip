@@ -105,7 +105,11 @@ const char* parse_blob(r0h_circuit* c, const uint32_t* w, size_t n_words) {
         uint32_t n_acc = 0, n_tab = 0;
         R0H_REQUIRE(word(&n_acc) && word(&n_tab) && n_acc >= 1 && n_acc <= 64 && n_tab <= 8, "circuit blob: LOGUP header");
         c->logup.tables.resize(n_tab);
-        for (LogupTable& t : c->logup.tables) R0H_REQUIRE(word(&t.data_col) && word(&t.kind) && (t.kind == R0H_TABLE_R16 || t.kind == R0H_TABLE_AND), "circuit blob: LOGUP table");
+        for (uint32_t k = 0; k < n_tab; k++) {
+          LogupTable& t = c->logup.tables[k];
+          R0H_REQUIRE(word(&t.data_col) && word(&t.kind) && (t.kind == R0H_TABLE_R16 || t.kind == R0H_TABLE_AND), "circuit blob: LOGUP table");
+          R0H_REQUIRE(t.kind == k + 1, "circuit blob: LOGUP table %u is not of kind %u", k, k + 1);
+        }
         c->logup.accs.resize(n_acc);
         bool chain_over = false;
         for (LogupAcc& a : c->logup.accs) {
@@ -119,7 +123,14 @@ const char* parse_blob(r0h_circuit* c, const uint32_t* w, size_t n_words) {
             R0H_REQUIRE(word(&f.table) && f.table <= 2 && form(&f.num) && word(&np) && np >= 1 && np <= 8, "circuit blob: LOGUP fraction");
             f.parts.resize(np);
             for (LogupPart& q : f.parts) R0H_REQUIRE(word(&q.ch_kind) && q.ch_kind <= 2 && word(&q.ch_idx) && form(&q.lf), "circuit blob: LOGUP part");
-            if (f.table) R0H_REQUIRE(np == 2 && f.parts[1].ch_kind == 0, "circuit blob: a lookup's value is its second part");
+            if (f.table) {
+              R0H_REQUIRE(np == 2 && f.parts[1].ch_kind == 0, "circuit blob: a lookup's value is its second part");
+              R0H_REQUIRE(f.table <= n_tab, "circuit blob: a lookup names table %u of %u", f.table, n_tab);
+              R0H_REQUIRE(a.final_global == 0xffffffffu, "circuit blob: a lookup in an accumulator with a public total can never balance");
+              for (const Lf* lf : {&f.num, &f.parts[1].lf})
+                for (const LfTerm& t : lf->terms)
+                  R0H_REQUIRE(!t.col || ((t.col - 1) >> 28) == R0H_GROUP_DATA, "circuit blob: a lookup's numerator and value read DATA columns, public inputs and constants only");
+            }
           }
         }
         R0H_REQUIRE(at == len, "circuit blob: LOGUP length mismatch");

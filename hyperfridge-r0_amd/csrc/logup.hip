@@ -5,8 +5,8 @@
 //
 // Three device steps, all streams over columns (consecutive lanes own consecutive rows, every column access is a 256-byte line):
 //   1. multiplicities: every lookup's value is binned -- per workgroup in LDS for the small (hot) values, with device atomics for the
-//      rest; zero, by far the most frequent value (idle slots), is counted by subtraction -- and the counts become the table's
-//      multiplicity column in DATA (before DATA is committed);
+//      rest; zero, by far the most frequent value (idle slots), is counted by subtraction from the slots that are not gated off (a
+//      numerator of 0) -- and the counts become the table's multiplicity column in DATA (before DATA is committed);
 //   2. terms: one thread per row evaluates the row's fractions accumulator by accumulator, sum_f n_f / d_f = N / D with ONE
 //      extension-field inversion per accumulator, and leaves the running sum WITHIN the row in the ACCUM columns;
 //   3. the row totals are scanned (r0h_prefix_sums) and added back: the chain runs through the rows.
@@ -119,13 +119,15 @@ __device__ __forceinline__ uint32_t eval_form(const uint32_t* __restrict__ tape,
 
 constexpr uint32_t HOT = 4096;  // values below this are binned in LDS per workgroup
 
-// one thread per row: every lookup's value goes into its table's histogram (zero is not counted: it is the remainder)
-__global__ __launch_bounds__(256) void logup_count_kernel(uint32_t* __restrict__ hist /* [n_tables][65536] */, const uint32_t* __restrict__ tape, uint32_t tape_end,
-                                                          const uint32_t* const* __restrict__ cols, uint32_t n, uint32_t n_tables) {
+// one thread per row: every lookup's value goes into its table's histogram.  Zero is not counted (it is the remainder); entry 0 counts
+// the slots gated off instead.  A numerator other than 0 or 1 sets bit 0 of *err, a value outside its table (numerator 1) bit 1.
+__global__ __launch_bounds__(256) void logup_count_kernel(uint32_t* __restrict__ hist /* [n_tables][65536] */, uint32_t* __restrict__ err, const uint32_t* __restrict__ tape,
+                                                          uint32_t tape_end, const uint32_t* const* __restrict__ cols, uint32_t n, uint32_t n_tables) {
   __shared__ uint32_t hot[2][HOT];
   for (uint32_t i = threadIdx.x; i < 2 * HOT; i += 256) (&hot[0][0])[i] = 0;
   __syncthreads();
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  uint32_t gated[2] = {0, 0};
   if (r < n) {
     uint32_t at = 0;
     while (at < tape_end) {  // fractions in tape order; an accumulator boundary has no marker of its own (four fractions each)
@@ -138,13 +140,19 @@ __global__ __launch_bounds__(256) void logup_count_kernel(uint32_t* __restrict__
         const uint32_t v = eval_form(tape, at, cols, r);
         if (q == 1) value = v;
       }
-      if (!table || table > n_tables || num != ONE) continue;
+      if (!table || table > n_tables) continue;
+      if (num != ONE) {
+        if (num) atomicOr(err, 1u);
+        else gated[table - 1]++;
+        continue;
+      }
       uint32_t v = dec(neg(value));
-      if (table == R0H_TABLE_AND) {
+      if (table == R0H_TABLE_AND) {  // (table k is of kind k + 1: the parser sees to it)
         v -= R0H_TAG_AND;
-        if (v >> 24 || ((v & 255u) & ((v >> 8) & 255u)) != v >> 16) continue;  // not an entry of the table: the sum will not close
+        if (v >> 24 || ((v & 255u) & ((v >> 8) & 255u)) != v >> 16) { atomicOr(err, 2u); continue; }
         v &= 0xffffu;
       } else if (v >> 16) {
+        atomicOr(err, 2u);
         continue;
       }
       if (!v) continue;
@@ -152,20 +160,22 @@ __global__ __launch_bounds__(256) void logup_count_kernel(uint32_t* __restrict__
       else atomicAdd(&hist[(size_t)(table - 1) * 65536 + v], 1u);
     }
   }
+  if (gated[0]) atomicAdd(&hot[0][0], gated[0]);
+  if (gated[1]) atomicAdd(&hot[1][0], gated[1]);
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < 2 * HOT; i += 256) {
     const uint32_t cnt = (&hot[0][0])[i];
     if (cnt) atomicAdd(&hist[(size_t)(i / HOT) * 65536 + (i % HOT)], cnt);
   }
 }
-// hist -> multiplicity column: entry 0 takes what the other entries leave of `total` lookups
+// hist -> multiplicity column: entry 0 takes what the other entries and the gated-off slots (hist[0]) leave of `total` lookup slots
 __global__ void logup_mult_kernel(uint32_t* __restrict__ column, const uint32_t* __restrict__ hist, uint32_t total, uint32_t n) {
   __shared__ uint32_t part[256];
-  // every block recomputes the sum of the non-zero entries (65536 words: cheap) -- only block 0 needs it
+  // only block 0 needs the sum of the histogram (65536 words: cheap)
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   if (blockIdx.x == 0) {
     uint32_t s = 0;
-    for (uint32_t i = threadIdx.x; i < 65536u; i += 256) s += i ? hist[i] : 0u;
+    for (uint32_t i = threadIdx.x; i < 65536u; i += 256) s += hist[i];
     part[threadIdx.x] = s;
     __syncthreads();
     for (uint32_t k = 128; k; k >>= 1) {
@@ -311,25 +321,31 @@ const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_
   R0H_TRY(build_tape(c, po2, nullptr, data, global ? global : dummy_global.data(), dummy_mix.data(), &t, true));  // the lookups alone (they read DATA only)
   DeviceTape d;
   R0H_TRY(upload_tape(ctx, t, &d));
-  std::vector<uint64_t> lookups(n_tables, 0);
+  std::vector<uint64_t> slots(n_tables, 0);  // lookup slots of each table: the chain links' lookups times the rows (only links look up)
   for (uint32_t j = 0; j < c->logup.n_chain; j++)
     for (const LogupFraction& f : c->logup.accs[j].fr)
-      if (f.table && f.table <= n_tables) lookups[f.table - 1]++;
-  r0h_buf* hist = nullptr;
-  R0H_TRY(buf_alloc_pooled(ctx, (size_t)n_tables * 65536 * 4, &hist));
+      if (f.table && f.table <= n_tables) slots[f.table - 1] += n;
+  for (uint32_t k = 0; k < n_tables; k++)
+    R0H_REQUIRE(slots[k] <= P - 1, "r0h_logup_multiplicities: table %u has %llu lookup slots at 2^%u rows: more than p - 1", k, (unsigned long long)slots[k], po2);
+  r0h_buf* hist = nullptr;  // [n_tables][65536] counts, then the error word
+  const size_t hist_words = (size_t)n_tables * 65536;
+  R0H_TRY(buf_alloc_pooled(ctx, hist_words * 4 + 16, &hist));
   struct Free { r0h_buf* b; ~Free() { r0h_buf_free(b); } } guard{hist};
-  R0H_TRY_HIP(hipMemsetAsync(hist->ptr, 0, (size_t)n_tables * 65536 * 4, ctx->stream));
+  R0H_TRY_HIP(hipMemsetAsync(hist->ptr, 0, hist_words * 4 + 16, ctx->stream));
   KScope ks(ctx, "logup_multiplicities", (double)t.cols.size() * n * 4);
-  hipLaunchKernelGGL(logup_count_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(hist), d.words, (uint32_t)t.words.size(), d.cols, n, n_tables);
+  hipLaunchKernelGGL(logup_count_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(hist), u32(hist) + hist_words, d.words, (uint32_t)t.words.size(), d.cols, n, n_tables);
   R0H_TRY(launch_check("logup_count_kernel"));
   for (uint32_t k = 0; k < n_tables; k++) {
     const LogupTable& tb = c->logup.tables[k];
-    R0H_REQUIRE(tb.kind == k + 1, "r0h_logup_multiplicities: table %u is not of kind %u", k, k + 1);
     hipLaunchKernelGGL(logup_mult_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(data) + ((size_t)tb.data_col << po2), u32(hist) + (size_t)k * 65536,
-                       (uint32_t)(lookups[k] * n), n);
+                       (uint32_t)slots[k], n);
     R0H_TRY(launch_check("logup_mult_kernel"));
   }
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  uint32_t err = 0;
+  R0H_TRY(r0h_buf_d2h(ctx, hist, hist_words * 4, &err, 4));
+  R0H_REQUIRE(!(err & 1u), "r0h_logup_multiplicities: a lookup's numerator is neither 0 nor 1");
+  R0H_REQUIRE(!(err & 2u), "r0h_logup_multiplicities: a row whose numerator is 1 looks up a value that is not in its table");
   return nullptr;
   R0H_GUARD_END
 }

@@ -21,29 +21,31 @@ const char* r0h_logup_multiplicities_host(const uint32_t* blob, size_t blob_word
   R0H_REQUIRE(po2 >= 16 && po2 <= R0H_MAX_PO2, "r0h_logup_multiplicities_host: the tables have 2^16 rows: po2 %u outside [16, %u]", po2, (unsigned)R0H_MAX_PO2);
   const size_t n = (size_t)1 << po2;
   std::vector<std::vector<uint32_t>> hist(c.logup.tables.size(), std::vector<uint32_t>(65536, 0));
-  auto form = [&](const Lf& lf, size_t r) {
+  std::vector<uint64_t> slots(c.logup.tables.size(), 0);
+  for (uint32_t j = 0; j < c.logup.n_chain; j++)
+    for (const LogupFraction& f : c.logup.accs[j].fr)
+      if (f.table) slots[f.table - 1] += n;
+  for (size_t k = 0; k < slots.size(); k++)
+    R0H_REQUIRE(slots[k] <= P - 1, "r0h_logup_multiplicities_host: table %zu has %llu lookup slots at 2^%u rows: more than p - 1", k, (unsigned long long)slots[k], po2);
+  auto form = [&](const Lf& lf, size_t r) {  // a lookup's forms read DATA columns, public inputs and constants (the parser sees to it)
     uint32_t acc = 0;
     for (const LfTerm& t : lf.terms) {
       uint32_t v = enc(t.coef);
       if (t.global) v = mul(v, global ? global[t.global - 1] : 0u);
-      if (t.col) {
-        const uint32_t ref = t.col - 1;
-        if ((ref >> 28) != R0H_GROUP_DATA) return 0xffffffffu;  // a lookup's value reads DATA only
-        v = mul(v, data[(size_t)(ref & 0xfffffu) * n + r]);
-      }
+      if (t.col) v = mul(v, data[(size_t)((t.col - 1) & 0xfffffu) * n + r]);
       acc = add(acc, v);
     }
     return acc;
   };
   for (uint32_t j = 0; j < c.logup.n_chain; j++)
     for (const LogupFraction& f : c.logup.accs[j].fr) {
-      if (!f.table || f.table > hist.size()) continue;
+      if (!f.table) continue;
       for (size_t r = 0; r < n; r++) {
-        if (form(f.num, r) != ONE) continue;
-        const uint32_t raw = form(f.parts[1].lf, r);
-        R0H_REQUIRE(raw != 0xffffffffu, "r0h_logup_multiplicities_host: a lookup's value reads another group than DATA");
-        uint32_t v = dec(neg(raw));
-        if (f.table == R0H_TABLE_AND) {
+        const uint32_t num = form(f.num, r);
+        R0H_REQUIRE(num == 0 || num == ONE, "r0h_logup_multiplicities_host: row %zu: a lookup's numerator is neither 0 nor 1", r);
+        if (num != ONE) continue;
+        uint32_t v = dec(neg(form(f.parts[1].lf, r)));
+        if (c.logup.tables[f.table - 1].kind == R0H_TABLE_AND) {
           v -= R0H_TAG_AND;
           R0H_REQUIRE(!(v >> 24) && ((v & 255u) & ((v >> 8) & 255u)) == v >> 16, "r0h_logup_multiplicities_host: row %zu looks up a value that is not in the byte-AND table", r);
           v &= 0xffffu;

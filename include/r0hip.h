@@ -570,7 +570,10 @@ const char* r0h_trace_witgen(r0h_ctx* ctx, const r0h_preflight_row* rows, size_t
  * sums in ACCUM.  Multiplicities: the table columns of DATA are filled from the lookups the rows make -- BEFORE the DATA group is
  * committed (r0h_trace_witgen and r0h_vm_trace_witness leave them zero).  Totals: the accumulators whose challenges are public inputs
  * (the trace circuit's session sum) are summed over the rows and written into global_io where the circuit reads them -- once those
- * challenges are known, before r0h_proof_late.  r0h_accum_public is r0h_accum for circuits whose accumulation reads public inputs. */
+ * challenges are known, before r0h_proof_late.  r0h_accum_public is r0h_accum for circuits whose accumulation reads public inputs.
+ * Both multiplicity functions keep the contract of include/r0hip_circuit.h (LOGUP): entry v of a table counts the rows whose lookup
+ * numerator is 1 and whose value is v; a numerator other than 0 or 1, a value outside its table on such a row, or more than p - 1
+ * lookup slots of one table is an error. */
 const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* data, const uint32_t* global);
 const char* r0h_logup_multiplicities_host(const uint32_t* blob, size_t blob_words, uint32_t po2, uint32_t* data, const uint32_t* global);
 const char* r0h_logup_totals(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io);

@@ -34,14 +34,20 @@
  *                (the trace circuit's session-wide challenge and the segment's sum under it)
  *   LOGUP  (10): [instead of ACCUM: a log-derivative argument -- lookups, memory tuples, session tuples] n_acc, n_tables, then
  *                (DATA column, kind) per looked-up table (the column receives the multiplicities; kind 1 = range-16, 2 = byte-AND),
- *                then per accumulator: n_fractions (<= 4), final (0xffffffff: a link of the chain; else the index of the first of
+ *                then per accumulator: n_fractions (4), final (0xffffffff: a link of the chain; else the index of the first of
  *                the four public inputs its total is), and per fraction: table (0 none / 1 / 2: a lookup into that table, whose
  *                value is minus the form of part 1 [minus 2^24 for kind 2]), the numerator (a linear form), n_parts, and per
  *                part (challenge kind 0 one / 1 mix element / 2 four public inputs, its index, a linear form): the denominator is
  *                the sum over parts of challenge x form.  A linear form is n_terms x (canonical coefficient, public input + 1 or
  *                0, column ref + 1 or 0 for the constant one), ref = group << 28 | column.  Extension column j (ACCUM columns
  *                4j..4j+3): chain links run ONE sum through the row's accumulators and on through the rows, wrapping around the
- *                end of the trace (so its total is zero); an accumulator with a public total runs alone and wraps with it
+ *                end of the trace (so its total is zero); an accumulator with a public total runs alone and wraps with it.
+ *                The contract both parsers and every implementation of the argument keep: an accumulator has exactly four
+ *                fractions; table k has kind k + 1, and a fraction's table is at most n_tables; lookups (fractions with a table)
+ *                appear in chain links only; a lookup's numerator and value read DATA columns, public inputs and constants only.
+ *                The multiplicity of v counts the rows whose lookup numerator is 1 and whose value is v (a numerator of 0 gates
+ *                the lookup off, whatever its value); a numerator other than 0 or 1, a value outside its table on a row whose
+ *                numerator is 1, and more than p - 1 lookup slots (lookups x rows) of one table are errors
  *   PERIODIC (11): period, n_cols, then n_cols x period canonical values: what CODE columns of kind 6 repeat
  *   SPONGE (12): [the in-circuit Poseidon2 sponge of the recursion circuit: tools/sponge_component.py] first CODE column (28 columns: rc[24],
  *                sel_mix, sel_full, sel_part, sel_last), first DATA column (65 columns: st[24], aux[24], in[16], act), first of the 8 public

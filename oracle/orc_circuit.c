@@ -142,7 +142,7 @@ orc_circuit_t* orc_circuit_parse(const uint32_t* w, size_t n_words) {
 #define FORM(lf) do { WORD((lf).n); if ((lf).n > 64 || at + 3 * (size_t)(lf).n > len) goto bad; (lf).t = (const orc_lf_term_t*)(q + at); at += 3 * (size_t)(lf).n; } while (0)
         WORD(c->n_logup); WORD(c->n_tables);
         if (c->n_logup < 1 || c->n_logup > 64 || c->n_tables > 8) goto bad;
-        for (uint32_t k = 0; k < c->n_tables; k++) { WORD(c->table_col[k]); WORD(c->table_kind[k]); }
+        for (uint32_t k = 0; k < c->n_tables; k++) { WORD(c->table_col[k]); WORD(c->table_kind[k]); if (c->table_kind[k] != k + 1) goto bad; }
         c->logup = (orc_logup_acc_t*)calloc(c->n_logup, sizeof(orc_logup_acc_t));
         int chain_over = 0;
         for (uint32_t j = 0; j < c->n_logup; j++) {
@@ -158,7 +158,14 @@ orc_circuit_t* orc_circuit_parse(const uint32_t* w, size_t n_words) {
             WORD(fr->n_parts);
             if (fr->table > 2 || fr->n_parts < 1 || fr->n_parts > 8) goto bad;
             for (uint32_t k = 0; k < fr->n_parts; k++) { WORD(fr->parts[k].ch_kind); WORD(fr->parts[k].ch_idx); FORM(fr->parts[k].lf); if (fr->parts[k].ch_kind > 2) goto bad; }
-            if (fr->table && (fr->n_parts != 2 || fr->parts[1].ch_kind != 0)) goto bad;
+            if (fr->table) {  /* a lookup: value in part 1, a table there is, in the chain, numerator and value read DATA / public inputs / constants */
+              if (fr->n_parts != 2 || fr->parts[1].ch_kind != 0 || fr->table > c->n_tables || a->final_global != 0xffffffffu) goto bad;
+              for (int k = 0; k < 2; k++) {
+                const orc_lf_t* lf = k ? &fr->parts[1].lf : &fr->num;
+                for (uint32_t t = 0; t < lf->n; t++)
+                  if (lf->t[t].col && ((lf->t[t].col - 1) >> 28) != ORC_GROUP_DATA) goto bad;
+              }
+            }
           }
         }
         if (at != len) goto bad;
@@ -352,19 +359,28 @@ static fp4_t logup_term(const orc_logup_acc_t* a, const uint32_t* code, const ui
   return fp4_mul(top, fp4_inv(fp4_mul(d01, d23)));
 }
 
-/* the multiplicity columns of DATA from the lookups the rows make (before DATA is committed); -1 if a value is not in its table */
+/* the multiplicity columns of DATA from the lookups the rows make (before DATA is committed): entry v of table k counts the rows
+   whose numerator is 1 and whose value is v.  -1 if a numerator is neither 0 nor 1, if a value on a row whose numerator is 1 is not in
+   its table, or if a table has more than p - 1 lookup slots (include/r0hip_circuit.h) */
 int orc_logup_multiplicities(const orc_circuit_t* c, uint32_t po2, uint32_t* data, const uint32_t* global) {
   size_t n = (size_t)1 << po2;
   if (!c->n_tables) return 0;
   if (po2 < 16) return -1;
+  uint64_t slots[8] = {0};
+  for (uint32_t j = 0; j < c->n_chain; j++)
+    for (int f = 0; f < 4; f++)
+      if (c->logup[j].fr[f].table) slots[c->logup[j].fr[f].table - 1] += n;
+  for (uint32_t k = 0; k < c->n_tables; k++)
+    if (slots[k] > ORC_P - 1) return -1;
   uint32_t* hist = (uint32_t*)calloc((size_t)c->n_tables * 65536, 4);
   int bad = 0;
   for (uint32_t j = 0; j < c->n_chain; j++)
     for (int f = 0; f < 4; f++) {
       const orc_logup_fraction_t* fr = &c->logup[j].fr[f];
-      if (!fr->table || fr->table > c->n_tables) continue;
+      if (!fr->table) continue;
       for (size_t r = 0; r < n; r++) {
-        if (lf_eval(&fr->num, data, data, global, n, r) != ORC_ONE) continue;
+        fp_t num = lf_eval(&fr->num, data, data, global, n, r);  /* (a lookup reads no CODE column: the parser sees to it) */
+        if (num != ORC_ONE) { if (num != 0) bad = 1; continue; }
         uint32_t v = fp_dec(fp_sub(0, lf_eval(&fr->parts[1].lf, data, data, global, n, r)));
         if (fr->table == 2) {
           v -= TAG_AND;
