@@ -691,32 +691,38 @@ const char* r0h_circuit_emit_hip(const uint32_t* blob, size_t n_words, char** so
   R0H_GUARD_END
 }
 
+// how a circuit goes, also on every early path out of r0h_circuit_load: its module (if one was loaded) is unloaded with it
+struct CircuitUnload {
+  void operator()(r0h_circuit* circuit) const {
+    if (circuit->module) (void)hipModuleUnload(circuit->module);
+    delete circuit;
+  }
+};
+
 const char* r0h_circuit_load(r0h_ctx* ctx, const uint32_t* blob, size_t n_words, const char* code_object_path, r0h_circuit** out) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && blob && out, "r0h_circuit_load: NULL argument");
-  r0h_circuit* c = new r0h_circuit();
+  std::unique_ptr<r0h_circuit, CircuitUnload> c(new r0h_circuit());
   c->ctx = ctx;
-  const char* err = parse_blob(c, blob, n_words);
-  if (err) { delete c; return err; }
-  make_plan(c);
+  R0H_TRY(parse_blob(c.get(), blob, n_words));
+  make_plan(c.get());
   R0H_TRY_HIP(hipSetDevice(ctx->device));
   std::vector<char> code;
   if (code_object_path) {
     FILE* f = fopen(code_object_path, "rb");
-    if (!f) { delete c; return make_error("r0h_circuit_load: cannot open code object %s", code_object_path); }
+    R0H_REQUIRE(f, "r0h_circuit_load: cannot open code object %s", code_object_path);
     fseek(f, 0, SEEK_END);
     long sz = ftell(f);
     fseek(f, 0, SEEK_SET);
     code.resize(sz > 0 ? (size_t)sz : 0);
     size_t got = fread(code.data(), 1, code.size(), f);
     fclose(f);
-    if (got != code.size() || code.empty()) { delete c; return make_error("r0h_circuit_load: short read of %s", code_object_path); }
+    R0H_REQUIRE(got == code.size() && !code.empty(), "r0h_circuit_load: short read of %s", code_object_path);
   } else {
-    err = compile_in_process(emit_source(c), code);
-    if (err) { delete c; return err; }
+    R0H_TRY(compile_in_process(emit_source(c.get()), code));
   }
   hipError_t e = hipModuleLoadData(&c->module, code.data());
-  if (e != hipSuccess) { delete c; return make_error("r0h_circuit_load: hipModuleLoadData: %s", hipGetErrorString(e)); }
+  R0H_REQUIRE(e == hipSuccess, "r0h_circuit_load: hipModuleLoadData: %s", hipGetErrorString(e));
   for (size_t k = 0;; k++) {  // the code object decides into how many kernels the program was cut
     char name[64];
     snprintf(name, sizeof name, "eval_check_%zu", k);
@@ -725,13 +731,9 @@ const char* r0h_circuit_load(r0h_ctx* ctx, const uint32_t* blob, size_t n_words,
     c->kernels.push_back(fn);
   }
   (void)hipGetLastError();
-  if (c->kernels.empty() && !c->plan.terms.empty()) {
-    hipModuleUnload(c->module);
-    delete c;
-    return make_error("r0h_circuit_load: the code object has no eval_check_0 (built from another source?)");
-  }
+  R0H_REQUIRE(!c->kernels.empty() || c->plan.terms.empty(), "r0h_circuit_load: the code object has no eval_check_0 (built from another source?)");
   ctx_retain(ctx);
-  *out = c;
+  *out = c.release();
   return nullptr;
   R0H_GUARD_END
 }
@@ -741,8 +743,7 @@ const char* r0h_circuit_free(r0h_circuit* c) {
   r0h_ctx* ctx = c->ctx;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  if (c->module) (void)hipModuleUnload(c->module);
-  delete c;
+  CircuitUnload()(c);
   ctx_release(ctx);
   return nullptr;
 }
@@ -819,8 +820,7 @@ static const char* witgen_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2,
     hipLaunchKernelGGL(witgen_derived_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(data) + ((size_t)k << po2), col(d.a), col(d.b),
                        col(rc), col(d.e), back(d.a), back(d.b), back(rc), back(d.e), d.kind, po2);
   }
-  hipError_t e = hipGetLastError();
-  R0H_REQUIRE(e == hipSuccess, "r0h_witgen: launch failed: %s", hipGetErrorString(e));
+  R0H_TRY(launch_ok("r0h_witgen"));
   if (global_out) {
     for (uint32_t k = 0; k < c->n_global; k++)
       R0H_TRY_HIP(hipMemcpyAsync(global_out + k, u32(data) + ((size_t)c->global_cols[k] << po2), 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -850,8 +850,8 @@ const char* r0h_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0
               "r0h_accum: buffers too small for 2^%u rows", po2);
   for (uint32_t i = 0; i < c->n_mix; i++) R0H_REQUIRE(mix[i] < P, "r0h_accum: mix[%u] not canonical", i);
   R0H_REQUIRE(c->logup.accs.empty(), "r0h_accum: this circuit accumulates a log-derivative argument that reads public inputs: use r0h_accum_public");
-  r0h_buf* term = nullptr;
-  R0H_TRY(buf_alloc_pooled(ctx, (size_t)n * 16, &term));
+  DevBuf term;
+  R0H_TRY(term.alloc(ctx, (size_t)n * 16));
   for (uint32_t j = 0; j < c->acc_fp.size(); j++) {
     const AccFp& a = c->acc_fp[j];
     FpCols cols;
@@ -859,23 +859,18 @@ const char* r0h_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0
     for (uint32_t f = 0; f < 3; f++)
       for (uint32_t q = 0; q < 4; q++) cols.col[f][q] = u32(data) + ((size_t)a.col[f][q] << po2);
     auto m = [&](uint32_t k) { return Fp4{{mix[4 * k], mix[4 * k + 1], mix[4 * k + 2], mix[4 * k + 3]}}; };
-    hipLaunchKernelGGL(accum_fp_term_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(term), cols, m(0), m(1), m(2), m(3));
-    const char* err = r0h_prefix_products(ctx, term, n);
-    if (err) { r0h_buf_free(term); return err; }
-    hipLaunchKernelGGL(accum_unpack_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(accum) + ((size_t)(4 * j) << po2), u32(term), po2);
+    hipLaunchKernelGGL(accum_fp_term_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(term.get()), cols, m(0), m(1), m(2), m(3));
+    R0H_TRY(r0h_prefix_products(ctx, term.get(), n));
+    hipLaunchKernelGGL(accum_unpack_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(accum) + ((size_t)(4 * j) << po2), u32(term.get()), po2);
   }
   for (uint32_t j = 0; j < c->acc_cols.size(); j++) {
     Fp4 m0{{mix[8 * j], mix[8 * j + 1], mix[8 * j + 2], mix[8 * j + 3]}}, m1{{mix[8 * j + 4], mix[8 * j + 5], mix[8 * j + 6], mix[8 * j + 7]}};
-    hipLaunchKernelGGL(accum_term_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(term), u32(data) + ((size_t)c->acc_cols[j].a << po2),
+    hipLaunchKernelGGL(accum_term_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(term.get()), u32(data) + ((size_t)c->acc_cols[j].a << po2),
                        u32(data) + ((size_t)c->acc_cols[j].b << po2), m0, m1);
-    const char* err = r0h_prefix_products(ctx, term, n);
-    if (err) { r0h_buf_free(term); return err; }
-    hipLaunchKernelGGL(accum_unpack_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(accum) + ((size_t)(4 * j) << po2), u32(term), po2);
+    R0H_TRY(r0h_prefix_products(ctx, term.get(), n));
+    hipLaunchKernelGGL(accum_unpack_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(accum) + ((size_t)(4 * j) << po2), u32(term.get()), po2);
   }
-  hipError_t e = hipGetLastError();
-  R0H_TRY(r0h_buf_free(term));
-  R0H_REQUIRE(e == hipSuccess, "r0h_accum: launch failed: %s", hipGetErrorString(e));
-  return nullptr;
+  return launch_ok("r0h_accum");
   R0H_GUARD_END
 }
 
@@ -909,13 +904,12 @@ const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, con
   }
   // the parameter block comes from the calling context's pool (stream-ordered reuse), not from the circuit: one loaded circuit
   // then serves every context of its device at once (r0h_prove_elf's prover lanes share it)
-  r0h_buf* pbuf = nullptr;
-  R0H_TRY(buf_alloc_pooled(ctx, params.size() * 4, &pbuf));
-  struct Free { r0h_buf* b; ~Free() { r0h_buf_free(b); } } pguard{pbuf};
+  DevBuf pbuf;
+  R0H_TRY(pbuf.alloc(ctx, params.size() * 4));
   R0H_TRY(stage_h2d(ctx, pbuf->ptr, params.data(), params.size() * 4));
   uint32_t* d_check = u32(check);
   const uint32_t *g0 = u32(g[0]), *g1 = u32(g[1]), *g2 = u32(g[2]);
-  const uint32_t *d_glob = u32(pbuf), *d_mix = d_glob + c->n_global, *d_pow = d_mix + c->n_mix, *d_van = d_pow + 4 * (size_t)c->plan.n_pow;
+  const uint32_t *d_glob = u32(pbuf.get()), *d_mix = d_glob + c->n_global, *d_pow = d_mix + c->n_mix, *d_van = d_pow + 4 * (size_t)c->plan.n_pow;
   double alg = (double)domain * 16;
   for (int k = 0; k < 3; k++) alg += (double)domain * c->group_size[k] * 4;
   KScope ks(ctx, "eval_check", alg);

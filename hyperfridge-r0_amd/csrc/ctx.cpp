@@ -4,6 +4,7 @@
 #include <stdarg.h>
 
 #include <exception>
+#include <stdexcept>
 
 #include "../../include/r0hip_poseidon2_consts.h"
 #include "internal.hpp"
@@ -211,6 +212,19 @@ const char* buf_alloc_pooled(r0h_ctx* ctx, size_t bytes, r0h_buf** out) {
   }
   ctx_retain(ctx);
   *out = b;
+  return nullptr;
+}
+
+r0h_buf buf_view(const r0h_buf* b, size_t offset_bytes, size_t bytes) {
+  if (offset_bytes > b->bytes || bytes > b->bytes - offset_bytes) throw std::out_of_range("buf_view: window outside its buffer");
+  r0h_buf v;
+  v.ctx = b->ctx; v.ptr = (char*)b->ptr + offset_bytes; v.bytes = bytes; v.owned = false;
+  return v;
+}
+
+const char* launch_ok(const char* what) {
+  hipError_t e = hipGetLastError();
+  R0H_REQUIRE(e == hipSuccess, "%s: launch failed: %s", what, hipGetErrorString(e));
   return nullptr;
 }
 

@@ -18,12 +18,6 @@ __device__ __forceinline__ Fp4 ld4(const uint32_t* p) {
 }
 __device__ __forceinline__ void st4(uint32_t* p, const Fp4& v) { *(uint4*)p = make_uint4(v.e[0], v.e[1], v.e[2], v.e[3]); }
 
-static const char* launch_ok(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return make_error("%s: launch failed: %s", what, hipGetErrorString(e));
-  return nullptr;
-}
-
 // ------------------------------------------------------------------ batch_evaluate_any
 // sum_i c[i] x^i = sum_hi B[hi] * (sum_lo c[hi*RL + lo] * A[lo]),  A[lo] = x^lo, B[hi] = x^(hi*RL).
 // A wave owns a row of RL coefficients: each lane keeps its 16 A-values in registers, multiplies base-field

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -157,6 +158,21 @@ const char* ensure_scratch(r0h_ctx* ctx, size_t bytes);
 const char* stage_h2d(r0h_ctx* ctx, void* dst_device, const void* src_host, size_t bytes);
 // device buffer from the context's pool: no hipMalloc / hipFree (and no implicit device sync) in steady state
 const char* buf_alloc_pooled(r0h_ctx* ctx, size_t bytes, r0h_buf** out);
+// Owner of one pooled buffer: back to its context's pool when the owner goes -- or at reset(), where the block has to be back
+// before what follows (the next allocation of that size reuses it in stream order); release() hands the pointer on.
+struct BufFree { void operator()(r0h_buf* b) const { r0h_buf_free(b); } };
+struct DevBuf : std::unique_ptr<r0h_buf, BufFree> {
+  const char* alloc(r0h_ctx* ctx, size_t bytes) {
+    r0h_buf* b = nullptr;
+    R0H_TRY(buf_alloc_pooled(ctx, bytes, &b));
+    reset(b);
+    return nullptr;
+  }
+};
+// bytes [offset_bytes, +bytes) of `b` as a buffer that owns nothing and is never freed; throws std::out_of_range outside `b`
+r0h_buf buf_view(const r0h_buf* b, size_t offset_bytes, size_t bytes);
+// after a kernel launch: the launch error, if any, as "<what>: launch failed: <hip text>"
+const char* launch_ok(const char* what);
 // inverse NTT with the coset shift f(x) -> f(3x) optionally fused into its last pass (sequencer path)
 const char* interpolate_ntt(r0h_ctx* ctx, r0h_buf* io, const r0h_buf* src, uint32_t count, uint32_t po2, bool zk_shift);  // src may be io
 // batch_evaluate_any over coefficients stored in natural or bit-reversed order (the sequencer keeps them bit-reversed)

@@ -87,15 +87,14 @@ const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, 
 }
 
 struct DeviceTape {
-  r0h_buf* buf = nullptr;
+  DevBuf buf;
   const uint32_t* words = nullptr;
   const uint32_t* const* cols = nullptr;
   const Fp4* ch = nullptr;
-  ~DeviceTape() { if (buf) r0h_buf_free(buf); }
 };
 const char* upload_tape(r0h_ctx* ctx, const Tape& t, DeviceTape* d) {
   const size_t w_bytes = (t.words.size() * 4 + 15) & ~(size_t)15, c_bytes = (t.cols.size() * sizeof(void*) + 15) & ~(size_t)15, h_bytes = t.ch.size() * 16;
-  R0H_TRY(buf_alloc_pooled(ctx, w_bytes + c_bytes + h_bytes, &d->buf));
+  R0H_TRY(d->buf.alloc(ctx, w_bytes + c_bytes + h_bytes));
   char* base = (char*)d->buf->ptr;
   R0H_TRY(stage_h2d(ctx, base, t.words.data(), t.words.size() * 4));
   R0H_TRY(stage_h2d(ctx, base + w_bytes, t.cols.data(), t.cols.size() * sizeof(void*)));
@@ -241,30 +240,21 @@ __global__ void logup_unpack_kernel(uint32_t* __restrict__ cols, const uint32_t*
 }
 }  // namespace
 
-static const char* launch_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  R0H_REQUIRE(e == hipSuccess, "%s: %s", what, hipGetErrorString(e));
-  return nullptr;
-}
-
 // standalone accumulators: terms -> running sums; totals_out (host, 4 words each) if wanted, ACCUM columns if `accum`
 static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const Tape& t, const DeviceTape& d, r0h_buf* accum, uint32_t* totals_out) {
   const uint32_t n = 1u << po2, n_chain = c->logup.n_chain, n_acc = (uint32_t)c->logup.accs.size(), n_own = n_acc - n_chain;
   if (!n_own) return nullptr;
-  r0h_buf* terms = nullptr;
-  R0H_TRY(buf_alloc_pooled(ctx, (size_t)n_own * n * 16, &terms));
-  struct Free { r0h_buf* b; ~Free() { r0h_buf_free(b); } } guard{terms};
-  hipLaunchKernelGGL(logup_term_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, accum ? u32(accum) : nullptr, (uint32_t*)nullptr, u32(terms),
+  DevBuf terms;
+  R0H_TRY(terms.alloc(ctx, (size_t)n_own * n * 16));
+  hipLaunchKernelGGL(logup_term_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, accum ? u32(accum) : nullptr, (uint32_t*)nullptr, u32(terms.get()),
                      d.words + t.acc_begin[n_chain], d.cols, d.ch, n_chain, n_acc, n_chain, po2);
-  R0H_TRY(launch_check("logup_term_kernel"));
+  R0H_TRY(launch_ok("logup_term_kernel"));
   for (uint32_t k = 0; k < n_own; k++) {
-    r0h_buf view = *terms;
-    view.ptr = (char*)terms->ptr + (size_t)k * n * 16;
-    view.bytes = (size_t)n * 16;
+    r0h_buf view = buf_view(terms.get(), (size_t)k * n * 16, (size_t)n * 16);
     R0H_TRY(r0h_prefix_sums(ctx, &view, n));
     if (accum) {
       hipLaunchKernelGGL(logup_unpack_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(accum) + ((size_t)(4 * (n_chain + k)) << po2), (const uint32_t*)view.ptr, po2);
-      R0H_TRY(launch_check("logup_unpack_kernel"));
+      R0H_TRY(launch_ok("logup_unpack_kernel"));
     }
     if (totals_out) R0H_TRY(r0h_buf_d2h(ctx, &view, (size_t)(n - 1) * 16, totals_out + 4 * k, 16));
   }
@@ -286,14 +276,13 @@ const char* logup_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const 
   DeviceTape d;
   R0H_TRY(upload_tape(ctx, t, &d));
   KScope ks(ctx, "logup_accum", ((double)t.cols.size() + 2.0 * c->group_size[R0H_GROUP_ACCUM]) * n * 4);
-  r0h_buf* totals = nullptr;
-  R0H_TRY(buf_alloc_pooled(ctx, (size_t)n * 16, &totals));
-  struct Free { r0h_buf* b; ~Free() { r0h_buf_free(b); } } guard{totals};
-  hipLaunchKernelGGL(logup_term_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(accum), u32(totals), (uint32_t*)nullptr, d.words, d.cols, d.ch, 0u, n_chain, n_chain, po2);
-  R0H_TRY(launch_check("logup_term_kernel"));
-  R0H_TRY(r0h_prefix_sums(ctx, totals, n));
-  hipLaunchKernelGGL(logup_chain_kernel, dim3((n + 255) / 256, 4 * n_chain), dim3(256), 0, ctx->stream, u32(accum), u32(totals), 4 * n_chain, po2);
-  R0H_TRY(launch_check("logup_chain_kernel"));
+  DevBuf totals;
+  R0H_TRY(totals.alloc(ctx, (size_t)n * 16));
+  hipLaunchKernelGGL(logup_term_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(accum), u32(totals.get()), (uint32_t*)nullptr, d.words, d.cols, d.ch, 0u, n_chain, n_chain, po2);
+  R0H_TRY(launch_ok("logup_term_kernel"));
+  R0H_TRY(r0h_prefix_sums(ctx, totals.get(), n));
+  hipLaunchKernelGGL(logup_chain_kernel, dim3((n + 255) / 256, 4 * n_chain), dim3(256), 0, ctx->stream, u32(accum), u32(totals.get()), 4 * n_chain, po2);
+  R0H_TRY(launch_ok("logup_chain_kernel"));
   R0H_TRY(own_accumulators(ctx, c, po2, t, d, accum, nullptr));
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the tape goes back to the pool
   return nullptr;
@@ -327,23 +316,22 @@ const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_
       if (f.table && f.table <= n_tables) slots[f.table - 1] += n;
   for (uint32_t k = 0; k < n_tables; k++)
     R0H_REQUIRE(slots[k] <= P - 1, "r0h_logup_multiplicities: table %u has %llu lookup slots at 2^%u rows: more than p - 1", k, (unsigned long long)slots[k], po2);
-  r0h_buf* hist = nullptr;  // [n_tables][65536] counts, then the error word
+  DevBuf hist;  // [n_tables][65536] counts, then the error word
   const size_t hist_words = (size_t)n_tables * 65536;
-  R0H_TRY(buf_alloc_pooled(ctx, hist_words * 4 + 16, &hist));
-  struct Free { r0h_buf* b; ~Free() { r0h_buf_free(b); } } guard{hist};
+  R0H_TRY(hist.alloc(ctx, hist_words * 4 + 16));
   R0H_TRY_HIP(hipMemsetAsync(hist->ptr, 0, hist_words * 4 + 16, ctx->stream));
   KScope ks(ctx, "logup_multiplicities", (double)t.cols.size() * n * 4);
-  hipLaunchKernelGGL(logup_count_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(hist), u32(hist) + hist_words, d.words, (uint32_t)t.words.size(), d.cols, n, n_tables);
-  R0H_TRY(launch_check("logup_count_kernel"));
+  hipLaunchKernelGGL(logup_count_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(hist.get()), u32(hist.get()) + hist_words, d.words, (uint32_t)t.words.size(), d.cols, n, n_tables);
+  R0H_TRY(launch_ok("logup_count_kernel"));
   for (uint32_t k = 0; k < n_tables; k++) {
     const LogupTable& tb = c->logup.tables[k];
-    hipLaunchKernelGGL(logup_mult_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(data) + ((size_t)tb.data_col << po2), u32(hist) + (size_t)k * 65536,
+    hipLaunchKernelGGL(logup_mult_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(data) + ((size_t)tb.data_col << po2), u32(hist.get()) + (size_t)k * 65536,
                        (uint32_t)slots[k], n);
-    R0H_TRY(launch_check("logup_mult_kernel"));
+    R0H_TRY(launch_ok("logup_mult_kernel"));
   }
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
   uint32_t err = 0;
-  R0H_TRY(r0h_buf_d2h(ctx, hist, hist_words * 4, &err, 4));
+  R0H_TRY(r0h_buf_d2h(ctx, hist.get(), hist_words * 4, &err, 4));
   R0H_REQUIRE(!(err & 1u), "r0h_logup_multiplicities: a lookup's numerator is neither 0 nor 1");
   R0H_REQUIRE(!(err & 2u), "r0h_logup_multiplicities: a row whose numerator is 1 looks up a value that is not in its table");
   return nullptr;

@@ -700,12 +700,6 @@ const char* ntt_init_device() {
   return nullptr;
 }
 
-static const char* launch_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return make_error("%s: launch failed: %s", what, hipGetErrorString(e));
-  return nullptr;
-}
-
 static const char* zk_shift_cols(r0h_ctx* ctx, uint32_t* io, size_t count, uint32_t po2) {
   const uint32_t threads = po2 >= 8 ? 256 : (1u << po2);
   KScope ks(ctx, "zk_shift_kernel", 8.0 * count * (double)((size_t)1 << po2));
@@ -713,7 +707,7 @@ static const char* zk_shift_cols(r0h_ctx* ctx, uint32_t* io, size_t count, uint3
     const dim3 grid((1u << po2) / threads, (uint32_t)std::min(count - c0, GRID_Y_MAX));
     hipLaunchKernelGGL(zk_shift_kernel, grid, dim3(threads), 0, ctx->stream, io + (c0 << po2), po2, ctx->pow3_lo, ctx->pow3_hi, ctx->pow3_top);
   }
-  return launch_check("zk_shift_kernel");
+  return launch_ok("zk_shift_kernel");
 }
 
 // Radix-16 forward transform of `count` columns (bit-reversed coefficients, 2^(n - expand_bits) words apart at `in`; natural
@@ -730,17 +724,17 @@ static const char* forward16(r0h_ctx* ctx, uint32_t* out, const uint32_t* in, si
     if (expand_bits == 2) launch_local16<0, 2>(ctx, sp.L, 1u << (n_in - sp.L), blocks, out, in, n_in, tw.tw12, c, 0u);
     else launch_local16<0, 0>(ctx, sp.L, 1u << (n_in - sp.L), blocks, out, in, n_in, tw.tw12, c, 0u);
   }
-  R0H_TRY(launch_check("ntt_local16_kernel<fwd>"));
+  R0H_TRY(launch_ok("ntt_local16_kernel<fwd>"));
   if (sp.H) {
     KScope ks(ctx, "ntt_strided_kernel", 8.0 * count * words);
     if (n_in > TW_TOP) launch_strided16<0, 1>(ctx, sp.H, 1u << (sp.L - 4), blocks, out, out, n_in, sp.L, twb, c);
     else launch_strided16<0, 0>(ctx, sp.H, 1u << (sp.L - 4), blocks, out, out, n_in, sp.L, tw, c);
-    R0H_TRY(launch_check("ntt_strided16_kernel<fwd>"));
+    R0H_TRY(launch_ok("ntt_strided16_kernel<fwd>"));
   }
   if (sp.outer) {
     KScope ks(ctx, "ntt_outer_kernel", 8.0 * count * words);
     launch_outer16<0>(ctx, count, out, out, n, twb, c);
-    R0H_TRY(launch_check("ntt_outer16_kernel<fwd>"));
+    R0H_TRY(launch_ok("ntt_outer16_kernel<fwd>"));
   }
   return nullptr;
 }
@@ -757,14 +751,14 @@ static const char* inverse16(r0h_ctx* ctx, uint32_t* io, const uint32_t* src, si
   if (sp.outer) {
     KScope ks(ctx, "ntt_outer_kernel", 8.0 * count * words);
     launch_outer16<1>(ctx, count, io, cur, n, twb, c);
-    R0H_TRY(launch_check("ntt_outer16_kernel<inv>"));
+    R0H_TRY(launch_ok("ntt_outer16_kernel<inv>"));
     cur = io;
   }
   if (sp.H) {
     KScope ks(ctx, "ntt_strided_kernel", 8.0 * count * words);
     if (n_in > TW_TOP) launch_strided16<1, 1>(ctx, sp.H, 1u << (sp.L - 4), blocks, io, cur, n_in, sp.L, twb, c);
     else launch_strided16<1, 0>(ctx, sp.H, 1u << (sp.L - 4), blocks, io, cur, n_in, sp.L, tw, c);
-    R0H_TRY(launch_check("ntt_strided16_kernel<inv>"));
+    R0H_TRY(launch_ok("ntt_strided16_kernel<inv>"));
     cur = io;
   }
   {
@@ -779,7 +773,7 @@ static const char* inverse16(r0h_ctx* ctx, uint32_t* io, const uint32_t* src, si
       launch_local16<1, 0>(ctx, sp.L, 1u << (n_in - sp.L), blocks, io, cur, n_in, tw.tw12, c, norm);
     }
   }
-  return launch_check("ntt_local16_kernel<inv>");
+  return launch_ok("ntt_local16_kernel<inv>");
 }
 
 }  // namespace r0h
@@ -810,12 +804,12 @@ const char* interpolate_ntt(r0h_ctx* ctx, r0h_buf* io, const r0h_buf* src, uint3
     KScope ks(ctx, "ntt_strided_kernel", 8.0 * count * (double)(1u << po2));
     dim3 grid(1u << (sp.L - sp.tlog), count);
     hipLaunchKernelGGL(ntt_strided_kernel<1>, grid, dim3(512), (size_t)4 << (sp.H + sp.tlog), ctx->stream, u32(io), po2, sp.L, sp.H, sp.tlog, tw);
-    R0H_TRY(launch_check("ntt_strided_kernel<inv>"));
+    R0H_TRY(launch_ok("ntt_strided_kernel<inv>"));
   }
   KScope ks(ctx, "ntt_local_kernel", 8.0 * count * (double)(1u << po2));
   dim3 grid(1u << (po2 - sp.L), count);
   hipLaunchKernelGGL(ntt_local_kernel<1>, grid, dim3(256), (size_t)4 << sp.L, ctx->stream, u32(io), u32(io), sp.L, po2, 0u, tw.tw12, norm);
-  R0H_TRY(launch_check("ntt_local_kernel<inv>"));
+  R0H_TRY(launch_ok("ntt_local_kernel<inv>"));
   if (zk_shift) return r0h_zk_shift(ctx, io, count, po2);  // small sizes: separate pass
   return nullptr;
   R0H_GUARD_END
@@ -844,12 +838,12 @@ const char* r0h_batch_expand_into_evaluate_ntt(r0h_ctx* ctx, r0h_buf* out, const
     KScope ks(ctx, "ntt_local_kernel", 4.0 * count * ((double)(1u << n) + (double)(1u << in_po2)));
     hipLaunchKernelGGL(ntt_local_kernel<0>, grid, dim3(256), (size_t)4 << sp.L, ctx->stream, u32(out), u32(in), sp.L, n, expand_bits, tw.tw12, 0u);
   }
-  R0H_TRY(launch_check("ntt_local_kernel<fwd>"));
+  R0H_TRY(launch_ok("ntt_local_kernel<fwd>"));
   if (sp.H) {
     KScope ks(ctx, "ntt_strided_kernel", 8.0 * count * (double)(1u << n));
     dim3 grid2(1u << (sp.L - sp.tlog), count);
     hipLaunchKernelGGL(ntt_strided_kernel<0>, grid2, dim3(512), (size_t)4 << (sp.H + sp.tlog), ctx->stream, u32(out), n, sp.L, sp.H, sp.tlog, tw);
-    R0H_TRY(launch_check("ntt_strided_kernel<fwd>"));
+    R0H_TRY(launch_ok("ntt_strided_kernel<fwd>"));
   }
   return nullptr;
   R0H_GUARD_END
@@ -864,13 +858,13 @@ const char* r0h_batch_bit_reverse(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uin
   if (po2 >= 10) {
     KScope ks(ctx, "bit_reverse_kernel", 8.0 * count * (double)(1u << po2));
     hipLaunchKernelGGL(bit_reverse_tiled_kernel, dim3(1u << (po2 - 10), count), dim3(256), 0, ctx->stream, u32(io), po2);
-    return launch_check("bit_reverse_tiled_kernel");
+    return launch_ok("bit_reverse_tiled_kernel");
   }
   uint32_t threads = po2 >= 8 ? 256 : (1u << po2);
   KScope ks(ctx, "bit_reverse_kernel", 8.0 * count * (double)(1u << po2));
   dim3 grid((1u << po2) / threads, count);
   hipLaunchKernelGGL(bit_reverse_kernel, grid, dim3(threads), 0, ctx->stream, u32(io), po2);
-  return launch_check("bit_reverse_kernel");
+  return launch_ok("bit_reverse_kernel");
   R0H_GUARD_END
 }
 
@@ -887,7 +881,7 @@ const char* bit_reverse_ext(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t 
   } else {
     hipLaunchKernelGGL(bit_reverse_ext_kernel, dim3(1, count), dim3(1u << po2), 0, ctx->stream, (uint4*)io->ptr, po2);
   }
-  return launch_check("bit_reverse_ext kernel");
+  return launch_ok("bit_reverse_ext kernel");
   R0H_GUARD_END
 }
 }  // namespace r0h

@@ -113,9 +113,7 @@ const char* r0h_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix,
   if (!rows) return nullptr;
   KScope ks(ctx, "hash_rows_kernel", (double)rows * cols * 4 + (double)rows * 32);
   hipLaunchKernelGGL(hash_rows_kernel, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, u32(digests), u32(matrix), rows, cols, ctx->p2);
-  hipError_t e = hipGetLastError();
-  R0H_REQUIRE(e == hipSuccess, "hash_rows_kernel: %s", hipGetErrorString(e));
-  return nullptr;
+  return launch_ok("hash_rows_kernel");
   R0H_GUARD_END
 }
 
@@ -128,14 +126,10 @@ const char* r0h_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size) {
   KScope ks(ctx, "hash_fold_kernel", (double)output_size * 96);
   if (output_size <= 8192) {  // fewer parents than the chip has SIMD slots (measured up to 8 K: 1.47 vs 1.52 ms per tree) (32x the instructions per permutation, ~7x less latency): spread each permutation over 24 lanes (latency, not throughput)
     hipLaunchKernelGGL(hash_fold_lanes_kernel, dim3((output_size * 32 + 255) / 256), dim3(256), 0, ctx->stream, u32(nodes), output_size, ctx->p2);
-    hipError_t e = hipGetLastError();
-    R0H_REQUIRE(e == hipSuccess, "hash_fold_lanes_kernel: %s", hipGetErrorString(e));
-    return nullptr;
+    return launch_ok("hash_fold_lanes_kernel");
   }
   hipLaunchKernelGGL(hash_fold_kernel, dim3((output_size + 255) / 256), dim3(256), 0, ctx->stream, u32(nodes), output_size, ctx->p2);
-  hipError_t e = hipGetLastError();
-  R0H_REQUIRE(e == hipSuccess, "hash_fold_kernel: %s", hipGetErrorString(e));
-  return nullptr;
+  return launch_ok("hash_fold_kernel");
   R0H_GUARD_END
 }
 

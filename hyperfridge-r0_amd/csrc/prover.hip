@@ -149,8 +149,7 @@ static const char* tree_open(r0h_ctx* ctx, Scope& sc, const Tree& t, const r0h_b
   R0H_TRY(sc.alloc(ctx, (size_t)n_q * words * 4, &packed));
   hipLaunchKernelGGL(merkle_open_kernel, dim3(n_q), dim3(256), 0, ctx->stream, u32(packed), u32(t.matrix), u32(t.nodes), u32(d_idx),
                      (uint32_t)t.mp.row_size, (uint32_t)t.mp.col_size, (uint32_t)t.mp.path_digests());
-  hipError_t e = hipGetLastError();
-  R0H_REQUIRE(e == hipSuccess, "merkle_open_kernel: %s", hipGetErrorString(e));
+  R0H_TRY(launch_ok("merkle_open_kernel"));
   host.resize((size_t)n_q * words);
   R0H_TRY(r0h_buf_d2h(ctx, packed, 0, host.data(), host.size() * 4));
   sc.release(packed);
@@ -378,15 +377,11 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
   for (int g = 0; g < 3; g++) {
     uint32_t b = cv.group_tap_begin[g], e = cv.group_tap_begin[g + 1];
     if (e == b) continue;
-    r0h_buf view = *d_eval;
-    view.ptr = (char*)d_eval->ptr + (size_t)b * 16;
-    view.bytes = (size_t)(e - b) * 16;
+    r0h_buf view = buf_view(d_eval, (size_t)b * 16, (size_t)(e - b) * 16);
     R0H_TRY(evaluate_any(ctx, grp[g]->coeffs, po2, which.data() + b, (const uint32_t*)(all_xs.data() + b), e - b, &view, true));
   }
   {
-    r0h_buf view = *d_eval;
-    view.ptr = (char*)d_eval->ptr + (size_t)cv.n_taps * 16;
-    view.bytes = (size_t)R0H_CHECK_SIZE * 16;
+    r0h_buf view = buf_view(d_eval, (size_t)cv.n_taps * 16, (size_t)R0H_CHECK_SIZE * 16);
     R0H_TRY(evaluate_any(ctx, g_check.coeffs, po2, which.data() + cv.n_taps, (const uint32_t*)(all_xs.data() + cv.n_taps), R0H_CHECK_SIZE, &view, true));
   }
   std::vector<Fp4> eval_u(n_u);
@@ -456,10 +451,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
     R0H_TRY(stage_h2d(ctx, d_fix->ptr, fix.data(), fix.size() * 4));
     uint32_t nf = (uint32_t)(fix.size() / 2);
     hipLaunchKernelGGL(sub_head_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, u32(combos), u32(d_fix), nf);
-    {
-      hipError_t e = hipGetLastError();
-      R0H_REQUIRE(e == hipSuccess, "sub_head_kernel: %s", hipGetErrorString(e));
-    }
+    R0H_TRY(launch_ok("sub_head_kernel"));
     sc.release(d_fix);
   }
   phase(ctx, "deep_divide");
@@ -542,9 +534,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
     for (Round& rd : rounds) trees.push_back(&rd.tree);
     std::vector<std::vector<uint32_t>> opened(n_trees);
     for (uint32_t t = 0; t < n_trees; t++) {
-      r0h_buf view = *d_idx;
-      view.ptr = (char*)d_idx->ptr + (size_t)t * nq * 4;
-      view.bytes = (size_t)nq * 4;
+      r0h_buf view = buf_view(d_idx, (size_t)t * nq * 4, (size_t)nq * 4);
       R0H_TRY(tree_open(ctx, sc, *trees[t], &view, nq, opened[t]));
     }
     for (uint32_t q = 0; q < nq; q++)

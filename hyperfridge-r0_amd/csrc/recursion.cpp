@@ -57,20 +57,17 @@ void naming_words(const r0h_receipt_claim& claim, uint32_t out[8]) {
 const char* prove_node(r0h_recursor* rc, const uint32_t publics[16], const uint32_t* consumed, size_t n_consumed, std::vector<uint32_t>& seal) {
   r0h_ctx* ctx = rc->ctx;
   const size_t n = (size_t)1 << rc->po2;
-  r0h_buf *code = nullptr, *data = nullptr;
-  R0H_TRY(buf_alloc_pooled(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_CODE] * n * 4, &code));
-  const char* err = buf_alloc_pooled(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_DATA] * n * 4, &data);
+  DevBuf data, code;  // (freed in the reverse order: CODE first)
+  R0H_TRY(code.alloc(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_CODE] * n * 4));
+  R0H_TRY(data.alloc(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_DATA] * n * 4));
   // the rest of the witness is the circuit's synthetic column program: any deterministic seed
   const uint64_t seed = (uint64_t)publics[0] | (uint64_t)publics[8] << 32;
-  if (!err) err = r0h_witgen_public(ctx, rc->circuit, rc->po2, seed, publics, code, data);
+  R0H_TRY(r0h_witgen_public(ctx, rc->circuit, rc->po2, seed, publics, code.get(), data.get()));
   // the sponge rows over what this node consumes: the digest the circuit computes from them is publics[8..16)
-  if (!err) err = sponge_plant(ctx, rc->circuit, rc->po2, consumed, n_consumed, data);
+  R0H_TRY(sponge_plant(ctx, rc->circuit, rc->po2, consumed, n_consumed, data.get()));
   seal.resize((size_t)1 << 19);
   size_t words = 0;
-  if (!err) err = r0h_prove_segment_committed(ctx, rc->circuit, rc->po2, rc->code, data, publics, seal.data(), seal.size(), &words);
-  r0h_buf_free(code);
-  if (data) r0h_buf_free(data);
-  if (err) return err;
+  R0H_TRY(r0h_prove_segment_committed(ctx, rc->circuit, rc->po2, rc->code, data.get(), publics, seal.data(), seal.size(), &words));
   seal.resize(words);
   return nullptr;
 }
@@ -121,14 +118,11 @@ const char* r0h_recursor_new(r0h_ctx* ctx, const uint32_t* recursion_blob, size_
               rc->circuit->n_global);
   R0H_REQUIRE(rc->circuit->has_sponge && rc->circuit->sponge_global == 8, "r0h_recursor_new: a recursion circuit computes the digest of what a node consumed in-circuit (blob section SPONGE, public inputs 8..15); this one does not");
   const size_t n = (size_t)1 << po2;
-  r0h_buf *code = nullptr, *data = nullptr;
-  R0H_TRY(buf_alloc_pooled(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_CODE] * n * 4, &code));
-  const char* err = buf_alloc_pooled(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_DATA] * n * 4, &data);
-  if (!err) err = r0h_witgen(ctx, rc->circuit, po2, 0, code, data, nullptr);
-  if (!err) err = r0h_code_commit_new(ctx, code, rc->circuit->group_size[R0H_GROUP_CODE], po2, &rc->code);
-  r0h_buf_free(code);
-  if (data) r0h_buf_free(data);
-  if (err) return err;
+  DevBuf data, code;  // (freed in the reverse order: CODE first)
+  R0H_TRY(code.alloc(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_CODE] * n * 4));
+  R0H_TRY(data.alloc(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_DATA] * n * 4));
+  R0H_TRY(r0h_witgen(ctx, rc->circuit, po2, 0, code.get(), data.get(), nullptr));
+  R0H_TRY(r0h_code_commit_new(ctx, code.get(), rc->circuit->group_size[R0H_GROUP_CODE], po2, &rc->code));
   R0H_TRY(r0h_code_commit_root(rc->code, rc->root));
   *out = rc.release();
   return nullptr;

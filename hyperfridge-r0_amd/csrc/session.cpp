@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -32,6 +33,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "circuit.hpp"
@@ -50,14 +52,11 @@ struct CodeCommits {  // one committed CODE group per trace size met in the run
     auto it = by_po2.find(po2);
     if (it == by_po2.end()) {
       // the fixed CODE columns come from the blob's column program (the DATA it also fills is scratch here)
-      const size_t n = (size_t)1 << po2;
-      r0h_buf* code = nullptr;
-      R0H_TRY(buf_alloc_pooled(ctx, (size_t)c->group_size[R0H_GROUP_CODE] * n * 4, &code));
-      const char* err = r0h_witgen(ctx, c, po2, 0, code, data_scratch, nullptr);
+      DevBuf code;
+      R0H_TRY(code.alloc(ctx, ((size_t)c->group_size[R0H_GROUP_CODE] << po2) * 4));
+      R0H_TRY(r0h_witgen(ctx, c, po2, 0, code.get(), data_scratch, nullptr));
       r0h_code_commit* cc = nullptr;
-      if (!err) err = r0h_code_commit_new(ctx, code, c->group_size[R0H_GROUP_CODE], po2, &cc);
-      r0h_buf_free(code);
-      if (err) return err;
+      R0H_TRY(r0h_code_commit_new(ctx, code.get(), c->group_size[R0H_GROUP_CODE], po2, &cc));
       it = by_po2.emplace(po2, cc).first;
     }
     *out = it->second;
@@ -81,10 +80,11 @@ uint32_t trace_size(uint64_t rows) {
 
 // Row buffers a context keeps between sessions (r0h_prove_elf): vectors with their heap blocks, some of them page-locked.
 struct RowPool {
-  std::mutex mu;
+  std::mutex mu;  // held by the session that has the buffers
   std::vector<std::vector<r0h_preflight_row>> rows;
   std::vector<std::vector<r0h_preflight_bound>> bounds;
   std::map<const void*, size_t> pinned;
+  ~RowPool() { settle(0); }  // unpins every block, then frees them
   void unpin(const void* p) {
     auto it = pinned.find(p);
     if (it == pinned.end()) return;
@@ -93,9 +93,7 @@ struct RowPool {
   }
   // keep at most `cap` row buffers (pinned ones first); a pinned block that is not among them is unpinned BEFORE its vector is freed
   void settle(size_t cap) {
-    for (size_t k = 0; k < rows.size();)
-      if (!rows[k].capacity()) rows.erase(rows.begin() + k);
-      else k++;
+    rows.erase(std::remove_if(rows.begin(), rows.end(), [](const std::vector<r0h_preflight_row>& r) { return !r.capacity(); }), rows.end());
     std::stable_sort(rows.begin(), rows.end(), [&](const std::vector<r0h_preflight_row>& a, const std::vector<r0h_preflight_row>& b) {
       return (pinned.count(a.data()) != 0) > (pinned.count(b.data()) != 0);
     });
@@ -115,14 +113,222 @@ RowPool* pool_of(r0h_ctx* ctx) {
   if (!ctx->session_rows) ctx->session_rows = new RowPool();
   return (RowPool*)ctx->session_rows;
 }
+
+// The row buffers of one session call.  They are recycled, so there are a handful of them in a run; each is page-locked the first
+// time it is seen (hipHostRegister): the 72 MiB of a segment then cross PCIe by DMA at the link's rate instead of through a staging
+// copy.  Pinning 72 MiB costs tens of milliseconds and a fresh buffer as much again in page faults, so the buffers stay with the
+// context from one call to the next (RowPool): a second run starts with warm, pinned buffers.  While another session on the context
+// has them, this one pins buffers of its own, all of which are unpinned and freed when the call returns.
+class RowBuffers {
+ public:
+  explicit RowBuffers(RowPool* shared) {  // the context's pool (NULL: none), used if no other session has it
+    if (shared) lock_ = std::unique_lock<std::mutex>(shared->mu, std::try_to_lock);
+    if (lock_.owns_lock()) pool_ = shared;
+  }
+  // last run's buffers go to the machine, if they have this run's size (the executor reserves min(2^po2, 2^22) rows)
+  void lend(r0h_vm* vm, uint32_t segment_po2) {
+    const size_t need = (size_t)std::min<uint64_t>((uint64_t)1 << segment_po2, (uint64_t)1 << 22);
+    for (size_t k = 0; k < pool_->rows.size(); k++) {
+      std::vector<r0h_preflight_bound> b;
+      if (k < pool_->bounds.size()) b.swap(pool_->bounds[k]);
+      if (pool_->rows[k].capacity() >= need && pool_->rows[k].capacity() <= 2 * need) vm_recycle_trace(vm, pool_->rows[k], b);
+      else pool_->unpin(pool_->rows[k].data());
+    }
+    pool_->rows.clear();
+    pool_->bounds.clear();
+  }
+  void pin(const void* p, size_t bytes) {  // (any lane)
+    if (!p || !bytes) return;
+    std::lock_guard<std::mutex> lk(pin_mu_);
+    auto it = pool_->pinned.find(p);
+    if (it != pool_->pinned.end() && it->second >= bytes) return;
+    pool_->unpin(p);
+    if (hipHostRegister(const_cast<void*>(p), bytes, hipHostRegisterDefault) == hipSuccess) pool_->pinned[p] = bytes;
+    else (void)hipGetLastError();  // pageable memory still works, only slower
+  }
+  // the hand-back, once the executor thread is gone: every buffer the machine holds; what is pinned but not kept is unpinned
+  // before its memory is freed
+  void take_spares(r0h_vm* vm) {
+    vm_take_spares(vm, pool_->rows, pool_->bounds);
+    pool_->settle(6);
+  }
+
+ private:
+  RowPool own_;
+  std::unique_lock<std::mutex> lock_;
+  RowPool* pool_ = &own_;
+  std::mutex pin_mu_;
+};
+
+struct VmFree { void operator()(r0h_vm* vm) const { r0h_vm_free(vm); } };
+
+// The executor's side of a session: the guest runs ahead on a thread of its own and a few finished segments wait for a prover lane
+// (a 2^20-cycle segment holds 72 MiB of rows).  Only this class locks `mu_`.  It is destroyed before the row buffers it was given:
+// the thread is told to stop and joined, then every row buffer goes back, then the queues and the machine go.
+class Feed {
+ public:
+  struct GiveBack { Feed* feed; void operator()(Produced* p) const { feed->give_back(p); } };
+  using Segment = std::unique_ptr<Produced, GiveBack>;  // in a lane's hands: whatever leaves the lane's iteration, it comes back
+  struct Run {  // what the executor thread leaves behind; read after join()
+    int exit_kind = R0H_VM_LIMIT;
+    uint32_t exit_code = 0;
+    double executor_s = 0;
+    r0h_system_state first_pre{};  // of segment 0: the image id
+    r0h_vm* vm = nullptr;        // finished: the machine is the caller's again
+  };
+
+  Feed(RowBuffers& rows, const r0h_vm_limits& lim, uint32_t part, uint32_t parts) : rows_(rows), lim_(lim), trace_mode_(lim.keep_trace != 0), part_(part), parts_(parts) {}
+  ~Feed() {
+    stop();
+    join();
+    if (producer_err_) r0h_free_error(producer_err_);
+    if (!vm_) return;
+    for (auto& p : queue_) vm_recycle_trace(vm_.get(), p->rows, p->bounds);  // (the machine is this thread's again)
+    for (auto& p : returned_) vm_recycle_trace(vm_.get(), p->rows, p->bounds);
+    rows_.take_spares(vm_.get());
+  }
+  const char* start(const uint8_t* elf, size_t elf_len, const uint32_t* input_words, size_t n_input) {
+    r0h_vm* vm = nullptr;
+    R0H_TRY(r0h_vm_new(&vm));
+    vm_.reset(vm);
+    R0H_TRY(r0h_vm_load_elf(vm, elf, elf_len));
+    R0H_TRY(r0h_vm_set_input(vm, input_words, n_input));
+    rows_.lend(vm, lim_.segment_po2);  // (before the executor thread exists: the machine is still this thread's)
+    thread_ = std::thread(&Feed::execute, this);
+    return nullptr;
+  }
+  // finished segments that may wait for a prover lane: 2 until the lanes are known, then one more than there are lanes
+  void set_lanes(size_t n) {
+    std::lock_guard<std::mutex> lk(mu_);
+    queue_depth_ = n + 1;
+    cv_.notify_all();
+  }
+  // the next segment for a lane; `seg` stays empty when there is none left or the session was stopped; the executor's error goes
+  // to exactly one lane
+  const char* next(Segment& seg) {
+    std::unique_lock<std::mutex> lk(mu_);
+    while (queue_.empty() && !producer_done_ && !stop_) cv_.wait(lk);
+    if (stop_) return nullptr;
+    if (queue_.empty()) return std::exchange(producer_err_, nullptr);
+    seg = Segment(queue_.front().release(), GiveBack{this});
+    queue_.pop_front();
+    cv_.notify_all();
+    return nullptr;
+  }
+  // a proved segment on its way back: the executor refills its row buffers (they may be page-locked: the pool unpins what it drops)
+  void give_back(Produced* p) {
+    std::unique_ptr<Produced> seg(p);
+    if (!trace_mode_) return;
+    std::lock_guard<std::mutex> lk(mu_);
+    returned_.push_back(std::move(seg));
+  }
+  void stop() {  // the lanes and the executor leave at their next look
+    std::lock_guard<std::mutex> lk(mu_);
+    stop_ = true;
+    cv_.notify_all();
+  }
+  const Run& join() {
+    if (thread_.joinable()) thread_.join();
+    run_.vm = vm_.get();
+    return run_;
+  }
+
+ private:
+  void execute() {
+    r0h_vm* vm = vm_.get();
+    const char* err = nullptr;
+    try {
+      size_t handed = 0;
+      for (int finished = 0; !finished && !err;) {
+        std::vector<std::unique_ptr<Produced>> back;
+        {
+          std::unique_lock<std::mutex> lk(mu_);
+          while (!stop_ && queue_.size() >= queue_depth_) cv_.wait(lk);
+          if (stop_) break;
+          back.swap(returned_);
+        }
+        for (auto& b : back) vm_recycle_trace(vm, b->rows, b->bounds);
+        const Clock::time_point t0 = Clock::now();
+        err = r0h_vm_run_segment(vm, &lim_, &finished, &run_.exit_kind, &run_.exit_code);
+        run_.executor_s += seconds(t0, Clock::now());
+        if (err) break;
+        // (the end of the run may have cut more than one segment: the last cycles and the rows that close the session)
+        for (; handed < r0h_vm_n_segments(vm) && !err; handed++) {
+          std::unique_ptr<Produced> p(new Produced());
+          const size_t i = handed;
+          err = r0h_vm_segment_info(vm, i, &p->info);
+          if (!err) err = r0h_vm_segment_claim(vm, i, &p->claim);
+          if (err) break;
+          p->index = i;
+          if (i == 0) run_.first_pre = p->info.pre;
+          if (trace_mode_) vm_take_trace(vm, i, p->rows, p->bounds);
+          const bool own = i % parts_ == part_;
+          std::unique_lock<std::mutex> lk(mu_);
+          while (own && !stop_ && queue_.size() >= queue_depth_ + 2) cv_.wait(lk);
+          if (!own || stop_) vm_recycle_trace(vm, p->rows, p->bounds);  // another rank's, or nobody left to take it: straight back to the machine
+          if (stop_) break;
+          if (!own) continue;
+          queue_.push_back(std::move(p));
+          cv_.notify_all();
+        }
+      }
+    } catch (const std::exception& ex) {
+      err = make_error("exception in the executor: %s", ex.what());
+    } catch (...) {
+      err = make_error("unknown exception in the executor");
+    }
+    std::lock_guard<std::mutex> lk(mu_);
+    producer_err_ = err;
+    producer_done_ = true;
+    cv_.notify_all();
+  }
+
+  RowBuffers& rows_;
+  const r0h_vm_limits lim_;
+  const bool trace_mode_;
+  const uint32_t part_, parts_;
+  std::unique_ptr<r0h_vm, VmFree> vm_;
+  Run run_;
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::deque<std::unique_ptr<Produced>> queue_;
+  std::vector<std::unique_ptr<Produced>> returned_;  // proved segments on their way back
+  bool producer_done_ = false, stop_ = false;
+  size_t queue_depth_ = 2;
+  const char* producer_err_ = nullptr;
+  std::thread thread_;
+};
+
+// Lane 0 on the calling thread, the others on threads of their own; the first error is kept (and `on_error` told), later ones are
+// freed; every thread has been joined when this returns.
+template <class Fn, class OnError>
+const char* run_lanes(const std::vector<r0h_ctx*>& lanes, Fn fn, OnError on_error) {
+  std::atomic<const char*> first(nullptr);
+  auto lane = [&](r0h_ctx* lctx) {
+    const char* err = nullptr;
+    try {
+      err = fn(lctx);
+    } catch (const std::exception& ex) {
+      err = make_error("exception in a prover lane: %s", ex.what());
+    } catch (...) {
+      err = make_error("unknown exception in a prover lane");
+    }
+    if (!err) return;
+    const char* none = nullptr;
+    if (!first.compare_exchange_strong(none, err)) r0h_free_error(err);
+    on_error();
+  };
+  std::vector<std::thread> workers;
+  for (size_t k = 1; k < lanes.size(); k++) workers.emplace_back(lane, lanes[k]);
+  lane(lanes[0]);
+  for (std::thread& t : workers) t.join();
+  return first;
+}
 }  // namespace
 
 namespace r0h {
 void session_rows_free(r0h_ctx* ctx) {
-  RowPool* p = (RowPool*)ctx->session_rows;
-  if (!p) return;
-  p->settle(0);  // unpins every block, then frees them
-  delete p;
+  delete (RowPool*)ctx->session_rows;
   ctx->session_rows = nullptr;
 }
 }  // namespace r0h
@@ -132,11 +338,13 @@ void session_rows_free(r0h_ctx* ctx) {
 constexpr uint32_t RECORD_WORDS = (R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS) + 8;
 static_assert(RECORD_WORDS == R0H_SESSION_RECORD_WORDS, "R0H_SESSION_RECORD_WORDS out of step");
 
+struct ProofAbort { void operator()(r0h_proof* p) const { r0h_proof_abort(p); } };
+
 struct Pending {  // a segment between the phases: committed, waiting for the session challenge
   size_t index = 0;
   r0h_ctx* lctx = nullptr;
-  r0h_proof* proof = nullptr;
-  r0h_buf* data = nullptr;
+  DevBuf data;
+  std::unique_ptr<r0h_proof, ProofAbort> proof;  // in flight (after `data`: it goes first)
   r0h_code_commit* cc = nullptr;
   uint32_t po2 = 0;
   std::vector<uint32_t> global;
@@ -152,6 +360,7 @@ struct r0h_session {
   bool trace_mode = false;
   uint32_t part = 0, parts = 1;
   size_t n_segments = 0;
+  std::mutex commit_mu, result_mu;  // the lanes share `commits`; and `pending`, `stats`, `resident_evaluations`
   std::vector<Pending> pending;  // this rank's segments, by index
   CodeCommits commits;
   std::vector<uint8_t> journal;
@@ -163,13 +372,103 @@ struct r0h_session {
   Clock::time_point t_begin;
   std::vector<r0h_ctx*> lane_ctx;
   ~r0h_session() {
-    for (Pending& p : pending) {
-      if (p.proof) r0h_proof_abort(p.proof);
-      if (p.data) r0h_buf_free(p.data);
-    }
+    pending.clear();  // proofs aborted, buffers freed: before the context is let go
     if (ctx) ctx_release(ctx);
   }
 };
+
+namespace {
+// Phase 1 of a trace-circuit segment: the rows are expanded on the device, the DATA group is committed, the proof waits in `pend`.
+const char* commit_segment(r0h_session* ses, RowBuffers& rows, const Produced& seg, DevBuf& data, std::vector<uint32_t>& global, Pending& pend) {
+  const r0h_circuit* c = ses->c;
+  const Clock::time_point t0 = Clock::now();
+  rows.pin(seg.rows.data(), seg.rows.capacity() * sizeof(r0h_preflight_row));
+  const r0h_trace_segment ts = {seg.info.index + 1, seg.info.closing, seg.info.pre.pc, 0};
+  R0H_TRY(r0h_trace_witgen(pend.lctx, seg.rows.data(), seg.rows.size(), seg.bounds.data(), seg.bounds.size(), pend.po2, &ts, data.get(), global.data()));
+  R0H_TRY(r0h_logup_multiplicities(pend.lctx, c, pend.po2, data.get(), global.data()));
+  const Clock::time_point t1 = Clock::now();
+  r0h_proof* proof = nullptr;
+  R0H_TRY(r0h_proof_begin_committed(pend.lctx, c, pend.po2, pend.cc, data.get(), global.data(), nullptr, &proof));
+  pend.proof.reset(proof);
+  R0H_TRY(r0h_proof_data_root(proof, pend.root));
+  {  // beyond the session's resident limit a segment waits for the challenge without its evaluations
+    const uint64_t evaluations = ((uint64_t)c->group_size[R0H_GROUP_DATA] << pend.po2) * 16;
+    std::unique_lock<std::mutex> lk(ses->result_mu);
+    const bool lean = ses->resident_evaluations + evaluations > ses->resident_limit;
+    if (lean) ses->stats.lean_segments++;
+    else ses->resident_evaluations += evaluations;
+    lk.unlock();
+    if (lean) R0H_TRY(r0h_proof_shrink(proof, nullptr));
+  }
+  const Clock::time_point t2 = Clock::now();
+  pend.global = global;
+  pend.data = std::move(data);
+  std::lock_guard<std::mutex> lk(ses->result_mu);
+  ses->stats.witgen_ms += 1e3 * seconds(t0, t1);
+  ses->stats.prove_ms += 1e3 * seconds(t1, t2);
+  ses->pending.push_back(std::move(pend));
+  return nullptr;
+}
+
+// A segment of any other circuit, proved at once: the synthetic column program with the claim planted.
+const char* prove_synthetic_segment(r0h_session* ses, const Produced& seg, DevBuf& data, std::vector<uint32_t>& global, std::vector<uint32_t>& seal, Pending& pend) {
+  const r0h_circuit* c = ses->c;
+  const Clock::time_point t0 = Clock::now();
+  {  // (CODE is regenerated into a scratch block: only DATA is used)
+    DevBuf code;
+    R0H_TRY(code.alloc(pend.lctx, ((size_t)c->group_size[R0H_GROUP_CODE] << pend.po2) * 4));
+    R0H_TRY(r0h_witgen_public(pend.lctx, c, pend.po2, 0x5E55 + seg.index, global.data(), code.get(), data.get()));
+  }
+  const Clock::time_point t1 = Clock::now();
+  size_t words = 0;
+  seal.resize((size_t)1 << 20);
+  R0H_TRY(r0h_prove_segment_committed(pend.lctx, c, pend.po2, pend.cc, data.get(), global.data(), seal.data(), seal.size(), &words));
+  const Clock::time_point t2 = Clock::now();
+  pend.seal.assign(seal.begin(), seal.begin() + words);
+  pend.done = true;
+  std::lock_guard<std::mutex> lk(ses->result_mu);
+  ses->stats.witgen_ms += 1e3 * seconds(t0, t1);
+  ses->stats.prove_ms += 1e3 * seconds(t1, t2);
+  ses->stats.segments++;
+  ses->pending.push_back(std::move(pend));
+  return nullptr;
+}
+
+// One prover lane of phase 1: every segment the feed has for it, as it arrives.
+const char* take_segments(r0h_session* ses, Feed& feed, RowBuffers& rows, r0h_ctx* lctx) {
+  const r0h_circuit* c = ses->c;
+  std::vector<uint32_t> seal, global(c->n_global);
+  for (;;) {
+    Feed::Segment seg;
+    R0H_TRY(feed.next(seg));
+    if (!seg) return nullptr;
+    const uint64_t rows_needed = ses->trace_mode ? seg->rows.size() + seg->bounds.size() : seg->info.user_cycles + seg->info.paging_cycles;
+    DevBuf data;  // (before `pend`: a proof that fails is aborted before its DATA block goes back)
+    Pending pend;
+    pend.index = seg->index;
+    pend.lctx = lctx;
+    pend.claim = seg->claim;
+    pend.po2 = trace_size(rows_needed);
+    if (ses->trace_mode && pend.po2 < R0H_TRACE_MIN_PO2) pend.po2 = R0H_TRACE_MIN_PO2;
+    uint8_t cd[32];
+    claim_digest(seg->claim, cd);
+    std::fill(global.begin(), global.end(), 0u);
+    claim_globals(cd, global.data());
+    R0H_TRY(data.alloc(lctx, ((size_t)c->group_size[R0H_GROUP_DATA] << pend.po2) * 4));
+    {
+      std::lock_guard<std::mutex> lk(ses->commit_mu);
+      R0H_TRY(ses->commits.get(lctx, c, pend.po2, data.get(), &pend.cc));
+    }
+    R0H_TRY(ses->trace_mode ? commit_segment(ses, rows, *seg, data, global, pend) : prove_synthetic_segment(ses, *seg, data, global, seal, pend));
+  }
+}
+
+uint32_t lane_count() {  // two prover lanes by default
+  uint32_t n = 2;
+  if (const char* v = getenv("R0H_SESSION_LANES")) n = (uint32_t)strtoul(v, nullptr, 10);
+  return n < 1 ? 1 : n > 4 ? 4 : n;
+}
+}  // namespace
 
 extern "C" {
 
@@ -219,293 +518,40 @@ const char* r0h_session_begin(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t*
     R0H_TRY_HIP(hipMemGetInfo(&free_b, &total_b));
     ses->resident_limit = total_b / 8;  // 36 GB of 288: 17 segments of 2^20 rows; the camt53 stand-in's 12 stay whole, the reference's 37 do not
   }
-  r0h_session_stats& stats = ses->stats;
-  r0h_vm* vm = nullptr;
-  R0H_TRY(r0h_vm_new(&vm));
-  struct VmGuard { r0h_vm* v; ~VmGuard() { r0h_vm_free(v); } } guard{vm};
-  R0H_TRY(r0h_vm_load_elf(vm, elf, elf_len));
-  R0H_TRY(r0h_vm_set_input(vm, input_words, n_input));
   r0h_vm_limits lim;
   memset(&lim, 0, sizeof lim);
   lim.segment_po2 = segment_po2;
   lim.max_cycles = max_cycles;
   lim.keep_trace = lim.boundary_rows = trace_mode ? 1 : 0;
 
-  // ---- the executor runs ahead on its own thread; a few finished segments wait (a 2^20-cycle segment holds 72 MiB of rows)
-  std::mutex mu;
-  std::condition_variable cv;
-  std::deque<std::unique_ptr<Produced>> queue;
-  std::vector<std::unique_ptr<Produced>> returned;  // proved segments on their way back: the executor refills their row buffers
-  bool producer_done = false, stop = false;
-  size_t queue_depth = 2;  // finished segments that may wait for a prover lane (set once the lanes are known)
-  const char* producer_err = nullptr;
-  int exit_kind = R0H_VM_LIMIT;
-  uint32_t exit_code = 0;
-  double executor_s = 0;
-  // The row buffers are recycled, so there are a handful of them in a run; each is page-locked the first time it is seen
-  // (hipHostRegister): the 72 MiB of a segment then cross PCIe by DMA at the link's rate instead of through a staging copy.  Pinning
-  // 72 MiB costs tens of milliseconds and a fresh buffer as much again in page faults, so the buffers stay with the context from one
-  // call to the next (RowPool): a second run starts with warm, pinned buffers.
-  RowPool* pool = trace_mode ? pool_of(ctx) : nullptr;
-  std::unique_lock<std::mutex> pool_lock;
-  if (pool) {
-    pool_lock = std::unique_lock<std::mutex>(pool->mu, std::try_to_lock);
-    if (!pool_lock.owns_lock()) pool = nullptr;  // another session on this context has them: this one pins its own
-  }
-  if (pool) {  // (before the executor thread exists: the machine is still this thread's)  last run's buffers, if they have this run's size (the executor reserves min(2^po2, 2^22) rows)
-    const size_t need = (size_t)std::min<uint64_t>((uint64_t)1 << segment_po2, (uint64_t)1 << 22);
-    for (size_t k = 0; k < pool->rows.size(); k++) {
-      std::vector<r0h_preflight_bound> b;
-      if (k < pool->bounds.size()) b.swap(pool->bounds[k]);
-      if (pool->rows[k].capacity() >= need && pool->rows[k].capacity() <= 2 * need) vm_recycle_trace(vm, pool->rows[k], b);
-      else pool->unpin(pool->rows[k].data());
-    }
-    pool->rows.clear();
-    pool->bounds.clear();
-  }
-  // whatever path leaves this function, after the executor thread is gone: the buffers go back to the pool, and what is pinned but
-  // no longer there is unpinned before its memory is freed
-  struct Collect {
-    RowPool* pool; r0h_vm* vm; std::deque<std::unique_ptr<Produced>>& queue; std::vector<std::unique_ptr<Produced>>& returned;
-    ~Collect() {
-      if (!pool) return;
-      for (auto& p : queue) if (p) { pool->rows.emplace_back(); pool->rows.back().swap(p->rows); pool->bounds.emplace_back(); pool->bounds.back().swap(p->bounds); }
-      for (auto& p : returned) if (p) { pool->rows.emplace_back(); pool->rows.back().swap(p->rows); pool->bounds.emplace_back(); pool->bounds.back().swap(p->bounds); }
-      vm_take_spares(vm, pool->rows, pool->bounds);
-      pool->settle(6);
-    }
-  } collect{pool, vm, queue, returned};
-  r0h_system_state first_pre;  // of segment 0: the image id (written by the executor thread, read after it is joined)
-  memset(&first_pre, 0, sizeof first_pre);
-  std::thread producer([&] {
-    const char* err = nullptr;
-    try {
-      size_t handed = 0;
-      for (int finished = 0; !finished && !err;) {
-        std::vector<std::unique_ptr<Produced>> back;
-        {
-          std::unique_lock<std::mutex> lk(mu);
-          cv.wait(lk, [&] { return stop || queue.size() < queue_depth; });
-          if (stop) break;
-          back.swap(returned);
-        }
-        for (auto& b : back) vm_recycle_trace(vm, b->rows, b->bounds);
-        const Clock::time_point t0 = Clock::now();
-        err = r0h_vm_run_segment(vm, &lim, &finished, &exit_kind, &exit_code);
-        executor_s += seconds(t0, Clock::now());
-        if (err) break;
-        // (the end of the run may have cut more than one segment: the last cycles and the rows that close the session)
-        for (; handed < r0h_vm_n_segments(vm) && !err; handed++) {
-          std::unique_ptr<Produced> p(new Produced());
-          const size_t i = handed;
-          err = r0h_vm_segment_info(vm, i, &p->info);
-          if (!err) err = r0h_vm_segment_claim(vm, i, &p->claim);
-          if (err) break;
-          p->index = i;
-          if (i == 0) first_pre = p->info.pre;
-          if (i % parts != part) {  // another rank's segment: its row buffers go straight back to the machine
-            if (trace_mode) { vm_take_trace(vm, i, p->rows, p->bounds); vm_recycle_trace(vm, p->rows, p->bounds); }
-            continue;
-          }
-          if (trace_mode) vm_take_trace(vm, i, p->rows, p->bounds);
-          std::unique_lock<std::mutex> lk(mu);
-          cv.wait(lk, [&] { return stop || queue.size() < queue_depth + 2; });
-          if (stop) break;
-          queue.push_back(std::move(p));
-          cv.notify_all();
-        }
-      }
-    } catch (const std::exception& ex) {
-      err = make_error("exception in the executor: %s", ex.what());
-    } catch (...) {
-      err = make_error("unknown exception in the executor");
-    }
-    std::lock_guard<std::mutex> lk(mu);
-    producer_err = err;
-    producer_done = true;
-    cv.notify_all();
-  });
-  struct Pins {
-    RowPool* pool;
-    std::map<const void*, size_t> local;
-    std::map<const void*, size_t>& seen() { return pool ? pool->pinned : local; }
-    void pin(const void* p, size_t bytes) {
-      if (!p || !bytes) return;
-      auto& m = seen();
-      auto it = m.find(p);
-      if (it != m.end() && it->second >= bytes) return;
-      if (it != m.end()) { (void)hipHostUnregister(const_cast<void*>(p)); m.erase(it); }
-      if (hipHostRegister(const_cast<void*>(p), bytes, hipHostRegisterDefault) == hipSuccess) m[p] = bytes;
-      else (void)hipGetLastError();  // pageable memory still works, only slower
-    }
-    ~Pins() { for (auto& kv : local) (void)hipHostUnregister(const_cast<void*>(kv.first)); }
-  } pins{pool, {}};
-  struct Join {  // whatever path leaves this function: the executor thread is told to stop and joined first
-    std::thread& t; std::mutex& mu; std::condition_variable& cv; bool& stop;
-    ~Join() {
-      { std::lock_guard<std::mutex> lk(mu); stop = true; }
-      cv.notify_all();
-      if (t.joinable()) t.join();
-    }
-  } join{producer, mu, cv, stop};
+  // ---- the executor runs ahead on its own thread (`feed` goes before `rows`: the thread is joined before any row buffer is let go)
+  RowBuffers rows(trace_mode ? pool_of(ctx) : nullptr);
+  Feed feed(rows, lim, part, parts);
+  R0H_TRY(feed.start(elf, elf_len, input_words, n_input));
 
   // ---- every segment as it arrives.  Two prover lanes by default (R0H_SESSION_LANES = 1..4): lane 0 is the caller's context on the
   // calling thread, the others are helper contexts of the same device (kept with `ctx` between calls) on threads of their own -- while
   // one lane waits for a transcript read-back the other keeps the device busy.  The circuit and the CODE commitments are shared.
-  uint32_t n_lanes = 2;
-  if (const char* v = getenv("R0H_SESSION_LANES")) n_lanes = (uint32_t)strtoul(v, nullptr, 10);
-  n_lanes = n_lanes < 1 ? 1 : n_lanes > 4 ? 4 : n_lanes;
-  std::vector<r0h_ctx*>& lane_ctx = ses->lane_ctx;
-  lane_ctx.assign(n_lanes, ctx);
-  for (uint32_t k = 1; k < n_lanes; k++) R0H_TRY(ctx_helper(ctx, k - 1, &lane_ctx[k]));
-  {
-    std::lock_guard<std::mutex> lk(mu);
-    queue_depth = n_lanes + 1;
-    cv.notify_all();
-  }
-  std::mutex commit_mu, result_mu;
-  CodeCommits& commits = ses->commits;
-  const char* lane_err = nullptr;
+  ses->lane_ctx.assign(lane_count(), ctx);
+  for (size_t k = 1; k < ses->lane_ctx.size(); k++) R0H_TRY(ctx_helper(ctx, k - 1, &ses->lane_ctx[k]));
+  feed.set_lanes(ses->lane_ctx.size());
+  R0H_TRY(run_lanes(ses->lane_ctx, [&](r0h_ctx* lctx) { return take_segments(ses.get(), feed, rows, lctx); }, [&] { feed.stop(); }));
 
-  auto lane_body = [&](r0h_ctx* lctx) -> const char* {
-    std::vector<uint32_t> seal, global(c->n_global);
-    for (;;) {
-      std::unique_ptr<Produced> seg;
-      size_t i;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return !queue.empty() || producer_done || stop; });
-        if (stop) return nullptr;
-        if (queue.empty()) {
-          if (producer_err) { const char* e = producer_err; producer_err = nullptr; return e; }
-          return nullptr;
-        }
-        seg = std::move(queue.front());
-        queue.pop_front();
-        i = seg->index;
-        cv.notify_all();
-      }
-      // whatever leaves this iteration, the segment's row buffers go back (they may be page-locked: the pool unpins what it drops)
-      struct Return {
-        std::unique_ptr<Produced>& seg; std::mutex& mu; std::vector<std::unique_ptr<Produced>>& returned; bool on;
-        ~Return() { if (on && seg) { std::lock_guard<std::mutex> lk(mu); returned.push_back(std::move(seg)); } }
-      } give_back{seg, mu, returned, trace_mode};
-      const uint64_t rows_needed = trace_mode ? seg->rows.size() + seg->bounds.size() : seg->info.user_cycles + seg->info.paging_cycles;
-      uint32_t po2 = trace_size(rows_needed);
-      if (trace_mode && po2 < R0H_TRACE_MIN_PO2) po2 = R0H_TRACE_MIN_PO2;
-      uint8_t cd[32];
-      claim_digest(seg->claim, cd);
-      std::fill(global.begin(), global.end(), 0u);
-      claim_globals(cd, global.data());
-      const size_t n = (size_t)1 << po2;
-      r0h_buf* data = nullptr;
-      R0H_TRY(buf_alloc_pooled(lctx, (size_t)c->group_size[R0H_GROUP_DATA] * n * 4, &data));
-      struct Free { r0h_buf* b; ~Free() { if (b) r0h_buf_free(b); } } data_guard{data};
-      r0h_code_commit* cc = nullptr;
-      {
-        std::lock_guard<std::mutex> lk(commit_mu);
-        R0H_TRY(commits.get(lctx, c, po2, data, &cc));
-      }
-      const Clock::time_point t0 = Clock::now();
-      Pending pend;
-      pend.index = i;
-      pend.lctx = lctx;
-      pend.po2 = po2;
-      pend.cc = cc;
-      pend.claim = seg->claim;
-      if (trace_mode) {
-        {
-          std::lock_guard<std::mutex> lk(result_mu);
-          pins.pin(seg->rows.data(), seg->rows.capacity() * sizeof(r0h_preflight_row));
-        }
-        const r0h_trace_segment ts = {seg->info.index + 1, seg->info.closing, seg->info.pre.pc, 0};
-        R0H_TRY(r0h_trace_witgen(lctx, seg->rows.data(), seg->rows.size(), seg->bounds.data(), seg->bounds.size(), po2, &ts, data, global.data()));
-        R0H_TRY(r0h_logup_multiplicities(lctx, c, po2, data, global.data()));
-        const Clock::time_point t1 = Clock::now();
-        R0H_TRY(r0h_proof_begin_committed(lctx, c, po2, cc, data, global.data(), nullptr, &pend.proof));
-        struct Abort { r0h_proof*& p; bool armed; ~Abort() { if (armed && p) { r0h_proof_abort(p); p = nullptr; } } } abort_guard{pend.proof, true};
-        R0H_TRY(r0h_proof_data_root(pend.proof, pend.root));
-        {  // beyond the session's resident limit a segment waits for the challenge without its evaluations
-          const uint64_t evaluations = (uint64_t)c->group_size[R0H_GROUP_DATA] * n * 16;
-          bool lean;
-          {
-            std::lock_guard<std::mutex> lk(result_mu);
-            lean = ses->resident_evaluations + evaluations > ses->resident_limit;
-            if (lean) stats.lean_segments++;
-            else ses->resident_evaluations += evaluations;
-          }
-          if (lean) R0H_TRY(r0h_proof_shrink(pend.proof, nullptr));
-        }
-        const Clock::time_point t2 = Clock::now();
-        pend.global = global;
-        pend.data = data;
-        data_guard.b = nullptr;
-        abort_guard.armed = false;
-        std::lock_guard<std::mutex> lk(result_mu);
-        stats.witgen_ms += 1e3 * seconds(t0, t1);
-        stats.prove_ms += 1e3 * seconds(t1, t2);
-        ses->pending.push_back(std::move(pend));
-      } else {
-        // synthetic column program with the claim planted (CODE is regenerated into a scratch block: only DATA is used)
-        r0h_buf* code = nullptr;
-        R0H_TRY(buf_alloc_pooled(lctx, (size_t)c->group_size[R0H_GROUP_CODE] * n * 4, &code));
-        const char* err = r0h_witgen_public(lctx, c, po2, 0x5E55 + i, global.data(), code, data);
-        r0h_buf_free(code);
-        if (err) return err;
-        const Clock::time_point t1 = Clock::now();
-        size_t words = 0;
-        seal.resize((size_t)1 << 20);
-        R0H_TRY(r0h_prove_segment_committed(lctx, c, po2, cc, data, global.data(), seal.data(), seal.size(), &words));
-        const Clock::time_point t2 = Clock::now();
-        pend.seal.assign(seal.begin(), seal.begin() + words);
-        pend.done = true;
-        std::lock_guard<std::mutex> lk(result_mu);
-        stats.witgen_ms += 1e3 * seconds(t0, t1);
-        stats.prove_ms += 1e3 * seconds(t1, t2);
-        stats.segments++;
-        ses->pending.push_back(std::move(pend));
-      }
-    }
-  };
-  auto guarded = [&](r0h_ctx* lctx) {
-    const char* err = nullptr;
-    try {
-      err = lane_body(lctx);
-    } catch (const std::exception& ex) {
-      err = make_error("exception in a prover lane: %s", ex.what());
-    } catch (...) {
-      err = make_error("unknown exception in a prover lane");
-    }
-    if (err) {
-      std::lock_guard<std::mutex> lk(mu);
-      if (!lane_err) lane_err = err;
-      else r0h_free_error(err);
-      stop = true;  // the other lanes and the executor leave at their next look
-      cv.notify_all();
-    }
-  };
-  {
-    std::vector<std::thread> workers;
-    for (uint32_t k = 1; k < n_lanes; k++) workers.emplace_back(guarded, lane_ctx[k]);
-    guarded(lane_ctx[0]);
-    for (std::thread& t : workers) t.join();
-  }
-  if (lane_err) return lane_err;
-  producer.join();  // finished: the machine is this thread's again
-  R0H_REQUIRE(exit_kind != R0H_VM_LIMIT, "r0h_prove_elf: the guest did not halt within %llu cycles (session limit)", (unsigned long long)max_cycles);
-  R0H_REQUIRE(exit_code == 0, "r0h_prove_elf: the guest exited with code %u", exit_code);  // `prove` is an Err for a failed guest
-  ses->n_segments = r0h_vm_n_segments(vm);
+  const Feed::Run& run = feed.join();
+  R0H_REQUIRE(run.exit_kind != R0H_VM_LIMIT, "r0h_prove_elf: the guest did not halt within %llu cycles (session limit)", (unsigned long long)max_cycles);
+  R0H_REQUIRE(run.exit_code == 0, "r0h_prove_elf: the guest exited with code %u", run.exit_code);  // `prove` is an Err for a failed guest
+  ses->n_segments = r0h_vm_n_segments(run.vm);
   std::sort(ses->pending.begin(), ses->pending.end(), [](const Pending& a, const Pending& b) { return a.index < b.index; });
   size_t own = 0;
   for (size_t i = part; i < ses->n_segments; i += parts) own++;
   R0H_REQUIRE(ses->pending.size() == own, "r0h_prove_elf: %zu of this rank's %zu segments were committed", ses->pending.size(), own);
-  ses->cycles = r0h_vm_cycles(vm);
+  ses->cycles = r0h_vm_cycles(run.vm);
   const uint8_t* journal; size_t journal_len;
-  R0H_TRY(r0h_vm_journal(vm, &journal, &journal_len));
+  R0H_TRY(r0h_vm_journal(run.vm, &journal, &journal_len));
   ses->journal.assign(journal, journal + journal_len);
-  system_state_digest(first_pre, ses->image_id);  // the image id the verifier is given: digest of the state the run started from
-  stats.cycles = ses->cycles;
-  stats.executor_s = executor_s;
+  system_state_digest(run.first_pre, ses->image_id);  // the image id the verifier is given: digest of the state the run started from
+  ses->stats.cycles = ses->cycles;
+  ses->stats.executor_s = run.executor_s;
   *session_out = ses.release();
   return nullptr;
   R0H_GUARD_END
@@ -529,12 +575,29 @@ const char* r0h_session_records(const r0h_session* s, uint32_t* indices_out, uin
   return nullptr;
 }
 
+namespace {
+// Phase 2 of a segment: the challenge and the segment's own sum under it become its late public inputs, and the proof is finished.
+// The DATA block goes back to the pool whether or not the proof succeeds.
+const char* finish_segment(r0h_session* s, Pending& p, const uint32_t challenge[16], std::vector<uint32_t>& mix, std::vector<uint32_t>& seal, size_t* words) {
+  const r0h_circuit* c = s->c;
+  DevBuf data = std::move(p.data);
+  memcpy(p.global.data() + R0H_TRACE_GAMMA, challenge, 64);
+  const r0h_buf* code_cols = nullptr;
+  R0H_TRY(r0h_code_commit_columns(p.cc, &code_cols));
+  R0H_TRY(r0h_logup_totals(p.lctx, c, p.po2, code_cols, data.get(), p.global.data()));
+  R0H_TRY(r0h_proof_late(p.proof.get(), p.global.data() + (R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS), mix.data()));
+  DevBuf accum;
+  R0H_TRY(accum.alloc(p.lctx, ((size_t)c->group_size[R0H_GROUP_ACCUM] << p.po2) * 4));
+  R0H_TRY(r0h_accum_public(p.lctx, c, p.po2, code_cols, data.get(), p.global.data(), mix.data(), accum.get()));
+  return r0h_proof_finish(p.proof.release(), accum.get(), seal.data(), seal.size(), words);  // consumed either way
+}
+}  // namespace
+
 // Phase 2: with the records of ALL segments of the session (in index order) the challenge is fixed; every proof of this rank receives
 // it and its own sum under it as late public inputs and is finished.  The receipt holds this rank's segments.
 const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size_t n_records, r0h_receipt** receipt_out, uint8_t image_id_out[32], uint64_t* cycles_out) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(s && receipt_out, "r0h_session_finish: NULL argument");
-  const r0h_circuit* c = s->c;
   std::vector<uint32_t> image_seal;
   if (s->trace_mode) {
     R0H_REQUIRE(all_records && n_records == s->n_segments, "r0h_session_finish: the session has %zu segments, %zu records were given", s->n_segments, n_records);
@@ -544,66 +607,30 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
                   "r0h_session_finish: record %zu is not the one this rank committed", p.index);
     uint32_t challenge[16];
     session_challenge(all_records, n_records, challenge);
-    std::mutex err_mu;
-    const char* first_err = nullptr;
-    auto lane = [&](r0h_ctx* lctx) {
-      std::vector<uint32_t> seal((size_t)1 << 20), mix(c->n_mix);
+    std::atomic<bool> failed(false);  // a lane's error: the others leave before their next segment
+    auto lane = [&](r0h_ctx* lctx) -> const char* {
+      std::vector<uint32_t> seal((size_t)1 << 20), mix(s->c->n_mix);
+      size_t words = 0;
       if (lctx == s->ctx && !s->elf.empty() && s->ctx->image_circuit) {
         // the image's side of the balance, proved (`receipt.verify(image_id)` then needs no ELF): first thing on the first lane, beside
         // the other lanes' segments -- all it waits for is the challenge
-        size_t words = 0;
-        const char* err = r0h_prove_image(s->ctx, s->ctx->image_circuit, s->elf.data(), s->elf.size(), challenge, seal.data(), seal.size(), &words);
-        std::lock_guard<std::mutex> lk(err_mu);
-        if (err) { if (!first_err) first_err = err; else r0h_free_error(err); return; }
+        R0H_TRY(r0h_prove_image(s->ctx, s->ctx->image_circuit, s->elf.data(), s->elf.size(), challenge, seal.data(), seal.size(), &words));
         image_seal.assign(seal.begin(), seal.begin() + words);
       }
       for (Pending& p : s->pending) {
         if (p.lctx != lctx || p.done) continue;
-        {
-          std::lock_guard<std::mutex> lk(err_mu);
-          if (first_err) return;
-        }
+        if (failed) return nullptr;
         const Clock::time_point t0 = Clock::now();
-        const char* err = nullptr;
-        const size_t n = (size_t)1 << p.po2;
-        r0h_buf* accum = nullptr;
-        size_t words = 0;
-        do {
-          memcpy(p.global.data() + R0H_TRACE_GAMMA, challenge, 64);
-          const r0h_buf* code_cols = nullptr;
-          if ((err = r0h_code_commit_columns(p.cc, &code_cols))) break;
-          if ((err = r0h_logup_totals(lctx, c, p.po2, code_cols, p.data, p.global.data()))) break;
-          if ((err = r0h_proof_late(p.proof, p.global.data() + (R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS), mix.data()))) break;
-          if ((err = buf_alloc_pooled(lctx, (size_t)c->group_size[R0H_GROUP_ACCUM] * n * 4, &accum))) break;
-          if ((err = r0h_accum_public(lctx, c, p.po2, code_cols, p.data, p.global.data(), mix.data(), accum))) break;
-          r0h_proof* proof = p.proof;
-          p.proof = nullptr;  // consumed either way
-          if ((err = r0h_proof_finish(proof, accum, seal.data(), seal.size(), &words))) break;
-        } while (false);
-        if (accum) r0h_buf_free(accum);
-        r0h_buf_free(p.data);
-        p.data = nullptr;
-        std::lock_guard<std::mutex> lk(err_mu);
-        if (err) { if (!first_err) first_err = err; else r0h_free_error(err); return; }
+        R0H_TRY(finish_segment(s, p, challenge, mix, seal, &words));
+        std::lock_guard<std::mutex> lk(s->result_mu);
         p.seal.assign(seal.begin(), seal.begin() + words);
         p.done = true;
         s->stats.prove_ms += 1e3 * seconds(t0, Clock::now());
         s->stats.segments++;
       }
+      return nullptr;
     };
-    auto guarded = [&](r0h_ctx* lctx) {
-      try {
-        lane(lctx);
-      } catch (const std::exception& ex) {
-        std::lock_guard<std::mutex> lk(err_mu);
-        if (!first_err) first_err = make_error("exception in a prover lane: %s", ex.what());
-      }
-    };
-    std::vector<std::thread> workers;
-    for (size_t k = 1; k < s->lane_ctx.size(); k++) workers.emplace_back(guarded, s->lane_ctx[k]);
-    guarded(s->lane_ctx[0]);
-    for (std::thread& t : workers) t.join();
-    if (first_err) return first_err;
+    R0H_TRY(run_lanes(s->lane_ctx, lane, [&] { failed = true; }));
   }
   r0h_receipt* rc = nullptr;
   R0H_TRY(r0h_receipt_new(R0H_RECEIPT_COMPOSITE, nullptr, 0, &rc));
@@ -623,17 +650,23 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
   R0H_GUARD_END
 }
 
+// both phases on one rank: the records this rank contributes are all there are
+static const char* prove_session(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t* elf, size_t elf_len, const uint32_t* input_words, size_t n_input, uint32_t segment_po2,
+                                 uint64_t max_cycles, uint32_t part, uint32_t parts, r0h_receipt** receipt_out, uint8_t image_id_out[32], uint64_t* cycles_out) {
+  r0h_session* s = nullptr;
+  R0H_TRY(r0h_session_begin(ctx, c, elf, elf_len, input_words, n_input, segment_po2, max_cycles, part, parts, &s));
+  std::unique_ptr<r0h_session> guard(s);
+  std::vector<uint32_t> indices(s->pending.size() + 1), records((s->pending.size() + 1) * RECORD_WORDS);
+  size_t n = 0;
+  R0H_TRY(r0h_session_records(s, indices.data(), records.data(), s->pending.size(), &n));
+  return r0h_session_finish(s, records.data(), n, receipt_out, image_id_out, cycles_out);
+}
+
 const char* r0h_prove_elf(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t* elf, size_t elf_len, const uint32_t* input_words, size_t n_input, uint32_t segment_po2,
                           uint64_t max_cycles, r0h_receipt** receipt_out, uint8_t image_id_out[32], uint64_t* cycles_out) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(receipt_out, "r0h_prove_elf: NULL argument");
-  r0h_session* s = nullptr;
-  R0H_TRY(r0h_session_begin(ctx, c, elf, elf_len, input_words, n_input, segment_po2, max_cycles, 0, 1, &s));
-  std::unique_ptr<r0h_session> guard(s);
-  std::vector<uint32_t> indices(s->pending.size()), records(s->pending.size() * RECORD_WORDS);
-  size_t n = 0;
-  R0H_TRY(r0h_session_records(s, indices.data(), records.data(), s->pending.size(), &n));
-  return r0h_session_finish(s, records.data(), n, receipt_out, image_id_out, cycles_out);
+  return prove_session(ctx, c, elf, elf_len, input_words, n_input, segment_po2, max_cycles, 0, 1, receipt_out, image_id_out, cycles_out);
   R0H_GUARD_END
 }
 
@@ -644,13 +677,7 @@ const char* r0h_prove_elf_part(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t
   R0H_GUARD_BEGIN
   R0H_REQUIRE(receipt_out && c, "r0h_prove_elf_part: NULL argument");
   R0H_REQUIRE(parts == 1 || c->n_late == 0, "r0h_prove_elf_part: the segments of a trace-circuit session share one challenge: ranks use r0h_session_begin / r0h_session_records / r0h_session_finish");
-  r0h_session* s = nullptr;
-  R0H_TRY(r0h_session_begin(ctx, c, elf, elf_len, input_words, n_input, segment_po2, max_cycles, part, parts, &s));
-  std::unique_ptr<r0h_session> guard(s);
-  std::vector<uint32_t> indices(s->pending.size() + 1), records((s->pending.size() + 1) * RECORD_WORDS);
-  size_t n = 0;
-  R0H_TRY(r0h_session_records(s, indices.data(), records.data(), s->pending.size(), &n));
-  return r0h_session_finish(s, records.data(), n, receipt_out, image_id_out, cycles_out);
+  return prove_session(ctx, c, elf, elf_len, input_words, n_input, segment_po2, max_cycles, part, parts, receipt_out, image_id_out, cycles_out);
   R0H_GUARD_END
 }
 

@@ -59,9 +59,8 @@ const char* r0h_trace_witgen(r0h_ctx* ctx, const r0h_preflight_row* rows, size_t
   }
   KScope ks(ctx, "trace_witgen", (double)n_rows * sizeof(r0h_preflight_row) + (double)n_bounds * sizeof(r0h_preflight_bound) + (double)R0H_TRACE_COLUMNS * n * 4);
   const size_t row_bytes = n_rows * sizeof(r0h_preflight_row), bound_bytes = n_bounds * sizeof(r0h_preflight_bound), tab_off = (row_bytes + bound_bytes + 15) & ~(size_t)15;
-  r0h_buf* staging = nullptr;
-  R0H_TRY(buf_alloc_pooled(ctx, tab_off + sizeof(trace::Tables), &staging));
-  struct Free { r0h_buf* b; ~Free() { r0h_buf_free(b); } } guard{staging};
+  DevBuf staging;
+  R0H_TRY(staging.alloc(ctx, tab_off + sizeof(trace::Tables)));
   char* base = (char*)staging->ptr;
   // the caller's arrays are pageable: the copies are stream-ordered but return only once the source has been read
   if (n_rows) R0H_TRY_HIP(hipMemcpyAsync(base, rows, row_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -69,8 +68,7 @@ const char* r0h_trace_witgen(r0h_ctx* ctx, const r0h_preflight_row* rows, size_t
   R0H_TRY(stage_h2d(ctx, base + tab_off, &trace::trace_tables(), sizeof(trace::Tables)));
   hipLaunchKernelGGL(trace_witgen_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, u32(data), (const r0h_preflight_row*)base, (uint32_t)n_rows,
                      (const r0h_preflight_bound*)(base + row_bytes), (uint32_t)n_bounds, (const trace::Tables*)(base + tab_off), po2, segment->number, segment->closing);
-  hipError_t e = hipGetLastError();
-  R0H_REQUIRE(e == hipSuccess, "trace_witgen_kernel: %s", hipGetErrorString(e));
+  R0H_TRY(launch_ok("trace_witgen_kernel"));
   trace::trace_globals(rows, n_rows, bounds, n_bounds, segment->number, segment->closing != 0, segment->idle_pc, globals_out);
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the staging block goes back to the pool and the caller may free its rows
   return nullptr;
