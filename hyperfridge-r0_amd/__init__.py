@@ -38,6 +38,11 @@ _SIGNATURES = {
     "r0h_ctx_create": [_c.c_int, _pp],
     "r0h_ctx_destroy": [_vp],
     "r0h_sync": [_vp],
+    "r0h_ctx_set_hashfn": [_vp, _cp],
+    "r0h_hash_pair_host": [_cp, _vp, _vp, _vp],
+    "r0h_hash_elems_host": [_cp, _vp, _sz, _vp],
+    "r0h_verify_seal_hashfn": [_vp, _sz, _cp, _vp, _sz, _vp, _c.POINTER(_c.c_int), _c.POINTER(_u32), _vp],
+    "r0h_control_root_host_hashfn": [_vp, _sz, _cp, _u32, _vp],
     "r0h_buf_alloc": [_vp, _sz, _pp],
     "r0h_buf_wrap": [_vp, _vp, _sz, _pp],
     "r0h_buf_slice": [_vp, _sz, _sz, _pp],
@@ -198,6 +203,7 @@ _SIGNATURES = {
 _PLAIN = {
     "r0h_free_error": ([_vp], None),
     "r0h_version": ([], _cp),
+    "r0h_ctx_hashfn": ([_vp], _cp),
     "r0h_receipt_kind": ([_vp], _c.c_int),
     "r0h_receipt_n_segments": ([_vp], _sz),
     "r0h_ebics_n_documents": ([_vp], _sz),
@@ -367,13 +373,25 @@ def emit_eval_check_source(blob):
     return src
 
 
-def verify_seal(blob, seal, poseidon2_consts=None, code_root=None):
+def verify_seal(blob, seal, poseidon2_consts=None, code_root=None, hashfn="poseidon2"):
     """Host-side check of a seal against a circuit blob (r0h_verify_seal_bound; needs no GPU): returns (verdict, reason, po2),
     verdict 0 = accepted.  poseidon2_consts = (round_constants[29*24], diag_m1[24]) canonical words, or None for the
     compiled-in table.  code_root = the program's control root at the seal's trace size (Hal.code_root); None leaves the
-    seal unbound to any program (proof-system tests only).  Mirrors `receipt.verify(image_id)` (verifier/src/main.rs:124-126)."""
+    seal unbound to any program (proof-system tests only).  Mirrors `receipt.verify(image_id)` (verifier/src/main.rs:124-126).
+    hashfn: the suite the seal was made under ("poseidon2" / "sha-256": r0h_verify_seal_hashfn; compiled-in tables only)."""
     b, pb = _u32arr(blob)
     s_, ps = _u32arr(seal)
+    if hashfn != "poseidon2":
+        if poseidon2_consts is not None:
+            raise R0HipError("verify_seal: Poseidon2 tables make no sense with hashfn=%r" % (hashfn,))
+        verdict, po2 = _c.c_int(-1), _u32(0)
+        proot = None
+        if code_root is not None:
+            root, proot = _u32arr(code_root)
+            if root.size != 8:
+                raise R0HipError("verify_seal: a code root is 8 words")
+        _check(lib().r0h_verify_seal_hashfn(pb, b.size, str(hashfn).encode(), ps, s_.size, proot, ctypes.byref(verdict), ctypes.byref(po2), None))
+        return verdict.value, lib().r0h_verify_reason(verdict.value).decode(), po2.value
     prc = pdg = None
     if poseidon2_consts is not None:
         rc, prc = _u32arr(poseidon2_consts[0])
@@ -858,17 +876,41 @@ def trace_blob():
     return _trace_blob
 
 
-def control_root_host(blob, po2, round_constants=None, diag_m1=None):
+def control_root_host(blob, po2, round_constants=None, diag_m1=None, hashfn="poseidon2"):
     """r0h_control_root_host: the control root of the circuit's own CODE columns at trace size 2^po2, computed on the host from the blob
-    (the 8 words Hal.code_commit(...).root() gives on the device)"""
+    (the 8 words Hal.code_commit(...).root() gives on the device); hashfn: under which hash suite (r0h_control_root_host_hashfn)"""
     blob, pb = _u32arr(blob)
     out = np.zeros(8, dtype=np.uint32)
+    if hashfn != "poseidon2":
+        if round_constants is not None:
+            raise R0HipError("control_root_host: Poseidon2 tables make no sense with hashfn=%r" % (hashfn,))
+        _check(lib().r0h_control_root_host_hashfn(pb, blob.size, str(hashfn).encode(), po2, out.ctypes.data_as(_vp)))
+        return out
     rc = dg = None
     prc = pdg = None
     if round_constants is not None:
         rc, prc = _u32arr(round_constants)
         dg, pdg = _u32arr(diag_m1)
     _check(lib().r0h_control_root_host(pb, blob.size, prc, pdg, po2, out.ctypes.data_as(_vp)))
+    return out
+
+
+def hash_pair_host(hashfn, a, b):
+    """r0h_hash_pair_host: the named suite's hash of two digests (pure host)"""
+    a, pa = _u32arr(a)
+    b, pb = _u32arr(b)
+    if a.size != 8 or b.size != 8:
+        raise R0HipError("hash_pair_host: a digest is 8 words")
+    out = np.zeros(8, dtype=np.uint32)
+    _check(lib().r0h_hash_pair_host(str(hashfn).encode(), pa, pb, out.ctypes.data_as(_vp)))
+    return out
+
+
+def hash_elems_host(hashfn, words):
+    """r0h_hash_elems_host: the named suite's hash of a slice of words (what hash_rows computes per row; pure host)"""
+    w, pw = _u32arr(words)
+    out = np.zeros(8, dtype=np.uint32)
+    _check(lib().r0h_hash_elems_host(str(hashfn).encode(), pw if w.size else None, w.size, out.ctypes.data_as(_vp)))
     return out
 
 
@@ -1119,6 +1161,14 @@ class Hal:
 
     def sync(self):
         _check(lib().r0h_sync(self.ctx))
+
+    def set_hashfn(self, name):
+        """the context's hash suite: "poseidon2" (default) or "sha-256" (r0h_ctx_set_hashfn)"""
+        _check(lib().r0h_ctx_set_hashfn(self.ctx, str(name).encode()))
+
+    @property
+    def hashfn(self):
+        return lib().r0h_ctx_hashfn(self.ctx).decode()
 
     # ---- buffers
     def alloc(self, words):

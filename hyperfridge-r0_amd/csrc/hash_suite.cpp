@@ -1,0 +1,210 @@
+// The two hash suites on the host: what the transcript (prover.hip), the verifier (verify.cpp) and a caller's own transcript hashing
+// (r0h_hash_pair_host / r0h_hash_elems_host) run.  Poseidon2 is the code of ctx.cpp behind the suite interface, word for word what
+// the sequencer did before there was a second suite.  SHA-256 is recalled from risc0-zkp core/hash/sha (`Sha256HashSuite`,
+// `Sha256Rng`) and risc0-sys sha256.h: unpinned (the reference vendors neither); tests/sha_suite_ref.py is normative here.
+//
+// SHA-256 suite: a digest is eight u32 words, word j = bswap32 of SHA-256 state word j (the digest's bytes in memory are the standard
+// big-endian byte order); message word i of a compression = bswap32 of input word i.
+//   hash_pair(a, b)        one compression of the IV over the 16 words a || b: no padding, no length
+//   hash_elems(words, n)   risc0 `hash_raw_data_slice`: 16-word blocks chained from the IV, the last partial block zero-filled, no
+//                          length block; the words are the 32-bit words the buffers hold (Montgomery form); n = 0 gives the IV
+//   Sha256Rng              pool0 = SHA-256("Hello"), pool1 = SHA-256("World") (padded hashes, as digests); mix(d): pool0 ^= d, step;
+//                          step: pool0 = hash_pair(pool0, pool1), pool1 = hash_pair(pool0, pool1), pool_used = 0; random_u32 steps
+//                          when the eight words of pool0 are used up; bits(b) = random_u32 & (2^b - 1); a field element folds six
+//                          draws: val = ((val << 32) + next) mod p
+#include "internal.hpp"
+#include "receipt_types.hpp"
+
+namespace r0h {
+namespace {
+
+const uint32_t SHA_K[64] = {
+    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,
+    0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa,
+    0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85,
+    0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3,
+    0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f,
+    0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+const uint32_t SHA_IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+
+inline uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+inline uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
+
+// one compression: `st` in the hash's own word order, `in` sixteen input words (byte-swapped into message words here)
+void sha_compress(uint32_t st[8], const uint32_t* in) {
+  uint32_t w[64];
+  for (int i = 0; i < 16; i++) w[i] = bswap(in[i]);
+  for (int i = 16; i < 64; i++) {
+    const uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
+    w[i] = w[i - 16] + s0 + w[i - 7] + s1;
+  }
+  uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+  for (int i = 0; i < 64; i++) {
+    const uint32_t t1 = h + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + SHA_K[i] + w[i];
+    const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
+    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+  }
+  st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+}
+
+struct P2Rng : SuiteRng {
+  const P2Consts* k;
+  uint32_t cells[P2_CELLS];
+  uint32_t pool_used = 0;
+  explicit P2Rng(const P2Consts* kk) : k(kk) { memset(cells, 0, sizeof cells); }
+  void mix(const uint32_t digest[8]) override {
+    if (pool_used != 0) { p2_mix_host(*k, cells); pool_used = 0; }
+    for (int i = 0; i < 8; i++) cells[i] = add(cells[i], digest[i]);  // digests come from the device or the host sponge: canonical
+    p2_mix_host(*k, cells);
+  }
+  uint32_t elem() override {
+    if (pool_used == P2_RATE) { p2_mix_host(*k, cells); pool_used = 0; }
+    return cells[pool_used++];
+  }
+  uint32_t bits(uint32_t n) override {
+    uint32_t val = dec(elem());
+    for (int i = 0; i < 3; i++) { uint32_t nv = dec(elem()); if (val == 0) val = nv; }
+    return val & (uint32_t)(((uint64_t)1 << n) - 1);
+  }
+};
+struct P2Suite : HashSuite {
+  const P2Consts* k;
+  explicit P2Suite(const P2Consts* kk) : k(kk) {}
+  int fn() const override { return HASH_POSEIDON2; }
+  void hash_pair(const uint32_t* left, const uint32_t* right, uint32_t* out) const override {
+    uint32_t st[P2_CELLS] = {0};
+    memcpy(st, left, 32);
+    memcpy(st + 8, right, 32);
+    p2_mix_host(*k, st);
+    memcpy(out, st, 32);
+  }
+  void hash_elems(const uint32_t* words, size_t n, uint32_t digest[8]) const override { p2_hash_elems_host(*k, words, n, digest); }
+  bool digests_are_elems() const override { return true; }
+  std::unique_ptr<SuiteRng> rng() const override { return std::unique_ptr<SuiteRng>(new P2Rng(k)); }
+};
+
+struct ShaRng : SuiteRng {
+  uint32_t pool0[8], pool1[8];
+  uint32_t pool_used = 0;
+  ShaRng() {
+    sha256("Hello", 5, (uint8_t*)pool0);
+    sha256("World", 5, (uint8_t*)pool1);
+  }
+  void step() {
+    sha_hash_pair_host(pool0, pool1, pool0);
+    sha_hash_pair_host(pool0, pool1, pool1);
+    pool_used = 0;
+  }
+  uint32_t random_u32() {
+    if (pool_used == 8) step();
+    return pool0[pool_used++];
+  }
+  void mix(const uint32_t digest[8]) override {
+    for (int i = 0; i < 8; i++) pool0[i] ^= digest[i];
+    step();
+  }
+  uint32_t elem() override {
+    uint64_t val = 0;
+    for (int i = 0; i < 6; i++) val = ((val << 32) + random_u32()) % P;
+    return enc((uint32_t)val);
+  }
+  uint32_t bits(uint32_t n) override { return random_u32() & (uint32_t)(((uint64_t)1 << n) - 1); }
+};
+struct ShaSuite : HashSuite {
+  int fn() const override { return HASH_SHA256; }
+  void hash_pair(const uint32_t* left, const uint32_t* right, uint32_t* out) const override { sha_hash_pair_host(left, right, out); }
+  void hash_elems(const uint32_t* words, size_t n, uint32_t digest[8]) const override { sha_hash_elems_host(words, n, digest); }
+  bool digests_are_elems() const override { return false; }
+  std::unique_ptr<SuiteRng> rng() const override { return std::unique_ptr<SuiteRng>(new ShaRng()); }
+};
+
+}  // namespace
+
+void sha_hash_pair_host(const uint32_t* left, const uint32_t* right, uint32_t* out) {
+  uint32_t st[8], in[16];
+  memcpy(st, SHA_IV, 32);
+  memcpy(in, left, 32);
+  memcpy(in + 8, right, 32);
+  sha_compress(st, in);
+  for (int i = 0; i < 8; i++) out[i] = bswap(st[i]);
+}
+void sha_hash_elems_host(const uint32_t* words, size_t n, uint32_t digest[8]) {
+  uint32_t st[8];
+  memcpy(st, SHA_IV, 32);
+  size_t i = 0;
+  for (; i + 16 <= n; i += 16) sha_compress(st, words + i);
+  if (i < n) {
+    uint32_t in[16] = {0};
+    memcpy(in, words + i, (n - i) * 4);
+    sha_compress(st, in);
+  }
+  for (int j = 0; j < 8; j++) digest[j] = bswap(st[j]);
+}
+
+const char* hashfn_name(int fn) { return fn == HASH_SHA256 ? "sha-256" : "poseidon2"; }
+const char* hashfn_parse(const char* caller, const char* name, int* fn_out) {
+  R0H_REQUIRE(name, "%s: the hash function's name is NULL", caller);
+  if (!strcmp(name, "poseidon2")) *fn_out = HASH_POSEIDON2;
+  else if (!strcmp(name, "sha-256")) *fn_out = HASH_SHA256;
+  else return make_error("%s: unknown hash function \"%.32s\" (\"poseidon2\" and \"sha-256\" are the suites)", caller, name);
+  return nullptr;
+}
+std::unique_ptr<HashSuite> make_suite(int fn, const P2Consts* k) {
+  if (fn == HASH_SHA256) return std::unique_ptr<HashSuite>(new ShaSuite());
+  return std::unique_ptr<HashSuite>(new P2Suite(k));
+}
+const char* require_poseidon2(const r0h_ctx* ctx, const char* caller) {
+  R0H_REQUIRE(ctx && ctx->hashfn == HASH_POSEIDON2,
+              "%s: the context's hash suite is %s; receipts, sessions, image proofs and recursion nodes are poseidon2 only "
+              "(r0h_ctx_set_hashfn(ctx, \"poseidon2\"))", caller, ctx ? hashfn_name(ctx->hashfn) : "unset (NULL context)");
+  return nullptr;
+}
+
+}  // namespace r0h
+
+using namespace r0h;
+
+extern "C" {
+
+const char* r0h_ctx_set_hashfn(r0h_ctx* ctx, const char* name) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_hashfn: NULL argument");
+  int fn = 0;
+  R0H_TRY(hashfn_parse("r0h_ctx_set_hashfn", name, &fn));
+  ctx->hashfn = fn;
+  return nullptr;
+}
+const char* r0h_ctx_hashfn(const r0h_ctx* ctx) { return ctx ? hashfn_name(ctx->hashfn) : "poseidon2"; }
+
+const char* r0h_hash_pair_host(const char* hashfn, const uint32_t a[8], const uint32_t b[8], uint32_t out[8]) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(a && b && out, "r0h_hash_pair_host: NULL argument");
+  int fn = 0;
+  R0H_TRY(hashfn_parse("r0h_hash_pair_host", hashfn, &fn));
+  std::unique_ptr<P2Consts> k;
+  if (fn == HASH_POSEIDON2) {
+    for (int i = 0; i < 8; i++) R0H_REQUIRE(a[i] < P && b[i] < P, "r0h_hash_pair_host: word %d is not a canonical field element", i);
+    k.reset(new P2Consts);
+    p2_default_host(*k);
+  }
+  make_suite(fn, k.get())->hash_pair(a, b, out);
+  return nullptr;
+  R0H_GUARD_END
+}
+
+const char* r0h_hash_elems_host(const char* hashfn, const uint32_t* words, size_t n, uint32_t out[8]) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE((words || n == 0) && out, "r0h_hash_elems_host: NULL argument");
+  int fn = 0;
+  R0H_TRY(hashfn_parse("r0h_hash_elems_host", hashfn, &fn));
+  std::unique_ptr<P2Consts> k;
+  if (fn == HASH_POSEIDON2) {
+    for (size_t i = 0; i < n; i++) R0H_REQUIRE(words[i] < P, "r0h_hash_elems_host: word %zu is not a canonical field element", i);
+    k.reset(new P2Consts);
+    p2_default_host(*k);
+  }
+  make_suite(fn, k.get())->hash_elems(words, n, out);
+  return nullptr;
+  R0H_GUARD_END
+}
+
+}  // extern "C"

@@ -99,6 +99,7 @@ struct r0h_ctx {
   uint32_t* pow3_top = nullptr; // 3^(i*2^22), i < 16 (exponents up to 2^26)
   r0h::P2Consts* p2 = nullptr;  // device
   r0h::P2Consts p2_host;
+  int hashfn = 0;               // r0h::HashFn: the suite hash_rows / hash_fold / the sequencer follow (r0h_ctx_set_hashfn)
   void* scratch = nullptr;      // small device scratch for scans / partial sums
   size_t scratch_bytes = 0;
   void* pinned = nullptr;       // pinned host staging ring for small parameter uploads
@@ -200,4 +201,38 @@ void fill_p2(P2Consts& k, const uint32_t* rc, const uint32_t* diag_m1);
 void p2_default_host(P2Consts& k);
 void p2_hash_elems_host(const P2Consts& k, const uint32_t* elems, size_t n, uint32_t digest[8]);
 void p2_sponge_rows_host(const P2Consts& k, const uint32_t* words, size_t n_words, uint32_t* cols, size_t stride, size_t* rows_used);
+
+// ---- hash suites (risc0 `HashSuite`: the Merkle hash and the transcript's generator go together).  Two of them: Poseidon2 over
+// BabyBear words, and SHA-256 as recalled from risc0-zkp core/hash/sha (`Sha256HashSuite`, `Sha256Rng`) and risc0-sys sha256.h --
+// unpinned like everything risc0-specific here (the reference vendors neither); tests/sha_suite_ref.py is this repository's norm.
+enum HashFn { HASH_POSEIDON2 = 0, HASH_SHA256 = 1 };
+const char* hashfn_name(int fn);                                   // "poseidon2" / "sha-256"
+const char* hashfn_parse(const char* caller, const char* name, int* fn_out);  // any other name is an error
+// the transcript's generator: what WriteIop (prover.hip) and SealReader (verify.cpp) draw their challenges from
+struct SuiteRng {
+  virtual ~SuiteRng() {}
+  virtual void mix(const uint32_t digest[8]) = 0;
+  virtual uint32_t elem() = 0;            // a field element, Montgomery form
+  virtual uint32_t bits(uint32_t n) = 0;  // an n-bit query index
+  Fp4 ext() { Fp4 r; for (int i = 0; i < 4; i++) r.e[i] = elem(); return r; }
+};
+// the host side of a suite: hashing of pairs and of word slices (what the device kernels of the suite compute per node / per row)
+struct HashSuite {
+  virtual ~HashSuite() {}
+  virtual int fn() const = 0;
+  virtual void hash_pair(const uint32_t* left, const uint32_t* right, uint32_t* out) const = 0;
+  virtual void hash_elems(const uint32_t* words, size_t n, uint32_t digest[8]) const = 0;
+  virtual bool digests_are_elems() const = 0;  // Poseidon2: every digest word is a field element; SHA-256: any 32-bit value
+  virtual std::unique_ptr<SuiteRng> rng() const = 0;
+};
+// `k` is read by the Poseidon2 suite only and must outlive it (a context's table, or the caller's)
+std::unique_ptr<HashSuite> make_suite(int fn, const P2Consts* k);
+// SHA-256 suite on the host (hash_suite.cpp): digests are 8 words whose bytes in memory are the standard big-endian SHA-256 bytes
+void sha_hash_pair_host(const uint32_t* left, const uint32_t* right, uint32_t* out);
+void sha_hash_elems_host(const uint32_t* words, size_t n, uint32_t digest[8]);
+// ... and on the device (sha256.hip): what r0h_hash_rows / r0h_hash_fold run on a context whose suite is SHA-256 (arguments checked by the callers)
+const char* sha256_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix, uint32_t rows, uint32_t cols);
+const char* sha256_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size);
+// receipts, sessions, image proofs and recursion nodes name Poseidon2 only: their entry points refuse a context on another suite
+const char* require_poseidon2(const r0h_ctx* ctx, const char* caller);
 }  // namespace r0h

@@ -111,6 +111,7 @@ const char* r0h_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix,
   R0H_REQUIRE((size_t)rows * 32 <= digests->bytes, "r0h_hash_rows: %u digests exceed the output buffer", rows);
   R0H_REQUIRE(((uintptr_t)digests->ptr & 15) == 0, "r0h_hash_rows: digest buffer must be 16-byte aligned");
   if (!rows) return nullptr;
+  if (ctx->hashfn == HASH_SHA256) return sha256_hash_rows(ctx, digests, matrix, rows, cols);  // the context's suite (r0h_ctx_set_hashfn)
   KScope ks(ctx, "hash_rows_kernel", (double)rows * cols * 4 + (double)rows * 32);
   hipLaunchKernelGGL(hash_rows_kernel, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, u32(digests), u32(matrix), rows, cols, ctx->p2);
   return launch_ok("hash_rows_kernel");
@@ -123,6 +124,7 @@ const char* r0h_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size) {
   R0H_REQUIRE((size_t)output_size * 4 * 32 <= nodes->bytes, "r0h_hash_fold: output_size %u needs %zu bytes of nodes", output_size, (size_t)output_size * 128);
   R0H_REQUIRE(((uintptr_t)nodes->ptr & 15) == 0, "r0h_hash_fold: node buffer must be 16-byte aligned");
   if (!output_size) return nullptr;
+  if (ctx->hashfn == HASH_SHA256) return sha256_hash_fold(ctx, nodes, output_size);
   KScope ks(ctx, "hash_fold_kernel", (double)output_size * 96);
   if (output_size <= 8192) {  // fewer parents than the chip has SIMD slots (measured up to 8 K: 1.47 vs 1.52 ms per tree) (32x the instructions per permutation, ~7x less latency): spread each permutation over 24 lanes (latency, not throughput)
     hipLaunchKernelGGL(hash_fold_lanes_kernel, dim3((output_size * 32 + 255) / 256), dim3(256), 0, ctx->stream, u32(nodes), output_size, ctx->p2);

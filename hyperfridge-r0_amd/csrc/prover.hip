@@ -1,7 +1,7 @@
 // The segment-proof sequencer: owns the Fiat-Shamir transcript on the host and drives the device operations.
 // Replaces risc0-circuit-rv32im 4.0.4 prove/hal/mod.rs (`SegmentProver::prove`: seed transcript, commit CODE and DATA,
 // draw the accumulation mix, accumulate, finalize) and risc0-zkp 3.0.4 prove/{prover.rs, poly_group.rs, merkle.rs,
-// fri.rs, write_iop.rs} + core/hash/poseidon2/rng.rs -- SURVEY.md 3.4 steps 3-13, 8(a) a8, a15-a17.
+// fri.rs, write_iop.rs} + core/hash/{poseidon2,sha}/rng.rs behind the suite interface of hash_suite.cpp -- SURVEY.md 3.4 steps 3-13, 8(a) a8, a15-a17.
 // This is what host/src/main.rs:423 (`prover.prove(env, HYPERFRIDGE_ELF)`) spends its time in, once per segment.
 //
 // Device-resident throughout: witness, coefficients, evaluations, Merkle nodes, combos.  What crosses to the host per
@@ -40,33 +40,21 @@ static void circuit_view(const r0h_circuit* c, CircuitView* v) {
 static unsigned log2u(size_t x) { unsigned n = 0; while (((size_t)1 << n) < x) n++; return n; }
 
 // ------------------------------------------------------------------ transcript
-struct Rng {
-  const P2Consts* k;
-  uint32_t cells[P2_CELLS];
-  uint32_t pool_used;
-  explicit Rng(const P2Consts* kk) : k(kk), pool_used(0) { memset(cells, 0, sizeof cells); }
-  void mix(const uint32_t digest[8]) {
-    if (pool_used != 0) { p2_mix_host(*k, cells); pool_used = 0; }
-    for (int i = 0; i < 8; i++) cells[i] = add(cells[i], digest[i]);  // digests come from the device or the host sponge: canonical
-    p2_mix_host(*k, cells);
-  }
-  uint32_t elem() {
-    if (pool_used == P2_RATE) { p2_mix_host(*k, cells); pool_used = 0; }
-    return cells[pool_used++];
-  }
-  Fp4 ext() { Fp4 r; for (int i = 0; i < 4; i++) r.e[i] = elem(); return r; }
-  uint32_t bits(uint32_t n) {
-    uint32_t val = dec(elem());
-    for (int i = 0; i < 3; i++) { uint32_t nv = dec(elem()); if (val == 0) val = nv; }
-    return val & (uint32_t)(((uint64_t)1 << n) - 1);
-  }
-};
+// The generator and the slice hash are the context's hash suite (internal.hpp HashSuite: Poseidon2 or SHA-256); the order of
+// commits, writes and draws below is the same under both.
 struct WriteIop {
   std::vector<uint32_t> proof;
-  Rng rng;
-  explicit WriteIop(const P2Consts* k) : rng(k) {}
+  std::unique_ptr<HashSuite> suite;
+  std::unique_ptr<SuiteRng> rng_;
+  SuiteRng& rng;
+  WriteIop(int hashfn, const P2Consts* k) : suite(make_suite(hashfn, k)), rng_(suite->rng()), rng(*rng_) {}
   void write(const uint32_t* w, size_t n) { proof.insert(proof.end(), w, w + n); }
   void commit(const uint32_t digest[8]) { rng.mix(digest); }
+  void commit_elems(const uint32_t* w, size_t n) {  // the suite's hash_elem_slice over words the seal carries (or a tag), then commit
+    uint32_t d[8];
+    suite->hash_elems(w, n, d);
+    commit(d);
+  }
 };
 
 // ------------------------------------------------------------------ Merkle
@@ -220,6 +208,7 @@ __global__ void sub_head_kernel(uint32_t* __restrict__ combos, const uint32_t* _
 struct r0h_code_commit {
   r0h_ctx* ctx = nullptr;
   uint32_t count = 0, po2 = 0;
+  int hashfn = 0;  // the suite the tree was hashed under (the context's when it was made): a proof under another suite refuses it
   r0h_buf *coeffs = nullptr, *evaluated = nullptr, *nodes = nullptr;
   r0h_buf* witness = nullptr;  // the CODE columns themselves (a log-derivative accumulation reads its tables from them); may be absent
   std::vector<uint32_t> top;  // the top layer as tree_commit writes it to the seal
@@ -241,7 +230,7 @@ struct r0h_proof {
   uint32_t data_root[8] = {0};  // the DATA group's Merkle root (what a session's common challenge is derived from)
   bool mix_drawn = false;
   r0h_proof(r0h_ctx* c, const r0h_circuit* ci, uint32_t p, const r0h::CircuitView& v)
-      : ctx(c), circ(ci), po2(p), cv(v), io(&c->p2_host), g_accum(v.group_size[R0H_GROUP_ACCUM], (size_t)4 << p),
+      : ctx(c), circ(ci), po2(p), cv(v), io(c->hashfn, &c->p2_host), g_accum(v.group_size[R0H_GROUP_ACCUM], (size_t)4 << p),
         g_code(v.group_size[R0H_GROUP_CODE], (size_t)4 << p), g_data(v.group_size[R0H_GROUP_DATA], (size_t)4 << p),
         g_check(R0H_CHECK_SIZE, (size_t)4 << p) {}
 };
@@ -265,21 +254,18 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* code, const r0h_cod
     // risc0-circuit-rv32im prove/hal: the hashes of two 16-byte ProtocolInfo tags (one field element per byte) open the
     // transcript: the proof system's and the circuit's
     static const char proof_system_info[] = "RISC0_STARK:v1__";
-    uint32_t e[16], d[8];
+    uint32_t e[16];
     for (int i = 0; i < 16; i++) e[i] = enc((uint8_t)proof_system_info[i]);
-    p2_hash_elems_host(ctx->p2_host, e, 16, d);
-    io.commit(d);
+    io.commit_elems(e, 16);
     for (int i = 0; i < 16; i++) e[i] = enc(circ->info[i]);
-    p2_hash_elems_host(ctx->p2_host, e, 16, d);
-    io.commit(d);
+    io.commit_elems(e, 16);
     // the seal opens with every public input and po2; the transcript takes the early ones here and the late ones (inputs that depend
     // on commitments made outside this proof, R0H_SEC_LATE) after the DATA group is committed
     const uint32_t n_early = cv.n_global - circ->n_late;
     std::vector<uint32_t> gv(global, global + n_early);
     for (uint32_t w : gv) R0H_REQUIRE(w < P, "prove_segment: global word not canonical");
     gv.push_back(enc(po2));
-    p2_hash_elems_host(ctx->p2_host, gv.data(), gv.size(), d);
-    io.commit(d);
+    io.commit_elems(gv.data(), gv.size());
     st.seal_globals_at = io.proof.size();
     io.write(global, cv.n_global);
     const uint32_t po2_word = enc(po2);
@@ -290,6 +276,8 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* code, const r0h_cod
   if (cc) {  // committed ahead of time: the group's buffers are the cache's (not this proof's to free), the transcript sees the same words
     R0H_REQUIRE(cc->po2 == po2 && cc->count == g_code.count, "prove_segment: the CODE commitment is for %u columns of 2^%u rows, this proof needs %u of 2^%u",
                 cc->count, cc->po2, g_code.count, po2);
+    R0H_REQUIRE(cc->hashfn == ctx->hashfn, "prove_segment: the CODE commitment was made under the %s hash suite, this context is on %s",
+                hashfn_name(cc->hashfn), hashfn_name(ctx->hashfn));
     R0H_REQUIRE(cc->ctx->device == ctx->device, "prove_segment: the CODE commitment lives on device %d, this context on device %d", cc->ctx->device, ctx->device);
     g_code.coeffs = cc->coeffs;
     g_code.evaluated = cc->evaluated;
@@ -318,9 +306,7 @@ static const char* proof_late(r0h_proof& st, const uint32_t* late) {
     for (uint32_t i = 0; i < n_late; i++) R0H_REQUIRE(late[i] < P, "r0h_proof_late: word %u not canonical", i);
     memcpy(st.global.data() + n_early, late, (size_t)n_late * 4);
     memcpy(st.io.proof.data() + st.seal_globals_at + n_early, late, (size_t)n_late * 4);
-    uint32_t d[8];
-    p2_hash_elems_host(st.ctx->p2_host, late, n_late, d);
-    st.io.commit(d);
+    st.io.commit_elems(late, n_late);
   }
   st.mix.resize(st.cv.n_mix);
   for (uint32_t i = 0; i < st.cv.n_mix; i++) st.mix[i] = st.io.rng.elem();
@@ -332,6 +318,8 @@ static const char* proof_late(r0h_proof& st, const uint32_t* late) {
 static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector<uint32_t>& seal) {
   R0H_REQUIRE(st.mix_drawn, "r0h_proof_finish: this circuit has late public inputs: r0h_proof_late comes first");
   r0h_ctx* ctx = st.ctx;
+  R0H_REQUIRE(st.io.suite->fn() == ctx->hashfn, "r0h_proof_finish: the proof was begun under the %s hash suite, its context is now on %s",
+              hashfn_name(st.io.suite->fn()), hashfn_name(ctx->hashfn));
   const r0h_circuit* circ = st.circ;
   const uint32_t po2 = st.po2;
   const size_t n = (size_t)1 << po2, domain = n * R0H_INV_RATE;
@@ -392,11 +380,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
   }
   for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) coeff_u[cv.n_taps + i] = eval_u[cv.n_taps + i];
   io.write((const uint32_t*)coeff_u.data(), 4 * (size_t)n_u);
-  {
-    uint32_t d[8];
-    p2_hash_elems_host(ctx->p2_host, (const uint32_t*)coeff_u.data(), 4 * (size_t)n_u, d);
-    io.commit(d);
-  }
+  io.commit_elems((const uint32_t*)coeff_u.data(), 4 * (size_t)n_u);
 
   phase(ctx, "mix_combos");
   const Fp4 mixv = io.rng.ext();
@@ -508,9 +492,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
     std::vector<uint32_t> fc(4 * deg);
     R0H_TRY(r0h_buf_d2h(ctx, fri_coeffs, 0, fc.data(), fc.size() * 4));
     io.write(fc.data(), fc.size());
-    uint32_t d[8];
-    p2_hash_elems_host(ctx->p2_host, fc.data(), fc.size(), d);
-    io.commit(d);
+    io.commit_elems(fc.data(), fc.size());
   }
 
   phase(ctx, "queries");
@@ -636,13 +618,13 @@ const char* r0h_code_commit_new(r0h_ctx* ctx, const r0h_buf* code, uint32_t coun
   R0H_REQUIRE(po2 >= 9 && po2 <= R0H_MAX_PO2, "r0h_code_commit_new: po2 %u outside [9, %u]", po2, R0H_MAX_PO2);
   R0H_TRY_HIP(hipSetDevice(ctx->device));
   std::unique_ptr<r0h_code_commit, const char* (*)(r0h_code_commit*)> cc(new r0h_code_commit(), r0h_code_commit_free);
-  cc->ctx = ctx; cc->count = count; cc->po2 = po2;
+  cc->ctx = ctx; cc->count = count; cc->po2 = po2; cc->hashfn = ctx->hashfn;
   ctx_retain(ctx);
   {
     Scope sc;  // the group's buffers are taken out of the scope once everything has succeeded
     Group g(count, (size_t)4 << po2);
     R0H_TRY(group_from_witness(ctx, sc, g, code, po2));
-    WriteIop io(&ctx->p2_host);
+    WriteIop io(ctx->hashfn, &ctx->p2_host);
     R0H_TRY(tree_commit(ctx, g.tree, io));  // blocking read-back: the stream has drained when it returns
     cc->top.swap(io.proof);
     R0H_TRY(r0h_buf_d2h(ctx, g.tree.nodes, 32, cc->root, 32));

@@ -2,8 +2,10 @@
 // witness on the device, prove K segments, print throughput and a digest of the seal.
 // It stands where hyperfridge's `host prove-camt53` stands relative to risc0 (host/src/main.rs:420-423 obtains a prover and
 // calls prove once); everything risc0-specific above the segment prover (executor, receipts) is out of scope.
-//   usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1]
+//   usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--hashfn poseidon2|sha-256]
 //                    [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]
+// --hashfn sha-256 proves (and with --verify 1 checks) the segments under the SHA-256 hash suite; receipts name Poseidon2 only, so it is
+// refused together with any of the receipt options and with --elf.
 // With --receipt-out / --receipt-dir every segment is proved for a claim (risc0-zkvm `ReceiptClaim`): the session's system states
 // are synthetic names (there is no executor here), segment k runs from state k to state k+1, all but the last end in SystemSplit,
 // the last halts with the journal's output; the claim's eight naming words are planted as the segment's public inputs.  The image
@@ -49,11 +51,12 @@ static void die(const char* what, const char* err) {
 
 int main(int argc, char** argv) {
   if (argc < 2 || !strcmp(argv[1], "--help") || !strcmp(argv[1], "-h")) {
-    printf("usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]\n"
+    printf("usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--hashfn poseidon2|sha-256] [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]\n"
            "       r0h_prove <trace.r0c> --elf guest.elf --input words.bin [--code-object file.hsaco] [--po2 N] [--device D] --receipt-out file.json\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   std::string blob_path = argv[1], co_path, seal_out, receipt_out, receipt_dir, journal_text, elf_path, input_path;
+  std::string hashfn = "poseidon2";         // --hashfn: the hash suite of the synthetic-circuit mode (seals only)
   std::map<std::string, std::string> camt;  // --camt53-response and what goes with it
   std::string receipt_prefix;               // --receipt-prefix P: the reference's file name, P-Receipt-<image id>-latest.json (host/src/main.rs:312-316)
   std::string image_circuit_path, image_co_path;
@@ -68,6 +71,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--contexts")) contexts = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--seal-out")) seal_out = argv[i + 1];
     else if (!strcmp(argv[i], "--verify")) verify = (unsigned)atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--hashfn")) hashfn = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
     else if (!strcmp(argv[i], "--journal")) journal_text = argv[i + 1];
@@ -82,6 +86,12 @@ int main(int argc, char** argv) {
              !strcmp(argv[i], "--witness-hex") || !strcmp(argv[i], "--iban") || !strcmp(argv[i], "--hostinfo") || !strcmp(argv[i], "--form"))
       camt[argv[i] + 2] = argv[i + 1];
     else { fprintf(stderr, "r0h_prove: unknown option %s\n", argv[i]); return 1; }
+  }
+  if (hashfn != "poseidon2" && hashfn != "sha-256") { fprintf(stderr, "r0h_prove: --hashfn is poseidon2 or sha-256, not %s\n", hashfn.c_str()); return 1; }
+  if (hashfn != "poseidon2" && (!elf_path.empty() || !receipt_out.empty() || !receipt_dir.empty() || !receipt_prefix.empty() || !camt.empty() || !image_circuit_path.empty())) {
+    fprintf(stderr, "r0h_prove: --hashfn %s proves bare seals (--seal-out / --verify); receipts name poseidon2 only, so it does not go with --elf, --receipt-out, "
+                    "--receipt-dir, --receipt-prefix, --image-circuit or --camt53-response\n", hashfn.c_str());
+    return 1;
   }
   FILE* f = fopen(blob_path.c_str(), "rb");
   if (!f) { fprintf(stderr, "r0h_prove: cannot open %s\n", blob_path.c_str()); return 1; }
@@ -282,6 +292,7 @@ int main(int argc, char** argv) {
   for (unsigned k = 0; k < contexts; k++) {
     Lane& ln = lanes[k];
     CHECK(r0h_ctx_create((int)device, &ln.ctx));
+    CHECK(r0h_ctx_set_hashfn(ln.ctx, hashfn.c_str()));
     CHECK(r0h_circuit_load(ln.ctx, blob.data(), blob.size(), co_path.empty() ? nullptr : co_path.c_str(), &ln.circ));
     CHECK(r0h_buf_alloc(ln.ctx, (size_t)r0h_circuit_group_size(ln.circ, R0H_GROUP_CODE) * n * 4, &ln.code));
     CHECK(r0h_buf_alloc(ln.ctx, (size_t)r0h_circuit_group_size(ln.circ, R0H_GROUP_DATA) * n * 4, &ln.data));
@@ -365,7 +376,7 @@ int main(int argc, char** argv) {
     for (const Lane& ln : lanes) {
       if (!ln.proved) continue;
       int verdict = -1;
-      CHECK(r0h_verify_seal(blob.data(), blob.size(), nullptr, nullptr, ln.seal.data(), ln.words, &verdict, nullptr));
+      CHECK(r0h_verify_seal_hashfn(blob.data(), blob.size(), hashfn.c_str(), ln.seal.data(), ln.words, nullptr, &verdict, nullptr, nullptr));
       if (verdict != R0H_VERIFY_OK) { fprintf(stderr, "r0h_prove: the verifier rejects the seal: %s\n", r0h_verify_reason(verdict)); return 3; }
     }
     fprintf(stderr, "r0h_prove: seals verified\n");

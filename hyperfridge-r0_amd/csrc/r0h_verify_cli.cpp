@@ -1,7 +1,7 @@
 // r0h_verify: check a seal file against a circuit blob on the host -- the compiled counterpart of the reference's
 // `verifier verify` step (verifier/src/main.rs:118-126: read the receipt, `receipt.verify(image_id)`, report).
 // Needs no GPU.  Exit status: 0 accepted, 1 rejected (reason on stdout), 2 unusable input.
-//   usage: r0h_verify <circuit.r0c> <seal.bin>
+//   usage: r0h_verify <circuit.r0c> <seal.bin> [--hashfn poseidon2|sha-256]   (the hash suite the bare seal was made under; receipts name poseidon2)
 //          r0h_verify --receipt <receipt.json> <circuit.r0c> --image-id <64 hex> --control-root <po2>:<w0,..,w7> [--control-root ..]
 //          r0h_verify --receipt <receipt.json> <circuit.r0c> --image-id <64 hex> --image-circuit <image.r0c>   a trace-circuit receipt that carries
 //                     an image proof, checked with the 32 bytes of the image id alone (r0h_receipt_verify_image) -- the reference's call
@@ -186,8 +186,10 @@ int main(int argc, char** argv) {
     }
     return verify_receipt(argv[2], argv[3], image_hex, roots, elf_path, image_circuit_path);
   }
+  const char* hashfn = "poseidon2";
+  if (argc == 5 && !strcmp(argv[3], "--hashfn")) { hashfn = argv[4]; argc = 3; }
   if (argc != 3) {
-    printf("usage: r0h_verify <circuit.r0c> <seal.bin>\n       r0h_verify --receipt <receipt.json> <circuit.r0c> --image-id <64 hex> --control-root <po2>:<w0,..,w7>\n%s\n", r0h_version());
+    printf("usage: r0h_verify <circuit.r0c> <seal.bin> [--hashfn poseidon2|sha-256]\n       r0h_verify --receipt <receipt.json> <circuit.r0c> --image-id <64 hex> --control-root <po2>:<w0,..,w7>\n%s\n", r0h_version());
     return 2;
   }
   std::vector<uint32_t> blob, seal;
@@ -195,7 +197,7 @@ int main(int argc, char** argv) {
   if (!read_words(argv[2], &seal)) { fprintf(stderr, "r0h_verify: cannot read %s as 32-bit words\n", argv[2]); return 2; }
   int verdict = -1;
   uint32_t po2 = 0;
-  const char* err = r0h_verify_seal(blob.data(), blob.size(), nullptr, nullptr, seal.data(), seal.size(), &verdict, &po2);
+  const char* err = r0h_verify_seal_hashfn(blob.data(), blob.size(), hashfn, seal.data(), seal.size(), nullptr, &verdict, &po2, nullptr);
   if (err) {
     fprintf(stderr, "r0h_verify: %s\n", err);
     r0h_free_error(err);

@@ -102,6 +102,7 @@ const char* r0h_recursor_new(r0h_ctx* ctx, const uint32_t* recursion_blob, size_
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && recursion_blob && segment_blob && out && (segment_control_roots || !n_roots), "r0h_recursor_new: NULL argument");
   R0H_REQUIRE(po2 >= 9 && po2 <= R0H_MAX_PO2, "r0h_recursor_new: po2 %u outside [9, %u]", po2, R0H_MAX_PO2);
+  R0H_TRY(require_poseidon2(ctx, "r0h_recursor_new"));
   std::unique_ptr<r0h_recursor, const char* (*)(r0h_recursor*)> rc(new r0h_recursor(), r0h_recursor_free);
   rc->ctx = ctx; rc->po2 = po2;
   ctx_retain(ctx);
@@ -148,6 +149,7 @@ const char* r0h_recursor_control_root(const r0h_recursor* rc, uint32_t root_out[
 const char* r0h_lift(r0h_recursor* rc, const uint32_t* seal, size_t seal_words, const r0h_receipt_claim* claim, r0h_node** out) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(rc && seal && claim && out, "r0h_lift: NULL argument");
+  R0H_TRY(require_poseidon2(rc->ctx, "r0h_lift"));
   r0h_circuit seg;
   R0H_TRY(parse_blob(&seg, rc->segment_blob.data(), rc->segment_blob.size()));
   R0H_REQUIRE(seal_words > (size_t)seg.n_global && seal[seg.n_global] < P, "r0h_lift: the segment seal is truncated");
@@ -178,6 +180,7 @@ const char* r0h_lift(r0h_recursor* rc, const uint32_t* seal, size_t seal_words, 
 const char* r0h_join(r0h_recursor* rc, const r0h_node* a, const r0h_node* b, r0h_node** out) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(rc && a && b && out, "r0h_join: NULL argument");
+  R0H_TRY(require_poseidon2(rc->ctx, "r0h_join"));
   // risc0 `ReceiptClaim::join`: a must stop in a system split exactly where b starts.  One more case here: b is a node of closing rows
   // only (the trace circuit's session may end in segments without cycles: pre == post, SystemSplit, no output) -- it follows whatever
   // a ends in, the run's last segment included, and the composed claim ends the way a does

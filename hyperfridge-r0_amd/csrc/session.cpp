@@ -489,6 +489,7 @@ const char* r0h_session_begin(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t*
                               uint64_t max_cycles, uint32_t part, uint32_t parts, r0h_session** session_out) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && c && elf && session_out && (input_words || !n_input), "r0h_prove_elf: NULL argument");
+  R0H_TRY(require_poseidon2(ctx, "r0h_prove_elf / r0h_session_begin"));
   R0H_REQUIRE(parts >= 1 && part < parts, "r0h_prove_elf_part: part %u of %u", part, parts);
   const bool trace_mode = !memcmp(c->info, "R0HIP_TRACE:v5__", 16);
   // (a trace-circuit segment of fewer than 2^16 rows is proved at 2^16: the lookup tables' size)

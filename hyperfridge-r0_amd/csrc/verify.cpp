@@ -29,9 +29,11 @@ struct Cursor {
   }
 };
 
+// The transcript and every hash go through the seal's hash suite (internal.hpp HashSuite).  Under SHA-256 a digest word is any 32-bit
+// value, so "word < P" is asked of field-element positions only; under Poseidon2 it is asked of digests too, as before.
 class SealReader {
  public:
-  SealReader(const P2Consts& k, const uint32_t* w, size_t n) : k_(k), w_(w), n_(n) { memset(cells_, 0, sizeof cells_); }
+  SealReader(const HashSuite& suite, const uint32_t* w, size_t n) : suite_(suite), rng_(suite.rng()), w_(w), n_(n) {}
   const uint32_t* take(size_t n) {
     if (n > n_ - pos_) throw Reject{R0H_VERIFY_TRUNCATED};
     const uint32_t* p = w_ + pos_;
@@ -44,48 +46,29 @@ class SealReader {
       if (p[i] >= P) throw Reject{R0H_VERIFY_BAD_ELEM};
     return p;
   }
+  const uint32_t* take_digests(size_t n) { return suite_.digests_are_elems() ? take_elems(8 * n) : take(8 * n); }
   bool exhausted() const { return pos_ == n_; }
   Cursor cursor() const { return Cursor{w_, n_, pos_}; }
   void skip_to(size_t pos) { pos_ = pos < n_ ? pos : n_; }
-  void commit(const uint32_t digest[8]) {
-    if (used_ != 0) { p2_mix_host(k_, cells_); used_ = 0; }
-    for (int i = 0; i < 8; i++) cells_[i] = add(cells_[i], digest[i]);  // canonical: every digest is checked when it is read
-    p2_mix_host(k_, cells_);
-  }
+  void commit(const uint32_t digest[8]) { rng_->mix(digest); }  // (Poseidon2: canonical, every digest is checked when it is read)
   void commit_elems(const uint32_t* e, size_t n) {
     uint32_t d[8];
-    p2_hash_elems_host(k_, e, n, d);
+    suite_.hash_elems(e, n, d);
     commit(d);
   }
-  uint32_t elem() {
-    if (used_ == P2_RATE) { p2_mix_host(k_, cells_); used_ = 0; }
-    return cells_[used_++];
-  }
-  Fp4 ext() { Fp4 r; for (int i = 0; i < 4; i++) r.e[i] = elem(); return r; }
-  uint32_t bits(uint32_t n) {
-    uint32_t v = dec(elem());
-    for (int i = 0; i < 3; i++) { uint32_t nv = dec(elem()); if (v == 0) v = nv; }
-    return v & (uint32_t)(((uint64_t)1 << n) - 1);
-  }
-  const P2Consts& consts() const { return k_; }
+  uint32_t elem() { return rng_->elem(); }
+  Fp4 ext() { return rng_->ext(); }
+  uint32_t bits(uint32_t n) { return rng_->bits(n); }
+  const HashSuite& suite() const { return suite_; }
 
  private:
-  const P2Consts& k_;
+  const HashSuite& suite_;
+  std::unique_ptr<SuiteRng> rng_;
   const uint32_t* w_;
   size_t n_, pos_ = 0;
-  uint32_t cells_[P2_CELLS];
-  uint32_t used_ = 0;
 };
 
 unsigned log2_exact(size_t x) { unsigned n = 0; while (((size_t)1 << n) < x) n++; return n; }
-
-void hash_pair(const P2Consts& k, const uint32_t* left, const uint32_t* right, uint32_t* out) {
-  uint32_t st[P2_CELLS] = {0};
-  memcpy(st, left, 32);
-  memcpy(st + 8, right, 32);
-  p2_mix_host(k, st);
-  memcpy(out, st, 32);
-}
 
 // The verifier's view of one committed matrix: the elided top layer (read from the seal) folded down to the root.
 class TreeVerifier {
@@ -99,25 +82,25 @@ class TreeVerifier {
     }
     top_size_ = (size_t)1 << top_layer;
     top_.assign(2 * top_size_ * 8, 0);
-    memcpy(&top_[top_size_ * 8], io.take_elems(top_size_ * 8), top_size_ * 32);  // digest words are field elements
-    for (size_t i = top_size_; i-- > 1;) hash_pair(io.consts(), &top_[2 * i * 8], &top_[(2 * i + 1) * 8], &top_[i * 8]);
+    memcpy(&top_[top_size_ * 8], io.take_digests(top_size_), top_size_ * 32);  // Poseidon2: digest words are field elements
+    for (size_t i = top_size_; i-- > 1;) io.suite().hash_pair(&top_[2 * i * 8], &top_[(2 * i + 1) * 8], &top_[i * 8]);
     io.commit(&top_[8]);
   }
   // the opened row (cols_ canonical words) if its path leads to the committed top layer
-  const uint32_t* open(Cursor& io, const P2Consts& k, size_t row) const {
+  const uint32_t* open(Cursor& io, const HashSuite& k, size_t row) const {
     if (row >= rows_) throw Reject{reject_};
     const uint32_t* values = io.take(cols_);
     for (size_t i = 0; i < cols_; i++)
       if (values[i] >= P) throw Reject{reject_};
     uint32_t cur[8];
-    p2_hash_elems_host(k, values, cols_, cur);
+    k.hash_elems(values, cols_, cur);
     size_t node = row + rows_;
     for (; node >= 2 * top_size_; node >>= 1) {
       const uint32_t* sibling = io.take(8);
-      for (int i = 0; i < 8; i++)
+      for (int i = 0; i < 8 && k.digests_are_elems(); i++)
         if (sibling[i] >= P) throw Reject{R0H_VERIFY_BAD_ELEM};  // two word sequences must not name one digest
       uint32_t parent[8];
-      if (node & 1) hash_pair(k, sibling, cur, parent); else hash_pair(k, cur, sibling, parent);
+      if (node & 1) k.hash_pair(sibling, cur, parent); else k.hash_pair(cur, sibling, parent);
       memcpy(cur, parent, 32);
     }
     if (memcmp(&top_[node * 8], cur, 32) != 0) throw Reject{reject_};
@@ -164,7 +147,7 @@ Fp4 constraint_at_z(const r0h_circuit& c, const Fp4& poly_mix, const std::vector
   return mx[c.ret].tot;
 }
 
-void verify(const r0h_circuit& c, const P2Consts& k, const uint32_t* seal, size_t seal_words, uint32_t* po2_out, const uint32_t* expected_code_root,
+void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size_t seal_words, uint32_t* po2_out, const uint32_t* expected_code_root,
             uint32_t* code_root_out, uint32_t* data_root_out = nullptr) {
   SealReader io(k, seal, seal_words);
   {
@@ -413,13 +396,13 @@ const char* r0h_sponge_trace(const uint32_t* words, size_t n_words, uint32_t po2
   R0H_GUARD_END
 }
 
-static const char* verify_entry(const uint32_t* blob, size_t blob_words, const uint32_t* p2_round_constants, const uint32_t* p2_diag_m1,
+static const char* verify_entry(int hashfn, const uint32_t* blob, size_t blob_words, const uint32_t* p2_round_constants, const uint32_t* p2_diag_m1,
                                 const uint32_t* seal, size_t seal_words, const uint32_t* expected_code_root, int* verdict_out, uint32_t* po2_out,
                                 uint32_t* code_root_out, uint32_t* data_root_out = nullptr) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(blob && (seal || seal_words == 0) && verdict_out, "r0h_verify_seal: NULL argument");
   R0H_REQUIRE((p2_round_constants == nullptr) == (p2_diag_m1 == nullptr), "r0h_verify_seal: pass both Poseidon2 tables or neither");
-  if (expected_code_root)
+  if (expected_code_root && hashfn == HASH_POSEIDON2)
     for (int i = 0; i < 8; i++) R0H_REQUIRE(expected_code_root[i] < P, "r0h_verify_seal: expected code root word %d not canonical", i);
   r0h_circuit c;
   R0H_TRY(parse_blob(&c, blob, blob_words));
@@ -434,7 +417,7 @@ static const char* verify_entry(const uint32_t* blob, size_t blob_words, const u
   if (po2_out) *po2_out = 0;
   if (code_root_out) memset(code_root_out, 0, 32);
   try {
-    verify(c, *k, seal, seal_words, po2_out, expected_code_root, code_root_out, data_root_out);
+    verify(c, *make_suite(hashfn, k.get()), seal, seal_words, po2_out, expected_code_root, code_root_out, data_root_out);
     *verdict_out = R0H_VERIFY_OK;
   } catch (const Reject& r) {
     *verdict_out = r.code;
@@ -445,13 +428,21 @@ static const char* verify_entry(const uint32_t* blob, size_t blob_words, const u
 
 const char* r0h_verify_seal(const uint32_t* blob, size_t blob_words, const uint32_t* p2_round_constants, const uint32_t* p2_diag_m1,
                             const uint32_t* seal, size_t seal_words, int* verdict_out, uint32_t* po2_out) {
-  return verify_entry(blob, blob_words, p2_round_constants, p2_diag_m1, seal, seal_words, nullptr, verdict_out, po2_out, nullptr);
+  return verify_entry(HASH_POSEIDON2, blob, blob_words, p2_round_constants, p2_diag_m1, seal, seal_words, nullptr, verdict_out, po2_out, nullptr);
 }
 
 const char* r0h_verify_seal_bound(const uint32_t* blob, size_t blob_words, const uint32_t* p2_round_constants, const uint32_t* p2_diag_m1,
                                   const uint32_t* seal, size_t seal_words, const uint32_t* expected_code_root, int* verdict_out,
                                   uint32_t* po2_out, uint32_t* code_root_out) {
-  return verify_entry(blob, blob_words, p2_round_constants, p2_diag_m1, seal, seal_words, expected_code_root, verdict_out, po2_out, code_root_out);
+  return verify_entry(HASH_POSEIDON2, blob, blob_words, p2_round_constants, p2_diag_m1, seal, seal_words, expected_code_root, verdict_out, po2_out, code_root_out);
+}
+
+// the same check of a seal made under the named hash suite ("poseidon2": the compiled-in table; "sha-256")
+const char* r0h_verify_seal_hashfn(const uint32_t* blob, size_t blob_words, const char* hashfn, const uint32_t* seal, size_t seal_words,
+                                   const uint32_t* expected_code_root, int* verdict_out, uint32_t* po2_out, uint32_t* code_root_out) {
+  int fn = 0;
+  R0H_TRY(hashfn_parse("r0h_verify_seal_hashfn", hashfn, &fn));
+  return verify_entry(fn, blob, blob_words, nullptr, nullptr, seal, seal_words, expected_code_root, verdict_out, po2_out, code_root_out);
 }
 
 // the same, also returning the DATA group's Merkle root as the seal's transcript recomputes it: what a session's common challenge is
@@ -460,7 +451,7 @@ const char* r0h_verify_seal_roots(const uint32_t* blob, size_t blob_words, const
                                   uint32_t* po2_out, uint32_t* data_root_out) {
   R0H_REQUIRE(data_root_out, "r0h_verify_seal_roots: NULL argument");
   memset(data_root_out, 0, 32);
-  return verify_entry(blob, blob_words, nullptr, nullptr, seal, seal_words, expected_code_root, verdict_out, po2_out, nullptr, data_root_out);
+  return verify_entry(HASH_POSEIDON2, blob, blob_words, nullptr, nullptr, seal, seal_words, expected_code_root, verdict_out, po2_out, nullptr, data_root_out);
 }
 
 // ---- the control root of a circuit's own CODE columns, on the host.  A verifier is handed control roots (risc0's has a table of
@@ -506,8 +497,8 @@ void in_parallel(size_t n, F f) {
 }  // namespace
 extern "C" {
 
-const char* r0h_control_root_host(const uint32_t* blob, size_t blob_words, const uint32_t* p2_round_constants, const uint32_t* p2_diag_m1,
-                                  uint32_t po2, uint32_t root_out[8]) {
+static const char* control_root_host(int hashfn, const uint32_t* blob, size_t blob_words, const uint32_t* p2_round_constants, const uint32_t* p2_diag_m1,
+                                     uint32_t po2, uint32_t root_out[8]) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(blob && root_out, "r0h_control_root_host: NULL argument");
   R0H_REQUIRE((p2_round_constants == nullptr) == (p2_diag_m1 == nullptr), "r0h_control_root_host: pass both Poseidon2 tables or neither");
@@ -518,6 +509,7 @@ const char* r0h_control_root_host(const uint32_t* blob, size_t blob_words, const
   std::unique_ptr<P2Consts> k(new P2Consts);
   if (p2_round_constants) fill_p2(*k, p2_round_constants, p2_diag_m1);
   else p2_default_host(*k);
+  const std::unique_ptr<HashSuite> suite = make_suite(hashfn, k.get());
   const uint32_t count = c.group_size[R0H_GROUP_CODE];
   const size_t n = (size_t)1 << po2, m = 4 * n;
   R0H_REQUIRE(c.code_cols.size() == count && count >= 1, "r0h_control_root_host: %zu CODE columns described, %u in the group", c.code_cols.size(), count);
@@ -554,13 +546,23 @@ const char* r0h_control_root_host(const uint32_t* blob, size_t blob_words, const
     uint32_t* v = row;
     if (count > 64) { wide.resize(count); v = wide.data(); }
     for (uint32_t col = 0; col < count; col++) v[col] = evals[(size_t)col * m + r];
-    p2_hash_elems_host(*k, v, count, &nodes[(m + r) * 8]);
+    suite->hash_elems(v, count, &nodes[(m + r) * 8]);
   });
   for (size_t level = m / 2; level >= 1; level /= 2)
-    in_parallel(level, [&](size_t i) { hash_pair(*k, &nodes[2 * (level + i) * 8], &nodes[(2 * (level + i) + 1) * 8], &nodes[(level + i) * 8]); });
+    in_parallel(level, [&](size_t i) { suite->hash_pair(&nodes[2 * (level + i) * 8], &nodes[(2 * (level + i) + 1) * 8], &nodes[(level + i) * 8]); });
   memcpy(root_out, &nodes[8], 32);
   return nullptr;
   R0H_GUARD_END
+}
+
+const char* r0h_control_root_host(const uint32_t* blob, size_t blob_words, const uint32_t* p2_round_constants, const uint32_t* p2_diag_m1,
+                                  uint32_t po2, uint32_t root_out[8]) {
+  return control_root_host(HASH_POSEIDON2, blob, blob_words, p2_round_constants, p2_diag_m1, po2, root_out);
+}
+const char* r0h_control_root_host_hashfn(const uint32_t* blob, size_t blob_words, const char* hashfn, uint32_t po2, uint32_t root_out[8]) {
+  int fn = 0;
+  R0H_TRY(hashfn_parse("r0h_control_root_host_hashfn", hashfn, &fn));
+  return control_root_host(fn, blob, blob_words, nullptr, nullptr, po2, root_out);
 }
 
 }  // extern "C"

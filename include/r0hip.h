@@ -51,6 +51,14 @@ const char* r0h_version(void);
 const char* r0h_ctx_create(int device, r0h_ctx** out);
 const char* r0h_ctx_destroy(r0h_ctx* ctx);
 const char* r0h_sync(r0h_ctx* ctx);
+/* The context's hash suite (risc0 `ProverOpts::hashfn`): "poseidon2" (the default) or "sha-256"; any other name is an error.
+ * r0h_hash_rows, r0h_hash_fold[_io], r0h_merkle_build, r0h_code_root, r0h_code_commit_new and every r0h_prove_segment* / r0h_proof_*
+ * entry follow it; under "poseidon2" they compute what they always did.  A r0h_code_commit remembers the suite it was made under
+ * (using it from a context on the other suite is an error that names both), and so does a proof between begin and finish.
+ * Receipts, sessions, image proofs and recursion nodes name Poseidon2 only: r0h_prove_elf*, r0h_session_begin, r0h_prove_image,
+ * r0h_lift and r0h_join return an error on a "sha-256" context.  r0h_ctx_hashfn returns a static string. */
+const char* r0h_ctx_set_hashfn(r0h_ctx* ctx, const char* name);
+const char* r0h_ctx_hashfn(const r0h_ctx* ctx);
 const char* r0h_buf_alloc(r0h_ctx* ctx, size_t bytes, r0h_buf** out);
 const char* r0h_buf_wrap(r0h_ctx* ctx, void* device_ptr, size_t bytes, r0h_buf** out); /* memory owned elsewhere */
 const char* r0h_buf_slice(r0h_buf* parent, size_t offset_bytes, size_t bytes, r0h_buf** out);
@@ -84,6 +92,16 @@ const char* r0h_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix,
 const char* r0h_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size);
 /* nodes has 2*rows digests: leaves at [rows, 2rows), root at index 1 */
 const char* r0h_merkle_build(r0h_ctx* ctx, r0h_buf* nodes, const r0h_buf* matrix, uint32_t rows, uint32_t cols);
+/* The SHA-256 suite (recalled from risc0-zkp core/hash/sha and risc0-sys sha256.h; unpinned: the reference vendors neither).
+ * A digest is 8 words, word j = bswap32 of SHA-256 state word j, so its bytes in memory are the standard big-endian digest; message
+ * word i of a compression = bswap32 of input word i.  Pair: one compression of the IV over the 16 words a || b, no padding, no
+ * length.  Slice (risc0 `hash_raw_data_slice`; what r0h_hash_rows computes per row): 16-word blocks chained from the IV, the last
+ * partial block zero-filled, no length block, over the 32-bit words as the buffers hold them (Montgomery form); an EMPTY slice
+ * hashes to the IV taken as a digest.  Digest words under this suite are arbitrary 32-bit values, not field elements.
+ * The two suites on the host, by name (pure host code: a caller's own transcript hashing; "poseidon2" uses the compiled-in table
+ * and wants canonical words): */
+const char* r0h_hash_pair_host(const char* hashfn, const uint32_t a[8], const uint32_t b[8], uint32_t out[8]);
+const char* r0h_hash_elems_host(const char* hashfn, const uint32_t* words, size_t n, uint32_t out[8]);
 
 /* ---- Hal: streaming ops (`batch_evaluate_any`, `mix_poly_coeffs`, `eltwise_*`, `gather_sample`, `scatter`,
  *      `fri_fold`, `prefix_products`; core/poly.rs `poly_divide`) ---- */
@@ -226,6 +244,12 @@ const char* r0h_verify_seal_bound(const uint32_t* blob, size_t blob_words, const
                                   const uint32_t* p2_diag_m1, const uint32_t* seal, size_t seal_words,
                                   const uint32_t* expected_code_root, int* verdict_out, uint32_t* po2_out,
                                   uint32_t* code_root_out);
+/* r0h_verify_seal_bound for a seal made under the named hash suite ("poseidon2": the compiled-in table; "sha-256": digest words in
+ * the seal -- Merkle tops, path siblings, the roots -- are arbitrary 32-bit values, only field-element positions are held to < p).
+ * A seal of the other suite is rejected with a verdict, like any other seal that does not verify. */
+const char* r0h_verify_seal_hashfn(const uint32_t* blob, size_t blob_words, const char* hashfn, const uint32_t* seal,
+                                   size_t seal_words, const uint32_t* expected_code_root, int* verdict_out, uint32_t* po2_out,
+                                   uint32_t* code_root_out);
 /* the same, also giving the DATA group's Merkle root as the seal's transcript recomputes it (the session challenge of the trace
  * circuit is derived from these roots: csrc/claim.cpp) */
 const char* r0h_verify_seal_roots(const uint32_t* blob, size_t blob_words, const uint32_t* seal, size_t seal_words,
@@ -235,6 +259,8 @@ const char* r0h_verify_seal_roots(const uint32_t* blob, size_t blob_words, const
  * A verifier that has the circuit need not be told its control roots (risc0's verifier has them compiled in).  Seconds at po2 = 20. */
 const char* r0h_control_root_host(const uint32_t* blob, size_t blob_words, const uint32_t* p2_round_constants, const uint32_t* p2_diag_m1,
                                   uint32_t po2, uint32_t root_out[8]);
+/* the same under the named hash suite: what r0h_code_root gives on a context set to it */
+const char* r0h_control_root_host_hashfn(const uint32_t* blob, size_t blob_words, const char* hashfn, uint32_t po2, uint32_t root_out[8]);
 const char* r0h_verify_reason(int verdict); /* static string, do not free */
 /* Poseidon2 sponge (compiled-in table) over a seal's words (all canonical field elements, else an error): the 8-word name a
  * recursion step commits to */

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Per-operation timing through the C ABI at bench sizes (po2 = 20): used to A/B kernel variants on the GPU box."""
+"""Per-operation timing through the C ABI at bench sizes (po2 = 20): used to A/B kernel variants on the GPU box.
+usage: bench_ops.py [--hashfn poseidon2|sha-256] [--cols N] [op ...]   (--hashfn: the hash suite hash_rows / hash_fold run under;
+--cols: the matrix's width, 192 by default)"""
 import os
 import sys
 
@@ -14,11 +16,18 @@ if os.environ.get("R0HIP_AB_LIB"):  # A/B runs: a variant build of the library (
 
 
 def main():
-    ops = sys.argv[1:] or ["hash_rows", "hash_fold", "intt", "ntt", "bitrev", "zk", "evalany"]
+    args, opts = sys.argv[1:], {"--hashfn": "poseidon2", "--cols": "192"}
+    for o in opts:
+        if o in args:
+            opts[o] = args[args.index(o) + 1]
+            del args[args.index(o):args.index(o) + 2]
+    ops = args or ["hash_rows", "hash_fold", "intt", "ntt", "bitrev", "zk", "evalany"]
     hal = r0.Hal(0)
+    hal.set_hashfn(opts["--hashfn"])
     po2, n, dom = 20, 1 << 20, 1 << 22
     rng = np.random.default_rng(0)
-    cols = 192
+    cols = int(opts["--cols"])
+    print("hashfn=%s cols=%d rows=2^22" % (hal.hashfn, cols), flush=True)
     src = hal.copy_from(rng.integers(0, r0.P, cols * n, dtype=np.uint32))
     ev = hal.alloc(cols * dom)
     hal.batch_expand_into_evaluate_ntt(ev, src, cols, po2, 2)
