@@ -606,37 +606,11 @@ static const char* compile_in_process(const std::string& src, std::vector<char>&
 }
 
 // ------------------------------------------------------------------ synthetic witness + accumulation kernels
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint32_t synth_word(uint64_t seed_mixed, uint32_t stream, uint32_t row) {
-  uint64_t h = splitmix64(seed_mixed ^ (((uint64_t)stream << 32) | row));
-  return (uint32_t)(((h >> 32) * (uint64_t)P) >> 32);
-}
-static uint64_t splitmix64_host(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-__global__ void witgen_fixed_kernel(uint32_t* __restrict__ buf, const uint32_t* __restrict__ kinds /* (kind, stream) per col */,
+__global__ void witgen_fixed_kernel(uint32_t* __restrict__ buf, const uint32_t* __restrict__ kinds /* (kind, fixed_cell's arg) per col */,
                                     uint32_t po2, uint64_t seed_mixed, const uint32_t* __restrict__ periodic /* Montgomery */, uint32_t period) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << po2, col = blockIdx.y;
-  const uint32_t kind = kinds[2 * col], stream = kinds[2 * col + 1];
-  uint32_t v;
-  if (kind == 0) v = r == 0 ? ONE : 0u;
-  else if (kind == 1) v = r == n - 1 ? ONE : 0u;
-  else if (kind == 2) v = enc(r);
-  else if (kind == 3) v = synth_word(seed_mixed, stream, r);
-  else if (kind == 4) v = r < 65536u ? enc(r) : 0u;                                                     // the 16-bit range table
-  else if (kind == 5) v = enc(R0H_TAG_AND + (r < 65536u ? r + 65536u * ((r & 255u) & (r >> 8)) : 0u));  // the byte-AND table
-  else if (kind == 6) v = r < (n / period) * period ? periodic[stream * period + r % period] : 0u;      // a periodic schedule (stream = its column)
-  else return;  // derived column: filled later
-  buf[((size_t)col << po2) + r] = v;
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x, col = blockIdx.y, kind = kinds[2 * col];
+  if (kind > 6) return;  // derived column: filled later
+  buf[((size_t)col << po2) + r] = fixed_cell(kind, kinds[2 * col + 1], r, 1u << po2, seed_mixed, periodic, period);
 }
 __global__ void witgen_derived_kernel(uint32_t* __restrict__ dst, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                       const uint32_t* __restrict__ c, const uint32_t* __restrict__ e, uint32_t ba, uint32_t bb,
@@ -761,16 +735,44 @@ const char* sponge_plant(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const
   R0H_REQUIRE(rows < n, "the in-circuit sponge over %zu words takes %zu rows: the recursion trace has 2^%u", n_words, rows, po2);
   R0H_REQUIRE(((size_t)c->group_size[R0H_GROUP_DATA] << po2) * 4 <= data->bytes, "sponge_plant: DATA buffer too small for 2^%u rows", po2);
   for (size_t i = 0; i < n_words; i++) R0H_REQUIRE(words[i] < P, "sponge_plant: word %zu is not a canonical field element", i);
-  std::unique_ptr<P2Consts> k(new P2Consts);
-  p2_default_host(*k);
   std::vector<uint32_t> cols((size_t)R0H_SPONGE_DATA_COLUMNS * rows);
   size_t used = 0;
-  p2_sponge_rows_host(*k, words, n_words, cols.data(), rows, &used);
+  p2_sponge_rows_host(p2_default(), words, n_words, cols.data(), rows, &used);
   uint32_t* first = u32(data) + ((size_t)c->sponge_data << po2);
   R0H_TRY_HIP(hipMemsetAsync(first, 0, (size_t)R0H_SPONGE_DATA_COLUMNS * n * 4, ctx->stream));
   R0H_TRY_HIP(hipMemcpy2DAsync(first, n * 4, cols.data(), rows * 4, rows * 4, R0H_SPONGE_DATA_COLUMNS, hipMemcpyHostToDevice, ctx->stream));
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // `cols` is pageable and goes out of scope
   return nullptr;
+}
+}  // namespace r0h
+namespace r0h {
+// one launch of witgen_fixed_kernel over the columns `kinds` describes; the parameter block (kinds, then the PERIODIC section in
+// Montgomery form) goes through the context's scratch, in stream order behind whatever read it last
+static const char* witgen_fixed(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, std::vector<uint32_t>& kinds, uint64_t seed_mixed, r0h_buf* buf) {
+  const uint32_t n = 1u << po2, threads = n < 256 ? n : 256, cols = (uint32_t)(kinds.size() / 2);
+  const size_t table_at = kinds.size();
+  for (uint32_t v : c->periodic) kinds.push_back(enc(v));
+  R0H_TRY(ensure_scratch(ctx, kinds.size() * 4));
+  R0H_TRY(stage_h2d(ctx, ctx->scratch, kinds.data(), kinds.size() * 4));
+  const uint32_t* dk = (const uint32_t*)ctx->scratch;
+  hipLaunchKernelGGL(witgen_fixed_kernel, dim3(n / threads, cols), dim3(threads), 0, ctx->stream, u32(buf), dk, po2, seed_mixed, dk + table_at, c->period);
+  return launch_ok("r0h_witgen");
+}
+const char* witgen_code(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* code) {
+  R0H_REQUIRE(ctx && c && code, "r0h_witgen: NULL argument");
+  R0H_REQUIRE(c->has_column_program, "r0h_witgen: this circuit carries no synthetic column program (WITGEN/ACCUM sections); supply the witness");
+  R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_witgen: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
+  const uint32_t nc = (uint32_t)c->code_cols.size();
+  R0H_REQUIRE(((size_t)nc << po2) * 4 <= code->bytes, "r0h_witgen: buffers too small for 2^%u rows", po2);
+  std::vector<uint32_t> kinds(2 * (size_t)nc);
+  for (uint32_t k = 0; k < nc; k++) { kinds[2 * k] = c->code_cols[k].kind; kinds[2 * k + 1] = code_col_arg(c->code_cols[k], k); }
+  return witgen_fixed(ctx, c, po2, kinds, splitmix64(CODE_SEED), code);
+}
+const char* code_commit_of(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_code_commit** out) {
+  DevBuf code;
+  R0H_TRY(code.alloc(ctx, ((size_t)c->group_size[R0H_GROUP_CODE] << po2) * 4));
+  R0H_TRY(witgen_code(ctx, c, po2, code.get()));
+  return r0h_code_commit_new(ctx, code.get(), c->group_size[R0H_GROUP_CODE], po2, out);
 }
 }  // namespace r0h
 extern "C" {
@@ -783,25 +785,17 @@ static const char* witgen_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2,
   R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_witgen: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
   const uint32_t n = 1u << po2, threads = n < 256 ? n : 256, nc = (uint32_t)c->code_cols.size(), nd = (uint32_t)c->data_cols.size();
   R0H_REQUIRE(((size_t)nc << po2) * 4 <= code->bytes && ((size_t)nd << po2) * 4 <= data->bytes, "r0h_witgen: buffers too small for 2^%u rows", po2);
-  std::vector<uint32_t> kinds(2 * (size_t)(nc + nd));
-  for (uint32_t k = 0; k < nc; k++) { kinds[2 * k] = c->code_cols[k].kind; kinds[2 * k + 1] = c->code_cols[k].kind == 6 ? c->code_cols[k].param : (1u << 16) | k; }
-  for (uint32_t k = 0; k < nd; k++) { kinds[2 * (nc + k)] = c->data_cols[k].kind == 0 ? 3u : 99u; kinds[2 * (nc + k) + 1] = (2u << 16) | k; }
-  const size_t table_at = kinds.size();
-  for (uint32_t v : c->periodic) kinds.push_back(enc(v));
-  R0H_TRY(ensure_scratch(ctx, kinds.size() * 4));
-  R0H_TRY(stage_h2d(ctx, ctx->scratch, kinds.data(), kinds.size() * 4));
-  const uint32_t* dk = (const uint32_t*)ctx->scratch;
-  hipLaunchKernelGGL(witgen_fixed_kernel, dim3(n / threads, nc), dim3(threads), 0, ctx->stream, u32(code), dk, po2, splitmix64_host(0xC0DEull), dk + table_at, c->period);
-  hipLaunchKernelGGL(witgen_fixed_kernel, dim3(n / threads, nd), dim3(threads), 0, ctx->stream, u32(data), dk + 2 * nc, po2, splitmix64_host(seed), dk + table_at, c->period);
+  R0H_TRY(witgen_code(ctx, c, po2, code));
+  std::vector<uint32_t> kinds(2 * (size_t)nd);
+  for (uint32_t k = 0; k < nd; k++) { kinds[2 * k] = c->data_cols[k].kind == 0 ? 3u : 99u; kinds[2 * k + 1] = (2u << 16) | k; }
+  R0H_TRY(witgen_fixed(ctx, c, po2, kinds, splitmix64(seed), data));
   if (c->has_sponge) {
     // the sponge's columns hold the sponge over no words at all, and -- unless the caller names the public inputs -- the inputs its
     // digest is tied to are that digest (a caller who names them plants the rows of what it hashed instead: r0h_lift / r0h_join)
     R0H_TRY(sponge_plant(ctx, c, po2, nullptr, 0, data));
     if (!global_in) {
-      std::unique_ptr<P2Consts> k(new P2Consts);
-      p2_default_host(*k);
       uint32_t digest[8];
-      p2_hash_elems_host(*k, nullptr, 0, digest);
+      p2_hash_elems_host(p2_default(), nullptr, 0, digest);
       for (uint32_t j = 0; j < 8; j++) R0H_TRY(stage_h2d(ctx, u32(data) + ((size_t)c->global_cols[c->sponge_global + j] << po2), digest + j, 4));
     }
   }

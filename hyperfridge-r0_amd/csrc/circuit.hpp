@@ -1,5 +1,6 @@
 // Parsed circuit blob (include/r0hip_circuit.h) shared by circuit.hip (loading, eval_check) and prover.hip (sequencer).
 #pragma once
+#include "../../include/r0hip_circuit.h"
 #include "internal.hpp"
 
 namespace r0h {
@@ -24,6 +25,34 @@ struct Logup {
   std::vector<LogupAcc> accs;
   uint32_t n_chain = 0;  // the first n_chain accumulators are links of the chain
 };
+
+// ---- the fixed columns of the synthetic column program (blob section WITGEN), one statement for the device (circuit.hip
+// witgen_fixed_kernel) and for the host (verify.cpp control_root_host)
+R0H_HD uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+R0H_HD uint32_t synth_word(uint64_t seed_mixed, uint32_t stream, uint32_t row) {
+  uint64_t h = splitmix64(seed_mixed ^ (((uint64_t)stream << 32) | row));
+  return (uint32_t)(((h >> 32) * (uint64_t)P) >> 32);
+}
+constexpr uint64_t CODE_SEED = 0xC0DEull;  // the CODE group's seed (a program's CODE columns do not depend on the witness seed); splitmix64 of it is seed_mixed
+// what fixed_cell takes beside the kind of CODE column `col`: a periodic column names its schedule, every other its stream of the generator
+inline uint32_t code_col_arg(const CodeCol& cc, uint32_t col) { return cc.kind == 6 ? cc.param : (1u << 16) | col; }
+// The word (Montgomery form) a fixed column of kind 0..6 holds at row r of n (include/r0hip_circuit.h WITGEN); `periodic` is the PERIODIC
+// section in Montgomery form, [column][period].  Any other kind is not a fixed column: 0.
+R0H_HD uint32_t fixed_cell(uint32_t kind, uint32_t arg, uint32_t r, uint32_t n, uint64_t seed_mixed, const uint32_t* periodic, uint32_t period) {
+  if (kind == 0) return r == 0 ? ONE : 0u;
+  if (kind == 1) return r == n - 1 ? ONE : 0u;
+  if (kind == 2) return enc(r);
+  if (kind == 3) return synth_word(seed_mixed, arg, r);
+  if (kind == 4) return r < 65536u ? enc(r) : 0u;                                                     // the 16-bit range table
+  if (kind == 5) return enc(R0H_TAG_AND + (r < 65536u ? r + 65536u * ((r & 255u) & (r >> 8)) : 0u));  // the byte-AND table
+  if (kind == 6) return r < (n / period) * period ? periodic[arg * period + r % period] : 0u;         // a periodic schedule
+  return 0u;
+}
 
 struct Plan {                      // how the constraint program is cut into kernels
   std::vector<Term> terms;         // flattened, in chain order

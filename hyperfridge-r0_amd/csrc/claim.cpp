@@ -35,7 +35,7 @@ namespace r0h {
 
 // ---------------------------------------------------------------- SHA-256 (FIPS 180-4)
 namespace {
-const uint32_t K256[64] = {
+const uint32_t SHA_K[64] = {
     0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,
     0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa,
     0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85,
@@ -45,26 +45,32 @@ const uint32_t K256[64] = {
 inline uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
 }  // namespace
 
+const uint32_t SHA_IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+void sha256_compress(uint32_t st[8], const uint32_t m[16]) {
+  uint32_t w[64];
+  memcpy(w, m, 64);
+  for (int i = 16; i < 64; i++) {
+    const uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
+    w[i] = w[i - 16] + s0 + w[i - 7] + s1;
+  }
+  uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+  for (int i = 0; i < 64; i++) {
+    const uint32_t t1 = h + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + SHA_K[i] + w[i];
+    const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
+    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+  }
+  st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+}
+
 void Sha256::reset() {
-  static const uint32_t iv[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-  memcpy(h, iv, sizeof h);
+  memcpy(h, SHA_IV, sizeof h);
   total = 0;
   fill = 0;
 }
 void Sha256::block(const uint8_t* p) {
-  uint32_t w[64];
+  uint32_t w[16];
   for (int i = 0; i < 16; i++) w[i] = ((uint32_t)p[4 * i] << 24) | ((uint32_t)p[4 * i + 1] << 16) | ((uint32_t)p[4 * i + 2] << 8) | p[4 * i + 3];
-  for (int i = 16; i < 64; i++) {
-    uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-    w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-  }
-  uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
-  for (int i = 0; i < 64; i++) {
-    uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + K256[i] + w[i];
-    uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-    hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-  }
-  h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+  sha256_compress(h, w);
 }
 void Sha256::update(const void* data, size_t n) {
   const uint8_t* p = (const uint8_t*)data;
@@ -129,9 +135,7 @@ void claim_digest(const r0h_receipt_claim& c, uint8_t out[32]) {
 void claim_globals(const uint8_t digest[32], uint32_t out[8]) {
   uint32_t halves[16];
   for (int i = 0; i < 16; i++) halves[i] = enc((uint32_t)digest[2 * i] | ((uint32_t)digest[2 * i + 1] << 8));
-  std::unique_ptr<P2Consts> k(new P2Consts);
-  p2_default_host(*k);
-  p2_hash_elems_host(*k, halves, 16, out);
+  p2_hash_elems_host(p2_default(), halves, 16, out);
 }
 
 // what a trace-circuit seal says in its public inputs beyond the claim's name, held against the claim it is carried with: the pc the
@@ -154,11 +158,9 @@ void session_challenge(const uint32_t* records, size_t n_records, uint32_t out[1
   elems.reserve(16 + n_records * R0H_SESSION_RECORD_WORDS);
   for (int i = 0; i < 16; i++) elems.push_back(enc((uint8_t)tag[i]));
   elems.insert(elems.end(), records, records + n_records * R0H_SESSION_RECORD_WORDS);
-  std::unique_ptr<P2Consts> k(new P2Consts);
-  p2_default_host(*k);
   uint32_t cells[P2_CELLS] = {0};
-  p2_hash_elems_host(*k, elems.data(), elems.size(), cells);
-  p2_mix_host(*k, cells);
+  p2_hash_elems_host(p2_default(), elems.data(), elems.size(), cells);
+  p2_mix_host(p2_default(), cells);
   Fp4 alpha{{cells[0], cells[1], cells[2], cells[3]}}, g{{cells[4], cells[5], cells[6], cells[7]}};
   const Fp4 g2 = g * g, g3 = g2 * g;
   memcpy(out, alpha.e, 16);

@@ -58,7 +58,10 @@ void fill_p2(P2Consts& k, const uint32_t* rc, const uint32_t* diag) {
   for (int i = 1; i < P2_CELLS; i++)
     for (int e = P2_PARTIAL; e >= 0; e--) *w++ = enc(pw[e][i]);
 }
-void p2_default_host(P2Consts& k) { fill_p2(k, R0H_P2_ROUND_CONSTANTS, R0H_P2_INT_DIAG_M1); }
+const P2Consts& p2_default() {
+  static const P2Consts k = [] { P2Consts t; fill_p2(t, R0H_P2_ROUND_CONSTANTS, R0H_P2_INT_DIAG_M1); return t; }();
+  return k;
+}
 
 static inline uint32_t sbox7(uint32_t x) {
   uint32_t x2 = mul(x, x), x4 = mul(x2, x2);
@@ -299,20 +302,13 @@ const char* r0h_ctx_create(int device, r0h_ctx** out) {
     R0H_TRY(upload_pow_table(&ctx->twb_hi[d], fpow(w26, TWB_SIZE), TWB_SIZE));
     R0H_TRY(upload_pow_table(&ctx->tw_lo[d], w22, TW_SIZE));
     R0H_TRY(upload_pow_table(&ctx->tw_hi[d], fpow(w22, TW_SIZE), TW_SIZE));
-    {  // the in-chunk table, followed by the same words canonical and by their Shoup companions (ntt.hip, R0H_NTT_SHOUP)
-      const uint32_t n12 = 1u << (TWL_BITS - 1), base = d == 0 ? rou_fwd(TWL_BITS) : rou_rev(TWL_BITS);
-      std::vector<uint32_t> t(3 * (size_t)n12);
-      uint32_t cur = ONE;
-      for (uint32_t i = 0; i < n12; i++) { t[i] = cur; t[n12 + i] = dec(cur); t[2 * n12 + i] = shoup_companion(t[n12 + i]); cur = mul(cur, base); }
-      R0H_TRY_HIP(hipMalloc((void**)&ctx->tw12[d], t.size() * 4));
-      R0H_TRY_HIP(hipMemcpy(ctx->tw12[d], t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    }
+    R0H_TRY(upload_pow_table(&ctx->tw12[d], d == 0 ? rou_fwd(TWL_BITS) : rou_rev(TWL_BITS), 1u << (TWL_BITS - 1)));
   }
   R0H_TRY(upload_pow_table(&ctx->pow3_lo, enc(3), TW_SIZE));
   R0H_TRY(upload_pow_table(&ctx->pow3_hi, fpow(enc(3), TW_SIZE), TW_SIZE));
   R0H_TRY(upload_pow_table(&ctx->pow3_top, fpow(enc(3), (uint64_t)1 << TW_TOP), 1u << (MAX_DOMAIN_PO2 - TW_TOP)));
   R0H_TRY_HIP(hipMalloc((void**)&ctx->p2, sizeof(P2Consts)));
-  fill_p2(ctx->p2_host, R0H_P2_ROUND_CONSTANTS, R0H_P2_INT_DIAG_M1);
+  ctx->p2_host = p2_default();
   R0H_TRY_HIP(hipMemcpy(ctx->p2, &ctx->p2_host, sizeof(P2Consts), hipMemcpyHostToDevice));
   ctx->pinned_bytes = 8u << 20;
   R0H_TRY_HIP(hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault));

@@ -18,33 +18,13 @@
 namespace r0h {
 namespace {
 
-const uint32_t SHA_K[64] = {
-    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01, 0x243185be,
-    0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa,
-    0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967, 0x27b70a85,
-    0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85, 0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3,
-    0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f,
-    0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
-const uint32_t SHA_IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
-
-inline uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
 inline uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
 
 // one compression: `st` in the hash's own word order, `in` sixteen input words (byte-swapped into message words here)
 void sha_compress(uint32_t st[8], const uint32_t* in) {
-  uint32_t w[64];
+  uint32_t w[16];
   for (int i = 0; i < 16; i++) w[i] = bswap(in[i]);
-  for (int i = 16; i < 64; i++) {
-    const uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3), s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
-    w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-  }
-  uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
-  for (int i = 0; i < 64; i++) {
-    const uint32_t t1 = h + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + SHA_K[i] + w[i];
-    const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
-    h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-  }
-  st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+  sha256_compress(st, w);
 }
 
 struct P2Rng : SuiteRng {
@@ -180,13 +160,9 @@ const char* r0h_hash_pair_host(const char* hashfn, const uint32_t a[8], const ui
   R0H_REQUIRE(a && b && out, "r0h_hash_pair_host: NULL argument");
   int fn = 0;
   R0H_TRY(hashfn_parse("r0h_hash_pair_host", hashfn, &fn));
-  std::unique_ptr<P2Consts> k;
-  if (fn == HASH_POSEIDON2) {
+  if (fn == HASH_POSEIDON2)
     for (int i = 0; i < 8; i++) R0H_REQUIRE(a[i] < P && b[i] < P, "r0h_hash_pair_host: word %d is not a canonical field element", i);
-    k.reset(new P2Consts);
-    p2_default_host(*k);
-  }
-  make_suite(fn, k.get())->hash_pair(a, b, out);
+  make_suite(fn, &p2_default())->hash_pair(a, b, out);
   return nullptr;
   R0H_GUARD_END
 }
@@ -196,13 +172,9 @@ const char* r0h_hash_elems_host(const char* hashfn, const uint32_t* words, size_
   R0H_REQUIRE((words || n == 0) && out, "r0h_hash_elems_host: NULL argument");
   int fn = 0;
   R0H_TRY(hashfn_parse("r0h_hash_elems_host", hashfn, &fn));
-  std::unique_ptr<P2Consts> k;
-  if (fn == HASH_POSEIDON2) {
+  if (fn == HASH_POSEIDON2)
     for (size_t i = 0; i < n; i++) R0H_REQUIRE(words[i] < P, "r0h_hash_elems_host: word %zu is not a canonical field element", i);
-    k.reset(new P2Consts);
-    p2_default_host(*k);
-  }
-  make_suite(fn, k.get())->hash_elems(words, n, out);
+  make_suite(fn, &p2_default())->hash_elems(words, n, out);
   return nullptr;
   R0H_GUARD_END
 }

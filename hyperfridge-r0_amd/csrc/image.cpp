@@ -32,15 +32,13 @@ const char* image_witness(const std::vector<std::pair<uint32_t, uint32_t>>& imag
   const size_t n = (size_t)1 << po2, n_blocks = stream.size() / 16;
   R0H_REQUIRE(n_blocks * R0H_SPONGE_PERIOD < n, "the image's %zu words take %zu rows: the image trace has 2^%u", image.size(), n_blocks * R0H_SPONGE_PERIOD, po2);
   memset(data, 0, (size_t)R0H_IMAGE_COLUMNS * n * 4);
-  std::unique_ptr<P2Consts> k(new P2Consts);
-  p2_default_host(*k);
   size_t used = 0;
-  p2_sponge_rows_host(*k, stream.data(), stream.size(), data, n, &used);
+  p2_sponge_rows_host(p2_default(), stream.data(), stream.size(), data, n, &used);
   for (size_t q = 0; q < n_blocks; q++) {  // the flags: the mask's bits, on the row that absorbs the block
     const size_t there = std::min<size_t>(4, image.size() - std::min<size_t>(image.size(), 4 * q));
     for (size_t j = 0; j < there; j++) data[(R0H_SPONGE_DATA_COLUMNS + j) * n + q * R0H_SPONGE_PERIOD] = ONE;
   }
-  if (digest) p2_hash_elems_host(*k, stream.data(), stream.size(), digest);
+  if (digest) p2_hash_elems_host(p2_default(), stream.data(), stream.size(), digest);
   return nullptr;
 }
 }  // namespace r0h
@@ -108,18 +106,13 @@ const char* r0h_prove_image(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t* e
   while (((size_t)1 << po2) <= rows) po2++;
   R0H_REQUIRE(po2 <= R0H_MAX_PO2, "r0h_prove_image: an image of %zu words does not fit a trace", image.size());
   const size_t n = (size_t)1 << po2;
-  {
-    std::unique_ptr<P2Consts> k(new P2Consts);
-    p2_default_host(*k);
-    p2_hash_elems_host(*k, stream.data(), stream.size(), global.data());
-  }
+  p2_hash_elems_host(p2_default(), stream.data(), stream.size(), global.data());
   memcpy(&global[R0H_IMAGE_GAMMA], challenge, 64);
-  DevBuf code, data, scratch;
+  DevBuf code, data;
   const size_t data_bytes = (size_t)R0H_IMAGE_COLUMNS * n * 4;
   R0H_TRY(code.alloc(ctx, (size_t)c->group_size[R0H_GROUP_CODE] * n * 4));
   R0H_TRY(data.alloc(ctx, data_bytes));
-  R0H_TRY(scratch.alloc(ctx, data_bytes));
-  R0H_TRY(r0h_witgen(ctx, c, po2, 0, code.get(), scratch.get(), nullptr));  // (the CODE columns; the DATA it fills beside them is not the image's)
+  R0H_TRY(witgen_code(ctx, c, po2, code.get()));
   // the witness: the sponge's rows over the blocks (only the rows in use travel), the flags on the rows that absorb a block
   R0H_TRY(sponge_plant(ctx, c, po2, stream.data(), stream.size(), data.get()));
   std::vector<uint32_t> flags(4 * n_blocks, 0u);  // [flag][block]

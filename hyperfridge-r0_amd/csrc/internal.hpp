@@ -185,6 +185,10 @@ const char* bit_reverse_ext(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t 
 const char* ntt_init_device();
 // batched synthetic division (DEEP step): job j divides polynomial poly_idx[j] of `polys` by (x - points[4j..]); one read-back
 const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* points, uint32_t n_jobs, uint32_t* remainders_host);
+// the CODE launch of r0h_witgen alone: the fixed CODE columns of `c` at 2^po2 rows into `code` (stream-ordered, not synchronised)
+const char* witgen_code(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* code);
+// the committed CODE group of `c` at 2^po2 rows: CODE from the pool, witgen_code, r0h_code_commit_new
+const char* code_commit_of(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_code_commit** out);
 // rv32im.cpp: the preflight rows of segment i are moved out of the machine (the session proves them while the guest runs on)
 void vm_take_trace(r0h_vm* vm, size_t i, std::vector<r0h_preflight_row>& rows, std::vector<r0h_preflight_bound>& bounds);
 void vm_recycle_trace(r0h_vm* vm, std::vector<r0h_preflight_row>& rows, std::vector<r0h_preflight_bound>& bounds);
@@ -196,9 +200,9 @@ void ctx_retain(r0h_ctx* ctx);
 void ctx_release(r0h_ctx* ctx);
 // host Poseidon2 (transcript only): permutation over 24 Montgomery words with the context's table
 void p2_mix_host(const P2Consts& k, uint32_t* cells);
-// table from canonical round constants [29][24] and canonical (mu_i - 1) [24]; the compiled-in risc0 table
+// table from canonical round constants [29][24] and canonical (mu_i - 1) [24]; the compiled-in risc0 table, filled on first use
 void fill_p2(P2Consts& k, const uint32_t* rc, const uint32_t* diag_m1);
-void p2_default_host(P2Consts& k);
+const P2Consts& p2_default();
 void p2_hash_elems_host(const P2Consts& k, const uint32_t* elems, size_t n, uint32_t digest[8]);
 void p2_sponge_rows_host(const P2Consts& k, const uint32_t* words, size_t n_words, uint32_t* cols, size_t stride, size_t* rows_used);
 

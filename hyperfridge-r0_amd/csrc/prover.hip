@@ -10,7 +10,7 @@
 // host for the DEEP division; here the division is a device scan (r0h_poly_divide).
 #include <memory>
 
-#include "circuit.hpp"
+#include "seal_layout.hpp"
 
 namespace r0h {
 
@@ -37,8 +37,6 @@ static void circuit_view(const r0h_circuit* c, CircuitView* v) {
   v->blob = c->blob.data(); v->blob_words = c->blob.size();
 }
 
-static unsigned log2u(size_t x) { unsigned n = 0; while (((size_t)1 << n) < x) n++; return n; }
-
 // ------------------------------------------------------------------ transcript
 // The generator and the slice hash are the context's hash suite (internal.hpp HashSuite: Poseidon2 or SHA-256); the order of
 // commits, writes and draws below is the same under both.
@@ -58,21 +56,6 @@ struct WriteIop {
 };
 
 // ------------------------------------------------------------------ Merkle
-struct MerkleParams {
-  size_t row_size, col_size, layers, top_layer, top_size;
-  MerkleParams(size_t rows, size_t cols) : row_size(rows), col_size(cols) {
-    layers = log2u(rows);
-    top_layer = 0;
-    for (size_t i = 1; i < layers; i++) {
-      if (((size_t)1 << i) > R0H_QUERIES) break;
-      top_layer = i;
-    }
-    top_size = (size_t)1 << top_layer;
-  }
-  size_t path_digests() const { return layers - top_layer; }
-  size_t opening_words() const { return col_size + 8 * path_digests(); }
-};
-
 // out[q] = column values at row idx[q] followed by the sibling digests up to (excluding) the top layer
 __global__ void merkle_open_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ matrix, const uint32_t* __restrict__ nodes,
                                    const uint32_t* __restrict__ idx, uint32_t row_size, uint32_t col_size, uint32_t n_path) {
@@ -86,7 +69,7 @@ __global__ void merkle_open_kernel(uint32_t* __restrict__ out, const uint32_t* _
 }
 
 struct Tree {
-  MerkleParams mp;
+  MerkleShape mp;
   r0h_buf* nodes = nullptr;
   const r0h_buf* matrix = nullptr;
   Tree(size_t rows, size_t cols) : mp(rows, cols) {}
@@ -120,8 +103,8 @@ static void phase(r0h_ctx* ctx, const char* name) {
 
 static const char* tree_build(r0h_ctx* ctx, Scope& sc, Tree& t, const r0h_buf* matrix) {
   t.matrix = matrix;
-  R0H_TRY(sc.alloc(ctx, t.mp.row_size * 2 * 32, &t.nodes));
-  return r0h_merkle_build(ctx, t.nodes, matrix, (uint32_t)t.mp.row_size, (uint32_t)t.mp.col_size);
+  R0H_TRY(sc.alloc(ctx, t.mp.rows * 2 * 32, &t.nodes));
+  return r0h_merkle_build(ctx, t.nodes, matrix, (uint32_t)t.mp.rows, (uint32_t)t.mp.cols);
 }
 static const char* tree_commit(r0h_ctx* ctx, Tree& t, WriteIop& io) {
   std::vector<uint32_t> host(2 * t.mp.top_size * 8);
@@ -136,7 +119,7 @@ static const char* tree_open(r0h_ctx* ctx, Scope& sc, const Tree& t, const r0h_b
   const size_t words = t.mp.opening_words();
   R0H_TRY(sc.alloc(ctx, (size_t)n_q * words * 4, &packed));
   hipLaunchKernelGGL(merkle_open_kernel, dim3(n_q), dim3(256), 0, ctx->stream, u32(packed), u32(t.matrix), u32(t.nodes), u32(d_idx),
-                     (uint32_t)t.mp.row_size, (uint32_t)t.mp.col_size, (uint32_t)t.mp.path_digests());
+                     (uint32_t)t.mp.rows, (uint32_t)t.mp.cols, (uint32_t)t.mp.path_digests());
   R0H_TRY(launch_ok("merkle_open_kernel"));
   host.resize((size_t)n_q * words);
   R0H_TRY(r0h_buf_d2h(ctx, packed, 0, host.data(), host.size() * 4));
@@ -251,21 +234,10 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* code, const r0h_cod
 
   phase(ctx, "transcript_seed");
   {
-    // risc0-circuit-rv32im prove/hal: the hashes of two 16-byte ProtocolInfo tags (one field element per byte) open the
-    // transcript: the proof system's and the circuit's
-    static const char proof_system_info[] = "RISC0_STARK:v1__";
-    uint32_t e[16];
-    for (int i = 0; i < 16; i++) e[i] = enc((uint8_t)proof_system_info[i]);
-    io.commit_elems(e, 16);
-    for (int i = 0; i < 16; i++) e[i] = enc(circ->info[i]);
-    io.commit_elems(e, 16);
     // the seal opens with every public input and po2; the transcript takes the early ones here and the late ones (inputs that depend
     // on commitments made outside this proof, R0H_SEC_LATE) after the DATA group is committed
-    const uint32_t n_early = cv.n_global - circ->n_late;
-    std::vector<uint32_t> gv(global, global + n_early);
-    for (uint32_t w : gv) R0H_REQUIRE(w < P, "prove_segment: global word not canonical");
-    gv.push_back(enc(po2));
-    io.commit_elems(gv.data(), gv.size());
+    for (uint32_t i = 0; i < cv.n_global - circ->n_late; i++) R0H_REQUIRE(global[i] < P, "prove_segment: global word not canonical");
+    transcript_open(io, *circ, global, po2);
     st.seal_globals_at = io.proof.size();
     io.write(global, cv.n_global);
     const uint32_t po2_word = enc(po2);
@@ -469,27 +441,26 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
 
   // ---- FRI
   phase(ctx, "fri_commit");
-  struct Round { Tree tree; r0h_buf* evaluated; size_t domain; };
+  struct Round { Tree tree; r0h_buf* evaluated; };
   std::vector<Round> rounds;
-  size_t deg = n;
-  while (deg > R0H_FRI_MIN_DEGREE) {
-    Round rd{Tree(deg * R0H_INV_RATE / R0H_FRI_FOLD, R0H_FRI_FOLD * 4), nullptr, deg * R0H_INV_RATE};
-    R0H_TRY(sc.alloc(ctx, rd.domain * 16, &rd.evaluated));
-    R0H_TRY(r0h_batch_expand_into_evaluate_ntt(ctx, rd.evaluated, fri_coeffs, 4, log2u(deg), 2));
+  const FriSchedule fri(n);
+  for (const FriRound& fr : fri.rounds) {
+    Round rd{Tree(fr.rows, R0H_FRI_FOLD * 4), nullptr};
+    R0H_TRY(sc.alloc(ctx, fr.domain * 16, &rd.evaluated));
+    R0H_TRY(r0h_batch_expand_into_evaluate_ntt(ctx, rd.evaluated, fri_coeffs, 4, log2u(fr.degree), 2));
     R0H_TRY(tree_build(ctx, sc, rd.tree, rd.evaluated));
     R0H_TRY(tree_commit(ctx, rd.tree, io));
     Fp4 fold_mix = io.rng.ext();
     r0h_buf* folded = nullptr;
-    R0H_TRY(sc.alloc(ctx, deg / R0H_FRI_FOLD * 16, &folded));
-    R0H_TRY(r0h_fri_fold(ctx, folded, fri_coeffs, fold_mix.e, (uint32_t)(deg / R0H_FRI_FOLD)));
+    R0H_TRY(sc.alloc(ctx, fr.degree / R0H_FRI_FOLD * 16, &folded));
+    R0H_TRY(r0h_fri_fold(ctx, folded, fri_coeffs, fold_mix.e, (uint32_t)(fr.degree / R0H_FRI_FOLD)));
     sc.release(fri_coeffs);
     fri_coeffs = folded;
-    deg /= R0H_FRI_FOLD;
     rounds.push_back(rd);
   }
-  R0H_TRY(r0h_batch_bit_reverse(ctx, fri_coeffs, 4, log2u(deg)));
+  R0H_TRY(r0h_batch_bit_reverse(ctx, fri_coeffs, 4, log2u(fri.final_degree)));
   {
-    std::vector<uint32_t> fc(4 * deg);
+    std::vector<uint32_t> fc(4 * fri.final_degree);
     R0H_TRY(r0h_buf_d2h(ctx, fri_coeffs, 0, fc.data(), fc.size() * 4));
     io.write(fc.data(), fc.size());
     io.commit_elems(fc.data(), fc.size());
@@ -505,7 +476,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
       size_t pos = io.rng.bits(log2u(domain)) % domain;
       for (uint32_t t = 0; t < 4; t++) idx[(size_t)t * nq + q] = (uint32_t)pos;
       for (size_t r = 0; r < rounds.size(); r++) {
-        pos = pos % (rounds[r].domain / R0H_FRI_FOLD);
+        pos = pos % rounds[r].tree.mp.rows;
         idx[(size_t)(4 + r) * nq + q] = (uint32_t)pos;
       }
     }

@@ -40,6 +40,9 @@ struct Sha256 {
   void block(const uint8_t* p);
 };
 void sha256(const void* data, size_t n, uint8_t out[32]);
+// one compression (FIPS 180-4 6.2.2): state and the sixteen message words in the hash's own word order; the initial state
+void sha256_compress(uint32_t state[8], const uint32_t w[16]);
+extern const uint32_t SHA_IV[8];
 void tagged_struct(const char* tag, const uint8_t (*down)[32], size_t n_down, const uint32_t* data, size_t n_data, uint8_t out[32]);
 void system_state_digest(const r0h_system_state& st, uint8_t out[32]);
 void claim_digest(const r0h_receipt_claim& c, uint8_t out[32]);

@@ -118,12 +118,7 @@ const char* r0h_recursor_new(r0h_ctx* ctx, const uint32_t* recursion_blob, size_
   R0H_REQUIRE(rc->circuit->n_global == 16 && rc->circuit->has_column_program, "r0h_recursor_new: a recursion circuit exposes 16 public inputs (claim words, digest of what it consumed) and carries a column program; this one has %u",
               rc->circuit->n_global);
   R0H_REQUIRE(rc->circuit->has_sponge && rc->circuit->sponge_global == 8, "r0h_recursor_new: a recursion circuit computes the digest of what a node consumed in-circuit (blob section SPONGE, public inputs 8..15); this one does not");
-  const size_t n = (size_t)1 << po2;
-  DevBuf data, code;  // (freed in the reverse order: CODE first)
-  R0H_TRY(code.alloc(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_CODE] * n * 4));
-  R0H_TRY(data.alloc(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_DATA] * n * 4));
-  R0H_TRY(r0h_witgen(ctx, rc->circuit, po2, 0, code.get(), data.get(), nullptr));
-  R0H_TRY(r0h_code_commit_new(ctx, code.get(), rc->circuit->group_size[R0H_GROUP_CODE], po2, &rc->code));
+  R0H_TRY(code_commit_of(ctx, rc->circuit, po2, &rc->code));
   R0H_TRY(r0h_code_commit_root(rc->code, rc->root));
   *out = rc.release();
   return nullptr;

@@ -845,9 +845,7 @@ void image_stream(const std::vector<std::pair<uint32_t, uint32_t>>& image, std::
 void image_digest(const std::vector<std::pair<uint32_t, uint32_t>>& image, uint32_t digest[8]) {
   std::vector<uint32_t> stream;
   image_stream(image, stream);
-  std::unique_ptr<P2Consts> k(new P2Consts);
-  p2_default_host(*k);
-  p2_hash_elems_host(*k, stream.data(), stream.size(), digest);
+  p2_hash_elems_host(p2_default(), stream.data(), stream.size(), digest);
 }
 // what a verifier needs of an ELF: the image as (word index, word) in address order, the entry point, the image id
 const char* elf_image(const uint8_t* elf, size_t n, std::vector<std::pair<uint32_t, uint32_t>>& image, uint32_t* entry, uint8_t image_id[32]) {

@@ -48,15 +48,11 @@ double seconds(Clock::time_point a, Clock::time_point b) { return std::chrono::d
 struct CodeCommits {  // one committed CODE group per trace size met in the run
   std::map<uint32_t, r0h_code_commit*> by_po2;
   ~CodeCommits() { for (auto& kv : by_po2) r0h_code_commit_free(kv.second); }
-  const char* get(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* data_scratch, r0h_code_commit** out) {
+  const char* get(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_code_commit** out) {
     auto it = by_po2.find(po2);
     if (it == by_po2.end()) {
-      // the fixed CODE columns come from the blob's column program (the DATA it also fills is scratch here)
-      DevBuf code;
-      R0H_TRY(code.alloc(ctx, ((size_t)c->group_size[R0H_GROUP_CODE] << po2) * 4));
-      R0H_TRY(r0h_witgen(ctx, c, po2, 0, code.get(), data_scratch, nullptr));
       r0h_code_commit* cc = nullptr;
-      R0H_TRY(r0h_code_commit_new(ctx, code.get(), c->group_size[R0H_GROUP_CODE], po2, &cc));
+      R0H_TRY(code_commit_of(ctx, c, po2, &cc));
       it = by_po2.emplace(po2, cc).first;
     }
     *out = it->second;
@@ -457,7 +453,7 @@ const char* take_segments(r0h_session* ses, Feed& feed, RowBuffers& rows, r0h_ct
     R0H_TRY(data.alloc(lctx, ((size_t)c->group_size[R0H_GROUP_DATA] << pend.po2) * 4));
     {
       std::lock_guard<std::mutex> lk(ses->commit_mu);
-      R0H_TRY(ses->commits.get(lctx, c, pend.po2, data.get(), &pend.cc));
+      R0H_TRY(ses->commits.get(lctx, c, pend.po2, &pend.cc));
     }
     R0H_TRY(ses->trace_mode ? commit_segment(ses, rows, *seg, data, global, pend) : prove_synthetic_segment(ses, *seg, data, global, seal, pend));
   }

@@ -4,7 +4,7 @@
 // `receipt.verify(image_id)` (host/src/main.rs:622-624, verifier/src/main.rs:124-126) -- SURVEY.md 8(f) rank 1.
 // Written against the seal layout the sequencer emits; the tests cross-check its verdicts with the CPU restatement's verifier.
 #include "../../include/r0hip_circuit.h"
-#include "circuit.hpp"
+#include "seal_layout.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -68,34 +68,26 @@ class SealReader {
   size_t n_, pos_ = 0;
 };
 
-unsigned log2_exact(size_t x) { unsigned n = 0; while (((size_t)1 << n) < x) n++; return n; }
-
 // The verifier's view of one committed matrix: the elided top layer (read from the seal) folded down to the root.
 class TreeVerifier {
  public:
-  TreeVerifier(SealReader& io, size_t rows, size_t cols, int reject_code) : rows_(rows), cols_(cols), reject_(reject_code) {
-    const size_t layers = log2_exact(rows);
-    size_t top_layer = 0;
-    for (size_t i = 1; i < layers; i++) {
-      if (((size_t)1 << i) > R0H_QUERIES) break;
-      top_layer = i;
-    }
-    top_size_ = (size_t)1 << top_layer;
-    top_.assign(2 * top_size_ * 8, 0);
-    memcpy(&top_[top_size_ * 8], io.take_digests(top_size_), top_size_ * 32);  // Poseidon2: digest words are field elements
-    for (size_t i = top_size_; i-- > 1;) io.suite().hash_pair(&top_[2 * i * 8], &top_[(2 * i + 1) * 8], &top_[i * 8]);
+  TreeVerifier(SealReader& io, size_t rows, size_t cols, int reject_code) : shape_(rows, cols), reject_(reject_code) {
+    const size_t top_size = shape_.top_size;
+    top_.assign(2 * top_size * 8, 0);
+    memcpy(&top_[top_size * 8], io.take_digests(top_size), top_size * 32);  // Poseidon2: digest words are field elements
+    for (size_t i = top_size; i-- > 1;) io.suite().hash_pair(&top_[2 * i * 8], &top_[(2 * i + 1) * 8], &top_[i * 8]);
     io.commit(&top_[8]);
   }
   // the opened row (cols_ canonical words) if its path leads to the committed top layer
   const uint32_t* open(Cursor& io, const HashSuite& k, size_t row) const {
-    if (row >= rows_) throw Reject{reject_};
-    const uint32_t* values = io.take(cols_);
-    for (size_t i = 0; i < cols_; i++)
+    if (row >= shape_.rows) throw Reject{reject_};
+    const uint32_t* values = io.take(shape_.cols);
+    for (size_t i = 0; i < shape_.cols; i++)
       if (values[i] >= P) throw Reject{reject_};
     uint32_t cur[8];
-    k.hash_elems(values, cols_, cur);
-    size_t node = row + rows_;
-    for (; node >= 2 * top_size_; node >>= 1) {
+    k.hash_elems(values, shape_.cols, cur);
+    size_t node = row + shape_.rows;
+    for (; node >= 2 * shape_.top_size; node >>= 1) {
       const uint32_t* sibling = io.take(8);
       for (int i = 0; i < 8 && k.digests_are_elems(); i++)
         if (sibling[i] >= P) throw Reject{R0H_VERIFY_BAD_ELEM};  // two word sequences must not name one digest
@@ -108,10 +100,10 @@ class TreeVerifier {
   }
 
   const uint32_t* root() const { return &top_[8]; }
-  size_t opening_words() const { return cols_ + 8 * (log2_exact(rows_) - log2_exact(top_size_)); }
+  size_t opening_words() const { return shape_.opening_words(); }
 
  private:
-  size_t rows_, cols_, top_size_ = 1;
+  MerkleShape shape_;
   int reject_;
   std::vector<uint32_t> top_;
 };
@@ -150,23 +142,11 @@ Fp4 constraint_at_z(const r0h_circuit& c, const Fp4& poly_mix, const std::vector
 void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size_t seal_words, uint32_t* po2_out, const uint32_t* expected_code_root,
             uint32_t* code_root_out, uint32_t* data_root_out = nullptr) {
   SealReader io(k, seal, seal_words);
-  {
-    static const char proof_system_info[] = "RISC0_STARK:v1__";
-    uint32_t e[16];
-    for (int i = 0; i < 16; i++) e[i] = enc((uint8_t)proof_system_info[i]);
-    io.commit_elems(e, 16);
-    for (int i = 0; i < 16; i++) e[i] = enc(c.info[i]);
-    io.commit_elems(e, 16);
-  }
   const uint32_t* global = io.take_elems((size_t)c.n_global + 1);
   const uint32_t po2 = dec(global[c.n_global]);
   if (po2 < 9 || po2 > 24) throw Reject{R0H_VERIFY_BAD_PO2};
   if (po2_out) *po2_out = po2;
-  {  // the early public inputs and po2 open the transcript; the late ones follow the DATA commitment
-    std::vector<uint32_t> early(global, global + (c.n_global - c.n_late));
-    early.push_back(global[c.n_global]);
-    io.commit_elems(early.data(), early.size());
-  }
+  transcript_open(io, c, global, po2);  // (the late public inputs follow the DATA commitment)
   const size_t n = (size_t)1 << po2, domain = n * R0H_INV_RATE;
   const uint32_t n_taps = (uint32_t)c.taps.size(), n_regs = (uint32_t)c.regs.size(), n_combos = (uint32_t)c.combo_begin.size() - 1;
   const uint32_t n_u = n_taps + R0H_CHECK_SIZE;
@@ -248,16 +228,15 @@ void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size
   // FRI commitments and the final polynomial
   struct Round { std::unique_ptr<TreeVerifier> tree; Fp4 mix; size_t rows; };
   std::vector<Round> rounds;
-  size_t degree = n, dom = domain;
-  while (degree > R0H_FRI_MIN_DEGREE) {
+  const FriSchedule fri(n);
+  for (const FriRound& fr : fri.rounds) {
     Round rd;
-    rd.rows = dom / R0H_FRI_FOLD;
+    rd.rows = fr.rows;
     rd.tree.reset(new TreeVerifier(io, rd.rows, R0H_FRI_FOLD * 4, R0H_VERIFY_FRI_MERKLE));
     rd.mix = io.ext();
     rounds.push_back(std::move(rd));
-    dom /= R0H_FRI_FOLD;
-    degree /= R0H_FRI_FOLD;
   }
+  const size_t degree = fri.final_degree;
   std::vector<Fp4> final_poly(degree);
   {
     const uint32_t* fc = io.take_elems(4 * degree);
@@ -273,11 +252,11 @@ void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size
     for (uint32_t j = 0; j < R0H_FRI_FOLD; j++)
       for (uint32_t kq = 0; kq < R0H_FRI_FOLD; kq++) idft[j][kq] = mul(inv16, fpow(zeta_inv, (uint64_t)j * kq));
   }
-  const uint32_t w_domain = rou_fwd(log2_exact(domain)), w_final = rou_fwd(log2_exact(dom));
+  const uint32_t w_domain = rou_fwd(log2u(domain)), w_final = rou_fwd(log2u(degree * R0H_INV_RATE));
   // The query positions depend only on the transcript, and every query's openings have the same size: the 50 queries are
   // independent and run on a few host threads.  The verdict is that of the first failing query, as in a sequential walk.
   size_t pos_of[R0H_QUERIES];
-  for (uint32_t q = 0; q < R0H_QUERIES; q++) pos_of[q] = io.bits(log2_exact(domain)) % domain;
+  for (uint32_t q = 0; q < R0H_QUERIES; q++) pos_of[q] = io.bits(log2u(domain)) % domain;
   size_t words_per_query = 0;
   for (int g = 0; g < 4; g++) words_per_query += group[g]->opening_words();
   for (const Round& rd : rounds) words_per_query += rd.tree->opening_words();
@@ -312,7 +291,7 @@ void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size
         for (int e = 0; e < 4; e++) v[i].e[e] = col[e * R0H_FRI_FOLD + i];
       if (!(v[quot] == goal)) throw Reject{R0H_VERIFY_FRI_GOAL};
       // interpolate the 16 values over the coset w^grp * <zeta>, then evaluate the interpolant's fold at the round mix
-      const uint32_t untwist = fpow(rou_rev(log2_exact(rows_above)), grp);
+      const uint32_t untwist = fpow(rou_rev(log2u(rows_above)), grp);
       Fp4 tot = fp4_zero(), mixpow = fp4_one();
       uint32_t tw = ONE;
       for (uint32_t j = 0; j < R0H_FRI_FOLD; j++) {
@@ -368,12 +347,10 @@ const char* r0h_verify_reason(int verdict) {
 const char* r0h_seal_digest(const uint32_t* seal, size_t seal_words, uint32_t digest_out[8]) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE((seal || seal_words == 0) && digest_out, "r0h_seal_digest: NULL argument");
-  std::unique_ptr<P2Consts> k(new P2Consts);
-  p2_default_host(*k);
   // every word of a well-formed seal is a canonical field element (globals, digests, interpolants, opened columns): reducing
   // mod p here would give two different word sequences the same name
   for (size_t i = 0; i < seal_words; i++) R0H_REQUIRE(seal[i] < P, "r0h_seal_digest: word %zu is not a canonical field element", i);
-  p2_hash_elems_host(*k, seal, seal_words, digest_out);
+  p2_hash_elems_host(p2_default(), seal, seal_words, digest_out);
   return nullptr;
   R0H_GUARD_END
 }
@@ -387,11 +364,9 @@ const char* r0h_sponge_trace(const uint32_t* words, size_t n_words, uint32_t po2
   const size_t n = (size_t)1 << po2, n_perm = n_words ? (n_words + P2_RATE - 1) / P2_RATE : 1;
   R0H_REQUIRE(n_perm * R0H_SPONGE_PERIOD < n, "r0h_sponge_trace: %zu words take %zu rows, the trace has 2^%u", n_words, n_perm * R0H_SPONGE_PERIOD, po2);
   for (size_t i = 0; i < n_words; i++) R0H_REQUIRE(words[i] < P, "r0h_sponge_trace: word %zu is not a canonical field element", i);
-  std::unique_ptr<P2Consts> k(new P2Consts);
-  p2_default_host(*k);
   memset(cols_out, 0, (size_t)R0H_SPONGE_DATA_COLUMNS * n * 4);
   size_t used = 0;
-  p2_sponge_rows_host(*k, words, n_words, cols_out, n, &used);
+  p2_sponge_rows_host(p2_default(), words, n_words, cols_out, n, &used);
   return nullptr;
   R0H_GUARD_END
 }
@@ -406,18 +381,17 @@ static const char* verify_entry(int hashfn, const uint32_t* blob, size_t blob_wo
     for (int i = 0; i < 8; i++) R0H_REQUIRE(expected_code_root[i] < P, "r0h_verify_seal: expected code root word %d not canonical", i);
   r0h_circuit c;
   R0H_TRY(parse_blob(&c, blob, blob_words));
-  std::unique_ptr<P2Consts> k(new P2Consts);
+  std::unique_ptr<P2Consts> own;  // a caller's table
   if (p2_round_constants) {
     for (size_t i = 0; i < (size_t)P2_ROUNDS * P2_CELLS; i++) R0H_REQUIRE(p2_round_constants[i] < P, "r0h_verify_seal: round constant %zu not canonical", i);
     for (size_t i = 0; i < P2_CELLS; i++) R0H_REQUIRE(p2_diag_m1[i] < P, "r0h_verify_seal: diagonal entry %zu not canonical", i);
-    fill_p2(*k, p2_round_constants, p2_diag_m1);
-  } else {
-    p2_default_host(*k);
+    own.reset(new P2Consts);
+    fill_p2(*own, p2_round_constants, p2_diag_m1);
   }
   if (po2_out) *po2_out = 0;
   if (code_root_out) memset(code_root_out, 0, 32);
   try {
-    verify(c, *make_suite(hashfn, k.get()), seal, seal_words, po2_out, expected_code_root, code_root_out, data_root_out);
+    verify(c, *make_suite(hashfn, own ? own.get() : &p2_default()), seal, seal_words, po2_out, expected_code_root, code_root_out, data_root_out);
     *verdict_out = R0H_VERIFY_OK;
   } catch (const Reject& r) {
     *verdict_out = r.code;
@@ -461,12 +435,6 @@ const char* r0h_verify_seal_roots(const uint32_t* blob, size_t blob_words, const
 // per row and node: seconds at 2^20 rows, spread over the host's threads.
 }  // extern "C"
 namespace {
-uint64_t splitmix64_h(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 // in place, natural order in and out; w = a primitive 2^log_n-th root of unity (Montgomery words throughout)
 void ntt_host(uint32_t* a, uint32_t log_n, uint32_t w) {
   const size_t n = (size_t)1 << log_n;
@@ -506,33 +474,22 @@ static const char* control_root_host(int hashfn, const uint32_t* blob, size_t bl
   r0h_circuit c;
   R0H_TRY(parse_blob(&c, blob, blob_words));
   R0H_REQUIRE(c.has_column_program, "r0h_control_root_host: the circuit has no column program: its CODE columns come from elsewhere");
-  std::unique_ptr<P2Consts> k(new P2Consts);
-  if (p2_round_constants) fill_p2(*k, p2_round_constants, p2_diag_m1);
-  else p2_default_host(*k);
-  const std::unique_ptr<HashSuite> suite = make_suite(hashfn, k.get());
+  std::unique_ptr<P2Consts> own;  // a caller's table
+  if (p2_round_constants) { own.reset(new P2Consts); fill_p2(*own, p2_round_constants, p2_diag_m1); }
+  const std::unique_ptr<HashSuite> suite = make_suite(hashfn, own ? own.get() : &p2_default());
   const uint32_t count = c.group_size[R0H_GROUP_CODE];
   const size_t n = (size_t)1 << po2, m = 4 * n;
   R0H_REQUIRE(c.code_cols.size() == count && count >= 1, "r0h_control_root_host: %zu CODE columns described, %u in the group", c.code_cols.size(), count);
-  const uint64_t seed = splitmix64_h(0xC0DEull);  // the seed r0h_witgen gives the CODE group
+  const uint64_t seed = splitmix64(CODE_SEED);
+  std::vector<uint32_t> periodic(c.periodic);  // Montgomery form, as fixed_cell reads it
+  for (uint32_t& v : periodic) v = enc(v);
   const uint32_t w_n_inv = rou_rev(po2), w_m = rou_fwd(po2 + 2), n_inv = inv(enc((uint32_t)n)), three = enc(3);
   std::vector<uint32_t> evals((size_t)count * m);
   for (uint32_t col = 0; col < count; col++) {
     uint32_t* a = &evals[(size_t)col * m];
-    const uint32_t kind = c.code_cols[col].kind, stream = (1u << 16) | col;  // the stream r0h_witgen draws CODE column `col` from
+    const uint32_t kind = c.code_cols[col].kind, arg = code_col_arg(c.code_cols[col], col);
     R0H_REQUIRE(kind <= 6, "r0h_control_root_host: CODE column %u has kind %u", col, kind);
-    const size_t whole = c.period ? (n / c.period) * c.period : 0;  // kind 6: rows below the last whole period
-    for (size_t r = 0; r < n; r++) {
-      if (kind == 0) a[r] = r == 0 ? ONE : 0u;
-      else if (kind == 1) a[r] = r == n - 1 ? ONE : 0u;
-      else if (kind == 2) a[r] = enc((uint32_t)r);
-      else if (kind == 4) a[r] = r < 65536 ? enc((uint32_t)r) : 0u;
-      else if (kind == 5) a[r] = enc(R0H_TAG_AND + (r < 65536 ? (uint32_t)r + 65536u * (((uint32_t)r & 255u) & ((uint32_t)r >> 8)) : 0u));
-      else if (kind == 6) a[r] = r < whole ? enc(c.periodic[(size_t)c.code_cols[col].param * c.period + r % c.period]) : 0u;
-      else {
-        const uint64_t h = splitmix64_h(seed ^ (((uint64_t)stream << 32) | (uint32_t)r));
-        a[r] = (uint32_t)(((h >> 32) * (uint64_t)P) >> 32);
-      }
-    }
+    for (uint32_t r = 0; r < n; r++) a[r] = fixed_cell(kind, arg, r, (uint32_t)n, seed, periodic.data(), c.period);
     ntt_host(a, po2, w_n_inv);  // values on the 2^po2 subgroup -> coefficients (times n)
     uint32_t shift = n_inv;     // ... scaled back and moved to the coset 3 <w>: coefficient i times 3^i
     for (size_t i = 0; i < n; i++) { a[i] = mul(a[i], shift); shift = mul(shift, three); }

@@ -188,8 +188,8 @@ def _log2(x):
 
 
 class _Tree:
-    """What the seal says of one committed matrix: its top layer (the lowest layer of at most QUERIES digests, as MerkleParams in
-    csrc/prover.hip chooses it), folded to the root here."""
+    """What the seal says of one committed matrix: its top layer (the lowest layer of at most QUERIES digests, as MerkleShape in
+    csrc/seal_layout.hpp chooses it), folded to the root here."""
 
     def __init__(self, seal, at, rows, cols):
         self.rows, self.cols = rows, cols

@@ -135,8 +135,7 @@ static void launch_valu(int blocks, int iters) { valu_kernel<<<blocks, 256>>>(d_
 static void launch_mfma(int blocks, int iters) { mfma_kernel<<<blocks, 256, 4 * WAVE_LDS>>>(d_res_mfma, d_btab, d_cs, iters); }
 
 int main() {
-  P2Consts hk;
-  p2_default_host(hk);  // from libr0hip.so
+  const P2Consts& hk = p2_default();  // from libr0hip.so
   // D_i^r for r = 1..20, i = 1..23: the first 23 words of each part_sigma row (Montgomery form)
   std::vector<uint32_t> tab(NR * NU), canon(NR * NU);
   const uint32_t* row = hk.part_sigma;

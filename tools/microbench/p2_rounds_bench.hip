@@ -56,8 +56,8 @@ static void run(const char* name, uint32_t* d, const P2Consts* dk, int iters, in
 
 int main() {
   uint32_t* d;
-  P2Consts hk, *dk;
-  p2_default_host(hk);  // from libr0hip.so
+  const P2Consts& hk = p2_default();  // from libr0hip.so
+  P2Consts* dk;
   (void)hipMalloc(&d, 4096);
   (void)hipMalloc(&dk, sizeof hk);
   (void)hipMemcpy(dk, &hk, sizeof hk, hipMemcpyHostToDevice);
