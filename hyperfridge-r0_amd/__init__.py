@@ -76,6 +76,10 @@ _SIGNATURES = {
     "r0h_poly_divide": [_vp, _vp, _u32, _vp, _vp],
     "r0h_circuit_emit_hip": [_vp, _sz, _c.POINTER(_c.c_char_p)],
     "r0h_circuit_load": [_vp, _vp, _sz, _cp, _pp],
+    "r0h_circuit_emit_hip_check": [_vp, _sz, _c.POINTER(_c.c_char_p)],
+    "r0h_circuit_load_check": [_vp, _cp],
+    "r0h_check_witness": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _c.POINTER(_sz)],
+    "r0h_ctx_set_check_witness": [_vp, _c.c_int],
     "r0h_circuit_free": [_vp],
     "r0h_witgen": [_vp, _vp, _u32, _u64, _vp, _vp, _vp],
     "r0h_witgen_public": [_vp, _vp, _u32, _u64, _vp, _vp, _vp],
@@ -222,6 +226,7 @@ _PLAIN = {
     "r0h_proof_resident_bytes": ([_vp], _sz),
     "r0h_circuit_n_mix": ([_vp], _u32),
     "r0h_circuit_n_taps": ([_vp], _u32),
+    "r0h_circuit_n_terms": ([_vp], _u32),
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_PLAIN))
 
@@ -326,6 +331,12 @@ class Circuit:
         self.n_global = L.r0h_circuit_n_global(handle)
         self.n_mix = L.r0h_circuit_n_mix(handle)
         self.n_taps = L.r0h_circuit_n_taps(handle)
+        self.n_terms = L.r0h_circuit_n_terms(handle)  # constraint terms: what Hal.check_witness numbers
+
+    def load_check(self, code_object_path=None):
+        """The witness checker's kernels now (r0h_circuit_load_check): from a gfx950 code object built from emit_check_witness_source,
+        or compiled in-process; without this call Hal.check_witness compiles them on first use."""
+        _check(lib().r0h_circuit_load_check(self.handle, code_object_path.encode() if code_object_path else None))
 
     def free(self):
         if self.handle:
@@ -371,6 +382,21 @@ def emit_eval_check_source(blob):
     src = out.value.decode()
     lib().r0h_free_error(ctypes.cast(out, _vp))
     return src
+
+
+def emit_check_witness_source(blob):
+    """HIP source of the circuit's witness checker, r0h_check_witness's kernels (pure host; needs no GPU)."""
+    a, p = _u32arr(blob)
+    out = ctypes.c_char_p()
+    _check(lib().r0h_circuit_emit_hip_check(p, a.size, ctypes.byref(out)))
+    src = out.value.decode()
+    lib().r0h_free_error(ctypes.cast(out, _vp))
+    return src
+
+
+class Violation(ctypes.Structure):
+    """r0h_violation: constraint term `term` does not vanish on `rows` rows of the trace, the first of them `first_row`"""
+    _fields_ = [("term", _u32), ("rows", _u32), ("first_row", _u32), ("reserved", _u32)]
 
 
 def verify_seal(blob, seal, poseidon2_consts=None, code_root=None, hashfn="poseidon2"):
@@ -1378,6 +1404,26 @@ class Hal:
         _check(lib().r0h_eval_check(self.ctx, circuit.handle, po2, eval_accum.handle, eval_code.handle, eval_data.handle,
                                     pg, pm, pq, check.handle))
         return check
+
+    def check_witness(self, circuit, po2, code, data, glob, accum=None, mix=None, capacity=None):
+        """Which constraint terms the witness violates, and where (r0h_check_witness): [(term, rows, first_row)] in term order, empty
+        for a witness that satisfies the circuit.  Without `accum` only the terms that reach neither the ACCUM group nor the mix are
+        checked.  `capacity` bounds the list (the total is still counted: a longer answer raises)."""
+        g, pg = _u32arr(glob if len(glob) else [0])
+        m, pm = _u32arr(mix if mix is not None and len(mix) else [0])
+        cap = circuit.n_terms if capacity is None else int(capacity)
+        out = (Violation * max(cap, 1))()
+        n = _sz(0)
+        _check(lib().r0h_check_witness(self.ctx, circuit.handle, po2, accum.handle if accum is not None else None, code.handle, data.handle,
+                                       pg, pm if mix is not None else None, out, cap, ctypes.byref(n)))
+        if n.value > cap:
+            raise R0HipError("check_witness: %d terms are violated, room for %d" % (n.value, cap))
+        return [(out[i].term, out[i].rows, out[i].first_row) for i in range(n.value)]
+
+    def set_check_witness(self, on=True):
+        """prove_segment, proof_finish and the sessions of this context check every segment's witness before its ACCUM group is
+        committed and raise, naming the first violated term, instead of returning a seal that cannot verify (r0h_ctx_set_check_witness)"""
+        _check(lib().r0h_ctx_set_check_witness(self.ctx, 1 if on else 0))
 
     def prove_segment(self, circuit, po2, code, data, glob, seal_capacity_words=1 << 20):
         """code: the CODE witness columns (Buf) or their commitment (CodeCommit, r0h_prove_segment_committed) -- same seal."""

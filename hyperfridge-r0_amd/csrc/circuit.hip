@@ -330,6 +330,20 @@ static void make_plan(r0h_circuit* c) {
     cost += add;
   }
   pl.cut.push_back((uint32_t)pl.terms.size());
+  // which terms wait for the accumulation: operands are defined before their readers, so one pass in creation order
+  std::vector<bool> reaches(c->fp_step.size(), false);
+  for (uint32_t v = 0; v < c->fp_step.size(); v++) {
+    const Step& s = c->steps[c->fp_step[v]];
+    if (s.op == R0H_OP_GET) reaches[v] = c->taps[s.a].group == R0H_GROUP_ACCUM;
+    else if (s.op == R0H_OP_GET_GLOBAL) reaches[v] = s.a == 1;
+    else if (s.op == R0H_OP_ADD || s.op == R0H_OP_SUB || s.op == R0H_OP_MUL) reaches[v] = reaches[s.a] || reaches[s.b];
+  }
+  pl.late.assign(pl.terms.size(), false);
+  for (uint32_t t = 0; t < pl.terms.size(); t++) {
+    bool late = reaches[pl.terms[t].v];
+    for (uint32_t g : pl.terms[t].conds) late = late || reaches[g];
+    pl.late[t] = late;
+  }
 }
 
 static const char* PRELUDE = R"SRC(// GENERATED by r0h_circuit_emit_hip -- eval_check for one circuit blob (gfx950).
@@ -583,6 +597,61 @@ static std::string emit_source(const r0h_circuit* c) {
   return os.str();
 }
 
+// The witness checker: the same terms on the N rows of the trace itself.  One lane per row reads the witness columns in natural
+// order (tap (col, back) at row (i - back) mod N, stride 1) and, instead of folding the terms with powers of poly_mix, tallies per
+// term how many rows leave it non-zero and the first such row: a wave's verdicts are gathered with one ballot, and only a wave that
+// holds a violation issues atomics -- one add and one min from one lane -- so a witness that is wrong everywhere costs
+// waves x terms atomics.  Same cuts as eval_check; inside a kernel the terms that wait for the accumulation (Plan::late) come last,
+// under a wave-uniform switch, so that one code object serves the check before the mix is drawn (no ACCUM group, no mix) too.
+static const char* CHECK_PRELUDE = R"SRC(// the witness checker: rows of the trace, not the coset
+#undef TAP
+#define TAP(g, col, back) g[(size_t)(col) * domain + ((i - (back)) & mask)]
+// table[2 t] += rows of this wave where term t does not vanish, table[2 t + 1] = min(.., the first of them): lanes are consecutive rows
+__device__ __forceinline__ void tally(u32* __restrict__ table, u32 t, u32 w, u32 i) {
+  const u64 bad = __ballot(w != 0u);
+  if (bad && (threadIdx.x & 63u) == 0u) {
+    atomicAdd(table + 2u * t, (u32)__popcll(bad));
+    atomicMin(table + 2u * t + 1u, i + (u32)__ffsll((long long)bad) - 1u);
+  }
+}
+)SRC";
+
+static std::string emit_check_source(const r0h_circuit* c) {
+  const Plan& pl = c->plan;
+  const std::vector<bool> lazy = lazy_additions(c);
+  const std::vector<Fuse> fuse(c->fp_step.size());
+  std::ostringstream os;
+  os << PRELUDE << CHECK_PRELUDE;
+  os << "// terms: " << pl.terms.size() << ", kernels: " << pl.cut.size() - 1 << "\n";
+  for (size_t k = 0; k + 1 < pl.cut.size(); k++) {
+    os << "extern \"C\" __global__ __launch_bounds__(256) void check_witness_" << k
+       << "(u32* __restrict__ table, const u32* __restrict__ g0, const u32* __restrict__ g1, const u32* __restrict__ g2,\n"
+          "    const u32* __restrict__ glob, const u32* __restrict__ mix, u32 po2, u32 with_accum) {\n"
+          "  const u32 domain = 1u << po2, mask = domain - 1u;\n"
+          "  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;\n";
+    std::vector<bool> done(c->fp_step.size(), false);
+    bool any_late = false;
+    for (uint32_t t = pl.cut[k]; t < pl.cut[k + 1]; t++) any_late = any_late || pl.late[t];
+    for (int late = 0; late < (any_late ? 2 : 1); late++) {
+      if (late) os << "  if (with_accum) {\n";
+      for (uint32_t t = pl.cut[k]; t < pl.cut[k + 1]; t++) {
+        if (pl.late[t] != (late != 0)) continue;
+        const Term& tm = pl.terms[t];
+        emit_var(c, tm.v, done, lazy, fuse, os);
+        for (uint32_t g : tm.conds) emit_var(c, g, done, lazy, fuse, os);
+        std::ostringstream val;
+        for (size_t g = 0; g < tm.conds.size(); g++) val << "fmul(v" << tm.conds[g] << ", ";
+        val << "v" << tm.v;
+        for (size_t g = 0; g < tm.conds.size(); g++) val << ")";
+        os << "  tally(table, " << t << "u, " << val.str() << ", i);\n";
+      }
+      if (late) os << "  }\n";
+    }
+    os << "}\n\n";
+  }
+  return os.str();
+}
+
 static const char* compile_in_process(const std::string& src, std::vector<char>& code) {
   hiprtcProgram prog;
   hiprtcResult r = hiprtcCreateProgram(&prog, src.c_str(), "eval_check.hip", 0, nullptr, nullptr);
@@ -638,6 +707,11 @@ __global__ void accum_fp_term_kernel(uint32_t* __restrict__ term, FpCols cols, F
   }
   *(uint4*)(term + 4 * (size_t)r) = make_uint4(prod.e[0], prod.e[1], prod.e[2], prod.e[3]);
 }
+// the checker's table before its kernels run: no row counted, no first row yet
+__global__ void check_table_init_kernel(uint32_t* __restrict__ table, uint32_t n_terms) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n_terms) { table[2 * t] = 0u; table[2 * t + 1] = 0xffffffffu; }
+}
 __global__ void accum_unpack_kernel(uint32_t* __restrict__ cols, const uint32_t* __restrict__ term, uint32_t po2) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   uint4 v = *(const uint4*)(term + 4 * (size_t)r);
@@ -665,10 +739,24 @@ const char* r0h_circuit_emit_hip(const uint32_t* blob, size_t n_words, char** so
   R0H_GUARD_END
 }
 
+static const char* read_code_object(const char* caller, const char* path, std::vector<char>& code) {
+  FILE* f = fopen(path, "rb");
+  R0H_REQUIRE(f, "%s: cannot open code object %s", caller, path);
+  fseek(f, 0, SEEK_END);
+  long sz = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  code.resize(sz > 0 ? (size_t)sz : 0);
+  size_t got = fread(code.data(), 1, code.size(), f);
+  fclose(f);
+  R0H_REQUIRE(got == code.size() && !code.empty(), "%s: short read of %s", caller, path);
+  return nullptr;
+}
+
 // how a circuit goes, also on every early path out of r0h_circuit_load: its module (if one was loaded) is unloaded with it
 struct CircuitUnload {
   void operator()(r0h_circuit* circuit) const {
     if (circuit->module) (void)hipModuleUnload(circuit->module);
+    if (circuit->check_module) (void)hipModuleUnload(circuit->check_module);
     delete circuit;
   }
 };
@@ -683,15 +771,7 @@ const char* r0h_circuit_load(r0h_ctx* ctx, const uint32_t* blob, size_t n_words,
   R0H_TRY_HIP(hipSetDevice(ctx->device));
   std::vector<char> code;
   if (code_object_path) {
-    FILE* f = fopen(code_object_path, "rb");
-    R0H_REQUIRE(f, "r0h_circuit_load: cannot open code object %s", code_object_path);
-    fseek(f, 0, SEEK_END);
-    long sz = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    code.resize(sz > 0 ? (size_t)sz : 0);
-    size_t got = fread(code.data(), 1, code.size(), f);
-    fclose(f);
-    R0H_REQUIRE(got == code.size() && !code.empty(), "r0h_circuit_load: short read of %s", code_object_path);
+    R0H_TRY(read_code_object("r0h_circuit_load", code_object_path, code));
   } else {
     R0H_TRY(compile_in_process(emit_source(c.get()), code));
   }
@@ -726,6 +806,58 @@ uint32_t r0h_circuit_group_size(const r0h_circuit* c, uint32_t group) { return c
 uint32_t r0h_circuit_n_global(const r0h_circuit* c) { return c ? c->n_global : 0; }
 uint32_t r0h_circuit_n_mix(const r0h_circuit* c) { return c ? c->n_mix : 0; }
 uint32_t r0h_circuit_n_taps(const r0h_circuit* c) { return c ? (uint32_t)c->taps.size() : 0; }
+uint32_t r0h_circuit_n_terms(const r0h_circuit* c) { return c ? (uint32_t)c->plan.terms.size() : 0; }
+
+const char* r0h_circuit_emit_hip_check(const uint32_t* blob, size_t n_words, char** source_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(blob && source_out, "r0h_circuit_emit_hip_check: NULL argument");
+  r0h_circuit c;
+  R0H_TRY(parse_blob(&c, blob, n_words));
+  make_plan(&c);
+  std::string src = emit_check_source(&c);
+  char* out = (char*)malloc(src.size() + 1);
+  R0H_REQUIRE(out, "r0h_circuit_emit_hip_check: out of memory");
+  memcpy(out, src.c_str(), src.size() + 1);
+  *source_out = out;
+  return nullptr;
+  R0H_GUARD_END
+}
+
+// the checker's module of `c`, under c->check_mu: from `code_object_path`, else compiled from the emitted text
+static const char* check_module_load(const r0h_circuit* c, const char* caller, const char* code_object_path) {
+  if (c->check_module) return nullptr;
+  R0H_TRY_HIP(hipSetDevice(c->ctx->device));
+  std::vector<char> code;
+  if (code_object_path) R0H_TRY(read_code_object(caller, code_object_path, code));
+  else R0H_TRY(compile_in_process(emit_check_source(c), code));
+  hipModule_t module = nullptr;
+  hipError_t e = hipModuleLoadData(&module, code.data());
+  R0H_REQUIRE(e == hipSuccess, "%s: hipModuleLoadData: %s", caller, hipGetErrorString(e));
+  std::vector<hipFunction_t> kernels;
+  for (size_t k = 0; k + 1 < c->plan.cut.size(); k++) {  // the checker's tallies are per term: the cuts must be this plan's
+    char name[64];
+    snprintf(name, sizeof name, "check_witness_%zu", k);
+    hipFunction_t fn;
+    if (hipModuleGetFunction(&fn, module, name) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipModuleUnload(module);
+      return make_error("%s: the code object has no %s (built from another source?)", caller, name);
+    }
+    kernels.push_back(fn);
+  }
+  c->check_module = module;
+  c->check_kernels.swap(kernels);
+  return nullptr;
+}
+
+const char* r0h_circuit_load_check(r0h_circuit* c, const char* code_object_path) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(c, "r0h_circuit_load_check: NULL argument");
+  std::lock_guard<std::mutex> lk(c->check_mu);
+  R0H_REQUIRE(!c->check_module, "r0h_circuit_load_check: the circuit's checker is loaded already");
+  return check_module_load(c, "r0h_circuit_load_check", code_object_path);
+  R0H_GUARD_END
+}
 
 }  // extern "C"
 namespace r0h {
@@ -917,4 +1049,78 @@ const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, con
   R0H_GUARD_END
 }
 
+const char* r0h_check_witness(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,
+                              const uint32_t* global, const uint32_t* mix, r0h_violation* out, size_t capacity, size_t* n_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && c && code && data && n_out && (out || !capacity), "r0h_check_witness: NULL argument");
+  R0H_REQUIRE((global || !c->n_global) && (mix || !c->n_mix || !accum), "r0h_check_witness: NULL globals");
+  R0H_REQUIRE(po2 >= 6 && po2 <= R0H_MAX_PO2, "r0h_check_witness: po2 %u outside [6, %u]", po2, R0H_MAX_PO2);
+  R0H_REQUIRE(c->ctx->device == ctx->device, "r0h_check_witness: the circuit lives on device %d, this context on device %d", c->ctx->device, ctx->device);
+  const size_t n = (size_t)1 << po2;
+  const r0h_buf* g[3] = {accum, code, data};
+  for (int k = 0; k < 3; k++) R0H_REQUIRE(!g[k] || n * c->group_size[k] * 4 <= g[k]->bytes, "r0h_check_witness: group %d buffer too small", k);
+  const uint32_t n_terms = (uint32_t)c->plan.terms.size();
+  *n_out = 0;
+  if (!n_terms) return nullptr;
+  {
+    std::lock_guard<std::mutex> lk(c->check_mu);
+    R0H_TRY(check_module_load(c, "r0h_check_witness", nullptr));
+  }
+  // parameters: globals and mix, then the table
+  const size_t n_params = (size_t)c->n_global + c->n_mix;
+  std::vector<uint32_t> params(n_params + 1, 0);
+  for (uint32_t i = 0; i < c->n_global; i++) { R0H_REQUIRE(global[i] < P, "r0h_check_witness: global[%u] not canonical", i); params[i] = global[i]; }
+  for (uint32_t i = 0; i < c->n_mix && accum; i++) { R0H_REQUIRE(mix[i] < P, "r0h_check_witness: mix[%u] not canonical", i); params[c->n_global + i] = mix[i]; }
+  DevBuf pbuf;
+  R0H_TRY(pbuf.alloc(ctx, (n_params + 1 + 2 * (size_t)n_terms) * 4));
+  R0H_TRY(stage_h2d(ctx, pbuf->ptr, params.data(), params.size() * 4));
+  const uint32_t *d_glob = u32(pbuf.get()), *d_mix = d_glob + c->n_global;
+  uint32_t* d_table = u32(pbuf.get()) + n_params + 1;
+  const uint32_t *g0 = accum ? u32(accum) : nullptr, *g1 = u32(code), *g2 = u32(data);
+  std::vector<uint32_t> table(2 * (size_t)n_terms);
+  {
+    double alg = 0;
+    for (int k = 0; k < 3; k++) alg += g[k] ? (double)n * c->group_size[k] * 4 : 0.0;
+    KScope ks(ctx, "check_witness", alg);
+    hipLaunchKernelGGL(check_table_init_kernel, dim3((n_terms + 255) / 256), dim3(256), 0, ctx->stream, d_table, n_terms);
+    R0H_TRY(launch_ok("r0h_check_witness"));
+    const uint32_t threads = n < 256 ? (uint32_t)n : 256u;  // whole waves: a lane per row, 2^po2 >= 64 rows
+    uint32_t with_accum = accum ? 1u : 0u;
+    for (hipFunction_t fn : c->check_kernels) {
+      void* args[] = {&d_table, &g0, &g1, &g2, &d_glob, &d_mix, &po2, &with_accum};
+      R0H_TRY_HIP(hipModuleLaunchKernel(fn, (uint32_t)(n / threads), 1, 1, threads, 1, 1, 0, ctx->stream, args, nullptr));
+    }
+  }
+  R0H_TRY_HIP(hipMemcpyAsync(table.data(), d_table, table.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  size_t found = 0;
+  for (uint32_t t = 0; t < n_terms; t++) {
+    if (!table[2 * t]) continue;
+    if (found < capacity) out[found] = r0h_violation{t, table[2 * t], table[2 * t + 1], 0};
+    found++;
+  }
+  *n_out = found;
+  return nullptr;
+  R0H_GUARD_END
+}
+
+const char* r0h_ctx_set_check_witness(r0h_ctx* ctx, int on) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_check_witness: ctx is NULL");
+  ctx->check_witness = on != 0;
+  for (r0h_ctx* h : ctx->helpers) h->check_witness = ctx->check_witness;
+  return nullptr;
+}
+
 }  // extern "C"
+
+namespace r0h {
+const char* require_witness(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,
+                            const uint32_t* global, const uint32_t* mix) {
+  r0h_violation first = {0, 0, 0, 0};
+  size_t n_bad = 0;
+  R0H_TRY(r0h_check_witness(ctx, c, po2, accum, code, data, global, mix, &first, 1, &n_bad));
+  R0H_REQUIRE(!n_bad, "%s: the witness violates %zu of the circuit's %zu constraint terms: term %u does not vanish on %u of 2^%u rows, first at row %u",
+              caller, n_bad, c->plan.terms.size(), first.term, first.rows, po2, first.first_row);
+  return nullptr;
+}
+}  // namespace r0h

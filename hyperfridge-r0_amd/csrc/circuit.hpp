@@ -1,5 +1,7 @@
 // Parsed circuit blob (include/r0hip_circuit.h) shared by circuit.hip (loading, eval_check) and prover.hip (sequencer).
 #pragma once
+#include <mutex>
+
 #include "../../include/r0hip_circuit.h"
 #include "internal.hpp"
 
@@ -58,6 +60,7 @@ struct Plan {                      // how the constraint program is cut into ker
   std::vector<Term> terms;         // flattened, in chain order
   std::vector<uint32_t> cut;       // kernel k owns terms [cut[k], cut[k+1])
   uint32_t n_pow = 0;
+  std::vector<bool> late;          // term t reaches an ACCUM tap or a word of the accumulation mix: it has no value before the mix is drawn
 };
 
 }  // namespace r0h
@@ -90,6 +93,11 @@ struct r0h_circuit {
   r0h::Plan plan;
   hipModule_t module = nullptr;
   std::vector<hipFunction_t> kernels;
+  // the witness checker (r0h_check_witness): its own module, compiled on first use -- or loaded from a code object by
+  // r0h_circuit_load_check -- under check_mu: one loaded circuit serves every context of its device, from any thread
+  mutable std::mutex check_mu;
+  mutable hipModule_t check_module = nullptr;
+  mutable std::vector<hipFunction_t> check_kernels;
 };
 
 namespace r0h {
@@ -98,5 +106,9 @@ const char* parse_blob(r0h_circuit* c, const uint32_t* blob, size_t n_words);
 // the log-derivative accumulation on the device (logup.hip): multiplicities into DATA, the ACCUM group, totals of the public accumulators
 // the rows of the in-circuit sponge over `words` written into the circuit's sponge columns of `data` (recursion.cpp: sponge_plant)
 const char* sponge_plant(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const uint32_t* words, size_t n_words, r0h_buf* data);
+// r0h_check_witness with the first violated term turned into an error that starts with `caller` (the sequencer under
+// r0h_ctx_set_check_witness); global / mix are host words as r0h_eval_check takes them
+const char* require_witness(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,
+                            const uint32_t* global, const uint32_t* mix);
 const char* logup_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum);
 }  // namespace r0h

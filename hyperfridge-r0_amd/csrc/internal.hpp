@@ -112,6 +112,7 @@ struct r0h_ctx {
   uint64_t session_resident_limit = 0;  // r0h_ctx_set_session_resident_limit (0: an eighth of the device's memory)
   void* session_rows = nullptr;   // session.cpp: the preflight row buffers of r0h_prove_elf, page-locked, kept from one call to the next (session_rows_free)
   std::vector<r0h_ctx*> helpers;  // further contexts of the same device, made on demand by r0h_prove_elf for its extra prover lanes; they go with this one
+  bool check_witness = false;     // r0h_ctx_set_check_witness: the sequencer runs r0h_check_witness on every segment before it commits ACCUM
   bool ktime_on = false;
   std::map<std::string, r0h::KTimer> ktimers;
 };

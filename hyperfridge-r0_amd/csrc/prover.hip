@@ -212,6 +212,7 @@ struct r0h_proof {
   size_t seal_globals_at = 0;   // where the seal's opening block of public inputs starts
   uint32_t data_root[8] = {0};  // the DATA group's Merkle root (what a session's common challenge is derived from)
   bool mix_drawn = false;
+  const r0h_buf *check_code = nullptr, *check_data = nullptr;  // r0h_ctx_set_check_witness: the witness columns proof_finish checks (the caller's buffers)
   r0h_proof(r0h_ctx* c, const r0h_circuit* ci, uint32_t p, const r0h::CircuitView& v)
       : ctx(c), circ(ci), po2(p), cv(v), io(c->hashfn, &c->p2_host), g_accum(v.group_size[R0H_GROUP_ACCUM], (size_t)4 << p),
         g_code(v.group_size[R0H_GROUP_CODE], (size_t)4 << p), g_data(v.group_size[R0H_GROUP_DATA], (size_t)4 << p),
@@ -231,6 +232,11 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* code, const r0h_cod
   Group &g_code = st.g_code, &g_data = st.g_data;
   ctx->prof.names.clear();
   st.global.assign(global, global + cv.n_global);
+  if (ctx->check_witness) {
+    st.check_code = code ? code : cc->witness;
+    st.check_data = data;
+    R0H_REQUIRE(st.check_code, "prove_segment: checking the witness needs the CODE columns, and this CODE commitment keeps none");
+  }
 
   phase(ctx, "transcript_seed");
   {
@@ -307,6 +313,10 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
     R0H_TRY(sc.alloc(ctx, ((size_t)g_data.count << (po2 + 2)) * 4, &g_data.evaluated));
     R0H_TRY(r0h_batch_expand_into_evaluate_ntt(ctx, g_data.evaluated, g_data.coeffs, g_data.count, po2, 2));
     g_data.tree.matrix = g_data.evaluated;
+  }
+  if (st.check_data) {
+    phase(ctx, "check_witness");
+    R0H_TRY(require_witness("prove_segment", ctx, circ, po2, accum, st.check_code, st.check_data, global, mix.data()));
   }
   phase(ctx, "commit_accum");
   R0H_TRY(group_from_witness(ctx, sc, g_accum, accum, po2));

@@ -6,6 +6,10 @@
 //                    [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]
 // --hashfn sha-256 proves (and with --verify 1 checks) the segments under the SHA-256 hash suite; receipts name Poseidon2 only, so it is
 // refused together with any of the receipt options and with --elf.
+// --check-witness 1 (both modes; [--check-code-object file.hsaco] [--term-names file.txt]) turns r0h_ctx_set_check_witness on: every segment's
+// witness is checked on the device before its ACCUM group is committed, and a violated segment ends the run with the term, its row count
+// and its first row -- and the term's name, from --term-names or <circuit>.terms.txt beside the blob (one name per line, in term
+// order: tools/gen_circuit.py --names; the build writes them for the trace and image circuits).
 // With --receipt-out / --receipt-dir every segment is proved for a claim (risc0-zkvm `ReceiptClaim`): the session's system states
 // are synthetic names (there is no executor here), segment k runs from state k to state k+1, all but the last end in SystemSplit,
 // the last halts with the journal's output; the claim's eight naming words are planted as the segment's public inputs.  The image
@@ -38,8 +42,14 @@
 
 #include "../../include/r0hip.h"
 
+static std::vector<std::string> term_names;  // --check-witness: what a violated term is called (empty: its number is all there is)
 static void die(const char* what, const char* err) {
   fprintf(stderr, "r0h_prove: %s: %s\n", what, err);
+  const char* at = strstr(err, "the witness violates");
+  if (at && (at = strstr(at, ": term "))) {
+    const unsigned long t = strtoul(at + 7, nullptr, 10);
+    if (t < term_names.size()) fprintf(stderr, "r0h_prove: term %lu is constraint \"%s\"\n", t, term_names[t].c_str());
+  }
   r0h_free_error(err);
   exit(2);
 }
@@ -52,14 +62,17 @@ static void die(const char* what, const char* err) {
 int main(int argc, char** argv) {
   if (argc < 2 || !strcmp(argv[1], "--help") || !strcmp(argv[1], "-h")) {
     printf("usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--hashfn poseidon2|sha-256] [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]\n"
-           "       r0h_prove <trace.r0c> --elf guest.elf --input words.bin [--code-object file.hsaco] [--po2 N] [--device D] --receipt-out file.json\n%s\n", r0h_version());
+           "       r0h_prove <trace.r0c> --elf guest.elf --input words.bin [--code-object file.hsaco] [--po2 N] [--device D] --receipt-out file.json\n"
+           "       --check-witness 1 [--check-code-object file.hsaco] [--term-names file.txt]: check every segment's witness on the device before its ACCUM group is committed; "
+           "a violated segment ends the run with the constraint term, its name, how many rows violate it and the first of them\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   std::string blob_path = argv[1], co_path, seal_out, receipt_out, receipt_dir, journal_text, elf_path, input_path;
   std::string hashfn = "poseidon2";         // --hashfn: the hash suite of the synthetic-circuit mode (seals only)
   std::map<std::string, std::string> camt;  // --camt53-response and what goes with it
   std::string receipt_prefix;               // --receipt-prefix P: the reference's file name, P-Receipt-<image id>-latest.json (host/src/main.rs:312-316)
-  std::string image_circuit_path, image_co_path;
+  std::string image_circuit_path, image_co_path, check_co_path, term_names_path;
+  unsigned check_witness = 0;
   unsigned po2 = 16, segments = 1, device = 0, contexts = 1, verify = 0, receipts = 1;
   unsigned long long seed = 1;
   for (int i = 2; i + 1 < argc; i += 2) {
@@ -72,6 +85,9 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--seal-out")) seal_out = argv[i + 1];
     else if (!strcmp(argv[i], "--verify")) verify = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--hashfn")) hashfn = argv[i + 1];
+    else if (!strcmp(argv[i], "--check-witness")) check_witness = (unsigned)atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--check-code-object")) check_co_path = argv[i + 1];
+    else if (!strcmp(argv[i], "--term-names")) term_names_path = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
     else if (!strcmp(argv[i], "--journal")) journal_text = argv[i + 1];
@@ -101,6 +117,24 @@ int main(int argc, char** argv) {
   std::vector<uint32_t> blob((size_t)sz / 4);
   if (fread(blob.data(), 4, blob.size(), f) != blob.size()) { fprintf(stderr, "r0h_prove: short read\n"); return 1; }
   fclose(f);
+  if (check_witness) {
+    std::string names = term_names_path;
+    if (names.empty() && blob_path.size() > 4 && blob_path.compare(blob_path.size() - 4, 4, ".r0c") == 0) names = blob_path.substr(0, blob_path.size() - 4) + ".terms.txt";
+    FILE* g = names.empty() ? nullptr : fopen(names.c_str(), "rb");
+    if (!g && !term_names_path.empty()) { fprintf(stderr, "r0h_prove: cannot open %s\n", names.c_str()); return 1; }
+    char line[256];
+    while (g && fgets(line, sizeof line, g)) {
+      line[strcspn(line, "\r\n")] = 0;
+      term_names.push_back(line);
+    }
+    if (g) fclose(g);
+  }
+  // --check-witness: the context's switch, and the checker's module now (from its code object, else compiled in-process) rather than inside the first proof
+  auto arm_checker = [&](r0h_ctx* ctx, r0h_circuit* circ) {
+    if (!check_witness) return;
+    CHECK(r0h_ctx_set_check_witness(ctx, 1));
+    CHECK(r0h_circuit_load_check(circ, check_co_path.empty() ? nullptr : check_co_path.c_str()));
+  };
   if (!elf_path.empty()) {  // prove(env, elf)
     auto slurp = [](const std::string& path, std::vector<uint8_t>* out) {
       FILE* g = fopen(path.c_str(), "rb");
@@ -155,6 +189,7 @@ int main(int argc, char** argv) {
     for (Worker& w : workers) {
       CHECK(r0h_ctx_create((int)device, &w.ctx));
       CHECK(r0h_circuit_load(w.ctx, blob.data(), blob.size(), co_path.empty() ? nullptr : co_path.c_str(), &w.circ));
+      arm_checker(w.ctx, w.circ);
       if (!image_blob.empty()) {  // every receipt then carries an image proof: `receipt.verify(image_id)` needs no ELF
         CHECK(r0h_circuit_load(w.ctx, image_blob.data(), image_blob.size(), image_co_path.empty() ? nullptr : image_co_path.c_str(), &w.image));
         CHECK(r0h_ctx_set_image_circuit(w.ctx, w.image));
@@ -294,6 +329,7 @@ int main(int argc, char** argv) {
     CHECK(r0h_ctx_create((int)device, &ln.ctx));
     CHECK(r0h_ctx_set_hashfn(ln.ctx, hashfn.c_str()));
     CHECK(r0h_circuit_load(ln.ctx, blob.data(), blob.size(), co_path.empty() ? nullptr : co_path.c_str(), &ln.circ));
+    arm_checker(ln.ctx, ln.circ);
     CHECK(r0h_buf_alloc(ln.ctx, (size_t)r0h_circuit_group_size(ln.circ, R0H_GROUP_CODE) * n * 4, &ln.code));
     CHECK(r0h_buf_alloc(ln.ctx, (size_t)r0h_circuit_group_size(ln.circ, R0H_GROUP_DATA) * n * 4, &ln.data));
     ln.global.resize(r0h_circuit_n_global(ln.circ) + 1);

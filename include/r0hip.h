@@ -162,6 +162,29 @@ const char* r0h_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0
 const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum,
                            const r0h_buf* eval_code, const r0h_buf* eval_data, const uint32_t* global_host,
                            const uint32_t* mix_host, const uint32_t poly_mix[4], r0h_buf* check);
+/* ---- the witness checker: which constraint a witness violates, and where.  Term t of a circuit is the t-th AndEqz of its
+ * constraint program once the AndCond gates are flattened into their inner terms -- numbered by the power of poly_mix it is folded
+ * with, 0 <= t < r0h_circuit_n_terms -- and its value on row r of a 2^po2-row trace is the AndEqz value times the product of its
+ * gates, tap (group, column, back) read from the WITNESS columns (natural row order, not the coset) at row (r - back) mod 2^po2.
+ * The witness satisfies the circuit iff every term is zero on every row: no row is exempt, the circuit divides by x^N - 1.
+ * r0h_check_witness evaluates every term on every row on the device (generated HIP like eval_check's, one lane per row) and reports
+ * the violated terms in term order: `rows` rows leave the term non-zero, the first of them is `first_row`.  n_out is their number,
+ * also beyond `capacity`.  accum == NULL checks only the terms that reach no ACCUM tap and no word of the mix -- what can be checked
+ * before the mix is drawn (mix_host may then be NULL).  The checker's text (r0h_circuit_emit_hip_check, pure host) is compiled
+ * in-process on first use and kept with the circuit; r0h_circuit_load_check loads a gfx950 code object built from that text instead.
+ * Lookups of values outside their table are r0h_logup_multiplicities' to report, not the checker's. */
+typedef struct { uint32_t term, rows, first_row, reserved; } r0h_violation;
+const char* r0h_circuit_emit_hip_check(const uint32_t* blob, size_t n_words, char** source_out);
+const char* r0h_circuit_load_check(r0h_circuit* c, const char* code_object_path /* NULL: compile in-process now */);
+uint32_t r0h_circuit_n_terms(const r0h_circuit* c);
+const char* r0h_check_witness(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code,
+                              const r0h_buf* data, const uint32_t* global_host, const uint32_t* mix_host, r0h_violation* out,
+                              size_t capacity, size_t* n_out);
+/* on != 0: from now on r0h_prove_segment*, r0h_proof_finish and the sessions of this context run the checker on every segment
+ * before they commit its ACCUM group, and a violated segment returns an error that names the first violated term, its row count
+ * and its first row instead of a seal no verifier accepts.  Between r0h_proof_begin* and r0h_proof_finish the CODE and DATA
+ * witness buffers must then stay as they were given.  Off (the default): nothing is checked, seals and timing are unchanged. */
+const char* r0h_ctx_set_check_witness(r0h_ctx* ctx, int on);
 
 /* ---- the sequencer: risc0-circuit-rv32im `SegmentProver::prove` + risc0-zkp `Prover::{commit_group, finalize}` ---- */
 /* code/data: witness columns resident in device memory ([group_size][2^po2]); global: host words.

@@ -455,11 +455,33 @@ def generate_image():
     return image_circuit.generate(Builder, E, fp4_mul_sym, OP_GET)
 
 
+def term_names(circuit):
+    """What the constraint terms of `circuit` (a shape's name) are called, in term order: term t is the t-th AndEqz of the flattened
+    constraint program, the number r0h_check_witness reports.  The trace and image circuits chain their generators' constraint lists
+    one AndEqz each, ungated, so a term carries its constraint's name; the synthetic shapes have no names: ordinals."""
+    if circuit == "trace":
+        return [name for name, _, _, _ in trace_constraints()[1]]
+    if circuit == "image":
+        import image_circuit
+        return [name for name, _, _, _ in image_circuit.constraints(Builder, E, fp4_mul_sym)[1]]
+    words, _ = generate(**SHAPES[circuit])
+    at = 3
+    while words[at] != SEC_POLY:
+        at += 2 + words[at + 1]
+    n_steps = words[at + 2]
+    return ["term:%d" % t for t in range(sum(1 for k in range(n_steps) if words[at + 4 + 4 * k] == OP_AND_EQZ))]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("shape", choices=sorted(SHAPES) + ["trace", "image"])
     ap.add_argument("out")
+    ap.add_argument("--names", action="store_true", help="write the names of the shape's constraint terms, one per line in term order, instead of the blob")
     args = ap.parse_args()
+    if args.names:
+        with open(args.out, "w") as f:
+            f.write("".join(name + "\n" for name in term_names(args.shape)))
+        return 0
     words, info = generate_trace() if args.shape == "trace" else generate_image() if args.shape == "image" else generate(**SHAPES[args.shape])
     with open(args.out, "wb") as f:
         f.write(struct.pack("<%dI" % len(words), *words))

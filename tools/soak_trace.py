@@ -5,7 +5,10 @@ compact preflight rows into the trace circuit's witness (r0h_trace_witgen) -- wh
 and proves each; the seal must equal the CPU oracle's word for word and verify bound to the control root.  Every eighth run is also
 tampered with (one register value read back wrong) and every other eighth carries a wrong result that keeps memory consistent (a dead
 write): both verifiers must refuse both.
-usage: python tools/soak_trace.py [minutes]"""
+With --device-check the witness checker (r0h_check_witness) looks at every witness on the device, where naming a broken constraint
+used to take the numpy evaluation of tools/gen_circuit.py check_trace_rows: every honest witness must violate no term -- before the
+mix and, under a random mix, with its accumulation -- and every tampered one must violate some, which are counted by name.
+usage: python tools/soak_trace.py [minutes] [--device-check]"""
 import os
 import sys
 import time
@@ -91,11 +94,28 @@ def dead_write_lie(rows, bounds, rng):
 
 
 def main():
-    budget = float(sys.argv[1]) * 60 if len(sys.argv) > 1 else 120.0
+    args = [a for a in sys.argv[1:] if a != "--device-check"]
+    device_check = "--device-check" in sys.argv[1:]
+    budget = float(args[0]) * 60 if args else 120.0
     orc, hal = orc_binding.load(), r0.Hal(0)
     blob = np.fromfile(os.path.join(ROOT, "circuits", "trace.r0c"), dtype=np.uint32)
     oc, gc = orc.circuit(blob), hal.load_circuit(blob)
     rng = np.random.default_rng(2026)
+    named = {}
+    if device_check:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from gen_circuit import term_names
+        names = term_names("trace")
+
+    def violated(po2, code, dev, glob):
+        """the names of the terms the witness violates: the terms that need no accumulation, then all of them under a random mix"""
+        early = hal.check_witness(gc, po2, code, dev, glob)
+        mix = np.array([orc.enc(int(v)) for v in rng.integers(0, 2013265921, gc.n_mix)], dtype=np.uint32)
+        accum = hal.accum_public(gc, po2, code, dev, glob, mix)
+        late = hal.check_witness(gc, po2, code, dev, glob, accum, mix)
+        accum.free()
+        assert [v for v in late if v in early] == early
+        return [names[t] for t, _, _ in late]
     fixed = {}
     t0, n, rows_total, taken, tampered, lied, parity = time.time(), 0, 0, 0, 0, 0, 0
     while time.time() - t0 < budget:
@@ -122,6 +142,9 @@ def main():
             sys.exit(1)
         glob[r0.TRACE_GAMMA:r0.TRACE_GAMMA + 16] = [orc.enc(int(v)) for v in rng.integers(0, 2013265921, 16)]  # one seal outside a session: any challenge
         glob = hal.logup_totals(gc, po2, code, dev, glob)
+        if device_check and violated(po2, code, dev, glob):
+            print("FAILED on program %d: the device's checker objects to an honest witness: %s" % (n, violated(po2, code, dev, glob)[:8]))
+            sys.exit(1)
         seal = hal.prove_segment(gc, po2, cc, dev, glob)
         if oc.verify(seal, code_root=root)[0] != 0 or r0.verify_seal(blob, seal, code_root=root)[0] != 0:
             print("FAILED on program %d (%d rows, po2 %d): a verifier refuses the device's seal" % (n, len(rows), po2))
@@ -140,6 +163,13 @@ def main():
             if oc.verify(forged, code_root=root)[0] != 4 or r0.verify_seal(blob, forged, code_root=root)[0] != 4:
                 print("FAILED on program %d: an inconsistent register read was accepted" % n)
                 sys.exit(1)
+            if device_check:
+                bad_terms = violated(po2, code, dev, hal.logup_totals(gc, po2, code, dev, glob))
+                if not bad_terms:
+                    print("FAILED on program %d: the device's checker is silent on an inconsistent register read" % n)
+                    sys.exit(1)
+                for nm in bad_terms:
+                    named[nm] = named.get(nm, 0) + 1
             tampered += 1
         if n % 8 == 4:  # a register whose value changes between a dead write and the next write of it: refused by both verifiers
             lie = dead_write_lie(rows, bounds, rng)
@@ -149,6 +179,13 @@ def main():
                 if oc.verify(forged, code_root=root)[0] != 4 or r0.verify_seal(blob, forged, code_root=root)[0] != 4:
                     print("FAILED on program %d: a wrong result was accepted" % n)
                     sys.exit(1)
+                if device_check:
+                    bad_terms = violated(po2, code, dev, hal.logup_totals(gc, po2, code, dev, glob))
+                    if not bad_terms:
+                        print("FAILED on program %d: the device's checker is silent on a wrong result" % n)
+                        sys.exit(1)
+                    for nm in bad_terms:
+                        named[nm] = named.get(nm, 0) + 1
                 lied += 1
         dev.free()
         n += 1
@@ -159,6 +196,9 @@ def main():
     print("soak ok: %d random executions (%d cycles, %d taken branches and jumps): device witness == host reference word for word, both verifiers accept every seal "
           "bound to the control root, %d seals proved by the oracle too and equal word for word; %d tampered runs (a register read back wrong) and %d runs with a "
           "dead register's value altered refused by both" % (n, rows_total, taken, parity, tampered, lied))
+    print("%.1f programs per minute%s" % (60.0 * n / (time.time() - t0), " with --device-check" if device_check else ""))
+    if device_check:
+        print("device check: every honest witness clean; the tampered ones violate %s" % ", ".join("%s x%d" % kv for kv in sorted(named.items(), key=lambda kv: -kv[1])[:12]))
 
 
 if __name__ == "__main__":
