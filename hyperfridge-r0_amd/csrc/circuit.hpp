@@ -1,4 +1,5 @@
-// Parsed circuit blob (include/r0hip_circuit.h) shared by circuit.hip (loading, eval_check) and prover.hip (sequencer).
+// Parsed circuit blob (include/r0hip_circuit.h): filled by blob.cpp (parse_blob), planned and turned into source text by
+// evalcheck_emit.cpp, compiled, loaded and launched by circuit.hip, walked by prover.hip (sequencer) and verify.cpp.
 #pragma once
 #include <mutex>
 
@@ -13,7 +14,6 @@ struct Step { uint32_t op, a, b, c; };
 struct CodeCol { uint32_t kind, param; };
 struct DataCol { uint32_t kind, a, b, c, e; };
 struct AccCol { uint32_t first, a, b; };
-struct AccFp { uint32_t n_f; uint32_t col[3][4]; };  // running product of up to three tuple fingerprints (R0H_SEC_ACCUM_FP)
 struct Term { uint32_t pow, v; std::vector<uint32_t> conds; };
 // the log-derivative argument (R0H_SEC_LOGUP): fractions numerator / (sum of challenge x linear form), four to an accumulator
 struct LfTerm { uint32_t coef, global, col; };  // canonical coefficient; public input + 1 or 0; column ref + 1 or 0 (the constant one)
@@ -80,7 +80,6 @@ struct r0h_circuit {
   std::vector<r0h::CodeCol> code_cols;
   std::vector<r0h::DataCol> data_cols;
   std::vector<r0h::AccCol> acc_cols;
-  std::vector<r0h::AccFp> acc_fp;
   r0h::Logup logup;
   uint32_t period = 0;               // R0H_SEC_PERIODIC: what CODE columns of kind 6 repeat, [n_periodic][period] canonical values
   std::vector<uint32_t> periodic;
@@ -103,12 +102,17 @@ struct r0h_circuit {
 namespace r0h {
 // fills the host tables of `c` from a blob (no device work); validates every index the sequencer and the verifier follow
 const char* parse_blob(r0h_circuit* c, const uint32_t* blob, size_t n_words);
-// the log-derivative accumulation on the device (logup.hip): multiplicities into DATA, the ACCUM group, totals of the public accumulators
+// evalcheck_emit.cpp: c->plan from the parsed tables (flattened terms, their cut into kernels), then the eval_check and the
+// witness-checker source text of that plan (kernels eval_check_<k> / check_witness_<k>, one per cut)
+void make_plan(r0h_circuit* c);
+std::string emit_source(const r0h_circuit* c);
+std::string emit_check_source(const r0h_circuit* c);
 // the rows of the in-circuit sponge over `words` written into the circuit's sponge columns of `data` (recursion.cpp: sponge_plant)
 const char* sponge_plant(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const uint32_t* words, size_t n_words, r0h_buf* data);
 // r0h_check_witness with the first violated term turned into an error that starts with `caller` (the sequencer under
 // r0h_ctx_set_check_witness); global / mix are host words as r0h_eval_check takes them
 const char* require_witness(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,
                             const uint32_t* global, const uint32_t* mix);
+// the log-derivative accumulation on the device (logup.hip): multiplicities into DATA, the ACCUM group, totals of the public accumulators
 const char* logup_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum);
 }  // namespace r0h

@@ -278,6 +278,14 @@ __global__ void prefix_apply_kernel(uint32_t* __restrict__ io, const uint32_t* _
   }
 }
 
+// what a scan leaves, n = 2^po2 packed extension elements, as the four columns of 2^po2 words an ACCUM accumulator is stored in
+__global__ void ext_unpack_kernel(uint32_t* __restrict__ cols, const uint32_t* __restrict__ packed, uint32_t po2) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= (1u << po2)) return;
+  const uint4 v = *(const uint4*)(packed + 4 * (size_t)r);
+  cols[r] = v.x; cols[((size_t)1 << po2) + r] = v.y; cols[((size_t)2 << po2) + r] = v.z; cols[((size_t)3 << po2) + r] = v.w;
+}
+
 // synthetic division by (x - z): q[i] = sum_{j>i} p[j] z^(j-i-1), remainder = sum_j p[j] z^j
 struct DivPowers {
   Fp4 z, zE, zChunk;  // z, z^E, z^chunk
@@ -647,6 +655,12 @@ const char* r0h_poly_divide(r0h_ctx* ctx, r0h_buf* poly, uint32_t n, const uint3
 }  // extern "C"
 
 namespace r0h {
+const char* unpack_ext_columns(r0h_ctx* ctx, uint32_t* cols, const uint32_t* packed, uint32_t po2) {
+  const uint32_t n = 1u << po2, threads = n < 256 ? n : 256;
+  hipLaunchKernelGGL(ext_unpack_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, cols, packed, po2);
+  return launch_ok("ext_unpack_kernel");
+}
+
 // polys: a buffer of n-coefficient extension polynomials (AoS, natural order); job j divides polynomial poly_idx[j] in place by
 // (x - points[4j..4j+4)).  Jobs on the same polynomial are applied in the order given.  remainders_host (4 words per job, may be
 // NULL) is filled by ONE blocking copy after everything has been enqueued.

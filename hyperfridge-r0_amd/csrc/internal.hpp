@@ -186,6 +186,9 @@ const char* bit_reverse_ext(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t 
 const char* ntt_init_device();
 // batched synthetic division (DEEP step): job j divides polynomial poly_idx[j] of `polys` by (x - points[4j..]); one read-back
 const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* points, uint32_t n_jobs, uint32_t* remainders_host);
+// 2^po2 packed extension elements at `packed` (what r0h_prefix_products / r0h_prefix_sums leave) into the four columns of 2^po2 words
+// at `cols`: how the product accumulators (circuit.hip) and the log-derivative ones (logup.hip) reach the ACCUM group (device pointers)
+const char* unpack_ext_columns(r0h_ctx* ctx, uint32_t* cols, const uint32_t* packed, uint32_t po2);
 // the CODE launch of r0h_witgen alone: the fixed CODE columns of `c` at 2^po2 rows into `code` (stream-ordered, not synchronised)
 const char* witgen_code(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* code);
 // the committed CODE group of `c` at 2^po2 rows: CODE from the pool, witgen_code, r0h_code_commit_new

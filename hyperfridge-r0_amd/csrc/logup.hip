@@ -232,12 +232,6 @@ __global__ void logup_chain_kernel(uint32_t* __restrict__ accum, const uint32_t*
   uint32_t* cell = accum + ((size_t)col << po2) + r;
   *cell = add(*cell, scanned[4 * (size_t)(r - 1) + (col & 3u)]);
 }
-__global__ void logup_unpack_kernel(uint32_t* __restrict__ cols, const uint32_t* __restrict__ scanned, uint32_t po2) {
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= (1u << po2)) return;
-  const uint4 v = *(const uint4*)(scanned + 4 * (size_t)r);
-  cols[r] = v.x; cols[((size_t)1 << po2) + r] = v.y; cols[((size_t)2 << po2) + r] = v.z; cols[((size_t)3 << po2) + r] = v.w;
-}
 }  // namespace
 
 // standalone accumulators: terms -> running sums; totals_out (host, 4 words each) if wanted, ACCUM columns if `accum`
@@ -252,10 +246,7 @@ static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t
   for (uint32_t k = 0; k < n_own; k++) {
     r0h_buf view = buf_view(terms.get(), (size_t)k * n * 16, (size_t)n * 16);
     R0H_TRY(r0h_prefix_sums(ctx, &view, n));
-    if (accum) {
-      hipLaunchKernelGGL(logup_unpack_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(accum) + ((size_t)(4 * (n_chain + k)) << po2), (const uint32_t*)view.ptr, po2);
-      R0H_TRY(launch_ok("logup_unpack_kernel"));
-    }
+    if (accum) R0H_TRY(unpack_ext_columns(ctx, u32(accum) + ((size_t)(4 * (n_chain + k)) << po2), (const uint32_t*)view.ptr, po2));
     if (totals_out) R0H_TRY(r0h_buf_d2h(ctx, &view, (size_t)(n - 1) * 16, totals_out + 4 * k, 16));
   }
   return nullptr;

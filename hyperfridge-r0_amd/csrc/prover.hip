@@ -14,29 +14,6 @@
 
 namespace r0h {
 
-// flat view of the circuit tables the sequencer walks
-struct CircuitView {
-  uint32_t group_size[3];
-  uint32_t n_taps, n_regs, n_combos, n_global, n_mix;
-  std::vector<uint32_t> tap_offset, tap_back, reg_group, reg_offset, reg_first, reg_size, reg_combo;
-  const uint32_t* combo_begin; const uint32_t* combo_backs;
-  uint32_t group_tap_begin[4];
-  const uint32_t* blob; size_t blob_words;
-};
-static void circuit_view(const r0h_circuit* c, CircuitView* v) {
-  memcpy(v->group_size, c->group_size, sizeof v->group_size);
-  v->n_taps = (uint32_t)c->taps.size(); v->n_regs = (uint32_t)c->regs.size(); v->n_combos = (uint32_t)c->combo_begin.size() - 1;
-  v->n_global = c->n_global; v->n_mix = c->n_mix;
-  for (const Tap& t : c->taps) { v->tap_offset.push_back(t.offset); v->tap_back.push_back(t.back); }
-  for (const Reg& r : c->regs) {
-    v->reg_group.push_back(r.group); v->reg_offset.push_back(r.offset); v->reg_first.push_back(r.first_tap);
-    v->reg_size.push_back(r.size); v->reg_combo.push_back(r.combo);
-  }
-  v->combo_begin = c->combo_begin.data(); v->combo_backs = c->combo_backs.data();
-  memcpy(v->group_tap_begin, c->group_tap_begin, sizeof v->group_tap_begin);
-  v->blob = c->blob.data(); v->blob_words = c->blob.size();
-}
-
 // ------------------------------------------------------------------ transcript
 // The generator and the slice hash are the context's hash suite (internal.hpp HashSuite: Poseidon2 or SHA-256); the order of
 // commits, writes and draws below is the same under both.
@@ -204,7 +181,6 @@ struct r0h_proof {
   r0h_ctx* ctx;
   const r0h_circuit* circ;
   uint32_t po2;
-  r0h::CircuitView cv;
   r0h::Scope sc;
   r0h::WriteIop io;
   r0h::Group g_accum, g_code, g_data, g_check;
@@ -213,9 +189,9 @@ struct r0h_proof {
   uint32_t data_root[8] = {0};  // the DATA group's Merkle root (what a session's common challenge is derived from)
   bool mix_drawn = false;
   const r0h_buf *check_code = nullptr, *check_data = nullptr;  // r0h_ctx_set_check_witness: the witness columns proof_finish checks (the caller's buffers)
-  r0h_proof(r0h_ctx* c, const r0h_circuit* ci, uint32_t p, const r0h::CircuitView& v)
-      : ctx(c), circ(ci), po2(p), cv(v), io(c->hashfn, &c->p2_host), g_accum(v.group_size[R0H_GROUP_ACCUM], (size_t)4 << p),
-        g_code(v.group_size[R0H_GROUP_CODE], (size_t)4 << p), g_data(v.group_size[R0H_GROUP_DATA], (size_t)4 << p),
+  r0h_proof(r0h_ctx* c, const r0h_circuit* ci, uint32_t p)
+      : ctx(c), circ(ci), po2(p), io(c->hashfn, &c->p2_host), g_accum(ci->group_size[R0H_GROUP_ACCUM], (size_t)4 << p),
+        g_code(ci->group_size[R0H_GROUP_CODE], (size_t)4 << p), g_data(ci->group_size[R0H_GROUP_DATA], (size_t)4 << p),
         g_check(R0H_CHECK_SIZE, (size_t)4 << p) {}
 };
 
@@ -226,12 +202,11 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* code, const r0h_cod
   r0h_ctx* ctx = st.ctx;
   const r0h_circuit* circ = st.circ;
   const uint32_t po2 = st.po2;
-  CircuitView& cv = st.cv;
   Scope& sc = st.sc;
   WriteIop& io = st.io;
   Group &g_code = st.g_code, &g_data = st.g_data;
   ctx->prof.names.clear();
-  st.global.assign(global, global + cv.n_global);
+  st.global.assign(global, global + circ->n_global);
   if (ctx->check_witness) {
     st.check_code = code ? code : cc->witness;
     st.check_data = data;
@@ -242,10 +217,10 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* code, const r0h_cod
   {
     // the seal opens with every public input and po2; the transcript takes the early ones here and the late ones (inputs that depend
     // on commitments made outside this proof, R0H_SEC_LATE) after the DATA group is committed
-    for (uint32_t i = 0; i < cv.n_global - circ->n_late; i++) R0H_REQUIRE(global[i] < P, "prove_segment: global word not canonical");
+    for (uint32_t i = 0; i < circ->n_global - circ->n_late; i++) R0H_REQUIRE(global[i] < P, "prove_segment: global word not canonical");
     transcript_open(io, *circ, global, po2);
     st.seal_globals_at = io.proof.size();
-    io.write(global, cv.n_global);
+    io.write(global, circ->n_global);
     const uint32_t po2_word = enc(po2);
     io.write(&po2_word, 1);
   }
@@ -277,7 +252,7 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* code, const r0h_cod
 
 // the late public inputs enter the transcript (and the seal's opening block), then the accumulation mix is drawn
 static const char* proof_late(r0h_proof& st, const uint32_t* late) {
-  const uint32_t n_late = st.circ->n_late, n_early = st.cv.n_global - n_late;
+  const uint32_t n_late = st.circ->n_late, n_early = st.circ->n_global - n_late;
   R0H_REQUIRE(!st.mix_drawn, "r0h_proof_late: the accumulation mix has been drawn already");
   if (n_late) {
     R0H_REQUIRE(late, "r0h_proof_late: NULL argument");
@@ -286,8 +261,8 @@ static const char* proof_late(r0h_proof& st, const uint32_t* late) {
     memcpy(st.io.proof.data() + st.seal_globals_at + n_early, late, (size_t)n_late * 4);
     st.io.commit_elems(late, n_late);
   }
-  st.mix.resize(st.cv.n_mix);
-  for (uint32_t i = 0; i < st.cv.n_mix; i++) st.mix[i] = st.io.rng.elem();
+  st.mix.resize(st.circ->n_mix);
+  for (uint32_t i = 0; i < st.circ->n_mix; i++) st.mix[i] = st.io.rng.elem();
   st.mix_drawn = true;
   phase(st.ctx, "accum");
   return nullptr;
@@ -301,7 +276,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
   const r0h_circuit* circ = st.circ;
   const uint32_t po2 = st.po2;
   const size_t n = (size_t)1 << po2, domain = n * R0H_INV_RATE;
-  CircuitView& cv = st.cv;
+  const uint32_t n_taps = (uint32_t)circ->taps.size();
   Scope& sc = st.sc;
   WriteIop& io = st.io;
   Group &g_accum = st.g_accum, &g_code = st.g_code, &g_data = st.g_data, &g_check = st.g_check;
@@ -334,48 +309,45 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
   phase(ctx, "evaluate_at_z");
   const Fp4 z = io.rng.ext(), z4 = fp4_pow(z, 4);
   const uint32_t back_one = rou_rev(po2);
-  const uint32_t n_u = cv.n_taps + R0H_CHECK_SIZE;
+  const uint32_t n_u = n_taps + R0H_CHECK_SIZE;
   std::vector<Fp4> all_xs(n_u), coeff_u(n_u);
   std::vector<uint32_t> which(n_u);
   r0h_buf* d_eval = nullptr;
   R0H_TRY(sc.alloc(ctx, (size_t)n_u * 16, &d_eval));
-  for (uint32_t t = 0; t < cv.n_taps; t++) {
-    all_xs[t] = scale(z, fpow(back_one, cv.tap_back[t]));
-    which[t] = cv.tap_offset[t];
+  for (uint32_t t = 0; t < n_taps; t++) {
+    all_xs[t] = scale(z, fpow(back_one, circ->taps[t].back));
+    which[t] = circ->taps[t].offset;
   }
-  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) { all_xs[cv.n_taps + i] = z4; which[cv.n_taps + i] = i; }
+  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) { all_xs[n_taps + i] = z4; which[n_taps + i] = i; }
   for (int g = 0; g < 3; g++) {
-    uint32_t b = cv.group_tap_begin[g], e = cv.group_tap_begin[g + 1];
+    uint32_t b = circ->group_tap_begin[g], e = circ->group_tap_begin[g + 1];
     if (e == b) continue;
     r0h_buf view = buf_view(d_eval, (size_t)b * 16, (size_t)(e - b) * 16);
     R0H_TRY(evaluate_any(ctx, grp[g]->coeffs, po2, which.data() + b, (const uint32_t*)(all_xs.data() + b), e - b, &view, true));
   }
   {
-    r0h_buf view = buf_view(d_eval, (size_t)cv.n_taps * 16, (size_t)R0H_CHECK_SIZE * 16);
-    R0H_TRY(evaluate_any(ctx, g_check.coeffs, po2, which.data() + cv.n_taps, (const uint32_t*)(all_xs.data() + cv.n_taps), R0H_CHECK_SIZE, &view, true));
+    r0h_buf view = buf_view(d_eval, (size_t)n_taps * 16, (size_t)R0H_CHECK_SIZE * 16);
+    R0H_TRY(evaluate_any(ctx, g_check.coeffs, po2, which.data() + n_taps, (const uint32_t*)(all_xs.data() + n_taps), R0H_CHECK_SIZE, &view, true));
   }
   std::vector<Fp4> eval_u(n_u);
   R0H_TRY(r0h_buf_d2h(ctx, d_eval, 0, eval_u.data(), (size_t)n_u * 16));
-  for (uint32_t r = 0; r < cv.n_regs; r++) {
-    uint32_t p = cv.reg_first[r];
-    poly_interpolate(&coeff_u[p], &all_xs[p], &eval_u[p], cv.reg_size[r]);
-  }
-  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) coeff_u[cv.n_taps + i] = eval_u[cv.n_taps + i];
+  for (const Reg& reg : circ->regs) poly_interpolate(&coeff_u[reg.first_tap], &all_xs[reg.first_tap], &eval_u[reg.first_tap], reg.size);
+  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) coeff_u[n_taps + i] = eval_u[n_taps + i];
   io.write((const uint32_t*)coeff_u.data(), 4 * (size_t)n_u);
   io.commit_elems((const uint32_t*)coeff_u.data(), 4 * (size_t)n_u);
 
   phase(ctx, "mix_combos");
   const Fp4 mixv = io.rng.ext();
-  const uint32_t n_combos = cv.n_combos;
+  const uint32_t n_combos = (uint32_t)circ->combo_begin.size() - 1;
   r0h_buf* combos = nullptr;
   R0H_TRY(sc.alloc(ctx, (size_t)(n_combos + 1) * n * 16, &combos));
   R0H_TRY(r0h_buf_zero(ctx, combos));
   Fp4 cur = fp4_one();
   for (int g = 0; g < 3; g++) {
-    uint32_t gs = cv.group_size[g];
+    uint32_t gs = circ->group_size[g];
     std::vector<uint32_t> combo_of(gs);
-    for (uint32_t r = 0; r < cv.n_regs; r++)
-      if (cv.reg_group[r] == (uint32_t)g) combo_of[cv.reg_offset[r]] = cv.reg_combo[r];
+    for (const Reg& reg : circ->regs)
+      if (reg.group == (uint32_t)g) combo_of[reg.offset] = reg.combo;
     R0H_TRY(r0h_mix_poly_coeffs(ctx, combos, cur.e, mixv.e, grp[g]->coeffs, combo_of.data(), gs, po2));
     cur = cur * fp4_pow(mixv, gs);
   }
@@ -390,17 +362,17 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
     std::vector<Fp4> head((size_t)(n_combos + 1) * 64, fp4_zero());
     std::vector<uint32_t> head_len(n_combos + 1, 0);
     cur = fp4_one();
-    for (uint32_t r = 0; r < cv.n_regs; r++) {
-      R0H_REQUIRE(cv.reg_size[r] <= 64, "prove_segment: register with more than 64 taps");
-      for (uint32_t i = 0; i < cv.reg_size[r]; i++) {
-        Fp4& h = head[(size_t)cv.reg_combo[r] * 64 + i];
-        h = h + cur * coeff_u[cv.reg_first[r] + i];
+    for (const Reg& reg : circ->regs) {
+      R0H_REQUIRE(reg.size <= 64, "prove_segment: register with more than 64 taps");
+      for (uint32_t i = 0; i < reg.size; i++) {
+        Fp4& h = head[(size_t)reg.combo * 64 + i];
+        h = h + cur * coeff_u[reg.first_tap + i];
       }
-      if (cv.reg_size[r] > head_len[cv.reg_combo[r]]) head_len[cv.reg_combo[r]] = cv.reg_size[r];
+      if (reg.size > head_len[reg.combo]) head_len[reg.combo] = reg.size;
       cur = cur * mixv;
     }
     for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) {
-      head[(size_t)n_combos * 64] = head[(size_t)n_combos * 64] + cur * coeff_u[cv.n_taps + i];
+      head[(size_t)n_combos * 64] = head[(size_t)n_combos * 64] + cur * coeff_u[n_taps + i];
       cur = cur * mixv;
     }
     head_len[n_combos] = 1;
@@ -427,8 +399,8 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
     std::vector<uint32_t> job_poly, job_pt;
     for (uint32_t k = 0; k <= n_combos; k++) {
       if (k < n_combos) {
-        for (uint32_t b = cv.combo_begin[k]; b < cv.combo_begin[k + 1]; b++) {
-          const Fp4 pt = scale(z, fpow(back_one, cv.combo_backs[b]));
+        for (uint32_t b = circ->combo_begin[k]; b < circ->combo_begin[k + 1]; b++) {
+          const Fp4 pt = scale(z, fpow(back_one, circ->combo_backs[b]));
           job_poly.push_back(k);
           job_pt.insert(job_pt.end(), pt.e, pt.e + 4);
         }
@@ -531,13 +503,11 @@ static const char* prove_segment_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32
   R0H_TRY_HIP(hipSetDevice(ctx->device));
   std::vector<uint32_t> seal;
   {
-    CircuitView cv;
-    circuit_view(c, &cv);
-    r0h_proof st(ctx, c, po2, cv);
+    r0h_proof st(ctx, c, po2);
     R0H_TRY(proof_begin(st, code, cc, data, global));
-    if (c->n_late) R0H_TRY(proof_late(st, global + (cv.n_global - c->n_late)));
+    if (c->n_late) R0H_TRY(proof_late(st, global + (c->n_global - c->n_late)));
     r0h_buf* accum = nullptr;
-    R0H_TRY(st.sc.alloc(ctx, ((size_t)cv.group_size[R0H_GROUP_ACCUM] << po2) * 4, &accum));
+    R0H_TRY(st.sc.alloc(ctx, ((size_t)c->group_size[R0H_GROUP_ACCUM] << po2) * 4, &accum));
     const r0h_buf* code_cols = code;
     r0h_buf code_view;
     if (!code_cols && cc && cc->witness) { code_view = *cc->witness; code_cols = &code_view; }
@@ -558,12 +528,10 @@ static const char* proof_begin_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32_t
   R0H_REQUIRE((global || r0h_circuit_n_global(c) == 0) && (mix_out || r0h_circuit_n_mix(c) == 0 || c->n_late), "r0h_proof_begin: NULL globals / mix_out");
   R0H_REQUIRE(po2 >= 9 && po2 <= R0H_MAX_PO2, "r0h_proof_begin: po2 %u outside [9, %u]", po2, R0H_MAX_PO2);
   R0H_TRY_HIP(hipSetDevice(ctx->device));
-  CircuitView cv;
-  circuit_view(c, &cv);
-  r0h_proof* st = new r0h_proof(ctx, c, po2, cv);
+  r0h_proof* st = new r0h_proof(ctx, c, po2);
   const char* err = proof_begin(*st, code, cc, data, global);
   if (err) { delete st; return err; }
-  if (cv.n_mix && st->mix_drawn && mix_out) memcpy(mix_out, st->mix.data(), (size_t)cv.n_mix * 4);
+  if (c->n_mix && st->mix_drawn && mix_out) memcpy(mix_out, st->mix.data(), (size_t)c->n_mix * 4);
   *out = st;
   return nullptr;
   R0H_GUARD_END
@@ -671,11 +639,11 @@ const char* r0h_proof_data_root(const r0h_proof* proof, uint32_t root_out[8]) {
 }
 const char* r0h_proof_late(r0h_proof* proof, const uint32_t* late_globals, uint32_t* mix_out) {
   R0H_GUARD_BEGIN
-  R0H_REQUIRE(proof && (mix_out || !proof->cv.n_mix), "r0h_proof_late: NULL argument");
+  R0H_REQUIRE(proof && (mix_out || !proof->circ->n_mix), "r0h_proof_late: NULL argument");
   R0H_REQUIRE(proof->circ->n_late, "r0h_proof_late: this circuit has no late public inputs");
   R0H_TRY_HIP(hipSetDevice(proof->ctx->device));
   R0H_TRY(proof_late(*proof, late_globals));
-  if (proof->cv.n_mix) memcpy(mix_out, proof->mix.data(), (size_t)proof->cv.n_mix * 4);
+  if (proof->circ->n_mix) memcpy(mix_out, proof->mix.data(), (size_t)proof->circ->n_mix * 4);
   return nullptr;
   R0H_GUARD_END
 }

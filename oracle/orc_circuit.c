@@ -31,7 +31,7 @@ uint32_t orc_circuit_n_combos(const orc_circuit_t* c) { return c->n_combos; }
 void orc_circuit_free(orc_circuit_t* c) {
   if (!c) return;
   free(c->taps); free(c->regs); free(c->combo_begin); free(c->combo_backs); free(c->steps);
-  free(c->code_cols); free(c->data_cols); free(c->acc_cols); free(c->acc_fp); free(c->global_cols); free(c->logup); free(c->logup_words); free(c->periodic); free(c);
+  free(c->code_cols); free(c->data_cols); free(c->acc_cols); free(c->global_cols); free(c->logup); free(c->logup_words); free(c->periodic); free(c);
 }
 
 static void derive_regs_and_combos(orc_circuit_t* c) {
@@ -108,12 +108,7 @@ orc_circuit_t* orc_circuit_parse(const uint32_t* w, size_t n_words) {
         c->acc_cols = (orc_acc_col_t*)malloc(sizeof(orc_acc_col_t) * (c->n_acc ? c->n_acc : 1));
         memcpy(c->acc_cols, p + 1, sizeof(orc_acc_col_t) * c->n_acc);
         break;
-      case SEC_ACCUM_FP:
-        if (len < 1 || len != 1 + 13 * (size_t)p[0]) goto bad;
-        c->n_acc_fp = p[0];
-        c->acc_fp = (orc_acc_fp_t*)malloc(sizeof(orc_acc_fp_t) * (c->n_acc_fp ? c->n_acc_fp : 1));
-        memcpy(c->acc_fp, p + 1, sizeof(orc_acc_fp_t) * c->n_acc_fp);
-        break;
+      case SEC_ACCUM_FP: goto bad; /* retired: the trace circuit's memory argument before LOGUP; refused, as the product refuses it */
       case SEC_INFO:
         if (len >= 4) memcpy(c->info, p, 16);
         break;
@@ -183,13 +178,13 @@ orc_circuit_t* orc_circuit_parse(const uint32_t* w, size_t n_words) {
     else c->n_fp_vars++;
   }
   /* WITGEN/ACCUM (the synthetic column program) are optional: circuits imported from risc0 tables omit both */
-  if ((c->code_cols || c->acc_cols || c->acc_fp || c->logup) && (c->n_code != c->group_size[ORC_GROUP_CODE] || c->n_data != c->group_size[ORC_GROUP_DATA])) goto bad;
+  if ((c->code_cols || c->acc_cols || c->logup) && (c->n_code != c->group_size[ORC_GROUP_CODE] || c->n_data != c->group_size[ORC_GROUP_DATA])) goto bad;
   if (c->n_late > c->n_global) goto bad;
   for (uint32_t k = 0; c->code_cols && k < c->n_code; k++)
     if (c->code_cols[k].kind == 6 && (!c->periodic || c->code_cols[k].param >= c->n_periodic)) goto bad;
   if (c->has_sponge && ((uint64_t)c->sponge_code + 28 > c->n_code || (uint64_t)c->sponge_data + 65 > c->n_data || (uint64_t)c->sponge_global + 8 > c->n_global || c->period != 30)) goto bad;
   if (c->logup) {  /* every reference of the log-derivative argument stays inside the circuit */
-    if (c->acc_cols || c->acc_fp || 4 * c->n_logup != c->group_size[ORC_GROUP_ACCUM] || !c->n_chain) goto bad;
+    if (c->acc_cols || 4 * c->n_logup != c->group_size[ORC_GROUP_ACCUM] || !c->n_chain) goto bad;
     for (uint32_t k = 0; k < c->n_tables; k++)
       if (c->table_col[k] >= c->n_data || (c->table_kind[k] != 1 && c->table_kind[k] != 2)) goto bad;
     for (uint32_t j = 0; j < c->n_logup; j++) {
@@ -212,15 +207,6 @@ orc_circuit_t* orc_circuit_parse(const uint32_t* w, size_t n_words) {
           }
         }
       }
-    }
-  } else
-  if (c->acc_fp) {  /* the trace circuit's memory-consistency accumulators: alpha, b1, b2, b3 shared */
-    if (c->acc_cols || 4 * c->n_acc_fp != c->group_size[ORC_GROUP_ACCUM] || c->n_mix != 16) goto bad;
-    for (uint32_t j = 0; j < c->n_acc_fp; j++) {
-      if (c->acc_fp[j].n_f < 1 || c->acc_fp[j].n_f > 3) goto bad;
-      for (int f = 0; f < 3; f++)
-        for (int q = 0; q < 4; q++)
-          if (c->acc_fp[j].col[f][q] >= c->n_data) goto bad;
     }
   } else if ((c->code_cols || c->acc_cols) && (4 * c->n_acc != c->group_size[ORC_GROUP_ACCUM] || c->n_mix != 8 * c->n_acc)) {
     goto bad;
@@ -450,30 +436,6 @@ void orc_accum(const orc_circuit_t* c, uint32_t po2, const uint32_t* code, const
   (void)code;
   size_t n = (size_t)1 << po2;
   fp4_t* tmp = (fp4_t*)malloc(sizeof(fp4_t) * n);
-  for (uint32_t j = 0; j < c->n_acc_fp; j++) {
-    /* running product over the rows of prod_f (alpha - addr_f - b1 lo_f - b2 hi_f - b3 t_f): the tuples one side of the
-     * memory argument reads (or writes) in a row */
-    const orc_acc_fp_t* a = &c->acc_fp[j];
-    fp4_t m[4];
-    memcpy(m, mix, 64);
-#pragma omp parallel for
-    for (size_t r = 0; r < n; r++) {
-      fp4_t prod = fp4_one();
-      for (uint32_t f = 0; f < a->n_f; f++) {
-        const fp_t addr = data[(size_t)a->col[f][0] * n + r], lo = data[(size_t)a->col[f][1] * n + r];
-        const fp_t hi = data[(size_t)a->col[f][2] * n + r], t = data[(size_t)a->col[f][3] * n + r];
-        fp4_t term = fp4_sub(fp4_sub(fp4_sub(m[0], fp4_scale(m[1], lo)), fp4_scale(m[2], hi)), fp4_scale(m[3], t));
-        term = fp4_sub(term, fp4_from_fp(addr));
-        prod = fp4_mul(prod, term);
-      }
-      tmp[r] = prod;
-    }
-    orc_prefix_products((uint32_t*)tmp, (uint32_t)n);
-    for (int k = 0; k < 4; k++) {
-      fp_t* dst = accum + ((size_t)4 * j + k) * n;
-      for (size_t r = 0; r < n; r++) dst[r] = tmp[r].e[k];
-    }
-  }
   for (uint32_t j = 0; j < c->n_acc; j++) {
     fp4_t m0, m1;
     memcpy(&m0, mix + 8 * j, 16); memcpy(&m1, mix + 8 * j + 4, 16);

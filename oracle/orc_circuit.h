@@ -10,7 +10,6 @@ typedef struct { uint32_t op, a, b, c; } orc_step_t;
 typedef struct { uint32_t kind, param; } orc_code_col_t;
 typedef struct { uint32_t kind, a, b, c, e; } orc_data_col_t;
 typedef struct { uint32_t first, a, b; } orc_acc_col_t;
-typedef struct { uint32_t n_f; uint32_t col[3][4]; } orc_acc_fp_t; /* running product of up to three tuple fingerprints (blob section 8) */
 /* the log-derivative argument (blob section 10): fractions numerator / sum of (challenge x linear form), four to an accumulator */
 typedef struct { uint32_t coef, global, col; } orc_lf_term_t; /* canonical coefficient; public input + 1 or 0; column ref + 1 or 0 */
 typedef struct { uint32_t n; const orc_lf_term_t* t; } orc_lf_t; /* points into the circuit's copy of the section */
@@ -30,7 +29,6 @@ struct orc_circuit {
   uint32_t n_code; orc_code_col_t* code_cols;
   uint32_t n_data; orc_data_col_t* data_cols;
   uint32_t n_acc; orc_acc_col_t* acc_cols;
-  uint32_t n_acc_fp; orc_acc_fp_t* acc_fp;
   uint32_t n_late;                       /* the last n_late public inputs enter the transcript after the DATA commitment */
   uint32_t n_logup, n_chain, n_tables;   /* accumulators of the log-derivative argument; how many are links of the chain */
   orc_logup_acc_t* logup;

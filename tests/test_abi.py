@@ -71,6 +71,30 @@ def test_eval_check_codegen_is_deterministic_and_complete():
         r0.emit_eval_check_source(bad)
 
 
+def test_a_blob_with_the_retired_section_8_is_refused_by_both_parsers(orc):
+    """ACCUM_FP (section 8) was the trace circuit's memory argument before LOGUP; no generator emits it any more.  tiny.r0c with its
+    accumulator section re-tagged 8 and given a well-formed one-accumulator body of that format (n_acc, then n_f and three quadruples
+    of DATA columns: 14 words) is refused by name by the product and refused by the oracle, so the two agree on every blob."""
+    import hyperfridge_r0_amd as r0
+    blob = np.fromfile(circuit_path("tiny"), dtype=np.uint32)
+    pos, at = 3, None
+    for _ in range(int(blob[2])):
+        if blob[pos] == 6:
+            at = pos
+        pos += 2 + int(blob[pos + 1])
+    assert at is not None and pos == blob.size
+    body = np.array([1, 1] + [0] * 12, dtype=np.uint32)
+    old = blob[:at + 2 + int(blob[at + 1])].size
+    retired = np.concatenate([blob[:at], np.array([8, body.size], dtype=np.uint32), body, blob[old:]])
+    assert body.size == 14 and retired[at] == 8
+    with pytest.raises(r0.R0HipError, match=r"circuit blob: section 8 \(ACCUM_FP\) is retired"):
+        r0.emit_eval_check_source(retired)
+    with pytest.raises(AssertionError, match="oracle rejected the circuit blob"):
+        orc.circuit(retired)
+    orc.circuit(blob)  # (the unaltered blob is fine with both)
+    assert r0.emit_eval_check_source(blob)
+
+
 def test_blob_parser_survives_random_corruption():
     """Host-only fuzz of the circuit loader's validation (r0h_circuit_emit_hip parses and plans without a GPU): a mutated
     blob must either be rejected with a message or produce source -- never crash, never hang."""

@@ -31,6 +31,16 @@ EVAL_CHECK_SHA256 = {
     "trace": "25c760bef0c453d0dc3f2ac398b8b53ad07c59336a629c3f915761704c4a7dc0",
     "image": "7a4110f0e9df0116395d0b0047f931195794bdbce6af4655251bbdde4a82928e",
 }
+# the same for r0h_circuit_emit_hip_check's text, recorded from the build of the commit before the generator moved out of circuit.hip
+# (no R0H_EC_* variable set): neither the move nor the one function that now writes a term's value for both emitters moved a byte
+CHECK_WITNESS_SHA256 = {
+    "tiny": "573511f972e6e6440f436528d5cd97040ebe647344cbb9b41cfc28cf893f4869",
+    "small": "5359c75a3c05934656fd44a5fd7326f475fca81067fcd4e7192b0637414e0099",
+    "bench": "3960542b8ff1b07cef305e2c647406e33dfc4ff31ac9b0db8e4af7a18d90feee",
+    "recursion": "21f1613ba62167ba333b7846eecb7fbf210421f9a0b7a8de3a9905b5c3a07dd6",
+    "trace": "d1c2f566f1b1fd93d51f7c6ad6858b752b59c0b0cf3e566a4d84a1d3bca2e4ed",
+    "image": "1512c2dc54759170fa1670e5574da7675b791739fd76df3bd3dc39d4d3281899",
+}
 
 
 def blob_of(name):
@@ -56,6 +66,7 @@ def test_terms_are_the_and_eqz_steps_and_eval_check_text_is_the_parents(name):
         late |= {int(x.split("u,")[0]) for x in ("\n" + part).split("\n  }\n")[0].split("  tally(table, ")[1:]}
     assert late == {t for t in range(n_terms) if pr.late[t]}
     assert hashlib.sha256(r0.emit_eval_check_source(blob).encode()).hexdigest() == EVAL_CHECK_SHA256[name]
+    assert hashlib.sha256(src.encode()).hexdigest() == CHECK_WITNESS_SHA256[name]
 
 
 def test_n_terms_is_exported_and_a_bad_blob_is_refused():

@@ -204,7 +204,9 @@ def test_argument_errors_are_reported_not_crashed(hal):
         hal.load_circuit(np.zeros(10, np.uint32))
 
 
-@pytest.mark.parametrize("name,po2", [("tiny", 9), ("small", 11)])
+# ("tiny", 6): 64 rows are one wave and less than a block -- the threads = n launch shape of witgen, the term kernel and the unpack
+# kernel the product and the log-derivative accumulators share -- and the 4N domain of 256 is exactly one eval_check block
+@pytest.mark.parametrize("name,po2", [("tiny", 6), ("tiny", 9), ("small", 11)])
 def test_witgen_accum_eval_check(hal, orc, name, po2):
     blob = np.fromfile(circuit_path(name), dtype=np.uint32)
     oc = orc.circuit(blob)

@@ -8,11 +8,11 @@ CLANG=/opt/rocm/lib/llvm/bin/clang++; CC=/opt/rocm/lib/llvm/bin/clang
 mkdir -p "$WORK/obj" "$WORK/corpus"
 # coverage counters only: the compare-tracing hooks of -fsanitize=fuzzer-no-link slow field arithmetic down a hundredfold
 FLAGS="-O2 -g -fno-omit-frame-pointer -fsanitize=address -fsanitize-coverage=inline-8bit-counters,pc-table"
-for f in verify ctx circuit; do
-  src=$ROOT/hyperfridge-r0_amd/csrc/$f.cpp; [ -f "$src" ] || src=$ROOT/hyperfridge-r0_amd/csrc/$f.hip  # host-only units are .cpp, circuit is .hip
+rm -f "$WORK/obj/circuit.o"  # (a work dir from before the parser moved out of circuit.hip)
+for f in verify ctx hash_suite blob claim receipt image rv32im ebics evalcheck_emit; do  # the verifier and what it links against: all host code
+  src=$ROOT/hyperfridge-r0_amd/csrc/$f.cpp
   if [ ! -f "$WORK/obj/$f.o" ] || [ "$src" -nt "$WORK/obj/$f.o" ]; then
-    if [ $f = circuit ]; then MODE="--offload-arch=gfx950 -fno-gpu-sanitize"; else MODE="-D__HIP_PLATFORM_AMD__ -I/opt/rocm/include"; fi
-    /opt/rocm/bin/hipcc $MODE $FLAGS -w -c "$src" -o "$WORK/obj/$f.o"
+    /opt/rocm/bin/hipcc -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $FLAGS -w -c "$src" -o "$WORK/obj/$f.o"
   fi
 done
 for src in "$ROOT"/oracle/*.c; do   # the oracle, single-threaded (its OpenMP pragmas are ignored), under the same sanitizers
@@ -21,12 +21,17 @@ for src in "$ROOT"/oracle/*.c; do   # the oracle, single-threaded (its OpenMP pr
   if [ ! -f "$o" ] || [ "$src" -nt "$o" ]; then $CC $FLAGS -w -I"$ROOT/oracle" -I"$ROOT/include" -c "$src" -o "$o"; fi
 done
 cat > "$WORK/stubs.cpp" <<'STUB'
+#include <stddef.h>
 #include <stdint.h>
 struct r0h_ctx; struct r0h_buf;
 struct r0h_circuit;
 namespace r0h { const char* ntt_init_device() { return nullptr; } void session_rows_free(r0h_ctx*) {}
-const char* logup_accum(r0h_ctx*, const r0h_circuit*, uint32_t, const r0h_buf*, const r0h_buf*, const uint32_t*, const uint32_t*, r0h_buf*) { __builtin_trap(); } }
+const char* logup_accum(r0h_ctx*, const r0h_circuit*, uint32_t, const r0h_buf*, const r0h_buf*, const uint32_t*, const uint32_t*, r0h_buf*) { __builtin_trap(); }
+const char* witgen_code(r0h_ctx*, const r0h_circuit*, uint32_t, r0h_buf*) { __builtin_trap(); }
+const char* sponge_plant(r0h_ctx*, const r0h_circuit*, uint32_t, const uint32_t*, size_t, r0h_buf*) { __builtin_trap(); } }
 extern "C" const char* r0h_prefix_products(r0h_ctx*, r0h_buf*, uint32_t) { __builtin_trap(); }
+extern "C" const char* r0h_logup_totals(r0h_ctx*, const r0h_circuit*, uint32_t, const r0h_buf*, const r0h_buf*, uint32_t*) { __builtin_trap(); }
+extern "C" const char* r0h_prove_segment(r0h_ctx*, const r0h_circuit*, uint32_t, const r0h_buf*, const r0h_buf*, const uint32_t*, uint32_t*, size_t, size_t*) { __builtin_trap(); }
 STUB
 $CLANG $FLAGS -c "$WORK/stubs.cpp" -o "$WORK/obj/stubs.o"
 $CLANG -O1 -g -fsanitize=address,fuzzer-no-link -I"$ROOT/include" -c "$ROOT/tools/fuzz/fuzz_verify_diff.cpp" -o "$WORK/harness.o"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Experiment driver for the eval_check code generator.
-  emit:  python tools/tune_evalcheck.py emit NAME SCOPE WAVES BUDGET   -> build/ec/NAME.hip (compile with hipcc --genco)
+  emit:  python tools/tune_evalcheck.py emit NAME BUDGET               -> build/ec/NAME.hip (compile with hipcc --genco)
   time:  python tools/tune_evalcheck.py time PO2 NAME [NAME...]        -> times r0h_eval_check with each code object (GPU)
 """
 import os
@@ -16,12 +16,8 @@ import hyperfridge_r0_amd as r0
 OUT = os.path.join(ROOT, "build", "ec")
 
 
-def emit(name, scope, waves, budget, circuit="bench"):
-    os.environ["R0H_EC_SCOPE"], os.environ["R0H_EC_WAVES"], os.environ["R0H_EC_BUDGET"] = scope, waves, budget
-    if name.startswith("fuse"):  # sums of products share one reduction (circuit.hip plan_fusion); off by default
-        os.environ["R0H_EC_FUSION"] = "1"
-    else:
-        os.environ.pop("R0H_EC_FUSION", None)
+def emit(name, budget, circuit="bench"):
+    os.environ["R0H_EC_BUDGET"] = budget  # expression nodes per kernel: the generator's one tunable (evalcheck_emit.cpp tunable_budget)
     blob = np.fromfile(os.path.join(ROOT, "circuits", circuit + ".r0c"), dtype=np.uint32)
     os.makedirs(OUT, exist_ok=True)
     with open(os.path.join(OUT, name + ".hip"), "w") as f:
@@ -69,6 +65,6 @@ def timeit(po2, names, circuit="bench"):
 
 if __name__ == "__main__":
     if sys.argv[1] == "emit":
-        emit(*sys.argv[2:6])
+        emit(*sys.argv[2:4])
     else:
         timeit(int(sys.argv[2]), sys.argv[3:])
