@@ -115,4 +115,24 @@ const char* require_witness(const char* caller, r0h_ctx* ctx, const r0h_circuit*
                             const uint32_t* global, const uint32_t* mix);
 // the log-derivative accumulation on the device (logup.hip): multiplicities into DATA, the ACCUM group, totals of the public accumulators
 const char* logup_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum);
+// The public accumulators' scanned terms of one segment, kept from the totals step for the accumulation that follows it on the same
+// context under the same public inputs (session.cpp): the accumulation then unpacks them into ACCUM instead of evaluating and scanning
+// them again.  logup_totals_keep is r0h_logup_totals with `keep` filled; logup_accum_kept is logup_accum with `kept` used (nullptr, or
+// one that holds nothing: evaluated as in logup_accum).
+struct LogupKept {
+  DevBuf terms;  // [n_own][2^po2] packed extension elements, inclusive prefix sums
+  uint32_t po2 = 0, n_own = 0;
+};
+const char* logup_totals_keep(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io, LogupKept* keep);
+const char* logup_accum_kept(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum,
+                             const LogupKept* kept);
+// The lookups of every table as a flat list (logup_host.cpp; what the device's counting kernel walks): per entry the numerator form
+// and the value form, form = n, (coefficient, DATA column + 1 or 0)..., coefficients in Montgomery form with the public inputs folded
+// in (absent public inputs count as 0).  Table k owns words [begin[k], begin[k + 1]) and `entries[k]` entries.
+struct LookupList {
+  std::vector<uint32_t> words;
+  uint32_t begin[3] = {0, 0, 0}, entries[2] = {0, 0};
+  uint32_t n_cols = 0;  // distinct DATA columns read
+};
+const char* logup_lookup_list(const r0h_circuit* c, const uint32_t* global, LookupList* out);
 }  // namespace r0h

@@ -10,6 +10,11 @@
 #else
 #define R0H_HD inline
 #endif
+#if defined(__clang__)
+#define R0H_UNROLL _Pragma("unroll")  // (g++ compiles the host-only units and does not know the pragma)
+#else
+#define R0H_UNROLL
+#endif
 
 namespace r0h {
 
@@ -154,6 +159,29 @@ R0H_HD Fp4 fp4_inv(const Fp4& a) {
   r.e[1] = neg(add(mul(B0, I0), mul(BETA_M, mul(B1, I1))));
   r.e[3] = neg(add(mul(B0, I1), mul(B1, I0)));
   return r;
+}
+// top[k] <- top[k] * fp4_inv(den[k]) for NB quotients with ONE inversion (Montgomery's trick: invert the product, unwind).  A zero
+// denominator gives a zero quotient, as fp4_inv(0) == 0 does: it enters the product as one and its quotient is masked.  The words are
+// those of NB separate inversions: an inverse is unique and every word is canonical.  NB is a compile-time count so that every index is.
+template <int NB>
+R0H_HD void fp4_batch_div(Fp4 (&top)[NB], const Fp4 (&den)[NB]) {
+  Fp4 d[NB], before[NB];  // den with one for zero; product of d[0 .. k)
+  bool zero[NB];
+  Fp4 run = fp4_one();
+R0H_UNROLL
+  for (int k = 0; k < NB; k++) {
+    zero[k] = (den[k].e[0] | den[k].e[1] | den[k].e[2] | den[k].e[3]) == 0;
+    d[k] = zero[k] ? fp4_one() : den[k];
+    before[k] = run;
+    run = k ? run * d[k] : d[k];
+  }
+  Fp4 inv_run = fp4_inv(run);  // 1 / (d[0] ... d[NB - 1])
+R0H_UNROLL
+  for (int k = NB - 1; k >= 0; k--) {
+    const Fp4 inv_k = k ? inv_run * before[k] : inv_run;
+    if (k) inv_run = inv_run * d[k];
+    top[k] = zero[k] ? fp4_zero() : top[k] * inv_k;
+  }
 }
 
 R0H_HD uint32_t bitrev(uint32_t x, uint32_t bits) {

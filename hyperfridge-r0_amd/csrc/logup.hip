@@ -4,14 +4,18 @@
 // "lookup/permutation argument ... log-derivative"); the fractions themselves come from the blob (tools/trace_circuit.py).
 //
 // Three device steps, all streams over columns (consecutive lanes own consecutive rows, every column access is a 256-byte line):
-//   1. multiplicities: every lookup's value is binned -- per workgroup in LDS for the small (hot) values, with device atomics for the
-//      rest; zero, by far the most frequent value (idle slots), is counted by subtraction from the slots that are not gated off (a
-//      numerator of 0) -- and the counts become the table's multiplicity column in DATA (before DATA is committed);
-//   2. terms: one thread per row evaluates the row's fractions accumulator by accumulator, sum_f n_f / d_f = N / D with ONE
-//      extension-field inversion per accumulator, and leaves the running sum WITHIN the row in the ACCUM columns;
+//   1. multiplicities: the lookups of a table are walked from a flat list of (numerator, value) forms (logup_lookup_list) by a grid of
+//      one workgroup per CU, each striding over the rows with an LDS histogram of half the table's value range -- one launch per (table,
+//      half), every in-table lookup an LDS atomic whatever its value; global memory sees each workgroup's flush alone, non-zero bins as
+//      contiguous runs.  Zero, by far the most frequent value (idle slots), is counted by subtraction from the slots that are not gated
+//      off (a numerator of 0); the counts become the table's multiplicity column in DATA (before DATA is committed);
+//   2. terms: one thread per row evaluates the row's fractions accumulator by accumulator, sum_f n_f / d_f = N / D, with ONE
+//      extension-field inversion per batch of up to four accumulators (fp4_batch_div), and leaves the running sum WITHIN the row in the
+//      ACCUM columns;
 //   3. the row totals are scanned (r0h_prefix_sums) and added back: the chain runs through the rows.
-// The interpreter reads a flat tape of the fractions (uniform across the wave: scalar loads) built per launch on the host, public
-// inputs folded into the coefficients.
+// The term interpreter reads a flat tape of the fractions (uniform across the wave: scalar loads) built per launch on the host, public
+// inputs folded into the coefficients.  The accumulators with a public total are evaluated and scanned for their totals
+// (r0h_logup_totals); a session keeps those scanned terms for the accumulation of the same segment (LogupKept, circuit.hpp).
 #include <algorithm>
 #include <map>
 
@@ -28,7 +32,7 @@ struct Tape {
   std::vector<uint32_t> acc_begin;          // word offset of every accumulator
 };
 
-const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, Tape* t, bool lookups_only = false) {
+const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, Tape* t) {
   std::map<uint32_t, uint32_t> col_index;
   std::map<uint64_t, uint32_t> ch_index;
   t->ch.push_back(fp4_one());
@@ -60,7 +64,6 @@ const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, 
   for (const LogupAcc& a : c->logup.accs) {
     t->acc_begin.push_back((uint32_t)t->words.size());
     for (const LogupFraction& f : a.fr) {
-      if (lookups_only && !f.table) continue;
       t->words.push_back(f.table);
       R0H_TRY(form(f.num));
       t->words.push_back((uint32_t)f.parts.size());
@@ -116,80 +119,130 @@ __device__ __forceinline__ uint32_t eval_form(const uint32_t* __restrict__ tape,
   return acc;
 }
 
-constexpr uint32_t HOT = 4096;  // values below this are binned in LDS per workgroup
+// a form of the lookup list (circuit.hpp LookupList): columns are DATA column indices
+__device__ __forceinline__ uint32_t eval_list_form(const uint32_t* __restrict__ list, uint32_t& at, const uint32_t* __restrict__ data, uint32_t po2, uint32_t r) {
+  const uint32_t n = list[at++];
+  uint32_t acc = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t coef = list[at], col = list[at + 1];
+    at += 2;
+    acc = add(acc, col ? mul(coef, data[((size_t)(col - 1) << po2) + r]) : coef);
+  }
+  return acc;
+}
 
-// one thread per row: every lookup's value goes into its table's histogram.  Zero is not counted (it is the remainder); entry 0 counts
-// the slots gated off instead.  A numerator other than 0 or 1 sets bit 0 of *err, a value outside its table (numerator 1) bit 1.
-__global__ __launch_bounds__(256) void logup_count_kernel(uint32_t* __restrict__ hist /* [n_tables][65536] */, uint32_t* __restrict__ err, const uint32_t* __restrict__ tape,
-                                                          uint32_t tape_end, const uint32_t* const* __restrict__ cols, uint32_t n, uint32_t n_tables) {
-  __shared__ uint32_t hot[2][HOT];
-  for (uint32_t i = threadIdx.x; i < 2 * HOT; i += 256) (&hot[0][0])[i] = 0;
+constexpr uint32_t BINS = 32768;         // one launch counts half a table: its whole value range is one LDS histogram (128 KB of the CU's 160)
+constexpr uint32_t COUNT_THREADS = 1024;
+
+// One launch per (table, half of its 65,536 values); a grid of at most one workgroup per CU, every workgroup striding over the rows.
+// Every in-table lookup of this half is one LDS atomic, whatever its value; global memory sees the workgroup's flush alone: consecutive
+// lanes add consecutive non-zero bins, at most BINS / 64 wave instructions per workgroup however many lookups there were.  A bin is a
+// whole 32-bit word: it cannot overflow, for all the bins of a table together hold at most its lookup slots, which the caller has
+// refused above p - 1 < 2^31 (at po2 = 24 with the trace circuit's 24 lookups a row: 24 * 2^24 < 2^29).  Zero is not counted (entry 0
+// is the remainder); counters[0] takes the lookups binned, counters[1] the slots gated off (half 0 counts those), one add per workgroup
+// each.  A numerator other than 0 or 1 sets bit 0 of *err, a value outside its table (numerator 1) bit 1.  No workgroup waits for another.
+__global__ __launch_bounds__(COUNT_THREADS) void logup_count_kernel(uint32_t* __restrict__ hist /* [65536], this table's */, uint32_t* __restrict__ counters, uint32_t* __restrict__ err,
+                                                                    const uint32_t* __restrict__ list, uint32_t n_entries, const uint32_t* __restrict__ data, uint32_t po2,
+                                                                    uint32_t half, uint32_t is_and) {
+  __shared__ uint32_t bins[BINS];
+  __shared__ uint32_t sums[2];
+  for (uint32_t i = threadIdx.x; i < BINS; i += COUNT_THREADS) bins[i] = 0;
+  if (threadIdx.x < 2) sums[threadIdx.x] = 0;
   __syncthreads();
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  uint32_t gated[2] = {0, 0};
-  if (r < n) {
+  const uint32_t n = 1u << po2, lo = half * BINS;
+  uint32_t gated = 0, bad = 0;
+  for (uint32_t r = blockIdx.x * COUNT_THREADS + threadIdx.x; r < n; r += gridDim.x * COUNT_THREADS) {
     uint32_t at = 0;
-    while (at < tape_end) {  // fractions in tape order; an accumulator boundary has no marker of its own (four fractions each)
-      const uint32_t table = tape[at++];
-      const uint32_t num = eval_form(tape, at, cols, r);
-      const uint32_t n_parts = tape[at++];
-      uint32_t value = 0;
-      for (uint32_t q = 0; q < n_parts; q++) {
-        at++;  // challenge index
-        const uint32_t v = eval_form(tape, at, cols, r);
-        if (q == 1) value = v;
-      }
-      if (!table || table > n_tables) continue;
+    for (uint32_t e = 0; e < n_entries; e++) {
+      const uint32_t num = eval_list_form(list, at, data, po2, r);
+      const uint32_t value = eval_list_form(list, at, data, po2, r);
       if (num != ONE) {
-        if (num) atomicOr(err, 1u);
-        else gated[table - 1]++;
+        if (num) bad |= 1u;
+        else gated++;
         continue;
       }
       uint32_t v = dec(neg(value));
-      if (table == R0H_TABLE_AND) {  // (table k is of kind k + 1: the parser sees to it)
+      if (is_and) {
         v -= R0H_TAG_AND;
-        if (v >> 24 || ((v & 255u) & ((v >> 8) & 255u)) != v >> 16) { atomicOr(err, 2u); continue; }
+        if (v >> 24 || ((v & 255u) & ((v >> 8) & 255u)) != v >> 16) { bad |= 2u; continue; }
         v &= 0xffffu;
       } else if (v >> 16) {
-        atomicOr(err, 2u);
+        bad |= 2u;
         continue;
       }
-      if (!v) continue;
-      if (v < HOT) atomicAdd(&hot[table - 1][v], 1u);
-      else atomicAdd(&hist[(size_t)(table - 1) * 65536 + v], 1u);
+      if (v && v - lo < BINS) atomicAdd(&bins[v - lo], 1u);
     }
   }
-  if (gated[0]) atomicAdd(&hot[0][0], gated[0]);
-  if (gated[1]) atomicAdd(&hot[1][0], gated[1]);
+  if (bad) atomicOr(err, bad);
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i < 2 * HOT; i += 256) {
-    const uint32_t cnt = (&hot[0][0])[i];
-    if (cnt) atomicAdd(&hist[(size_t)(i / HOT) * 65536 + (i % HOT)], cnt);
+  uint32_t binned = 0;
+  for (uint32_t i = threadIdx.x; i < BINS; i += COUNT_THREADS) {
+    const uint32_t cnt = bins[i];
+    if (cnt) atomicAdd(&hist[lo + i], cnt);
+    binned += cnt;
   }
+  if (binned) atomicAdd(&sums[0], binned);
+  if (gated && half == 0) atomicAdd(&sums[1], gated);
+  __syncthreads();
+  if (threadIdx.x < 2 && sums[threadIdx.x]) atomicAdd(&counters[threadIdx.x], sums[threadIdx.x]);
 }
-// hist -> multiplicity column: entry 0 takes what the other entries and the gated-off slots (hist[0]) leave of `total` lookup slots
-__global__ void logup_mult_kernel(uint32_t* __restrict__ column, const uint32_t* __restrict__ hist, uint32_t total, uint32_t n) {
-  __shared__ uint32_t part[256];
-  // only block 0 needs the sum of the histogram (65536 words: cheap)
+// hist -> multiplicity column: entry 0 takes what the lookups binned and the slots gated off leave of `total` lookup slots
+__global__ void logup_mult_kernel(uint32_t* __restrict__ column, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ counters, uint32_t total, uint32_t n) {
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (blockIdx.x == 0) {
-    uint32_t s = 0;
-    for (uint32_t i = threadIdx.x; i < 65536u; i += 256) s += hist[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t k = 128; k; k >>= 1) {
-      if (threadIdx.x < k) part[threadIdx.x] += part[threadIdx.x + k];
-      __syncthreads();
-    }
-  }
   if (r >= n) return;
   uint32_t v = r < 65536u ? hist[r] : 0u;
-  if (r == 0) v = total - part[0];
+  if (r == 0) v = total - counters[0] - counters[1];
   column[r] = enc(v);
 }
 
-// the row's fractions, accumulators [a0, a1): chain links leave their running sum within the row in the ACCUM columns and the
-// row total in `row_total`; an accumulator with a public total leaves its term in its own scan buffer
+// one accumulator's four fractions at row r as one quotient: sum_f n_f / d_f = top / den
+__device__ __forceinline__ void eval_accumulator(const uint32_t* __restrict__ tape, uint32_t& at, const uint32_t* const* __restrict__ cols, const Fp4* __restrict__ ch, uint32_t r,
+                                                 Fp4& top, Fp4& den_out) {
+  Fp4 d[4];
+  uint32_t num[4];
+#pragma unroll
+  for (uint32_t f = 0; f < 4; f++) {
+    at++;  // table
+    num[f] = eval_form(tape, at, cols, r);
+    const uint32_t n_parts = tape[at++];
+    Fp4 den = fp4_zero();
+    for (uint32_t q = 0; q < n_parts; q++) {
+      const uint32_t ci = tape[at++];
+      const uint32_t v = eval_form(tape, at, cols, r);
+      if (ci == 0) den.e[0] = add(den.e[0], v);
+      else den = den + scale(ch[ci], v);
+    }
+    d[f] = den;
+  }
+  const Fp4 d01 = d[0] * d[1], d23 = d[2] * d[3];
+  top = (scale(d[1], num[0]) + scale(d[0], num[1])) * d23 + (scale(d[3], num[2]) + scale(d[2], num[3])) * d01;
+  den_out = d01 * d23;
+}
+// accumulators [j, j + NB) of the row with one inversion between them (fp4_batch_div); NB is a compile-time count: no array is indexed
+// by a run-time value, so all of it stays in registers
+template <int NB>
+__device__ __forceinline__ void term_batch(uint32_t* __restrict__ accum, uint32_t* __restrict__ own_terms, const uint32_t* __restrict__ tape, uint32_t& at,
+                                           const uint32_t* const* __restrict__ cols, const Fp4* __restrict__ ch, uint32_t j, uint32_t n_chain, uint32_t po2, uint32_t r, Fp4& run) {
+  Fp4 top[NB], den[NB];
+  eval_accumulator(tape, at, cols, ch, r, top[0], den[0]);  // (spelled out: the compiler declines to unroll a loop over a body this size)
+  if constexpr (NB > 1) eval_accumulator(tape, at, cols, ch, r, top[1], den[1]);
+  if constexpr (NB > 2) eval_accumulator(tape, at, cols, ch, r, top[2], den[2]);
+  if constexpr (NB > 3) eval_accumulator(tape, at, cols, ch, r, top[3], den[3]);
+  static_assert(NB >= 1 && NB <= 4, "batches of one to four accumulators");
+  fp4_batch_div<NB>(top, den);
+#pragma unroll
+  for (int k = 0; k < NB; k++) {
+    const Fp4 term = top[k];
+    if (j + k < n_chain) {
+      run = run + term;
+      for (uint32_t i = 0; i < 4; i++) accum[((size_t)(4 * (j + k) + i) << po2) + r] = run.e[i];
+    } else {
+      *(uint4*)(own_terms + 4 * (((size_t)(j + k - n_chain) << po2) + r)) = make_uint4(term.e[0], term.e[1], term.e[2], term.e[3]);
+    }
+  }
+}
+// the row's fractions, accumulators [a0, a1), in batches of up to four: chain links leave their running sum within the row in the ACCUM
+// columns and the row total in `row_total`; an accumulator with a public total leaves its term in its own scan buffer
 __global__ __launch_bounds__(256) void logup_term_kernel(uint32_t* __restrict__ accum, uint32_t* __restrict__ row_total, uint32_t* __restrict__ own_terms,
                                                          const uint32_t* __restrict__ tape, const uint32_t* const* __restrict__ cols, const Fp4* __restrict__ ch,
                                                          uint32_t a0, uint32_t a1, uint32_t n_chain, uint32_t po2) {
@@ -197,32 +250,11 @@ __global__ __launch_bounds__(256) void logup_term_kernel(uint32_t* __restrict__ 
   if (r >= n) return;
   uint32_t at = 0;
   Fp4 run = fp4_zero();
-  for (uint32_t j = a0; j < a1; j++) {
-    Fp4 d[4];
-    uint32_t num[4];
-    for (uint32_t f = 0; f < 4; f++) {
-      at++;  // table
-      num[f] = eval_form(tape, at, cols, r);
-      const uint32_t n_parts = tape[at++];
-      Fp4 den = fp4_zero();
-      for (uint32_t q = 0; q < n_parts; q++) {
-        const uint32_t ci = tape[at++];
-        const uint32_t v = eval_form(tape, at, cols, r);
-        if (ci == 0) den.e[0] = add(den.e[0], v);
-        else den = den + scale(ch[ci], v);
-      }
-      d[f] = den;
-    }
-    const Fp4 d01 = d[0] * d[1], d23 = d[2] * d[3];
-    const Fp4 top = (scale(d[1], num[0]) + scale(d[0], num[1])) * d23 + (scale(d[3], num[2]) + scale(d[2], num[3])) * d01;
-    const Fp4 term = top * fp4_inv(d01 * d23);
-    if (j < n_chain) {
-      run = run + term;
-      for (uint32_t i = 0; i < 4; i++) accum[((size_t)(4 * j + i) << po2) + r] = run.e[i];
-    } else {
-      *(uint4*)(own_terms + 4 * ((size_t)(j - n_chain) * n + r)) = make_uint4(term.e[0], term.e[1], term.e[2], term.e[3]);
-    }
-  }
+  uint32_t j = a0;
+  for (; j + 4 <= a1; j += 4) term_batch<4>(accum, own_terms, tape, at, cols, ch, j, n_chain, po2, r, run);
+  if (a1 - j == 3) term_batch<3>(accum, own_terms, tape, at, cols, ch, j, n_chain, po2, r, run);
+  else if (a1 - j == 2) term_batch<2>(accum, own_terms, tape, at, cols, ch, j, n_chain, po2, r, run);
+  else if (a1 - j == 1) term_batch<1>(accum, own_terms, tape, at, cols, ch, j, n_chain, po2, r, run);
   if (a0 < n_chain) *(uint4*)(row_total + 4 * (size_t)r) = make_uint4(run.e[0], run.e[1], run.e[2], run.e[3]);
 }
 // chain links: add the sum of all earlier rows (inclusive scan of the row totals, one row back)
@@ -234,8 +266,12 @@ __global__ void logup_chain_kernel(uint32_t* __restrict__ accum, const uint32_t*
 }
 }  // namespace
 
+// tests/test_gpu_logup_kept.py hands the two internal entry points an empty LogupKept of its own making: one pointer, then po2, then n_own
+static_assert(sizeof(DevBuf) == sizeof(void*) && sizeof(LogupKept) == sizeof(void*) + 8 && alignof(LogupKept) == alignof(void*),
+              "LogupKept is no longer {buffer pointer, po2, n_own}: tests/test_gpu_logup_kept.py builds one by hand");
 // standalone accumulators: terms -> running sums; totals_out (host, 4 words each) if wanted, ACCUM columns if `accum`
-static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const Tape& t, const DeviceTape& d, r0h_buf* accum, uint32_t* totals_out) {
+// `keep`: the scanned terms outlive the call (the accumulation of the same segment unpacks them: logup_accum_kept)
+static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const Tape& t, const DeviceTape& d, r0h_buf* accum, uint32_t* totals_out, LogupKept* keep = nullptr) {
   const uint32_t n = 1u << po2, n_chain = c->logup.n_chain, n_acc = (uint32_t)c->logup.accs.size(), n_own = n_acc - n_chain;
   if (!n_own) return nullptr;
   DevBuf terms;
@@ -249,10 +285,20 @@ static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t
     if (accum) R0H_TRY(unpack_ext_columns(ctx, u32(accum) + ((size_t)(4 * (n_chain + k)) << po2), (const uint32_t*)view.ptr, po2));
     if (totals_out) R0H_TRY(r0h_buf_d2h(ctx, &view, (size_t)(n - 1) * 16, totals_out + 4 * k, 16));
   }
+  if (keep) {
+    keep->terms = std::move(terms);
+    keep->po2 = po2;
+    keep->n_own = n_own;
+  }
   return nullptr;
 }
 
 const char* logup_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum) {
+  return logup_accum_kept(ctx, c, po2, code, data, global, mix, accum, nullptr);
+}
+
+const char* logup_accum_kept(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum,
+                             const LogupKept* kept) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && c && data && accum, "r0h_accum: NULL argument");
   R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_accum: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
@@ -274,7 +320,14 @@ const char* logup_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const 
   R0H_TRY(r0h_prefix_sums(ctx, totals.get(), n));
   hipLaunchKernelGGL(logup_chain_kernel, dim3((n + 255) / 256, 4 * n_chain), dim3(256), 0, ctx->stream, u32(accum), u32(totals.get()), 4 * n_chain, po2);
   R0H_TRY(launch_ok("logup_chain_kernel"));
-  R0H_TRY(own_accumulators(ctx, c, po2, t, d, accum, nullptr));
+  if (kept && kept->terms) {  // the totals step of this segment has evaluated and scanned them (same columns, same public inputs)
+    const uint32_t n_own = (uint32_t)c->logup.accs.size() - n_chain;
+    R0H_REQUIRE(kept->po2 == po2 && kept->n_own == n_own && kept->terms->ctx == ctx, "r0h_accum: the kept terms are not this segment's (2^%u rows, %u accumulators)", kept->po2, kept->n_own);
+    for (uint32_t k = 0; k < n_own; k++)
+      R0H_TRY(unpack_ext_columns(ctx, u32(accum) + ((size_t)(4 * (n_chain + k)) << po2), u32(kept->terms.get()) + 4 * (size_t)k * n, po2));
+  } else {
+    R0H_TRY(own_accumulators(ctx, c, po2, t, d, accum, nullptr));
+  }
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the tape goes back to the pool
   return nullptr;
   R0H_GUARD_END
@@ -295,34 +348,38 @@ const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_
   R0H_REQUIRE(((size_t)c->group_size[R0H_GROUP_DATA] << po2) * 4 <= data->bytes, "r0h_logup_multiplicities: the DATA buffer is too small for 2^%u rows", po2);
   R0H_REQUIRE(c->logup.tables.size() <= 2, "r0h_logup_multiplicities: at most two tables");
   const uint32_t n = 1u << po2, n_tables = (uint32_t)c->logup.tables.size();
-  // only the lookups are on this tape: chain links in order, challenges unused (their indices are skipped)
-  Tape t;
-  std::vector<uint32_t> dummy_mix(c->n_mix, 0), dummy_global(c->n_global, 0);
-  R0H_TRY(build_tape(c, po2, nullptr, data, global ? global : dummy_global.data(), dummy_mix.data(), &t, true));  // the lookups alone (they read DATA only)
-  DeviceTape d;
-  R0H_TRY(upload_tape(ctx, t, &d));
+  LookupList list;  // the lookups alone, table by table: numerator and value (they read DATA only)
+  R0H_TRY(logup_lookup_list(c, global, &list));
   std::vector<uint64_t> slots(n_tables, 0);  // lookup slots of each table: the chain links' lookups times the rows (only links look up)
-  for (uint32_t j = 0; j < c->logup.n_chain; j++)
-    for (const LogupFraction& f : c->logup.accs[j].fr)
-      if (f.table && f.table <= n_tables) slots[f.table - 1] += n;
+  for (uint32_t k = 0; k < n_tables; k++) slots[k] = (uint64_t)list.entries[k] * n;
   for (uint32_t k = 0; k < n_tables; k++)
     R0H_REQUIRE(slots[k] <= P - 1, "r0h_logup_multiplicities: table %u has %llu lookup slots at 2^%u rows: more than p - 1", k, (unsigned long long)slots[k], po2);
-  DevBuf hist;  // [n_tables][65536] counts, then the error word
+  DevBuf dlist;
+  R0H_TRY(dlist.alloc(ctx, list.words.size() * 4 + 16));
+  R0H_TRY(stage_h2d(ctx, dlist->ptr, list.words.data(), list.words.size() * 4));
+  DevBuf hist;  // [n_tables][65536] counts, then per table the lookups binned and the slots gated off, then the error word
   const size_t hist_words = (size_t)n_tables * 65536;
-  R0H_TRY(hist.alloc(ctx, hist_words * 4 + 16));
-  R0H_TRY_HIP(hipMemsetAsync(hist->ptr, 0, hist_words * 4 + 16, ctx->stream));
-  KScope ks(ctx, "logup_multiplicities", (double)t.cols.size() * n * 4);
-  hipLaunchKernelGGL(logup_count_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(hist.get()), u32(hist.get()) + hist_words, d.words, (uint32_t)t.words.size(), d.cols, n, n_tables);
-  R0H_TRY(launch_ok("logup_count_kernel"));
+  R0H_TRY(hist.alloc(ctx, hist_words * 4 + 32));
+  R0H_TRY_HIP(hipMemsetAsync(hist->ptr, 0, hist_words * 4 + 32, ctx->stream));
+  uint32_t* const counters = u32(hist.get()) + hist_words;
+  uint32_t* const err_word = counters + 4;
+  if (!ctx->n_cu) R0H_TRY_HIP(hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  const uint32_t grid = std::min<uint32_t>((uint32_t)std::max(ctx->n_cu, 1), n / COUNT_THREADS);  // persistent: a workgroup per CU, fewer where the rows do not fill them
+  KScope ks(ctx, "logup_multiplicities", 2.0 * list.n_cols * n * 4);  // (each half's launch reads the lookups' columns)
   for (uint32_t k = 0; k < n_tables; k++) {
+    for (uint32_t half = 0; half < 2; half++) {
+      hipLaunchKernelGGL(logup_count_kernel, dim3(grid), dim3(COUNT_THREADS), 0, ctx->stream, u32(hist.get()) + (size_t)k * 65536, counters + 2 * k, err_word, u32(dlist.get()) + list.begin[k],
+                         list.entries[k], u32(data), po2, half, (uint32_t)(k + 1 == R0H_TABLE_AND));
+      R0H_TRY(launch_ok("logup_count_kernel"));
+    }
     const LogupTable& tb = c->logup.tables[k];
-    hipLaunchKernelGGL(logup_mult_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(data) + ((size_t)tb.data_col << po2), u32(hist.get()) + (size_t)k * 65536,
+    hipLaunchKernelGGL(logup_mult_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, u32(data) + ((size_t)tb.data_col << po2), u32(hist.get()) + (size_t)k * 65536, counters + 2 * k,
                        (uint32_t)slots[k], n);
     R0H_TRY(launch_ok("logup_mult_kernel"));
   }
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
   uint32_t err = 0;
-  R0H_TRY(r0h_buf_d2h(ctx, hist.get(), hist_words * 4, &err, 4));
+  R0H_TRY(r0h_buf_d2h(ctx, hist.get(), hist_words * 4 + 16, &err, 4));
   R0H_REQUIRE(!(err & 1u), "r0h_logup_multiplicities: a lookup's numerator is neither 0 nor 1");
   R0H_REQUIRE(!(err & 2u), "r0h_logup_multiplicities: a row whose numerator is 1 looks up a value that is not in its table");
   return nullptr;
@@ -332,6 +389,12 @@ const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_
 // The totals of the accumulators that run alone (their challenges are public inputs, so they can be had before the mix is drawn):
 // global_io[final .. final + 4) of each is overwritten with its total over the rows.
 const char* r0h_logup_totals(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io) {
+  return logup_totals_keep(ctx, c, po2, code, data, global_io, nullptr);
+}
+
+}  // extern "C"
+
+const char* r0h::logup_totals_keep(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io, LogupKept* keep) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && c && data && global_io, "r0h_logup_totals: NULL argument");
   R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_logup_totals: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
@@ -346,10 +409,8 @@ const char* r0h_logup_totals(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, c
   DeviceTape d;
   R0H_TRY(upload_tape(ctx, t, &d));
   std::vector<uint32_t> totals(4 * (size_t)(n_acc - n_chain));
-  R0H_TRY(own_accumulators(ctx, c, po2, t, d, nullptr, totals.data()));
+  R0H_TRY(own_accumulators(ctx, c, po2, t, d, nullptr, totals.data(), keep));
   for (uint32_t j = n_chain; j < n_acc; j++) memcpy(global_io + c->logup.accs[j].final_global, totals.data() + 4 * (size_t)(j - n_chain), 16);
   return nullptr;
   R0H_GUARD_END
 }
-
-}  // extern "C"

@@ -8,7 +8,41 @@
 #include "../../include/r0hip_circuit.h"
 #include "circuit.hpp"
 
+#include <set>
+
 using namespace r0h;
+
+namespace r0h {
+// the lookups alone, table by table, chain links in order: numerator and value (a lookup's second part: the parser sees to it); the
+// challenge part of a lookup and fractions without a table are not on the list
+const char* logup_lookup_list(const r0h_circuit* c, const uint32_t* global, LookupList* out) {
+  R0H_REQUIRE(c->logup.tables.size() <= 2, "r0h_logup_multiplicities: at most two tables");
+  std::set<uint32_t> cols;
+  auto form = [&](const Lf& lf) {
+    out->words.push_back((uint32_t)lf.terms.size());
+    for (const LfTerm& t : lf.terms) {
+      uint32_t coef = enc(t.coef);
+      if (t.global) coef = mul(coef, global ? global[t.global - 1] : 0u);
+      out->words.push_back(coef);
+      out->words.push_back(t.col ? ((t.col - 1) & 0xfffffu) + 1 : 0u);
+      if (t.col) cols.insert((t.col - 1) & 0xfffffu);
+    }
+  };
+  for (uint32_t k = 0; k < c->logup.tables.size(); k++) {
+    out->begin[k] = (uint32_t)out->words.size();
+    for (uint32_t j = 0; j < c->logup.n_chain; j++)
+      for (const LogupFraction& f : c->logup.accs[j].fr) {
+        if (f.table != k + 1) continue;
+        form(f.num);
+        form(f.parts[1].lf);
+        out->entries[k]++;
+      }
+    out->begin[k + 1] = (uint32_t)out->words.size();
+  }
+  out->n_cols = (uint32_t)cols.size();
+  return nullptr;
+}
+}  // namespace r0h
 
 extern "C" {
 

@@ -581,11 +581,13 @@ const char* finish_segment(r0h_session* s, Pending& p, const uint32_t challenge[
   memcpy(p.global.data() + R0H_TRACE_GAMMA, challenge, 64);
   const r0h_buf* code_cols = nullptr;
   R0H_TRY(r0h_code_commit_columns(p.cc, &code_cols));
-  R0H_TRY(r0h_logup_totals(p.lctx, c, p.po2, code_cols, data.get(), p.global.data()));
+  LogupKept kept;  // the session accumulator's scanned terms: evaluated once, for its total here and for its ACCUM columns below
+  R0H_TRY(logup_totals_keep(p.lctx, c, p.po2, code_cols, data.get(), p.global.data(), &kept));
   R0H_TRY(r0h_proof_late(p.proof.get(), p.global.data() + (R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS), mix.data()));
   DevBuf accum;
   R0H_TRY(accum.alloc(p.lctx, ((size_t)c->group_size[R0H_GROUP_ACCUM] << p.po2) * 4));
-  R0H_TRY(r0h_accum_public(p.lctx, c, p.po2, code_cols, data.get(), p.global.data(), mix.data(), accum.get()));
+  R0H_TRY(logup_accum_kept(p.lctx, c, p.po2, code_cols, data.get(), p.global.data(), mix.data(), accum.get(), &kept));
+  kept.terms.reset();
   return r0h_proof_finish(p.proof.release(), accum.get(), seal.data(), seal.size(), words);  // consumed either way
 }
 }  // namespace
