@@ -80,6 +80,10 @@ _SIGNATURES = {
     "r0h_circuit_load_check": [_vp, _cp],
     "r0h_check_witness": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _c.POINTER(_sz)],
     "r0h_ctx_set_check_witness": [_vp, _c.c_int],
+    "r0h_logup_check_balance": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _c.POINTER(_sz)],
+    "r0h_logup_check_balance_host": [_vp, _sz, _u32, _vp, _vp, _vp, _vp, _sz, _c.POINTER(_sz)],
+    "r0h_logup_check_balance_stats": [_vp, _vp],
+    "r0h_ctx_set_check_balance": [_vp, _c.c_int],
     "r0h_circuit_free": [_vp],
     "r0h_witgen": [_vp, _vp, _u32, _u64, _vp, _vp, _vp],
     "r0h_witgen_public": [_vp, _vp, _u32, _u64, _vp, _vp, _vp],
@@ -227,6 +231,7 @@ _PLAIN = {
     "r0h_circuit_n_mix": ([_vp], _u32),
     "r0h_circuit_n_taps": ([_vp], _u32),
     "r0h_circuit_n_terms": ([_vp], _u32),
+    "r0h_circuit_n_chain_fractions": ([_vp], _u32),
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_PLAIN))
 
@@ -332,6 +337,7 @@ class Circuit:
         self.n_mix = L.r0h_circuit_n_mix(handle)
         self.n_taps = L.r0h_circuit_n_taps(handle)
         self.n_terms = L.r0h_circuit_n_terms(handle)  # constraint terms: what Hal.check_witness numbers
+        self.n_chain_fractions = L.r0h_circuit_n_chain_fractions(handle)  # the chain links' fractions: what Hal.logup_check_balance numbers
 
     def load_check(self, code_object_path=None):
         """The witness checker's kernels now (r0h_circuit_load_check): from a gfx950 code object built from emit_check_witness_source,
@@ -397,6 +403,35 @@ def emit_check_witness_source(blob):
 class Violation(ctypes.Structure):
     """r0h_violation: constraint term `term` does not vanish on `rows` rows of the trace, the first of them `first_row`"""
     _fields_ = [("term", _u32), ("rows", _u32), ("first_row", _u32), ("reserved", _u32)]
+
+
+class Imbalance(ctypes.Structure):
+    """r0h_imbalance: a class of tuples whose numerators sum to `net` (canonical, not 0) over `members` tuples, the lowest of them
+    fraction `fraction` on row `first_row`"""
+    _fields_ = [("fraction", _u32), ("first_row", _u32), ("net", _u32), ("members", _u32)]
+
+
+def logup_check_balance_host(blob, po2, code, data, glob, capacity=None):
+    """Which classes of the chain links' fractions do not cancel, on the host (r0h_logup_check_balance_host; needs no GPU): code / data
+    are the groups' Montgomery words, column-major (code may be None for a circuit whose chain reads no CODE column).
+    -> [(fraction, first_row, net, members)] in (first_row, fraction) order; with `capacity` the lowest of them and the total:
+    ([...], n)."""
+    b, pb = _u32arr(blob)
+    d, pd = _u32arr(data)
+    g, pg = _u32arr(glob if glob is not None and len(glob) else [0])
+    pc = None
+    if code is not None:
+        cd, pc = _u32arr(code)
+    n = _sz(0)
+    cap = 0 if capacity is None else int(capacity)
+    out = (Imbalance * max(cap, 1))()
+    _check(lib().r0h_logup_check_balance_host(pb, b.size, po2, pc, pd, pg, out, cap, ctypes.byref(n)))
+    if capacity is None:  # counted: now with room for all of them
+        cap = n.value
+        out = (Imbalance * max(cap, 1))()
+        _check(lib().r0h_logup_check_balance_host(pb, b.size, po2, pc, pd, pg, out, cap, ctypes.byref(n)))
+    found = [(out[i].fraction, out[i].first_row, out[i].net, out[i].members) for i in range(min(n.value, cap))]
+    return found if capacity is None else (found, n.value)
 
 
 def verify_seal(blob, seal, poseidon2_consts=None, code_root=None, hashfn="poseidon2"):
@@ -1419,6 +1454,34 @@ class Hal:
         if n.value > cap:
             raise R0HipError("check_witness: %d terms are violated, room for %d" % (n.value, cap))
         return [(out[i].term, out[i].rows, out[i].first_row) for i in range(n.value)]
+
+    def logup_check_balance(self, circuit, po2, code, data, glob, capacity=None):
+        """Which classes of the chain links' fractions do not cancel (r0h_logup_check_balance): [(fraction, first_row, net, members)]
+        in (first_row, fraction) order, empty for a witness whose argument balances.  code / data are Bufs (code may be None for a
+        circuit whose chain reads no CODE column).  With `capacity` the lowest `capacity` of them and the total: ([...], n)."""
+        g, pg = _u32arr(glob if glob is not None and len(glob) else [0])
+        n = _sz(0)
+        ch = code.handle if code is not None else None
+        cap = 0 if capacity is None else int(capacity)
+        out = (Imbalance * max(cap, 1))()
+        _check(lib().r0h_logup_check_balance(self.ctx, circuit.handle, po2, ch, data.handle, pg, out, cap, ctypes.byref(n)))
+        if capacity is None and n.value:  # counted: now with room for all of them
+            cap = n.value
+            out = (Imbalance * cap)()
+            _check(lib().r0h_logup_check_balance(self.ctx, circuit.handle, po2, ch, data.handle, pg, out, cap, ctypes.byref(n)))
+        found = [(out[i].fraction, out[i].first_row, out[i].net, out[i].members) for i in range(min(n.value, cap))]
+        return found if capacity is None else (found, n.value)
+
+    def logup_check_balance_stats(self):
+        """of this context's last logup_check_balance: (tuples, inserts that reached the global table, the table's slots)"""
+        out = (_u64 * 3)()
+        _check(lib().r0h_logup_check_balance_stats(self.ctx, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def set_check_balance(self, on=True):
+        """prove_segment, proof_begin and the sessions of this context check that every segment's log-derivative fractions cancel
+        before its DATA group is committed and raise, naming the lowest fraction of a class that does not (r0h_ctx_set_check_balance)"""
+        _check(lib().r0h_ctx_set_check_balance(self.ctx, 1 if on else 0))
 
     def set_check_witness(self, on=True):
         """prove_segment, proof_finish and the sessions of this context check every segment's witness before its ACCUM group is

@@ -56,6 +56,15 @@ R0H_HD uint32_t fixed_cell(uint32_t kind, uint32_t arg, uint32_t r, uint32_t n, 
   return 0u;
 }
 
+// ---- the balance check (r0h_logup_check_balance, include/r0hip.h), one statement for the device (logup.hip) and the host
+// (logup_host.cpp): a tuple's class is known by two linear hashes over F_p of its per-identity part sums, h_j = sum_i w_j(i) s_i.
+// The weights are fixed words in [1, p) of the challenge's identity (kind << 32 | index; 0 is "one"); the key is never 0 (an empty slot).
+R0H_HD uint32_t balance_weight(uint32_t j, uint64_t identity) {
+  const uint64_t h = splitmix64(splitmix64(identity) + 0xBA1A9CEull * (j + 1));
+  return 1u + (uint32_t)(((h >> 32) * (uint64_t)(P - 1)) >> 32);
+}
+R0H_HD uint64_t balance_key(uint32_t h0, uint32_t h1) { return (((uint64_t)h0 << 31) | h1) + 1; }
+
 struct Plan {                      // how the constraint program is cut into kernels
   std::vector<Term> terms;         // flattened, in chain order
   std::vector<uint32_t> cut;       // kernel k owns terms [cut[k], cut[k+1])
@@ -113,6 +122,9 @@ const char* sponge_plant(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const
 // r0h_ctx_set_check_witness); global / mix are host words as r0h_eval_check takes them
 const char* require_witness(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,
                             const uint32_t* global, const uint32_t* mix);
+// r0h_logup_check_balance with the lowest imbalanced class turned into an error that starts with `caller` (the sequencer under
+// r0h_ctx_set_check_balance)
+const char* require_balance(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global);
 // the log-derivative accumulation on the device (logup.hip): multiplicities into DATA, the ACCUM group, totals of the public accumulators
 const char* logup_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum);
 // The public accumulators' scanned terms of one segment, kept from the totals step for the accumulation that follows it on the same

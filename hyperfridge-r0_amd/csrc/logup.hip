@@ -16,6 +16,8 @@
 // The term interpreter reads a flat tape of the fractions (uniform across the wave: scalar loads) built per launch on the host, public
 // inputs folded into the coefficients.  The accumulators with a public total are evaluated and scanned for their totals
 // (r0h_logup_totals); a session keeps those scanned terms for the accumulation of the same segment (LogupKept, circuit.hpp).
+// The same tape, with the challenges' identities in place of their values, is what the balance check walks (r0h_logup_check_balance: which
+// classes of the chain links' tuples do not cancel; the kernels are described where they stand).
 #include <algorithm>
 #include <map>
 
@@ -29,13 +31,16 @@ struct Tape {
   std::vector<uint32_t> words;              // per accumulator, per fraction: table, num form, n_parts, (challenge index, form)...; form = n, (coef, column + 1)...
   std::vector<const uint32_t*> cols;        // column base pointers
   std::vector<Fp4> ch;                      // challenges; index 0 is "one"
+  std::vector<uint64_t> ch_id;              // their identities, kind << 32 | index (0: "one"): what the balance check's weights are indexed by
   std::vector<uint32_t> acc_begin;          // word offset of every accumulator
 };
 
-const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, Tape* t) {
+// `n_accs`: the first n_accs accumulators alone (the balance check walks the chain links and nothing else)
+const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, Tape* t, uint32_t n_accs = 0xffffffffu) {
   std::map<uint32_t, uint32_t> col_index;
   std::map<uint64_t, uint32_t> ch_index;
   t->ch.push_back(fp4_one());
+  t->ch_id.push_back(0);
   auto form = [&](const Lf& lf) -> const char* {
     t->words.push_back((uint32_t)lf.terms.size());
     for (const LfTerm& term : lf.terms) {
@@ -62,6 +67,7 @@ const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, 
     return nullptr;
   };
   for (const LogupAcc& a : c->logup.accs) {
+    if (t->acc_begin.size() >= n_accs) break;
     t->acc_begin.push_back((uint32_t)t->words.size());
     for (const LogupFraction& f : a.fr) {
       t->words.push_back(f.table);
@@ -77,6 +83,7 @@ const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, 
             R0H_REQUIRE(q.ch_kind == 1 ? mix != nullptr : global != nullptr, "log-derivative accumulation: a challenge is read from %s and none were given", q.ch_kind == 1 ? "the mix" : "the public inputs");
             it = ch_index.emplace(key, (uint32_t)t->ch.size()).first;
             t->ch.push_back(Fp4{{src[0], src[1], src[2], src[3]}});
+            t->ch_id.push_back(key);
           }
           idx = it->second;
         }
@@ -264,6 +271,175 @@ __global__ void logup_chain_kernel(uint32_t* __restrict__ accum, const uint32_t*
   uint32_t* cell = accum + ((size_t)col << po2) + r;
   *cell = add(*cell, scanned[4 * (size_t)(r - 1) + (col & 3u)]);
 }
+// ---- the balance check of the chain links (r0h_logup_check_balance, include/r0hip.h): every fraction with a non-zero numerator is a
+// tuple, its class the denominator as a polynomial in the challenges, told apart by balance_key (circuit.hpp).  Classes meet in an
+// open-addressed table in global memory -- one 64-bit compare-and-swap claims a slot, then a sum, a count and a minimum, all atomics
+// at device scope, so the table's CONTENT does not depend on scheduling (where a class sits does; the host orders what it reads
+// back) -- behind a table of the same shape in LDS that takes every insert of its workgroup first: on a real trace most lookup slots
+// ask for value 0, one class of tens of millions of members, which without that stage would all meet in one global slot
+// (profiles/r05/logup_before.md, for the multiplicity count).  No workgroup waits for another, every probe sequence is bounded by its
+// table's size, and what the scan reads is complete by the kernel boundary alone.
+struct BalanceSlot {
+  unsigned long long key;        // 0: empty
+  unsigned long long sum;        // of the canonical numerators
+  unsigned long long first_inv;  // ~(row << 32 | fraction) of the lowest member: a maximum, so that an all-zero table is an empty one
+  uint32_t members, pad;
+};
+static_assert(sizeof(BalanceSlot) == 32, "a slot is half a 64-byte line");
+constexpr uint32_t BAL_THREADS = 1024;
+constexpr uint32_t BAL_LDS_BITS = 12, BAL_LDS_SLOTS = 1u << BAL_LDS_BITS;  // 4,096 classes a workgroup: 112 KB of the CU's 160
+constexpr uint32_t BAL_LDS_PROBES = 8;
+constexpr unsigned long long BAL_SPREAD = 0x9E3779B97F4A7C15ull;
+enum { BAL_TUPLES = 0, BAL_GLOBAL_INSERTS, BAL_IMBALANCED, BAL_FIRST_INV, BAL_ERR, BAL_CURSOR, BAL_COUNTERS };
+
+__device__ __forceinline__ void balance_global_insert(BalanceSlot* __restrict__ table, uint32_t slot_bits, unsigned long long* __restrict__ ctr, unsigned long long key,
+                                                      unsigned long long sum, uint32_t members, unsigned long long first_inv) {
+  const unsigned long long mask = (1ull << slot_bits) - 1;
+  unsigned long long i = (key * BAL_SPREAD) >> (64 - slot_bits);
+  for (unsigned long long probe = 0; probe <= mask; probe++) {  // (at a load of 1/2 or less: a handful)
+    BalanceSlot* s = table + i;
+    const unsigned long long prev = atomicCAS(&s->key, 0ull, key);
+    if (prev == 0ull || prev == key) {
+      atomicAdd(&s->sum, sum);
+      atomicAdd(&s->members, members);
+      atomicMax(&s->first_inv, first_inv);
+      return;
+    }
+    i = (i + 1) & mask;
+  }
+  atomicOr(&ctr[BAL_ERR], 1ull);  // every slot is another class's: the caller reports "table full"
+}
+
+// the tuples there are: what the table is sized from.  The numerators alone are evaluated; the parts are stepped over.
+__global__ __launch_bounds__(BAL_THREADS) void balance_count_kernel(unsigned long long* __restrict__ ctr, const uint32_t* __restrict__ tape, const uint32_t* const* __restrict__ cols,
+                                                                    uint32_t n_acc, uint32_t po2) {
+  __shared__ unsigned long long total;
+  if (threadIdx.x == 0) total = 0;
+  __syncthreads();
+  const uint32_t n = 1u << po2;
+  uint32_t count = 0;
+  for (uint32_t r = blockIdx.x * BAL_THREADS + threadIdx.x; r < n; r += gridDim.x * BAL_THREADS) {
+    uint32_t at = 0;
+    for (uint32_t f = 0; f < 4 * n_acc; f++) {
+      at++;  // table
+      count += eval_form(tape, at, cols, r) != 0u;
+      const uint32_t n_parts = tape[at++];
+      for (uint32_t q = 0; q < n_parts; q++) {
+        const uint32_t n_terms = tape[at + 1];
+        at += 2 + 2 * n_terms;
+      }
+    }
+  }
+  if (count) atomicAdd(&total, (unsigned long long)count);
+  __syncthreads();
+  if (threadIdx.x == 0 && total) atomicAdd(&ctr[BAL_TUPLES], total);
+}
+
+// A grid of at most one workgroup per CU strides over the rows, a lane per row.  Every fraction's parts are evaluated whatever its
+// numerator (the tape position stays uniform across the wave: scalar loads); a numerator of zero inserts nothing.
+__global__ __launch_bounds__(BAL_THREADS) void balance_insert_kernel(BalanceSlot* __restrict__ table, uint32_t slot_bits, unsigned long long* __restrict__ ctr,
+                                                                     const uint32_t* __restrict__ tape, const uint32_t* const* __restrict__ cols,
+                                                                     const uint32_t* __restrict__ weights /* [2][n_ch] */, uint32_t n_ch, uint32_t n_acc, uint32_t po2) {
+  __shared__ unsigned long long l_key[BAL_LDS_SLOTS], l_sum[BAL_LDS_SLOTS], l_first[BAL_LDS_SLOTS];
+  __shared__ uint32_t l_members[BAL_LDS_SLOTS];
+  __shared__ uint32_t l_used;
+  __shared__ unsigned long long l_sent;
+  for (uint32_t i = threadIdx.x; i < BAL_LDS_SLOTS; i += BAL_THREADS) {
+    l_key[i] = 0;
+    l_sum[i] = 0;
+    l_first[i] = 0;
+    l_members[i] = 0;
+  }
+  if (threadIdx.x == 0) {
+    l_used = 0;
+    l_sent = 0;
+  }
+  __syncthreads();
+  const uint32_t n = 1u << po2;
+  uint32_t sent = 0;  // inserts of this lane into the global table
+  for (uint32_t base = blockIdx.x * BAL_THREADS; base < n; base += gridDim.x * BAL_THREADS) {  // uniform across the workgroup: it meets at barriers
+    const uint32_t r = base + threadIdx.x;
+    if (r < n) {
+      uint32_t at = 0;
+      for (uint32_t f = 0; f < 4 * n_acc; f++) {
+        at++;  // table
+        const uint32_t num = eval_form(tape, at, cols, r);
+        const uint32_t n_parts = tape[at++];
+        uint32_t h0 = 0, h1 = 0;
+        for (uint32_t q = 0; q < n_parts; q++) {
+          const uint32_t ci = tape[at++];
+          const uint32_t v = eval_form(tape, at, cols, r);
+          h0 = add(h0, mul(weights[ci], v));
+          h1 = add(h1, mul(weights[n_ch + ci], v));
+        }
+        if (!num) continue;
+        const unsigned long long key = balance_key(h0, h1), value = dec(num), first_inv = ~((unsigned long long)r << 32 | f);
+        uint32_t i = (uint32_t)((key * BAL_SPREAD) >> (64 - BAL_LDS_BITS));
+        bool placed = false;
+        for (uint32_t probe = 0; probe < BAL_LDS_PROBES && !placed; probe++) {
+          const unsigned long long prev = atomicCAS(&l_key[i], 0ull, key);
+          if (prev == 0ull) atomicAdd(&l_used, 1u);
+          if (prev == 0ull || prev == key) {
+            atomicAdd(&l_sum[i], value);
+            atomicAdd(&l_members[i], 1u);
+            atomicMax(&l_first[i], first_inv);
+            placed = true;
+          }
+          i = (i + 1) & (BAL_LDS_SLOTS - 1);
+        }
+        if (!placed) {  // the workgroup's table is full hereabouts: straight to the global one
+          balance_global_insert(table, slot_bits, ctr, key, value, 1u, first_inv);
+          sent++;
+        }
+      }
+    }
+    __syncthreads();
+    const bool full = l_used > BAL_LDS_SLOTS / 2;
+    const bool last = base + gridDim.x * BAL_THREADS >= n;  // (n <= 2^24 rows and at most a workgroup per CU: no wrap)
+    __syncthreads();
+    if (full || last) {  // flushed when it fills, and once more at the end
+      for (uint32_t i = threadIdx.x; i < BAL_LDS_SLOTS; i += BAL_THREADS) {
+        if (!l_key[i]) continue;
+        balance_global_insert(table, slot_bits, ctr, l_key[i], l_sum[i], l_members[i], l_first[i]);
+        sent++;
+        l_key[i] = 0;
+        l_sum[i] = 0;
+        l_first[i] = 0;
+        l_members[i] = 0;
+      }
+      if (threadIdx.x == 0) l_used = 0;
+      __syncthreads();
+    }
+  }
+  if (sent) atomicAdd(&l_sent, (unsigned long long)sent);
+  __syncthreads();
+  if (threadIdx.x == 0 && l_sent) atomicAdd(&ctr[BAL_GLOBAL_INSERTS], l_sent);
+}
+
+// the classes whose numerators do not sum to zero: how many, and the lowest (row, fraction) among their first members
+__global__ __launch_bounds__(256) void balance_scan_kernel(const BalanceSlot* __restrict__ table, unsigned long long slots, unsigned long long* __restrict__ ctr) {
+  unsigned long long count = 0, best = 0;
+  for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i < slots; i += gridDim.x * 256ull) {
+    const BalanceSlot s = table[i];
+    if (!s.key || s.sum % P == 0) continue;
+    count++;
+    best = s.first_inv > best ? s.first_inv : best;
+  }
+  if (count) {
+    atomicAdd(&ctr[BAL_IMBALANCED], count);
+    atomicMax(&ctr[BAL_FIRST_INV], best);
+  }
+}
+// ... and the list of them: those whose first member is at or below `floor_inv` (inverted: at or above), `room` of them at the most
+__global__ __launch_bounds__(256) void balance_compact_kernel(BalanceSlot* __restrict__ list, unsigned long long room, const BalanceSlot* __restrict__ table, unsigned long long slots,
+                                                              unsigned long long floor_inv, unsigned long long* __restrict__ ctr) {
+  for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i < slots; i += gridDim.x * 256ull) {
+    const BalanceSlot s = table[i];
+    if (!s.key || s.sum % P == 0 || s.first_inv < floor_inv) continue;
+    const unsigned long long at = atomicAdd(&ctr[BAL_CURSOR], 1ull);
+    if (at < room) list[at] = s;
+  }
+}
 }  // namespace
 
 // tests/test_gpu_logup_kept.py hands the two internal entry points an empty LogupKept of its own making: one pointer, then po2, then n_own
@@ -386,6 +562,96 @@ const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_
   R0H_GUARD_END
 }
 
+// Which classes of the chain links' fractions do not cancel (include/r0hip.h).  Reads DATA, CODE and the public inputs: no mix.
+const char* r0h_logup_check_balance(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, r0h_imbalance* out,
+                                    size_t capacity, size_t* n_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && c && data && n_out && (out || !capacity), "r0h_logup_check_balance: NULL argument");
+  R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_logup_check_balance: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
+  *n_out = 0;
+  const uint32_t n = 1u << po2, n_chain = c->logup.n_chain;
+  if (!n_chain) return nullptr;
+  R0H_REQUIRE(((size_t)c->group_size[R0H_GROUP_DATA] << po2) * 4 <= data->bytes && (!code || ((size_t)c->group_size[R0H_GROUP_CODE] << po2) * 4 <= code->bytes),
+              "r0h_logup_check_balance: buffers too small for 2^%u rows", po2);
+  R0H_REQUIRE(((uint64_t)(4 * n_chain) << po2) <= 0xffffffffull, "r0h_logup_check_balance: %u fractions on 2^%u rows: more than 2^32 - 1 tuples", 4 * n_chain, po2);
+  for (uint32_t i = 0; i + c->n_late < c->n_global; i++) R0H_REQUIRE(!global || global[i] < P, "r0h_logup_check_balance: global[%u] not canonical", i);
+  Tape t;
+  std::vector<uint32_t> dummy_mix(c->n_mix, 0);  // the challenges' values are not read, their identities are
+  R0H_TRY(build_tape(c, po2, code, data, global, dummy_mix.data(), &t, n_chain));
+  DeviceTape d;
+  R0H_TRY(upload_tape(ctx, t, &d));
+  const uint32_t n_ch = (uint32_t)t.ch.size();
+  std::vector<uint32_t> weights(2 * (size_t)n_ch);
+  for (uint32_t j = 0; j < 2; j++)
+    for (uint32_t k = 0; k < n_ch; k++) weights[(size_t)j * n_ch + k] = balance_weight(j, t.ch_id[k]);
+  DevBuf side;  // the counters, then the two weight rows
+  R0H_TRY(side.alloc(ctx, BAL_COUNTERS * 8 + weights.size() * 4));
+  unsigned long long* const ctr = (unsigned long long*)side->ptr;
+  const uint32_t* const d_weights = (const uint32_t*)(ctr + BAL_COUNTERS);
+  R0H_TRY_HIP(hipMemsetAsync(ctr, 0, BAL_COUNTERS * 8, ctx->stream));
+  R0H_TRY(stage_h2d(ctx, (void*)d_weights, weights.data(), weights.size() * 4));
+  if (!ctx->n_cu) R0H_TRY_HIP(hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  const uint32_t grid = std::min<uint32_t>((uint32_t)std::max(ctx->n_cu, 1), (n + BAL_THREADS - 1) / BAL_THREADS);  // persistent: a workgroup per CU, fewer where the rows do not fill them
+  KScope ks(ctx, "logup_check_balance", 2.0 * t.cols.size() * n * 4);
+  hipLaunchKernelGGL(balance_count_kernel, dim3(grid), dim3(BAL_THREADS), 0, ctx->stream, ctr, d.words, d.cols, n_chain, po2);
+  R0H_TRY(launch_ok("balance_count_kernel"));
+  unsigned long long counters[BAL_COUNTERS];
+  R0H_TRY(r0h_buf_d2h(ctx, side.get(), 0, counters, sizeof counters));
+  const uint64_t tuples = counters[BAL_TUPLES];
+  ctx->balance_stats[0] = tuples;
+  ctx->balance_stats[1] = ctx->balance_stats[2] = 0;
+  if (!tuples) return nullptr;
+  uint32_t slot_bits = 10;  // a load of 1/2 at the most (every tuple a class of its own), and no table smaller than 1,024 slots
+  while ((1ull << slot_bits) < 2 * tuples) slot_bits++;
+  const uint64_t slots = 1ull << slot_bits;
+  DevBuf table;
+  R0H_TRY(table.alloc(ctx, slots * sizeof(BalanceSlot)));  // (an allocation the device refuses is this call's error)
+  R0H_TRY_HIP(hipMemsetAsync(table->ptr, 0, slots * sizeof(BalanceSlot), ctx->stream));
+  BalanceSlot* const d_table = (BalanceSlot*)table->ptr;
+  hipLaunchKernelGGL(balance_insert_kernel, dim3(grid), dim3(BAL_THREADS), 0, ctx->stream, d_table, slot_bits, ctr, d.words, d.cols, d_weights, n_ch, n_chain, po2);
+  R0H_TRY(launch_ok("balance_insert_kernel"));
+  const uint32_t scan_grid = (uint32_t)std::min<uint64_t>((slots + 255) / 256, 8ull * (uint32_t)std::max(ctx->n_cu, 1));
+  hipLaunchKernelGGL(balance_scan_kernel, dim3(scan_grid), dim3(256), 0, ctx->stream, d_table, (unsigned long long)slots, ctr);
+  R0H_TRY(launch_ok("balance_scan_kernel"));
+  R0H_TRY(r0h_buf_d2h(ctx, side.get(), 0, counters, sizeof counters));
+  ctx->balance_stats[1] = counters[BAL_GLOBAL_INSERTS];
+  ctx->balance_stats[2] = slots;
+  R0H_REQUIRE(!counters[BAL_ERR], "r0h_logup_check_balance: table full");
+  const uint64_t n_bad = counters[BAL_IMBALANCED];
+  *n_out = (size_t)n_bad;
+  if (!n_bad || !capacity) return nullptr;
+  // the `capacity` lowest: one wanted of many is the minimum the scan has found; otherwise all of them come back and are ordered here
+  const bool lowest_only = capacity == 1 && n_bad > 1;
+  const uint64_t room = lowest_only ? 1 : n_bad;
+  DevBuf list;
+  R0H_TRY(list.alloc(ctx, room * sizeof(BalanceSlot)));
+  hipLaunchKernelGGL(balance_compact_kernel, dim3(scan_grid), dim3(256), 0, ctx->stream, (BalanceSlot*)list->ptr, (unsigned long long)room, d_table, (unsigned long long)slots,
+                     lowest_only ? counters[BAL_FIRST_INV] : 0ull, ctr);
+  R0H_TRY(launch_ok("balance_compact_kernel"));
+  std::vector<BalanceSlot> found(room);
+  R0H_TRY(r0h_buf_d2h(ctx, list.get(), 0, found.data(), room * sizeof(BalanceSlot)));
+  std::sort(found.begin(), found.end(), [](const BalanceSlot& a, const BalanceSlot& b) { return a.first_inv > b.first_inv; });
+  for (size_t k = 0; k < found.size() && k < capacity; k++) {
+    const uint64_t first = ~found[k].first_inv;
+    out[k] = r0h_imbalance{(uint32_t)first, (uint32_t)(first >> 32), (uint32_t)(found[k].sum % P), found[k].members};
+  }
+  return nullptr;
+  R0H_GUARD_END
+}
+
+const char* r0h_logup_check_balance_stats(const r0h_ctx* ctx, uint64_t stats_out[3]) {
+  R0H_REQUIRE(ctx && stats_out, "r0h_logup_check_balance_stats: NULL argument");
+  for (int k = 0; k < 3; k++) stats_out[k] = ctx->balance_stats[k];
+  return nullptr;
+}
+
+const char* r0h_ctx_set_check_balance(r0h_ctx* ctx, int on) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_check_balance: ctx is NULL");
+  ctx->check_balance = on != 0;
+  for (r0h_ctx* h : ctx->helpers) h->check_balance = ctx->check_balance;
+  return nullptr;
+}
+
 // The totals of the accumulators that run alone (their challenges are public inputs, so they can be had before the mix is drawn):
 // global_io[final .. final + 4) of each is overwritten with its total over the rows.
 const char* r0h_logup_totals(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io) {
@@ -393,6 +659,14 @@ const char* r0h_logup_totals(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, c
 }
 
 }  // extern "C"
+
+const char* r0h::require_balance(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global) {
+  r0h_imbalance first = {0, 0, 0, 0};
+  size_t n_bad = 0;
+  R0H_TRY(r0h_logup_check_balance(ctx, c, po2, code, data, global, &first, 1, &n_bad));
+  R0H_REQUIRE(!n_bad, "%s: fraction %u does not balance: net %u over %u tuples, first at row %u; %zu classes in all", caller, first.fraction, first.net, first.members, first.first_row, n_bad);
+  return nullptr;
+}
 
 const char* r0h::logup_totals_keep(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io, LogupKept* keep) {
   R0H_GUARD_BEGIN

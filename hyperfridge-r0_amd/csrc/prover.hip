@@ -212,6 +212,12 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* code, const r0h_cod
     st.check_data = data;
     R0H_REQUIRE(st.check_code, "prove_segment: checking the witness needs the CODE columns, and this CODE commitment keeps none");
   }
+  if (ctx->check_balance && circ->logup.n_chain) {  // r0h_ctx_set_check_balance: before anything of this segment is committed
+    const r0h_buf* columns = code ? code : cc->witness;
+    R0H_REQUIRE(columns, "prove_segment: checking the witness needs the CODE columns, and this CODE commitment keeps none");
+    phase(ctx, "check_balance");
+    R0H_TRY(require_balance("prove_segment", ctx, circ, po2, columns, data, global));
+  }
 
   phase(ctx, "transcript_seed");
   {

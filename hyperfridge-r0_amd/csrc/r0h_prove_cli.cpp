@@ -10,6 +10,11 @@
 // witness is checked on the device before its ACCUM group is committed, and a violated segment ends the run with the term, its row count
 // and its first row -- and the term's name, from --term-names or <circuit>.terms.txt beside the blob (one name per line, in term
 // order: tools/gen_circuit.py --names; the build writes them for the trace and image circuits).
+// --check-balance 1 (both modes; [--fraction-names file.txt]) turns r0h_ctx_set_check_balance on: the chain links' fractions of every
+// segment's witness must cancel class by class (r0h_logup_check_balance) before its DATA group is committed, and a segment that does not
+// balance ends the run with the fraction, the net of its class, its tuples and its first row -- and the fraction's name, from
+// --fraction-names or <circuit>.fractions.txt beside the blob (tools/gen_circuit.py --fraction-names; the build writes them for the trace
+// and image circuits).  A circuit without a LOGUP section has nothing to check.
 // With --receipt-out / --receipt-dir every segment is proved for a claim (risc0-zkvm `ReceiptClaim`): the session's system states
 // are synthetic names (there is no executor here), segment k runs from state k to state k+1, all but the last end in SystemSplit,
 // the last halts with the journal's output; the claim's eight naming words are planted as the segment's public inputs.  The image
@@ -43,8 +48,14 @@
 #include "../../include/r0hip.h"
 
 static std::vector<std::string> term_names;  // --check-witness: what a violated term is called (empty: its number is all there is)
+static std::vector<std::string> fraction_names;  // --check-balance: likewise for a fraction that does not balance
 static void die(const char* what, const char* err) {
   fprintf(stderr, "r0h_prove: %s: %s\n", what, err);
+  const char* fr = strstr(err, ": fraction ");
+  if (fr && strstr(fr, " does not balance: net ")) {
+    const unsigned long f = strtoul(fr + 11, nullptr, 10);
+    if (f < fraction_names.size()) fprintf(stderr, "r0h_prove: fraction %lu is \"%s\"\n", f, fraction_names[f].c_str());
+  }
   const char* at = strstr(err, "the witness violates");
   if (at && (at = strstr(at, ": term "))) {
     const unsigned long t = strtoul(at + 7, nullptr, 10);
@@ -64,15 +75,17 @@ int main(int argc, char** argv) {
     printf("usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--hashfn poseidon2|sha-256] [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]\n"
            "       r0h_prove <trace.r0c> --elf guest.elf --input words.bin [--code-object file.hsaco] [--po2 N] [--device D] --receipt-out file.json\n"
            "       --check-witness 1 [--check-code-object file.hsaco] [--term-names file.txt]: check every segment's witness on the device before its ACCUM group is committed; "
-           "a violated segment ends the run with the constraint term, its name, how many rows violate it and the first of them\n%s\n", r0h_version());
+           "a violated segment ends the run with the constraint term, its name, how many rows violate it and the first of them\n"
+           "       --check-balance 1 [--fraction-names file.txt]: check that the log-derivative fractions of every segment's witness cancel before its DATA group is committed; "
+           "a segment that does not balance ends the run with the fraction, its name, the net of its class and its first row\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   std::string blob_path = argv[1], co_path, seal_out, receipt_out, receipt_dir, journal_text, elf_path, input_path;
   std::string hashfn = "poseidon2";         // --hashfn: the hash suite of the synthetic-circuit mode (seals only)
   std::map<std::string, std::string> camt;  // --camt53-response and what goes with it
   std::string receipt_prefix;               // --receipt-prefix P: the reference's file name, P-Receipt-<image id>-latest.json (host/src/main.rs:312-316)
-  std::string image_circuit_path, image_co_path, check_co_path, term_names_path;
-  unsigned check_witness = 0;
+  std::string image_circuit_path, image_co_path, check_co_path, term_names_path, fraction_names_path;
+  unsigned check_witness = 0, check_balance = 0;
   unsigned po2 = 16, segments = 1, device = 0, contexts = 1, verify = 0, receipts = 1;
   unsigned long long seed = 1;
   for (int i = 2; i + 1 < argc; i += 2) {
@@ -88,6 +101,8 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--check-witness")) check_witness = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--check-code-object")) check_co_path = argv[i + 1];
     else if (!strcmp(argv[i], "--term-names")) term_names_path = argv[i + 1];
+    else if (!strcmp(argv[i], "--check-balance")) check_balance = (unsigned)atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--fraction-names")) fraction_names_path = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
     else if (!strcmp(argv[i], "--journal")) journal_text = argv[i + 1];
@@ -103,6 +118,7 @@ int main(int argc, char** argv) {
       camt[argv[i] + 2] = argv[i + 1];
     else { fprintf(stderr, "r0h_prove: unknown option %s\n", argv[i]); return 1; }
   }
+  if ((argc - 2) % 2) { fprintf(stderr, "r0h_prove: option %s needs a value\n", argv[argc - 1]); return 1; }
   if (hashfn != "poseidon2" && hashfn != "sha-256") { fprintf(stderr, "r0h_prove: --hashfn is poseidon2 or sha-256, not %s\n", hashfn.c_str()); return 1; }
   if (hashfn != "poseidon2" && (!elf_path.empty() || !receipt_out.empty() || !receipt_dir.empty() || !receipt_prefix.empty() || !camt.empty() || !image_circuit_path.empty())) {
     fprintf(stderr, "r0h_prove: --hashfn %s proves bare seals (--seal-out / --verify); receipts name poseidon2 only, so it does not go with --elf, --receipt-out, "
@@ -129,8 +145,21 @@ int main(int argc, char** argv) {
     }
     if (g) fclose(g);
   }
+  if (check_balance) {
+    std::string names = fraction_names_path;
+    if (names.empty() && blob_path.size() > 4 && blob_path.compare(blob_path.size() - 4, 4, ".r0c") == 0) names = blob_path.substr(0, blob_path.size() - 4) + ".fractions.txt";
+    FILE* g = names.empty() ? nullptr : fopen(names.c_str(), "rb");
+    if (!g && !fraction_names_path.empty()) { fprintf(stderr, "r0h_prove: cannot open %s\n", names.c_str()); return 1; }
+    char line[256];
+    while (g && fgets(line, sizeof line, g)) {
+      line[strcspn(line, "\r\n")] = 0;
+      fraction_names.push_back(line);
+    }
+    if (g) fclose(g);
+  }
   // --check-witness: the context's switch, and the checker's module now (from its code object, else compiled in-process) rather than inside the first proof
   auto arm_checker = [&](r0h_ctx* ctx, r0h_circuit* circ) {
+    if (check_balance) CHECK(r0h_ctx_set_check_balance(ctx, 1));
     if (!check_witness) return;
     CHECK(r0h_ctx_set_check_witness(ctx, 1));
     CHECK(r0h_circuit_load_check(circ, check_co_path.empty() ? nullptr : check_co_path.c_str()));

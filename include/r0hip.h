@@ -172,7 +172,8 @@ const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, con
  * also beyond `capacity`.  accum == NULL checks only the terms that reach no ACCUM tap and no word of the mix -- what can be checked
  * before the mix is drawn (mix_host may then be NULL).  The checker's text (r0h_circuit_emit_hip_check, pure host) is compiled
  * in-process on first use and kept with the circuit; r0h_circuit_load_check loads a gfx950 code object built from that text instead.
- * Lookups of values outside their table are r0h_logup_multiplicities' to report, not the checker's. */
+ * Lookups of values outside their table are r0h_logup_multiplicities' to report, not the checker's; whether the tuples and lookups of
+ * a log-derivative argument cancel is r0h_logup_check_balance's (below). */
 typedef struct { uint32_t term, rows, first_row, reserved; } r0h_violation;
 const char* r0h_circuit_emit_hip_check(const uint32_t* blob, size_t n_words, char** source_out);
 const char* r0h_circuit_load_check(r0h_circuit* c, const char* code_object_path /* NULL: compile in-process now */);
@@ -185,6 +186,43 @@ const char* r0h_check_witness(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, 
  * and its first row instead of a seal no verifier accepts.  Between r0h_proof_begin* and r0h_proof_finish the CODE and DATA
  * witness buffers must then stay as they were given.  Off (the default): nothing is checked, seals and timing are unchanged. */
 const char* r0h_ctx_set_check_witness(r0h_ctx* ctx, int on);
+/* ---- the balance check: which tuples a log-derivative argument (blob section LOGUP, r0hip_circuit.h) fails to cancel.  A witness
+ * whose reads do not return what was written, whose boundary rows or multiplicities are off, still has running sums: the checker
+ * above sees one chain-link term violated on the wrap row and nothing else.  This check names the fractions instead.
+ * Only the links of the chain are looked at (accumulators whose `final` is 0xffffffff); an accumulator with a public total -- the
+ * trace circuit's session sum -- balances across segments and the verifier only, and is left out.  Fraction f = 4 * accumulator + slot,
+ * 0 <= f < r0h_circuit_n_chain_fractions.  Fraction f contributes a TUPLE on row r iff its numerator n(f, r) is not zero.  The tuple's
+ * CLASS is its denominator as a polynomial in the challenges: per challenge identity -- "one", (1, index), (2, index) -- the sum of the
+ * values of the parts under it, identities whose sum is zero dropped; two tuples are of one class iff these vectors are equal (the
+ * order of the parts, a challenge split over several parts, and a part whose value is zero make no difference).  The argument
+ * BALANCES iff in every class the numerators sum to 0 mod p; a lookup and its table's multiplicity fraction are ordinary members of
+ * one class.  DATA, CODE and the public inputs are read and no mix: the check can run before anything is committed.
+ * Classes are told apart by a 62-bit fingerprint, two linear hashes over F_p of the per-identity sums under fixed weights: two given
+ * distinct classes share it with probability about p^-2 < 2^-61 over the choice of weights, and two that do are reported as one (their
+ * sums added).  The weights are public and fixed: this is a diagnostic for honest mistakes, not a verifier.
+ * One r0h_imbalance per class that does not balance: (first_row, fraction) is the lexicographically smallest (row, fraction) among its
+ * members, `net` the sum of the numerators as a canonical integer in [1, p) (1: produced once too often, p - 1: consumed once too
+ * often), `members` its tuples (saturating at 2^32 - 1; more than 2^32 - 1 tuple slots, fractions x rows, are refused).  Entries come
+ * in (first_row, fraction) order; *n_out counts all of them, also beyond `capacity`, and `out` then holds the `capacity` lowest.
+ * Every field is a minimum, a sum or a count: the answer does not depend on scheduling.  po2 in [4, R0H_MAX_PO2]; a circuit without
+ * chain fractions gives *n_out = 0.  code may be NULL for a circuit whose chain reads no CODE column.  The device takes its table
+ * from the context's pool, sized from the tuples there are (load <= 1/2); a probe sequence that runs out of slots returns
+ * "r0h_logup_check_balance: table full".  r0h_logup_check_balance_host is the same contract in plain loops over host words (Montgomery
+ * form, column-major, as the device buffers hold them).  r0h_logup_check_balance_stats: of the context's last device call, the tuples,
+ * the inserts that reached the global table (the rest were merged in LDS) and the table's slots. */
+typedef struct { uint32_t fraction, first_row, net, members; } r0h_imbalance;
+uint32_t r0h_circuit_n_chain_fractions(const r0h_circuit* c);
+const char* r0h_logup_check_balance(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data,
+                                    const uint32_t* global_host, r0h_imbalance* out, size_t capacity, size_t* n_out);
+const char* r0h_logup_check_balance_host(const uint32_t* blob, size_t blob_words, uint32_t po2, const uint32_t* code,
+                                         const uint32_t* data, const uint32_t* global, r0h_imbalance* out, size_t capacity,
+                                         size_t* n_out);
+const char* r0h_logup_check_balance_stats(const r0h_ctx* ctx, uint64_t stats_out[3]);
+/* on != 0: from now on r0h_prove_segment*, r0h_proof_begin* and the sessions of this context run the balance check on the caller's
+ * CODE and DATA witness before the DATA group is committed, and a segment that does not balance returns "...: fraction F does not
+ * balance: net N over M tuples, first at row R; K classes in all".  Independent of r0h_ctx_set_check_witness.  Off (the default):
+ * nothing is checked, seals and timing are unchanged. */
+const char* r0h_ctx_set_check_balance(r0h_ctx* ctx, int on);
 
 /* ---- the sequencer: risc0-circuit-rv32im `SegmentProver::prove` + risc0-zkp `Prover::{commit_group, finalize}` ---- */
 /* code/data: witness columns resident in device memory ([group_size][2^po2]); global: host words.

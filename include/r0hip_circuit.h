@@ -45,6 +45,11 @@
  *                The multiplicity of v counts the rows whose lookup numerator is 1 and whose value is v (a numerator of 0 gates
  *                the lookup off, whatever its value); a numerator other than 0 or 1, a value outside its table on a row whose
  *                numerator is 1, and more than p - 1 lookup slots (lookups x rows) of one table are errors
+ *                Balance (r0h_logup_check_balance, r0hip.h): number the chain links' fractions in blob order, f = 4 * accumulator +
+ *                slot; fraction f on row r is a tuple iff its numerator there is not zero; the tuple's class is its denominator as
+ *                a polynomial in the challenges -- per challenge identity (kind 0 "one", (1, index), (2, index)) the sum of the
+ *                values of the parts under it, zero sums dropped -- and the chain closes iff in every class the numerators sum to
+ *                0 mod p.  Accumulators with a public total balance across segments and the verifier only: they are left out
  *   PERIODIC (11): period, n_cols, then n_cols x period canonical values: what CODE columns of kind 6 repeat
  *   SPONGE (12): [the in-circuit Poseidon2 sponge of the recursion circuit: tools/sponge_component.py] first CODE column (28 columns: rc[24],
  *                sel_mix, sel_full, sel_part, sel_last), first DATA column (65 columns: st[24], aux[24], in[16], act), first of the 8 public

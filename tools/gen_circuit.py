@@ -472,12 +472,47 @@ def term_names(circuit):
     return ["term:%d" % t for t in range(sum(1 for k in range(n_steps) if words[at + 4 + 4 * k] == OP_AND_EQZ))]
 
 
+def fraction_names(circuit):
+    """What the chain links' fractions of `circuit` (a shape's name) are called, in the order r0h_logup_check_balance numbers them
+    (4 * accumulator + slot, r0h_circuit_n_chain_fractions of them): the trace circuit's carry the names its generator gives them
+    (tools/trace_circuit.fractions); every other circuit has ordinals, none where it has no LOGUP section."""
+    if circuit == "trace":
+        import trace_circuit
+        return [f.name for f in trace_circuit.fractions()[0]]
+    words = generate_image()[0] if circuit == "image" else generate(**SHAPES[circuit])[0]
+    at, end = 3, len(words)
+    while at < end and words[at] != SEC_LOGUP:
+        at += 2 + words[at + 1]
+    if at >= end:
+        return []
+    n_chain, pos = 0, at + 4 + 2 * words[at + 3]      # past n_acc, n_tables and the tables
+
+    def form(pos):
+        return pos + 1 + 3 * words[pos]
+    for _ in range(words[at + 2]):
+        n_fr, final = words[pos], words[pos + 1]
+        pos += 2
+        for _ in range(n_fr):
+            pos = form(pos + 1)
+            n_parts = words[pos]
+            pos += 1
+            for _ in range(n_parts):
+                pos = form(pos + 2)
+        n_chain += final == 0xFFFFFFFF
+    return ["fraction:%d" % f for f in range(4 * n_chain)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("shape", choices=sorted(SHAPES) + ["trace", "image"])
     ap.add_argument("out")
     ap.add_argument("--names", action="store_true", help="write the names of the shape's constraint terms, one per line in term order, instead of the blob")
+    ap.add_argument("--fraction-names", action="store_true", help="write the names of the shape's chain fractions, one per line in the order r0h_logup_check_balance numbers them, instead of the blob")
     args = ap.parse_args()
+    if args.fraction_names:
+        with open(args.out, "w") as f:
+            f.write("".join(name + "\n" for name in fraction_names(args.shape)))
+        return 0
     if args.names:
         with open(args.out, "w") as f:
             f.write("".join(name + "\n" for name in term_names(args.shape)))
