@@ -84,6 +84,17 @@ _SIGNATURES = {
     "r0h_logup_check_balance_host": [_vp, _sz, _u32, _vp, _vp, _vp, _vp, _sz, _c.POINTER(_sz)],
     "r0h_logup_check_balance_stats": [_vp, _vp],
     "r0h_ctx_set_check_balance": [_vp, _c.c_int],
+    "r0h_session_balance_new": [_vp, _vp, _sz, _pp],
+    "r0h_session_balance_free": [_vp],
+    "r0h_session_balance_identity": [_vp, _u32, _c.POINTER(_u32), _c.POINTER(_u32)],
+    "r0h_session_balance_add": [_vp, _u32, _vp, _u32, _vp, _vp, _vp],
+    "r0h_session_balance_add_host": [_vp, _u32, _u32, _vp, _vp, _vp],
+    "r0h_session_balance_add_tuples": [_vp, _u32, _vp, _vp, _sz],
+    "r0h_session_balance_add_verifier_side": [_vp, _vp, _sz, _vp, _sz],
+    "r0h_session_balance_report": [_vp, _vp, _sz, _c.POINTER(_sz)],
+    "r0h_session_balance_message": [_vp, _c.POINTER(_vp)],
+    "r0h_session_balance_stats": [_vp, _vp],
+    "r0h_ctx_set_check_session": [_vp, _c.c_int],
     "r0h_circuit_free": [_vp],
     "r0h_witgen": [_vp, _vp, _u32, _u64, _vp, _vp, _vp],
     "r0h_witgen_public": [_vp, _vp, _u32, _u64, _vp, _vp, _vp],
@@ -232,6 +243,7 @@ _PLAIN = {
     "r0h_circuit_n_taps": ([_vp], _u32),
     "r0h_circuit_n_terms": ([_vp], _u32),
     "r0h_circuit_n_chain_fractions": ([_vp], _u32),
+    "r0h_session_balance_n_identities": ([_vp], _u32),
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(_PLAIN))
 
@@ -409,6 +421,107 @@ class Imbalance(ctypes.Structure):
     """r0h_imbalance: a class of tuples whose numerators sum to `net` (canonical, not 0) over `members` tuples, the lowest of them
     fraction `fraction` on row `first_row`"""
     _fields_ = [("fraction", _u32), ("first_row", _u32), ("net", _u32), ("members", _u32)]
+
+
+class SessionImbalance(ctypes.Structure):
+    """r0h_session_imbalance: a class of session tuples whose numerators sum to `net` (canonical, not 0) over `members` tuples, the
+    lowest of them fraction `fraction` (255: a tuple from outside) on row `first_row` of source `source`; values[:n_values] are the
+    class's canonical per-identity sums"""
+    _fields_ = [("source", _u32), ("fraction", _u32), ("first_row", _u32), ("net", _u32), ("members", _u32), ("n_values", _u32), ("values", _u32 * 8)]
+
+    def as_tuple(self):
+        return (self.source, self.first_row, self.fraction, self.net, self.members, tuple(self.values[:self.n_values]))
+
+
+SESSION_SOURCE_IMAGE, SESSION_SOURCE_JOURNAL = 0xFFFFFFFE, 0xFFFFFFFF
+
+
+class SessionBalance:
+    """The session balance (r0h_session_balance_*, include/r0hip.h): which classes of the tuples of the accumulators with a public
+    total -- the trace circuit's session sum -- do not cancel over the segments of a session and what the verifier adds.  `hal` = None:
+    a host handle (needs no GPU; segments are numpy words), else a device handle on that Hal's context (segments are Bufs).
+    report() -> [(source, first_row, fraction, net, members, values)] in (source, row, fraction) order of the lowest member."""
+
+    def __init__(self, blob, hal=None):
+        self.hal = hal
+        self._blob, pb = _u32arr(blob)
+        self.handle = _vp()
+        _check(lib().r0h_session_balance_new(hal.ctx if hal is not None else None, pb, self._blob.size, ctypes.byref(self.handle)))
+        self.identities = []
+        for k in range(lib().r0h_session_balance_n_identities(self.handle)):
+            kind, index = _u32(0), _u32(0)
+            _check(lib().r0h_session_balance_identity(self.handle, k, ctypes.byref(kind), ctypes.byref(index)))
+            self.identities.append((kind.value, index.value))
+
+    def add(self, source, po2, code, data, glob, circuit=None):
+        """one segment: host handle -- code / data / glob numpy words (Montgomery, column-major); device handle -- Bufs and the loaded
+        `circuit`.  code may be None where no form reads the CODE group, glob where none reads a public input."""
+        pg = None
+        if glob is not None and len(glob):
+            g, pg = _u32arr(glob)
+        if self.hal is None:
+            if isinstance(data, Buf):
+                raise R0HipError("r0h_session_balance_add_host: this handle was made without a context: its segments are host words, not device buffers")
+            d, pd = _u32arr(data)
+            pc = None
+            if code is not None:
+                cd, pc = _u32arr(code)
+            _check(lib().r0h_session_balance_add_host(self.handle, source, po2, pc, pd, pg))
+        else:
+            if not isinstance(data, Buf) or circuit is None:
+                raise R0HipError("r0h_session_balance_add: this handle was made with a context: its segments are device buffers and a loaded circuit")
+            _check(lib().r0h_session_balance_add(self.handle, source, circuit.handle, po2, code.handle if code is not None else None, data.handle, pg))
+
+    def add_tuples(self, source, numerators, values):
+        """tuples from outside: numerators[n], values[n][len(identities)], canonical words"""
+        num, pn = _u32arr(numerators)
+        val, pv = _u32arr(values)
+        if val.size != num.size * len(self.identities):
+            raise R0HipError("SessionBalance.add_tuples: %d values for %d tuples of %d identities" % (val.size, num.size, len(self.identities)))
+        _check(lib().r0h_session_balance_add_tuples(self.handle, source, pn, pv, num.size))
+
+    def add_verifier_side(self, elf=None, journal=None):
+        """the trace circuit's image words of `elf` and words of `journal` (bytes), numerator p - 1 each"""
+        _check(lib().r0h_session_balance_add_verifier_side(self.handle, elf, len(elf) if elf is not None else 0, journal, len(journal) if journal is not None else 0))
+
+    def report(self, capacity=None):
+        n = _sz(0)
+        cap = 0 if capacity is None else int(capacity)
+        out = (SessionImbalance * max(cap, 1))()
+        _check(lib().r0h_session_balance_report(self.handle, out, cap, ctypes.byref(n)))
+        if capacity is None and n.value:
+            cap = n.value
+            out = (SessionImbalance * cap)()
+            _check(lib().r0h_session_balance_report(self.handle, out, cap, ctypes.byref(n)))
+        found = [out[i].as_tuple() for i in range(min(n.value, cap))]
+        return found if capacity is None else (found, n.value)
+
+    def message(self):
+        """None when the session balances, else the sequencer's text for the lowest class"""
+        text = _vp()
+        _check(lib().r0h_session_balance_message(self.handle, ctypes.byref(text)))
+        if not text.value:
+            return None
+        msg = ctypes.cast(text, ctypes.c_char_p).value.decode()
+        lib().r0h_free_error(text)
+        return msg
+
+    def stats(self):
+        """(tuples added, the table's slots, how often it grew, classes held); a host handle has no table: slots 0"""
+        out = (_u64 * 4)()
+        _check(lib().r0h_session_balance_stats(self.handle, out))
+        return tuple(int(x) for x in out)
+
+    def free(self):
+        if self.handle:
+            _check(lib().r0h_session_balance_free(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def logup_check_balance_host(blob, po2, code, data, glob, capacity=None):
@@ -1482,6 +1595,12 @@ class Hal:
         """prove_segment, proof_begin and the sessions of this context check that every segment's log-derivative fractions cancel
         before its DATA group is committed and raise, naming the lowest fraction of a class that does not (r0h_ctx_set_check_balance)"""
         _check(lib().r0h_ctx_set_check_balance(self.ctx, 1 if on else 0))
+
+    def set_check_session(self, on=True):
+        """prove_elf and the two-phase sessions of this context check, before the session challenge is derived, that the session tuples
+        of all segments cancel against one another, the ELF's image and the journal, and raise naming the lowest class that does not
+        (r0h_ctx_set_check_session; single-rank sessions only)"""
+        _check(lib().r0h_ctx_set_check_session(self.ctx, 1 if on else 0))
 
     def set_check_witness(self, on=True):
         """prove_segment, proof_finish and the sessions of this context check every segment's witness before its ACCUM group is

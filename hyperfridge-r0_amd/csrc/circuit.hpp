@@ -2,6 +2,7 @@
 // evalcheck_emit.cpp, compiled, loaded and launched by circuit.hip, walked by prover.hip (sequencer) and verify.cpp.
 #pragma once
 #include <mutex>
+#include <unordered_map>
 
 #include "../../include/r0hip_circuit.h"
 #include "internal.hpp"
@@ -147,4 +148,39 @@ struct LookupList {
   uint32_t n_cols = 0;  // distinct DATA columns read
 };
 const char* logup_lookup_list(const r0h_circuit* c, const uint32_t* global, LookupList* out);
+
+// ---- the session balance (r0h_session_balance_*, include/r0hip.h): the balance check's definitions over the accumulators with a
+// public total, across the segments of a session and what the verifier adds.  The handle, its host half and the entry points that need
+// no device are in logup_host.cpp; the device's table and kernels in logup.hip behind the session_table_* functions.
+struct SessionClass {  // a class of a host handle
+  uint64_t sum = 0, first = ~0ull /* source << 32 | row << 8 | fraction of the lowest member */, members = 0;
+  uint32_t values[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // canonical per-identity sums, as the first member has them
+};
+struct SessionTable;  // the device's table (logup.hip)
+constexpr uint32_t SESSION_MAX_IDS = 8, SESSION_OUTSIDE_FRACTION = 255;
+constexpr size_t SESSION_MAX_LIST = (size_t)1 << 24;
+R0H_HD uint64_t session_first(uint32_t source, uint32_t row, uint32_t fraction) { return (uint64_t)source << 32 | (uint64_t)row << 8 | fraction; }
+}  // namespace r0h
+
+struct r0h_session_balance {
+  r0h_ctx* ctx = nullptr;             // nullptr: a host handle
+  r0h_circuit circuit;                // parsed from the blob it was made with (no device side)
+  std::vector<uint64_t> ids;          // the challenge identities (kind << 32 | index; 0 is "one") in order of first appearance
+  std::vector<uint32_t> weights;      // [2][ids.size()]: balance_weight of each
+  bool reads_global = false;          // some numerator or part reads an (early) public input
+  uint64_t tuples = 0, grows = 0;
+  std::unordered_map<uint64_t, r0h::SessionClass> classes;  // host handle: by balance_key
+  r0h::SessionTable* table = nullptr;                       // device handle
+};
+
+namespace r0h {
+// logup.hip.  `keys` are the tuples' balance_key, `numerators` / `values` ([n][n_ids]) canonical; `report` returns the `capacity`
+// lowest imbalanced classes in order and counts all of them
+const char* session_table_add_list(r0h_session_balance* sb, uint32_t source, const uint64_t* keys, const uint32_t* numerators, const uint32_t* values, size_t n);
+const char* session_table_report(r0h_session_balance* sb, r0h_session_imbalance* out, size_t capacity, size_t* n_out);
+const char* session_table_stats(r0h_session_balance* sb, uint64_t* slots_out, uint64_t* occupied_out);
+void session_table_free(r0h_session_balance* sb);
+// the sequencer's use of it (session.cpp under r0h_ctx_set_check_session): a phase of the context's profile by name (prover.hip)
+void profile_phase(r0h_ctx* ctx, const char* name);
+void profile_close(r0h_ctx* ctx);
 }  // namespace r0h

@@ -241,6 +241,7 @@ const char* ctx_helper(r0h_ctx* ctx, size_t k, r0h_ctx** out) {
   r0h_ctx* h = ctx->helpers[k];
   h->check_witness = ctx->check_witness;
   h->check_balance = ctx->check_balance;
+  h->check_session = ctx->check_session;
   if (memcmp(&h->p2_host, &ctx->p2_host, sizeof(P2Consts)) != 0) {  // r0h_poseidon2_set_consts on the owner since the helper was made
     h->p2_host = ctx->p2_host;
     R0H_TRY_HIP(hipSetDevice(h->device));

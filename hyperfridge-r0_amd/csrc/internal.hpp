@@ -115,6 +115,7 @@ struct r0h_ctx {
   std::vector<r0h_ctx*> helpers;  // further contexts of the same device, made on demand by r0h_prove_elf for its extra prover lanes; they go with this one
   bool check_witness = false;     // r0h_ctx_set_check_witness: the sequencer runs r0h_check_witness on every segment before it commits ACCUM
   bool check_balance = false;     // r0h_ctx_set_check_balance: the sequencer runs r0h_logup_check_balance on every segment before it commits DATA
+  bool check_session = false;     // r0h_ctx_set_check_session: r0h_session_finish checks the session balance of all segments before it derives the challenge
   uint64_t balance_stats[3] = {0, 0, 0};  // the last r0h_logup_check_balance: tuples, inserts that reached the global table, its slots
   bool ktime_on = false;
   std::map<std::string, r0h::KTimer> ktimers;

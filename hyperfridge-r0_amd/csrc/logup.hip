@@ -35,8 +35,10 @@ struct Tape {
   std::vector<uint32_t> acc_begin;          // word offset of every accumulator
 };
 
-// `n_accs`: the first n_accs accumulators alone (the balance check walks the chain links and nothing else)
-const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, Tape* t, uint32_t n_accs = 0xffffffffu) {
+// `n_accs`: the first n_accs accumulators alone (the balance check walks the chain links and nothing else); `first_acc`: those before
+// it are left out (the session balance walks the accumulators with a public total and nothing else)
+const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, Tape* t, uint32_t n_accs = 0xffffffffu,
+                       uint32_t first_acc = 0) {
   std::map<uint32_t, uint32_t> col_index;
   std::map<uint64_t, uint32_t> ch_index;
   t->ch.push_back(fp4_one());
@@ -66,8 +68,9 @@ const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, 
     }
     return nullptr;
   };
-  for (const LogupAcc& a : c->logup.accs) {
-    if (t->acc_begin.size() >= n_accs) break;
+  for (size_t j = first_acc; j < c->logup.accs.size(); j++) {
+    const LogupAcc& a = c->logup.accs[j];
+    if (first_acc + t->acc_begin.size() >= n_accs) break;
     t->acc_begin.push_back((uint32_t)t->words.size());
     for (const LogupFraction& f : a.fr) {
       t->words.push_back(f.table);
@@ -417,10 +420,11 @@ __global__ __launch_bounds__(BAL_THREADS) void balance_insert_kernel(BalanceSlot
 }
 
 // the classes whose numerators do not sum to zero: how many, and the lowest (row, fraction) among their first members
-__global__ __launch_bounds__(256) void balance_scan_kernel(const BalanceSlot* __restrict__ table, unsigned long long slots, unsigned long long* __restrict__ ctr) {
+template <class Slot>
+__global__ __launch_bounds__(256) void balance_scan_kernel(const Slot* __restrict__ table, unsigned long long slots, unsigned long long* __restrict__ ctr) {
   unsigned long long count = 0, best = 0;
   for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i < slots; i += gridDim.x * 256ull) {
-    const BalanceSlot s = table[i];
+    const Slot s = table[i];
     if (!s.key || s.sum % P == 0) continue;
     count++;
     best = s.first_inv > best ? s.first_inv : best;
@@ -431,13 +435,114 @@ __global__ __launch_bounds__(256) void balance_scan_kernel(const BalanceSlot* __
   }
 }
 // ... and the list of them: those whose first member is at or below `floor_inv` (inverted: at or above), `room` of them at the most
-__global__ __launch_bounds__(256) void balance_compact_kernel(BalanceSlot* __restrict__ list, unsigned long long room, const BalanceSlot* __restrict__ table, unsigned long long slots,
+template <class Slot>
+__global__ __launch_bounds__(256) void balance_compact_kernel(Slot* __restrict__ list, unsigned long long room, const Slot* __restrict__ table, unsigned long long slots,
                                                               unsigned long long floor_inv, unsigned long long* __restrict__ ctr) {
   for (unsigned long long i = blockIdx.x * 256ull + threadIdx.x; i < slots; i += gridDim.x * 256ull) {
-    const BalanceSlot s = table[i];
+    const Slot s = table[i];
     if (!s.key || s.sum % P == 0 || s.first_inv < floor_inv) continue;
     const unsigned long long at = atomicAdd(&ctr[BAL_CURSOR], 1ull);
     if (at < room) list[at] = s;
+  }
+}
+// ---- the session balance (r0h_session_balance_*, include/r0hip.h): the same definitions over the accumulators with a public total,
+// whose tuples cancel across the segments of a session and against the verifier's side.  The table belongs to the handle and lives
+// through its additions: a slot is one 64-byte line and also holds the class's per-identity sums, written by whoever claims it.
+struct SessionSlot {
+  unsigned long long key;        // 0: empty
+  unsigned long long sum;        // of the canonical numerators
+  unsigned long long first_inv;  // ~(source << 32 | row << 8 | fraction) of the lowest member
+  uint32_t members, pad;
+  uint32_t values[8];            // canonical per-identity sums (class-constant)
+};
+static_assert(sizeof(SessionSlot) == 64, "a slot is one 64-byte line");
+enum { SES_OCCUPIED = BAL_COUNTERS, SES_COUNTERS };
+constexpr uint32_t SES_THREADS = 256, SES_FIRST_BITS = 10;
+
+// `occupied`: where a claim is counted (nullptr: a rehash, which moves classes and makes none)
+__device__ __forceinline__ void session_insert(SessionSlot* __restrict__ table, uint32_t slot_bits, unsigned long long* __restrict__ ctr, unsigned long long* __restrict__ occupied,
+                                               unsigned long long key, unsigned long long sum, uint32_t members, unsigned long long first_inv, const uint32_t (&vals)[8]) {
+  const unsigned long long mask = (1ull << slot_bits) - 1;
+  unsigned long long i = (key * BAL_SPREAD) >> (64 - slot_bits);
+  for (unsigned long long probe = 0; probe <= mask; probe++) {  // bounded by the table's size (at a load of 1/2 or less: a handful)
+    SessionSlot* s = table + i;
+    const unsigned long long prev = atomicCAS(&s->key, 0ull, key);
+    if (prev == 0ull) {  // the claimer alone writes the class's values, two to a word; the scan reads them after the kernel boundary.  Atomic
+                         // exchanges, not plain stores: the line's other words are updated by device-scope atomics from every XCD
+      unsigned long long* v = (unsigned long long*)&s->values[0];
+#pragma unroll
+      for (uint32_t k = 0; k < 4; k++) atomicExch(&v[k], (unsigned long long)vals[2 * k + 1] << 32 | vals[2 * k]);
+      if (occupied) atomicAdd(occupied, 1ull);
+    }
+    if (prev == 0ull || prev == key) {
+      atomicAdd(&s->sum, sum);
+      atomicAdd(&s->members, members);
+      atomicMax(&s->first_inv, first_inv);
+      return;
+    }
+    i = (i + 1) & mask;
+  }
+  atomicOr(&ctr[BAL_ERR], 1ull);  // every slot is another class's: the caller reports "table full"
+}
+
+// One lane per row, straight into the global table: no LDS stage as in balance_insert_kernel, for there is nothing to merge -- a
+// session class has two or three members in the whole session (a producer, a consumer, perhaps the verifier's word), and almost every
+// row has no session tuple at all (the boundary rows and the COMMIT rows have).  So the parts are evaluated on rows with a numerator
+// only; the tape position after a fraction is stepped to from the tape alone and stays uniform across the wave.  No workgroup waits
+// for another.
+__global__ __launch_bounds__(SES_THREADS) void session_insert_kernel(SessionSlot* __restrict__ table, uint32_t slot_bits, unsigned long long* __restrict__ ctr,
+                                                                     const uint32_t* __restrict__ tape, const uint32_t* const* __restrict__ cols,
+                                                                     const uint32_t* __restrict__ weights /* [2][n_ids] */, const uint32_t* __restrict__ ch_to_id, uint32_t n_ids,
+                                                                     uint32_t n_acc, uint32_t first_fraction, uint32_t source, uint32_t po2) {
+  const uint32_t r = blockIdx.x * SES_THREADS + threadIdx.x;
+  if (r >= (1u << po2)) return;
+  uint32_t at = 0;
+  for (uint32_t f = 0; f < 4 * n_acc; f++) {
+    at++;  // table
+    const uint32_t num = eval_form(tape, at, cols, r);
+    const uint32_t n_parts = tape[at++];
+    uint32_t next = at;
+    for (uint32_t q = 0; q < n_parts; q++) next += 2 + 2 * tape[next + 1];
+    if (num) {
+      uint32_t a = at, vals[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (uint32_t q = 0; q < n_parts; q++) {
+        const uint32_t id = ch_to_id[tape[a++]];
+        const uint32_t v = eval_form(tape, a, cols, r);
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) vals[k] = id == k ? add(vals[k], v) : vals[k];  // (no array indexed by a run-time value: registers)
+      }
+      uint32_t h0 = 0, h1 = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < 8; k++) {
+        if (k < n_ids) {
+          h0 = add(h0, mul(weights[k], vals[k]));
+          h1 = add(h1, mul(weights[n_ids + k], vals[k]));
+        }
+        vals[k] = dec(vals[k]);
+      }
+      session_insert(table, slot_bits, ctr, &ctr[SES_OCCUPIED], balance_key(h0, h1), dec(num), 1u, ~session_first(source, r, first_fraction + f), vals);
+    }
+    at = next;
+  }
+}
+// tuples from outside (r0h_session_balance_add_tuples): the host has formed their keys with the same balance_key
+__global__ __launch_bounds__(SES_THREADS) void session_list_kernel(SessionSlot* __restrict__ table, uint32_t slot_bits, unsigned long long* __restrict__ ctr,
+                                                                   const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ numerators,
+                                                                   const uint32_t* __restrict__ values /* [n][n_ids] */, uint32_t n_ids, uint32_t source, uint32_t n) {
+  const uint32_t i = blockIdx.x * SES_THREADS + threadIdx.x;
+  if (i >= n || !numerators[i]) return;
+  uint32_t vals[8];
+#pragma unroll
+  for (uint32_t k = 0; k < 8; k++) vals[k] = k < n_ids ? values[(size_t)i * n_ids + k] : 0u;
+  session_insert(table, slot_bits, ctr, &ctr[SES_OCCUPIED], keys[i], numerators[i], 1u, ~session_first(source, i, SESSION_OUTSIDE_FRACTION), vals);
+}
+// growth: every occupied slot of the old table into the new one -- sum (reduced: only its residue counts), members, first member, values
+__global__ __launch_bounds__(SES_THREADS) void session_rehash_kernel(SessionSlot* __restrict__ to, uint32_t to_bits, unsigned long long* __restrict__ ctr,
+                                                                     const SessionSlot* __restrict__ from, unsigned long long from_slots) {
+  for (unsigned long long i = blockIdx.x * (unsigned long long)SES_THREADS + threadIdx.x; i < from_slots; i += gridDim.x * (unsigned long long)SES_THREADS) {
+    const SessionSlot s = from[i];
+    if (!s.key) continue;
+    session_insert(to, to_bits, ctr, nullptr, s.key, s.sum % P, s.members, s.first_inv, s.values);
   }
 }
 }  // namespace
@@ -611,7 +716,7 @@ const char* r0h_logup_check_balance(r0h_ctx* ctx, const r0h_circuit* c, uint32_t
   hipLaunchKernelGGL(balance_insert_kernel, dim3(grid), dim3(BAL_THREADS), 0, ctx->stream, d_table, slot_bits, ctr, d.words, d.cols, d_weights, n_ch, n_chain, po2);
   R0H_TRY(launch_ok("balance_insert_kernel"));
   const uint32_t scan_grid = (uint32_t)std::min<uint64_t>((slots + 255) / 256, 8ull * (uint32_t)std::max(ctx->n_cu, 1));
-  hipLaunchKernelGGL(balance_scan_kernel, dim3(scan_grid), dim3(256), 0, ctx->stream, d_table, (unsigned long long)slots, ctr);
+  hipLaunchKernelGGL(balance_scan_kernel<BalanceSlot>, dim3(scan_grid), dim3(256), 0, ctx->stream, d_table, (unsigned long long)slots, ctr);
   R0H_TRY(launch_ok("balance_scan_kernel"));
   R0H_TRY(r0h_buf_d2h(ctx, side.get(), 0, counters, sizeof counters));
   ctx->balance_stats[1] = counters[BAL_GLOBAL_INSERTS];
@@ -625,7 +730,7 @@ const char* r0h_logup_check_balance(r0h_ctx* ctx, const r0h_circuit* c, uint32_t
   const uint64_t room = lowest_only ? 1 : n_bad;
   DevBuf list;
   R0H_TRY(list.alloc(ctx, room * sizeof(BalanceSlot)));
-  hipLaunchKernelGGL(balance_compact_kernel, dim3(scan_grid), dim3(256), 0, ctx->stream, (BalanceSlot*)list->ptr, (unsigned long long)room, d_table, (unsigned long long)slots,
+  hipLaunchKernelGGL(balance_compact_kernel<BalanceSlot>, dim3(scan_grid), dim3(256), 0, ctx->stream, (BalanceSlot*)list->ptr, (unsigned long long)room, d_table, (unsigned long long)slots,
                      lowest_only ? counters[BAL_FIRST_INV] : 0ull, ctr);
   R0H_TRY(launch_ok("balance_compact_kernel"));
   std::vector<BalanceSlot> found(room);
@@ -685,6 +790,187 @@ const char* r0h::logup_totals_keep(r0h_ctx* ctx, const r0h_circuit* c, uint32_t 
   std::vector<uint32_t> totals(4 * (size_t)(n_acc - n_chain));
   R0H_TRY(own_accumulators(ctx, c, po2, t, d, nullptr, totals.data(), keep));
   for (uint32_t j = n_chain; j < n_acc; j++) memcpy(global_io + c->logup.accs[j].final_global, totals.data() + 4 * (size_t)(j - n_chain), 16);
+  return nullptr;
+  R0H_GUARD_END
+}
+
+// ---- the session balance's device half (the handle and everything that needs no device: logup_host.cpp)
+struct r0h::SessionTable {
+  DevBuf side;   // SES_COUNTERS counters, then the two weight rows
+  DevBuf table;  // 2^slot_bits slots
+  uint32_t slot_bits = SES_FIRST_BITS;
+  unsigned long long* ctr() const { return (unsigned long long*)side->ptr; }
+  const uint32_t* weights() const { return (const uint32_t*)(ctr() + SES_COUNTERS); }
+  SessionSlot* slots() const { return (SessionSlot*)table->ptr; }
+};
+
+namespace {
+const char* session_table_ensure(r0h_session_balance* sb) {
+  if (sb->table) return nullptr;
+  r0h_ctx* ctx = sb->ctx;
+  std::unique_ptr<SessionTable> t(new SessionTable());
+  R0H_TRY(t->side.alloc(ctx, SES_COUNTERS * 8 + sb->weights.size() * 4 + 16));
+  R0H_TRY_HIP(hipMemsetAsync(t->side->ptr, 0, SES_COUNTERS * 8, ctx->stream));
+  if (!sb->weights.empty()) R0H_TRY(stage_h2d(ctx, (void*)t->weights(), sb->weights.data(), sb->weights.size() * 4));
+  R0H_TRY(t->table.alloc(ctx, sizeof(SessionSlot) << t->slot_bits));
+  R0H_TRY_HIP(hipMemsetAsync(t->table->ptr, 0, sizeof(SessionSlot) << t->slot_bits, ctx->stream));
+  if (!ctx->n_cu) R0H_TRY_HIP(hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  sb->table = t.release();
+  return nullptr;
+}
+// slots >= 2 x the tuples there will be: the next power of two that holds them, every occupied slot re-inserted, the old table released
+const char* session_table_grow(r0h_session_balance* sb, uint64_t tuples) {
+  SessionTable* t = sb->table;
+  r0h_ctx* ctx = sb->ctx;
+  uint32_t bits = t->slot_bits;
+  while ((1ull << bits) < 2 * tuples) bits++;
+  if (bits == t->slot_bits) return nullptr;
+  DevBuf bigger;
+  R0H_TRY(bigger.alloc(ctx, sizeof(SessionSlot) << bits));  // (an allocation the device refuses is this call's error)
+  R0H_TRY_HIP(hipMemsetAsync(bigger->ptr, 0, sizeof(SessionSlot) << bits, ctx->stream));
+  const unsigned long long from_slots = 1ull << t->slot_bits;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((from_slots + SES_THREADS - 1) / SES_THREADS, 8ull * (uint32_t)std::max(ctx->n_cu, 1));
+  hipLaunchKernelGGL(session_rehash_kernel, dim3(grid), dim3(SES_THREADS), 0, ctx->stream, (SessionSlot*)bigger->ptr, bits, t->ctr(), t->slots(), from_slots);
+  R0H_TRY(launch_ok("session_rehash_kernel"));
+  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the old table goes back to the pool
+  t->table = std::move(bigger);
+  t->slot_bits = bits;
+  sb->grows++;
+  return nullptr;
+}
+// after the inserts of one addition: they are complete, and none ran out of slots
+const char* session_table_settle(r0h_session_balance* sb) {
+  unsigned long long err = 0;
+  R0H_TRY(r0h_buf_d2h(sb->ctx, sb->table->side.get(), BAL_ERR * 8, &err, 8));
+  R0H_REQUIRE(!err, "r0h_session_balance: table full");
+  return nullptr;
+}
+}  // namespace
+
+void r0h::session_table_free(r0h_session_balance* sb) {
+  delete sb->table;
+  sb->table = nullptr;
+}
+
+const char* r0h::session_table_stats(r0h_session_balance* sb, uint64_t* slots_out, uint64_t* occupied_out) {
+  KScope ks(sb->ctx, "session_balance", 0);
+  R0H_TRY(session_table_ensure(sb));
+  unsigned long long occupied = 0;
+  R0H_TRY(r0h_buf_d2h(sb->ctx, sb->table->side.get(), SES_OCCUPIED * 8, &occupied, 8));
+  *slots_out = 1ull << sb->table->slot_bits;
+  *occupied_out = occupied;
+  return nullptr;
+}
+
+const char* r0h::session_table_add_list(r0h_session_balance* sb, uint32_t source, const uint64_t* keys, const uint32_t* numerators, const uint32_t* values, size_t n) {
+  r0h_ctx* ctx = sb->ctx;
+  const uint32_t n_ids = (uint32_t)sb->ids.size();
+  KScope ks(ctx, "session_balance", (double)n * (12 + 4 * n_ids));
+  R0H_TRY(session_table_ensure(sb));
+  uint64_t tuples = 0;
+  for (size_t i = 0; i < n; i++) tuples += numerators[i] != 0;
+  R0H_TRY(session_table_grow(sb, sb->tuples + tuples));
+  const size_t k_bytes = n * 8, n_bytes = (n * 4 + 15) & ~(size_t)15, v_bytes = n * n_ids * 4;
+  DevBuf list;  // keys, numerators, values
+  R0H_TRY(list.alloc(ctx, k_bytes + n_bytes + v_bytes));
+  char* base = (char*)list->ptr;
+  R0H_TRY(r0h_buf_h2d(ctx, list.get(), 0, keys, k_bytes));
+  R0H_TRY(r0h_buf_h2d(ctx, list.get(), k_bytes, numerators, n * 4));
+  R0H_TRY(r0h_buf_h2d(ctx, list.get(), k_bytes + n_bytes, values, v_bytes));
+  SessionTable* t = sb->table;
+  hipLaunchKernelGGL(session_list_kernel, dim3((uint32_t)((n + SES_THREADS - 1) / SES_THREADS)), dim3(SES_THREADS), 0, ctx->stream, t->slots(), t->slot_bits, t->ctr(),
+                     (const unsigned long long*)base, (const uint32_t*)(base + k_bytes), (const uint32_t*)(base + k_bytes + n_bytes), n_ids, source, (uint32_t)n);
+  R0H_TRY(launch_ok("session_list_kernel"));
+  return session_table_settle(sb);  // (synchronises: the list goes back to the pool)
+}
+
+const char* r0h::session_table_report(r0h_session_balance* sb, r0h_session_imbalance* out, size_t capacity, size_t* n_out) {
+  r0h_ctx* ctx = sb->ctx;
+  *n_out = 0;
+  if (!sb->table) return nullptr;  // nothing was added
+  SessionTable* t = sb->table;
+  const uint64_t slots = 1ull << t->slot_bits;
+  KScope ks(ctx, "session_balance", (double)slots * sizeof(SessionSlot));
+  unsigned long long* const ctr = t->ctr();
+  R0H_TRY_HIP(hipMemsetAsync(ctr + BAL_IMBALANCED, 0, 16, ctx->stream));  // ... and BAL_FIRST_INV: a report starts from nothing
+  R0H_TRY_HIP(hipMemsetAsync(ctr + BAL_CURSOR, 0, 8, ctx->stream));
+  static_assert(BAL_FIRST_INV == BAL_IMBALANCED + 1, "the two counters of a scan are cleared together");
+  // scan and compaction as the chain's check has them; the host orders what comes back
+  const uint32_t scan_grid = (uint32_t)std::min<uint64_t>((slots + 255) / 256, 8ull * (uint32_t)std::max(ctx->n_cu, 1));
+  hipLaunchKernelGGL(balance_scan_kernel<SessionSlot>, dim3(scan_grid), dim3(256), 0, ctx->stream, t->slots(), (unsigned long long)slots, ctr);
+  R0H_TRY(launch_ok("balance_scan_kernel"));
+  unsigned long long counters[BAL_COUNTERS];
+  R0H_TRY(r0h_buf_d2h(ctx, t->side.get(), 0, counters, sizeof counters));
+  R0H_REQUIRE(!counters[BAL_ERR], "r0h_session_balance: table full");
+  const uint64_t n_bad = counters[BAL_IMBALANCED];
+  *n_out = (size_t)n_bad;
+  if (!n_bad || !capacity) return nullptr;
+  const bool lowest_only = capacity == 1 && n_bad > 1;
+  const uint64_t room = lowest_only ? 1 : n_bad;
+  DevBuf list;
+  R0H_TRY(list.alloc(ctx, room * sizeof(SessionSlot)));
+  hipLaunchKernelGGL(balance_compact_kernel<SessionSlot>, dim3(scan_grid), dim3(256), 0, ctx->stream, (SessionSlot*)list->ptr, (unsigned long long)room, t->slots(), (unsigned long long)slots,
+                     lowest_only ? counters[BAL_FIRST_INV] : 0ull, ctr);
+  R0H_TRY(launch_ok("balance_compact_kernel"));
+  std::vector<SessionSlot> found(room);
+  R0H_TRY(r0h_buf_d2h(ctx, list.get(), 0, found.data(), room * sizeof(SessionSlot)));
+  std::sort(found.begin(), found.end(), [](const SessionSlot& a, const SessionSlot& b) { return a.first_inv > b.first_inv; });
+  for (size_t k = 0; k < found.size() && k < capacity; k++) {
+    const uint64_t first = ~found[k].first_inv;
+    out[k] = r0h_session_imbalance{(uint32_t)(first >> 32), (uint32_t)(first & 255u), (uint32_t)(first >> 8) & 0xffffffu, (uint32_t)(found[k].sum % P), found[k].members, (uint32_t)sb->ids.size(),
+                                   {0, 0, 0, 0, 0, 0, 0, 0}};
+    memcpy(out[k].values, found[k].values, sizeof found[k].values);
+  }
+  return nullptr;
+}
+
+extern "C" const char* r0h_session_balance_add(r0h_session_balance* sb, uint32_t source, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data,
+                                               const uint32_t* global_host) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(sb && c && data, "r0h_session_balance_add: NULL argument");
+  R0H_REQUIRE(sb->ctx, "r0h_session_balance_add: this handle was made without a context: its segments are added with r0h_session_balance_add_host");
+  R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_session_balance_add: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
+  R0H_REQUIRE(c->blob == sb->circuit.blob, "r0h_session_balance_add: the circuit is not the one the handle was made with");
+  r0h_ctx* ctx = sb->ctx;
+  R0H_REQUIRE(data->ctx->device == ctx->device && (!code || code->ctx->device == ctx->device), "r0h_session_balance_add: the buffers are on another device than the handle's context");
+  const uint32_t n = 1u << po2, n_chain = c->logup.n_chain, n_own = (uint32_t)c->logup.accs.size() - n_chain, n_ids = (uint32_t)sb->ids.size();
+  if (!n_own) return nullptr;
+  R0H_REQUIRE(((size_t)c->group_size[R0H_GROUP_DATA] << po2) * 4 <= data->bytes && (!code || ((size_t)c->group_size[R0H_GROUP_CODE] << po2) * 4 <= code->bytes),
+              "r0h_session_balance_add: buffers too small for 2^%u rows", po2);
+  R0H_REQUIRE(global_host || !sb->reads_global, "r0h_session_balance_add: a form reads a public input and none were given");
+  for (uint32_t i = 0; i + c->n_late < c->n_global; i++) R0H_REQUIRE(!global_host || global_host[i] < P, "r0h_session_balance_add: global[%u] not canonical", i);
+  std::vector<uint32_t> no_global(c->n_global + 4, 0), dummy_mix(c->n_mix, 0);  // the challenges' values are not read, their identities are
+  Tape t;
+  R0H_TRY(build_tape(c, po2, code, data, global_host ? global_host : no_global.data(), dummy_mix.data(), &t, 0xffffffffu, n_chain));
+  DeviceTape d;
+  R0H_TRY(upload_tape(ctx, t, &d));
+  std::vector<uint32_t> ch_to_id(t.ch_id.size() + 4, 0xffu);  // the tape's challenge numbers -> the handle's identities ("one" is on every tape, used or not)
+  for (size_t k = 0; k < t.ch_id.size(); k++) {
+    const auto it = std::find(sb->ids.begin(), sb->ids.end(), t.ch_id[k]);
+    if (it != sb->ids.end()) ch_to_id[k] = (uint32_t)(it - sb->ids.begin());
+  }
+  KScope ks(ctx, "session_balance", (double)t.cols.size() * n * 4);
+  R0H_TRY(session_table_ensure(sb));
+  SessionTable* tb = sb->table;
+  DevBuf map;
+  R0H_TRY(map.alloc(ctx, ch_to_id.size() * 4));
+  R0H_TRY(stage_h2d(ctx, map->ptr, ch_to_id.data(), ch_to_id.size() * 4));
+  // the tuples to come: the numerators alone (the chain's counting kernel on this tape)
+  R0H_TRY_HIP(hipMemsetAsync(tb->ctr() + BAL_TUPLES, 0, 8, ctx->stream));
+  const uint32_t count_grid = std::min<uint32_t>((uint32_t)std::max(ctx->n_cu, 1), (n + BAL_THREADS - 1) / BAL_THREADS);
+  hipLaunchKernelGGL(balance_count_kernel, dim3(count_grid), dim3(BAL_THREADS), 0, ctx->stream, tb->ctr(), d.words, d.cols, n_own, po2);
+  R0H_TRY(launch_ok("balance_count_kernel"));
+  unsigned long long tuples = 0;
+  R0H_TRY(r0h_buf_d2h(ctx, tb->side.get(), BAL_TUPLES * 8, &tuples, 8));
+  R0H_REQUIRE(sb->tuples + tuples <= 0xffffffffull, "r0h_session_balance_add: more than 2^32 - 1 tuples in one handle");
+  if (tuples) {
+    R0H_TRY(session_table_grow(sb, sb->tuples + tuples));
+    hipLaunchKernelGGL(session_insert_kernel, dim3((n + SES_THREADS - 1) / SES_THREADS), dim3(SES_THREADS), 0, ctx->stream, tb->slots(), tb->slot_bits, tb->ctr(), d.words, d.cols, tb->weights(),
+                       (const uint32_t*)map->ptr, n_ids, n_own, 4 * n_chain, source, po2);
+    R0H_TRY(launch_ok("session_insert_kernel"));
+  }
+  R0H_TRY(session_table_settle(sb));  // (synchronises: the tape goes back to the pool, the caller's buffers are its own again)
+  sb->tuples += tuples;
   return nullptr;
   R0H_GUARD_END
 }

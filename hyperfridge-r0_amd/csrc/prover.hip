@@ -78,6 +78,20 @@ static void phase(r0h_ctx* ctx, const char* name) {
   p.names.push_back(name);
 }
 
+// the elapsed times of the phases recorded so far, the last of them "end"
+static const char* profile_times(r0h_ctx* ctx) {
+  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  Profile& pf = ctx->prof;
+  pf.ms.assign(pf.names.size(), 0.f);
+  for (size_t i = 0; i + 1 < pf.names.size(); i++) hipEventElapsedTime(&pf.ms[i], pf.events[i], pf.events[i + 1]);
+  return nullptr;
+}
+void profile_phase(r0h_ctx* ctx, const char* name) { phase(ctx, name); }
+void profile_close(r0h_ctx* ctx) {
+  phase(ctx, "end");
+  if (const char* err = profile_times(ctx)) r0h_free_error(err);
+}
+
 static const char* tree_build(r0h_ctx* ctx, Scope& sc, Tree& t, const r0h_buf* matrix) {
   t.matrix = matrix;
   R0H_TRY(sc.alloc(ctx, t.mp.rows * 2 * 32, &t.nodes));
@@ -485,10 +499,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
       }
   }
   phase(ctx, "end");
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
-  Profile& pf = ctx->prof;
-  pf.ms.assign(pf.names.size(), 0.f);
-  for (size_t i = 0; i + 1 < pf.names.size(); i++) hipEventElapsedTime(&pf.ms[i], pf.events[i], pf.events[i + 1]);
+  R0H_TRY(profile_times(ctx));
   seal.swap(io.proof);
   return nullptr;
 }

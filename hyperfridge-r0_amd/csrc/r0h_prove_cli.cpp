@@ -15,6 +15,10 @@
 // balance ends the run with the fraction, the net of its class, its tuples and its first row -- and the fraction's name, from
 // --fraction-names or <circuit>.fractions.txt beside the blob (tools/gen_circuit.py --fraction-names; the build writes them for the trace
 // and image circuits).  A circuit without a LOGUP section has nothing to check.
+// --check-session 1 (--elf mode; [--fraction-names file.txt]) turns r0h_ctx_set_check_session on: before the session challenge is derived,
+// the session tuples of all segments must cancel against one another, the ELF's image words and the journal's words
+// (r0h_session_balance_*); a session that does not balance ends the run with the lowest class -- fraction, net, tuples, the segment and
+// row of its first member, the class's values -- and the fraction's name from the same file (its lines go on past the chain's fractions).
 // With --receipt-out / --receipt-dir every segment is proved for a claim (risc0-zkvm `ReceiptClaim`): the session's system states
 // are synthetic names (there is no executor here), segment k runs from state k to state k+1, all but the last end in SystemSplit,
 // the last halts with the journal's output; the claim's eight naming words are planted as the segment's public inputs.  The image
@@ -52,8 +56,9 @@ static std::vector<std::string> fraction_names;  // --check-balance: likewise fo
 static void die(const char* what, const char* err) {
   fprintf(stderr, "r0h_prove: %s: %s\n", what, err);
   const char* fr = strstr(err, ": fraction ");
+  if (!fr) fr = strstr(err, ": session fraction ");  // --check-session
   if (fr && strstr(fr, " does not balance: net ")) {
-    const unsigned long f = strtoul(fr + 11, nullptr, 10);
+    const unsigned long f = strtoul(strstr(fr, "fraction ") + 9, nullptr, 10);
     if (f < fraction_names.size()) fprintf(stderr, "r0h_prove: fraction %lu is \"%s\"\n", f, fraction_names[f].c_str());
   }
   const char* at = strstr(err, "the witness violates");
@@ -77,7 +82,10 @@ int main(int argc, char** argv) {
            "       --check-witness 1 [--check-code-object file.hsaco] [--term-names file.txt]: check every segment's witness on the device before its ACCUM group is committed; "
            "a violated segment ends the run with the constraint term, its name, how many rows violate it and the first of them\n"
            "       --check-balance 1 [--fraction-names file.txt]: check that the log-derivative fractions of every segment's witness cancel before its DATA group is committed; "
-           "a segment that does not balance ends the run with the fraction, its name, the net of its class and its first row\n%s\n", r0h_version());
+           "a segment that does not balance ends the run with the fraction, its name, the net of its class and its first row\n"
+           "       --check-session 1 [--fraction-names file.txt]: with --elf, check before the session challenge is derived that the session tuples of all segments cancel against "
+           "one another, the program image and the journal; a session that does not balance ends the run with the fraction, its name, the net of its class, the segment and row of its first tuple "
+           "and the class's values (single-rank sessions; a diagnostic, not a verifier)\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   std::string blob_path = argv[1], co_path, seal_out, receipt_out, receipt_dir, journal_text, elf_path, input_path;
@@ -85,7 +93,7 @@ int main(int argc, char** argv) {
   std::map<std::string, std::string> camt;  // --camt53-response and what goes with it
   std::string receipt_prefix;               // --receipt-prefix P: the reference's file name, P-Receipt-<image id>-latest.json (host/src/main.rs:312-316)
   std::string image_circuit_path, image_co_path, check_co_path, term_names_path, fraction_names_path;
-  unsigned check_witness = 0, check_balance = 0;
+  unsigned check_witness = 0, check_balance = 0, check_session = 0;
   unsigned po2 = 16, segments = 1, device = 0, contexts = 1, verify = 0, receipts = 1;
   unsigned long long seed = 1;
   for (int i = 2; i + 1 < argc; i += 2) {
@@ -102,6 +110,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--check-code-object")) check_co_path = argv[i + 1];
     else if (!strcmp(argv[i], "--term-names")) term_names_path = argv[i + 1];
     else if (!strcmp(argv[i], "--check-balance")) check_balance = (unsigned)atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--check-session")) check_session = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--fraction-names")) fraction_names_path = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
@@ -145,7 +154,7 @@ int main(int argc, char** argv) {
     }
     if (g) fclose(g);
   }
-  if (check_balance) {
+  if (check_balance || check_session) {
     std::string names = fraction_names_path;
     if (names.empty() && blob_path.size() > 4 && blob_path.compare(blob_path.size() - 4, 4, ".r0c") == 0) names = blob_path.substr(0, blob_path.size() - 4) + ".fractions.txt";
     FILE* g = names.empty() ? nullptr : fopen(names.c_str(), "rb");
@@ -160,6 +169,7 @@ int main(int argc, char** argv) {
   // --check-witness: the context's switch, and the checker's module now (from its code object, else compiled in-process) rather than inside the first proof
   auto arm_checker = [&](r0h_ctx* ctx, r0h_circuit* circ) {
     if (check_balance) CHECK(r0h_ctx_set_check_balance(ctx, 1));
+    if (check_session) CHECK(r0h_ctx_set_check_session(ctx, 1));
     if (!check_witness) return;
     CHECK(r0h_ctx_set_check_witness(ctx, 1));
     CHECK(r0h_circuit_load_check(circ, check_co_path.empty() ? nullptr : check_co_path.c_str()));

@@ -360,7 +360,8 @@ struct r0h_session {
   std::vector<Pending> pending;  // this rank's segments, by index
   CodeCommits commits;
   std::vector<uint8_t> journal;
-  std::vector<uint8_t> elf;  // kept for the image proof (r0h_ctx_set_image_circuit)
+  std::vector<uint8_t> elf;  // kept for the image proof (r0h_ctx_set_image_circuit) and for the session check's verifier side
+  bool check_session = false;  // r0h_ctx_set_check_session was on when the session began
   uint8_t image_id[32] = {0};
   uint64_t cycles = 0;
   r0h_session_stats stats = {0, 0, 0, 0, 0, 0, 0};
@@ -507,7 +508,10 @@ const char* r0h_session_begin(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t*
   ses->part = part;
   ses->parts = parts;
   ses->t_begin = Clock::now();
-  if (trace_mode && ctx->image_circuit && part == 0) ses->elf.assign(elf, elf + elf_len);
+  R0H_REQUIRE(!(trace_mode && ctx->check_session) || parts == 1,
+              "r0h_session_begin: r0h_ctx_set_check_session is on and this is part %u of %u: a rank sees its own segments only, the session check covers single-rank sessions", part, parts);
+  ses->check_session = trace_mode && ctx->check_session;
+  if (trace_mode && ((ctx->image_circuit && part == 0) || ses->check_session)) ses->elf.assign(elf, elf + elf_len);
   ses->resident_limit = ctx->session_resident_limit;
   if (!ses->resident_limit) {
     size_t free_b = 0, total_b = 0;
@@ -573,6 +577,34 @@ const char* r0h_session_records(const r0h_session* s, uint32_t* indices_out, uin
 }
 
 namespace {
+struct SessionBalanceFree { void operator()(r0h_session_balance* sb) const { r0h_session_balance_free(sb); } };
+// r0h_ctx_set_check_session: between the phases, before the challenge exists -- every segment's session tuples (their DATA witnesses
+// are still resident, lean segments included) and the verifier's side from the ELF and the run's journal must cancel class by class.
+// A session that does not balance is this call's error, by the name of its lowest class, and its proofs are aborted.
+const char* check_session(r0h_session* s) {
+  r0h_ctx* ctx = s->ctx;
+  profile_phase(ctx, "check_session");
+  r0h_session_balance* made = nullptr;
+  R0H_TRY(r0h_session_balance_new(ctx, s->c->blob.data(), s->c->blob.size(), &made));
+  std::unique_ptr<r0h_session_balance, SessionBalanceFree> sb(made);
+  bool own_proof = false;  // a proof of the caller's context is still to be finished: it closes the profile
+  for (Pending& p : s->pending) {  // in index order
+    if (p.lctx != ctx) R0H_TRY(r0h_sync(p.lctx));
+    else own_proof = own_proof || !p.done;
+    const r0h_buf* code_cols = nullptr;
+    R0H_TRY(r0h_code_commit_columns(p.cc, &code_cols));
+    R0H_TRY(r0h_session_balance_add(sb.get(), (uint32_t)p.index, s->c, p.po2, code_cols, p.data.get(), p.global.data()));
+  }
+  R0H_TRY(r0h_session_balance_add_verifier_side(sb.get(), s->elf.data(), s->elf.size(), s->journal.data(), s->journal.size()));
+  char* text = nullptr;
+  R0H_TRY(r0h_session_balance_message(sb.get(), &text));
+  if (!own_proof || text) profile_close(ctx);
+  if (!text) return nullptr;
+  for (Pending& p : s->pending) p.proof.reset();  // aborted
+  const char* err = make_error("r0h_prove_elf: %s", text);
+  r0h_free_error(text);
+  return err;
+}
 // Phase 2 of a segment: the challenge and the segment's own sum under it become its late public inputs, and the proof is finished.
 // The DATA block goes back to the pool whether or not the proof succeeds.
 const char* finish_segment(r0h_session* s, Pending& p, const uint32_t challenge[16], std::vector<uint32_t>& mix, std::vector<uint32_t>& seal, size_t* words) {
@@ -604,6 +636,7 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
     for (const Pending& p : s->pending)
       R0H_REQUIRE(!memcmp(all_records + p.index * RECORD_WORDS, p.global.data(), n_early * 4) && !memcmp(all_records + p.index * RECORD_WORDS + n_early, p.root, 32),
                   "r0h_session_finish: record %zu is not the one this rank committed", p.index);
+    if (s->check_session) R0H_TRY(check_session(s));
     uint32_t challenge[16];
     session_challenge(all_records, n_records, challenge);
     std::atomic<bool> failed(false);  // a lane's error: the others leave before their next segment

@@ -190,7 +190,7 @@ const char* r0h_ctx_set_check_witness(r0h_ctx* ctx, int on);
  * whose reads do not return what was written, whose boundary rows or multiplicities are off, still has running sums: the checker
  * above sees one chain-link term violated on the wrap row and nothing else.  This check names the fractions instead.
  * Only the links of the chain are looked at (accumulators whose `final` is 0xffffffff); an accumulator with a public total -- the
- * trace circuit's session sum -- balances across segments and the verifier only, and is left out.  Fraction f = 4 * accumulator + slot,
+ * trace circuit's session sum -- balances across segments and the verifier only, and is left out (r0h_session_balance_*, below, is its check).  Fraction f = 4 * accumulator + slot,
  * 0 <= f < r0h_circuit_n_chain_fractions.  Fraction f contributes a TUPLE on row r iff its numerator n(f, r) is not zero.  The tuple's
  * CLASS is its denominator as a polynomial in the challenges: per challenge identity -- "one", (1, index), (2, index) -- the sum of the
  * values of the parts under it, identities whose sum is zero dropped; two tuples are of one class iff these vectors are equal (the
@@ -223,6 +223,67 @@ const char* r0h_logup_check_balance_stats(const r0h_ctx* ctx, uint64_t stats_out
  * balance: net N over M tuples, first at row R; K classes in all".  Independent of r0h_ctx_set_check_witness.  Off (the default):
  * nothing is checked, seals and timing are unchanged. */
 const char* r0h_ctx_set_check_balance(r0h_ctx* ctx, int on);
+/* ---- the session balance: the same check for the accumulators the one above leaves out, those whose `final` is a public input (the
+ * trace circuit's session sum, fractions 36..39: session:consume, session:produce, session:image, session:journal).  Their tuples
+ * cancel across the segments of a session and against what the verifier adds (the program image's words, the journal's words), and
+ * when they do not, r0h_receipt_verify_elf says verdict 14 and nothing else.  A tuple's class does not depend on the challenge's
+ * value, so a whole session can be checked before the challenge exists.
+ * The definitions are r0h_logup_check_balance's: fractions keep their global numbering f = 4 * accumulator + slot; fraction f on row r
+ * of a segment is a tuple iff its numerator there is not zero; its class is, per challenge identity, the sum of the parts' values
+ * under that identity.  The identities are those of the public-total accumulators in order of first appearance in the blob
+ * (r0h_session_balance_identity: kind 0 "one", 1 a mix element, 2 four public inputs; at most 8, more is refused by _new, as are more
+ * than 255 fractions in all).  A numerator or part that reads the VALUE of a late public input is refused by _new: late inputs do
+ * not exist yet when this runs (a late input as a challenge's identity is what the session sum is made of).
+ * A handle collects tuples: r0h_session_balance_add takes a segment's CODE / DATA witness on the device (handle made with a context;
+ * the work goes on that context's stream, the buffers may belong to any context of the same device and must be complete),
+ * r0h_session_balance_add_host the same as host words (handle made with ctx = NULL; Montgomery form, column-major), and
+ * r0h_session_balance_add_tuples a list from outside -- the verifier's side: numerators[n] and values[n][n_identities], canonical words
+ * (anything >= p is refused), n <= 2^24 a call.  r0h_session_balance_add_verifier_side is that list for the trace circuit: numerator
+ * p - 1 for every image word of the ELF (source R0H_SESSION_SOURCE_IMAGE) and every journal word (R0H_SESSION_SOURCE_JOURNAL) under
+ * R0H_SESSION_TAG_IMAGE / R0H_SESSION_TAG_JOURNAL, the fingerprints r0h_receipt_verify_elf forms; either of elf / journal may be
+ * NULL to leave that side out.  Every tuple has a key (source, row, fraction): `source` is the caller's u32 per addition (the
+ * sequencer: the segment's index), a tuple from outside has its index in its list as row and fraction 255.  The session BALANCES iff
+ * every class's numerators sum to 0 mod p over everything added.  po2 in [4, R0H_MAX_PO2]; at most 2^32 - 1 tuples a handle.
+ * r0h_session_balance_report: one entry per class that does not balance, in (source, row, fraction) order of the lowest member
+ * (source, first_row, fraction); `net` in [1, p); `members` saturating at 2^32 - 1; values[0 .. n_values) the class's canonical
+ * per-identity sums (the trace circuit: 1, -address, -lo, -hi, -tag or -segment).  *n_out counts all of them, `out` holds the
+ * `capacity` lowest.  It may be called between additions and again after more.  Every field is a sum, a count, a minimum or
+ * class-constant: the answer depends neither on scheduling nor on the order of the additions.  A circuit without public-total
+ * accumulators gives *n_out = 0.  r0h_session_balance_message: NULL text when the session balances, else (caller frees with
+ * r0h_free_error) "session fraction F does not balance: net N over M tuples, first in source S at row R, class (v0, v1, ...); K
+ * classes in all" for the lowest entry.  r0h_session_balance_stats: tuples added, the table's slots, how often it grew, classes held.
+ * Classes are told apart by the 62-bit fingerprint of the balance check above (same weights); two that collide are reported as one.
+ * The weights are public and fixed: a diagnostic for honest mistakes, not a verifier -- r0h_receipt_verify_elf stays the judge.
+ * The device keeps an open-addressed table of 64-byte slots that belongs to the handle, starts at 1,024 slots and is rehashed into
+ * the next power of two whenever an addition would take the load above 1/2; "r0h_session_balance: table full" if a probe sequence
+ * runs out all the same.  One handle is used from one thread at a time. */
+#define R0H_SESSION_SOURCE_IMAGE 0xfffffffeu
+#define R0H_SESSION_SOURCE_JOURNAL 0xffffffffu
+typedef struct { uint32_t source, fraction, first_row, net, members, n_values, values[8]; } r0h_session_imbalance;
+typedef struct r0h_session_balance r0h_session_balance;
+const char* r0h_session_balance_new(r0h_ctx* ctx /* NULL: a host handle */, const uint32_t* blob, size_t blob_words,
+                                    r0h_session_balance** sb_out);
+const char* r0h_session_balance_free(r0h_session_balance* sb);
+uint32_t r0h_session_balance_n_identities(const r0h_session_balance* sb);
+const char* r0h_session_balance_identity(const r0h_session_balance* sb, uint32_t k, uint32_t* kind_out, uint32_t* index_out);
+const char* r0h_session_balance_add(r0h_session_balance* sb, uint32_t source, const r0h_circuit* c, uint32_t po2, const r0h_buf* code,
+                                    const r0h_buf* data, const uint32_t* global_host);
+const char* r0h_session_balance_add_host(r0h_session_balance* sb, uint32_t source, uint32_t po2, const uint32_t* code,
+                                         const uint32_t* data, const uint32_t* global);
+const char* r0h_session_balance_add_tuples(r0h_session_balance* sb, uint32_t source, const uint32_t* numerators, const uint32_t* values,
+                                           size_t n);
+const char* r0h_session_balance_add_verifier_side(r0h_session_balance* sb, const uint8_t* elf, size_t elf_len, const uint8_t* journal,
+                                                  size_t journal_len);
+const char* r0h_session_balance_report(r0h_session_balance* sb, r0h_session_imbalance* out, size_t capacity, size_t* n_out);
+const char* r0h_session_balance_message(r0h_session_balance* sb, char** text_out);
+const char* r0h_session_balance_stats(r0h_session_balance* sb, uint64_t stats_out[4]);
+/* on != 0: from now on r0h_session_finish (and so r0h_prove_elf) of a trace-circuit session on this context checks the session balance
+ * of all its segments' DATA witnesses (still resident, lean segments included) with the verifier's side from the ELF and the run's
+ * journal BEFORE the session challenge is derived, and a session that does not balance returns "r0h_prove_elf: session fraction F
+ * does not balance: ..." (the message above) with its proofs aborted; the phase is `check_session` in the profile.  Single-rank
+ * sessions only: a rank sees its own segments alone, and r0h_session_begin with parts > 1 refuses the switch (a multi-rank driver
+ * would gather the tuples through the handle above).  Off (the default): nothing is checked, seals, launches and timing are unchanged. */
+const char* r0h_ctx_set_check_session(r0h_ctx* ctx, int on);
 
 /* ---- the sequencer: risc0-circuit-rv32im `SegmentProver::prove` + risc0-zkp `Prover::{commit_group, finalize}` ---- */
 /* code/data: witness columns resident in device memory ([group_size][2^po2]); global: host words.

@@ -50,6 +50,7 @@
  *                a polynomial in the challenges -- per challenge identity (kind 0 "one", (1, index), (2, index)) the sum of the
  *                values of the parts under it, zero sums dropped -- and the chain closes iff in every class the numerators sum to
  *                0 mod p.  Accumulators with a public total balance across segments and the verifier only: they are left out
+ *                there and checked, by the same definitions over a whole session, by r0h_session_balance_* (r0hip.h)
  *   PERIODIC (11): period, n_cols, then n_cols x period canonical values: what CODE columns of kind 6 repeat
  *   SPONGE (12): [the in-circuit Poseidon2 sponge of the recursion circuit: tools/sponge_component.py] first CODE column (28 columns: rc[24],
  *                sel_mix, sel_full, sel_part, sel_last), first DATA column (65 columns: st[24], aux[24], in[16], act), first of the 8 public

@@ -57,6 +57,7 @@ def main():
     ap.add_argument("--share-device", action="store_true", help="all ranks on GPU 0 (rehearsal on a one-GPU box)")
     ap.add_argument("--sessions", type=int, default=1, help="sessions in flight on this GPU, each on a context of its own (single rank only)")
     ap.add_argument("--resident-limit-gb", type=float, default=-1.0, help="r0h_ctx_set_session_resident_limit per session context (default: the library's, an eighth of the device)")
+    ap.add_argument("--check-session", type=int, default=0, help="1: r0h_ctx_set_check_session -- the session balance of all segments is checked before the challenge is derived (single rank only)")
     args = ap.parse_args()
     world, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     import __graft_entry__ as entry
@@ -90,6 +91,8 @@ def main():
     blob = np.fromfile(entry.circuit_blob_path("trace"), dtype=np.uint32)
     hal = r0.Hal(0 if (env is None or args.share_device) else local)
     gc = hal.load_circuit(blob, entry.code_object_path("trace"))
+    if args.check_session:
+        hal.set_check_session(True)
     if args.resident_limit_gb >= 0:
         hal.set_session_resident_limit(int(args.resident_limit_gb * (1 << 30)))
     others = []  # further sessions in flight beside this one: a context and a loaded circuit each
@@ -155,7 +158,7 @@ def main():
     n = len(seals) * max(1, args.sessions if env is None else 1)
     line = {"sessions_in_flight": args.sessions if env is None else 1, "lean_segments_of_the_reported_session": st["lean_segments"],
             "peak_device_memory_used_GiB": round(peak_used / (1 << 30), 1) if peak_used else None, "metric": "segments/s of prove(env, elf) with the trace circuit: executor + device witgen + proof, all inside the timed region",
-            "value": round(n / wall, 4), "unit": "segments/s", "n_gpus": world, "sharding": None if env is None else "segments rank, rank + %d, ... per rank (%s%s); receipts merged on rank 0" % (world, args.backend, ", all ranks on one GPU" if args.share_device else ""), "segment_po2": args.po2, "segments": len(seals), "cycles": cycles,
+            "value": round(n / wall, 4), "unit": "segments/s", "n_gpus": world, "sharding": None if env is None else "segments rank, rank + %d, ... per rank (%s%s); receipts merged on rank 0" % (world, args.backend, ", all ranks on one GPU" if args.share_device else ""), "segment_po2": args.po2, "segments": len(seals), "cycles": cycles, "check_session": bool(args.check_session),
             "wall_s": round(wall, 4), "guest": what,
             "executor": {"host_s": round(st["executor_s"], 4), "MHz_with_trace_kept": round(cycles / st["executor_s"] / 1e6, 2), "host_ms_per_segment": round(1e3 * st["executor_s"] / max(1, st["segments"]), 3),
                          "note": "own host thread, overlaps the device work of the previous segment"},

@@ -27,6 +27,14 @@ const char* make_error(const char* fmt, ...) {  // (csrc/ctx.cpp's, which comes 
   va_end(ap);
   return strdup(buf);
 }
+// logup_host.cpp also holds the session balance's handle; what a device handle or the verifier's side would call is not reached here
+void ctx_retain(r0h_ctx*) {}
+void ctx_release(r0h_ctx*) {}
+void session_table_free(r0h_session_balance*) {}
+const char* session_table_add_list(r0h_session_balance*, uint32_t, const uint64_t*, const uint32_t*, const uint32_t*, size_t) { return make_error("no device"); }
+const char* session_table_report(r0h_session_balance*, r0h_session_imbalance*, size_t, size_t*) { return make_error("no device"); }
+const char* session_table_stats(r0h_session_balance*, uint64_t*, uint64_t*) { return make_error("no device"); }
+const char* elf_image(const uint8_t*, size_t, std::vector<std::pair<uint32_t, uint32_t>>&, uint32_t*, uint8_t[32]) { return make_error("no executor"); }
 }  // namespace r0h
 
 static std::vector<uint32_t> read_words(const char* path) {

@@ -472,20 +472,23 @@ def term_names(circuit):
     return ["term:%d" % t for t in range(sum(1 for k in range(n_steps) if words[at + 4 + 4 * k] == OP_AND_EQZ))]
 
 
-def fraction_names(circuit):
+def fraction_names(circuit, public_totals=False):
     """What the chain links' fractions of `circuit` (a shape's name) are called, in the order r0h_logup_check_balance numbers them
     (4 * accumulator + slot, r0h_circuit_n_chain_fractions of them): the trace circuit's carry the names its generator gives them
-    (tools/trace_circuit.fractions); every other circuit has ordinals, none where it has no LOGUP section."""
+    (tools/trace_circuit.fractions); every other circuit has ordinals, none where it has no LOGUP section.  public_totals=True: the
+    list goes on, in the same numbering, through the fractions of the accumulators with a public total -- what r0h_session_balance_*
+    reports (the trace circuit's 36..39: session:consume, session:produce, session:image, session:journal)."""
     if circuit == "trace":
         import trace_circuit
-        return [f.name for f in trace_circuit.fractions()[0]]
+        chained, session = trace_circuit.fractions()
+        return [f.name for f in chained] + ([f.name for f in session] if public_totals else [])
     words = generate_image()[0] if circuit == "image" else generate(**SHAPES[circuit])[0]
     at, end = 3, len(words)
     while at < end and words[at] != SEC_LOGUP:
         at += 2 + words[at + 1]
     if at >= end:
         return []
-    n_chain, pos = 0, at + 4 + 2 * words[at + 3]      # past n_acc, n_tables and the tables
+    n_chain, n_public, pos = 0, 0, at + 4 + 2 * words[at + 3]      # past n_acc, n_tables and the tables
 
     def form(pos):
         return pos + 1 + 3 * words[pos]
@@ -499,7 +502,8 @@ def fraction_names(circuit):
             for _ in range(n_parts):
                 pos = form(pos + 2)
         n_chain += final == 0xFFFFFFFF
-    return ["fraction:%d" % f for f in range(4 * n_chain)]
+        n_public += final != 0xFFFFFFFF
+    return ["fraction:%d" % f for f in range(4 * (n_chain + (n_public if public_totals else 0)))]
 
 
 def main():
@@ -507,11 +511,11 @@ def main():
     ap.add_argument("shape", choices=sorted(SHAPES) + ["trace", "image"])
     ap.add_argument("out")
     ap.add_argument("--names", action="store_true", help="write the names of the shape's constraint terms, one per line in term order, instead of the blob")
-    ap.add_argument("--fraction-names", action="store_true", help="write the names of the shape's chain fractions, one per line in the order r0h_logup_check_balance numbers them, instead of the blob")
+    ap.add_argument("--fraction-names", action="store_true", help="write the names of the shape's fractions, one per line in the order r0h_logup_check_balance numbers them -- the chain's, then those of the accumulators with a public total (r0h_session_balance_*) -- instead of the blob")
     args = ap.parse_args()
     if args.fraction_names:
         with open(args.out, "w") as f:
-            f.write("".join(name + "\n" for name in fraction_names(args.shape)))
+            f.write("".join(name + "\n" for name in fraction_names(args.shape, public_totals=True)))
         return 0
     if args.names:
         with open(args.out, "w") as f:
