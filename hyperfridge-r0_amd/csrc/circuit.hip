@@ -137,6 +137,7 @@ const char* r0h_circuit_free(r0h_circuit* c) {
   r0h_ctx* ctx = c->ctx;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  ctx_code_commits_drop(ctx, c);  // the commitments of its CODE group go with the circuit
   CircuitUnload()(c);
   ctx_release(ctx);
   return nullptr;
@@ -209,6 +210,31 @@ const char* code_commit_of(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h
   R0H_TRY(code.alloc(ctx, ((size_t)c->group_size[R0H_GROUP_CODE] << po2) * 4));
   R0H_TRY(witgen_code(ctx, c, po2, code.get()));
   return r0h_code_commit_new(ctx, code.get(), c->group_size[R0H_GROUP_CODE], po2, out);
+}
+const char* ctx_code_commit(r0h_ctx* lane, const r0h_circuit* c, uint32_t po2, std::shared_ptr<r0h_code_commit>* out) {
+  r0h_ctx* owner = c->ctx;
+  std::lock_guard<std::mutex> lk(owner->code_commits_mu);
+  const auto key = std::make_tuple(c, po2, lane->hashfn);  // (a helper lane follows its owner's suite: ctx_helper)
+  auto it = owner->code_commits.find(key);
+  if (it != owner->code_commits.end() && memcmp(&it->second.table, &lane->p2_host, sizeof(P2Consts)) != 0) {  // r0h_poseidon2_set_consts since
+    owner->code_commits.erase(it);
+    it = owner->code_commits.end();
+  }
+  if (it == owner->code_commits.end()) {
+    r0h_code_commit* cc = nullptr;
+    R0H_TRY(code_commit_of(lane, c, po2, &cc));
+    std::shared_ptr<r0h_code_commit> held(cc, [](r0h_code_commit* p) { r0h_code_commit_free(p); });
+    it = owner->code_commits.emplace(key, r0h_ctx::CodeCommitEntry{held, lane->p2_host}).first;
+  }
+  *out = it->second.cc;
+  return nullptr;
+}
+void ctx_code_commits_drop(r0h_ctx* ctx, const r0h_circuit* c) {
+  std::lock_guard<std::mutex> lk(ctx->code_commits_mu);
+  for (auto it = ctx->code_commits.begin(); it != ctx->code_commits.end();) {
+    if (c && std::get<0>(it->first) != c) { ++it; continue; }
+    it = ctx->code_commits.erase(it);
+  }
 }
 }  // namespace r0h
 extern "C" {

@@ -242,6 +242,7 @@ const char* ctx_helper(r0h_ctx* ctx, size_t k, r0h_ctx** out) {
   h->check_witness = ctx->check_witness;
   h->check_balance = ctx->check_balance;
   h->check_session = ctx->check_session;
+  h->hashfn = ctx->hashfn;
   if (memcmp(&h->p2_host, &ctx->p2_host, sizeof(P2Consts)) != 0) {  // r0h_poseidon2_set_consts on the owner since the helper was made
     h->p2_host = ctx->p2_host;
     R0H_TRY_HIP(hipSetDevice(h->device));
@@ -325,6 +326,7 @@ const char* r0h_ctx_destroy(r0h_ctx* ctx) {
   if (!ctx) return nullptr;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  ctx_code_commits_drop(ctx, nullptr);  // cached CODE commitments hold references of their own: they go first, their buffers while the device state is whole
   ctx_release(ctx);  // buffers and circuits still alive keep the device state until they are freed
   return nullptr;
 }

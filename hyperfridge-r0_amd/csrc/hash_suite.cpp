@@ -150,6 +150,7 @@ const char* r0h_ctx_set_hashfn(r0h_ctx* ctx, const char* name) {
   R0H_REQUIRE(ctx, "r0h_ctx_set_hashfn: NULL argument");
   int fn = 0;
   R0H_TRY(hashfn_parse("r0h_ctx_set_hashfn", name, &fn));
+  if (fn != ctx->hashfn) ctx_code_commits_drop(ctx, nullptr);  // CODE trees hashed under the suite that is left
   ctx->hashfn = fn;
   return nullptr;
 }

@@ -8,7 +8,9 @@
 
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/r0hip.h"
@@ -119,6 +121,15 @@ struct r0h_ctx {
   uint64_t balance_stats[3] = {0, 0, 0};  // the last r0h_logup_check_balance: tuples, inserts that reached the global table, its slots
   bool ktime_on = false;
   std::map<std::string, r0h::KTimer> ktimers;
+  // The committed CODE groups of the circuits loaded on this context, by (circuit, po2, hash suite): CODE depends on nothing else, so
+  // the sessions of a context commit each once (ctx_code_commit).  The lanes of a session share it under the mutex.  Every entry holds
+  // references on the context that made it (this one or one of its helpers), so the entries go explicitly: with their circuit
+  // (r0h_circuit_free), when the suite changes (r0h_ctx_set_hashfn) and at r0h_ctx_destroy, before the reference count is looked at.
+  // `table`: the Poseidon2 constants the tree was hashed with.  Shared: a session holds its segments' commitments from begin to finish,
+  // so an entry that is dropped meanwhile (suite changed, circuit freed, context destroyed) is freed when the last such session lets go.
+  struct CodeCommitEntry { std::shared_ptr<r0h_code_commit> cc; r0h::P2Consts table; };
+  std::mutex code_commits_mu;
+  std::map<std::tuple<const r0h_circuit*, uint32_t, int>, CodeCommitEntry> code_commits;
 };
 
 struct r0h_buf {
@@ -197,6 +208,13 @@ const char* unpack_ext_columns(r0h_ctx* ctx, uint32_t* cols, const uint32_t* pac
 const char* witgen_code(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* code);
 // the committed CODE group of `c` at 2^po2 rows: CODE from the pool, witgen_code, r0h_code_commit_new
 const char* code_commit_of(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_code_commit** out);
+// the same, made once and kept by the circuit's context (r0h_ctx::code_commits): committed on `lane` -- the caller's own context of that
+// device -- when it is missing, or was made under other Poseidon2 constants.  The caller shares it with the cache for as long as it
+// keeps `out`.
+const char* ctx_code_commit(r0h_ctx* lane, const r0h_circuit* c, uint32_t po2, std::shared_ptr<r0h_code_commit>* out);
+// takes the cached commitments of `c` on `ctx`, or all of them (c == nullptr), out of the cache: freed here, or by the last session
+// that still holds them
+void ctx_code_commits_drop(r0h_ctx* ctx, const r0h_circuit* c);
 // rv32im.cpp: the preflight rows of segment i are moved out of the machine (the session proves them while the guest runs on)
 void vm_take_trace(r0h_vm* vm, size_t i, std::vector<r0h_preflight_row>& rows, std::vector<r0h_preflight_bound>& bounds);
 void vm_recycle_trace(r0h_vm* vm, std::vector<r0h_preflight_row>& rows, std::vector<r0h_preflight_bound>& bounds);

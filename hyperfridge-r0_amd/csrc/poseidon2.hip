@@ -18,17 +18,16 @@ __global__ __launch_bounds__(256) void hash_rows_kernel(uint32_t* __restrict__ d
 #pragma unroll
   for (int i = 0; i < P2_CELLS; i++) c[i] = 0;
   const uint32_t* src = matrix + row;
-  uint32_t full = cols / P2_RATE, rem = cols % P2_RATE;
+  const uint32_t blocks = cols ? (cols + P2_RATE - 1) / P2_RATE : 1u;  // the last one may be partial, zero-padded (all zeros for cols == 0)
+  // One permutation body for every block: the first enters with a zero capacity, only the digest is read from the last.  One
+  // form of the loads too, each behind a scalar test of its column (two bodies, or a full and a padded form of the loads side by
+  // side, cost registers and 0.2-0.6 % of the kernel: profiles/r11/poseidon2_trims.md).
   // (prefetching the next rate block into registers was measured: no gain, the kernel is VALU-issue bound)
-  for (uint32_t blk = 0; blk < full; blk++) {
+  for (uint32_t blk = 0; blk < blocks; blk++) {
+    const uint32_t have = cols - blk * P2_RATE;  // columns left, this block's included
 #pragma unroll
-    for (int i = 0; i < P2_RATE; i++) c[i] = src[(size_t)(blk * P2_RATE + i) * rows];
-    p2_mix(c, k);
-  }
-  if (rem != 0 || cols == 0) {
-#pragma unroll
-    for (int i = 0; i < P2_RATE; i++) c[i] = (uint32_t)i < rem ? src[(size_t)(full * P2_RATE + i) * rows] : 0u;
-    p2_mix(c, k);
+    for (int i = 0; i < P2_RATE; i++) c[i] = (uint32_t)i < have ? src[(size_t)(blk * P2_RATE + i) * rows] : 0u;
+    p2_mix_ends(c, k, blk == 0, blk + 1 == blocks);
   }
   uint4* dst = (uint4*)(digests + (size_t)row * 8);
   dst[0] = make_uint4(c[0], c[1], c[2], c[3]);
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(256) void hash_fold_kernel(uint32_t* __restrict__ n
   }
 #pragma unroll
   for (int q = 16; q < P2_CELLS; q++) c[q] = 0;
-  p2_mix(c, k);
+  p2_mix<P2_ZERO_CAP | P2_DIGEST_ONLY>(c, k);
   uint4* dst = (uint4*)(nodes + (size_t)i * 8);
   dst[0] = make_uint4(c[0], c[1], c[2], c[3]);
   dst[1] = make_uint4(c[4], c[5], c[6], c[7]);

@@ -19,7 +19,8 @@ __device__ __forceinline__ uint32_t sbox7(uint32_t x) {
 
 // One modular add inside a larger asm statement: r = a + b mod p (x: scratch).  r may be a or b.
 #define R0H_ASM_ADD(r, a, b, x) "v_add_u32 " r ", " a ", " b "\n\tv_subrev_co_u32 " x ", vcc, 0x78000001, " r "\n\tv_cndmask_b32 " r ", " x ", " r ", vcc\n\t"
-// External linear layer: circ(2 M4, M4, .., M4) with M4 = [[2,3,1,1],[1,2,3,1],[1,1,2,3],[3,1,1,2]] -- 128 modular adds.
+// External linear layer: circ(2 M4, M4, .., M4) with M4 = [[2,3,1,1],[1,2,3,1],[1,1,2,3],[3,1,1,2]] -- 124 modular adds (the
+// first block's outputs seed the column sums; the plain form below is the restatement).
 // Written as seven asm statements (one per block of four cells incl. its share of the column sums, one for the final 24 adds):
 // hipcc puts an `s_nop 0` between an asm statement and the next instruction touching a register that statement wrote (it assumes
 // a dst-forwarding hazard on gfx950 for anything inside asm), so the one-statement-per-add form carried a nop with every add:
@@ -27,34 +28,74 @@ __device__ __forceinline__ uint32_t sbox7(uint32_t x) {
 // VGPRs (four waves per SIMD instead of three) and measures 0.45 % faster on hash_rows in an A/B on one box
 // (profiles/r02/poseidon2_variants.md).  Same canonical words: every add is reduced, only the statement boundaries moved.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(R0H_MEXT_PLAIN)
+// M4 on one block of four cells and its share of the column sums.  FIRST: the block's outputs ARE the sums so far (nothing is
+// added to zero); the second block then writes its sums to fresh registers (the first block's outputs stay live as cells).
+#define R0H_ASM_M4(T0, T1, T2, T3, U, X, A, B, D, E, O0, O1, O2, O3) \
+  R0H_ASM_ADD(T0, A, B, X)    /* t0 = a + b */ \
+  R0H_ASM_ADD(T1, D, E, X)    /* t1 = d + e */ \
+  R0H_ASM_ADD(U, B, B, X)     /* u = 2b */ \
+  R0H_ASM_ADD(T2, U, T1, X)   /* t2 = 2b + t1 */ \
+  R0H_ASM_ADD(U, E, E, X)     /* u = 2e */ \
+  R0H_ASM_ADD(T3, U, T0, X)   /* t3 = 2e + t0 */ \
+  R0H_ASM_ADD(T1, T1, T1, X)  /* 2 t1 */ \
+  R0H_ASM_ADD(T1, T1, T1, X)  /* 4 t1 */ \
+  R0H_ASM_ADD(O3, T1, T3, X)  /* o3 = t4 = 4 t1 + t3 */ \
+  R0H_ASM_ADD(T0, T0, T0, X)  /* 2 t0 */ \
+  R0H_ASM_ADD(T0, T0, T0, X)  /* 4 t0 */ \
+  R0H_ASM_ADD(O1, T0, T2, X)  /* o1 = t5 = 4 t0 + t2 */ \
+  R0H_ASM_ADD(O0, T3, O1, X)  /* o0 = t3 + t5 */ \
+  R0H_ASM_ADD(O2, T2, O3, X)  /* o2 = t2 + t4 */
 template <bool FIRST>
 __device__ __forceinline__ void m4_block(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t& s0, uint32_t& s1, uint32_t& s2, uint32_t& s3) {
   uint32_t o0, o1, o2, o3, t0, t1, t2, t3, u, x;
-  // %0-3 o, %4-7 s (in/out), %8-13 t0 t1 t2 t3 u x, %14-17 a b d e
-  asm(R0H_ASM_ADD("%8", "%14", "%15", "%13")   // t0 = a + b
-      R0H_ASM_ADD("%9", "%16", "%17", "%13")   // t1 = d + e
-      R0H_ASM_ADD("%12", "%15", "%15", "%13")  // u = 2b
-      R0H_ASM_ADD("%10", "%12", "%9", "%13")   // t2 = 2b + t1
-      R0H_ASM_ADD("%12", "%17", "%17", "%13")  // u = 2e
-      R0H_ASM_ADD("%11", "%12", "%8", "%13")   // t3 = 2e + t0
-      R0H_ASM_ADD("%9", "%9", "%9", "%13")     // 2 t1
-      R0H_ASM_ADD("%9", "%9", "%9", "%13")     // 4 t1
-      R0H_ASM_ADD("%3", "%9", "%11", "%13")    // o3 = t4 = 4 t1 + t3
-      R0H_ASM_ADD("%8", "%8", "%8", "%13")     // 2 t0
-      R0H_ASM_ADD("%8", "%8", "%8", "%13")     // 4 t0
-      R0H_ASM_ADD("%1", "%8", "%10", "%13")    // o1 = t5 = 4 t0 + t2
-      R0H_ASM_ADD("%0", "%11", "%1", "%13")    // o0 = t3 + t5
-      R0H_ASM_ADD("%2", "%10", "%3", "%13")    // o2 = t2 + t4
-      R0H_ASM_ADD("%4", "%4", "%0", "%13") R0H_ASM_ADD("%5", "%5", "%1", "%13") R0H_ASM_ADD("%6", "%6", "%2", "%13") R0H_ASM_ADD("%7", "%7", "%3", "%13")
-      : "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3), "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(u), "=&v"(x)
-      : "v"(c0), "v"(c1), "v"(c2), "v"(c3)
-      : "vcc");
+  if (FIRST) {
+    // %0-3 o, %4-9 t0 t1 t2 t3 u x, %10-13 a b d e
+    asm(R0H_ASM_M4("%4", "%5", "%6", "%7", "%8", "%9", "%10", "%11", "%12", "%13", "%0", "%1", "%2", "%3")
+        : "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(u), "=&v"(x)
+        : "v"(c0), "v"(c1), "v"(c2), "v"(c3)
+        : "vcc");
+    s0 = o0; s1 = o1; s2 = o2; s3 = o3;
+  } else {
+    // %0-3 o, %4-7 s (out), %8-13 t0 t1 t2 t3 u x, %14-17 a b d e, %18-21 s (in)
+    uint32_t n0, n1, n2, n3;
+    asm(R0H_ASM_M4("%8", "%9", "%10", "%11", "%12", "%13", "%14", "%15", "%16", "%17", "%0", "%1", "%2", "%3")
+        R0H_ASM_ADD("%4", "%18", "%0", "%13") R0H_ASM_ADD("%5", "%19", "%1", "%13") R0H_ASM_ADD("%6", "%20", "%2", "%13") R0H_ASM_ADD("%7", "%21", "%3", "%13")
+        : "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3), "=&v"(n0), "=&v"(n1), "=&v"(n2), "=&v"(n3), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(u), "=&v"(x)
+        : "v"(c0), "v"(c1), "v"(c2), "v"(c3), "v"(s0), "v"(s1), "v"(s2), "v"(s3)
+        : "vcc");
+    s0 = n0; s1 = n1; s2 = n2; s3 = n3;
+  }
   c0 = o0; c1 = o1; c2 = o2; c3 = o3;
 }
-__device__ __forceinline__ void m_ext(uint32_t (&c)[P2_CELLS]) {
-  uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0, x;
-#pragma unroll
-  for (int k = 0; k < P2_CELLS; k += 4) m4_block<false>(c[k], c[k + 1], c[k + 2], c[k + 3], s0, s1, s2, s3);
+// c[k..k+3] += (s0, s1, s2, s3) for the blocks [0, N) of four cells, one statement
+template <int N>
+__device__ __forceinline__ void add_sums(uint32_t (&c)[P2_CELLS], uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3);
+template <>
+__device__ __forceinline__ void add_sums<2>(uint32_t (&c)[P2_CELLS], uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3) {
+  uint32_t x;
+  // %0-7 cells (in/out), %8 scratch, %9-12 column sums
+  asm(R0H_ASM_ADD("%0", "%0", "%9", "%8") R0H_ASM_ADD("%1", "%1", "%10", "%8") R0H_ASM_ADD("%2", "%2", "%11", "%8") R0H_ASM_ADD("%3", "%3", "%12", "%8")
+      R0H_ASM_ADD("%4", "%4", "%9", "%8") R0H_ASM_ADD("%5", "%5", "%10", "%8") R0H_ASM_ADD("%6", "%6", "%11", "%8") R0H_ASM_ADD("%7", "%7", "%12", "%8")
+      : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]), "=&v"(x)
+      : "v"(s0), "v"(s1), "v"(s2), "v"(s3)
+      : "vcc");
+}
+template <>
+__device__ __forceinline__ void add_sums<4>(uint32_t (&c)[P2_CELLS], uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3) {
+  uint32_t x;
+  // %0-15 cells (in/out), %16 scratch, %17-20 column sums
+  asm(R0H_ASM_ADD("%0", "%0", "%17", "%16") R0H_ASM_ADD("%1", "%1", "%18", "%16") R0H_ASM_ADD("%2", "%2", "%19", "%16") R0H_ASM_ADD("%3", "%3", "%20", "%16")
+      R0H_ASM_ADD("%4", "%4", "%17", "%16") R0H_ASM_ADD("%5", "%5", "%18", "%16") R0H_ASM_ADD("%6", "%6", "%19", "%16") R0H_ASM_ADD("%7", "%7", "%20", "%16")
+      R0H_ASM_ADD("%8", "%8", "%17", "%16") R0H_ASM_ADD("%9", "%9", "%18", "%16") R0H_ASM_ADD("%10", "%10", "%19", "%16") R0H_ASM_ADD("%11", "%11", "%20", "%16")
+      R0H_ASM_ADD("%12", "%12", "%17", "%16") R0H_ASM_ADD("%13", "%13", "%18", "%16") R0H_ASM_ADD("%14", "%14", "%19", "%16") R0H_ASM_ADD("%15", "%15", "%20", "%16")
+      : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]), "+v"(c[8]), "+v"(c[9]), "+v"(c[10]), "+v"(c[11]),
+        "+v"(c[12]), "+v"(c[13]), "+v"(c[14]), "+v"(c[15]), "=&v"(x)
+      : "v"(s0), "v"(s1), "v"(s2), "v"(s3)
+      : "vcc");
+}
+template <>
+__device__ __forceinline__ void add_sums<6>(uint32_t (&c)[P2_CELLS], uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3) {
+  uint32_t x;
   // %0-23 cells (in/out), %24 scratch, %25-28 column sums
   asm(R0H_ASM_ADD("%0", "%0", "%25", "%24") R0H_ASM_ADD("%1", "%1", "%26", "%24") R0H_ASM_ADD("%2", "%2", "%27", "%24") R0H_ASM_ADD("%3", "%3", "%28", "%24")
       R0H_ASM_ADD("%4", "%4", "%25", "%24") R0H_ASM_ADD("%5", "%5", "%26", "%24") R0H_ASM_ADD("%6", "%6", "%27", "%24") R0H_ASM_ADD("%7", "%7", "%28", "%24")
@@ -68,7 +109,25 @@ __device__ __forceinline__ void m_ext(uint32_t (&c)[P2_CELLS]) {
       : "v"(s0), "v"(s1), "v"(s2), "v"(s3)
       : "vcc");
 }
+// The layer as a whole.  ZERO_CAP: the capacity cells c[16..23] are zero on entry, so their two M4 blocks are zero and they leave
+// as the column sums.  DIGEST_ONLY: only c[0..7] are read afterwards (the cells c[8..23] are left without their column sums).
+template <bool ZERO_CAP = false, bool DIGEST_ONLY = false>
+__device__ __forceinline__ void m_ext(uint32_t (&c)[P2_CELLS]) {
+  uint32_t s0, s1, s2, s3;
+  m4_block<true>(c[0], c[1], c[2], c[3], s0, s1, s2, s3);
+#pragma unroll
+  for (int k = 4; k < (ZERO_CAP ? P2_RATE : P2_CELLS); k += 4) m4_block<false>(c[k], c[k + 1], c[k + 2], c[k + 3], s0, s1, s2, s3);
+  if (DIGEST_ONLY) {
+    add_sums<2>(c, s0, s1, s2, s3);
+  } else if (ZERO_CAP) {
+    add_sums<4>(c, s0, s1, s2, s3);
+    c[16] = c[20] = s0; c[17] = c[21] = s1; c[18] = c[22] = s2; c[19] = c[23] = s3;
+  } else {
+    add_sums<6>(c, s0, s1, s2, s3);
+  }
+}
 #else
+template <bool ZERO_CAP = false, bool DIGEST_ONLY = false>  // (the plain form takes no advantage of either)
 __device__ __forceinline__ void m_ext(uint32_t (&c)[P2_CELLS]) {
   uint32_t s0, s1, s2, s3;
 #pragma unroll
@@ -101,10 +160,12 @@ __device__ __forceinline__ uint32_t sum_lanes_1_to_23(const uint32_t (&c)[P2_CEL
   return add(add(add(s2[0], s2[1]), add(s2[2], s2[3])), add(s2[4], s2[5]));
 }
 
-__device__ __forceinline__ void p2_full_round(uint32_t (&c)[P2_CELLS], const uint32_t* __restrict__ rc) {
+// digest_only (wave-uniform; a constant folds away): the round is a hash's last, only c[0..7] are read after it
+__device__ __forceinline__ void p2_full_round(uint32_t (&c)[P2_CELLS], const uint32_t* __restrict__ rc, bool digest_only = false) {
 #pragma unroll
   for (int i = 0; i < P2_CELLS; i++) c[i] = sbox7(add(c[i], rc[i]));
-  m_ext(c);
+  if (digest_only) m_ext<false, true>(c);
+  else m_ext(c);
 }
 
 // Lazily accumulated dot product mod p: 64-bit accumulator, products of reduced words.  The first four products fit as they
@@ -112,7 +173,17 @@ __device__ __forceinline__ void p2_full_round(uint32_t (&c)[P2_CELLS], const uin
 // below p 2^32 + 2 p^2 < 2^64 and its high word below 2p.  ~11 SIMD cycles per term against ~34 for a reduced product plus a
 // modular add (tools/microbench/dot_bench.hip).  `idx` is the term's position: compile-time after unrolling.
 __device__ __forceinline__ void dot_fix(uint64_t& acc) {
-  acc = ((uint64_t)reduce1((uint32_t)(acc >> 32)) << 32) | (uint32_t)acc;
+  uint32_t hi = (uint32_t)(acc >> 32);
+#if defined(__HIP_DEVICE_COMPILE__)
+  // reduce1 on the high word IN PLACE: the word is a read-write operand and only the scratch is early-clobber, so the register
+  // coalescer keeps it in the accumulator pair.  reduce1 itself returns an early-clobber output, which cost a v_mov_b32 back into
+  // the pair after every correction (550 per permutation); same two full-rate instructions, same word.
+  uint32_t x;
+  asm("v_subrev_co_u32 %1, vcc, 0x78000001, %0\n\tv_cndmask_b32 %0, %1, %0, vcc" : "+v"(hi), "=&v"(x) : : "vcc");
+#else
+  hi = reduce1(hi);
+#endif
+  acc = ((uint64_t)hi << 32) | (uint32_t)acc;
   // opaque re-pack: seen as (hi << 32) + lo, the optimiser re-associates the following multiply-adds into separate 64-bit
   // additions and moves instead of one v_mad_u64_u32 on the accumulator pair
   asm("" : "+v"(acc));
@@ -169,13 +240,26 @@ __device__ __forceinline__ void p2_partial_rounds(uint32_t (&c)[P2_CELLS], const
   }
 }
 
-__device__ __forceinline__ void p2_mix(uint32_t (&c)[P2_CELLS], const P2Consts* __restrict__ k) {
-  m_ext(c);
+// The permutation, with what the sponge knows about its ends (both wave-uniform; compile-time constants fold away):
+//   zero_cap     the capacity cells c[16..23] are zero on entry (a hash's first block): the first linear layer skips their blocks
+//   digest_only  only c[0..7] are read afterwards (a hash's last block): the last linear layer leaves c[8..23] unfinished
+// The canonical words that are read are those of the plain permutation.  One body serves every block of hash_rows: the two
+// shorter layers sit beside the full ones behind scalar branches, the rounds themselves are not duplicated.
+__device__ __forceinline__ void p2_mix_ends(uint32_t (&c)[P2_CELLS], const P2Consts* __restrict__ k, bool zero_cap, bool digest_only) {
+  if (zero_cap) m_ext<true, false>(c);
+  else m_ext(c);
 #pragma unroll 1
   for (int r = 0; r < P2_HALF_FULL; r++) p2_full_round(c, k->rc_full[r]);
   p2_partial_rounds(c, k);
 #pragma unroll 1
-  for (int r = P2_HALF_FULL; r < 2 * P2_HALF_FULL; r++) p2_full_round(c, k->rc_full[r]);
+  for (int r = P2_HALF_FULL; r < 2 * P2_HALF_FULL; r++) {
+    p2_full_round(c, k->rc_full[r], digest_only && r == 2 * P2_HALF_FULL - 1);
+  }
+}
+constexpr int P2_ZERO_CAP = 1, P2_DIGEST_ONLY = 2;
+template <int ENDS = 0>
+__device__ __forceinline__ void p2_mix(uint32_t (&c)[P2_CELLS], const P2Consts* __restrict__ k) {
+  p2_mix_ends(c, k, (ENDS & P2_ZERO_CAP) != 0, (ENDS & P2_DIGEST_ONLY) != 0);
 }
 
 }  // namespace r0h

@@ -45,21 +45,6 @@ namespace {
 using Clock = std::chrono::steady_clock;
 double seconds(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
 
-struct CodeCommits {  // one committed CODE group per trace size met in the run
-  std::map<uint32_t, r0h_code_commit*> by_po2;
-  ~CodeCommits() { for (auto& kv : by_po2) r0h_code_commit_free(kv.second); }
-  const char* get(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_code_commit** out) {
-    auto it = by_po2.find(po2);
-    if (it == by_po2.end()) {
-      r0h_code_commit* cc = nullptr;
-      R0H_TRY(code_commit_of(ctx, c, po2, &cc));
-      it = by_po2.emplace(po2, cc).first;
-    }
-    *out = it->second;
-    return nullptr;
-  }
-};
-
 struct Produced {  // a segment as the executor thread hands it over
   size_t index = 0;
   r0h_vm_segment info;
@@ -339,6 +324,7 @@ struct ProofAbort { void operator()(r0h_proof* p) const { r0h_proof_abort(p); } 
 struct Pending {  // a segment between the phases: committed, waiting for the session challenge
   size_t index = 0;
   r0h_ctx* lctx = nullptr;
+  std::shared_ptr<r0h_code_commit> cc_held;  // shared with the context's cache (ctx_code_commit); before `proof`: it outlives the proof that reads it
   DevBuf data;
   std::unique_ptr<r0h_proof, ProofAbort> proof;  // in flight (after `data`: it goes first)
   r0h_code_commit* cc = nullptr;
@@ -356,9 +342,8 @@ struct r0h_session {
   bool trace_mode = false;
   uint32_t part = 0, parts = 1;
   size_t n_segments = 0;
-  std::mutex commit_mu, result_mu;  // the lanes share `commits`; and `pending`, `stats`, `resident_evaluations`
+  std::mutex result_mu;  // the lanes share `pending`, `stats`, `resident_evaluations`
   std::vector<Pending> pending;  // this rank's segments, by index
-  CodeCommits commits;
   std::vector<uint8_t> journal;
   std::vector<uint8_t> elf;  // kept for the image proof (r0h_ctx_set_image_circuit) and for the session check's verifier side
   bool check_session = false;  // r0h_ctx_set_check_session was on when the session began
@@ -452,10 +437,8 @@ const char* take_segments(r0h_session* ses, Feed& feed, RowBuffers& rows, r0h_ct
     std::fill(global.begin(), global.end(), 0u);
     claim_globals(cd, global.data());
     R0H_TRY(data.alloc(lctx, ((size_t)c->group_size[R0H_GROUP_DATA] << pend.po2) * 4));
-    {
-      std::lock_guard<std::mutex> lk(ses->commit_mu);
-      R0H_TRY(ses->commits.get(lctx, c, pend.po2, &pend.cc));
-    }
+    R0H_TRY(ctx_code_commit(lctx, c, pend.po2, &pend.cc_held));
+    pend.cc = pend.cc_held.get();  // committed once per (circuit, po2) and kept by the circuit's context
     R0H_TRY(ses->trace_mode ? commit_segment(ses, rows, *seg, data, global, pend) : prove_synthetic_segment(ses, *seg, data, global, seal, pend));
   }
 }

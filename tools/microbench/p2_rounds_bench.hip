@@ -21,6 +21,11 @@ __global__ __launch_bounds__(256) void rounds_kernel(uint32_t* out, const P2Cons
     if (MODE == 1) p2_partial_rounds(c, k);
     if (MODE == 2) p2_mix(c, k);
     if (MODE == 3) m_ext(c);
+    if (MODE == 5) {  // a hash's only block: zero capacity in, digest out (hash_fold; cols <= 16 in hash_rows)
+#pragma unroll
+      for (int i = P2_RATE; i < P2_CELLS; i++) c[i] = 0;
+      p2_mix<P2_ZERO_CAP | P2_DIGEST_ONLY>(c, k);
+    }
     if (MODE == 4) {
 #pragma unroll
       for (int i = 0; i < P2_CELLS; i++) c[i] = sbox7(c[i]);
@@ -67,6 +72,7 @@ int main() {
     run<3>("m_ext", d, dk, 8000, w);
     run<4>("24 x sbox7", d, dk, 4000, w);
     run<2>("permutation", d, dk, 200, w);
+    run<5>("first-and-last", d, dk, 200, w);
   }
   return 0;
 }
