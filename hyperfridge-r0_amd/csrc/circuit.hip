@@ -322,7 +322,7 @@ const char* r0h_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0
 const char* r0h_accum_public(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum) {
   R0H_REQUIRE(ctx && c, "r0h_accum_public: NULL argument");
   if (c->logup.accs.empty()) return r0h_accum(ctx, c, po2, code, data, mix, accum);
-  return logup_accum(ctx, c, po2, code, data, global, mix, accum);
+  return logup_accum_kept(ctx, c, po2, code, data, global, mix, accum, nullptr);
 }
 
 const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code,

@@ -1,6 +1,8 @@
 // Parsed circuit blob (include/r0hip_circuit.h): filled by blob.cpp (parse_blob), planned and turned into source text by
 // evalcheck_emit.cpp, compiled, loaded and launched by circuit.hip, walked by prover.hip (sequencer) and verify.cpp.
 #pragma once
+#include <algorithm>
+#include <functional>
 #include <mutex>
 #include <unordered_map>
 
@@ -57,14 +59,19 @@ R0H_HD uint32_t fixed_cell(uint32_t kind, uint32_t arg, uint32_t r, uint32_t n, 
   return 0u;
 }
 
-// ---- the balance check (r0h_logup_check_balance, include/r0hip.h), one statement for the device (logup.hip) and the host
-// (logup_host.cpp): a tuple's class is known by two linear hashes over F_p of its per-identity part sums, h_j = sum_i w_j(i) s_i.
+// ---- the balance check (r0h_logup_check_balance, include/r0hip.h), one statement for the device (balance.hip) and the host
+// (logup_host.cpp's walk_tuples, for balance_host.cpp): a tuple's class is known by two linear hashes over F_p of its per-identity part sums, h_j = sum_i w_j(i) s_i.
 // The weights are fixed words in [1, p) of the challenge's identity (kind << 32 | index; 0 is "one"); the key is never 0 (an empty slot).
 R0H_HD uint32_t balance_weight(uint32_t j, uint64_t identity) {
   const uint64_t h = splitmix64(splitmix64(identity) + 0xBA1A9CEull * (j + 1));
   return 1u + (uint32_t)(((h >> 32) * (uint64_t)(P - 1)) >> 32);
 }
 R0H_HD uint64_t balance_key(uint32_t h0, uint32_t h1) { return (((uint64_t)h0 << 31) | h1) + 1; }
+inline std::vector<uint32_t> balance_weights(const std::vector<uint64_t>& ids) {  // [2][ids.size()]: row j is balance_weight(j, .) of each
+  std::vector<uint32_t> w(2 * ids.size());
+  for (size_t k = 0; k < w.size(); k++) w[k] = balance_weight((uint32_t)(k / ids.size()), ids[k % ids.size()]);
+  return w;
+}
 
 struct Plan {                      // how the constraint program is cut into kernels
   std::vector<Term> terms;         // flattened, in chain order
@@ -123,15 +130,14 @@ const char* sponge_plant(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const
 // r0h_ctx_set_check_witness); global / mix are host words as r0h_eval_check takes them
 const char* require_witness(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,
                             const uint32_t* global, const uint32_t* mix);
-// r0h_logup_check_balance with the lowest imbalanced class turned into an error that starts with `caller` (the sequencer under
-// r0h_ctx_set_check_balance)
+// r0h_logup_check_balance with the lowest imbalanced class turned into an error that starts with `caller` (balance.hip; the sequencer
+// under r0h_ctx_set_check_balance)
 const char* require_balance(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global);
-// the log-derivative accumulation on the device (logup.hip): multiplicities into DATA, the ACCUM group, totals of the public accumulators
-const char* logup_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum);
-// The public accumulators' scanned terms of one segment, kept from the totals step for the accumulation that follows it on the same
+// The log-derivative accumulation on the device (logup.hip): multiplicities into DATA, the ACCUM group (logup_accum_kept), totals of the
+// public accumulators.  The public accumulators' scanned terms of one segment, kept from the totals step for the accumulation that follows it on the same
 // context under the same public inputs (session.cpp): the accumulation then unpacks them into ACCUM instead of evaluating and scanning
-// them again.  logup_totals_keep is r0h_logup_totals with `keep` filled; logup_accum_kept is logup_accum with `kept` used (nullptr, or
-// one that holds nothing: evaluated as in logup_accum).
+// them again.  logup_totals_keep is r0h_logup_totals with `keep` filled; logup_accum_kept uses `kept` (nullptr, or one that holds
+// nothing: they are evaluated and scanned here).
 struct LogupKept {
   DevBuf terms;  // [n_own][2^po2] packed extension elements, inclusive prefix sums
   uint32_t po2 = 0, n_own = 0;
@@ -148,18 +154,39 @@ struct LookupList {
   uint32_t n_cols = 0;  // distinct DATA columns read
 };
 const char* logup_lookup_list(const r0h_circuit* c, const uint32_t* global, LookupList* out);
+// ---- the host's plain-loop statements of the argument (logup_host.cpp), shared by every host check.  A linear form at row r of n over
+// host words (Montgomery form, column-major; absent public inputs count as 0), and what it needs of `caller`'s arguments:
+// "<caller>: a form reads the CODE group and none was given" / "... a public input and none were given"
+uint32_t eval_lf(const Lf& lf, const uint32_t* code, const uint32_t* data, const uint32_t* global, size_t n, size_t r);
+const char* require_lf_inputs(const char* caller, const Lf& lf, const uint32_t* code, const uint32_t* global);
+// The tuples of accumulators [first, first + count): `each` is called for every fraction (numbered 4 * accumulator + slot, in order)
+// and every row on which its numerator is not zero, and what it returns other than nullptr ends the walk as its error.  `sums` are the
+// canonical per-identity sums of the fraction's parts, one per entry of tuple_identities (the challenge identities kind << 32 | index,
+// 0 for "one", in order of first appearance: as many as the accumulators have); `key` is the balance_key of their two hashes.
+inline uint64_t part_identity(const LogupPart& q) { return q.ch_kind ? (uint64_t)q.ch_kind << 32 | q.ch_idx : 0; }
+std::vector<uint64_t> tuple_identities(const r0h_circuit& c, uint32_t first, uint32_t count);
+struct HostTuple { uint64_t key; uint32_t numerator /* canonical */, row, fraction; const uint32_t* sums; };
+const char* walk_tuples(const char* caller, const r0h_circuit& c, uint32_t first, uint32_t count, uint32_t po2, const uint32_t* code, const uint32_t* data, const uint32_t* global,
+                        const std::function<const char*(const HostTuple&)>& each);
 
 // ---- the session balance (r0h_session_balance_*, include/r0hip.h): the balance check's definitions over the accumulators with a
 // public total, across the segments of a session and what the verifier adds.  The handle, its host half and the entry points that need
-// no device are in logup_host.cpp; the device's table and kernels in logup.hip behind the session_table_* functions.
+// no device are in balance_host.cpp; the device's table and kernels in balance.hip behind the session_table_* functions.
 struct SessionClass {  // a class of a host handle
   uint64_t sum = 0, first = ~0ull /* source << 32 | row << 8 | fraction of the lowest member */, members = 0;
   uint32_t values[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // canonical per-identity sums, as the first member has them
 };
-struct SessionTable;  // the device's table (logup.hip)
+struct SessionTable;  // the device's table (balance.hip)
 constexpr uint32_t SESSION_MAX_IDS = 8, SESSION_OUTSIDE_FRACTION = 255;
 constexpr size_t SESSION_MAX_LIST = (size_t)1 << 24;
 R0H_HD uint64_t session_first(uint32_t source, uint32_t row, uint32_t fraction) { return (uint64_t)source << 32 | (uint64_t)row << 8 | fraction; }
+// a report's entry of the class whose lowest member is `first` (session_first), from a host handle's classes or the device's slots
+inline r0h_session_imbalance session_entry(uint64_t first, uint64_t sum, uint64_t members, size_t n_values, const uint32_t (&values)[8]) {
+  r0h_session_imbalance e = {(uint32_t)(first >> 32), (uint32_t)(first & 255u), (uint32_t)(first >> 8) & 0xffffffu, (uint32_t)(sum % P), (uint32_t)std::min<uint64_t>(members, 0xffffffffull),
+                             (uint32_t)n_values, {0, 0, 0, 0, 0, 0, 0, 0}};
+  memcpy(e.values, values, sizeof e.values);
+  return e;
+}
 }  // namespace r0h
 
 struct r0h_session_balance {
@@ -174,7 +201,7 @@ struct r0h_session_balance {
 };
 
 namespace r0h {
-// logup.hip.  `keys` are the tuples' balance_key, `numerators` / `values` ([n][n_ids]) canonical; `report` returns the `capacity`
+// balance.hip.  `keys` are the tuples' balance_key, `numerators` / `values` ([n][n_ids]) canonical; `report` returns the `capacity`
 // lowest imbalanced classes in order and counts all of them
 const char* session_table_add_list(r0h_session_balance* sb, uint32_t source, const uint64_t* keys, const uint32_t* numerators, const uint32_t* values, size_t n);
 const char* session_table_report(r0h_session_balance* sb, r0h_session_imbalance* out, size_t capacity, size_t* n_out);

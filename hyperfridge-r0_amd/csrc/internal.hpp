@@ -86,7 +86,7 @@ struct Profile {
 struct r0h_ctx {
   int device = 0;
   int refs = 1;  // the handle itself + every live buffer / circuit: teardown happens when the last one goes
-  int n_cu = 0;  // the device's compute units, asked once by whoever sizes a persistent grid (logup.hip)
+  int n_cu = 0;  // the device's compute units, asked once by whoever sizes a persistent grid (logup_tape.hpp cu_count)
 
   hipStream_t stream = nullptr;
   // twiddles: tw_lo[d][i] = w^i, tw_hi[d][i] = w^(i*2^11) with w = ROU_{FWD,REV}[22]; d = 0 forward, 1 inverse

@@ -26,11 +26,11 @@ CODE_COLS = [(0, 0), (1, 0), (3, 7)]
 
 
 class Circuit:
-    def __init__(self, fractions, n_data, n_global=0):
+    def __init__(self, fractions, n_data, n_global=0, n_mix=8):
         fractions = list(fractions)
         while len(fractions) % 4:
             fractions.append(Fraction("nothing", LF(), [(A, ONE)]))   # a numerator of zero: never a tuple
-        self.fractions, self.n_data, self.n_global, self.n_mix = fractions, n_data, n_global, 8
+        self.fractions, self.n_data, self.n_global, self.n_mix = fractions, n_data, n_global, n_mix
         self.accs = [(fractions[i:i + 4], None) for i in range(0, len(fractions), 4)]
         self.words = self._blob()
 
@@ -61,6 +61,12 @@ def pair(parts_of, cols_p, cols_c, num_p=ONE, num_c=-ONE):
 
 def two(a0, a1):
     return [(A, ONE), (("one",), -col(a0)), (B, -col(a1))]
+
+
+def five(first):
+    """a pair's denominator spread over the five mix challenges from `first` on and over "one": six identities"""
+    m = [("mix", first + k) for k in range(5)]
+    return lambda a0, a1: [(m[0], ONE), (("one",), -col(a0)), (m[1], -col(a1)), (m[2], -col(a0)), (m[3], -col(a1)), (m[4], -col(a0))]
 
 
 def _values(rng, n):
@@ -116,10 +122,24 @@ def scenario(name, po2, seed=0):
         m[0], m[1] = 7, 7
         if name == "surplus":
             m[2, n - 3] = 1
+    elif name == "many identities":   # two pairs under five mix challenges each: eleven identities with "one", more than a session's eight
+        c = Circuit(pair(five(0), (0, 1), (2, 3)) + pair(five(5), (4, 5), (6, 7)), 8, n_mix=40)
+        m = np.zeros((8, n), dtype=np.int64)
+        other = rng.permutation(n)
+        m[0], m[1], m[4], m[5] = _values(rng, n), rows, _values(rng, n), rows
+        m[2], m[3], m[6], m[7] = m[0][perm], m[1][perm], m[4][other], m[5][other]
     else:
         raise KeyError(name)
     return c, ref.enc(m).reshape(-1), glob[:c.n_global]
 
 
-SCENARIOS = ("permutation", "order", "zero part", "weights", "minus ones", "own class", "hot", "surplus")
-BALANCED = ("permutation", "order", "zero part", "weights", "minus ones", "hot")
+def altered(data, po2, column, row):
+    """the witness with one cell changed (by one)"""
+    bad = data.copy()
+    at = (column << po2) + row
+    bad[at] = ref.enc((int(ref.dec(bad[at])) + 1) % P)
+    return bad
+
+
+SCENARIOS = ("permutation", "order", "zero part", "weights", "minus ones", "own class", "hot", "surplus", "many identities")
+BALANCED = ("permutation", "order", "zero part", "weights", "minus ones", "hot", "many identities")

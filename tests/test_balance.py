@@ -56,6 +56,20 @@ def test_host_equals_the_reference_on_tuple_circuits(name, po2):
         assert host(c.words, po2, None, bad, glob) == want
 
 
+@pytest.mark.parametrize("po2", [4, 9])
+def test_more_identities_than_a_session_has_room_for(po2):
+    """eleven challenge identities under the chain: the host's walk has no limit of eight"""
+    c, data, glob = bc.scenario("many identities", po2)
+    assert len({(kind, idx if kind else 0) for _, f in br.chain_fractions(ref.parse(c.words)) for kind, idx, _ in f["parts"]}) == 11
+    assert br.check(c.words, po2, None, data, glob) == []
+    n = 1 << po2
+    for column, row in ((6, n // 2), (0, n - 1)):   # a consumed value of the second pair, a produced one of the first
+        bad = bc.altered(data, po2, column, row)
+        want = br.check(c.words, po2, None, bad, glob)
+        assert len(want) == 2 and sorted(net for _, _, net, _ in want) == [1, P - 1] and row in [r for _, r, _, _ in want]
+        assert host(c.words, po2, None, bad, glob) == want
+
+
 @pytest.mark.parametrize("tables", [[1], [1, 2]])
 def test_host_equals_the_reference_on_generated_lookup_circuits(orc, tables):
     c = lc.generate(7, tables=tables, n_chain=3, n_public=1)

@@ -62,7 +62,7 @@ def test_a_permutation_balances_and_one_altered_cell_does_not(hal, po2):
     gc.free()
 
 
-@pytest.mark.parametrize("name", ["order", "zero part", "weights", "minus ones", "hot", "surplus"])
+@pytest.mark.parametrize("name", ["order", "zero part", "weights", "minus ones", "hot", "surplus", "many identities"])
 def test_kernel_paths_on_tuple_circuits(hal, name):
     po2 = 12
     c, data, glob = bc.scenario(name, po2)
@@ -75,6 +75,9 @@ def test_kernel_paths_on_tuple_circuits(hal, name):
         bad = data.copy()
         bad[4 << po2] = ref.enc((int(ref.dec(bad[4 << po2])) + 1) % P)   # one half of a split coordinate, row 0
         assert len(three_ways(hal, gc, po2, None, bad, glob)) == 2
+    if name == "many identities":  # eleven challenge identities; one consumed value of the second pair altered
+        want = three_ways(hal, gc, po2, None, bc.altered(data, po2, 6, 1 << (po2 - 1)), glob, capacity=1)
+        assert len(want) == 2 and sorted(net for _, _, net, _ in want) == [1, P - 1]
     gc.free()
 
 

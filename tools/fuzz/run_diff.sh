@@ -26,7 +26,6 @@ cat > "$WORK/stubs.cpp" <<'STUB'
 struct r0h_ctx; struct r0h_buf;
 struct r0h_circuit;
 namespace r0h { const char* ntt_init_device() { return nullptr; } void session_rows_free(r0h_ctx*) {}
-const char* logup_accum(r0h_ctx*, const r0h_circuit*, uint32_t, const r0h_buf*, const r0h_buf*, const uint32_t*, const uint32_t*, r0h_buf*) { __builtin_trap(); }
 const char* witgen_code(r0h_ctx*, const r0h_circuit*, uint32_t, r0h_buf*) { __builtin_trap(); }
 const char* sponge_plant(r0h_ctx*, const r0h_circuit*, uint32_t, const uint32_t*, size_t, r0h_buf*) { __builtin_trap(); } }
 extern "C" const char* r0h_prefix_products(r0h_ctx*, r0h_buf*, uint32_t) { __builtin_trap(); }
