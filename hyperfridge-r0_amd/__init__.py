@@ -215,6 +215,13 @@ _SIGNATURES = {
     "r0h_node_seal": [_vp, _pp, _c.POINTER(_sz)],
     "r0h_node_claim": [_vp, _vp],
     "r0h_node_verify": [_vp, _sz, _vp, _vp, _c.POINTER(_c.c_int)],
+    "r0h_node_session": [_vp, _pp, _c.POINTER(_sz)],
+    "r0h_node_new_with_session": [_vp, _sz, _vp, _vp, _sz, _pp],
+    "r0h_trace_seal_session_part": [_vp, _sz, _vp, _sz, _vp],
+    "r0h_compress": [_vp, _vp, _u32, _pp],
+    "r0h_root_verify_session_elf": [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _c.POINTER(_c.c_int), _c.POINTER(_sz)],
+    "r0h_root_verify_session_image": [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _c.POINTER(_c.c_int), _c.POINTER(_sz)],
+    "r0h_sponge_trace_device": [_vp, _vp, _sz, _u32, _vp],
     "r0h_kernel_timing": [_vp, _c.c_int],
     "r0h_kernel_stats": [_vp, _vp, _sz],
     "r0h_last_profile": [_vp, _c.POINTER(_c.POINTER(_cp)), _c.POINTER(_c.POINTER(_c.c_float)), _c.POINTER(_u32)],
@@ -674,6 +681,19 @@ def sponge_trace(words, po2):
     a, pa = _u32arr(words)
     out = np.zeros((SPONGE_DATA_COLUMNS, 1 << po2), dtype=np.uint32)
     _check(lib().r0h_sponge_trace(pa, a.size, po2, out.ctypes.data_as(_vp)))
+    return out
+
+
+NODE_SESSION_WORDS = 48  # R0H_NODE_SESSION_WORDS: early public inputs [0, 20), DATA root [20, 28), challenge [28, 44), sum [44, 48)
+
+
+def trace_seal_session_part(blob, seal):
+    """What a trace-circuit segment seal contributes to a root's session part (r0h_trace_seal_session_part: the extraction r0h_lift
+    makes; host only, the seal is verified on the way): NODE_SESSION_WORDS words."""
+    b, pb = _u32arr(blob)
+    a, pa = _u32arr(seal)
+    out = np.zeros(NODE_SESSION_WORDS, dtype=np.uint32)
+    _check(lib().r0h_trace_seal_session_part(pb, b.size, pa, a.size, out.ctypes.data_as(_vp)))
     return out
 
 
@@ -1711,6 +1731,18 @@ class Hal:
 
     def proof_abort(self, proof):
         _check(lib().r0h_proof_abort(proof))
+
+    def sponge_trace_device(self, words, po2, out=None):
+        """sponge_trace made on the device (r0h_sponge_trace_device: host chain, sponge_rows_kernel): [65][2^po2] read back.  `out`: a
+        Buf of 65 * 2^po2 words to write into (one is allocated otherwise); every word of it is written."""
+        a, pa = _u32arr(np.asarray(words, dtype=np.uint32))
+        buf = out if out is not None else self.alloc(SPONGE_DATA_COLUMNS << po2)
+        try:
+            _check(lib().r0h_sponge_trace_device(self.ctx, pa, a.size, po2, buf.handle))
+            return buf.to_host(0, SPONGE_DATA_COLUMNS << po2).reshape(SPONGE_DATA_COLUMNS, 1 << po2)
+        finally:
+            if out is None:
+                buf.free()
 
     def kernel_timing(self, enable=True):
         _check(lib().r0h_kernel_timing(self.ctx, 1 if enable else 0))

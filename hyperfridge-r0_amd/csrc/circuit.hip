@@ -166,23 +166,6 @@ const char* r0h_circuit_load_check(r0h_circuit* c, const char* code_object_path)
 
 }  // extern "C"
 namespace r0h {
-const char* sponge_plant(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const uint32_t* words, size_t n_words, r0h_buf* data) {
-  R0H_REQUIRE(ctx && c && data && c->has_sponge && (words || !n_words), "sponge_plant: NULL argument, or a circuit without the sponge component");
-  const size_t n = (size_t)1 << po2, n_perm = n_words ? (n_words + P2_RATE - 1) / P2_RATE : 1, rows = n_perm * R0H_SPONGE_PERIOD;
-  R0H_REQUIRE(rows < n, "the in-circuit sponge over %zu words takes %zu rows: the recursion trace has 2^%u", n_words, rows, po2);
-  R0H_REQUIRE(((size_t)c->group_size[R0H_GROUP_DATA] << po2) * 4 <= data->bytes, "sponge_plant: DATA buffer too small for 2^%u rows", po2);
-  for (size_t i = 0; i < n_words; i++) R0H_REQUIRE(words[i] < P, "sponge_plant: word %zu is not a canonical field element", i);
-  std::vector<uint32_t> cols((size_t)R0H_SPONGE_DATA_COLUMNS * rows);
-  size_t used = 0;
-  p2_sponge_rows_host(p2_default(), words, n_words, cols.data(), rows, &used);
-  uint32_t* first = u32(data) + ((size_t)c->sponge_data << po2);
-  R0H_TRY_HIP(hipMemsetAsync(first, 0, (size_t)R0H_SPONGE_DATA_COLUMNS * n * 4, ctx->stream));
-  R0H_TRY_HIP(hipMemcpy2DAsync(first, n * 4, cols.data(), rows * 4, rows * 4, R0H_SPONGE_DATA_COLUMNS, hipMemcpyHostToDevice, ctx->stream));
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // `cols` is pageable and goes out of scope
-  return nullptr;
-}
-}  // namespace r0h
-namespace r0h {
 // one launch of witgen_fixed_kernel over the columns `kinds` describes; the parameter block (kinds, then the PERIODIC section in
 // Montgomery form) goes through the context's scratch, in stream order behind whatever read it last
 static const char* witgen_fixed(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, std::vector<uint32_t>& kinds, uint64_t seed_mixed, r0h_buf* buf) {

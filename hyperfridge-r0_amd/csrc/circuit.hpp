@@ -124,8 +124,14 @@ const char* parse_blob(r0h_circuit* c, const uint32_t* blob, size_t n_words);
 void make_plan(r0h_circuit* c);
 std::string emit_source(const r0h_circuit* c);
 std::string emit_check_source(const r0h_circuit* c);
-// the rows of the in-circuit sponge over `words` written into the circuit's sponge columns of `data` (recursion.cpp: sponge_plant)
+// the rows of the in-circuit sponge over `words` written into the circuit's sponge columns of `data`, zero behind the last permutation
+// (sponge.hip: the host runs the chain, sponge_rows_kernel expands the rows; stream-ordered)
 const char* sponge_plant(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const uint32_t* words, size_t n_words, r0h_buf* data);
+// the same for a caller that has run the chain already (p2_sponge_chain_host: r0h_lift / r0h_join need its digest anyway): the
+// 24 words each of the n_perm permutations starts from; the host words may be released on return
+const char* sponge_plant_states(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const uint32_t* states, size_t n_perm, r0h_buf* data);
+// what r0h_sponge_trace and r0h_sponge_trace_device refuse, in the same words (verify.cpp); *n_perm_out: the permutations the words take
+const char* sponge_trace_args(const char* caller, const uint32_t* words, size_t n_words, uint32_t po2, size_t* n_perm_out);
 // r0h_check_witness with the first violated term turned into an error that starts with `caller` (the sequencer under
 // r0h_ctx_set_check_witness); global / mix are host words as r0h_eval_check takes them
 const char* require_witness(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,

@@ -169,6 +169,93 @@ void session_challenge(const uint32_t* records, size_t n_records, uint32_t out[1
   memcpy(out + 12, g3.e, 16);
 }
 
+
+void session_part_of(const uint32_t* seal, const uint32_t data_root[8], uint32_t part_out[R0H_NODE_SESSION_WORDS]) {
+  constexpr size_t early = R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS;
+  static_assert(early + 8 == R0H_SESSION_RECORD_WORDS && R0H_SESSION_RECORD_WORDS + 16 + 4 == R0H_NODE_SESSION_WORDS, "session part layout");
+  memcpy(part_out, seal, early * 4);
+  memcpy(part_out + early, data_root, 32);
+  memcpy(part_out + R0H_SESSION_RECORD_WORDS, seal + R0H_TRACE_GAMMA, 64);
+  memcpy(part_out + R0H_SESSION_RECORD_WORDS + 16, seal + R0H_TRACE_SUM, 16);
+}
+
+int session_verdict(const std::vector<SessionLeaf>& leaves, size_t term, const SessionOtherSide* other, size_t* leaf_out) {
+  constexpr size_t early = R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS;
+  const size_t n = leaves.size();
+  auto done = [&](int v, size_t leaf) { *leaf_out = leaf; return v; };
+  // ---- the session: numbers, closing segments, the common challenge
+  std::vector<uint32_t> records(n * R0H_SESSION_RECORD_WORDS);
+  for (size_t i = 0; i < n; i++) {
+    memcpy(&records[i * R0H_SESSION_RECORD_WORDS], leaves[i].early, early * 4);
+    memcpy(&records[i * R0H_SESSION_RECORD_WORDS + early], leaves[i].data_root, 32);
+  }
+  uint32_t challenge[16];
+  session_challenge(records.data(), n, challenge);
+  bool closing_seen = false;
+  uint32_t closed_up_to = 0;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t* sl = leaves[i].early;
+    const uint32_t fin = sl[16];
+    if (sl[15] != enc((uint32_t)i + 1) || (fin != 0 && fin != ONE) || sl[17] != (fin ? 0u : sl[15])) return done(R0H_RECEIPT_V_SESSION, i);
+    if (memcmp(leaves[i].challenge, challenge, 64) != 0) return done(R0H_RECEIPT_V_SESSION, i);
+    // closing segments: the one that ends the run when it is the last, else every segment after it; their rows go up through the addresses
+    const bool must_close = term == n - 1 ? i == term : i > term;
+    if ((fin != 0) != must_close) return done(R0H_RECEIPT_V_SESSION, i);
+    if (fin) {
+      const uint32_t lo = dec(sl[18]), hi = dec(sl[19]);
+      if (closing_seen && lo <= closed_up_to) return done(R0H_RECEIPT_V_SESSION, i);
+      if (hi < lo) return done(R0H_RECEIPT_V_SESSION, i);
+      closing_seen = true;
+      closed_up_to = hi;
+    }
+  }
+  if (!other) return done(R0H_RECEIPT_V_OK, 0);
+  const uint32_t* image_public = other->image_public;
+  const std::vector<std::pair<uint32_t, uint32_t>>* image = other->image;
+  if (image_public) {  // the image's side comes from the image proof: it must be about THIS image (the digest in the first claim's pre-state,
+    // which is held against the image id by the caller) and under THIS session's challenge
+    const uint8_t* root = other->first_root;
+    for (int i = 0; i < 8; i++) {
+      const uint32_t w = (uint32_t)root[4 * i] | (uint32_t)root[4 * i + 1] << 8 | (uint32_t)root[4 * i + 2] << 16 | (uint32_t)root[4 * i + 3] << 24;
+      if (w >= P || image_public[i] != enc(w)) return done(R0H_RECEIPT_V_IMAGE_PROOF, 0);
+    }
+    if (memcmp(&image_public[R0H_IMAGE_GAMMA], challenge, 64) != 0) return done(R0H_RECEIPT_V_IMAGE_PROOF, 0);
+  }
+  // ---- the balance: sum of the segments' sums = sum over the image's words + sum over the journal's words of 1 / fingerprint
+  const Fp4 ag{{challenge[0], challenge[1], challenge[2], challenge[3]}}, g1{{challenge[4], challenge[5], challenge[6], challenge[7]}},
+      g2{{challenge[8], challenge[9], challenge[10], challenge[11]}}, g3{{challenge[12], challenge[13], challenge[14], challenge[15]}};
+  Fp4 total = fp4_zero();
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t* q = leaves[i].sum;
+    total = total + Fp4{{q[0], q[1], q[2], q[3]}};
+  }
+  // batched inversion: the fingerprints are multiplied up, one inversion, and walked back
+  std::vector<Fp4> fps;
+  fps.reserve((image ? image->size() : 0) + other->journal_len / 4);
+  auto fingerprint = [&](uint32_t addr, uint32_t word, uint32_t tag) {
+    Fp4 f = ag - scale(g1, enc(word & 0xffffu)) - scale(g2, enc(word >> 16)) - scale(g3, enc(tag));
+    f.e[0] = sub(f.e[0], enc(addr));
+    fps.push_back(f);
+  };
+  if (image)
+    for (const auto& w : *image) fingerprint(w.first, w.second, R0H_SESSION_TAG_IMAGE);
+  if (other->journal_len % 4) return done(R0H_RECEIPT_V_JOURNAL, term);  // COMMIT moves words
+  for (size_t j = 0; j < other->journal_len / 4; j++) {
+    const uint8_t* b = &other->journal[4 * j];
+    fingerprint(R0H_JOURNAL_BASE / 4 + (uint32_t)j, (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24, R0H_SESSION_TAG_JOURNAL);
+  }
+  std::vector<Fp4> prefix(fps.size() + 1, fp4_one());
+  for (size_t k = 0; k < fps.size(); k++) prefix[k + 1] = prefix[k] * fps[k];
+  Fp4 inv_run = fp4_inv(prefix[fps.size()]), rest = fp4_zero();
+  for (size_t k = fps.size(); k-- > 0;) {
+    rest = rest + inv_run * prefix[k];
+    inv_run = inv_run * fps[k];
+  }
+  if (!image) rest = rest + Fp4{{image_public[R0H_IMAGE_SUM], image_public[R0H_IMAGE_SUM + 1], image_public[R0H_IMAGE_SUM + 2], image_public[R0H_IMAGE_SUM + 3]}};
+  if (!(total == rest)) return done(R0H_RECEIPT_V_SESSION_SUM, 0);
+  return done(R0H_RECEIPT_V_OK, 0);
+}
+
 }  // namespace r0h
 
 using namespace r0h;
@@ -350,75 +437,24 @@ static const char* receipt_verify_impl(const r0h_receipt* rc, const uint32_t* bl
   uint8_t out[32];
   R0H_TRY(r0h_output_digest(rc->journal.data(), rc->journal.size(), nullptr, out));
   if (memcmp(out, last.output_digest, 32) != 0) return done(R0H_RECEIPT_V_JOURNAL, term);
-  if (trace_circuit) {
-    // ---- the session: numbers, closing segments, the common challenge
-    uint32_t challenge[16];
-    session_challenge(records.data(), n, challenge);
-    bool closing_seen = false;
-    uint32_t closed_up_to = 0;
+  if (trace_circuit) {  // the session (session_verdict): numbers, closing segments, the common challenge; then the balance
+    std::vector<SessionLeaf> leaves(n);
     for (size_t i = 0; i < n; i++) {
-      const std::vector<uint32_t>& sl = rc->segments[i].seal;
-      const uint32_t fin = sl[16];
-      if (sl[15] != enc((uint32_t)i + 1) || (fin != 0 && fin != ONE) || sl[17] != (fin ? 0u : sl[15])) return done(R0H_RECEIPT_V_SESSION, i);
-      if (memcmp(&sl[R0H_TRACE_GAMMA], challenge, 64) != 0) return done(R0H_RECEIPT_V_SESSION, i);
-      // closing segments: the one that ends the run when it is the last, else every segment after it; their rows go up through the addresses
-      const bool must_close = term == n - 1 ? i == term : i > term;
-      if ((fin != 0) != must_close) return done(R0H_RECEIPT_V_SESSION, i);
-      if (fin) {
-        const uint32_t lo = dec(sl[18]), hi = dec(sl[19]);
-        if (closing_seen && lo <= closed_up_to) return done(R0H_RECEIPT_V_SESSION, i);
-        if (hi < lo) return done(R0H_RECEIPT_V_SESSION, i);
-        closing_seen = true;
-        closed_up_to = hi;
-      }
+      const uint32_t* sl = rc->segments[i].seal.data();
+      leaves[i] = SessionLeaf{sl, &records[i * R0H_SESSION_RECORD_WORDS + (R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS)], sl + R0H_TRACE_GAMMA, sl + R0H_TRACE_SUM};
     }
-    if (image_public) {  // the image's side comes from the image proof: it must be about THIS image (the digest in the first claim's pre-state,
-      // which is held against the image id below) and under THIS session's challenge
-      const uint8_t* root = rc->segments[0].claim.pre.merkle_root;
-      for (int i = 0; i < 8; i++) {
-        const uint32_t w = (uint32_t)root[4 * i] | (uint32_t)root[4 * i + 1] << 8 | (uint32_t)root[4 * i + 2] << 16 | (uint32_t)root[4 * i + 3] << 24;
-        if (w >= P || image_public[i] != enc(w)) return done(R0H_RECEIPT_V_IMAGE_PROOF, 0);
-      }
-      if (memcmp(&image_public[R0H_IMAGE_GAMMA], challenge, 64) != 0) return done(R0H_RECEIPT_V_IMAGE_PROOF, 0);
-    } else if (!image) {
+    const SessionOtherSide other{image, image_public, rc->segments[0].claim.pre.merkle_root, rc->journal.data(), rc->journal.size()};
+    const bool balanced = image_public || image;  // with neither, nothing can stand for the image's side: the ELF-free checks, then the image id
+    size_t leaf = 0;
+    const int v = session_verdict(leaves, term, balanced ? &other : nullptr, &leaf);
+    if (v != R0H_RECEIPT_V_OK) return done(v, leaf);
+    if (!balanced) {
       if (!image_id) return done(R0H_RECEIPT_V_UNBOUND, 0);
       uint8_t pre[32];
       system_state_digest(rc->segments[0].claim.pre, pre);
       if (memcmp(pre, image_id, 32) != 0) return done(R0H_RECEIPT_V_IMAGE_ID, 0);
       return done(R0H_RECEIPT_V_NEEDS_IMAGE, 0);
     }
-    // ---- the balance: sum of the segments' sums = sum over the image's words + sum over the journal's words of 1 / fingerprint
-    const Fp4 ag{{challenge[0], challenge[1], challenge[2], challenge[3]}}, g1{{challenge[4], challenge[5], challenge[6], challenge[7]}},
-        g2{{challenge[8], challenge[9], challenge[10], challenge[11]}}, g3{{challenge[12], challenge[13], challenge[14], challenge[15]}};
-    Fp4 total = fp4_zero();
-    for (size_t i = 0; i < n; i++) {
-      const uint32_t* q = &rc->segments[i].seal[R0H_TRACE_SUM];
-      total = total + Fp4{{q[0], q[1], q[2], q[3]}};
-    }
-    // batched inversion: the fingerprints are multiplied up, one inversion, and walked back
-    std::vector<Fp4> fps;
-    fps.reserve((image ? image->size() : 0) + rc->journal.size() / 4);
-    auto fingerprint = [&](uint32_t addr, uint32_t word, uint32_t tag) {
-      Fp4 f = ag - scale(g1, enc(word & 0xffffu)) - scale(g2, enc(word >> 16)) - scale(g3, enc(tag));
-      f.e[0] = sub(f.e[0], enc(addr));
-      fps.push_back(f);
-    };
-    if (image)
-      for (const auto& w : *image) fingerprint(w.first, w.second, R0H_SESSION_TAG_IMAGE);
-    if (rc->journal.size() % 4) return done(R0H_RECEIPT_V_JOURNAL, term);  // COMMIT moves words
-    for (size_t j = 0; j < rc->journal.size() / 4; j++) {
-      const uint8_t* b = &rc->journal[4 * j];
-      fingerprint(R0H_JOURNAL_BASE / 4 + (uint32_t)j, (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24, R0H_SESSION_TAG_JOURNAL);
-    }
-    std::vector<Fp4> prefix(fps.size() + 1, fp4_one());
-    for (size_t k = 0; k < fps.size(); k++) prefix[k + 1] = prefix[k] * fps[k];
-    Fp4 inv_run = fp4_inv(prefix[fps.size()]), other = fp4_zero();
-    for (size_t k = fps.size(); k-- > 0;) {
-      other = other + inv_run * prefix[k];
-      inv_run = inv_run * fps[k];
-    }
-    if (!image) other = other + Fp4{{image_public[R0H_IMAGE_SUM], image_public[R0H_IMAGE_SUM + 1], image_public[R0H_IMAGE_SUM + 2], image_public[R0H_IMAGE_SUM + 3]}};
-    if (!(total == other)) return done(R0H_RECEIPT_V_SESSION_SUM, 0);
   }
   if (!image_id) return done(R0H_RECEIPT_V_UNBOUND, 0);  // `receipt.verify(image_id)` always names the program: without it this is not OK
   uint8_t pre[32];
@@ -477,6 +513,113 @@ const char* r0h_receipt_verify_elf(const r0h_receipt* rc, const uint32_t* blob, 
   uint8_t image_id[32];
   R0H_TRY(elf_image(elf, elf_len, image, &entry, image_id));
   return receipt_verify_impl(rc, blob, blob_words, control_roots, n_roots, image_id, &image, verdict_out, segment_out, seal_verdict_out);
+  R0H_GUARD_END
+}
+
+// ---- a root of the lift / join tree held to what r0h_receipt_verify_elf / _image hold a receipt to, from the session parts its leaves
+// left in it (recursion.cpp: r0h_lift takes them from the seal it verified).  Pure host code; no seal is read.
+const char* r0h_trace_seal_session_part(const uint32_t* blob, size_t blob_words, const uint32_t* seal, size_t seal_words, uint32_t part_out[R0H_NODE_SESSION_WORDS]) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(blob && seal && part_out, "r0h_trace_seal_session_part: NULL argument");
+  r0h_circuit circ;
+  R0H_TRY(parse_blob(&circ, blob, blob_words));
+  R0H_REQUIRE(is_trace_circuit(circ), "r0h_trace_seal_session_part: the blob is not the trace circuit (circuits/trace.r0c): only its seals carry a session");
+  int sv = -1;
+  uint32_t data_root[8];
+  R0H_TRY(r0h_verify_seal_roots(blob, blob_words, seal, seal_words, nullptr, &sv, nullptr, data_root));
+  R0H_REQUIRE(sv == R0H_VERIFY_OK, "r0h_trace_seal_session_part: the seal does not verify: %s", r0h_verify_reason(sv));
+  session_part_of(seal, data_root, part_out);
+  return nullptr;
+  R0H_GUARD_END
+}
+
+static const char* root_verify_session_impl(const char* caller, const uint32_t* blob, size_t blob_words, const r0h_node* node, const uint8_t* journal, size_t journal_len,
+                                            const uint8_t* image_id, const std::vector<std::pair<uint32_t, uint32_t>>* image, const uint32_t* image_public,
+                                            int* verdict_out, size_t* leaf_out) {
+  R0H_REQUIRE(blob && node && (journal || !journal_len) && verdict_out && image_id, "%s: NULL argument", caller);
+  if (leaf_out) *leaf_out = 0;
+  auto done = [&](int v, size_t leaf) { *verdict_out = v; if (leaf_out) *leaf_out = leaf; return (const char*)nullptr; };
+  r0h_circuit circ;
+  R0H_TRY(parse_blob(&circ, blob, blob_words));
+  R0H_REQUIRE(is_trace_circuit(circ), "%s: the blob is not the trace circuit (circuits/trace.r0c): only its sessions are bound this way", caller);
+  R0H_REQUIRE(!node->session.empty() && node->session.size() % R0H_NODE_SESSION_WORDS == 0,
+              "%s: the node carries no session part (a leaf below it is no trace-circuit segment, or it arrived without one: r0h_node_new)", caller);
+  const size_t n = node->session.size() / R0H_NODE_SESSION_WORDS;
+  // a segment's number is a coordinate of its session tuples, and R0H_SESSION_TAG_IMAGE / _JOURNAL sit in the same slot at 2^20 + 1, + 2
+  R0H_REQUIRE(n < ((size_t)1 << 20), "%s: %zu leaves: a session has fewer than 2^20 segments (their numbers share a field slot with R0H_SESSION_TAG_IMAGE)", caller, n);
+  for (size_t i = 0; i < node->session.size(); i++)
+    R0H_REQUIRE(node->session[i] < P, "%s: word %zu of leaf %zu's session part is not a canonical field word", caller, i % R0H_NODE_SESSION_WORDS, i / R0H_NODE_SESSION_WORDS);
+  std::vector<SessionLeaf> leaves(n);
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t* w = &node->session[i * R0H_NODE_SESSION_WORDS];
+    leaves[i] = SessionLeaf{w, w + (R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS), w + R0H_SESSION_RECORD_WORDS, w + R0H_SESSION_RECORD_WORDS + 16};
+  }
+  const r0h_receipt_claim& claim = node->claim;
+  // the leaves chain: the run starts at the claim's first pc, every leaf starts where its predecessor stopped
+  for (size_t i = 0; i < n; i++)
+    if (leaves[i].early[8] != (i ? leaves[i - 1].early[9] : enc(claim.pre.pc))) return done(R0H_RECEIPT_V_CHAIN, i);
+  // the leaf that ends the run: the first that ends in HALT / PAUSE; it carries the claim's way of ending, exit code and last pc; what
+  // follows it has no cycles and stands where the run stopped
+  size_t term = n - 1;
+  for (size_t i = 0; i < n; i++)
+    if (leaves[i].early[11] != 0) { term = i; break; }
+  {
+    const uint32_t* e = leaves[term].early;
+    const uint32_t kind = claim.exit_system == 0 ? 1u : claim.exit_system == 1 ? 2u : 0u, code = kind ? claim.exit_user : 0u;
+    if (e[9] != enc(claim.post.pc) || e[11] != enc(kind) || e[12] != enc(kind ? 1u : 0u) || e[13] != enc(code & 0xffffu) || e[14] != enc(code >> 16))
+      return done(R0H_RECEIPT_V_CLAIM_MISMATCH, term);
+  }
+  for (size_t i = term + 1; i < n; i++)
+    if (leaves[i].early[10] != 0 || leaves[i].early[11] != 0 || leaves[i].early[8] != leaves[i].early[9]) return done(R0H_RECEIPT_V_CHAIN, i);
+  if (!(claim.exit_system <= 1 && claim.exit_user == 0)) return done(R0H_RECEIPT_V_EXIT_CODE, term);
+  uint8_t out[32];
+  R0H_TRY(r0h_output_digest(journal, journal_len, nullptr, out));
+  if (memcmp(out, claim.output_digest, 32) != 0) return done(R0H_RECEIPT_V_JOURNAL, term);
+  // the program: the claim's pre-state is the image id -- before the session section, so that another program's ELF is told apart by
+  // its id (r0h_receipt_verify_elf reaches the balance first and says R0H_RECEIPT_V_SESSION_SUM for it)
+  uint8_t pre[32];
+  system_state_digest(claim.pre, pre);
+  if (memcmp(pre, image_id, 32) != 0) return done(R0H_RECEIPT_V_IMAGE_ID, 0);
+  const SessionOtherSide other{image, image_public, claim.pre.merkle_root, journal, journal_len};
+  size_t leaf = 0;
+  const int v = session_verdict(leaves, term, &other, &leaf);
+  return done(v, leaf);
+}
+
+const char* r0h_root_verify_session_elf(const uint32_t* blob, size_t blob_words, const r0h_node* node, const uint8_t* journal, size_t journal_len, const uint8_t* elf,
+                                        size_t elf_len, int* verdict_out, size_t* leaf_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(elf, "r0h_root_verify_session_elf: NULL argument");
+  std::vector<std::pair<uint32_t, uint32_t>> image;
+  uint32_t entry = 0;
+  uint8_t image_id[32];
+  R0H_TRY(elf_image(elf, elf_len, image, &entry, image_id));
+  return root_verify_session_impl("r0h_root_verify_session_elf", blob, blob_words, node, journal, journal_len, image_id, &image, nullptr, verdict_out, leaf_out);
+  R0H_GUARD_END
+}
+
+const char* r0h_root_verify_session_image(const uint32_t* blob, size_t blob_words, const r0h_node* node, const uint8_t* journal, size_t journal_len,
+                                          const uint32_t* image_blob, size_t image_blob_words, const uint32_t* image_control_root, const uint32_t* image_seal,
+                                          size_t image_seal_words, const uint8_t* image_id, int* verdict_out, size_t* leaf_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(blob && node && image_blob && image_id && verdict_out && (image_seal || !image_seal_words), "r0h_root_verify_session_image: NULL argument");
+  if (leaf_out) *leaf_out = 0;
+  r0h_circuit ic;
+  R0H_TRY(parse_blob(&ic, image_blob, image_blob_words));
+  R0H_REQUIRE(is_image_circuit(ic), "r0h_root_verify_session_image: the second blob is not the image circuit (circuits/image.r0c)");
+  if (image_seal_words <= R0H_IMAGE_GLOBALS) { *verdict_out = R0H_RECEIPT_V_IMAGE_PROOF; return nullptr; }
+  int sv = -1;
+  uint32_t po2 = 0, root[8];
+  if (!image_control_root) {  // a verifier with the blob derives the root of the size the seal names -- once the seal as such holds
+    R0H_TRY(r0h_verify_seal(image_blob, image_blob_words, nullptr, nullptr, image_seal, image_seal_words, &sv, &po2));
+    if (sv == R0H_VERIFY_OK) {
+      R0H_TRY(r0h_control_root_host(image_blob, image_blob_words, nullptr, nullptr, po2, root));
+      image_control_root = root;
+    }
+  }
+  if (image_control_root) R0H_TRY(r0h_verify_seal_bound(image_blob, image_blob_words, nullptr, nullptr, image_seal, image_seal_words, image_control_root, &sv, &po2, nullptr));
+  if (sv != R0H_VERIFY_OK) { *verdict_out = R0H_RECEIPT_V_IMAGE_PROOF; return nullptr; }
+  return root_verify_session_impl("r0h_root_verify_session_image", blob, blob_words, node, journal, journal_len, image_id, nullptr, image_seal, verdict_out, leaf_out);
   R0H_GUARD_END
 }
 

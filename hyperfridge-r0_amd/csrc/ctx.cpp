@@ -141,19 +141,21 @@ void p2_sponge_rows_host(const P2Consts& k, const uint32_t* words, size_t n_word
   }
   *rows_used = n_perm * ROWS;
 }
-void p2_hash_elems_host(const P2Consts& k, const uint32_t* elems, size_t n, uint32_t digest[8]) {
+// One pass of the sponge chain: the digest, and -- with `states` -- what every permutation starts from, 24 words each: the state after
+// the absorb and before the external layer.  A permutation's 30 rows (p2_sponge_rows_host) depend on nothing else, so whoever wants
+// the rows as well as the digest runs the sequential part once (r0h_lift / r0h_join: sponge_plant_states expands them on the device).
+void p2_sponge_chain_host(const P2Consts& k, const uint32_t* elems, size_t n, uint32_t digest[8], std::vector<uint32_t>* states) {
+  const size_t n_perm = n ? (n + P2_RATE - 1) / P2_RATE : 1;
+  if (states) states->resize(n_perm * P2_CELLS);
   uint32_t st[P2_CELLS] = {0};
-  size_t used = 0;
-  for (size_t i = 0; i < n; i++) {
-    st[used++] = elems[i];
-    if (used == P2_RATE) { p2_mix_host(k, st); used = 0; }
-  }
-  if (used != 0 || n == 0) {
-    for (size_t i = used; i < P2_RATE; i++) st[i] = 0;
+  for (size_t q = 0; q < n_perm; q++) {
+    for (size_t j = 0; j < P2_RATE; j++) st[j] = q * P2_RATE + j < n ? elems[q * P2_RATE + j] : 0u;  // the last block is zero-padded
+    if (states) memcpy(states->data() + q * P2_CELLS, st, sizeof st);
     p2_mix_host(k, st);
   }
   memcpy(digest, st, 32);
 }
+void p2_hash_elems_host(const P2Consts& k, const uint32_t* elems, size_t n, uint32_t digest[8]) { p2_sponge_chain_host(k, elems, n, digest, nullptr); }
 
 const char* ensure_scratch(r0h_ctx* ctx, size_t bytes) {
   if (ctx->scratch_bytes >= bytes) return nullptr;

@@ -6,10 +6,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <thread>
 #include <tuple>
 #include <vector>
 
@@ -224,6 +226,31 @@ void session_rows_free(r0h_ctx* ctx);  // session.cpp: unpins and frees the row 
 const char* ctx_helper(r0h_ctx* ctx, size_t k, r0h_ctx** out);
 void ctx_retain(r0h_ctx* ctx);
 void ctx_release(r0h_ctx* ctx);
+// Prover lanes (sessions: session.cpp; the lift / join tree: recursion.cpp).  Lane 0 on the calling thread, the others on threads of
+// their own; the first error is kept (and `on_error` told), later ones are freed; every thread has been joined when this returns.
+template <class Fn, class OnError>
+const char* run_lanes(const std::vector<r0h_ctx*>& lanes, Fn fn, OnError on_error) {
+  std::atomic<const char*> first(nullptr);
+  auto lane = [&](r0h_ctx* lctx) {
+    const char* err = nullptr;
+    try {
+      err = fn(lctx);
+    } catch (const std::exception& ex) {
+      err = make_error("exception in a prover lane: %s", ex.what());
+    } catch (...) {
+      err = make_error("unknown exception in a prover lane");
+    }
+    if (!err) return;
+    const char* none = nullptr;
+    if (!first.compare_exchange_strong(none, err)) r0h_free_error(err);
+    on_error();
+  };
+  std::vector<std::thread> workers;
+  for (size_t k = 1; k < lanes.size(); k++) workers.emplace_back(lane, lanes[k]);
+  lane(lanes[0]);
+  for (std::thread& t : workers) t.join();
+  return first;
+}
 // host Poseidon2 (transcript only): permutation over 24 Montgomery words with the context's table
 void p2_mix_host(const P2Consts& k, uint32_t* cells);
 // table from canonical round constants [29][24] and canonical (mu_i - 1) [24]; the compiled-in risc0 table, filled on first use
@@ -231,6 +258,8 @@ void fill_p2(P2Consts& k, const uint32_t* rc, const uint32_t* diag_m1);
 const P2Consts& p2_default();
 void p2_hash_elems_host(const P2Consts& k, const uint32_t* elems, size_t n, uint32_t digest[8]);
 void p2_sponge_rows_host(const P2Consts& k, const uint32_t* words, size_t n_words, uint32_t* cols, size_t stride, size_t* rows_used);
+// the digest of p2_hash_elems_host and (states != nullptr) the 24 words every permutation of the chain starts from, before its external layer
+void p2_sponge_chain_host(const P2Consts& k, const uint32_t* elems, size_t n, uint32_t digest[8], std::vector<uint32_t>* states);
 
 // ---- hash suites (risc0 `HashSuite`: the Merkle hash and the transcript's generator go together).  Two of them: Poseidon2 over
 // BabyBear words, and SHA-256 as recalled from risc0-zkp core/hash/sha (`Sha256HashSuite`, `Sha256Rng`) and risc0-sys sha256.h --

@@ -79,6 +79,8 @@ int main(int argc, char** argv) {
   if (argc < 2 || !strcmp(argv[1], "--help") || !strcmp(argv[1], "-h")) {
     printf("usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--hashfn poseidon2|sha-256] [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]\n"
            "       r0h_prove <trace.r0c> --elf guest.elf --input words.bin [--code-object file.hsaco] [--po2 N] [--device D] --receipt-out file.json\n"
+           "       ... --elf guest.elf --compress --recursion-circuit recursion.r0c [--recursion-code-object file.hsaco] [--recursion-po2 N] [--compress-lanes 1..4] --root-out root.bin: "
+           "the receipt's segments lifted and joined into one root (wire form) for r0h_verify --root\n"
            "       --check-witness 1 [--check-code-object file.hsaco] [--term-names file.txt]: check every segment's witness on the device before its ACCUM group is committed; "
            "a violated segment ends the run with the constraint term, its name, how many rows violate it and the first of them\n"
            "       --check-balance 1 [--fraction-names file.txt]: check that the log-derivative fractions of every segment's witness cancel before its DATA group is committed; "
@@ -88,6 +90,17 @@ int main(int argc, char** argv) {
            "and the class's values (single-rank sessions; a diagnostic, not a verifier)\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
+  // --compress takes no value: it is taken out of the arguments before the "--option value" pairs are read
+  bool compress = false;
+  for (int i = 2; i < argc; i++)
+    if (!strcmp(argv[i], "--compress")) {
+      compress = true;
+      for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
+      argc--;
+      i--;
+    }
+  std::string recursion_path, recursion_co_path, root_out;
+  unsigned recursion_po2 = 18, compress_lanes = 0;
   std::string blob_path = argv[1], co_path, seal_out, receipt_out, receipt_dir, journal_text, elf_path, input_path;
   std::string hashfn = "poseidon2";         // --hashfn: the hash suite of the synthetic-circuit mode (seals only)
   std::map<std::string, std::string> camt;  // --camt53-response and what goes with it
@@ -121,6 +134,11 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--receipt-prefix")) receipt_prefix = argv[i + 1];
     else if (!strcmp(argv[i], "--image-circuit")) image_circuit_path = argv[i + 1];        // circuits/image.r0c: the receipts carry an image proof
     else if (!strcmp(argv[i], "--image-code-object")) image_co_path = argv[i + 1];
+    else if (!strcmp(argv[i], "--recursion-circuit")) recursion_path = argv[i + 1];       // with --compress: circuits/recursion.r0c
+    else if (!strcmp(argv[i], "--recursion-code-object")) recursion_co_path = argv[i + 1];
+    else if (!strcmp(argv[i], "--recursion-po2")) recursion_po2 = (unsigned)atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--compress-lanes")) compress_lanes = (unsigned)atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--root-out")) root_out = argv[i + 1];
     else if (!strcmp(argv[i], "--camt53-response")) camt["response"] = argv[i + 1];  // the library's own camt53 guest fed from an EBICS response
     else if (!strcmp(argv[i], "--pub-bank") || !strcmp(argv[i], "--pub-client") || !strcmp(argv[i], "--pub-witness") || !strcmp(argv[i], "--tx-key-raw") ||
              !strcmp(argv[i], "--witness-hex") || !strcmp(argv[i], "--iban") || !strcmp(argv[i], "--hostinfo") || !strcmp(argv[i], "--form"))
@@ -128,6 +146,10 @@ int main(int argc, char** argv) {
     else { fprintf(stderr, "r0h_prove: unknown option %s\n", argv[i]); return 1; }
   }
   if ((argc - 2) % 2) { fprintf(stderr, "r0h_prove: option %s needs a value\n", argv[argc - 1]); return 1; }
+  if (compress && (elf_path.empty() || recursion_path.empty() || root_out.empty())) {
+    fprintf(stderr, "r0h_prove: --compress goes with --elf and needs --recursion-circuit and --root-out (and takes --recursion-code-object, --recursion-po2, --compress-lanes)\n");
+    return 1;
+  }
   if (hashfn != "poseidon2" && hashfn != "sha-256") { fprintf(stderr, "r0h_prove: --hashfn is poseidon2 or sha-256, not %s\n", hashfn.c_str()); return 1; }
   if (hashfn != "poseidon2" && (!elf_path.empty() || !receipt_out.empty() || !receipt_dir.empty() || !receipt_prefix.empty() || !camt.empty() || !image_circuit_path.empty())) {
     fprintf(stderr, "r0h_prove: --hashfn %s proves bare seals (--seal-out / --verify); receipts name poseidon2 only, so it does not go with --elf, --receipt-out, "
@@ -325,6 +347,39 @@ int main(int argc, char** argv) {
     }
     const double verify_secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - v0).count();
     if (refused) return 3;
+    // --compress: the first receipt lifted and joined into one root (r0h_compress), written in wire form -- claim words,
+    // [n_leaves, seal_words], seal, session words -- for `r0h_verify --root`
+    double compress_secs = 0;
+    size_t root_leaves = 0;
+    if (compress) {
+      std::vector<uint8_t> bytes;
+      if (!slurp(recursion_path, &bytes) || bytes.size() % 4) { fprintf(stderr, "r0h_prove: cannot read %s\n", recursion_path.c_str()); return 1; }
+      std::vector<uint32_t> rec_blob(bytes.size() / 4);
+      memcpy(rec_blob.data(), bytes.data(), bytes.size());
+      r0h_recursor* recursor = nullptr;
+      CHECK(r0h_recursor_new(ctx, rec_blob.data(), rec_blob.size(), recursion_co_path.empty() ? nullptr : recursion_co_path.c_str(), recursion_po2, blob.data(), blob.size(),
+                             root_table.data(), root_table.size() / 9, &recursor));
+      r0h_node* root = nullptr;
+      const auto c0 = std::chrono::steady_clock::now();
+      CHECK(r0h_compress(recursor, rc, compress_lanes, &root));
+      compress_secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - c0).count();
+      const uint32_t *seal = nullptr, *session = nullptr;
+      size_t seal_words = 0;
+      r0h_receipt_claim claim;
+      CHECK(r0h_node_seal(root, &seal, &seal_words));
+      CHECK(r0h_node_claim(root, &claim));
+      CHECK(r0h_node_session(root, &session, &root_leaves));
+      const uint32_t head[2] = {(uint32_t)root_leaves, (uint32_t)seal_words};
+      FILE* o = fopen(root_out.c_str(), "wb");
+      if (!o || fwrite(&claim, 1, sizeof claim, o) != sizeof claim || fwrite(head, 4, 2, o) != 2 || fwrite(seal, 4, seal_words, o) != seal_words ||
+          fwrite(session, 4, root_leaves * R0H_NODE_SESSION_WORDS, o) != root_leaves * R0H_NODE_SESSION_WORDS) {
+        fprintf(stderr, "r0h_prove: cannot write %s\n", root_out.c_str());
+        return 1;
+      }
+      fclose(o);
+      CHECK(r0h_node_free(root));
+      CHECK(r0h_recursor_free(recursor));
+    }
     char hex[65];
     CHECK(r0h_image_id_to_hex(image_id, hex));
     r0h_session_stats st;
@@ -337,7 +392,9 @@ int main(int argc, char** argv) {
       const uint32_t* root = &root_table[9 * k + 1];
       printf("%s\"%u:%u,%u,%u,%u,%u,%u,%u,%u\"", k ? ", " : "", sizes[k], root[0], root[1], root[2], root[3], root[4], root[5], root[6], root[7]);
     }
-    printf("]}\n");
+    printf("]");
+    if (compress) printf(", \"root\": \"%s\", \"root_leaves\": %zu, \"compress_seconds\": %.4f", root_out.c_str(), root_leaves, compress_secs);
+    printf("}\n");
     for (r0h_receipt* r : made) CHECK(r0h_receipt_free(r));
     for (Worker& w : workers) {
       CHECK(r0h_circuit_free(w.circ));

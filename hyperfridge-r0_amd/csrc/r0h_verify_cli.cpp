@@ -5,6 +5,8 @@
 //          r0h_verify --receipt <receipt.json> <circuit.r0c> --image-id <64 hex> --control-root <po2>:<w0,..,w7> [--control-root ..]
 //          r0h_verify --receipt <receipt.json> <circuit.r0c> --image-id <64 hex> --image-circuit <image.r0c>   a trace-circuit receipt that carries
 //                     an image proof, checked with the 32 bytes of the image id alone (r0h_receipt_verify_image) -- the reference's call
+//          r0h_verify --root <root.bin> --receipt <receipt.json> <trace.r0c> --recursion-circuit <recursion.r0c> (--elf <guest.elf> | --image-id <64 hex> --image-circuit <image.r0c>)
+//                     a root made by `r0h_prove --compress --root-out` held to its session (r0h_node_verify, r0h_root_verify_session_*)
 //          r0h_verify --image-id-of <guest.elf>          prints the image id in the reference's IMAGE_ID.hex form (`host show-image-id`)
 //          r0h_verify --receipt <receipt.json> <circuit.r0c> --elf <guest.elf> --control-root ...   (the image id computed from the ELF:
 //                     r0h_compute_image_id, what risc0_build embeds as HYPERFRIDGE_ID).  A receipt over the trace circuit binds its
@@ -150,7 +152,93 @@ static int verify_receipt(const char* receipt_path, const char* blob_path, const
   return accepted ? 0 : 1;
 }
 
+// A root of the lift / join tree (r0h_prove --compress --root-out: wire form) held to what --receipt holds a receipt to: its seal
+// verified bound to the recursion circuit's control root derived from that circuit (r0h_node_verify), then its session
+// (r0h_root_verify_session_elf / _image).  The journal and the image proof come from the receipt; its seals are not read.
+static int verify_root(const char* root_path, const char* receipt_path, const char* blob_path, const char* recursion_path, const char* elf_path, const char* image_hex,
+                       const char* image_circuit_path) {
+  std::vector<uint32_t> blob, rec_blob, wire, image_blob;
+  if (!read_words(blob_path, &blob)) { fprintf(stderr, "r0h_verify: cannot read %s as 32-bit words\n", blob_path); return 2; }
+  if (!recursion_path || !read_words(recursion_path, &rec_blob)) { fprintf(stderr, "r0h_verify: --root needs --recursion-circuit <recursion.r0c>\n"); return 2; }
+  if (!read_words(root_path, &wire)) { fprintf(stderr, "r0h_verify: cannot read %s as 32-bit words\n", root_path); return 2; }
+  if (!elf_path && !(image_hex && image_circuit_path)) { fprintf(stderr, "r0h_verify: --root needs --elf, or --image-id with --image-circuit\n"); return 2; }
+  const size_t claim_words = sizeof(r0h_receipt_claim) / 4;
+  if (wire.size() < claim_words + 2 || wire[claim_words + 1] == 0 ||
+      wire.size() != claim_words + 2 + (size_t)wire[claim_words + 1] + (size_t)wire[claim_words] * R0H_NODE_SESSION_WORDS) {
+    fprintf(stderr, "r0h_verify: %s is not a node in wire form (claim words, [n_leaves, seal_words], seal, session words)\n", root_path);
+    return 2;
+  }
+  r0h_receipt_claim claim;
+  memcpy(&claim, wire.data(), sizeof claim);
+  const size_t n_leaves = wire[claim_words], seal_words = wire[claim_words + 1];
+  const uint32_t* seal = wire.data() + claim_words + 2;
+  char buf[65536];
+  std::vector<char> text;
+  std::vector<uint8_t> elf;
+  FILE* f = fopen(receipt_path, "rb");
+  if (!f) { fprintf(stderr, "r0h_verify: cannot open %s\n", receipt_path); return 2; }
+  for (size_t got; (got = fread(buf, 1, sizeof buf, f)) > 0;) text.insert(text.end(), buf, buf + got);
+  fclose(f);
+  if (elf_path) {
+    FILE* e = fopen(elf_path, "rb");
+    if (!e) { fprintf(stderr, "r0h_verify: cannot open %s\n", elf_path); return 2; }
+    for (size_t got; (got = fread(buf, 1, sizeof buf, e)) > 0;) elf.insert(elf.end(), buf, buf + got);
+    fclose(e);
+  } else if (!read_words(image_circuit_path, &image_blob)) { fprintf(stderr, "r0h_verify: cannot read %s\n", image_circuit_path); return 2; }
+  r0h_receipt* rc = nullptr;
+  r0h_node* node = nullptr;
+  int verdict = -1, seal_verdict = -1, node_ok = 0;
+  size_t leaf = 0;
+  uint32_t po2 = 0, control_root[8];
+  const uint8_t* journal = nullptr; size_t jn = 0;
+  const uint32_t* image_seal = nullptr; size_t image_seal_words = 0;
+  uint8_t image_id[32];
+  const char* err = r0h_receipt_parse(text.data(), text.size(), &rc);
+  if (!err) err = r0h_receipt_journal(rc, &journal, &jn);
+  if (!err) err = r0h_receipt_image_proof(rc, &image_seal, &image_seal_words);
+  if (!err) err = r0h_node_new_with_session(seal, seal_words, &claim, seal + seal_words, n_leaves, &node);
+  // the control root of the recursion circuit at the size the root's seal names, derived once the seal as such holds
+  if (!err) err = r0h_verify_seal(rec_blob.data(), rec_blob.size(), nullptr, nullptr, seal, seal_words, &seal_verdict, &po2);
+  if (!err && seal_verdict == R0H_VERIFY_OK) {
+    err = r0h_control_root_host(rec_blob.data(), rec_blob.size(), nullptr, nullptr, po2, control_root);
+    if (!err) err = r0h_node_verify(rec_blob.data(), rec_blob.size(), control_root, node, &node_ok);
+  }
+  if (!err && node_ok) {
+    if (elf_path) err = r0h_root_verify_session_elf(blob.data(), blob.size(), node, journal, jn, elf.data(), elf.size(), &verdict, &leaf);
+    else {
+      err = r0h_image_id_from_hex(image_hex, image_id);
+      if (!err) err = r0h_root_verify_session_image(blob.data(), blob.size(), node, journal, jn, image_blob.data(), image_blob.size(), nullptr, image_seal, image_seal_words, image_id,
+                                                    &verdict, &leaf);
+    }
+  }
+  if (err) { fprintf(stderr, "r0h_verify: %s\n", err); r0h_free_error(err); r0h_node_free(node); r0h_receipt_free(rc); return 2; }
+  const bool accepted = node_ok && verdict == R0H_RECEIPT_V_OK;
+  const char* reason = accepted ? "ok" : seal_verdict != R0H_VERIFY_OK ? r0h_verify_reason(seal_verdict) : !node_ok ? "the root's seal does not name the claim it is carried with"
+                                                                                                              : r0h_receipt_verify_reason(verdict);
+  size_t off = 0, len = 0;
+  err = r0h_journal_commitment_span(journal, jn, &off, &len);
+  if (err) { r0h_free_error(err); len = 0; }
+  printf("{\"accepted\": %s, \"root_valid\": %s, \"verdict\": %d, \"leaves\": %zu, \"leaf_at_fault\": %zu, \"reason\": \"%s\", \"recursion_po2\": %u, \"control_root\": \"derived from the recursion circuit\", \"commitment\": ",
+         accepted ? "true" : "false", node_ok ? "true" : "false", verdict, n_leaves, leaf, reason, po2);
+  print_json_string(journal + off, len);
+  printf("}\n");
+  r0h_node_free(node);
+  r0h_receipt_free(rc);
+  return accepted ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 6 && !strcmp(argv[1], "--root") && !strcmp(argv[3], "--receipt")) {
+    const char *recursion_path = nullptr, *elf_path = nullptr, *image_hex = nullptr, *image_circuit_path = nullptr;
+    for (int i = 6; i + 1 < argc; i += 2) {
+      if (!strcmp(argv[i], "--recursion-circuit")) recursion_path = argv[i + 1];
+      else if (!strcmp(argv[i], "--elf")) elf_path = argv[i + 1];
+      else if (!strcmp(argv[i], "--image-id")) image_hex = argv[i + 1];
+      else if (!strcmp(argv[i], "--image-circuit")) image_circuit_path = argv[i + 1];
+      else { fprintf(stderr, "r0h_verify: unknown option %s\n", argv[i]); return 2; }
+    }
+    return verify_root(argv[2], argv[4], argv[5], recursion_path, elf_path, image_hex, image_circuit_path);
+  }
   if (argc == 3 && !strcmp(argv[1], "--image-id-of")) {  // `host show-image-id` (host/src/main.rs): the id a verifier holds a receipt against
     FILE* e = fopen(argv[2], "rb");
     if (!e) { fprintf(stderr, "r0h_verify: cannot open %s\n", argv[2]); return 2; }

@@ -25,7 +25,39 @@ struct r0h_receipt {
   uint8_t verifier_parameters[32] = {0};
 };
 
+// A node of the lift / join tree (recursion.cpp): its seal, the composed claim it is carried with and -- when every leaf below it is a
+// trace-circuit segment -- its leaves' session parts in leaf order, R0H_NODE_SESSION_WORDS each: what r0h_root_verify_session_* reads.
+struct r0h_node {
+  std::vector<uint32_t> seal;
+  r0h_receipt_claim claim;
+  std::vector<uint32_t> session;
+};
+
 namespace r0h {
+// One leaf of a trace-circuit session as its checks read it (claim.cpp session_verdict): the segment seal's early public inputs, the
+// root of its DATA commitment, the challenge and the sum the seal carries.  A receipt's segments and a root's session parts both give these.
+struct SessionLeaf {
+  const uint32_t* early;      // R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS words
+  const uint32_t* data_root;  // 8
+  const uint32_t* challenge;  // 16 (the seal's words at R0H_TRACE_GAMMA)
+  const uint32_t* sum;        // 4 (at R0H_TRACE_SUM)
+};
+// what the balance is held against: the program's image words (the ELF's) or the verified image proof's public inputs, and the journal
+struct SessionOtherSide {
+  const std::vector<std::pair<uint32_t, uint32_t>>* image;  // or nullptr
+  const uint32_t* image_public;                              // or nullptr: R0H_IMAGE_GLOBALS words
+  const uint8_t* first_root;                                 // the merkle root in the first claim's pre-state (what an image proof must be about)
+  const uint8_t* journal;
+  size_t journal_len;
+};
+// The session section of a trace-circuit receipt's verification, over n leaves of which leaf `term` ends the run: numbers 1..n, the
+// closing rules, every leaf's challenge = session_challenge over all records (R0H_RECEIPT_V_SESSION); then, with `other`, the image
+// proof's digest and challenge (R0H_RECEIPT_V_IMAGE_PROOF) and the balance of the leaves' sums with the image's and the journal's words
+// (R0H_RECEIPT_V_SESSION_SUM; a journal that is no whole number of words: R0H_RECEIPT_V_JOURNAL at `term`).  Without `other` the
+// ELF-free checks only.  Returns R0H_RECEIPT_V_OK or the verdict, *leaf_out the leaf it is about.
+int session_verdict(const std::vector<SessionLeaf>& leaves, size_t term, const SessionOtherSide* other, size_t* leaf_out);
+// the session part of one verified trace-circuit seal (R0H_NODE_SESSION_WORDS words: early public inputs, DATA root, challenge, sum)
+void session_part_of(const uint32_t* seal, const uint32_t data_root[8], uint32_t part_out[R0H_NODE_SESSION_WORDS]);
 struct Sha256 {
   uint32_t h[8];
   uint64_t total;

@@ -13,9 +13,20 @@
 // still verified BESIDE the proof -- host threads run the verifier while the device proves -- because risc0's recursion circuit (whose
 // programs are downloaded at build time upstream) cannot be reproduced here; a root node is a checkable tree of seals with a composed
 // claim, not a succinct receipt.  r0h_node_verify checks one node's seal, control root and naming words.
+//
+// What none of lift / join / node_verify checks is the SESSION argument of trace-circuit seals (numbers, closing rules, the common
+// challenge, the balance of the sums with the image and the journal: csrc/claim.cpp session_verdict).  A node therefore carries its
+// leaves' session parts (R0H_NODE_SESSION_WORDS each, taken by lift from the seal it verified, concatenated by join) beside its claim,
+// and r0h_root_verify_session_elf / _image (claim.cpp) hold a root to them.  r0h_compress is the whole tree in one call: a queue of
+// lifts and joins taken by up to four prover lanes of the device, refusing a receipt that fails the image-free session checks first.
 #include <string.h>
 
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <deque>
 #include <memory>
+#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -23,11 +34,6 @@
 #include "receipt_types.hpp"
 
 using namespace r0h;
-
-struct r0h_node {
-  std::vector<uint32_t> seal;
-  r0h_receipt_claim claim;
-};
 
 struct r0h_recursor {
   r0h_ctx* ctx = nullptr;
@@ -53,9 +59,10 @@ void naming_words(const r0h_receipt_claim& claim, uint32_t out[8]) {
   claim_globals(cd, out);
 }
 
-// one recursion-circuit proof with the given 16 public inputs, on the recursor's context, while `checks` run on host threads
-const char* prove_node(r0h_recursor* rc, const uint32_t publics[16], const uint32_t* consumed, size_t n_consumed, std::vector<uint32_t>& seal) {
-  r0h_ctx* ctx = rc->ctx;
+// one recursion-circuit proof with the given 16 public inputs, on `ctx` -- the recursor's context or a helper lane of it (r0h_compress:
+// the lanes share the loaded circuit and its CODE commitment) -- while `checks` run on host threads.  `states`: what the sponge chain
+// over the consumed words starts every permutation from (p2_sponge_chain_host); the rows are expanded on the device (sponge.hip)
+const char* prove_node(r0h_recursor* rc, r0h_ctx* ctx, const uint32_t publics[16], const std::vector<uint32_t>& states, std::vector<uint32_t>& seal) {
   const size_t n = (size_t)1 << rc->po2;
   DevBuf data, code;  // (freed in the reverse order: CODE first)
   R0H_TRY(code.alloc(ctx, (size_t)rc->circuit->group_size[R0H_GROUP_CODE] * n * 4));
@@ -64,7 +71,7 @@ const char* prove_node(r0h_recursor* rc, const uint32_t publics[16], const uint3
   const uint64_t seed = (uint64_t)publics[0] | (uint64_t)publics[8] << 32;
   R0H_TRY(r0h_witgen_public(ctx, rc->circuit, rc->po2, seed, publics, code.get(), data.get()));
   // the sponge rows over what this node consumes: the digest the circuit computes from them is publics[8..16)
-  R0H_TRY(sponge_plant(ctx, rc->circuit, rc->po2, consumed, n_consumed, data.get()));
+  R0H_TRY(sponge_plant_states(ctx, rc->circuit, rc->po2, states.data(), states.size() / P2_CELLS, data.get()));
   seal.resize((size_t)1 << 19);
   size_t words = 0;
   R0H_TRY(r0h_prove_segment_committed(ctx, rc->circuit, rc->po2, rc->code, data.get(), publics, seal.data(), seal.size(), &words));
@@ -76,14 +83,15 @@ struct Check {  // a seal this step consumes, verified on a host thread while th
   const uint32_t* blob; size_t blob_words; const uint32_t* seal; size_t seal_words; const uint32_t* root; const char* what;
   int verdict = -1;
   const char* err = nullptr;
-  void run() { err = r0h_verify_seal_bound(blob, blob_words, nullptr, nullptr, seal, seal_words, root, &verdict, nullptr, nullptr); }
+  uint32_t data_root[8] = {0};  // of the seal's DATA commitment, as its transcript recomputes it
+  void run() { err = r0h_verify_seal_roots(blob, blob_words, seal, seal_words, root, &verdict, nullptr, data_root); }
 };
 
-const char* prove_checked(r0h_recursor* rc, std::vector<Check>& checks, const uint32_t publics[16], const uint32_t* consumed, size_t n_consumed,
+const char* prove_checked(r0h_recursor* rc, r0h_ctx* ctx, std::vector<Check>& checks, const uint32_t publics[16], const std::vector<uint32_t>& states,
                           std::vector<uint32_t>& seal) {
   std::vector<std::thread> threads;
   for (Check& c : checks) threads.emplace_back([&c] { c.run(); });
-  const char* err = prove_node(rc, publics, consumed, n_consumed, seal);
+  const char* err = prove_node(rc, ctx, publics, states, seal);
   for (std::thread& t : threads) t.join();
   for (Check& c : checks) {
     if (c.err && !err) err = c.err;
@@ -93,6 +101,108 @@ const char* prove_checked(r0h_recursor* rc, std::vector<Check>& checks, const ui
   for (Check& c : checks) R0H_REQUIRE(c.verdict == R0H_VERIFY_OK, "%s: the seal to be consumed does not verify: %s", c.what, r0h_verify_reason(c.verdict));
   return nullptr;
 }
+
+// the control root a segment seal of 2^po2 rows is verified against: nullptr when the recursor was given none at all
+const char* segment_root(const r0h_recursor* rc, const char* caller, uint32_t po2, const uint32_t** root_out) {
+  *root_out = nullptr;
+  for (size_t k = 0; k < rc->segment_roots.size() / 9; k++)
+    if (rc->segment_roots[9 * k] == po2) *root_out = rc->segment_roots.data() + 9 * k + 1;
+  R0H_REQUIRE(*root_out || rc->segment_roots.empty(), "%s: no control root known for a segment of 2^%u rows", caller, po2);
+  return nullptr;
+}
+
+// r0h_lift on `ctx`.  `verified_data_root`: the seal has been verified bound to its control root already and this is the root of its
+// DATA commitment (r0h_compress verifies a receipt's seals before it proves anything); nullptr: verified beside the proof
+const char* lift_on(r0h_recursor* rc, r0h_ctx* ctx, const uint32_t* seal, size_t seal_words, const r0h_receipt_claim* claim, const uint32_t* verified_data_root,
+                    r0h_node** out) {
+  r0h_circuit seg;
+  R0H_TRY(parse_blob(&seg, rc->segment_blob.data(), rc->segment_blob.size()));
+  R0H_REQUIRE(seal_words > (size_t)seg.n_global && seal[seg.n_global] < P, "r0h_lift: the segment seal is truncated");
+  // `SegmentReceipt::verify_integrity`: the seal names the claim it is lifted for ...
+  uint32_t publics[16];
+  naming_words(*claim, publics);
+  R0H_REQUIRE(!memcmp(publics, seal, 32), "r0h_lift: the segment seal's public inputs do not name this claim");
+  // a trace-circuit seal also says where its run starts and stops and how it ends: the claim it is lifted under must say the same
+  // (r0h_receipt_verify refuses a receipt otherwise; a root built from lifted nodes must not carry a claim that check would refuse)
+  const bool trace = is_trace_circuit(seg);
+  if (trace) R0H_REQUIRE(trace_seal_carries_claim(seal, *claim), "r0h_lift: the segment seal's first / last pc, way of ending or exit code are not this claim's");
+  // ... and verifies against the control root of its trace size, when the recursor was given one (else against the circuit alone)
+  const uint32_t* root = nullptr;
+  R0H_TRY(segment_root(rc, "r0h_lift", dec(seal[seg.n_global]), &root));
+  // one pass of the sponge chain over the seal: the digest among the public inputs, and what the planted rows start from
+  for (size_t i = 0; i < seal_words; i++) R0H_REQUIRE(seal[i] < P, "r0h_seal_digest: word %zu is not a canonical field element", i);
+  std::vector<uint32_t> states;
+  p2_sponge_chain_host(p2_default(), seal, seal_words, publics + 8, &states);
+  std::vector<Check> checks(verified_data_root ? 0 : 1);
+  if (!verified_data_root) checks[0] = Check{rc->segment_blob.data(), rc->segment_blob.size(), seal, seal_words, root, "lift"};
+  std::unique_ptr<r0h_node> node(new r0h_node());
+  node->claim = *claim;
+  R0H_TRY(prove_checked(rc, ctx, checks, publics, states, node->seal));
+  if (trace) {  // the leaf's session part, from the seal that was just verified
+    node->session.resize(R0H_NODE_SESSION_WORDS);
+    session_part_of(seal, verified_data_root ? verified_data_root : checks[0].data_root, node->session.data());
+  }
+  *out = node.release();
+  return nullptr;
+}
+
+const char* join_on(r0h_recursor* rc, r0h_ctx* ctx, const r0h_node* a, const r0h_node* b, r0h_node** out) {
+  // risc0 `ReceiptClaim::join`: a must stop in a system split exactly where b starts.  One more case here: b is a node of closing rows
+  // only (the trace circuit's session may end in segments without cycles: pre == post, SystemSplit, no output) -- it follows whatever
+  // a ends in, the run's last segment included, and the composed claim ends the way a does
+  static const uint8_t no_output[32] = {0};
+  const bool b_idle = same_state(b->claim.pre, b->claim.post) && b->claim.exit_system == 2 && b->claim.exit_user == 0 && !memcmp(b->claim.output_digest, no_output, 32);
+  R0H_REQUIRE(b_idle || (a->claim.exit_system == 2 && a->claim.exit_user == 0), "r0h_join: the left node does not end in SystemSplit: nothing can follow it");
+  R0H_REQUIRE(same_state(a->claim.post, b->claim.pre), "r0h_join: the left node's post-state is not the right node's pre-state: these two do not follow one another");
+  uint32_t names[16];
+  for (int side = 0; side < 2; side++) {  // each child's seal names the claim it is carried with
+    const r0h_node* nd = side ? b : a;
+    R0H_REQUIRE(nd->seal.size() > 17, "r0h_join: a child seal is truncated");
+    naming_words(nd->claim, names);
+    R0H_REQUIRE(!memcmp(names, nd->seal.data(), 32), "r0h_join: the %s node's seal does not name the claim it is carried with", side ? "right" : "left");
+  }
+  std::unique_ptr<r0h_node> node(new r0h_node());
+  node->claim = a->claim;             // pre, input from the left ...
+  node->claim.post = b->claim.post;   // ... post, exit code, output from the right (a node of closing rows only leaves the left's)
+  if (!(b_idle && a->claim.exit_system != 2)) {
+    node->claim.exit_system = b->claim.exit_system;
+    node->claim.exit_user = b->claim.exit_user;
+    memcpy(node->claim.output_digest, b->claim.output_digest, 32);
+  }
+  // the leaves' session parts, left then right; a tree with a leaf that has none has none
+  if (!a->session.empty() && !b->session.empty()) {
+    node->session = a->session;
+    node->session.insert(node->session.end(), b->session.begin(), b->session.end());
+  }
+  uint32_t publics[16], children[16];
+  naming_words(node->claim, publics);
+  R0H_TRY(r0h_seal_digest(a->seal.data(), a->seal.size(), children));
+  R0H_TRY(r0h_seal_digest(b->seal.data(), b->seal.size(), children + 8));
+  std::vector<uint32_t> states;  // the consumed words are the two digests: one permutation, its digest and its rows from one pass
+  p2_sponge_chain_host(p2_default(), children, 16, publics + 8, &states);
+  std::vector<Check> checks(2);
+  checks[0] = Check{rc->recursion_blob.data(), rc->recursion_blob.size(), a->seal.data(), a->seal.size(), rc->root, "join (left)"};
+  checks[1] = Check{rc->recursion_blob.data(), rc->recursion_blob.size(), b->seal.data(), b->seal.size(), rc->root, "join (right)"};
+  R0H_TRY(prove_checked(rc, ctx, checks, publics, states, node->seal));
+  *out = node.release();
+  return nullptr;
+}
+
+// ---- r0h_compress: the whole tree as a queue of work.  A lift is ready at once, a join when both its children are done; the lanes
+// take what is ready.  The shape is the level-by-level fold of neighbours with an odd last node carried up.
+struct TreeTask {
+  int left = -1, right = -1;  // tasks whose nodes a join consumes; a lift has none and names its segment instead
+  size_t segment = 0;
+  int parent = -1, waiting = 0;
+  std::unique_ptr<r0h_node> node;
+};
+struct TreeQueue {
+  std::mutex mu;
+  std::condition_variable cv;
+  std::deque<int> ready;
+  size_t left_to_do = 0;
+  bool stop = false;
+};
 }  // namespace
 
 extern "C" {
@@ -145,30 +255,7 @@ const char* r0h_lift(r0h_recursor* rc, const uint32_t* seal, size_t seal_words, 
   R0H_GUARD_BEGIN
   R0H_REQUIRE(rc && seal && claim && out, "r0h_lift: NULL argument");
   R0H_TRY(require_poseidon2(rc->ctx, "r0h_lift"));
-  r0h_circuit seg;
-  R0H_TRY(parse_blob(&seg, rc->segment_blob.data(), rc->segment_blob.size()));
-  R0H_REQUIRE(seal_words > (size_t)seg.n_global && seal[seg.n_global] < P, "r0h_lift: the segment seal is truncated");
-  // `SegmentReceipt::verify_integrity`: the seal names the claim it is lifted for ...
-  uint32_t publics[16];
-  naming_words(*claim, publics);
-  R0H_REQUIRE(!memcmp(publics, seal, 32), "r0h_lift: the segment seal's public inputs do not name this claim");
-  // a trace-circuit seal also says where its run starts and stops and how it ends: the claim it is lifted under must say the same
-  // (r0h_receipt_verify refuses a receipt otherwise; a root built from lifted nodes must not carry a claim that check would refuse)
-  if (is_trace_circuit(seg)) R0H_REQUIRE(trace_seal_carries_claim(seal, *claim), "r0h_lift: the segment seal's first / last pc, way of ending or exit code are not this claim's");
-  // ... and verifies against the control root of its trace size, when the recursor was given one (else against the circuit alone)
-  const uint32_t po2 = dec(seal[seg.n_global]);
-  const uint32_t* root = nullptr;
-  for (size_t k = 0; k < rc->segment_roots.size() / 9; k++)
-    if (rc->segment_roots[9 * k] == po2) root = rc->segment_roots.data() + 9 * k + 1;
-  R0H_REQUIRE(root || rc->segment_roots.empty(), "r0h_lift: no control root known for a segment of 2^%u rows", po2);
-  R0H_TRY(r0h_seal_digest(seal, seal_words, publics + 8));
-  std::vector<Check> checks(1);
-  checks[0] = Check{rc->segment_blob.data(), rc->segment_blob.size(), seal, seal_words, root, "lift"};
-  std::unique_ptr<r0h_node> node(new r0h_node());
-  node->claim = *claim;
-  R0H_TRY(prove_checked(rc, checks, publics, seal, seal_words, node->seal));
-  *out = node.release();
-  return nullptr;
+  return lift_on(rc, rc->ctx, seal, seal_words, claim, nullptr, out);
   R0H_GUARD_END
 }
 
@@ -176,38 +263,117 @@ const char* r0h_join(r0h_recursor* rc, const r0h_node* a, const r0h_node* b, r0h
   R0H_GUARD_BEGIN
   R0H_REQUIRE(rc && a && b && out, "r0h_join: NULL argument");
   R0H_TRY(require_poseidon2(rc->ctx, "r0h_join"));
-  // risc0 `ReceiptClaim::join`: a must stop in a system split exactly where b starts.  One more case here: b is a node of closing rows
-  // only (the trace circuit's session may end in segments without cycles: pre == post, SystemSplit, no output) -- it follows whatever
-  // a ends in, the run's last segment included, and the composed claim ends the way a does
-  static const uint8_t no_output[32] = {0};
-  const bool b_idle = same_state(b->claim.pre, b->claim.post) && b->claim.exit_system == 2 && b->claim.exit_user == 0 && !memcmp(b->claim.output_digest, no_output, 32);
-  R0H_REQUIRE(b_idle || (a->claim.exit_system == 2 && a->claim.exit_user == 0), "r0h_join: the left node does not end in SystemSplit: nothing can follow it");
-  R0H_REQUIRE(same_state(a->claim.post, b->claim.pre), "r0h_join: the left node's post-state is not the right node's pre-state: these two do not follow one another");
-  uint32_t names[16];
-  for (int side = 0; side < 2; side++) {  // each child's seal names the claim it is carried with
-    const r0h_node* nd = side ? b : a;
-    R0H_REQUIRE(nd->seal.size() > 17, "r0h_join: a child seal is truncated");
-    naming_words(nd->claim, names);
-    R0H_REQUIRE(!memcmp(names, nd->seal.data(), 32), "r0h_join: the %s node's seal does not name the claim it is carried with", side ? "right" : "left");
+  return join_on(rc, rc->ctx, a, b, out);
+  R0H_GUARD_END
+}
+
+// risc0 `prover.compress(opts, &receipt)`: every segment lifted, the nodes joined into one root, on `lanes` prover lanes (1..4; 0: 2).
+// Lane 0 is the recursor's context on the calling thread, the others are helper contexts of the same device on threads of their own
+// (ctx_helper / run_lanes, as sessions use them); all share the loaded recursion circuit and its CODE commitment.  A node's seal depends
+// only on its public inputs and what it consumed, so the root is the one the sequential fold of r0h_lift / r0h_join gives, word for
+// word, whatever the lanes' order.  A trace-circuit receipt's seals are verified first, all of them, and the receipt is held to the
+// ELF-free session checks (numbers, closing rules, the common challenge) before any proof is made; the balance needs the image and
+// stays r0h_root_verify_session_*'s.  The first failure stops the queue; every lane has been joined when the error is returned.
+const char* r0h_compress(r0h_recursor* rc, const r0h_receipt* receipt, uint32_t lanes, r0h_node** out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(rc && receipt && out, "r0h_compress: NULL argument");
+  R0H_REQUIRE(lanes <= 4, "r0h_compress: %u lanes: 1 to 4 (0 selects 2)", lanes);
+  if (!lanes) lanes = 2;
+  R0H_TRY(require_poseidon2(rc->ctx, "r0h_compress"));
+  R0H_REQUIRE(receipt->kind == R0H_RECEIPT_COMPOSITE && !receipt->segments.empty(), "r0h_compress: not a composite receipt: there are no segment seals to lift");
+  const size_t n = receipt->segments.size();
+  for (size_t i = 0; i < n; i++) {
+    const r0h_receipt::Segment& g = receipt->segments[i];
+    R0H_REQUIRE(g.has_claim, "r0h_compress: segment %zu carries no claim", i);
+    R0H_REQUIRE(g.hashfn == "poseidon2", "r0h_compress: segment %zu names the hash function %s: nodes are Poseidon2 only", i, g.hashfn.c_str());
   }
-  std::unique_ptr<r0h_node> node(new r0h_node());
-  node->claim = a->claim;             // pre, input from the left ...
-  node->claim.post = b->claim.post;   // ... post, exit code, output from the right (a node of closing rows only leaves the left's)
-  if (!(b_idle && a->claim.exit_system != 2)) {
-    node->claim.exit_system = b->claim.exit_system;
-    node->claim.exit_user = b->claim.exit_user;
-    memcpy(node->claim.output_digest, b->claim.output_digest, 32);
+  r0h_circuit seg;
+  R0H_TRY(parse_blob(&seg, rc->segment_blob.data(), rc->segment_blob.size()));
+  // a trace-circuit receipt: every seal verified bound to its control root (what r0h_lift would do beside its proof, done here on
+  // up to three host threads per lane instead), which gives the DATA roots the session's challenge is derived from
+  std::vector<uint32_t> data_roots;
+  if (is_trace_circuit(seg)) {
+    data_roots.resize(8 * n);
+    std::vector<Check> checks(n);
+    for (size_t i = 0; i < n; i++) {
+      const std::vector<uint32_t>& sl = receipt->segments[i].seal;
+      R0H_REQUIRE(sl.size() > (size_t)seg.n_global && sl[seg.n_global] < P, "r0h_lift: the segment seal is truncated");
+      const uint32_t* root = nullptr;
+      R0H_TRY(segment_root(rc, "r0h_lift", dec(sl[seg.n_global]), &root));
+      checks[i] = Check{rc->segment_blob.data(), rc->segment_blob.size(), sl.data(), sl.size(), root, "lift"};
+    }
+    std::atomic<size_t> next(0);
+    std::vector<std::thread> threads;
+    for (size_t t = 0; t < std::min<size_t>(n, 3 * (size_t)lanes); t++)
+      threads.emplace_back([&] { for (size_t i = next++; i < n; i = next++) checks[i].run(); });
+    for (std::thread& t : threads) t.join();
+    const char* err = nullptr;
+    for (Check& c : checks) {
+      if (c.err && !err) err = c.err;
+      else if (c.err) r0h_free_error(c.err);
+    }
+    if (err) return err;
+    std::vector<SessionLeaf> leaves(n);
+    for (size_t i = 0; i < n; i++) {
+      R0H_REQUIRE(checks[i].verdict == R0H_VERIFY_OK, "lift: the seal to be consumed does not verify: %s (segment %zu)", r0h_verify_reason(checks[i].verdict), i);
+      memcpy(&data_roots[8 * i], checks[i].data_root, 32);
+      const uint32_t* sl = receipt->segments[i].seal.data();
+      leaves[i] = SessionLeaf{sl, &data_roots[8 * i], sl + R0H_TRACE_GAMMA, sl + R0H_TRACE_SUM};
+    }
+    size_t term = n - 1, leaf = 0;
+    for (size_t i = 0; i < n; i++)
+      if (receipt->segments[i].claim.exit_system <= 1) { term = i; break; }
+    const int v = session_verdict(leaves, term, nullptr, &leaf);
+    R0H_REQUIRE(v == R0H_RECEIPT_V_OK, "r0h_compress: segment %zu: %s", leaf, r0h_receipt_verify_reason(v));
   }
-  uint32_t publics[16], children[16];
-  naming_words(node->claim, publics);
-  R0H_TRY(r0h_seal_digest(a->seal.data(), a->seal.size(), children));
-  R0H_TRY(r0h_seal_digest(b->seal.data(), b->seal.size(), children + 8));
-  R0H_TRY(r0h_seal_digest(children, 16, publics + 8));
-  std::vector<Check> checks(2);
-  checks[0] = Check{rc->recursion_blob.data(), rc->recursion_blob.size(), a->seal.data(), a->seal.size(), rc->root, "join (left)"};
-  checks[1] = Check{rc->recursion_blob.data(), rc->recursion_blob.size(), b->seal.data(), b->seal.size(), rc->root, "join (right)"};
-  R0H_TRY(prove_checked(rc, checks, publics, children, 16, node->seal));
-  *out = node.release();
+  // the tree: tasks [0, n) lift, the joins follow level by level
+  std::vector<TreeTask> tasks(n);
+  std::vector<int> level(n);
+  for (size_t i = 0; i < n; i++) { tasks[i].segment = i; level[i] = (int)i; }
+  while (level.size() > 1) {
+    std::vector<int> up;
+    for (size_t i = 0; i + 1 < level.size(); i += 2) {
+      TreeTask t;
+      t.left = level[i]; t.right = level[i + 1]; t.waiting = 2;
+      tasks[t.left].parent = tasks[t.right].parent = (int)tasks.size();
+      up.push_back((int)tasks.size());
+      tasks.push_back(std::move(t));
+    }
+    if (level.size() & 1) up.push_back(level.back());
+    level.swap(up);
+  }
+  TreeQueue q;
+  q.left_to_do = tasks.size();
+  for (size_t i = 0; i < n; i++) q.ready.push_back((int)i);
+  std::vector<r0h_ctx*> lane_ctx(std::min<size_t>(lanes, tasks.size()), rc->ctx);
+  for (size_t k = 1; k < lane_ctx.size(); k++) R0H_TRY(ctx_helper(rc->ctx, k - 1, &lane_ctx[k]));
+  auto lane = [&](r0h_ctx* lctx) -> const char* {
+    for (;;) {
+      int id;
+      {
+        std::unique_lock<std::mutex> lk(q.mu);
+        q.cv.wait(lk, [&] { return q.stop || !q.left_to_do || !q.ready.empty(); });
+        if (q.stop || !q.left_to_do) return nullptr;
+        id = q.ready.front();
+        q.ready.pop_front();
+      }
+      TreeTask& t = tasks[id];
+      r0h_node* made = nullptr;
+      if (t.left < 0) {
+        const r0h_receipt::Segment& g = receipt->segments[t.segment];
+        R0H_TRY(lift_on(rc, lctx, g.seal.data(), g.seal.size(), &g.claim, data_roots.empty() ? nullptr : &data_roots[8 * t.segment], &made));
+      } else {
+        R0H_TRY(join_on(rc, lctx, tasks[t.left].node.get(), tasks[t.right].node.get(), &made));
+      }
+      std::lock_guard<std::mutex> lk(q.mu);
+      t.node.reset(made);
+      q.left_to_do--;
+      if (t.parent >= 0 && --tasks[t.parent].waiting == 0) q.ready.push_back(t.parent);
+      q.cv.notify_all();
+    }
+  };
+  R0H_TRY(run_lanes(lane_ctx, lane, [&] { std::lock_guard<std::mutex> lk(q.mu); q.stop = true; q.cv.notify_all(); }));
+  *out = tasks[level[0]].node.release();
   return nullptr;
   R0H_GUARD_END
 }
@@ -222,6 +388,25 @@ const char* r0h_node_new(const uint32_t* seal, size_t seal_words, const r0h_rece
   *out = node.release();
   return nullptr;
   R0H_GUARD_END
+}
+// ... and with its leaves' session parts, as r0h_node_session gave them where it was made (n_leaves x R0H_NODE_SESSION_WORDS words).
+// They travel beside the node as the claim does: r0h_root_verify_session_* reads them, nothing here checks them against the seal.
+const char* r0h_node_new_with_session(const uint32_t* seal, size_t seal_words, const r0h_receipt_claim* claim, const uint32_t* session, size_t n_leaves, r0h_node** out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(seal && claim && out && (session || !n_leaves), "r0h_node_new_with_session: NULL argument");
+  std::unique_ptr<r0h_node> node(new r0h_node());
+  node->seal.assign(seal, seal + seal_words);
+  node->claim = *claim;
+  node->session.assign(session, session + n_leaves * R0H_NODE_SESSION_WORDS);
+  *out = node.release();
+  return nullptr;
+  R0H_GUARD_END
+}
+const char* r0h_node_session(const r0h_node* node, const uint32_t** words, size_t* n_leaves) {
+  R0H_REQUIRE(node && words && n_leaves, "r0h_node_session: NULL argument");
+  *words = node->session.data();
+  *n_leaves = node->session.size() / R0H_NODE_SESSION_WORDS;
+  return nullptr;
 }
 const char* r0h_node_free(r0h_node* node) {
   delete node;

@@ -280,31 +280,6 @@ class Feed {
   std::thread thread_;
 };
 
-// Lane 0 on the calling thread, the others on threads of their own; the first error is kept (and `on_error` told), later ones are
-// freed; every thread has been joined when this returns.
-template <class Fn, class OnError>
-const char* run_lanes(const std::vector<r0h_ctx*>& lanes, Fn fn, OnError on_error) {
-  std::atomic<const char*> first(nullptr);
-  auto lane = [&](r0h_ctx* lctx) {
-    const char* err = nullptr;
-    try {
-      err = fn(lctx);
-    } catch (const std::exception& ex) {
-      err = make_error("exception in a prover lane: %s", ex.what());
-    } catch (...) {
-      err = make_error("unknown exception in a prover lane");
-    }
-    if (!err) return;
-    const char* none = nullptr;
-    if (!first.compare_exchange_strong(none, err)) r0h_free_error(err);
-    on_error();
-  };
-  std::vector<std::thread> workers;
-  for (size_t k = 1; k < lanes.size(); k++) workers.emplace_back(lane, lanes[k]);
-  lane(lanes[0]);
-  for (std::thread& t : workers) t.join();
-  return first;
-}
 }  // namespace
 
 namespace r0h {

@@ -333,6 +333,17 @@ void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size
 }  // namespace
 }  // namespace r0h
 
+namespace r0h {
+const char* sponge_trace_args(const char* caller, const uint32_t* words, size_t n_words, uint32_t po2, size_t* n_perm_out) {
+  R0H_REQUIRE(po2 >= 6 && po2 <= R0H_MAX_PO2, "%s: po2 %u outside [6, %u]", caller, po2, R0H_MAX_PO2);
+  const size_t n = (size_t)1 << po2, n_perm = n_words ? (n_words + P2_RATE - 1) / P2_RATE : 1;
+  R0H_REQUIRE(n_perm * R0H_SPONGE_PERIOD < n, "%s: %zu words take %zu rows, the trace has 2^%u", caller, n_words, n_perm * R0H_SPONGE_PERIOD, po2);
+  for (size_t i = 0; i < n_words; i++) R0H_REQUIRE(words[i] < P, "%s: word %zu is not a canonical field element", caller, i);
+  *n_perm_out = n_perm;
+  return nullptr;
+}
+}  // namespace r0h
+
 using namespace r0h;
 
 extern "C" {
@@ -360,10 +371,9 @@ const char* r0h_seal_digest(const uint32_t* seal, size_t seal_words, uint32_t di
 const char* r0h_sponge_trace(const uint32_t* words, size_t n_words, uint32_t po2, uint32_t* cols_out) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE((words || n_words == 0) && cols_out, "r0h_sponge_trace: NULL argument");
-  R0H_REQUIRE(po2 >= 6 && po2 <= R0H_MAX_PO2, "r0h_sponge_trace: po2 %u outside [6, %u]", po2, R0H_MAX_PO2);
-  const size_t n = (size_t)1 << po2, n_perm = n_words ? (n_words + P2_RATE - 1) / P2_RATE : 1;
-  R0H_REQUIRE(n_perm * R0H_SPONGE_PERIOD < n, "r0h_sponge_trace: %zu words take %zu rows, the trace has 2^%u", n_words, n_perm * R0H_SPONGE_PERIOD, po2);
-  for (size_t i = 0; i < n_words; i++) R0H_REQUIRE(words[i] < P, "r0h_sponge_trace: word %zu is not a canonical field element", i);
+  size_t n_perm = 0;
+  R0H_TRY(sponge_trace_args("r0h_sponge_trace", words, n_words, po2, &n_perm));
+  const size_t n = (size_t)1 << po2;
   memset(cols_out, 0, (size_t)R0H_SPONGE_DATA_COLUMNS * n * 4);
   size_t used = 0;
   p2_sponge_rows_host(p2_default(), words, n_words, cols_out, n, &used);

@@ -10,13 +10,15 @@ This module is the transport only: which rank hands its subtree to which, and ho
 
 Transport: `torch.distributed` point-to-point send/recv (backend "nccl" = RCCL over xGMI on a GPU node, "gloo" on CPU), one
 process per GPU; partner of rank r at level l is r ^ (1 << l), the lower rank of a pair joins.  No collective is involved.
-A node travels as its claim (the 144 bytes of r0h_receipt_claim) followed by its seal.
+A node travels as its claim (the 144 bytes of r0h_receipt_claim) followed by its seal (`to_words`), or -- when its leaves' session
+parts are to reach the root (r0h_root_verify_session_*) -- in wire form (`to_wire`): claim words, [n_leaves, seal_words], seal,
+session words.
 """
 import ctypes
 
 import numpy as np
 
-from . import Hal, ReceiptClaim, R0HipError, _check, _u32arr, _vp, _sz, lib, seal_digest, verify_seal  # noqa: F401  (package __init__ is the ctypes harness)
+from . import Hal, NODE_SESSION_WORDS, ReceiptClaim, R0HipError, _check, _u32arr, _vp, _sz, lib, seal_digest, verify_seal  # noqa: F401  (package __init__ is the ctypes harness)
 
 RECURSION_PO2 = 18
 CLAIM_WORDS = ctypes.sizeof(ReceiptClaim) // 4
@@ -34,7 +36,8 @@ def tree_schedule(world):
 
 
 class Node:
-    """A proven tree node (r0h_node): its seal and the composed claim it is carried with."""
+    """A proven tree node (r0h_node): its seal, the composed claim it is carried with and `session`, its leaves' session parts in leaf
+    order as an (n, 48) array (n = 0: a leaf below it is no trace-circuit segment, or the node arrived without them)."""
 
     def __init__(self, handle):
         self.handle = handle
@@ -43,13 +46,40 @@ class Node:
         self.seal = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint32)), shape=(n.value,)).copy()
         self.claim = ReceiptClaim()
         _check(lib().r0h_node_claim(handle, ctypes.byref(self.claim)))
+        p, n = _vp(), _sz(0)
+        _check(lib().r0h_node_session(handle, ctypes.byref(p), ctypes.byref(n)))
+        self.session = np.zeros((0, NODE_SESSION_WORDS), dtype=np.uint32)
+        if n.value:
+            self.session = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint32)), shape=(n.value, NODE_SESSION_WORDS)).copy()
 
     @classmethod
-    def from_parts(cls, seal, claim):
+    def from_parts(cls, seal, claim, session=None):
         a, pa = _u32arr(seal)
         h = _vp()
-        _check(lib().r0h_node_new(pa, a.size, ctypes.byref(claim), ctypes.byref(h)))
+        if session is None:
+            _check(lib().r0h_node_new(pa, a.size, ctypes.byref(claim), ctypes.byref(h)))
+        else:
+            b, pb = _u32arr(np.asarray(session, dtype=np.uint32).reshape(-1, NODE_SESSION_WORDS))
+            _check(lib().r0h_node_new_with_session(pa, a.size, ctypes.byref(claim), pb, b.shape[0], ctypes.byref(h)))
         return cls(h)
+
+    def to_wire(self):
+        """claim words, [n_leaves, seal_words], seal, session words"""
+        head = np.array([self.session.shape[0], self.seal.size], dtype=np.uint32)
+        return np.concatenate([np.frombuffer(bytes(self.claim), dtype=np.uint32), head, self.seal, self.session.reshape(-1)]).astype(np.uint32)
+
+    @classmethod
+    def from_wire(cls, words):
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        if words.size < CLAIM_WORDS + 2:
+            raise R0HipError("a node in wire form starts with %d claim words and two counts; got %d words" % (CLAIM_WORDS, words.size))
+        n_leaves, seal_words = int(words[CLAIM_WORDS]), int(words[CLAIM_WORDS + 1])
+        want = CLAIM_WORDS + 2 + seal_words + n_leaves * NODE_SESSION_WORDS
+        if seal_words == 0 or words.size != want:
+            raise R0HipError("a node in wire form with %d leaves and a seal of %d words has %d words; got %d" % (n_leaves, seal_words, want, words.size))
+        claim = ReceiptClaim.from_buffer_copy(words[:CLAIM_WORDS].tobytes())
+        at = CLAIM_WORDS + 2
+        return cls.from_parts(words[at:at + seal_words], claim, words[at + seal_words:] if n_leaves else None)
 
     def to_words(self):
         return np.concatenate([np.frombuffer(bytes(self.claim), dtype=np.uint32), self.seal]).astype(np.uint32)
@@ -123,6 +153,36 @@ class Recursor:
     def node_from_words(self, words):
         return Node.from_words(words)
 
+    def node_from_wire(self, words):
+        return Node.from_wire(words)
+
+    def compress(self, receipt, lanes=0):
+        """risc0 `prover.compress`: every segment of a composite receipt lifted and the nodes joined into one root, on `lanes` prover
+        lanes (1..4; 0: 2) of this device (r0h_compress).  The root is `fold` of the lifted segments, word for word."""
+        h = _vp()
+        _check(lib().r0h_compress(self.handle, receipt.handle, lanes, ctypes.byref(h)))
+        return Node(h)
+
+    @staticmethod
+    def verify_session(node, trace_blob, journal, elf=None, image_id=None, image_blob=None, image_proof=None, image_control_root=None):
+        """A root held to what `receipt.verify` holds a receipt to beyond its seals (r0h_root_verify_session_elf, or _image with
+        image_id + image_blob + image_proof): -> (verdict, reason, leaf).  Host only; `verify` checks the node's own seal."""
+        b, pb = _u32arr(trace_blob)
+        journal = bytes(journal)
+        verdict, leaf = ctypes.c_int(-1), _sz(0)
+        if elf is not None:
+            elf = bytes(elf)
+            _check(lib().r0h_root_verify_session_elf(pb, b.size, node.handle, journal, len(journal), elf, len(elf), ctypes.byref(verdict), ctypes.byref(leaf)))
+        else:
+            ib, pib = _u32arr(image_blob)
+            sl, psl = _u32arr(image_proof if image_proof is not None else np.zeros(0, dtype=np.uint32))
+            proot = None
+            if image_control_root is not None:
+                root, proot = _u32arr(image_control_root)
+            _check(lib().r0h_root_verify_session_image(pb, b.size, node.handle, journal, len(journal), pib, ib.size, proot, psl, sl.size, bytes(image_id),
+                                                       ctypes.byref(verdict), ctypes.byref(leaf)))
+        return verdict.value, lib().r0h_receipt_verify_reason(verdict.value).decode(), leaf.value
+
     def verify(self, node):
         """the node's seal verifies bound to the recursion circuit's control root and names the claim it is carried with"""
         ok = ctypes.c_int(0)
@@ -150,8 +210,9 @@ FAILED = np.array([0xFFFFFFFF], dtype=np.uint32)  # handed up instead of a seal 
 EMPTY = np.zeros(0, dtype=np.uint32)               # handed up by a rank that owns no segment (segments < world)
 
 
-def join_across_ranks(recursor, node, rank, world, send, recv):
-    """Run the cross-rank part of the tree.  `send(array, dst)` / `recv(src) -> array` move one node (uint32 words: claim, seal).
+def join_across_ranks(recursor, node, rank, world, send, recv, with_session=False):
+    """Run the cross-rank part of the tree.  `send(array, dst)` / `recv(src) -> array` move one node (uint32 words: claim, seal; with
+    `with_session` the wire form, so that the leaves' session parts reach the root in leaf order).
     A rank's own nodes cover a contiguous run of segments and rank r's run precedes rank r + 1's (driver.shard_contiguous), so the
     receiver's node is always the LEFT operand of the join.
     Returns the root Node on rank 0 and None elsewhere.
@@ -163,7 +224,7 @@ def join_across_ranks(recursor, node, rank, world, send, recv):
     failed = None
     for _level, receiver, sender in tree_schedule(world):
         if rank == sender:
-            send(FAILED if failed is not None else (EMPTY if node is None else node.to_words()), receiver)
+            send(FAILED if failed is not None else (EMPTY if node is None else (node.to_wire() if with_session else node.to_words())), receiver)
             if failed is not None:
                 raise failed
             return None  # this rank's subtree has been handed up
@@ -173,7 +234,7 @@ def join_across_ranks(recursor, node, rank, world, send, recv):
                 failed = failed or R0HipError("join tree: rank %d reported a failure in its subtree" % sender)
             elif failed is None and other.size:
                 try:
-                    arrived = recursor.node_from_words(other)
+                    arrived = recursor.node_from_wire(other) if with_session else recursor.node_from_words(other)
                     node = arrived if node is None else recursor.join(node, arrived)
                 except Exception as exc:  # noqa: BLE001 -- carried up the tree, re-raised below
                     failed = exc

@@ -392,6 +392,11 @@ const char* r0h_seal_digest(const uint32_t* seal, size_t seal_words, uint32_t di
  * r0h_join plant exactly this into a node's witness, so that the digest among the node's public inputs is computed inside its proof.
  * Refused: words that are not canonical field elements, more words than the trace has rows for (30 rows per 16 words). */
 const char* r0h_sponge_trace(const uint32_t* words, size_t n_words, uint32_t po2, uint32_t* cols_out /* [65][2^po2] */);
+/* The same rows made on the device, as r0h_lift / r0h_join / r0h_prove_image plant them: the host runs the sequential chain once (24
+ * words per permutation go up through the context's pinned ring), one lane per trace row expands them, rows behind the last permutation
+ * included (written as zero).  cols_out: a device buffer of 65 * 2^po2 words.  Stream-ordered.  Refuses what r0h_sponge_trace refuses,
+ * in the same words. */
+const char* r0h_sponge_trace_device(r0h_ctx* ctx, const uint32_t* words, size_t n_words, uint32_t po2, r0h_buf* cols_out);
 
 /* ---- data formats either side of the path (SURVEY.md 8(a) a0', a0'', a18): pure host code ----
  * serde word stream of a String: [u32 LE length][utf8][zero padding to 4] -- what `ExecutorEnv::builder().write(&s)` feeds the
@@ -806,20 +811,41 @@ const char* r0h_ctx_set_image_circuit(r0h_ctx* ctx, const r0h_circuit* image_cir
 const char* r0h_prove_image(r0h_ctx* ctx, const r0h_circuit* image_circuit, const uint8_t* elf, size_t elf_len, const uint32_t challenge[16],
                             uint32_t* seal_out, size_t seal_capacity_words, size_t* seal_words_out);
 
-/* ---- recursion: risc0-zkvm `ProverServer::{lift, join}` (risc0-circuit-recursion 4.0.4, Cargo.lock:3050-3085; BASELINE.json
+/* ---- recursion: risc0-zkvm `ProverServer::{lift, join, compress}` (risc0-circuit-recursion 4.0.4, Cargo.lock:3050-3085; BASELINE.json
  * configs[4]).  `lift` stands one recursion-circuit proof for one segment seal and its claim; `join` folds two nodes into one whose
  * claim is the composition {pre: a.pre, post: b.post, exit_code: b.exit_code, input: a.input, output: b.output}, and refuses two
- * nodes that do not follow one another (a must end in SystemSplit with a.post == b.pre).  A node's 16 public inputs are the 8 words
- * naming its composed claim (r0h_claim_globals) and the Poseidon2 digest of what it consumed -- the segment seal's words for a lift,
- * the two child seals' digests for a join.  That digest is computed INSIDE the node's proof: the circuit's sponge component runs the
- * permutation one round per row over witness cells holding the consumed words and ties the result to public inputs 8..15, so a
- * witness holding other words than the digest names satisfies no trace.  A lift of a 2^20-row trace-circuit seal (61k words: 3.8k
- * permutations of 30 rows) needs a recursion trace of 2^17 rows or more.
+ * nodes that do not follow one another (a must end in SystemSplit with a.post == b.pre); `compress` lifts every segment of a composite
+ * receipt and joins the nodes into one root.  A node's 16 public inputs are the 8 words naming its composed claim (r0h_claim_globals)
+ * and the Poseidon2 digest of what it consumed -- the segment seal's words for a lift, the two child seals' digests for a join.  That
+ * digest is computed INSIDE the node's proof: the circuit's sponge component runs the permutation one round per row over witness cells
+ * holding the consumed words and ties the result to public inputs 8..15, so a witness holding other words than the digest names
+ * satisfies no trace.  A lift of a 2^20-row trace-circuit seal (61k words: 3.8k permutations of 30 rows) needs a recursion trace of
+ * 2^17 rows or more.
  * NOT risc0's recursion circuit: that in-circuit hash is the first and only in-circuit step.  Every node is a proof over this
  * repository's recursion circuit (circuits/recursion.r0c) made with the same kernels, and the SEALS it consumes are verified BESIDE
  * that proof (host threads, while the device proves), not inside it -- a root is a checkable tree of seals carrying the end-to-end
- * claim, not a succinct receipt.  Moving nodes between ranks
- * (the tree's levels) is the caller's: hyperfridge-r0_amd/recursion.py does it over torch.distributed point-to-point. ---- */
+ * claim, not a succinct receipt.
+ * WHAT A ROOT CARRIES.  Its seal, its composed claim, and -- when every leaf below it is a trace-circuit segment -- its leaves' session
+ * parts in leaf order, R0H_NODE_SESSION_WORDS words each, all taken from the segment seal r0h_lift verified: [0, 20) the seal's early
+ * public inputs, [20, 28) the root of its DATA commitment (together the segment's R0H_SESSION_RECORD_WORDS record), [28, 44) the
+ * session challenge as the seal carries it, [44, 48) the segment's sum.  A lift over any other circuit leaves the part empty; a join
+ * concatenates left then right and has none unless both children have one.  A trace-circuit seal binds its memory to the program
+ * image and to the journal only through the session argument -- segment numbers, closing flags and ranges, the common challenge, the
+ * balance of the sums -- and neither r0h_lift nor r0h_join nor r0h_node_verify checks that argument.  r0h_root_verify_session_elf /
+ * _image do: they hold a root to everything r0h_receipt_verify_elf / _image hold a receipt to beyond the seals themselves (the leaves
+ * chain from the claim's first pc to its last, the way of ending and the exit code are the claim's, the journal is the one the claim
+ * commits to, numbers 1..n, the closing rules, every leaf's challenge is r0h_session_challenge over all records, the sums balance with
+ * the image's words -- the ELF's, or the image proof's total -- and the journal's, the claim's pre-state is the image id), with the
+ * same R0H_RECEIPT_V_* verdicts (one difference in order: the image id is looked at before the session section, so another program's
+ * ELF gets R0H_RECEIPT_V_IMAGE_ID where r0h_receipt_verify_elf, which reaches the balance first, says R0H_RECEIPT_V_SESSION_SUM).  Without that call a root built by honest lift / join calls over seals made under a self-chosen
+ * challenge, or whose sums do not balance, passes r0h_node_verify.
+ * THE LIMIT, in plain words.  The session part is not among the node's public inputs: it travels BESIDE the node, as the claim does.
+ * What binds it is that r0h_lift takes it from the seal it verified.  Someone who holds only a root trusts whoever ran lift / join for
+ * it -- exactly as for the validity of the children, which is also checked beside the proofs.  Someone who holds the tree can recheck
+ * it: r0h_trace_seal_session_part gives a leaf's part from its seal.
+ * Moving nodes between ranks (the tree's levels) is the caller's: hyperfridge-r0_amd/recursion.py does it over torch.distributed
+ * point-to-point. ---- */
+#define R0H_NODE_SESSION_WORDS 48
 typedef struct r0h_recursor r0h_recursor;
 typedef struct r0h_node r0h_node;
 /* segment_control_roots: n_roots records of 9 words [po2, root[8]] (r0h_code_root of the segment circuit); with n_roots = 0 the
@@ -837,6 +863,34 @@ const char* r0h_node_seal(const r0h_node* node, const uint32_t** seal, size_t* s
 const char* r0h_node_claim(const r0h_node* node, r0h_receipt_claim* claim_out);
 const char* r0h_node_verify(const uint32_t* recursion_blob, size_t blob_words, const uint32_t* control_root, const r0h_node* node,
                             int* ok_out);
+/* the leaves' session parts: *words points at n_leaves * R0H_NODE_SESSION_WORDS words owned by the node (n_leaves = 0: none) */
+const char* r0h_node_session(const r0h_node* node, const uint32_t** words, size_t* n_leaves);
+/* r0h_node_new for a node that arrives with its session parts */
+const char* r0h_node_new_with_session(const uint32_t* seal, size_t seal_words, const r0h_receipt_claim* claim, const uint32_t* session,
+                                      size_t n_leaves, r0h_node** out);
+/* host only: the session part of one trace-circuit seal -- the extraction r0h_lift makes.  The seal is verified against the circuit
+ * (it yields the DATA root); one that does not verify is an error. */
+const char* r0h_trace_seal_session_part(const uint32_t* blob, size_t blob_words, const uint32_t* seal, size_t seal_words,
+                                        uint32_t part_out[R0H_NODE_SESSION_WORDS]);
+/* `prover.compress(opts, &receipt)`: every segment of a composite receipt lifted and the nodes joined into one root, neighbours per
+ * level, an odd last node carried up -- the root r0h_lift / r0h_join give one after another, word for word.  lanes = 1..4 prover lanes
+ * (0: 2): lane 0 is the recursor's context on the calling thread, the others helper contexts of the same device on threads of their
+ * own; a lift is ready at once, a join when both its children are done.  Refused: what r0h_lift refuses, and, for a trace-circuit
+ * receipt, before any proof is made, one that fails the session checks that need no image (numbers, closing rules, the common
+ * challenge: R0H_RECEIPT_V_SESSION's reason and the segment are named).  The balance stays r0h_root_verify_session_*'s. */
+const char* r0h_compress(r0h_recursor* rc, const r0h_receipt* receipt, uint32_t lanes, r0h_node** out);
+/* A root held to its session (host only; see above).  blob: the trace circuit.  Returns an error string for a node that cannot be
+ * read as a session at all -- no session part, 2^20 leaves or more, a word that is no field element -- and otherwise NULL with
+ * *verdict_out an R0H_RECEIPT_V_* code and *leaf_out (optional) the leaf it is about.  The node's seal is not read: r0h_node_verify
+ * does that. */
+const char* r0h_root_verify_session_elf(const uint32_t* blob, size_t blob_words, const r0h_node* node, const uint8_t* journal,
+                                        size_t journal_len, const uint8_t* elf, size_t elf_len, int* verdict_out, size_t* leaf_out);
+/* ... the program image not in hand: the image proof (a receipt's `image_proof`) stands for it, checked as r0h_receipt_verify_image
+ * checks it (image_control_root NULL: derived from the image blob) */
+const char* r0h_root_verify_session_image(const uint32_t* blob, size_t blob_words, const r0h_node* node, const uint8_t* journal,
+                                          size_t journal_len, const uint32_t* image_blob, size_t image_blob_words,
+                                          const uint32_t* image_control_root, const uint32_t* image_seal, size_t image_seal_words,
+                                          const uint8_t* image_id, int* verdict_out, size_t* leaf_out);
 
 /* Optional per-kernel timing with HIP events on the context's stream (for bench.py's roofline object): enable, run,
  * then read {"kernel family": {"launches", "total_ms", "alg_bytes"}} as JSON.  Enabling resets the counters. */

@@ -6,6 +6,9 @@ a step consumes inside the proof (one Poseidon2 round per row); the consumed sea
 beside the proof, not inside it.
 
   python tools/bench_recursion.py --segments 8                                    one GPU, whole tree in-process
+  python tools/bench_recursion.py --segments 8 --compress 2                       ... and r0h_compress on 2 prover lanes against the sequential
+                                   fold in the same process (same root, word for word), plus a small trace-circuit session compressed
+                                   and its root held to its session (r0h_root_verify_session_elf)
   python tools/bench_recursion.py --gpus N --segments 64 [--backend gloo --share-device]
                                    N ranks, segments sharded: this process starts one fresh process per rank before touching the GPU
                                    (an outer `python -m torch.distributed.run ...` that sets WORLD_SIZE works too)
@@ -29,6 +32,8 @@ def main():
     ap.add_argument("--recursion-po2", type=int, default=18)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--root-out", default="", help="rank 0 writes the root seal there (.npy) for checking")
+    ap.add_argument("--compress", type=int, default=None, metavar="LANES", help="one GPU: also time r0h_compress on LANES prover lanes (1..4, 0 = the default) against the sequential fold")
+    ap.add_argument("--repeat", type=int, default=3, help="with --compress: timed repetitions of the fold and of compress, alternating; the minimum and all values are reported")
     ap.add_argument("--share-device", action="store_true", help="all ranks use GPU 0 (rehearsal on a one-GPU box; needs --backend gloo)")
     args = ap.parse_args()
 
@@ -57,6 +62,7 @@ def main():
         import torch.distributed as dist
         dist.init_process_group(args.backend, rank=rank, world_size=world,
                                 device_id=torch.device("cuda", device) if args.backend == "nccl" else None)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
     import hyperfridge_r0_amd as r0
     from hyperfridge_r0_amd import driver, recursion
 
@@ -108,6 +114,45 @@ def main():
         node = recursion.join_across_ranks(rec, node, rank, world, send, recv)
     barrier()
     t3 = time.perf_counter()
+    compress = None
+    if args.compress is not None:
+        if world > 1:
+            raise SystemExit("bench_recursion.py: --compress is one call on one GPU")
+        # the same seals as one composite receipt, compressed in one call; the sequential lift + fold again beside it, taking turns
+        receipt = r0.Receipt.new(journal, seals, claims)
+        fold_s, compress_s, same = [t2 - t1], [], True
+        for _ in range(max(1, args.repeat)):
+            hal.sync()
+            c0 = time.perf_counter()
+            root = rec.compress(receipt, lanes=args.compress)
+            hal.sync()
+            compress_s.append(time.perf_counter() - c0)
+            same = same and np.array_equal(root.seal, node.seal) and bytes(root.claim) == bytes(node.claim)
+            c0 = time.perf_counter()
+            again = rec.fold([rec.lift(seal, claims[s]) for seal, s in zip(seals, mine)])
+            hal.sync()
+            fold_s.append(time.perf_counter() - c0)
+            same = same and np.array_equal(again.seal, node.seal)
+        compress = {"lanes": args.compress, "compress_s": [round(v, 4) for v in compress_s], "sequential_fold_s": [round(v, 4) for v in fold_s],
+                    "compress_min_s": round(min(compress_s), 4), "sequential_fold_min_s": round(min(fold_s), 4), "same_root_word_for_word": bool(same)}
+        # a root's session can only be held to a trace-circuit receipt: a short guest proved from its own execution, compressed, verified
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from bench_session import elf_of
+        from test_rv32im import _guest
+        tblob = np.fromfile(entry.circuit_blob_path("trace"), dtype=np.uint32)
+        tc = hal.load_circuit(tblob, entry.code_object_path("trace"))
+        elf = elf_of(_guest(2000), 0x400)
+        session, _, _ = hal.prove_elf(tc, elf, [7, 0x01020304], segment_po2=11)
+        roots = {}
+        for _, s in session.seals():
+            size = r0.verify_seal(tblob, s)[2]
+            if size not in roots:
+                roots[size] = hal.code_root(tc, size)
+        trec = recursion.Recursor(hal, rec_blob, tblob, entry.code_object_path("recursion"), po2=17, segment_roots=roots)
+        troot = trec.compress(session, lanes=args.compress)
+        verdict = recursion.Recursor.verify_session(troot, tblob, session.journal, elf=elf)
+        compress.update({"session_segments": len(session.seals()), "session_root_verifies": bool(trec.verify(troot)), "session_root_verdict": verdict[0], "session_root_reason": verdict[1]})
+        trec.close(); tc.free()
     if rank == 0:
         # the root: its seal verifies bound to the recursion circuit's control root, names its claim, and that claim is the session's
         # end-to-end claim (first pre-state = the image id, last post-state, Halted(0), the journal's output digest)
@@ -127,7 +172,7 @@ def main():
             "cross_rank_join_steps": steps, "tree_latency_s": round(t3 - t1, 4), "end_to_end_s": round(t3 - t0, 4),
             "root_verifies": bool(root_ok), "root_claim_is_the_sessions_end_to_end_claim": bool(node.claim.digest() == end_to_end.digest()),
             "root_seal_words": int(node.seal.size), "backend": args.backend if world > 1 else "none",
-            "data": "synthetic"})
+            "data": "synthetic", **({"compress": compress} if compress else {})})
     code.free(); data.free(); seg_cc.free()
     rec.close(); seg.free()
     hal.close()
