@@ -94,7 +94,7 @@ struct r0h_ctx {
   // twiddles: tw_lo[d][i] = w^i, tw_hi[d][i] = w^(i*2^11) with w = ROU_{FWD,REV}[22]; d = 0 forward, 1 inverse
   uint32_t* tw_lo[2] = {nullptr, nullptr};
   uint32_t* tw_hi[2] = {nullptr, nullptr};
-  // local table: tw12[d][i] = ROU[12]^i for i < 2048
+  // local table: tw12[d][i] = ROU[TWL_BITS]^i for i < 2^(TWL_BITS - 1) = 4096 (the name is from when chunks ended at 2^12)
   uint32_t* tw12[2] = {nullptr, nullptr};
   // the same for w = ROU_{FWD,REV}[26] with 2^13 entries per level: outer pass of transforms above 2^22 points
   uint32_t* twb_lo[2] = {nullptr, nullptr};

@@ -1,14 +1,16 @@
-// Batched BabyBear NTTs for gfx950: LDS-staged radix-2 butterflies, two HBM passes for sizes above 2^12.
+// Batched BabyBear NTTs for gfx950: register-blocked radix-16 butterflies, one to three HBM passes.
 // Replaces risc0-zkp 3.0.4 hal `batch_interpolate_ntt` / `batch_expand_into_evaluate_ntt` / `batch_bit_reverse` /
 // `zk_shift` (core/ntt.rs; CUDA side in risc0-sys 1.5.0) -- SURVEY.md 8(a) a2-a5.
 //
-// Decomposition (N = 2^n = N1 * N2, N2 = 2^L contiguous, N1 = 2^H strided):
-//   forward  (bit-reversed coeffs -> natural evals, DIT):  local size-2^L DITs on contiguous chunks, then for every
-//            residue lo a size-2^H DIT over the chunk index with the inter-pass twiddle w_N^(brev_H(hi) * lo) on load;
-//   inverse  (natural evals -> bit-reversed coeffs, DIF):  the transpose: strided DIF first (twiddle on store), then
-//            local DIFs with the 1/N normalisation folded into the final store.
-// The strided pass stages a [2^H][T] tile (T consecutive residues, 64-byte rows at T=16) so every global access is a
-// run of T words; the local pass moves whole contiguous chunks.  Column-major batches map to blockIdx.y.
+// Decomposition (N = 2^n = N0 * N1 * N2; N2 = 2^L contiguous, N1 = 2^H strided, N0 = 2^outer = 16 or 1: split16_for):
+//   forward  (bit-reversed coeffs -> natural evals, DIT):  local size-2^L DITs on contiguous chunks (ntt_local16_kernel), then for
+//            every residue lo a size-2^H DIT over the chunk index with the inter-pass twiddle w^(brev_H(hi) * lo) on load
+//            (ntt_strided16_kernel), then one radix-16 butterfly over the top four index bits (ntt_outer16_kernel);
+//   inverse  (natural evals -> bit-reversed coeffs, DIF):  the transpose: outer, strided (twiddle on store), then local DIFs with
+//            the 1/N normalisation -- and on request the coset shift f(x) -> f(3x) -- folded into the final store.
+// Every thread keeps sixteen words in VGPRs and runs four butterfly layers on them per round; the rounds of a pass exchange through
+// LDS.  Column-major batches map to blockIdx.y.  Transforms below 2^8 points, and the contiguous pass of an expansion other than
+// x1 or x4, go through one small radix-2 kernel (ntt_local_kernel).
 #include <algorithm>
 
 #include "internal.hpp"
@@ -33,7 +35,8 @@ __device__ __forceinline__ uint32_t omega_n(const TwTables& t, uint32_t e, uint3
   return mul(t.lo[E & (TW_SIZE - 1)], t.hi[E >> TW_BITS]);
 }
 
-// One contiguous chunk of 2^L words per block.  DIR 0: DIT layers (expand_bits, L]; DIR 1: DIF layers L..1.
+// One contiguous chunk of 2^L words per block, radix-2 in LDS: whole transforms below 2^8 points, and the contiguous pass of a forward
+// transform whose expand_bits the radix-16 kernel has no instantiation for.  DIR 0: DIT layers (expand_bits, L]; DIR 1: DIF layers L..1.
 template <int DIR>
 __global__ __launch_bounds__(256) void ntt_local_kernel(uint32_t* out, const uint32_t* in /* may alias out */,
                                                          uint32_t L, uint32_t n_out, uint32_t expand_bits,
@@ -76,57 +79,8 @@ __global__ __launch_bounds__(256) void ntt_local_kernel(uint32_t* out, const uin
   }
 }
 
-// A [2^H][T] tile per block: T = 2^tlog consecutive residues lo, every chunk index hi.
-template <int DIR>
-__global__ __launch_bounds__(512) void ntt_strided_kernel(uint32_t* io, uint32_t n, uint32_t L, uint32_t H,
-                                                           uint32_t tlog, TwTables tw) {
-  extern __shared__ uint32_t s[];
-  const uint32_t T = 1u << tlog, tid = threadIdx.x, total = T << H;
-  uint32_t* col = io + ((size_t)blockIdx.y << n);
-  const uint32_t lo0 = blockIdx.x << tlog;
-  for (uint32_t idx = tid; idx < total; idx += 512) {
-    uint32_t hi = idx >> tlog, lo = lo0 + (idx & (T - 1));
-    uint32_t v = col[((size_t)hi << L) + lo];
-    if (DIR == 0) v = mul(v, omega_n(tw, bitrev(hi, H) * lo, n));
-    s[idx] = v;
-  }
-  __syncthreads();
-  if (DIR == 0) {
-    for (uint32_t l = 1; l <= H; l++) {
-      const uint32_t half = 1u << (l - 1);
-      for (uint32_t b = tid; b < total / 2; b += 512) {
-        uint32_t lo = b & (T - 1), jj = b >> tlog, j = jj & (half - 1);
-        uint32_t i0 = ((((jj >> (l - 1)) << l) + j) << tlog) + lo, i1 = i0 + (half << tlog);
-        uint32_t a = s[i0], t = mul(s[i1], tw.tw12[j << (TWL_BITS - l)]);
-        s[i0] = add(a, t);
-        s[i1] = sub(a, t);
-      }
-      __syncthreads();
-    }
-  } else {
-    for (uint32_t l = H; l >= 1; l--) {
-      const uint32_t half = 1u << (l - 1);
-      for (uint32_t b = tid; b < total / 2; b += 512) {
-        uint32_t lo = b & (T - 1), jj = b >> tlog, j = jj & (half - 1);
-        uint32_t i0 = ((((jj >> (l - 1)) << l) + j) << tlog) + lo, i1 = i0 + (half << tlog);
-        uint32_t a = s[i0], t = s[i1];
-        s[i0] = add(a, t);
-        s[i1] = mul(sub(a, t), tw.tw12[j << (TWL_BITS - l)]);
-      }
-      __syncthreads();
-    }
-  }
-  for (uint32_t idx = tid; idx < total; idx += 512) {
-    uint32_t hi = idx >> tlog, lo = lo0 + (idx & (T - 1));
-    uint32_t v = s[idx];
-    if (DIR == 1) v = mul(v, omega_n(tw, bitrev(hi, H) * lo, n));
-    col[((size_t)hi << L) + lo] = v;
-  }
-}
-
-
 // ------------------------------------------------------------------ radix-16 register-blocked kernels
-// Sub-transforms of size 2^m (8 <= m <= 12) are done in rounds of four butterfly layers: every thread keeps 16 words
+// Sub-transforms of size 2^m (8 <= m <= 13) are done in rounds of four butterfly layers: every thread keeps 16 words
 // in VGPRs, runs the layers of one 4-bit index field on them, and the block exchanges through LDS between rounds
 // (2 LDS writes + 2 LDS reads per word per pass instead of 2 per layer).  Twiddles of a round are
 // ROU[l]^(low bits) -- one table word per layer and thread -- times a constant 16th root of unity.
@@ -177,6 +131,17 @@ __device__ __forceinline__ uint32_t field_index(uint32_t rest0, int s, int j) {
   return ((r >> B) << (B + W)) | ((uint32_t)j << B) | (r & ((1u << B) - 1u));
 }
 
+// The sixteen words of thread q in the layout of the field <W, B> -- the thread's first set is q * (16 >> W), as for field_layers:
+// f(element index, register slot) for each of them
+template <int W, int B, class F>
+__device__ __forceinline__ void field_walk(uint32_t q, F&& f) {
+  constexpr int SETS = 16 >> W;
+#pragma unroll
+  for (int s = 0; s < SETS; s++)
+#pragma unroll
+    for (int j = 0; j < (1 << W); j++) f(field_index<W, B>(q * SETS, s, j), s * (1 << W) + j);
+}
+
 // Inter-pass twiddles of one thread: element e = q*16 + j needs w_n^(brev_H(e) * lo) with
 // brev_H(e) = brev_4(j) << (H-4) | brev_{H-4}(q), i.e. base * g^brev_4(j) with base = w_n^(brev(q) * lo), g = w_n^(lo << (H-4)):
 // four table words and 29 products per 16 elements instead of 32 table words and 16 products.
@@ -191,46 +156,34 @@ __device__ __forceinline__ void interpass_twiddles(uint32_t (&t)[16], const TwTa
   for (int j = 0; j < 16; j++) t[j] = gp[((j & 1) << 3) | ((j & 2) << 1) | ((j & 4) >> 1) | ((j & 8) >> 3)];
 }
 
-// [2^H][T] tile, H = 8 + WL, T = 16 * WORDS consecutive residues: forward = DIT over the chunk index with the inter-pass
-// twiddle on load, inverse = DIF with the twiddle on store.  Block = 16 << (H - 4) threads; a thread owns WORDS adjacent
-// residues (one radix-16 column each).  WORDS = 2 makes every global access a 128-byte row: 4.8 TB/s against 3.2 TB/s for
-// 64-byte rows in a plain copy of the same shape (tools/microbench/tile_copy_bench.hip).  The tile has to stay small enough
-// for two blocks per CU (load, butterflies and store of different blocks overlap): H <= 9, i.e. the contiguous pass takes
-// up to 2^13 words.  LDS rows are padded by two words so that the four row groups of a wave fall into different banks.
+// [2^H][32] tile, H = 8 + WL, 32 consecutive residues: forward = DIT over the chunk index with the inter-pass twiddle on load,
+// inverse = DIF with the twiddle on store.  Block = 16 << (H - 4) threads; a thread owns two adjacent residues (one radix-16
+// column each), so every global access is a 128-byte row: 4.8 TB/s against 3.2 TB/s for 64-byte rows in a plain copy of the same
+// shape (tools/microbench/tile_copy_bench.hip) -- the rows always hold that much, since a strided pass runs over chunks of at least
+// 2^8 words (split16_for).  The tile has to stay small enough for two blocks per CU (load, butterflies and store of different
+// blocks overlap): H <= 9, i.e. the contiguous pass takes up to 2^13 words.  LDS rows are padded by two words so that the four row
+// groups of a wave fall into different banks.
 // BIG: the rows are 2^L <= 2^18 words apart and the transform has more than 2^22 points (third level, see the host side).
-template <int WL, int DIR, int WORDS, int BIG = 0>
+template <int WL, int DIR, int BIG = 0>
 __global__ __launch_bounds__(16 << (4 + WL)) void ntt_strided16_kernel(uint32_t* io, const uint32_t* in, uint32_t n, uint32_t L, TwTables tw, W16 c) {
   extern __shared__ uint32_t s[];
   constexpr uint32_t H = 8 + WL;
-  constexpr uint32_t S = WORDS == 1 ? 16 : 16 * WORDS + 2;  // LDS row stride in words
+  constexpr int WORDS = 2;
+  constexpr uint32_t S = 16 * WORDS + 2;  // LDS row stride in words
   const uint32_t t = threadIdx.x & 15, q = threadIdx.x >> 4, lo = ((blockIdx.x << 4) + t) * WORDS;
-  uint32_t* col = io + ((size_t)blockIdx.y << n);
-  const uint32_t* src = in + ((size_t)blockIdx.y << n);  // may alias col (in-place): every word is read before its tile is written
+  uint32_t* col = io + ((size_t)blockIdx.y << n) + lo;
+  const uint32_t* src = in + ((size_t)blockIdx.y << n) + lo;  // may alias col (in-place): every word is read before its tile is written
   uint32_t x[WORDS][16];
-  auto gload = [&](const uint32_t* base, uint32_t row, int j) {
-    const uint32_t* p = base + ((size_t)row << L) + lo;
-    if (WORDS == 1) x[0][j] = p[0];
-    else { const uint2 v = *(const uint2*)p; x[0][j] = v.x; x[WORDS - 1][j] = v.y; }
-  };
-  auto gstore = [&](uint32_t row, int j) {
-    uint32_t* p = col + ((size_t)row << L) + lo;
-    if (WORDS == 1) p[0] = x[0][j];
-    else *(uint2*)p = make_uint2(x[0][j], x[WORDS - 1][j]);
-  };
-  auto sput = [&](uint32_t row, int j) {
-    uint32_t* p = s + row * S + t * WORDS;
-    if (WORDS == 1) p[0] = x[0][j];
-    else *(uint2*)p = make_uint2(x[0][j], x[WORDS - 1][j]);
-  };
-  auto sget = [&](uint32_t row, int j) {
-    const uint32_t* p = s + row * S + t * WORDS;
-    if (WORDS == 1) x[0][j] = p[0];
-    else { const uint2 v = *(const uint2*)p; x[0][j] = v.x; x[WORDS - 1][j] = v.y; }
-  };
+  auto take = [&](const uint32_t* p, int k) { const uint2 v = *(const uint2*)p; x[0][k] = v.x; x[1][k] = v.y; };
+  auto give = [&](uint32_t* p, int k) { *(uint2*)p = make_uint2(x[0][k], x[1][k]); };
+  auto gload = [&](uint32_t row, int k) { take(src + ((size_t)row << L), k); };
+  auto gstore = [&](uint32_t row, int k) { give(col + ((size_t)row << L), k); };
+  auto sput = [&](uint32_t row, int k) { give(s + row * S + t * WORDS, k); };
+  auto sget = [&](uint32_t row, int k) { take(s + row * S + t * WORDS, k); };
+  // rounds: rows' bits 0-3, 4-7, then WLs more bits at 8
   constexpr int WLs = WL == 0 ? 1 : WL, SETS = 16 >> WLs;
   if (DIR == 0) {
-#pragma unroll
-    for (int j = 0; j < 16; j++) gload(src, q * 16 + j, j);
+    field_walk<4, 0>(q, gload);
 #pragma unroll
     for (int w = 0; w < WORDS; w++) {
       uint32_t tws[16];
@@ -239,57 +192,37 @@ __global__ __launch_bounds__(16 << (4 + WL)) void ntt_strided16_kernel(uint32_t*
       for (int j = 0; j < 16; j++) x[w][j] = mul(x[w][j], tws[j]);
       field_layers<4, 0, 0, 0>(x[w], q, tw.tw12, c);
     }
-#pragma unroll
-    for (int j = 0; j < 16; j++) sput(q * 16 + j, j);
+    field_walk<4, 0>(q, sput);
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 16; j++) sget(field_index<4, 4>(q, 0, j), j);
+    field_walk<4, 4>(q, sget);
 #pragma unroll
     for (int w = 0; w < WORDS; w++) field_layers<4, 4, 0, 0>(x[w], q, tw.tw12, c);
     if (WL == 0) {
-#pragma unroll
-      for (int j = 0; j < 16; j++) gstore(field_index<4, 4>(q, 0, j), j);
+      field_walk<4, 4>(q, gstore);
       return;
     }
-#pragma unroll
-    for (int j = 0; j < 16; j++) sput(field_index<4, 4>(q, 0, j), j);
+    field_walk<4, 4>(q, sput);
     __syncthreads();
-#pragma unroll
-    for (int ss = 0; ss < SETS; ss++)
-#pragma unroll
-      for (int j = 0; j < (1 << WLs); j++) sget(field_index<WLs, 8>(q * SETS, ss, j), ss * (1 << WLs) + j);
+    field_walk<WLs, 8>(q, sget);
 #pragma unroll
     for (int w = 0; w < WORDS; w++) field_layers<WLs, 8, 0, 0>(x[w], q * SETS, tw.tw12, c);
-#pragma unroll
-    for (int ss = 0; ss < SETS; ss++)
-#pragma unroll
-      for (int j = 0; j < (1 << WLs); j++) gstore(field_index<WLs, 8>(q * SETS, ss, j), ss * (1 << WLs) + j);
+    field_walk<WLs, 8>(q, gstore);
   } else {
     if (WL != 0) {
-#pragma unroll
-      for (int ss = 0; ss < SETS; ss++)
-#pragma unroll
-        for (int j = 0; j < (1 << WLs); j++) gload(src, field_index<WLs, 8>(q * SETS, ss, j), ss * (1 << WLs) + j);
+      field_walk<WLs, 8>(q, gload);
 #pragma unroll
       for (int w = 0; w < WORDS; w++) field_layers<WLs, 8, 1, 0>(x[w], q * SETS, tw.tw12, c);
-#pragma unroll
-      for (int ss = 0; ss < SETS; ss++)
-#pragma unroll
-        for (int j = 0; j < (1 << WLs); j++) sput(field_index<WLs, 8>(q * SETS, ss, j), ss * (1 << WLs) + j);
+      field_walk<WLs, 8>(q, sput);
       __syncthreads();
-#pragma unroll
-      for (int j = 0; j < 16; j++) sget(field_index<4, 4>(q, 0, j), j);
+      field_walk<4, 4>(q, sget);
     } else {
-#pragma unroll
-      for (int j = 0; j < 16; j++) gload(src, field_index<4, 4>(q, 0, j), j);
+      field_walk<4, 4>(q, gload);
     }
 #pragma unroll
     for (int w = 0; w < WORDS; w++) field_layers<4, 4, 1, 0>(x[w], q, tw.tw12, c);
-#pragma unroll
-    for (int j = 0; j < 16; j++) sput(field_index<4, 4>(q, 0, j), j);
+    field_walk<4, 4>(q, sput);
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 16; j++) sget(q * 16 + j, j);
+    field_walk<4, 0>(q, sget);
 #pragma unroll
     for (int w = 0; w < WORDS; w++) {
       field_layers<4, 0, 1, 0>(x[w], q, tw.tw12, c);
@@ -298,12 +231,11 @@ __global__ __launch_bounds__(16 << (4 + WL)) void ntt_strided16_kernel(uint32_t*
 #pragma unroll
       for (int j = 0; j < 16; j++) x[w][j] = mul(x[w][j], tws[j]);
     }
-#pragma unroll
-    for (int j = 0; j < 16; j++) gstore(q * 16 + j, j);
+    field_walk<4, 0>(q, gstore);
   }
 }
 
-// Third level of transforms above 2^23 points: the top four bits of the index -- 16 rows, 2^(n-4) words apart.  A thread owns one
+// Third level (transforms of 2^14, 2^15 and above 2^23 points): the top four bits of the index -- 16 rows, 2^(n-4) words apart.  A thread owns one
 // residue: sixteen words, the inter-pass twiddles w_n^(brev_4(j) * lo) as powers of one table product, one radix-16 butterfly in
 // registers.  No LDS; every access of a wave is a 256-byte run per row, sixteen of them in flight per lane.
 template <int DIR>
@@ -328,9 +260,6 @@ __global__ __launch_bounds__(256) void ntt_outer16_kernel(uint32_t* io, const ui
 
 __device__ __forceinline__ uint32_t lds_pad(uint32_t e) { return e + (e >> 4); }
 
-// One contiguous chunk of 2^L words (L = 8 + WL) per block of 2^(L-4) threads.
-// Forward (DIR 0): DIT, optionally fed by an input EXP_BITS (0 or 2) times shorter (each word replicated 2^EXP_BITS times,
-// the first EXP_BITS layers skipped).  Inverse (DIR 1): DIF, result scaled by `scale`.
 struct ZkShift {        // optional fused f(x) -> f(3x) on the inverse transform's output
   const uint32_t* lo;   // 3^i, i < 2^11
   const uint32_t* hi;   // 3^(i << 11)
@@ -340,6 +269,9 @@ struct ZkShift {        // optional fused f(x) -> f(3x) on the inverse transform
   uint32_t g[16];       // 3^(k << (n - 4)), k < 16, n = log2 of the whole transform
 };
 
+// One contiguous chunk of 2^L words (L = 8 + WL) per block of 2^(L-4) threads.
+// Forward (DIR 0): DIT, optionally fed by an input 2^EXP_BITS (EXP_BITS 0 or 2) times shorter (each word replicated 2^EXP_BITS times,
+// the first EXP_BITS layers skipped).  Inverse (DIR 1): DIF, result scaled by `scale`.
 template <int WL, int DIR, int EXP_BITS, int ZK>
 __global__ __launch_bounds__(1 << (4 + (WL < 4 ? 4 : WL))) void ntt_local16_kernel(uint32_t* out, const uint32_t* in /* may alias out */, uint32_t n_out,
                                                            const uint32_t* __restrict__ tw12, W16 c, uint32_t scale, ZkShift zk) {
@@ -352,8 +284,11 @@ __global__ __launch_bounds__(1 << (4 + (WL < 4 ? 4 : WL))) void ntt_local16_kern
   const uint32_t base = blockIdx.x << L;
   uint32_t* dst = out + (colid << n_out) + base;
   uint32_t x[16];
+  auto put = [&](uint32_t e, int k) { s[lds_pad(e)] = x[k]; };
+  auto get = [&](uint32_t e, int k) { x[k] = s[lds_pad(e)]; };
   if (DIR == 0) {
     const uint32_t* src = in + (colid << (n_out - EXP_BITS)) + (base >> EXP_BITS);
+    auto store = [&](uint32_t e, int k) { dst[e] = x[k]; };
     if (EXP_BITS == 2) {
       uint4 v = *(const uint4*)(src + q * 4);
       const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
@@ -367,85 +302,52 @@ __global__ __launch_bounds__(1 << (4 + (WL < 4 ? 4 : WL))) void ntt_local16_kern
       }
     }
     field_layers<4, 0, 0, EXP_BITS>(x, q, tw12, c);
-#pragma unroll
-    for (int j = 0; j < 16; j++) s[lds_pad(q * 16 + j)] = x[j];
+    field_walk<4, 0>(q, put);
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 16; j++) x[j] = s[lds_pad(field_index<4, 4>(q, 0, j))];
+    field_walk<4, 4>(q, get);
     field_layers<4, 4, 0, 0>(x, q, tw12, c);
     if (WL == 0) {
-#pragma unroll
-      for (int j = 0; j < 16; j++) dst[field_index<4, 4>(q, 0, j)] = x[j];
+      field_walk<4, 4>(q, store);
       return;
     }
-#pragma unroll
-    for (int j = 0; j < 16; j++) s[lds_pad(field_index<4, 4>(q, 0, j))] = x[j];
+    field_walk<4, 4>(q, put);
     __syncthreads();
-#pragma unroll
-    for (int ss = 0; ss < SETS; ss++)
-#pragma unroll
-      for (int j = 0; j < (1 << WLs); j++) x[ss * (1 << WLs) + j] = s[lds_pad(field_index<WLs, 8>(q * SETS, ss, j))];
+    field_walk<WLs, 8>(q, get);
     field_layers<WLs, 8, 0, 0>(x, q * SETS, tw12, c);
-    if (WL == 5) {
-#pragma unroll
-      for (int j = 0; j < 16; j++) s[lds_pad(field_index<4, 8>(q, 0, j))] = x[j];
-      __syncthreads();
-#pragma unroll
-      for (int ss = 0; ss < 8; ss++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) x[ss * 2 + j] = s[lds_pad(field_index<1, 12>(q * 8, ss, j))];
-      field_layers<1, 12, 0, 0>(x, q * 8, tw12, c);
-#pragma unroll
-      for (int ss = 0; ss < 8; ss++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) dst[field_index<1, 12>(q * 8, ss, j)] = x[ss * 2 + j];
+    if (WL != 5) {
+      field_walk<WLs, 8>(q, store);
       return;
     }
-#pragma unroll
-    for (int ss = 0; ss < SETS; ss++)
-#pragma unroll
-      for (int j = 0; j < (1 << WLs); j++) dst[field_index<WLs, 8>(q * SETS, ss, j)] = x[ss * (1 << WLs) + j];
+    field_walk<4, 8>(q, put);
+    __syncthreads();
+    field_walk<1, 12>(q, get);
+    field_layers<1, 12, 0, 0>(x, q * 8, tw12, c);
+    field_walk<1, 12>(q, store);
   } else {
     const uint32_t* src = in + (colid << n_out) + base;
-    if (WL != 0) {
+    auto load = [&](uint32_t e, int k) { x[k] = src[e]; };
+    if (WL == 0) {
+      field_walk<4, 4>(q, load);
+    } else {
       if (WL == 5) {  // the one-layer round at bit 12 first, then through LDS into the bit-8 layout
-#pragma unroll
-        for (int ss = 0; ss < 8; ss++)
-#pragma unroll
-          for (int j = 0; j < 2; j++) x[ss * 2 + j] = src[field_index<1, 12>(q * 8, ss, j)];
+        field_walk<1, 12>(q, load);
         field_layers<1, 12, 1, 0>(x, q * 8, tw12, c);
-#pragma unroll
-        for (int ss = 0; ss < 8; ss++)
-#pragma unroll
-          for (int j = 0; j < 2; j++) s[lds_pad(field_index<1, 12>(q * 8, ss, j))] = x[ss * 2 + j];
+        field_walk<1, 12>(q, put);
         __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 16; j++) x[j] = s[lds_pad(field_index<4, 8>(q, 0, j))];
+        field_walk<4, 8>(q, get);
         __syncthreads();  // the next exchange reuses the buffer
       } else {
-#pragma unroll
-        for (int ss = 0; ss < SETS; ss++)
-#pragma unroll
-          for (int j = 0; j < (1 << WLs); j++) x[ss * (1 << WLs) + j] = src[field_index<WLs, 8>(q * SETS, ss, j)];
+        field_walk<WLs, 8>(q, load);
       }
       field_layers<WLs, 8, 1, 0>(x, q * SETS, tw12, c);
-#pragma unroll
-      for (int ss = 0; ss < SETS; ss++)
-#pragma unroll
-        for (int j = 0; j < (1 << WLs); j++) s[lds_pad(field_index<WLs, 8>(q * SETS, ss, j))] = x[ss * (1 << WLs) + j];
+      field_walk<WLs, 8>(q, put);
       __syncthreads();
-#pragma unroll
-      for (int j = 0; j < 16; j++) x[j] = s[lds_pad(field_index<4, 4>(q, 0, j))];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 16; j++) x[j] = src[field_index<4, 4>(q, 0, j)];
+      field_walk<4, 4>(q, get);
     }
     field_layers<4, 4, 1, 0>(x, q, tw12, c);
-#pragma unroll
-    for (int j = 0; j < 16; j++) s[lds_pad(field_index<4, 4>(q, 0, j))] = x[j];
+    field_walk<4, 4>(q, put);
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 16; j++) x[j] = s[lds_pad(q * 16 + j)];
+    field_walk<4, 0>(q, get);
     field_layers<4, 0, 1, 0>(x, q, tw12, c);
     if (ZK) {
       // position p = base + 16 q + j holds the coefficient of x^brev_n(p), brev_n(p) = brev_n(base + 16 q) + (brev_4(j) << (n - 4));
@@ -464,65 +366,43 @@ __global__ __launch_bounds__(1 << (4 + (WL < 4 ? 4 : WL))) void ntt_local16_kern
   }
 }
 
-__global__ void bit_reverse_kernel(uint32_t* io, uint32_t po2) {
+template <class T>  // uint32_t, or uint4 for extension elements
+__global__ void bit_reverse_kernel(T* io, uint32_t po2) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t* col = io + ((size_t)blockIdx.y << po2);
+  T* col = io + ((size_t)blockIdx.y << po2);
   uint32_t j = bitrev(i, po2);
   if (i < j) {
-    uint32_t a = col[i], b = col[j];
+    T a = col[i], b = col[j];
     col[i] = b;
     col[j] = a;
   }
 }
 
-// Tiled in-place bit reversal for po2 >= 10: i = (a:5 | m:po2-10 | b:5) maps to (brev b | brev m | brev a), so the 32x32
-// tile of middle index m lands, transposed and index-reversed, in the tile of brev(m).  A block swaps the pair
-// (m, brev m) through LDS: every global access is a 128-byte row.
-__global__ __launch_bounds__(256) void bit_reverse_tiled_kernel(uint32_t* io, uint32_t po2) {
-  __shared__ uint32_t ta[32][33], tb[32][33];
-  const uint32_t mbits = po2 - 10, m = blockIdx.x, mr = bitrev(m, mbits);
+// Tiled in-place bit reversal for po2 >= 2 EB, tiles of E x E elements, E = 2^EB: i = (a:EB | m:po2-2EB | b:EB) maps to
+// (brev b | brev m | brev a), so the tile of middle index m lands, transposed and index-reversed, in the tile of brev(m).  A block
+// swaps the pair (m, brev m) through LDS.  32 x 32 words: every global access is a 128-byte row; 16 x 16 uint4: 256-byte rows.
+template <class T, int EB>
+__global__ __launch_bounds__(256) void bit_reverse_tiled_kernel(T* io, uint32_t po2) {
+  constexpr uint32_t E = 1u << EB, ROWS = 256 / E;  // rows of a tile that the block moves at a time
+  __shared__ T ta[E][E + 1], tb[E][E + 1];
+  const uint32_t mbits = po2 - 2 * EB, m = blockIdx.x, mr = bitrev(m, mbits);
   if (m > mr) return;
-  uint32_t* col = io + ((size_t)blockIdx.y << po2);
-  const uint32_t b = threadIdx.x & 31, a0 = threadIdx.x >> 5;
+  T* col = io + ((size_t)blockIdx.y << po2);
+  const uint32_t b = threadIdx.x & (E - 1), a0 = threadIdx.x >> EB;
 #pragma unroll
-  for (uint32_t k = 0; k < 4; k++) {
-    uint32_t a = a0 + 8 * k;
-    ta[a][b] = col[((size_t)a << (po2 - 5)) + (m << 5) + b];
-    if (m != mr) tb[a][b] = col[((size_t)a << (po2 - 5)) + (mr << 5) + b];
+  for (uint32_t k = 0; k < E / ROWS; k++) {
+    const uint32_t a = a0 + ROWS * k;
+    ta[a][b] = col[((size_t)a << (po2 - EB)) + (m << EB) + b];
+    if (m != mr) tb[a][b] = col[((size_t)a << (po2 - EB)) + (mr << EB) + b];
   }
   __syncthreads();
-  const uint32_t rb = __brev(b) >> 27;
+  const uint32_t rb = __brev(b) >> (32 - EB);
 #pragma unroll
-  for (uint32_t k = 0; k < 4; k++) {
-    uint32_t a = a0 + 8 * k, ra = __brev(a) >> 27;
+  for (uint32_t k = 0; k < E / ROWS; k++) {
+    const uint32_t a = a0 + ROWS * k, ra = __brev(a) >> (32 - EB);
     // new tile(mr)[a][b] = old tile(m)[brev b][brev a]; and symmetrically
-    col[((size_t)a << (po2 - 5)) + (mr << 5) + b] = ta[rb][ra];
-    if (m != mr) col[((size_t)a << (po2 - 5)) + (m << 5) + b] = tb[rb][ra];
-  }
-}
-
-// the same pair-of-tiles swap for 16-byte (extension) elements: 16x16 tiles, 256-byte rows
-__global__ __launch_bounds__(256) void bit_reverse_ext_tiled_kernel(uint4* io, uint32_t po2) {
-  __shared__ uint4 ta[16][17], tb[16][17];
-  const uint32_t mbits = po2 - 8, m = blockIdx.x, mr = bitrev(m, mbits);
-  if (m > mr) return;
-  uint4* col = io + ((size_t)blockIdx.y << po2);
-  const uint32_t b = threadIdx.x & 15, a = threadIdx.x >> 4;
-  ta[a][b] = col[((size_t)a << (po2 - 4)) + (m << 4) + b];
-  if (m != mr) tb[a][b] = col[((size_t)a << (po2 - 4)) + (mr << 4) + b];
-  __syncthreads();
-  const uint32_t rb = __brev(b) >> 28, ra = __brev(a) >> 28;
-  col[((size_t)a << (po2 - 4)) + (mr << 4) + b] = ta[rb][ra];
-  if (m != mr) col[((size_t)a << (po2 - 4)) + (m << 4) + b] = tb[rb][ra];
-}
-__global__ void bit_reverse_ext_kernel(uint4* io, uint32_t po2) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  uint4* col = io + ((size_t)blockIdx.y << po2);
-  uint32_t j = bitrev(i, po2);
-  if (i < j) {
-    uint4 a = col[i], b = col[j];
-    col[i] = b;
-    col[j] = a;
+    col[((size_t)a << (po2 - EB)) + (mr << EB) + b] = ta[rb][ra];
+    if (m != mr) col[((size_t)a << (po2 - EB)) + (m << EB) + b] = tb[rb][ra];
   }
 }
 
@@ -535,41 +415,22 @@ __global__ void zk_shift_kernel(uint32_t* io, uint32_t po2, const uint32_t* pow3
   col[i] = mul(col[i], s);
 }
 
-struct Split {
-  uint32_t L, H, tlog;
-};
-static Split split_for(uint32_t n) {
-  Split sp;
-  if (n <= 12) { sp.L = n; sp.H = 0; sp.tlog = 0; return sp; }
-  uint32_t H = n / 2;
-  if (H > 10) H = 10;
-  if (n - H > 12) H = n - 12;
-  sp.H = H;
-  sp.L = n - H;
-  sp.tlog = 14 - H;
-  if (sp.tlog > sp.L) sp.tlog = sp.L;
-  return sp;
-}
-
-
+constexpr uint32_t LOCAL16_MIN = 8;  // the radix-16 contiguous pass takes chunks of 2^8 .. 2^13 words; smaller transforms are radix-2
 struct Split16 {
-  bool use16;      // radix-16 kernels apply
-  uint32_t L, H;   // contiguous chunk 2^L, strided 2^H (0 = single pass)
-  uint32_t outer;  // third level (domains above 2^23): a column is 2^outer blocks of 2^(L + H) words (0 = none)
+  uint32_t L, H;   // contiguous chunk 2^L, strided 2^H (0 = no strided pass)
+  uint32_t outer;  // third level: a column is 2^outer blocks of 2^(L + H) words (0 = none)
 };
-// 2^16 .. 2^22: two passes (H = 8 or 9: two strided tiles per CU).  2^23: two passes with 2^10-row tiles (139 KB of LDS, one
-// block per CU) and the ROU[26] tables.  2^24 .. 2^26 (segments of 2^22 .. 2^24 rows -- what 288 GB of HBM has room for): three
-// levels.  A column's 16 blocks of 2^20 .. 2^22 contiguous words are transformed like 16 columns by the two tuned passes above,
-// and one register-only radix-16 pass runs across the blocks (ntt_outer16_kernel).
+// Up to 2^13: one contiguous pass.  2^14, 2^15: sixteen contiguous blocks of 2^10, 2^11 and the pass over the top four bits.
+// 2^16 .. 2^22: two passes (H = 8 or 9: two strided tiles per CU).  2^23: two passes with 2^10-row tiles (139 KB of LDS, one block
+// per CU) and the ROU[26] tables.  2^24 .. 2^26 (segments of 2^22 .. 2^24 rows -- what 288 GB of HBM has room for): three levels.
+// With a third level a column's 16 blocks are transformed like 16 columns by the passes below it, and one register-only radix-16
+// pass runs across the blocks (ntt_outer16_kernel).
 static Split16 split16_for(uint32_t n) {
-  Split16 sp{false, n, 0, 0};
-  if (n >= 8 && n <= 12) { sp.use16 = true; return sp; }
-  if (n >= 16 && n <= MAX_DOMAIN_PO2) {
-    sp.use16 = true;
-    if (n > 23) { sp.outer = 4; n -= 4; }
-    sp.H = n <= 20 ? 8 : (n <= 22 ? 9 : 10);  // the contiguous pass takes up to 2^13 words
-    sp.L = n - sp.H;
-  }
+  Split16 sp{n, 0, 0};
+  if (n <= 13) return sp;
+  if (n <= 15 || n > 23) { sp.outer = 4; n -= 4; }
+  if (n >= 16) sp.H = n <= 20 ? 8 : (n <= 22 ? 9 : 10);  // the contiguous pass takes up to 2^13 words
+  sp.L = n - sp.H;
   return sp;
 }
 static W16 make_w16(bool inverse) {
@@ -581,54 +442,55 @@ static W16 make_w16(bool inverse) {
   }
   return c;
 }
-static size_t local16_lds_bytes(uint32_t L) { return (((size_t)1 << L) + ((size_t)1 << (L - 4))) * 4; }
 
 constexpr size_t GRID_Y_MAX = 32768;  // columns per launch (blockIdx.y): the blocks of large transforms count as columns
+
+// `count` columns, 2^n_out words apart at `out`, as chunks of 2^L words through the radix-2 kernel
+template <int DIR>
+static void launch_local(r0h_ctx* ctx, uint32_t L, size_t count, uint32_t* out, const uint32_t* in, uint32_t n_out, uint32_t expand_bits, const uint32_t* tw12,
+                         uint32_t scale) {
+  for (size_t c0 = 0; c0 < count; c0 += GRID_Y_MAX) {
+    const dim3 grid(1u << (n_out - L), (uint32_t)std::min(count - c0, GRID_Y_MAX));
+    hipLaunchKernelGGL(ntt_local_kernel<DIR>, grid, dim3(256), (size_t)4 << L, ctx->stream, out + (c0 << n_out), in + (c0 << (n_out - expand_bits)), L, n_out,
+                       expand_bits, tw12, scale);
+  }
+}
+
+// The instantiations that exist: chunks of 2^8 .. 2^13 words; strided tiles of 2^8 .. 2^10 rows
+using Local16Kernel = void (*)(uint32_t*, const uint32_t*, uint32_t, const uint32_t*, W16, uint32_t, ZkShift);
+template <int DIR, int EXP_BITS, int ZK>
+static Local16Kernel local16_kernel(uint32_t L) {
+  static const Local16Kernel k[6] = {ntt_local16_kernel<0, DIR, EXP_BITS, ZK>, ntt_local16_kernel<1, DIR, EXP_BITS, ZK>, ntt_local16_kernel<2, DIR, EXP_BITS, ZK>,
+                                     ntt_local16_kernel<3, DIR, EXP_BITS, ZK>, ntt_local16_kernel<4, DIR, EXP_BITS, ZK>, ntt_local16_kernel<5, DIR, EXP_BITS, ZK>};
+  return k[L - 8];
+}
+using Strided16Kernel = void (*)(uint32_t*, const uint32_t*, uint32_t, uint32_t, TwTables, W16);
+template <int DIR, int BIG>
+static Strided16Kernel strided16_kernel(uint32_t H) {
+  static const Strided16Kernel k[3] = {ntt_strided16_kernel<0, DIR, BIG>, ntt_strided16_kernel<1, DIR, BIG>, ntt_strided16_kernel<2, DIR, BIG>};
+  return k[H - 8];
+}
+static size_t local16_lds_bytes(uint32_t L) { return (((size_t)1 << L) + ((size_t)1 << (L - 4))) * 4; }
+constexpr size_t strided16_lds_bytes(uint32_t H) { return ((size_t)1 << H) * (16 * 2 + 2) * 4; }
 
 template <int DIR, int EXP_BITS, int ZK = 0>
 static void launch_local16(r0h_ctx* ctx, uint32_t L, uint32_t blocks_x, size_t count, uint32_t* out, const uint32_t* in, uint32_t n_out, const uint32_t* tw12,
                            const W16& c, uint32_t scale, const ZkShift& zk = ZkShift{}) {
-  const size_t lds = local16_lds_bytes(L);
-  const dim3 block(1u << (L - 4));
+  const Local16Kernel kernel = local16_kernel<DIR, EXP_BITS, ZK>(L);
   for (size_t c0 = 0; c0 < count; c0 += GRID_Y_MAX) {
     const dim3 grid(blocks_x, (uint32_t)std::min(count - c0, GRID_Y_MAX));
-    uint32_t* o = out + (c0 << n_out);
-    const uint32_t* i = in + (c0 << (DIR == 0 ? n_out - EXP_BITS : n_out));
-    switch (L) {
-      case 8: hipLaunchKernelGGL((ntt_local16_kernel<0, DIR, EXP_BITS, ZK>), grid, block, lds, ctx->stream, o, i, n_out, tw12, c, scale, zk); break;
-      case 9: hipLaunchKernelGGL((ntt_local16_kernel<1, DIR, EXP_BITS, ZK>), grid, block, lds, ctx->stream, o, i, n_out, tw12, c, scale, zk); break;
-      case 10: hipLaunchKernelGGL((ntt_local16_kernel<2, DIR, EXP_BITS, ZK>), grid, block, lds, ctx->stream, o, i, n_out, tw12, c, scale, zk); break;
-      case 11: hipLaunchKernelGGL((ntt_local16_kernel<3, DIR, EXP_BITS, ZK>), grid, block, lds, ctx->stream, o, i, n_out, tw12, c, scale, zk); break;
-      case 12: hipLaunchKernelGGL((ntt_local16_kernel<4, DIR, EXP_BITS, ZK>), grid, block, lds, ctx->stream, o, i, n_out, tw12, c, scale, zk); break;
-      default: hipLaunchKernelGGL((ntt_local16_kernel<5, DIR, EXP_BITS, ZK>), grid, block, lds, ctx->stream, o, i, n_out, tw12, c, scale, zk); break;
-    }
-  }
-}
-constexpr size_t strided16_lds_bytes(uint32_t H) { return ((size_t)1 << H) * (16 * 2 + 2) * 4; }
-template <int WL, int DIR, int BIG>
-static void launch_strided16_wl(r0h_ctx* ctx, uint32_t blocks_x, size_t count, uint32_t* io, const uint32_t* in, uint32_t n, uint32_t L, const TwTables& tw,
-                                const W16& c) {
-  constexpr uint32_t H = 8 + WL;
-  const dim3 block(16u << (H - 4));
-  for (size_t c0 = 0; c0 < count; c0 += GRID_Y_MAX) {
-    const uint32_t cols = (uint32_t)std::min(count - c0, GRID_Y_MAX);
-    uint32_t* o = io + (c0 << n);
-    const uint32_t* i = in + (c0 << n);
-    if (L >= 5) {  // two residues per thread: 128-byte rows
-      // tiles above 64 KB of LDS: the limit was raised for this device when its first context was created (ntt_init_device)
-      hipLaunchKernelGGL((ntt_strided16_kernel<WL, DIR, 2, BIG>), dim3(blocks_x / 2, cols), block, strided16_lds_bytes(H), ctx->stream, o, i, n, L, tw, c);
-    } else {
-      hipLaunchKernelGGL((ntt_strided16_kernel<WL, DIR, 1, BIG>), dim3(blocks_x, cols), block, ((size_t)16 << H) * 4, ctx->stream, o, i, n, L, tw, c);
-    }
+    hipLaunchKernelGGL(kernel, grid, dim3(1u << (L - 4)), local16_lds_bytes(L), ctx->stream, out + (c0 << n_out),
+                       in + (c0 << (DIR == 0 ? n_out - EXP_BITS : n_out)), n_out, tw12, c, scale, zk);
   }
 }
 template <int DIR, int BIG>
-static void launch_strided16(r0h_ctx* ctx, uint32_t H, uint32_t blocks_x, size_t count, uint32_t* io, const uint32_t* in, uint32_t n, uint32_t L,
+static void launch_strided16(r0h_ctx* ctx, uint32_t H, size_t count, uint32_t* io, const uint32_t* in, uint32_t n, uint32_t L,
                              const TwTables& tw, const W16& c) {
-  switch (H) {
-    case 8: launch_strided16_wl<0, DIR, BIG>(ctx, blocks_x, count, io, in, n, L, tw, c); break;
-    case 9: launch_strided16_wl<1, DIR, BIG>(ctx, blocks_x, count, io, in, n, L, tw, c); break;
-    default: launch_strided16_wl<2, DIR, BIG>(ctx, blocks_x, count, io, in, n, L, tw, c); break;
+  const Strided16Kernel kernel = strided16_kernel<DIR, BIG>(H);
+  for (size_t c0 = 0; c0 < count; c0 += GRID_Y_MAX) {
+    const dim3 grid(1u << (L - 5), (uint32_t)std::min(count - c0, GRID_Y_MAX));  // 32 residues per block
+    // tiles above 64 KB of LDS: the limit was raised for this device when its first context was created (ntt_init_device)
+    hipLaunchKernelGGL(kernel, grid, dim3(16u << (H - 4)), strided16_lds_bytes(H), ctx->stream, io + (c0 << n), in + (c0 << n), n, L, tw, c);
   }
 }
 
@@ -643,26 +505,19 @@ static void launch_outer16(r0h_ctx* ctx, size_t count, uint32_t* io, const uint3
 // Dynamic LDS above the 64 KB default has to be asked for per kernel instantiation and device.  Done for every instantiation
 // that needs it when a context is created (r0h_ctx_create, after hipSetDevice), so no launch can race the request and a
 // refusal is reported instead of surfacing later as "launch failed".
-template <int WL, int DIR, int BIG>
-static const char* raise_lds_limit() {
-  constexpr size_t lds = strided16_lds_bytes(8 + WL);
-  if (lds <= 65536) return nullptr;
-  R0H_TRY_HIP(hipFuncSetAttribute((const void*)ntt_strided16_kernel<WL, DIR, 2, BIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+template <int DIR, int BIG>
+static const char* raise_lds_limits() {
+  for (uint32_t H = 8; H <= 10; H++) {
+    const size_t lds = strided16_lds_bytes(H);
+    if (lds > 65536) R0H_TRY_HIP(hipFuncSetAttribute((const void*)(strided16_kernel<DIR, BIG>(H)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
   return nullptr;
 }
 const char* ntt_init_device() {
-  R0H_TRY((raise_lds_limit<0, 0, 0>()));
-  R0H_TRY((raise_lds_limit<0, 1, 0>()));
-  R0H_TRY((raise_lds_limit<1, 0, 0>()));
-  R0H_TRY((raise_lds_limit<1, 1, 0>()));
-  R0H_TRY((raise_lds_limit<2, 0, 0>()));
-  R0H_TRY((raise_lds_limit<2, 1, 0>()));
-  R0H_TRY((raise_lds_limit<0, 0, 1>()));
-  R0H_TRY((raise_lds_limit<0, 1, 1>()));
-  R0H_TRY((raise_lds_limit<1, 0, 1>()));
-  R0H_TRY((raise_lds_limit<1, 1, 1>()));
-  R0H_TRY((raise_lds_limit<2, 0, 1>()));
-  R0H_TRY((raise_lds_limit<2, 1, 1>()));
+  R0H_TRY((raise_lds_limits<0, 0>()));
+  R0H_TRY((raise_lds_limits<1, 0>()));
+  R0H_TRY((raise_lds_limits<0, 1>()));
+  R0H_TRY((raise_lds_limits<1, 1>()));
   return nullptr;
 }
 
@@ -676,8 +531,8 @@ static const char* zk_shift_cols(r0h_ctx* ctx, uint32_t* io, size_t count, uint3
   return launch_ok("zk_shift_kernel");
 }
 
-// Radix-16 forward transform of `count` columns (bit-reversed coefficients, 2^(n - expand_bits) words apart at `in`; natural
-// evaluations, 2^n words apart at `out`); split16_for(n).use16 holds and expand_bits is 0 or 2.
+// Forward transform of `count` columns: bit-reversed coefficients, 2^(n - expand_bits) words apart at `in`; natural evaluations,
+// 2^n words apart at `out`; expand_bits < split16_for(n).L
 static const char* forward16(r0h_ctx* ctx, uint32_t* out, const uint32_t* in, size_t count, uint32_t n, uint32_t expand_bits) {
   const Split16 sp = split16_for(n);
   const W16 c = make_w16(false);
@@ -687,14 +542,15 @@ static const char* forward16(r0h_ctx* ctx, uint32_t* out, const uint32_t* in, si
   const double words = (double)((size_t)1 << n);
   {
     KScope ks(ctx, "ntt_local_kernel", 4.0 * count * (words + (double)((size_t)1 << (n - expand_bits))));
-    if (expand_bits == 2) launch_local16<0, 2>(ctx, sp.L, 1u << (n_in - sp.L), blocks, out, in, n_in, tw.tw12, c, 0u);
+    if (sp.L < LOCAL16_MIN || (expand_bits != 0 && expand_bits != 2)) launch_local<0>(ctx, sp.L, blocks, out, in, n_in, expand_bits, tw.tw12, 0u);
+    else if (expand_bits == 2) launch_local16<0, 2>(ctx, sp.L, 1u << (n_in - sp.L), blocks, out, in, n_in, tw.tw12, c, 0u);
     else launch_local16<0, 0>(ctx, sp.L, 1u << (n_in - sp.L), blocks, out, in, n_in, tw.tw12, c, 0u);
   }
-  R0H_TRY(launch_ok("ntt_local16_kernel<fwd>"));
+  R0H_TRY(launch_ok("ntt_local_kernel<fwd>"));
   if (sp.H) {
     KScope ks(ctx, "ntt_strided_kernel", 8.0 * count * words);
-    if (n_in > TW_TOP) launch_strided16<0, 1>(ctx, sp.H, 1u << (sp.L - 4), blocks, out, out, n_in, sp.L, twb, c);
-    else launch_strided16<0, 0>(ctx, sp.H, 1u << (sp.L - 4), blocks, out, out, n_in, sp.L, tw, c);
+    if (n_in > TW_TOP) launch_strided16<0, 1>(ctx, sp.H, blocks, out, out, n_in, sp.L, twb, c);
+    else launch_strided16<0, 0>(ctx, sp.H, blocks, out, out, n_in, sp.L, tw, c);
     R0H_TRY(launch_ok("ntt_strided16_kernel<fwd>"));
   }
   if (sp.outer) {
@@ -722,14 +578,16 @@ static const char* inverse16(r0h_ctx* ctx, uint32_t* io, const uint32_t* src, si
   }
   if (sp.H) {
     KScope ks(ctx, "ntt_strided_kernel", 8.0 * count * words);
-    if (n_in > TW_TOP) launch_strided16<1, 1>(ctx, sp.H, 1u << (sp.L - 4), blocks, io, cur, n_in, sp.L, twb, c);
-    else launch_strided16<1, 0>(ctx, sp.H, 1u << (sp.L - 4), blocks, io, cur, n_in, sp.L, tw, c);
+    if (n_in > TW_TOP) launch_strided16<1, 1>(ctx, sp.H, blocks, io, cur, n_in, sp.L, twb, c);
+    else launch_strided16<1, 0>(ctx, sp.H, blocks, io, cur, n_in, sp.L, tw, c);
     R0H_TRY(launch_ok("ntt_strided16_kernel<inv>"));
     cur = io;
   }
   {
     KScope ks(ctx, "ntt_local_kernel", 8.0 * count * words);
-    if (zk_shift) {  // fused into the last pass: no separate sweep over the coefficients
+    if (sp.L < LOCAL16_MIN) {
+      launch_local<1>(ctx, sp.L, blocks, io, cur, n_in, 0u, tw.tw12, norm);
+    } else if (zk_shift) {  // fused into the last pass: no separate sweep over the coefficients
       ZkShift zk{ctx->pow3_lo, ctx->pow3_hi, ctx->pow3_top, sp.outer, {0}};
       const uint32_t g = fpow(enc(3), (uint64_t)1 << (n - 4));
       uint32_t pw = ONE;
@@ -739,7 +597,35 @@ static const char* inverse16(r0h_ctx* ctx, uint32_t* io, const uint32_t* src, si
       launch_local16<1, 0>(ctx, sp.L, 1u << (n_in - sp.L), blocks, io, cur, n_in, tw.tw12, c, norm);
     }
   }
-  return launch_ok("ntt_local16_kernel<inv>");
+  R0H_TRY(launch_ok("ntt_local_kernel<inv>"));
+  if (sp.L < LOCAL16_MIN && zk_shift) return zk_shift_cols(ctx, io, count, n);  // the radix-2 kernel carries no shift: a sweep of its own
+  return nullptr;
+}
+
+const char* interpolate_ntt(r0h_ctx* ctx, r0h_buf* io, const r0h_buf* src, uint32_t count, uint32_t po2, bool zk_shift) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && io && src, "r0h_batch_interpolate_ntt: NULL argument");
+  R0H_REQUIRE(((size_t)count << po2) * 4 <= src->bytes, "r0h_batch_interpolate_ntt: %u columns of 2^%u exceed the source buffer", count, po2);
+  R0H_REQUIRE(po2 >= 1 && po2 <= MAX_DOMAIN_PO2, "r0h_batch_interpolate_ntt: po2 %u outside [1, %u]", po2, MAX_DOMAIN_PO2);
+  R0H_REQUIRE(((size_t)count << po2) * 4 <= io->bytes, "r0h_batch_interpolate_ntt: %u columns of 2^%u exceed the buffer", count, po2);
+  if (!count) return nullptr;
+  return inverse16(ctx, u32(io), u32(src), count, po2, zk_shift);
+  R0H_GUARD_END
+}
+
+const char* bit_reverse_ext(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t po2) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && io && po2 <= MAX_DOMAIN_PO2, "bit_reverse_ext: bad argument");
+  R0H_REQUIRE(((size_t)count << po2) * 16 <= io->bytes, "bit_reverse_ext: %u columns of 2^%u exceed the buffer", count, po2);
+  if (!count || po2 == 0) return nullptr;
+  KScope ks(ctx, "bit_reverse_kernel", 32.0 * count * (double)(1u << po2));
+  if (po2 >= 8) {
+    hipLaunchKernelGGL((bit_reverse_tiled_kernel<uint4, 4>), dim3(1u << (po2 - 8), count), dim3(256), 0, ctx->stream, (uint4*)io->ptr, po2);
+  } else {
+    hipLaunchKernelGGL(bit_reverse_kernel<uint4>, dim3(1, count), dim3(1u << po2), 0, ctx->stream, (uint4*)io->ptr, po2);
+  }
+  return launch_ok("bit_reverse_ext kernel");
+  R0H_GUARD_END
 }
 
 }  // namespace r0h
@@ -748,41 +634,8 @@ using namespace r0h;
 
 extern "C" {
 
-const char* r0h_batch_interpolate_ntt(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t po2) { return r0h::interpolate_ntt(ctx, io, io, count, po2, false); }
-const char* r0h_batch_interpolate_ntt_zk_shift(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t po2) { return r0h::interpolate_ntt(ctx, io, io, count, po2, true); }
-
-}  // extern "C"
-
-namespace r0h {
-const char* interpolate_ntt(r0h_ctx* ctx, r0h_buf* io, const r0h_buf* src, uint32_t count, uint32_t po2, bool zk_shift) {
-  R0H_GUARD_BEGIN
-  R0H_REQUIRE(ctx && io && src, "r0h_batch_interpolate_ntt: NULL argument");
-  R0H_REQUIRE(((size_t)count << po2) * 4 <= src->bytes, "r0h_batch_interpolate_ntt: %u columns of 2^%u exceed the source buffer", count, po2);
-  R0H_REQUIRE(po2 >= 1 && po2 <= MAX_DOMAIN_PO2, "r0h_batch_interpolate_ntt: po2 %u outside [1, %u]", po2, MAX_DOMAIN_PO2);
-  R0H_REQUIRE(((size_t)count << po2) * 4 <= io->bytes, "r0h_batch_interpolate_ntt: %u columns of 2^%u exceed the buffer", count, po2);
-  if (!count) return nullptr;
-  if (split16_for(po2).use16) return inverse16(ctx, u32(io), u32(src), count, po2, zk_shift);
-  const uint32_t norm = inv(enc(1u << po2));
-  TwTables tw{ctx->tw_lo[1], ctx->tw_hi[1], ctx->tw12[1]};
-  if (src->ptr != io->ptr) R0H_TRY_HIP(hipMemcpyAsync(io->ptr, src->ptr, ((size_t)count << po2) * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  const Split sp = split_for(po2);
-  if (sp.H) {
-    KScope ks(ctx, "ntt_strided_kernel", 8.0 * count * (double)(1u << po2));
-    dim3 grid(1u << (sp.L - sp.tlog), count);
-    hipLaunchKernelGGL(ntt_strided_kernel<1>, grid, dim3(512), (size_t)4 << (sp.H + sp.tlog), ctx->stream, u32(io), po2, sp.L, sp.H, sp.tlog, tw);
-    R0H_TRY(launch_ok("ntt_strided_kernel<inv>"));
-  }
-  KScope ks(ctx, "ntt_local_kernel", 8.0 * count * (double)(1u << po2));
-  dim3 grid(1u << (po2 - sp.L), count);
-  hipLaunchKernelGGL(ntt_local_kernel<1>, grid, dim3(256), (size_t)4 << sp.L, ctx->stream, u32(io), u32(io), sp.L, po2, 0u, tw.tw12, norm);
-  R0H_TRY(launch_ok("ntt_local_kernel<inv>"));
-  if (zk_shift) return r0h_zk_shift(ctx, io, count, po2);  // small sizes: separate pass
-  return nullptr;
-  R0H_GUARD_END
-}
-}  // namespace r0h
-
-extern "C" {
+const char* r0h_batch_interpolate_ntt(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t po2) { return interpolate_ntt(ctx, io, io, count, po2, false); }
+const char* r0h_batch_interpolate_ntt_zk_shift(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t po2) { return interpolate_ntt(ctx, io, io, count, po2, true); }
 
 const char* r0h_batch_expand_into_evaluate_ntt(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* in, uint32_t count,
                                                uint32_t in_po2, uint32_t expand_bits) {
@@ -794,24 +647,8 @@ const char* r0h_batch_expand_into_evaluate_ntt(r0h_ctx* ctx, r0h_buf* out, const
               "r0h_batch_expand_into_evaluate_ntt: %u columns exceed the buffers", count);
   R0H_REQUIRE(out->ptr != in->ptr || expand_bits == 0, "r0h_batch_expand_into_evaluate_ntt: in-place expansion is not supported");
   if (!count) return nullptr;
-  if (split16_for(n).use16 && (expand_bits == 0 || expand_bits == 2)) return forward16(ctx, u32(out), u32(in), count, n, expand_bits);
-  R0H_REQUIRE(n <= TW_TOP, "r0h_batch_expand_into_evaluate_ntt: expand_bits %u is not supported above 2^%u points (0 or 2 are)", expand_bits, TW_TOP);
-  TwTables tw{ctx->tw_lo[0], ctx->tw_hi[0], ctx->tw12[0]};
-  const Split sp = split_for(n);
-  R0H_REQUIRE(expand_bits < sp.L, "r0h_batch_expand_into_evaluate_ntt: expand_bits %u too large for size 2^%u", expand_bits, n);
-  dim3 grid(1u << (n - sp.L), count);
-  {
-    KScope ks(ctx, "ntt_local_kernel", 4.0 * count * ((double)(1u << n) + (double)(1u << in_po2)));
-    hipLaunchKernelGGL(ntt_local_kernel<0>, grid, dim3(256), (size_t)4 << sp.L, ctx->stream, u32(out), u32(in), sp.L, n, expand_bits, tw.tw12, 0u);
-  }
-  R0H_TRY(launch_ok("ntt_local_kernel<fwd>"));
-  if (sp.H) {
-    KScope ks(ctx, "ntt_strided_kernel", 8.0 * count * (double)(1u << n));
-    dim3 grid2(1u << (sp.L - sp.tlog), count);
-    hipLaunchKernelGGL(ntt_strided_kernel<0>, grid2, dim3(512), (size_t)4 << (sp.H + sp.tlog), ctx->stream, u32(out), n, sp.L, sp.H, sp.tlog, tw);
-    R0H_TRY(launch_ok("ntt_strided_kernel<fwd>"));
-  }
-  return nullptr;
+  R0H_REQUIRE(expand_bits < split16_for(n).L, "r0h_batch_expand_into_evaluate_ntt: expand_bits %u too large for size 2^%u", expand_bits, n);
+  return forward16(ctx, u32(out), u32(in), count, n, expand_bits);
   R0H_GUARD_END
 }
 
@@ -821,37 +658,17 @@ const char* r0h_batch_bit_reverse(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uin
   R0H_REQUIRE(po2 <= MAX_DOMAIN_PO2 + 2, "r0h_batch_bit_reverse: po2 %u too large", po2);
   R0H_REQUIRE(((size_t)count << po2) * 4 <= io->bytes, "r0h_batch_bit_reverse: %u columns of 2^%u exceed the buffer", count, po2);
   if (!count || po2 == 0) return nullptr;
+  KScope ks(ctx, "bit_reverse_kernel", 8.0 * count * (double)(1u << po2));
   if (po2 >= 10) {
-    KScope ks(ctx, "bit_reverse_kernel", 8.0 * count * (double)(1u << po2));
-    hipLaunchKernelGGL(bit_reverse_tiled_kernel, dim3(1u << (po2 - 10), count), dim3(256), 0, ctx->stream, u32(io), po2);
+    hipLaunchKernelGGL((bit_reverse_tiled_kernel<uint32_t, 5>), dim3(1u << (po2 - 10), count), dim3(256), 0, ctx->stream, u32(io), po2);
     return launch_ok("bit_reverse_tiled_kernel");
   }
   uint32_t threads = po2 >= 8 ? 256 : (1u << po2);
-  KScope ks(ctx, "bit_reverse_kernel", 8.0 * count * (double)(1u << po2));
   dim3 grid((1u << po2) / threads, count);
-  hipLaunchKernelGGL(bit_reverse_kernel, grid, dim3(threads), 0, ctx->stream, u32(io), po2);
+  hipLaunchKernelGGL(bit_reverse_kernel<uint32_t>, grid, dim3(threads), 0, ctx->stream, u32(io), po2);
   return launch_ok("bit_reverse_kernel");
   R0H_GUARD_END
 }
-
-}  // extern "C"
-namespace r0h {
-const char* bit_reverse_ext(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t po2) {
-  R0H_GUARD_BEGIN
-  R0H_REQUIRE(ctx && io && po2 <= MAX_DOMAIN_PO2, "bit_reverse_ext: bad argument");
-  R0H_REQUIRE(((size_t)count << po2) * 16 <= io->bytes, "bit_reverse_ext: %u columns of 2^%u exceed the buffer", count, po2);
-  if (!count || po2 == 0) return nullptr;
-  KScope ks(ctx, "bit_reverse_kernel", 32.0 * count * (double)(1u << po2));
-  if (po2 >= 8) {
-    hipLaunchKernelGGL(bit_reverse_ext_tiled_kernel, dim3(1u << (po2 - 8), count), dim3(256), 0, ctx->stream, (uint4*)io->ptr, po2);
-  } else {
-    hipLaunchKernelGGL(bit_reverse_ext_kernel, dim3(1, count), dim3(1u << po2), 0, ctx->stream, (uint4*)io->ptr, po2);
-  }
-  return launch_ok("bit_reverse_ext kernel");
-  R0H_GUARD_END
-}
-}  // namespace r0h
-extern "C" {
 
 const char* r0h_zk_shift(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t po2) {
   R0H_GUARD_BEGIN

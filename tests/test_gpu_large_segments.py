@@ -57,7 +57,7 @@ def test_bit_reverse_and_zk_shift_large(hal, orc, po2, count):
     assert np.array_equal(buf.to_host(), orc.zk_shift(x, count, po2))
 
 
-@pytest.mark.parametrize("po2,count", [(5, 3), (10, 2), (14, 2), (20, 2), (22, 1), (23, 2), (24, 2), (25, 1), (26, 1)])
+@pytest.mark.parametrize("po2,count", [(5, 3), (7, 3), (8, 3), (10, 2), (13, 2), (14, 2), (15, 2), (20, 2), (22, 1), (23, 2), (24, 2), (25, 1), (26, 1)])
 def test_interpolate_with_the_coset_shift_fused_equals_the_two_calls(hal, orc, po2, count):
     """what the sequencer issues for every group: one-pass, two-pass, ROU[26]-table and three-level transforms all carry the shift"""
     rng = np.random.default_rng(950 + po2)
@@ -69,9 +69,10 @@ def test_interpolate_with_the_coset_shift_fused_equals_the_two_calls(hal, orc, p
 
 def test_more_columns_than_one_launch_takes(hal, orc):
     """The blocks of a large transform count as columns of its inner passes, so launches are cut at 32,768 columns: the same cut
-    with plain columns -- 33,000 of 2^8 (one pass) and of 2^16 (two passes) -- checked on columns either side of it."""
+    with plain columns -- 33,000 of 2^8 (one pass) and of 2^16 (two passes) -- checked on columns either side of it; and 2,100
+    columns of 2^14, whose 33,600 blocks of 2^10 put the cut inside column 2048."""
     rng = np.random.default_rng(6)
-    for po2, count in [(8, 33000), (16, 33000)]:
+    for po2, count, cut in [(8, 33000, 32768), (16, 33000, 32768), (14, 2100, 2048)]:
         x = rnd(rng, count << po2)
         buf = hal.copy_from(x)
         hal.batch_interpolate_ntt(buf, count, po2)
@@ -79,9 +80,23 @@ def test_more_columns_than_one_launch_takes(hal, orc):
         out = hal.alloc(count << po2)
         hal.batch_expand_into_evaluate_ntt(out, buf, count, po2, 0)
         assert np.array_equal(out.to_host(), x)
-        for c in (0, 1, 32767, 32768, 32769, count - 1):
+        for c in (0, 1, cut - 1, cut, cut + 1, count - 1):
             col = x[c << po2:(c + 1) << po2]
             assert np.array_equal(got[c], orc.batch_interpolate_ntt(col, 1, po2)), (po2, c)
+
+
+def test_more_small_columns_than_a_grid_takes(hal, orc):
+    """70,000 columns of 2^5: more than the 65,535 that blockIdx.y holds, so the small kernel's launches are cut like the others"""
+    po2, count = 5, 70000
+    x = rnd(np.random.default_rng(7), count << po2)
+    buf = hal.copy_from(x)
+    hal.batch_interpolate_ntt(buf, count, po2)
+    got = buf.to_host().reshape(count, 1 << po2)
+    out = hal.alloc(count << po2)
+    hal.batch_expand_into_evaluate_ntt(out, buf, count, po2, 0)
+    assert np.array_equal(out.to_host(), x)
+    for c in (0, 65535, 65536, count - 1):
+        assert np.array_equal(got[c], orc.batch_interpolate_ntt(x[c << po2:(c + 1) << po2], 1, po2)), c
 
 
 @pytest.mark.parametrize("name,po2,seed", [("tiny", 21, 31), ("tiny", 22, 32)])

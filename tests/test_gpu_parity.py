@@ -14,7 +14,14 @@ def rnd(rng, n):
     return rng.integers(0, P, size=n, dtype=np.uint32)
 
 
-@pytest.mark.parametrize("po2,count", [(1, 3), (4, 2), (9, 5), (12, 3), (13, 2), (14, 4), (17, 3), (20, 2), (21, 2), (22, 1)])
+# every size across the seams of the decomposition (7 | 8, 12 | 13 | 14, 15 | 16) with three columns, then the larger cases
+SEAM_PO2 = range(1, 18)
+
+
+_INTERPOLATE_CASES = [(1, 3), (4, 2), (9, 5), (12, 3), (13, 2), (14, 4), (17, 3), (20, 2), (21, 2), (22, 1)]
+
+
+@pytest.mark.parametrize("po2,count", _INTERPOLATE_CASES + [(po2, 3) for po2 in SEAM_PO2 if (po2, 3) not in _INTERPOLATE_CASES])
 def test_interpolate_ntt(hal, orc, po2, count):
     rng = np.random.default_rng(100 + po2)
     x = rnd(rng, count << po2)
@@ -23,9 +30,25 @@ def test_interpolate_ntt(hal, orc, po2, count):
     assert np.array_equal(buf.to_host(), orc.batch_interpolate_ntt(x, count, po2))
 
 
-@pytest.mark.parametrize("in_po2,expand,count", [(3, 0, 2), (5, 2, 3), (10, 2, 4), (12, 0, 2), (11, 2, 3), (14, 2, 2), (16, 2, 3), (20, 2, 1), (18, 0, 2), (19, 2, 2), (21, 0, 1), (22, 0, 1)])
+_EXPAND_CASES = [(3, 0, 2), (5, 2, 3), (10, 2, 4), (12, 0, 2), (11, 2, 3), (14, 2, 2), (16, 2, 3), (20, 2, 1), (18, 0, 2), (19, 2, 2), (21, 0, 1), (22, 0, 1)]
+_EXPAND_SEAMS = [(n, 0, 3) for n in SEAM_PO2] + [(n - 2, 2, 3) for n in SEAM_PO2 if n >= 3]  # every output size 2^1 .. 2^17
+
+
+@pytest.mark.parametrize("in_po2,expand,count", _EXPAND_CASES + [c for c in _EXPAND_SEAMS if c not in _EXPAND_CASES])
 def test_expand_into_evaluate_ntt(hal, orc, in_po2, expand, count):
     rng = np.random.default_rng(200 + in_po2)
+    x = rnd(rng, count << in_po2)
+    out = hal.alloc(count << (in_po2 + expand))
+    hal.batch_expand_into_evaluate_ntt(out, hal.copy_from(x), count, in_po2, expand)
+    assert np.array_equal(out.to_host(), orc.batch_expand_into_evaluate_ntt(x, count, in_po2, expand))
+
+
+@pytest.mark.parametrize("in_po2,expand", [(6, 1), (9, 1), (11, 3), (13, 1), (15, 1)])
+def test_expand_into_evaluate_ntt_by_two_and_by_eight(hal, orc, in_po2, expand):
+    """expand_bits outside {0, 2}: the contiguous chunks go through the radix-2 kernel -- a whole transform (2^7), one chunk (2^10),
+    chunks + the pass over the top four bits (2^14, twice), chunks + the strided pass (2^16)"""
+    count = 3
+    rng = np.random.default_rng(250 + in_po2)
     x = rnd(rng, count << in_po2)
     out = hal.alloc(count << (in_po2 + expand))
     hal.batch_expand_into_evaluate_ntt(out, hal.copy_from(x), count, in_po2, expand)
@@ -366,8 +389,8 @@ def test_extreme_field_values_through_every_arithmetic_kernel(hal, orc):
         nb = hal.copy_from(lvl)
         hal.hash_fold(nb, out_size)
         assert np.array_equal(nb.to_host(), orc.hash_fold(lvl, out_size))
-    # NTTs (radix-16 and radix-2 routes), zk shift, bit reversal
-    for po2, cols in ((10, 3), (13, 2), (17, 2)):
+    # NTTs (radix-16: one pass, two passes; 2^5: the radix-2 kernel), zk shift, bit reversal
+    for po2, cols in ((10, 3), (13, 2), (17, 2), (5, 3)):
         x = _extreme(rng, cols << po2)
         buf = hal.copy_from(x)
         hal.batch_interpolate_ntt(buf, cols, po2)
