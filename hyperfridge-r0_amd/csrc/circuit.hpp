@@ -213,7 +213,4 @@ const char* session_table_add_list(r0h_session_balance* sb, uint32_t source, con
 const char* session_table_report(r0h_session_balance* sb, r0h_session_imbalance* out, size_t capacity, size_t* n_out);
 const char* session_table_stats(r0h_session_balance* sb, uint64_t* slots_out, uint64_t* occupied_out);
 void session_table_free(r0h_session_balance* sb);
-// the sequencer's use of it (session.cpp under r0h_ctx_set_check_session): a phase of the context's profile by name (prover.hip)
-void profile_phase(r0h_ctx* ctx, const char* name);
-void profile_close(r0h_ctx* ctx);
 }  // namespace r0h

@@ -233,6 +233,28 @@ const char* launch_ok(const char* what) {
   return nullptr;
 }
 
+void profile_phase(r0h_ctx* ctx, const char* name) {
+  Profile& p = ctx->prof;
+  size_t i = p.names.size();
+  if (p.events.size() <= i) {
+    hipEvent_t e;
+    (void)hipEventCreate(&e);
+    p.events.push_back(e);
+  }
+  (void)hipEventRecord(p.events[i], ctx->stream);
+  p.names.push_back(name);
+}
+const char* profile_close(r0h_ctx* ctx) {
+  profile_phase(ctx, "end");
+  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  Profile& p = ctx->prof;
+  std::vector<float> ms(p.names.size() - 1, 0.f);
+  for (size_t i = 0; i < ms.size(); i++) (void)hipEventElapsedTime(&ms[i], p.events[i], p.events[i + 1]);
+  p.closed_names.assign(p.names.begin(), p.names.end() - 1);  // ("end" names no phase)
+  p.closed_ms.swap(ms);
+  return nullptr;
+}
+
 void ctx_retain(r0h_ctx* ctx) { ctx->refs++; }
 const char* ctx_helper(r0h_ctx* ctx, size_t k, r0h_ctx** out) {
   while (ctx->helpers.size() <= k) {
@@ -480,6 +502,15 @@ const char* r0h_kernel_stats(r0h_ctx* ctx, char* json_out, size_t capacity) {
   memcpy(json_out, js.c_str(), js.size() + 1);
   return nullptr;
   R0H_GUARD_END
+}
+
+const char* r0h_last_profile(r0h_ctx* ctx, const char*** names_out, const float** ms_out, uint32_t* n_out) {
+  R0H_REQUIRE(ctx && names_out && ms_out && n_out, "r0h_last_profile: NULL argument");
+  const Profile& p = ctx->prof;  // the closed one: a proof in flight, aborted or failed since has not touched it
+  *names_out = const_cast<const char**>(p.closed_names.data());
+  *ms_out = p.closed_ms.data();
+  *n_out = (uint32_t)p.closed_names.size();
+  return nullptr;
 }
 
 void* r0h_buf_device_ptr(const r0h_buf* buf) { return buf ? buf->ptr : nullptr; }

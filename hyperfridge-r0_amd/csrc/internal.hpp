@@ -77,10 +77,13 @@ struct KTimer {
   double alg_bytes = 0;        // algorithmic HBM bytes of the recorded launches
 };
 
+// The per-phase device time of a proof (ctx.cpp: profile_phase, profile_close).  `names` and `events` belong to the proof in flight;
+// r0h_last_profile reports the last profile that was closed, names and times of one length, whatever has been begun since.
 struct Profile {
-  std::vector<const char*> names;
-  std::vector<float> ms;
+  std::vector<const char*> names;  // static strings, "end" among them once closed
   std::vector<hipEvent_t> events;  // events[i], events[i+1] bracket phase i
+  std::vector<const char*> closed_names;
+  std::vector<float> closed_ms;
 };
 
 }  // namespace r0h
@@ -177,8 +180,8 @@ const char* ensure_scratch(r0h_ctx* ctx, size_t bytes);
 const char* stage_h2d(r0h_ctx* ctx, void* dst_device, const void* src_host, size_t bytes);
 // device buffer from the context's pool: no hipMalloc / hipFree (and no implicit device sync) in steady state
 const char* buf_alloc_pooled(r0h_ctx* ctx, size_t bytes, r0h_buf** out);
-// Owner of one pooled buffer: back to its context's pool when the owner goes -- or at reset(), where the block has to be back
-// before what follows (the next allocation of that size reuses it in stream order); release() hands the pointer on.
+// Owner of one device buffer -- pooled, if alloc() made it: back to its context's pool when the owner goes, or at reset(), where the
+// block has to be back before what follows (the next allocation of that size reuses it in stream order); release() hands the pointer on.
 struct BufFree { void operator()(r0h_buf* b) const { r0h_buf_free(b); } };
 struct DevBuf : std::unique_ptr<r0h_buf, BufFree> {
   const char* alloc(r0h_ctx* ctx, size_t bytes) {
@@ -190,6 +193,10 @@ struct DevBuf : std::unique_ptr<r0h_buf, BufFree> {
 };
 // bytes [offset_bytes, +bytes) of `b` as a buffer that owns nothing and is never freed; throws std::out_of_range outside `b`
 r0h_buf buf_view(const r0h_buf* b, size_t offset_bytes, size_t bytes);
+// A phase of the context's profile opens here, by name (an event on the context's stream); profile_close ends the last one, waits
+// for the stream and makes the phases recorded since the last proof began what r0h_last_profile reports.  Host only.
+void profile_phase(r0h_ctx* ctx, const char* name);
+const char* profile_close(r0h_ctx* ctx);
 // after a kernel launch: the launch error, if any, as "<what>: launch failed: <hip text>"
 const char* launch_ok(const char* what);
 // inverse NTT with the coset shift f(x) -> f(3x) optionally fused into its last pass (sequencer path)

@@ -556,7 +556,7 @@ const char* check_session(r0h_session* s) {
   R0H_TRY(r0h_session_balance_add_verifier_side(sb.get(), s->elf.data(), s->elf.size(), s->journal.data(), s->journal.size()));
   char* text = nullptr;
   R0H_TRY(r0h_session_balance_message(sb.get(), &text));
-  if (!own_proof || text) profile_close(ctx);
+  if (!own_proof || text) r0h_free_error(profile_close(ctx));
   if (!text) return nullptr;
   for (Pending& p : s->pending) p.proof.reset();  // aborted
   const char* err = make_error("r0h_prove_elf: %s", text);

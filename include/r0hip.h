@@ -335,7 +335,9 @@ const char* r0h_prove_segment_committed(r0h_ctx* ctx, const r0h_circuit* c, uint
                                         size_t seal_capacity_words, size_t* seal_words_out);
 const char* r0h_proof_begin_committed(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code,
                                       const r0h_buf* data, const uint32_t* global_host, uint32_t* mix_out, r0h_proof** out);
-/* Per-phase device time of the last r0h_prove_segment on this context (ms), for bench.py; names are static strings. */
+/* Per-phase device time (ms) of the last proof on this context that came out -- r0h_prove_segment*, r0h_proof_finish, or the session check
+ * that closes a profile; names are static strings, *n_out names and times, valid until the next one closes.  A proof in flight, aborted or failed
+ * leaves the report as it was; a context that has closed none reports *n_out = 0. */
 const char* r0h_last_profile(r0h_ctx* ctx, const char*** names_out, const float** ms_out, uint32_t* n_out);
 
 /* ---- verifier: risc0-zkp verify/mod.rs as reached from `receipt.verify(image_id)` (host/src/main.rs:622-624,
