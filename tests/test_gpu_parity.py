@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import circuit_path
+from field_words import extreme as _extreme
 
 pytestmark = pytest.mark.gpu
 P = 2013265921
@@ -369,12 +370,6 @@ def test_two_contexts_prove_concurrently_and_agree(orc):
         ln[0].close()
 
 
-def _extreme(rng, n):
-    """Words drawn from the corners of [0, p): the lazy-reduction bounds of the kernels are worst at p-1."""
-    pool = np.array([0, 1, 2, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, 2**31 - 2**27, 0x0FFFFFFF, 0x70000000], dtype=np.uint32)
-    return pool[rng.integers(0, pool.size, size=n)]
-
-
 def test_extreme_field_values_through_every_arithmetic_kernel(hal, orc):
     rng = np.random.default_rng(4242)
     # Poseidon2: lane-per-row, lane-per-parent and the 24-lane cross-lane variant
@@ -430,6 +425,50 @@ def test_extreme_field_values_through_every_arithmetic_kernel(hal, orc):
     glob, mixw, pm = _extreme(rng, oc.n_global), _extreme(rng, oc.n_mix), np.array([P - 1, P - 1, P - 1, P - 1], np.uint32)
     check = hal.eval_check(gc, po2, hal.copy_from(ea), hal.copy_from(ec), hal.copy_from(ed), glob, mixw, pm)
     assert np.array_equal(check.to_host(), oc.eval_check(po2, ea, ec, ed, glob, mixw, pm))
+
+
+def _ntt_words(rng, n, kind):
+    """`pool`: the corners of [0, p); `top`: every word p - 1; `sevenths`: random with every 7th word p - 1"""
+    if kind == "pool":
+        return _extreme(rng, n)
+    x = np.full(n, P - 1, dtype=np.uint32) if kind == "top" else rnd(rng, n)
+    x[::7] = P - 1
+    return x
+
+
+NTT_FAMILIES = ("pool", "top", "sevenths")
+
+
+# every instantiation of the one-route transform keeps its own lazy-reduction bounds (split16_for): chunks of 2^8, 2^9, 2^11, 2^12 in one
+# pass; 2^14, 2^15: sixteen chunks of 2^10, 2^11 and the pass over the top four bits; 2^16: H = 8 with the smallest chunk; 2^21: H = 9;
+# 2^23: H = 10 on the ROU[26] tables; 2^24: three levels
+@pytest.mark.parametrize("kind", NTT_FAMILIES)
+@pytest.mark.parametrize("po2", [8, 9, 11, 12, 14, 15, 16, 21, 23, 24])
+def test_extreme_field_values_through_interpolation_with_and_without_the_fused_shift(hal, orc, po2, kind):
+    count = 2 if po2 <= 16 else 1
+    x = _ntt_words(np.random.default_rng([4243, po2, len(kind)]), count << po2, kind)
+    buf = hal.copy_from(x)
+    hal.batch_interpolate_ntt(buf, count, po2)
+    want = orc.batch_interpolate_ntt(x, count, po2)
+    assert np.array_equal(buf.to_host(), want)
+    buf.upload(x)
+    hal.batch_interpolate_ntt_zk_shift(buf, count, po2)  # the coset shift inside the last pass
+    assert np.array_equal(buf.to_host(), orc.zk_shift(want, count, po2))
+    buf.free()
+
+
+# (in_po2, expand_bits): 0 and 2 take the radix-16 contiguous pass, at the sizes and splits above; 1 and 3 take the radix-2 one -- alone
+# at 2^7, under the pass over the top four bits at 2^14 (twice) and under the strided pass at 2^16
+@pytest.mark.parametrize("kind", NTT_FAMILIES)
+@pytest.mark.parametrize("in_po2,expand", [(8, 0), (6, 2), (9, 2), (12, 2), (14, 0), (16, 0), (19, 2), (21, 2), (24, 0), (6, 1), (11, 3), (13, 1), (15, 1)])
+def test_extreme_field_values_through_expansion(hal, orc, in_po2, expand, kind):
+    count = 2 if in_po2 + expand <= 16 else 1
+    x = _ntt_words(np.random.default_rng([4244, in_po2, expand, len(kind)]), count << in_po2, kind)
+    out, inp = hal.alloc(count << (in_po2 + expand)), hal.copy_from(x)
+    hal.batch_expand_into_evaluate_ntt(out, inp, count, in_po2, expand)
+    assert np.array_equal(out.to_host(), orc.batch_expand_into_evaluate_ntt(x, count, in_po2, expand))
+    out.free()
+    inp.free()
 
 
 def test_hal_trait_operand_placement_forms_match_the_host_array_forms(hal, orc):
