@@ -100,6 +100,8 @@ _SIGNATURES = {
     "r0h_witgen_public": [_vp, _vp, _u32, _u64, _vp, _vp, _vp],
     "r0h_seal_digest": [_vp, _sz, _vp],
     "r0h_ctx_set_session_resident_limit": [_vp, _u64],
+    "r0h_ctx_set_session_device_limit": [_vp, _u64],
+    "r0h_last_session_device": [_vp, _vp],
     "r0h_proof_shrink": [_vp, _vp],
     "r0h_sponge_trace": [_vp, _sz, _u32, _vp],
     "r0h_image_po2": [_vp, _sz, _vp],
@@ -181,6 +183,9 @@ _SIGNATURES = {
     "r0h_vm_release_trace": [_vp, _sz],
     "r0h_vm_boundary": [_vp, _sz, _pp, _c.POINTER(_sz)],
     "r0h_trace_witgen": [_vp, _vp, _sz, _vp, _sz, _u32, _vp, _vp, _vp],
+    "r0h_trace_rows_upload": [_vp, _vp, _sz, _vp, _sz, _u32, _vp, _vp, _vp],
+    "r0h_trace_rows_expand": [_vp, _vp],
+    "r0h_trace_rows_free": [_vp],
     "r0h_logup_multiplicities": [_vp, _vp, _u32, _vp, _vp],
     "r0h_logup_multiplicities_host": [_vp, _sz, _u32, _vp, _vp],
     "r0h_logup_totals": [_vp, _vp, _u32, _vp, _vp, _vp],
@@ -246,6 +251,8 @@ _PLAIN = {
     "r0h_circuit_group_size": ([_vp, _u32], _u32),
     "r0h_circuit_n_global": ([_vp], _u32),
     "r0h_proof_resident_bytes": ([_vp], _sz),
+    "r0h_trace_rows_bytes": ([_vp], _sz),
+    "r0h_ctx_session_held_bytes": ([_vp], _u64),
     "r0h_circuit_n_mix": ([_vp], _u32),
     "r0h_circuit_n_taps": ([_vp], _u32),
     "r0h_circuit_n_terms": ([_vp], _u32),
@@ -1527,6 +1534,32 @@ class Hal:
             glob[:8] = claim_globals
         return data, glob
 
+    def trace_rows_upload(self, rows, bounds, po2, number=1, closing=True, idle_pc=0):
+        """The compact preflight rows of one segment staged on the device (r0h_trace_rows_upload; arguments as trace_witgen's).  Returns
+        (handle, the TRACE_GLOBALS public inputs -- the claim's eight and the late ones zero); the handle is expanded with
+        trace_rows_expand as often as wanted and released with trace_rows_free."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 18)
+        bounds = np.ascontiguousarray(bounds, dtype=np.uint32).reshape(-1, 8)
+        glob = np.zeros(TRACE_GLOBALS, dtype=np.uint32)
+        seg = TraceSegment(number, 1 if closing else 0, idle_pc, 0)
+        h = _vp()
+        _check(lib().r0h_trace_rows_upload(self.ctx, rows.ctypes.data_as(_vp), rows.shape[0], bounds.ctypes.data_as(_vp), bounds.shape[0], po2, ctypes.byref(seg),
+                                           ctypes.byref(h), glob.ctypes.data_as(_vp)))
+        return h, glob
+
+    def trace_rows_expand(self, handle, into):
+        """DATA group of the trace circuit from staged rows into the Buf `into` (r0h_trace_rows_expand): the words trace_witgen leaves,
+        multiplicity columns zero.  Stream-ordered."""
+        _check(lib().r0h_trace_rows_expand(handle, into.handle))
+        return into
+
+    def trace_rows_bytes(self, handle):
+        """device bytes a rows handle keeps (r0h_trace_rows_bytes)"""
+        return lib().r0h_trace_rows_bytes(handle)
+
+    def trace_rows_free(self, handle):
+        _check(lib().r0h_trace_rows_free(handle))
+
     def witgen_into(self, circuit, po2, seed, code, data):
         """Regenerate the synthetic witness of another segment into existing buffers; returns its public inputs."""
         glob = np.zeros(max(circuit.n_global, 1), dtype=np.uint32)
@@ -1691,6 +1724,23 @@ class Hal:
         """bytes of committed DATA evaluations a session on this context keeps between its phases (r0h_ctx_set_session_resident_limit;
         0 = an eighth of the device's memory); segments beyond it are evaluated again when their proofs are finished -- same seals"""
         _check(lib().r0h_ctx_set_session_resident_limit(self.ctx, n_bytes))
+
+    def set_session_device_limit(self, n_bytes):
+        """bytes the committed segments of a trace-circuit session on this context may keep on the device between its phases
+        (r0h_ctx_set_session_device_limit; 0 = no limit, the default); a segment beyond it is evicted to its compact rows and
+        committed again when the session is finished -- same seals"""
+        _check(lib().r0h_ctx_set_session_device_limit(self.ctx, n_bytes))
+
+    def last_session_device(self):
+        """Of the last session finished on this context (r0h_last_session_device): segments evicted, segments replayed, the peak of
+        the bytes counted against the device limit, the peak of the bytes in rows handles."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().r0h_last_session_device(self.ctx, out))
+        return dict(zip(("evicted", "replayed", "peak_counted_bytes", "rows_bytes"), (int(v) for v in out)))
+
+    def session_held_bytes(self):
+        """device bytes the unfinished sessions of this context hold right now (r0h_ctx_session_held_bytes)"""
+        return int(lib().r0h_ctx_session_held_bytes(self.ctx))
 
     def set_image_circuit(self, image_circuit):
         """sessions on this context attach an image proof to their receipts from now on (r0h_ctx_set_image_circuit; None: stop)"""

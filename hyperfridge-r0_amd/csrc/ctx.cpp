@@ -470,6 +470,17 @@ const char* r0h_ctx_set_session_resident_limit(r0h_ctx* ctx, uint64_t bytes) {
   ctx->session_resident_limit = bytes;
   return nullptr;
 }
+const char* r0h_ctx_set_session_device_limit(r0h_ctx* ctx, uint64_t bytes) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_session_device_limit: ctx is NULL");
+  ctx->session_device_limit = bytes;
+  return nullptr;
+}
+const char* r0h_last_session_device(r0h_ctx* ctx, uint64_t out[4]) {
+  R0H_REQUIRE(ctx && out, "r0h_last_session_device: NULL argument");
+  memcpy(out, ctx->session_device, sizeof ctx->session_device);
+  return nullptr;
+}
+uint64_t r0h_ctx_session_held_bytes(const r0h_ctx* ctx) { return ctx ? ctx->session_held.load() : 0; }
 const char* r0h_kernel_timing(r0h_ctx* ctx, int enable) {
   R0H_REQUIRE(ctx, "r0h_kernel_timing: ctx is NULL");
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));

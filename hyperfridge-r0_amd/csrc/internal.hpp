@@ -84,6 +84,7 @@ struct Profile {
   std::vector<hipEvent_t> events;  // events[i], events[i+1] bracket phase i
   std::vector<const char*> closed_names;
   std::vector<float> closed_ms;
+  bool continued = false;  // the next proof that begins adds its phases to `names` instead of starting over (session.cpp: replay_segment)
 };
 
 }  // namespace r0h
@@ -118,6 +119,9 @@ struct r0h_ctx {
   r0h_session_stats session = {0, 0, 0, 0, 0, 0, 0};  // stage timing of the last r0h_prove_elf
   const r0h_circuit* image_circuit = nullptr;  // r0h_ctx_set_image_circuit: sessions on this context attach an image proof to their receipts
   uint64_t session_resident_limit = 0;  // r0h_ctx_set_session_resident_limit (0: an eighth of the device's memory)
+  uint64_t session_device_limit = 0;    // r0h_ctx_set_session_device_limit (0: none)
+  uint64_t session_device[4] = {0, 0, 0, 0};  // r0h_last_session_device: evicted, replayed, peak count, peak bytes in rows handles
+  std::atomic<uint64_t> session_held{0};  // r0h_ctx_session_held_bytes: what unfinished sessions of this context hold (their lanes add and subtract)
   void* session_rows = nullptr;   // session.cpp: the preflight row buffers of r0h_prove_elf, page-locked, kept from one call to the next (session_rows_free)
   std::vector<r0h_ctx*> helpers;  // further contexts of the same device, made on demand by r0h_prove_elf for its extra prover lanes; they go with this one
   bool check_witness = false;     // r0h_ctx_set_check_witness: the sequencer runs r0h_check_witness on every segment before it commits ACCUM

@@ -225,7 +225,7 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_
   const uint32_t po2 = st.po2;
   WriteIop& io = st.io;
   const r0h_code_commit& code = *st.code;
-  ctx->prof.names.clear();
+  if (!ctx->prof.continued) ctx->prof.names.clear();
   st.global.assign(global, global + circ->n_global);
   if (ctx->check_witness) {
     st.check_code = code.witness;

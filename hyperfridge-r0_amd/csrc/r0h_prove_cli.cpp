@@ -19,6 +19,9 @@
 // the session tuples of all segments must cancel against one another, the ELF's image words and the journal's words
 // (r0h_session_balance_*); a session that does not balance ends the run with the lowest class -- fraction, net, tuples, the segment and
 // row of its first member, the class's values -- and the fraction's name from the same file (its lines go on past the chain's fractions).
+// --session-device-limit-gb G (--elf mode, trace circuit) sets r0h_ctx_set_session_device_limit on every session context: the segments a
+// session cannot keep committed within G GiB wait for the challenge as their compact rows and are committed again when it is known; the
+// receipt is the one an unlimited run writes, and the result line says how many segments were evicted.
 // With --receipt-out / --receipt-dir every segment is proved for a claim (risc0-zkvm `ReceiptClaim`): the session's system states
 // are synthetic names (there is no executor here), segment k runs from state k to state k+1, all but the last end in SystemSplit,
 // the last halts with the journal's output; the claim's eight naming words are planted as the segment's public inputs.  The image
@@ -87,7 +90,10 @@ int main(int argc, char** argv) {
            "a segment that does not balance ends the run with the fraction, its name, the net of its class and its first row\n"
            "       --check-session 1 [--fraction-names file.txt]: with --elf, check before the session challenge is derived that the session tuples of all segments cancel against "
            "one another, the program image and the journal; a session that does not balance ends the run with the fraction, its name, the net of its class, the segment and row of its first tuple "
-           "and the class's values (single-rank sessions; a diagnostic, not a verifier)\n%s\n", r0h_version());
+           "and the class's values (single-rank sessions; a diagnostic, not a verifier)\n"
+           "       --session-device-limit-gb G: with --elf over the trace circuit, the committed segments of a session keep at most G GiB on the device between its two phases "
+           "(a fraction is fine); a segment beyond that is evicted to its compact rows and committed again when the session is finished -- the same receipt; the run reports "
+           "how many were (default: no limit)\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   // --compress takes no value: it is taken out of the arguments before the "--option value" pairs are read
@@ -109,6 +115,7 @@ int main(int argc, char** argv) {
   unsigned check_witness = 0, check_balance = 0, check_session = 0;
   unsigned po2 = 16, segments = 1, device = 0, contexts = 1, verify = 0, receipts = 1;
   unsigned long long seed = 1;
+  double session_device_limit_gb = 0;  // --session-device-limit-gb: r0h_ctx_set_session_device_limit of every session context
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--code-object")) co_path = argv[i + 1];
     else if (!strcmp(argv[i], "--po2")) po2 = (unsigned)atoi(argv[i + 1]);
@@ -125,6 +132,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--check-balance")) check_balance = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--check-session")) check_session = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--fraction-names")) fraction_names_path = argv[i + 1];
+    else if (!strcmp(argv[i], "--session-device-limit-gb")) session_device_limit_gb = atof(argv[i + 1]);
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
     else if (!strcmp(argv[i], "--journal")) journal_text = argv[i + 1];
@@ -148,6 +156,10 @@ int main(int argc, char** argv) {
   if ((argc - 2) % 2) { fprintf(stderr, "r0h_prove: option %s needs a value\n", argv[argc - 1]); return 1; }
   if (compress && (elf_path.empty() || recursion_path.empty() || root_out.empty())) {
     fprintf(stderr, "r0h_prove: --compress goes with --elf and needs --recursion-circuit and --root-out (and takes --recursion-code-object, --recursion-po2, --compress-lanes)\n");
+    return 1;
+  }
+  if (session_device_limit_gb < 0 || (session_device_limit_gb > 0 && elf_path.empty())) {
+    fprintf(stderr, "r0h_prove: --session-device-limit-gb takes a size of zero or more and goes with --elf\n");
     return 1;
   }
   if (hashfn != "poseidon2" && hashfn != "sha-256") { fprintf(stderr, "r0h_prove: --hashfn is poseidon2 or sha-256, not %s\n", hashfn.c_str()); return 1; }
@@ -190,6 +202,7 @@ int main(int argc, char** argv) {
   }
   // --check-witness: the context's switch, and the checker's module now (from its code object, else compiled in-process) rather than inside the first proof
   auto arm_checker = [&](r0h_ctx* ctx, r0h_circuit* circ) {
+    if (session_device_limit_gb > 0) CHECK(r0h_ctx_set_session_device_limit(ctx, std::max<uint64_t>(1, (uint64_t)(session_device_limit_gb * (double)(1ull << 30)))));
     if (check_balance) CHECK(r0h_ctx_set_check_balance(ctx, 1));
     if (check_session) CHECK(r0h_ctx_set_check_session(ctx, 1));
     if (!check_witness) return;
@@ -384,9 +397,11 @@ int main(int argc, char** argv) {
     CHECK(r0h_image_id_to_hex(image_id, hex));
     r0h_session_stats st;
     CHECK(r0h_last_session_stats(ctx, &st));
+    uint64_t device[4];  // of the first context's last session
+    CHECK(r0h_last_session_device(ctx, device));
     printf("{\"receipt\": \"%s\", \"image_id\": \"%s\", \"receipts\": %u, \"contexts\": %u, \"segments\": %zu, \"cycles\": %llu, \"seconds\": %.4f, \"segments_per_s\": %.3f, \"receipts_per_s\": %.4f, "
-           "\"executor_s\": %.4f, \"receipts_verified_with_the_elf\": %u, \"receipts_verified_with_the_image_id_alone\": %u, \"verify_seconds\": %.3f, \"control_roots\": [",
-           receipt_out.c_str(), hex, receipts, contexts, n_seg, (unsigned long long)cycles, secs, (double)n_seg * receipts / secs, receipts / secs, st.executor_s, receipts,
+           "\"executor_s\": %.4f, \"evicted_segments\": %llu, \"receipts_verified_with_the_elf\": %u, \"receipts_verified_with_the_image_id_alone\": %u, \"verify_seconds\": %.3f, \"control_roots\": [",
+           receipt_out.c_str(), hex, receipts, contexts, n_seg, (unsigned long long)cycles, secs, (double)n_seg * receipts / secs, receipts / secs, st.executor_s, (unsigned long long)device[0], receipts,
            image_blob.empty() ? 0u : receipts, verify_secs);
     for (size_t k = 0; k < sizes.size(); k++) {
       const uint32_t* root = &root_table[9 * k + 1];

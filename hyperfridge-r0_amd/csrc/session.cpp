@@ -19,6 +19,8 @@
 // commitments); the session challenge is derived from all the DATA roots (and the segments' early public inputs); phase 2 gives
 // every proof its late public inputs -- the challenge and the segment's sum under it -- and finishes it.  Ranks that share a
 // session exchange 28 words per segment between the phases (r0h_session_begin / _records / _finish; one rank: r0h_prove_elf).
+// A session with a device limit (r0h_ctx_set_session_device_limit) keeps the segments beyond it as their compact rows alone and
+// commits them a second time in phase 2 (commit_rows, replay_segment): its length is not bounded by the device's memory.
 // With any other circuit the witness is the blob's synthetic column program with the claim planted: the seal then proves "a
 // satisfying trace of the loaded circuit exists whose public inputs name this claim", not "this program ran".
 #include <stdlib.h>
@@ -295,6 +297,33 @@ constexpr uint32_t RECORD_WORDS = (R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS) +
 static_assert(RECORD_WORDS == R0H_SESSION_RECORD_WORDS, "R0H_SESSION_RECORD_WORDS out of step");
 
 struct ProofAbort { void operator()(r0h_proof* p) const { r0h_proof_abort(p); } };
+struct RowsFree { void operator()(r0h_trace_rows* h) const { r0h_trace_rows_free(h); } };
+
+// What a pending segment adds to r0h_ctx_session_held_bytes of the session's context: taken back when the segment goes, however it goes.
+class Held {
+ public:
+  Held() {}
+  Held(Held&& o) noexcept : ctx_(std::exchange(o.ctx_, nullptr)), bytes_(std::exchange(o.bytes_, 0)) {}
+  Held& operator=(Held&& o) noexcept {
+    if (this != &o) {
+      set(nullptr, 0);
+      ctx_ = std::exchange(o.ctx_, nullptr);
+      bytes_ = std::exchange(o.bytes_, 0);
+    }
+    return *this;
+  }
+  ~Held() { set(nullptr, 0); }
+  void set(r0h_ctx* ctx, uint64_t bytes) {
+    if (ctx_) ctx_->session_held -= bytes_;
+    ctx_ = bytes ? ctx : nullptr;
+    bytes_ = ctx_ ? bytes : 0;
+    if (ctx_) ctx_->session_held += bytes_;
+  }
+
+ private:
+  r0h_ctx* ctx_ = nullptr;  // the session's context: the session holds a reference for as long as it has segments
+  uint64_t bytes_ = 0;
+};
 
 struct Pending {  // a segment between the phases: committed, waiting for the session challenge
   size_t index = 0;
@@ -302,6 +331,12 @@ struct Pending {  // a segment between the phases: committed, waiting for the se
   std::shared_ptr<r0h_code_commit> cc_held;  // shared with the context's cache (ctx_code_commit); before `proof`: it outlives the proof that reads it
   DevBuf data;
   std::unique_ptr<r0h_proof, ProofAbort> proof;  // in flight (after `data`: it goes first)
+  // a session with a device limit: the compact rows on the device, from which the segment is committed again once it has been evicted
+  // (a block of its own from the lane's pool: no order towards `data` and `proof`)
+  std::unique_ptr<r0h_trace_rows, RowsFree> rows;
+  bool evicted = false;  // `proof` and `data` were given up after phase 1: `rows`, `global`, `root`, `claim`, `po2` and the CODE commitment stay
+  uint64_t rows_bytes = 0;
+  Held held;
   r0h_code_commit* cc = nullptr;
   uint32_t po2 = 0;
   std::vector<uint32_t> global;
@@ -317,7 +352,7 @@ struct r0h_session {
   bool trace_mode = false;
   uint32_t part = 0, parts = 1;
   size_t n_segments = 0;
-  std::mutex result_mu;  // the lanes share `pending`, `stats`, `resident_evaluations`
+  std::mutex result_mu;  // the lanes share `pending`, `stats`, `resident_evaluations`, `device`
   std::vector<Pending> pending;  // this rank's segments, by index
   std::vector<uint8_t> journal;
   std::vector<uint8_t> elf;  // kept for the image proof (r0h_ctx_set_image_circuit) and for the session check's verifier side
@@ -326,36 +361,75 @@ struct r0h_session {
   uint64_t cycles = 0;
   r0h_session_stats stats = {0, 0, 0, 0, 0, 0, 0};
   uint64_t resident_limit = 0, resident_evaluations = 0;  // bytes of DATA evaluations kept between the phases (r0h_ctx_set_session_resident_limit)
+  // r0h_ctx_set_session_device_limit: `counted` is what the segments that stay committed keep on the device (witness, proof, rows
+  // handle), the value held against the limit; `rows_held` the bytes in rows handles, evicted segments' included
+  struct Device { uint64_t limit = 0, counted = 0, counted_peak = 0, rows_held = 0, rows_peak = 0, evicted = 0, replayed = 0; } device;
   Clock::time_point t_begin;
   std::vector<r0h_ctx*> lane_ctx;
   ~r0h_session() {
-    pending.clear();  // proofs aborted, buffers freed: before the context is let go
+    pending.clear();  // proofs aborted, buffers and rows handles freed, their bytes taken off the context's count: before the context is let go
     if (ctx) ctx_release(ctx);
   }
 };
 
 namespace {
-// Phase 1 of a trace-circuit segment: the rows are expanded on the device, the DATA group is committed, the proof waits in `pend`.
+// The DATA group of a segment from its staged rows, committed: phase 1 of every segment and phase 2 of an evicted one -- the same
+// launches over the same rows, so the same root.  `global`: the early public inputs, the late ones still zero.
+const char* commit_rows(const r0h_circuit* c, Pending& pend, r0h_buf* data, const uint32_t* global, uint32_t root[8], Clock::time_point* t_witness) {
+  R0H_TRY(r0h_trace_rows_expand(pend.rows.get(), data));
+  R0H_TRY(r0h_logup_multiplicities(pend.lctx, c, pend.po2, data, global));
+  *t_witness = Clock::now();
+  r0h_proof* proof = nullptr;
+  R0H_TRY(r0h_proof_begin_committed(pend.lctx, c, pend.po2, pend.cc, data, global, nullptr, &proof));
+  pend.proof.reset(proof);
+  return r0h_proof_data_root(proof, root);
+}
+
+// Phase 1 of a trace-circuit segment: the rows are staged and expanded on the device, the DATA group is committed, the proof waits in
+// `pend` -- or, beyond the session's device limit, only the rows do.
 const char* commit_segment(r0h_session* ses, RowBuffers& rows, const Produced& seg, DevBuf& data, std::vector<uint32_t>& global, Pending& pend) {
   const r0h_circuit* c = ses->c;
   const Clock::time_point t0 = Clock::now();
   rows.pin(seg.rows.data(), seg.rows.capacity() * sizeof(r0h_preflight_row));
   const r0h_trace_segment ts = {seg.info.index + 1, seg.info.closing, seg.info.pre.pc, 0};
-  R0H_TRY(r0h_trace_witgen(pend.lctx, seg.rows.data(), seg.rows.size(), seg.bounds.data(), seg.bounds.size(), pend.po2, &ts, data.get(), global.data()));
-  R0H_TRY(r0h_logup_multiplicities(pend.lctx, c, pend.po2, data.get(), global.data()));
-  const Clock::time_point t1 = Clock::now();
-  r0h_proof* proof = nullptr;
-  R0H_TRY(r0h_proof_begin_committed(pend.lctx, c, pend.po2, pend.cc, data.get(), global.data(), nullptr, &proof));
-  pend.proof.reset(proof);
-  R0H_TRY(r0h_proof_data_root(proof, pend.root));
+  r0h_trace_rows* staged = nullptr;
+  R0H_TRY(r0h_trace_rows_upload(pend.lctx, seg.rows.data(), seg.rows.size(), seg.bounds.data(), seg.bounds.size(), pend.po2, &ts, &staged, global.data()));
+  pend.rows.reset(staged);
+  Clock::time_point t1;
+  R0H_TRY(commit_rows(c, pend, data.get(), global.data(), pend.root, &t1));
+  r0h_session::Device& dev = ses->device;
+  if (!dev.limit) pend.rows.reset();  // nothing will be committed twice (multiplicities and the root have waited for the stream: the block is idle)
+  pend.rows_bytes = r0h_trace_rows_bytes(pend.rows.get());
+  const uint64_t evaluations = ((uint64_t)c->group_size[R0H_GROUP_DATA] << pend.po2) * 16;
+  bool lean;
   {  // beyond the session's resident limit a segment waits for the challenge without its evaluations
-    const uint64_t evaluations = ((uint64_t)c->group_size[R0H_GROUP_DATA] << pend.po2) * 16;
     std::unique_lock<std::mutex> lk(ses->result_mu);
-    const bool lean = ses->resident_evaluations + evaluations > ses->resident_limit;
+    lean = ses->resident_evaluations + evaluations > ses->resident_limit;
     if (lean) ses->stats.lean_segments++;
     else ses->resident_evaluations += evaluations;
     lk.unlock();
-    if (lean) R0H_TRY(r0h_proof_shrink(proof, nullptr));
+    if (lean) R0H_TRY(r0h_proof_shrink(pend.proof.get(), nullptr));
+  }
+  {  // beyond its device limit it waits as rows alone, and is neither resident nor lean
+    const uint64_t cost = data->bytes + r0h_proof_resident_bytes(pend.proof.get()) + pend.rows_bytes;
+    std::unique_lock<std::mutex> lk(ses->result_mu);
+    pend.evicted = dev.limit && dev.counted + cost > dev.limit;
+    if (pend.evicted) {
+      dev.evicted++;
+      if (lean) ses->stats.lean_segments--;
+      else ses->resident_evaluations -= evaluations;
+    } else {
+      dev.counted += cost;
+      dev.counted_peak = std::max(dev.counted_peak, dev.counted);
+    }
+    dev.rows_held += pend.rows_bytes;
+    dev.rows_peak = std::max(dev.rows_peak, dev.rows_held);
+    lk.unlock();
+    if (pend.evicted) {
+      pend.proof.reset();  // aborted; then its witness goes back to the lane's pool
+      data.reset();
+    }
+    pend.held.set(ses->ctx, pend.evicted ? pend.rows_bytes : cost);
   }
   const Clock::time_point t2 = Clock::now();
   pend.global = global;
@@ -470,6 +544,7 @@ const char* r0h_session_begin(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t*
               "r0h_session_begin: r0h_ctx_set_check_session is on and this is part %u of %u: a rank sees its own segments only, the session check covers single-rank sessions", part, parts);
   ses->check_session = trace_mode && ctx->check_session;
   if (trace_mode && ((ctx->image_circuit && part == 0) || ses->check_session)) ses->elf.assign(elf, elf + elf_len);
+  ses->device.limit = trace_mode ? ctx->session_device_limit : 0;
   ses->resident_limit = ctx->session_resident_limit;
   if (!ses->resident_limit) {
     size_t free_b = 0, total_b = 0;
@@ -547,11 +622,19 @@ const char* check_session(r0h_session* s) {
   std::unique_ptr<r0h_session_balance, SessionBalanceFree> sb(made);
   bool own_proof = false;  // a proof of the caller's context is still to be finished: it closes the profile
   for (Pending& p : s->pending) {  // in index order
+    // an evicted segment's witness is expanded again for its addition, into a block that goes back behind it.  The multiplicity
+    // columns stay zero there: the addition walks the accumulators with a public total only, and those read no table column
+    // (balance.hip builds its tape from accumulators n_chain.. alone; the tables' fractions are links of the chain).
+    DevBuf again;
+    if (p.evicted) {
+      R0H_TRY(again.alloc(p.lctx, ((size_t)s->c->group_size[R0H_GROUP_DATA] << p.po2) * 4));
+      R0H_TRY(r0h_trace_rows_expand(p.rows.get(), again.get()));
+    }
     if (p.lctx != ctx) R0H_TRY(r0h_sync(p.lctx));
     else own_proof = own_proof || !p.done;
     const r0h_buf* code_cols = nullptr;
     R0H_TRY(r0h_code_commit_columns(p.cc, &code_cols));
-    R0H_TRY(r0h_session_balance_add(sb.get(), (uint32_t)p.index, s->c, p.po2, code_cols, p.data.get(), p.global.data()));
+    R0H_TRY(r0h_session_balance_add(sb.get(), (uint32_t)p.index, s->c, p.po2, code_cols, p.evicted ? again.get() : p.data.get(), p.global.data()));
   }
   R0H_TRY(r0h_session_balance_add_verifier_side(sb.get(), s->elf.data(), s->elf.size(), s->journal.data(), s->journal.size()));
   char* text = nullptr;
@@ -579,6 +662,28 @@ const char* finish_segment(r0h_session* s, Pending& p, const uint32_t challenge[
   R0H_TRY(logup_accum_kept(p.lctx, c, p.po2, code_cols, data.get(), p.global.data(), mix.data(), accum.get(), &kept));
   kept.terms.reset();
   return r0h_proof_finish(p.proof.release(), accum.get(), seal.data(), seal.size(), words);  // consumed either way
+}
+// Phase 2 of an evicted segment, before it is finished: committed again from its rows, on its lane, to the root it was recorded with.
+// A replayed commitment continues the profile of the lane's context (the session check's phase is in it) instead of opening one.
+const char* replay_segment(r0h_session* s, Pending& p) {
+  const Clock::time_point t0 = Clock::now();
+  R0H_TRY(p.data.alloc(p.lctx, ((size_t)s->c->group_size[R0H_GROUP_DATA] << p.po2) * 4));
+  uint32_t root[8];
+  Clock::time_point t1;
+  p.lctx->prof.continued = true;
+  const char* err = commit_rows(s->c, p, p.data.get(), p.global.data(), root, &t1);
+  p.lctx->prof.continued = false;
+  R0H_TRY(err);
+  R0H_REQUIRE(!memcmp(root, p.root, 32), "r0h_session_finish: segment %zu committed another root when it was replayed", p.index);
+  p.evicted = false;
+  p.rows.reset();  // (the commitment has waited for the stream)
+  p.held.set(s->ctx, p.data->bytes + r0h_proof_resident_bytes(p.proof.get()));
+  std::lock_guard<std::mutex> lk(s->result_mu);
+  s->device.replayed++;
+  s->device.rows_held -= p.rows_bytes;
+  s->stats.witgen_ms += 1e3 * seconds(t0, t1);
+  s->stats.prove_ms += 1e3 * seconds(t1, Clock::now());
+  return nullptr;
 }
 }  // namespace
 
@@ -610,8 +715,15 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
       for (Pending& p : s->pending) {
         if (p.lctx != lctx || p.done) continue;
         if (failed) return nullptr;
+        if (p.evicted) R0H_TRY(replay_segment(s, p));  // one at a time: finished before the lane's next one is committed again
         const Clock::time_point t0 = Clock::now();
         R0H_TRY(finish_segment(s, p, challenge, mix, seal, &words));
+        if (p.rows) {  // a segment that stayed committed: its rows were not needed
+          p.rows.reset();
+          std::lock_guard<std::mutex> lk(s->result_mu);
+          s->device.rows_held -= p.rows_bytes;
+        }
+        p.held.set(nullptr, 0);  // (witness and proof went with finish_segment)
         std::lock_guard<std::mutex> lk(s->result_mu);
         p.seal.assign(seal.begin(), seal.begin() + words);
         p.done = true;
@@ -635,6 +747,8 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
   if (cycles_out) *cycles_out = s->cycles;
   s->stats.wall_s = seconds(s->t_begin, Clock::now());
   s->ctx->session = s->stats;
+  const uint64_t device[4] = {s->device.evicted, s->device.replayed, s->device.counted_peak, s->device.rows_peak};
+  memcpy(s->ctx->session_device, device, sizeof device);
   *receipt_out = rc_guard.release();
   return nullptr;
   R0H_GUARD_END

@@ -278,7 +278,7 @@ const char* r0h_session_balance_report(r0h_session_balance* sb, r0h_session_imba
 const char* r0h_session_balance_message(r0h_session_balance* sb, char** text_out);
 const char* r0h_session_balance_stats(r0h_session_balance* sb, uint64_t stats_out[4]);
 /* on != 0: from now on r0h_session_finish (and so r0h_prove_elf) of a trace-circuit session on this context checks the session balance
- * of all its segments' DATA witnesses (still resident, lean segments included) with the verifier's side from the ELF and the run's
+ * of all its segments' DATA witnesses (still resident, lean segments included; an evicted segment's is expanded again from its rows) with the verifier's side from the ELF and the run's
  * journal BEFORE the session challenge is derived, and a session that does not balance returns "r0h_prove_elf: session fraction F
  * does not balance: ..." (the message above) with its proofs aborted; the phase is `check_session` in the profile.  Single-rank
  * sessions only: a rank sees its own segments alone, and r0h_session_begin with parts > 1 refuses the switch (a multi-rank driver
@@ -721,6 +721,21 @@ typedef struct { uint32_t number /* index + 1 */, closing, idle_pc /* where a se
 const char* r0h_trace_witgen(r0h_ctx* ctx, const r0h_preflight_row* rows, size_t n_rows, const r0h_preflight_bound* bounds,
                              size_t n_bounds, uint32_t po2, const r0h_trace_segment* segment, r0h_buf* data,
                              uint32_t globals_out[R0H_TRACE_GLOBALS]);
+/* The two halves of r0h_trace_witgen, for a caller that expands the same rows more than once (a session that evicts a committed
+ * segment and commits it again: r0h_ctx_set_session_device_limit).  r0h_trace_rows_upload checks the arguments as r0h_trace_witgen
+ * does, copies the rows, the boundary rows and the expansion's tables into one device block owned by the handle, and gives the early
+ * public inputs; the host arrays may be released when it returns.  r0h_trace_rows_expand launches the expansion from that block into
+ * `data` (R0H_TRACE_COLUMNS * 2^po2 words, same device): stream-ordered on the handle's context, not synchronised, any number of
+ * times, the same words every time -- those r0h_trace_witgen leaves.  r0h_trace_rows_bytes: the device bytes the handle keeps (72 per
+ * cycle, 32 per boundary row, the tables; 0 for NULL).  The handle holds a reference on its context; r0h_trace_rows_free releases it
+ * and the block (NULL is fine).  r0h_trace_witgen == upload + expand + free with one wait at the end. */
+typedef struct r0h_trace_rows r0h_trace_rows;
+const char* r0h_trace_rows_upload(r0h_ctx* ctx, const r0h_preflight_row* rows, size_t n_rows, const r0h_preflight_bound* bounds,
+                                  size_t n_bounds, uint32_t po2, const r0h_trace_segment* segment, r0h_trace_rows** rows_out,
+                                  uint32_t globals_out[R0H_TRACE_GLOBALS]);
+const char* r0h_trace_rows_expand(const r0h_trace_rows* rows, r0h_buf* data);
+size_t r0h_trace_rows_bytes(const r0h_trace_rows* rows);
+const char* r0h_trace_rows_free(r0h_trace_rows* rows);
 /* ---- the log-derivative argument of a circuit (blob section LOGUP): lookups, memory tuples, session tuples as fractions of running
  * sums in ACCUM.  Multiplicities: the table columns of DATA are filled from the lookups the rows make -- BEFORE the DATA group is
  * committed (r0h_trace_witgen and r0h_vm_trace_witness leave them zero).  Totals: the accumulators whose challenges are public inputs
@@ -753,6 +768,23 @@ const char* r0h_vm_segment_claim(const r0h_vm* vm, size_t i, r0h_receipt_claim* 
  * when their proofs are finished (about 2 ms each).  0 = the default: an eighth of the device's memory.  The reference's own run is
  * 37 segments (docs/runtime.md: session_cycles = 39,265,237): 100 GiB resident without a limit, per session in flight. */
 const char* r0h_ctx_set_session_resident_limit(r0h_ctx* ctx, uint64_t bytes);
+/* How many bytes the committed segments of a trace-circuit session begun on this context may keep on the device between its two
+ * phases.  A segment counts as its DATA witness, what its proof holds (r0h_proof_resident_bytes, after the shrink of a lean segment)
+ * and its rows handle.  A segment whose commitment would take the count above the limit is EVICTED as soon as its DATA root and early
+ * public inputs are recorded: its proof is aborted, its witness released, and only its compact rows stay on the device (r0h_trace_rows:
+ * a seventeenth of what a lean segment holds; they are on top of the limit).  r0h_session_finish commits such a segment a second time
+ * on its lane -- commitment is deterministic: the root must be the recorded one, else "r0h_session_finish: segment I committed another
+ * root when it was replayed" -- and finishes it like any other; a lane replays one segment at a time, so a session holds at most the
+ * limit, its evicted rows and one segment in flight per lane.  The seals are the ones an unlimited session makes.  The cost is one more
+ * expansion and DATA commitment per evicted segment.  0 = the default: no limit, nothing is kept or counted differently.  Taken per
+ * session at r0h_session_begin; other circuits are proved at once and have nothing to evict.
+ * r0h_last_session_device: of the last session finished on this context -- segments evicted, segments replayed, the largest value
+ * the count reached (bytes; kept with or without a limit), the most bytes held in rows handles (0 without a limit).
+ * r0h_ctx_session_held_bytes: what the unfinished sessions begun on this context hold on the device right now by the same count,
+ * evicted segments' rows included; 0 once every session is finished or freed. */
+const char* r0h_ctx_set_session_device_limit(r0h_ctx* ctx, uint64_t bytes);
+const char* r0h_last_session_device(r0h_ctx* ctx, uint64_t out[4]);
+uint64_t r0h_ctx_session_held_bytes(const r0h_ctx* ctx);
 const char* r0h_prove_elf(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t* elf, size_t elf_len, const uint32_t* input_words,
                           size_t n_input, uint32_t segment_po2, uint64_t max_cycles, r0h_receipt** receipt_out,
                           uint8_t image_id_out[32], uint64_t* cycles_out);
