@@ -59,6 +59,8 @@ _SIGNATURES = {
     "r0h_hash_rows": [_vp, _vp, _vp, _u32, _u32],
     "r0h_hash_fold": [_vp, _vp, _u32],
     "r0h_merkle_build": [_vp, _vp, _vp, _u32, _u32],
+    "r0h_merkle_top": [_vp, _vp, _u32, _u32, _vp],
+    "r0h_merkle_open_top": [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp],
     "r0h_batch_evaluate_any": [_vp, _vp, _u32, _vp, _vp, _u32, _vp],
     "r0h_mix_poly_coeffs": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32],
     "r0h_eltwise_add_elem": [_vp, _vp, _vp, _vp, _u32],
@@ -102,6 +104,8 @@ _SIGNATURES = {
     "r0h_ctx_set_session_resident_limit": [_vp, _u64],
     "r0h_ctx_set_session_device_limit": [_vp, _u64],
     "r0h_last_session_device": [_vp, _vp],
+    "r0h_ctx_set_session_tree_tops": [_vp, _u32],
+    "r0h_last_session_tree_tops": [_vp, _vp],
     "r0h_proof_shrink": [_vp, _vp],
     "r0h_sponge_trace": [_vp, _sz, _u32, _vp],
     "r0h_image_po2": [_vp, _sz, _vp],
@@ -121,6 +125,8 @@ _SIGNATURES = {
     "r0h_code_commit_root": [_vp, _vp],
     "r0h_prove_segment_committed": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _c.POINTER(_sz)],
     "r0h_proof_begin_committed": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _pp],
+    "r0h_proof_data_top": [_vp, _u32, _vp],
+    "r0h_proof_begin_committed_top": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _pp],
     "r0h_serde_encode_str": [_vp, _sz, _vp, _sz, _c.POINTER(_sz)],
     "r0h_serde_decode_str": [_vp, _sz, _c.POINTER(_sz), _c.POINTER(_sz), _c.POINTER(_sz)],
     "r0h_journal_commitment_span": [_vp, _sz, _c.POINTER(_sz), _c.POINTER(_sz)],
@@ -1425,6 +1431,26 @@ class Hal:
     def merkle_build(self, nodes, matrix, rows, cols):
         _check(lib().r0h_merkle_build(self.ctx, nodes.handle, matrix.handle, rows, cols))
 
+    def merkle_top(self, nodes, rows, levels, top=None):
+        """The top of a built tree (r0h_merkle_top): digests [0, 2 * rows >> levels) of `nodes` into `top` (a Buf of that many digests
+        is allocated otherwise); returns it."""
+        out = top if top is not None else self.alloc(max(8, ((2 * rows) >> min(levels, 31)) * 8))
+        try:
+            _check(lib().r0h_merkle_top(self.ctx, nodes.handle, rows, levels, out.handle))
+        except R0HipError:
+            if top is None:
+                out.free()
+            raise
+        return out
+
+    def merkle_open_top(self, out, matrix, top, levels, idx, rows, cols):
+        """Packed openings of the rows `idx` from a matrix and its tree's top (r0h_merkle_open_top) into the Buf `out`: per query the
+        `cols` column values, then the sibling digests.  A top that does not belong to the matrix raises the library's error, which
+        names the first query whose subtree does not hash to the top's node."""
+        a, pa = _u32arr(idx)
+        first = _u32(0)
+        _check(lib().r0h_merkle_open_top(self.ctx, out.handle, matrix.handle, top.handle, levels, pa, a.size, rows, cols, ctypes.byref(first)))
+
     def batch_evaluate_any(self, coeffs, po2, which, xs, out):
         w, pw = _u32arr(which)
         x, px = _u32arr(xs)
@@ -1738,6 +1764,18 @@ class Hal:
         _check(lib().r0h_last_session_device(self.ctx, out))
         return dict(zip(("evicted", "replayed", "peak_counted_bytes", "rows_bytes"), (int(v) for v in out)))
 
+    def set_session_tree_tops(self, levels):
+        """an evicted segment of a session on this context also keeps the top of its DATA tree, down to `levels` above the leaves, and
+        is committed again without hashing (r0h_ctx_set_session_tree_tops; 0 = off, the default) -- same seals"""
+        _check(lib().r0h_ctx_set_session_tree_tops(self.ctx, levels))
+
+    def last_session_tree_tops(self):
+        """Of the last session finished on this context (r0h_last_session_tree_tops): segments replayed from their tree top, the peak
+        of the bytes held in tops, the levels in force."""
+        out = (ctypes.c_uint64 * 3)()
+        _check(lib().r0h_last_session_tree_tops(self.ctx, out))
+        return dict(zip(("replayed_from_top", "tops_bytes", "levels"), (int(v) for v in out)))
+
     def session_held_bytes(self):
         """device bytes the unfinished sessions of this context hold right now (r0h_ctx_session_held_bytes)"""
         return int(lib().r0h_ctx_session_held_bytes(self.ctx))
@@ -1764,14 +1802,34 @@ class Hal:
         _check(lib().r0h_last_session_stats(self.ctx, ctypes.byref(st)))
         return {name: getattr(st, name) for name, _ in SessionStats._fields_}
 
-    def proof_begin(self, circuit, po2, code, data, glob):
-        """Commit CODE and DATA; returns (proof handle, accumulation mix words)."""
+    def proof_begin(self, circuit, po2, code, data, glob, top=None):
+        """Commit CODE and DATA; returns (proof handle, accumulation mix words).  top=(Buf, levels): the DATA group's tree top as
+        proof_data_top gave it -- DATA is interpolated and evaluated, no tree is built (r0h_proof_begin_committed_top; `code` is a
+        CodeCommit then)."""
         g, pg = _u32arr(glob)
         mix = np.zeros(max(circuit.n_mix, 1), dtype=np.uint32)
         h = _vp()
+        if top is not None:
+            if not isinstance(code, CodeCommit):
+                raise R0HipError("proof_begin: the top= form takes a CodeCommit (r0h_proof_begin_committed_top)")
+            _check(lib().r0h_proof_begin_committed_top(self.ctx, circuit.handle, po2, code.handle, data.handle, pg, top[0].handle, top[1], mix.ctypes.data_as(_vp),
+                                                       ctypes.byref(h)))
+            return h, mix[:circuit.n_mix]
         fn = lib().r0h_proof_begin_committed if isinstance(code, CodeCommit) else lib().r0h_proof_begin
         _check(fn(self.ctx, circuit.handle, po2, code.handle, data.handle, pg, mix.ctypes.data_as(_vp), ctypes.byref(h)))
         return h, mix[:circuit.n_mix]
+
+    def proof_data_top(self, proof, po2, levels, top=None):
+        """The top of a begun proof's DATA tree (r0h_proof_data_top): 2 * 4 * 2^po2 >> levels digests into `top` (allocated otherwise);
+        returns the Buf."""
+        out = top if top is not None else self.alloc(max(8, ((8 << po2) >> min(levels, 31)) * 8))
+        try:
+            _check(lib().r0h_proof_data_top(proof, levels, out.handle))
+        except R0HipError:
+            if top is None:
+                out.free()
+            raise
+        return out
 
     def proof_finish(self, proof, accum, seal_capacity_words=1 << 20):
         seal = np.empty(seal_capacity_words, dtype=np.uint32)

@@ -481,6 +481,17 @@ const char* r0h_last_session_device(r0h_ctx* ctx, uint64_t out[4]) {
   return nullptr;
 }
 uint64_t r0h_ctx_session_held_bytes(const r0h_ctx* ctx) { return ctx ? ctx->session_held.load() : 0; }
+const char* r0h_ctx_set_session_tree_tops(r0h_ctx* ctx, uint32_t levels) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_session_tree_tops: ctx is NULL");
+  R0H_REQUIRE(levels <= R0H_MERKLE_TOP_MAX_LEVELS, "r0h_ctx_set_session_tree_tops: levels %u outside [0, %u] (0: off)", levels, (unsigned)R0H_MERKLE_TOP_MAX_LEVELS);
+  ctx->session_tree_tops = levels;
+  return nullptr;
+}
+const char* r0h_last_session_tree_tops(r0h_ctx* ctx, uint64_t out[3]) {
+  R0H_REQUIRE(ctx && out, "r0h_last_session_tree_tops: NULL argument");
+  memcpy(out, ctx->session_tops, sizeof ctx->session_tops);
+  return nullptr;
+}
 const char* r0h_kernel_timing(r0h_ctx* ctx, int enable) {
   R0H_REQUIRE(ctx, "r0h_kernel_timing: ctx is NULL");
   R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));

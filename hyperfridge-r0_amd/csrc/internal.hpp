@@ -121,6 +121,8 @@ struct r0h_ctx {
   uint64_t session_resident_limit = 0;  // r0h_ctx_set_session_resident_limit (0: an eighth of the device's memory)
   uint64_t session_device_limit = 0;    // r0h_ctx_set_session_device_limit (0: none)
   uint64_t session_device[4] = {0, 0, 0, 0};  // r0h_last_session_device: evicted, replayed, peak count, peak bytes in rows handles
+  uint32_t session_tree_tops = 0;       // r0h_ctx_set_session_tree_tops: levels an evicted segment's DATA tree top stops above the leaves (0: no tops kept)
+  uint64_t session_tops[3] = {0, 0, 0}; // r0h_last_session_tree_tops: replayed from their top, peak bytes in tops, levels in force
   std::atomic<uint64_t> session_held{0};  // r0h_ctx_session_held_bytes: what unfinished sessions of this context hold (their lanes add and subtract)
   void* session_rows = nullptr;   // session.cpp: the preflight row buffers of r0h_prove_elf, page-locked, kept from one call to the next (session_rows_free)
   std::vector<r0h_ctx*> helpers;  // further contexts of the same device, made on demand by r0h_prove_elf for its extra prover lanes; they go with this one
@@ -303,6 +305,14 @@ void sha_hash_elems_host(const uint32_t* words, size_t n, uint32_t digest[8]);
 // ... and on the device (sha256.hip): what r0h_hash_rows / r0h_hash_fold run on a context whose suite is SHA-256 (arguments checked by the callers)
 const char* sha256_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix, uint32_t rows, uint32_t cols);
 const char* sha256_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size);
+// merkle_top.hip: a tree kept as its top (digests [0, 2 * rows >> levels)) and the openings made from it under the context's suite.
+// merkle_top_copy: r0h_merkle_top under the caller's name.  merkle_open_top: device pointers, stream-ordered; `report` (two device words,
+// reset here) receives the count of queries whose subtree does not hash to the top's node and the lowest such query;
+// merkle_open_top_verdict makes the caller's error of it ("<caller>: tree top does not match the matrix under query q (row r)").
+const char* merkle_top_copy(r0h_ctx* ctx, const r0h_buf* nodes, uint32_t rows, uint32_t levels, r0h_buf* top_out, const char* caller);
+const char* merkle_open_top(r0h_ctx* ctx, uint32_t* out, const uint32_t* matrix, const uint32_t* top, uint32_t levels, const uint32_t* d_idx, uint32_t n_q, uint32_t rows,
+                            uint32_t cols, uint32_t* report);
+const char* merkle_open_top_verdict(const char* caller, const uint32_t report[2], const uint32_t* idx_host);
 // receipts, sessions, image proofs and recursion nodes name Poseidon2 only: their entry points refuse a context on another suite
 const char* require_poseidon2(const r0h_ctx* ctx, const char* caller);
 }  // namespace r0h

@@ -15,20 +15,7 @@ __global__ __launch_bounds__(256) void hash_rows_kernel(uint32_t* __restrict__ d
   uint32_t row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
   uint32_t c[P2_CELLS];
-#pragma unroll
-  for (int i = 0; i < P2_CELLS; i++) c[i] = 0;
-  const uint32_t* src = matrix + row;
-  const uint32_t blocks = cols ? (cols + P2_RATE - 1) / P2_RATE : 1u;  // the last one may be partial, zero-padded (all zeros for cols == 0)
-  // One permutation body for every block: the first enters with a zero capacity, only the digest is read from the last.  One
-  // form of the loads too, each behind a scalar test of its column (two bodies, or a full and a padded form of the loads side by
-  // side, cost registers and 0.2-0.6 % of the kernel: profiles/r11/poseidon2_trims.md).
-  // (prefetching the next rate block into registers was measured: no gain, the kernel is VALU-issue bound)
-  for (uint32_t blk = 0; blk < blocks; blk++) {
-    const uint32_t have = cols - blk * P2_RATE;  // columns left, this block's included
-#pragma unroll
-    for (int i = 0; i < P2_RATE; i++) c[i] = (uint32_t)i < have ? src[(size_t)(blk * P2_RATE + i) * rows] : 0u;
-    p2_mix_ends(c, k, blk == 0, blk + 1 == blocks);
-  }
+  p2_hash_row(c, matrix + row, rows, cols, k);  // the row sponge (poseidon2_device.hpp)
   uint4* dst = (uint4*)(digests + (size_t)row * 8);
   dst[0] = make_uint4(c[0], c[1], c[2], c[3]);
   dst[1] = make_uint4(c[4], c[5], c[6], c[7]);

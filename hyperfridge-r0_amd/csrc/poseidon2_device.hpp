@@ -262,4 +262,23 @@ __device__ __forceinline__ void p2_mix(uint32_t (&c)[P2_CELLS], const P2Consts* 
   p2_mix_ends(c, k, (ENDS & P2_ZERO_CAP) != 0, (ENDS & P2_DIGEST_ONLY) != 0);
 }
 
+// The row sponge: c[0..7] = digest of the `cols` words src[0], src[rows], src[2 * rows], .. (one row of a column-major matrix), absorbed
+// in rate blocks.  What hash_rows_kernel computes per lane (poseidon2.hip) and merkle_open_top_kernel per leaf (merkle_top.hip).
+__device__ __forceinline__ void p2_hash_row(uint32_t (&c)[P2_CELLS], const uint32_t* src, uint32_t rows, uint32_t cols,
+                                            const P2Consts* __restrict__ k) {
+#pragma unroll
+  for (int i = 0; i < P2_CELLS; i++) c[i] = 0;
+  const uint32_t blocks = cols ? (cols + P2_RATE - 1) / P2_RATE : 1u;  // the last one may be partial, zero-padded (all zeros for cols == 0)
+  // One permutation body for every block: the first enters with a zero capacity, only the digest is read from the last.  One
+  // form of the loads too, each behind a scalar test of its column (two bodies, or a full and a padded form of the loads side by
+  // side, cost registers and 0.2-0.6 % of the kernel: profiles/r11/poseidon2_trims.md).
+  // (prefetching the next rate block into registers was measured: no gain, the kernel is VALU-issue bound)
+  for (uint32_t blk = 0; blk < blocks; blk++) {
+    const uint32_t have = cols - blk * P2_RATE;  // columns left, this block's included
+#pragma unroll
+    for (int i = 0; i < P2_RATE; i++) c[i] = (uint32_t)i < have ? src[(size_t)(blk * P2_RATE + i) * rows] : 0u;
+    p2_mix_ends(c, k, blk == 0, blk + 1 == blocks);
+  }
+}
+
 }  // namespace r0h

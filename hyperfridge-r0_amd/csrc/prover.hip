@@ -44,9 +44,12 @@ __global__ void merkle_open_kernel(uint32_t* __restrict__ out, const uint32_t* _
     dst[col_size + w] = nodes[(size_t)node * 8 + (w & 7)];
   }
 }
+// The full form holds all 2 * rows nodes.  The top form (top_levels != 0: r0h_proof_begin_committed_top) holds digests
+// [0, 2 * rows >> top_levels) only, and its openings hash the bottom top_levels levels again from the matrix (merkle_top.hip).
 struct Tree {
   MerkleShape mp;
   DevBuf nodes;
+  uint32_t top_levels = 0;
   const r0h_buf* matrix = nullptr;
   Tree(size_t rows, size_t cols) : mp(rows, cols) {}
 };
@@ -69,10 +72,21 @@ static const char* tree_top(r0h_ctx* ctx, const Tree& t, TreeTop& top) {
   top.nodes.assign(2 * t.mp.top_size * 8, 0u);
   return r0h_buf_d2h(ctx, t.nodes.get(), 32, top.nodes.data() + 8, (2 * t.mp.top_size - 1) * 32);
 }
-// open `n_q` rows: returns packed openings on the host (their device block goes back to the pool behind the read-back)
-static const char* tree_open(r0h_ctx* ctx, const Tree& t, const r0h_buf* d_idx, uint32_t n_q, std::vector<uint32_t>& host) {
+// open `n_q` rows: returns packed openings on the host (their device block goes back to the pool behind the read-back).  A tree in
+// its top form reports, behind the openings in the same block, whether every queried subtree hashed to the top's node.
+static const char* tree_open(r0h_ctx* ctx, const Tree& t, const r0h_buf* d_idx, const uint32_t* idx_host, uint32_t n_q, std::vector<uint32_t>& host) {
   DevBuf packed;
   const size_t words = t.mp.opening_words();
+  if (t.top_levels) {
+    R0H_TRY(packed.alloc(ctx, ((size_t)n_q * words + 2) * 4));
+    R0H_TRY(merkle_open_top(ctx, u32(packed.get()), u32(t.matrix), u32(t.nodes.get()), t.top_levels, u32(d_idx), n_q, (uint32_t)t.mp.rows, (uint32_t)t.mp.cols,
+                            u32(packed.get()) + (size_t)n_q * words));
+    host.resize((size_t)n_q * words + 2);
+    R0H_TRY(r0h_buf_d2h(ctx, packed.get(), 0, host.data(), host.size() * 4));
+    const uint32_t report[2] = {host[host.size() - 2], host[host.size() - 1]};
+    host.resize((size_t)n_q * words);
+    return merkle_open_top_verdict("r0h_proof_finish", report, idx_host);
+  }
   R0H_TRY(packed.alloc(ctx, (size_t)n_q * words * 4));
   hipLaunchKernelGGL(merkle_open_kernel, dim3(n_q), dim3(256), 0, ctx->stream, u32(packed.get()), u32(t.matrix), u32(t.nodes.get()), u32(d_idx),
                      (uint32_t)t.mp.rows, (uint32_t)t.mp.cols, (uint32_t)t.mp.path_digests());
@@ -102,7 +116,8 @@ static const char* group_evaluate(r0h_ctx* ctx, Group& g, uint32_t po2) {
 // The commit of a group: witness columns -> bit-reversed, zk-shifted coefficients -> evaluations on 4N -> tree -> its top layer and
 // root on the host (a blocking read-back: the stream has drained when this returns).  CHECK comes with its coefficients made by its
 // own interpolation (witness == nullptr).
-static const char* group_commit(r0h_ctx* ctx, Group& g, const r0h_buf* witness, uint32_t po2, TreeTop& top) {
+// With `kept_top` (levels != 0) no tree is built: the group's tree takes its top form from a copy of those digests.
+static const char* group_commit(r0h_ctx* ctx, Group& g, const r0h_buf* witness, uint32_t po2, TreeTop& top, const r0h_buf* kept_top = nullptr, uint32_t levels = 0) {
   if (witness) {
     const size_t bytes = ((size_t)g.count << po2) * 4;
     R0H_REQUIRE(bytes <= witness->bytes, "prove_segment: witness buffer holds fewer than %u columns of 2^%u", g.count, po2);
@@ -113,7 +128,13 @@ static const char* group_commit(r0h_ctx* ctx, Group& g, const r0h_buf* witness, 
   R0H_TRY(group_evaluate(ctx, g, po2));
   // upstream flips the coefficients to natural order here; the sequencer keeps them bit-reversed instead (evaluate-at-z
   // uses permuted power tables, the FRI mix is order-agnostic) and flips only the handful of mixed combos
-  R0H_TRY(tree_build(ctx, g.tree, g.evaluated.get()));
+  if (levels) {
+    R0H_TRY(g.tree.nodes.alloc(ctx, ((g.tree.mp.rows * 2) >> levels) * 32));
+    R0H_TRY(merkle_top_copy(ctx, kept_top, (uint32_t)g.tree.mp.rows, levels, g.tree.nodes.get(), "r0h_proof_begin_committed_top"));
+    g.tree.top_levels = levels;
+  } else {
+    R0H_TRY(tree_build(ctx, g.tree, g.evaluated.get()));
+  }
   return tree_top(ctx, g.tree, top);
 }
 
@@ -210,16 +231,16 @@ static const char* code_commit(r0h_ctx* ctx, r0h_code_commit& cc, const r0h_buf*
   return group_commit(ctx, cc.g, columns, cc.po2, cc.top);
 }
 // a group of the proof committed: its top layer into the seal, its root into the transcript
-static const char* proof_commit(r0h_proof& st, Group& g, const r0h_buf* witness) {
+static const char* proof_commit(r0h_proof& st, Group& g, const r0h_buf* witness, const r0h_buf* kept_top = nullptr, uint32_t levels = 0) {
   TreeTop top;
-  R0H_TRY(group_commit(st.ctx, g, witness, st.po2, top));
+  R0H_TRY(group_commit(st.ctx, g, witness, st.po2, top, kept_top, levels));
   top.into(st.io);
   return nullptr;
 }
 
 static const char* proof_late(r0h_proof& st, const uint32_t* late);
-// steps 1 and 2: the transcript opens, CODE and DATA are committed
-static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_t* global) {
+// steps 1 and 2: the transcript opens, CODE and DATA are committed (DATA through its kept tree top where one is given)
+static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_t* global, const r0h_buf* data_top = nullptr, uint32_t top_levels = 0) {
   r0h_ctx* ctx = st.ctx;
   const r0h_circuit* circ = st.circ;
   const uint32_t po2 = st.po2;
@@ -260,7 +281,7 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_
   R0H_REQUIRE(code.ctx->device == ctx->device, "prove_segment: the CODE commitment lives on device %d, this context on device %d", code.ctx->device, ctx->device);
   code.top.into(io);  // the same words whoever committed
   profile_phase(ctx, "commit_data");
-  R0H_TRY(proof_commit(st, st.g_data, data));
+  R0H_TRY(proof_commit(st, st.g_data, data, data_top, top_levels));
   R0H_TRY(r0h_buf_d2h(ctx, st.g_data.tree.nodes.get(), 32, st.data_root, 32));
   if (!circ->n_late) return proof_late(st, nullptr);
   return nullptr;
@@ -490,7 +511,7 @@ static const char* queries(r0h_proof& st) {
   std::vector<std::vector<uint32_t>> opened(n_trees);
   for (uint32_t t = 0; t < n_trees; t++) {
     r0h_buf view = buf_view(d_idx.get(), (size_t)t * nq * 4, (size_t)nq * 4);
-    R0H_TRY(tree_open(ctx, *trees[t], &view, nq, opened[t]));
+    R0H_TRY(tree_open(ctx, *trees[t], &view, idx.data() + (size_t)t * nq, nq, opened[t]));
   }
   for (uint32_t q = 0; q < nq; q++)
     for (uint32_t t = 0; t < n_trees; t++) {
@@ -558,14 +579,15 @@ static const char* prove_segment_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32
 }
 
 static const char* proof_begin_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_code_commit* cc,
-                                    const r0h_buf* data, const uint32_t* global, uint32_t* mix_out, r0h_proof** out) {
+                                    const r0h_buf* data, const uint32_t* global, uint32_t* mix_out, r0h_proof** out, const r0h_buf* data_top = nullptr,
+                                    uint32_t top_levels = 0) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && c && (code || cc) && data && out, "r0h_proof_begin: NULL argument");
   R0H_REQUIRE((global || r0h_circuit_n_global(c) == 0) && (mix_out || r0h_circuit_n_mix(c) == 0 || c->n_late), "r0h_proof_begin: NULL globals / mix_out");
   R0H_TRY(require_po2("r0h_proof_begin", po2));
   R0H_TRY_HIP(hipSetDevice(ctx->device));
   std::unique_ptr<r0h_proof> st(new r0h_proof(ctx, c, po2, code, cc));
-  R0H_TRY(proof_begin(*st, data, global));
+  R0H_TRY(proof_begin(*st, data, global, data_top, top_levels));
   if (c->n_mix && st->mix_drawn && mix_out) memcpy(mix_out, st->mix.data(), (size_t)c->n_mix * 4);
   *out = st.release();
   return nullptr;
@@ -592,6 +614,24 @@ const char* r0h_proof_begin_committed(r0h_ctx* ctx, const r0h_circuit* c, uint32
                                       const uint32_t* global, uint32_t* mix_out, r0h_proof** out) {
   R0H_REQUIRE(code, "r0h_proof_begin_committed: NULL argument");
   return proof_begin_impl(ctx, c, po2, nullptr, code, data, global, mix_out, out);
+}
+
+// The DATA commitment carried as its tree top: taken from a proof in flight, and a proof begun from it without hashing (merkle_top.hip)
+const char* r0h_proof_data_top(const r0h_proof* proof, uint32_t levels, r0h_buf* top_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(proof && top_out, "r0h_proof_data_top: NULL argument");
+  const Tree& t = proof->g_data.tree;
+  R0H_REQUIRE(!t.top_levels || t.top_levels <= levels, "r0h_proof_data_top: this proof keeps its DATA tree to %u levels above the leaves, a top at %u levels needs more", t.top_levels,
+              levels);
+  return merkle_top_copy(proof->ctx, t.nodes.get(), (uint32_t)t.mp.rows, levels, top_out, "r0h_proof_data_top");
+  R0H_GUARD_END
+}
+const char* r0h_proof_begin_committed_top(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data,
+                                          const uint32_t* global, const r0h_buf* top, uint32_t levels, uint32_t* mix_out, r0h_proof** out) {
+  R0H_REQUIRE(code && top, "r0h_proof_begin_committed_top: NULL argument");
+  R0H_REQUIRE(levels >= 1 && levels <= R0H_MERKLE_TOP_MAX_LEVELS, "r0h_proof_begin_committed_top: levels %u outside [1, %u]", levels,
+              (unsigned)R0H_MERKLE_TOP_MAX_LEVELS);  // (and at most the tree's path digests: merkle_top_copy, by name)
+  return proof_begin_impl(ctx, c, po2, nullptr, code, data, global, mix_out, out, top, levels);
 }
 
 // Commit the CODE group once (the sequencer's commit_code: code_commit above) and keep it, with a copy of the columns.

@@ -22,6 +22,9 @@
 // --session-device-limit-gb G (--elf mode, trace circuit) sets r0h_ctx_set_session_device_limit on every session context: the segments a
 // session cannot keep committed within G GiB wait for the challenge as their compact rows and are committed again when it is known; the
 // receipt is the one an unlimited run writes, and the result line says how many segments were evicted.
+// --session-keep-tree-tops L (with it) sets r0h_ctx_set_session_tree_tops: an evicted segment also keeps the top of its DATA tree, down to
+// L levels above the leaves (1..8; 6 is 4 MiB per 2^20-row segment), and is committed again without hashing; the result line says how
+// many segments were replayed from their top.
 // With --receipt-out / --receipt-dir every segment is proved for a claim (risc0-zkvm `ReceiptClaim`): the session's system states
 // are synthetic names (there is no executor here), segment k runs from state k to state k+1, all but the last end in SystemSplit,
 // the last halts with the journal's output; the claim's eight naming words are planted as the segment's public inputs.  The image
@@ -93,7 +96,9 @@ int main(int argc, char** argv) {
            "and the class's values (single-rank sessions; a diagnostic, not a verifier)\n"
            "       --session-device-limit-gb G: with --elf over the trace circuit, the committed segments of a session keep at most G GiB on the device between its two phases "
            "(a fraction is fine); a segment beyond that is evicted to its compact rows and committed again when the session is finished -- the same receipt; the run reports "
-           "how many were (default: no limit)\n%s\n", r0h_version());
+           "how many were (default: no limit)\n"
+           "       --session-keep-tree-tops L: with it, an evicted segment also keeps the top of its DATA tree down to L levels above the leaves (1..8) and is committed again "
+           "without hashing -- the same receipt; the run reports how many were replayed from their top (default 0: off)\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   // --compress takes no value: it is taken out of the arguments before the "--option value" pairs are read
@@ -116,6 +121,7 @@ int main(int argc, char** argv) {
   unsigned po2 = 16, segments = 1, device = 0, contexts = 1, verify = 0, receipts = 1;
   unsigned long long seed = 1;
   double session_device_limit_gb = 0;  // --session-device-limit-gb: r0h_ctx_set_session_device_limit of every session context
+  unsigned session_keep_tree_tops = 0;  // --session-keep-tree-tops: r0h_ctx_set_session_tree_tops of every session context
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--code-object")) co_path = argv[i + 1];
     else if (!strcmp(argv[i], "--po2")) po2 = (unsigned)atoi(argv[i + 1]);
@@ -133,6 +139,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--check-session")) check_session = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--fraction-names")) fraction_names_path = argv[i + 1];
     else if (!strcmp(argv[i], "--session-device-limit-gb")) session_device_limit_gb = atof(argv[i + 1]);
+    else if (!strcmp(argv[i], "--session-keep-tree-tops")) session_keep_tree_tops = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
     else if (!strcmp(argv[i], "--journal")) journal_text = argv[i + 1];
@@ -160,6 +167,10 @@ int main(int argc, char** argv) {
   }
   if (session_device_limit_gb < 0 || (session_device_limit_gb > 0 && elf_path.empty())) {
     fprintf(stderr, "r0h_prove: --session-device-limit-gb takes a size of zero or more and goes with --elf\n");
+    return 1;
+  }
+  if (session_keep_tree_tops > R0H_MERKLE_TOP_MAX_LEVELS || (session_keep_tree_tops && elf_path.empty())) {
+    fprintf(stderr, "r0h_prove: --session-keep-tree-tops takes 0 .. %u levels and goes with --elf\n", (unsigned)R0H_MERKLE_TOP_MAX_LEVELS);
     return 1;
   }
   if (hashfn != "poseidon2" && hashfn != "sha-256") { fprintf(stderr, "r0h_prove: --hashfn is poseidon2 or sha-256, not %s\n", hashfn.c_str()); return 1; }
@@ -203,6 +214,7 @@ int main(int argc, char** argv) {
   // --check-witness: the context's switch, and the checker's module now (from its code object, else compiled in-process) rather than inside the first proof
   auto arm_checker = [&](r0h_ctx* ctx, r0h_circuit* circ) {
     if (session_device_limit_gb > 0) CHECK(r0h_ctx_set_session_device_limit(ctx, std::max<uint64_t>(1, (uint64_t)(session_device_limit_gb * (double)(1ull << 30)))));
+    if (session_keep_tree_tops) CHECK(r0h_ctx_set_session_tree_tops(ctx, session_keep_tree_tops));
     if (check_balance) CHECK(r0h_ctx_set_check_balance(ctx, 1));
     if (check_session) CHECK(r0h_ctx_set_check_session(ctx, 1));
     if (!check_witness) return;
@@ -399,9 +411,11 @@ int main(int argc, char** argv) {
     CHECK(r0h_last_session_stats(ctx, &st));
     uint64_t device[4];  // of the first context's last session
     CHECK(r0h_last_session_device(ctx, device));
+    uint64_t tops[3];
+    CHECK(r0h_last_session_tree_tops(ctx, tops));
     printf("{\"receipt\": \"%s\", \"image_id\": \"%s\", \"receipts\": %u, \"contexts\": %u, \"segments\": %zu, \"cycles\": %llu, \"seconds\": %.4f, \"segments_per_s\": %.3f, \"receipts_per_s\": %.4f, "
-           "\"executor_s\": %.4f, \"evicted_segments\": %llu, \"receipts_verified_with_the_elf\": %u, \"receipts_verified_with_the_image_id_alone\": %u, \"verify_seconds\": %.3f, \"control_roots\": [",
-           receipt_out.c_str(), hex, receipts, contexts, n_seg, (unsigned long long)cycles, secs, (double)n_seg * receipts / secs, receipts / secs, st.executor_s, (unsigned long long)device[0], receipts,
+           "\"executor_s\": %.4f, \"evicted_segments\": %llu, \"segments_replayed_from_their_tree_top\": %llu, \"receipts_verified_with_the_elf\": %u, \"receipts_verified_with_the_image_id_alone\": %u, \"verify_seconds\": %.3f, \"control_roots\": [",
+           receipt_out.c_str(), hex, receipts, contexts, n_seg, (unsigned long long)cycles, secs, (double)n_seg * receipts / secs, receipts / secs, st.executor_s, (unsigned long long)device[0], (unsigned long long)tops[0], receipts,
            image_blob.empty() ? 0u : receipts, verify_secs);
     for (size_t k = 0; k < sizes.size(); k++) {
       const uint32_t* root = &root_table[9 * k + 1];

@@ -21,6 +21,9 @@
 // session exchange 28 words per segment between the phases (r0h_session_begin / _records / _finish; one rank: r0h_prove_elf).
 // A session with a device limit (r0h_ctx_set_session_device_limit) keeps the segments beyond it as their compact rows alone and
 // commits them a second time in phase 2 (commit_rows, replay_segment): its length is not bounded by the device's memory.
+// With r0h_ctx_set_session_tree_tops such a segment also keeps the top of its DATA tree and is committed again without hashing
+// (r0h_proof_begin_committed_top); that its rows still belong to the top is then checked where its proof opens the tree, not by
+// comparing roots.
 // With any other circuit the witness is the blob's synthetic column program with the claim planted: the seal then proves "a
 // satisfying trace of the loaded circuit exists whose public inputs name this claim", not "this program ran".
 #include <stdlib.h>
@@ -336,6 +339,7 @@ struct Pending {  // a segment between the phases: committed, waiting for the se
   std::unique_ptr<r0h_trace_rows, RowsFree> rows;
   bool evicted = false;  // `proof` and `data` were given up after phase 1: `rows`, `global`, `root`, `claim`, `po2` and the CODE commitment stay
   uint64_t rows_bytes = 0;
+  DevBuf top;  // r0h_ctx_set_session_tree_tops: an evicted segment's DATA tree top (from the lane's pool, like `rows`)
   Held held;
   r0h_code_commit* cc = nullptr;
   uint32_t po2 = 0;
@@ -363,7 +367,12 @@ struct r0h_session {
   uint64_t resident_limit = 0, resident_evaluations = 0;  // bytes of DATA evaluations kept between the phases (r0h_ctx_set_session_resident_limit)
   // r0h_ctx_set_session_device_limit: `counted` is what the segments that stay committed keep on the device (witness, proof, rows
   // handle), the value held against the limit; `rows_held` the bytes in rows handles, evicted segments' included
-  struct Device { uint64_t limit = 0, counted = 0, counted_peak = 0, rows_held = 0, rows_peak = 0, evicted = 0, replayed = 0; } device;
+  // r0h_ctx_set_session_tree_tops: `tops_levels` (0: none kept), the bytes in kept tops, the segments replayed from theirs
+  struct Device {
+    uint64_t limit = 0, counted = 0, counted_peak = 0, rows_held = 0, rows_peak = 0, evicted = 0, replayed = 0;
+    uint32_t tops_levels = 0;
+    uint64_t tops_held = 0, tops_peak = 0, replayed_from_top = 0;
+  } device;
   Clock::time_point t_begin;
   std::vector<r0h_ctx*> lane_ctx;
   ~r0h_session() {
@@ -374,13 +383,15 @@ struct r0h_session {
 
 namespace {
 // The DATA group of a segment from its staged rows, committed: phase 1 of every segment and phase 2 of an evicted one -- the same
-// launches over the same rows, so the same root.  `global`: the early public inputs, the late ones still zero.
-const char* commit_rows(const r0h_circuit* c, Pending& pend, r0h_buf* data, const uint32_t* global, uint32_t root[8], Clock::time_point* t_witness) {
+// launches over the same rows, so the same root.  `global`: the early public inputs, the late ones still zero.  A segment that kept
+// its tree top (`pend.top`, `top_levels`) is committed through it: the same witness, no tree built, the root the top's.
+const char* commit_rows(const r0h_circuit* c, Pending& pend, r0h_buf* data, const uint32_t* global, uint32_t root[8], Clock::time_point* t_witness, uint32_t top_levels = 0) {
   R0H_TRY(r0h_trace_rows_expand(pend.rows.get(), data));
   R0H_TRY(r0h_logup_multiplicities(pend.lctx, c, pend.po2, data, global));
   *t_witness = Clock::now();
   r0h_proof* proof = nullptr;
-  R0H_TRY(r0h_proof_begin_committed(pend.lctx, c, pend.po2, pend.cc, data, global, nullptr, &proof));
+  if (pend.top) R0H_TRY(r0h_proof_begin_committed_top(pend.lctx, c, pend.po2, pend.cc, data, global, pend.top.get(), top_levels, nullptr, &proof));
+  else R0H_TRY(r0h_proof_begin_committed(pend.lctx, c, pend.po2, pend.cc, data, global, nullptr, &proof));
   pend.proof.reset(proof);
   return r0h_proof_data_root(proof, root);
 }
@@ -425,11 +436,24 @@ const char* commit_segment(r0h_session* ses, RowBuffers& rows, const Produced& s
     dev.rows_held += pend.rows_bytes;
     dev.rows_peak = std::max(dev.rows_peak, dev.rows_held);
     lk.unlock();
+    uint64_t top_bytes = 0;
+    if (pend.evicted && dev.tops_levels) {  // the DATA tree's top stays, device to device, before the tree goes; its root is the recorded one
+      top_bytes = ((((uint64_t)R0H_INV_RATE << pend.po2) * 2) >> dev.tops_levels) * 32;
+      R0H_TRY(pend.top.alloc(pend.lctx, top_bytes));
+      R0H_TRY(r0h_proof_data_top(pend.proof.get(), dev.tops_levels, pend.top.get()));
+      uint32_t kept_root[8];
+      R0H_TRY(r0h_buf_d2h(pend.lctx, pend.top.get(), 32, kept_root, 32));
+      R0H_REQUIRE(!memcmp(kept_root, pend.root, 32), "r0h_session_begin: the tree top kept of segment %zu does not carry its recorded root", pend.index);
+      lk.lock();
+      dev.tops_held += top_bytes;
+      dev.tops_peak = std::max(dev.tops_peak, dev.tops_held);
+      lk.unlock();
+    }
     if (pend.evicted) {
       pend.proof.reset();  // aborted; then its witness goes back to the lane's pool
       data.reset();
     }
-    pend.held.set(ses->ctx, pend.evicted ? pend.rows_bytes : cost);
+    pend.held.set(ses->ctx, pend.evicted ? pend.rows_bytes + top_bytes : cost);
   }
   const Clock::time_point t2 = Clock::now();
   pend.global = global;
@@ -545,6 +569,7 @@ const char* r0h_session_begin(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t*
   ses->check_session = trace_mode && ctx->check_session;
   if (trace_mode && ((ctx->image_circuit && part == 0) || ses->check_session)) ses->elf.assign(elf, elf + elf_len);
   ses->device.limit = trace_mode ? ctx->session_device_limit : 0;
+  ses->device.tops_levels = ses->device.limit ? ctx->session_tree_tops : 0;  // (only an evicted segment keeps a top)
   ses->resident_limit = ctx->session_resident_limit;
   if (!ses->resident_limit) {
     size_t free_b = 0, total_b = 0;
@@ -671,15 +696,21 @@ const char* replay_segment(r0h_session* s, Pending& p) {
   uint32_t root[8];
   Clock::time_point t1;
   p.lctx->prof.continued = true;
-  const char* err = commit_rows(s->c, p, p.data.get(), p.global.data(), root, &t1);
+  const char* err = commit_rows(s->c, p, p.data.get(), p.global.data(), root, &t1, s->device.tops_levels);
   p.lctx->prof.continued = false;
   R0H_TRY(err);
+  // (from a kept top the root is the top's, held against the recorded one when it was kept: what ties the rows to it is the subtree
+  // check of the proof's openings)
   R0H_REQUIRE(!memcmp(root, p.root, 32), "r0h_session_finish: segment %zu committed another root when it was replayed", p.index);
   p.evicted = false;
   p.rows.reset();  // (the commitment has waited for the stream)
+  const uint64_t top_bytes = p.top ? p.top->bytes : 0;
+  p.top.reset();  // (the proof has its own copy)
   p.held.set(s->ctx, p.data->bytes + r0h_proof_resident_bytes(p.proof.get()));
   std::lock_guard<std::mutex> lk(s->result_mu);
   s->device.replayed++;
+  if (top_bytes) s->device.replayed_from_top++;
+  s->device.tops_held -= top_bytes;
   s->device.rows_held -= p.rows_bytes;
   s->stats.witgen_ms += 1e3 * seconds(t0, t1);
   s->stats.prove_ms += 1e3 * seconds(t1, Clock::now());
@@ -749,6 +780,8 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
   s->ctx->session = s->stats;
   const uint64_t device[4] = {s->device.evicted, s->device.replayed, s->device.counted_peak, s->device.rows_peak};
   memcpy(s->ctx->session_device, device, sizeof device);
+  const uint64_t tops[3] = {s->device.replayed_from_top, s->device.tops_peak, s->device.tops_levels};
+  memcpy(s->ctx->session_tops, tops, sizeof tops);
   *receipt_out = rc_guard.release();
   return nullptr;
   R0H_GUARD_END

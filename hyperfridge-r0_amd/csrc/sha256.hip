@@ -14,20 +14,8 @@ __global__ __launch_bounds__(256) void sha256_hash_rows_kernel(uint32_t* __restr
                                                                 uint32_t rows, uint32_t cols) {
   const uint32_t row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
-  uint32_t st[8], w[16];
-  sha_init(st);
-  const uint32_t* src = matrix + row;
-  const uint32_t blocks = (cols + 15) / 16, full = cols / 16;
-  for (uint32_t blk = 0; blk < blocks; blk++) {
-    if (blk < full) {  // (wave-uniform: cols is a kernel argument)
-#pragma unroll
-      for (int i = 0; i < 16; i++) w[i] = sha_bswap(src[(size_t)(blk * 16 + i) * rows]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; i++) w[i] = blk * 16 + i < cols ? sha_bswap(src[(size_t)(blk * 16 + i) * rows]) : 0u;
-    }
-    sha_compress(st, w);
-  }
+  uint32_t st[8];
+  sha_hash_row(st, matrix + row, rows, cols);  // the row sponge (sha256_device.hpp)
   uint4* dst = (uint4*)(digests + (size_t)row * 8);
   dst[0] = make_uint4(sha_bswap(st[0]), sha_bswap(st[1]), sha_bswap(st[2]), sha_bswap(st[3]));
   dst[1] = make_uint4(sha_bswap(st[4]), sha_bswap(st[5]), sha_bswap(st[6]), sha_bswap(st[7]));

@@ -51,4 +51,23 @@ __device__ __forceinline__ void sha_compress(uint32_t st[8], uint32_t w[16]) {
   st[0] += a; st[1] += b; st[2] += c; st[3] += d; st[4] += e; st[5] += f; st[6] += g; st[7] += h;
 }
 
+// The row sponge: st = state after the `cols` words src[0], src[rows], src[2 * rows], .. (one row of a column-major matrix), compressed in
+// 16-word blocks chained from the IV, the last partial block zero-filled; digest word j is sha_bswap(st[j]).  What
+// sha256_hash_rows_kernel computes per lane (sha256.hip) and merkle_open_top_kernel per leaf (merkle_top.hip).
+__device__ __forceinline__ void sha_hash_row(uint32_t st[8], const uint32_t* src, uint32_t rows, uint32_t cols) {
+  uint32_t w[16];
+  sha_init(st);
+  const uint32_t blocks = (cols + 15) / 16, full = cols / 16;
+  for (uint32_t blk = 0; blk < blocks; blk++) {
+    if (blk < full) {  // (wave-uniform: cols is a kernel argument)
+#pragma unroll
+      for (int i = 0; i < 16; i++) w[i] = sha_bswap(src[(size_t)(blk * 16 + i) * rows]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; i++) w[i] = blk * 16 + i < cols ? sha_bswap(src[(size_t)(blk * 16 + i) * rows]) : 0u;
+    }
+    sha_compress(st, w);
+  }
+}
+
 }  // namespace r0h

@@ -52,7 +52,7 @@ const char* r0h_ctx_create(int device, r0h_ctx** out);
 const char* r0h_ctx_destroy(r0h_ctx* ctx);
 const char* r0h_sync(r0h_ctx* ctx);
 /* The context's hash suite (risc0 `ProverOpts::hashfn`): "poseidon2" (the default) or "sha-256"; any other name is an error.
- * r0h_hash_rows, r0h_hash_fold[_io], r0h_merkle_build, r0h_code_root, r0h_code_commit_new and every r0h_prove_segment* / r0h_proof_*
+ * r0h_hash_rows, r0h_hash_fold[_io], r0h_merkle_build, r0h_merkle_open_top, r0h_code_root, r0h_code_commit_new and every r0h_prove_segment* / r0h_proof_*
  * entry follow it; under "poseidon2" they compute what they always did.  A r0h_code_commit remembers the suite it was made under
  * (using it from a context on the other suite is an error that names both), and so does a proof between begin and finish.
  * Receipts, sessions, image proofs and recursion nodes name Poseidon2 only: r0h_prove_elf*, r0h_session_begin, r0h_prove_image,
@@ -92,6 +92,23 @@ const char* r0h_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix,
 const char* r0h_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size);
 /* nodes has 2*rows digests: leaves at [rows, 2rows), root at index 1 */
 const char* r0h_merkle_build(r0h_ctx* ctx, r0h_buf* nodes, const r0h_buf* matrix, uint32_t rows, uint32_t cols);
+/* A tree kept as its top.  A Merkle path needs the whole tree only because the sibling at level l covers 2^l leaves; kept from the
+ * root down to `levels` levels above the leaves a tree is 2 * rows >> levels digests (2^-levels of it), and the bottom `levels`
+ * siblings of an opened leaf are hashed again from the 2^levels matrix rows of its subtree when the opening is made.
+ * `levels` lies in [1, min(R0H_MERKLE_TOP_MAX_LEVELS, path_digests)], path_digests = log2(rows) - top_layer being the sibling digests
+ * of an opening (the layer a seal carries instead of the root, the deepest one of at most 50 nodes, must lie in the kept part);
+ * anything else is an error that names the bounds.
+ * r0h_merkle_top: digests [0, 2 * rows >> levels) of the tree r0h_merkle_build left in `nodes` into top_out (index 0 unused, the root
+ * at 1); stream-ordered like every operation of the context.
+ * r0h_merkle_open_top: n_q packed openings into `out` -- per query the `cols` values of row idx_host[q], then the path_digests sibling
+ * digests nodes[((row + rows) >> l) ^ 1], l = 0 .. path_digests - 1, as the sequencer packs them -- read from (matrix, top) under the
+ * context's hash suite.  idx_host[q] < rows is checked here.  Every query's subtree must hash to the node the top has for it; if one
+ * does not the openings are still written, *first_mismatch_out (optional; 0xffffffff otherwise) is the lowest such query and the call
+ * returns "r0h_merkle_open_top: tree top does not match the matrix under query q (row r)".  Blocks until the report is back. */
+#define R0H_MERKLE_TOP_MAX_LEVELS 8
+const char* r0h_merkle_top(r0h_ctx* ctx, const r0h_buf* nodes, uint32_t rows, uint32_t levels, r0h_buf* top_out);
+const char* r0h_merkle_open_top(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* matrix, const r0h_buf* top, uint32_t levels,
+                                const uint32_t* idx_host, uint32_t n_q, uint32_t rows, uint32_t cols, uint32_t* first_mismatch_out);
 /* The SHA-256 suite (recalled from risc0-zkp core/hash/sha and risc0-sys sha256.h; unpinned: the reference vendors neither).
  * A digest is 8 words, word j = bswap32 of SHA-256 state word j, so its bytes in memory are the standard big-endian digest; message
  * word i of a compression = bswap32 of input word i.  Pair: one compression of the IV over the 16 words a || b, no padding, no
@@ -335,6 +352,20 @@ const char* r0h_prove_segment_committed(r0h_ctx* ctx, const r0h_circuit* c, uint
                                         size_t seal_capacity_words, size_t* seal_words_out);
 const char* r0h_proof_begin_committed(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code,
                                       const r0h_buf* data, const uint32_t* global_host, uint32_t* mix_out, r0h_proof** out);
+/* A DATA commitment made once and carried as its tree top (r0h_merkle_top of the 4N-row DATA tree; `levels` as there).
+ * r0h_proof_data_top: after a begin, the top of the proof's DATA tree into top_out (2 * 4N >> levels digests).
+ * r0h_proof_begin_committed_top: r0h_proof_begin_committed for a DATA group whose top is known: the columns are interpolated and
+ * evaluated, but no tree is built -- the seal's top layer and the transcript's root are read from `top` (copied: the caller's buffer
+ * is free again when the call returns), so both receive the words of the first commitment.  r0h_proof_late, r0h_proof_shrink and
+ * r0h_proof_finish take such a proof like any other; its openings are made by r0h_merkle_open_top's kernel, and if a queried subtree
+ * of the evaluations does not hash to the top's node -- the top belongs to other columns -- r0h_proof_finish returns "r0h_proof_finish:
+ * tree top does not match the matrix under query q (row r)" (the proof is consumed as always, the context stays usable).  The check
+ * is made at the queries only: a top that is wrong elsewhere yields a seal whose DATA root is not the columns' -- the verifier remains
+ * the judge of a seal.  r0h_proof_resident_bytes counts the kept top, not a whole tree. */
+const char* r0h_proof_data_top(const r0h_proof* proof, uint32_t levels, r0h_buf* top_out);
+const char* r0h_proof_begin_committed_top(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code,
+                                          const r0h_buf* data, const uint32_t* global_host, const r0h_buf* top, uint32_t levels,
+                                          uint32_t* mix_out, r0h_proof** out);
 /* Per-phase device time (ms) of the last proof on this context that came out -- r0h_prove_segment*, r0h_proof_finish, or the session check
  * that closes a profile; names are static strings, *n_out names and times, valid until the next one closes.  A proof in flight, aborted or failed
  * leaves the report as it was; a context that has closed none reports *n_out = 0. */
@@ -785,6 +816,18 @@ const char* r0h_ctx_set_session_resident_limit(r0h_ctx* ctx, uint64_t bytes);
 const char* r0h_ctx_set_session_device_limit(r0h_ctx* ctx, uint64_t bytes);
 const char* r0h_last_session_device(r0h_ctx* ctx, uint64_t out[4]);
 uint64_t r0h_ctx_session_held_bytes(const r0h_ctx* ctx);
+/* What an evicted segment keeps besides its rows: with levels in [1, R0H_MERKLE_TOP_MAX_LEVELS] the top of its DATA tree
+ * (r0h_proof_data_top: 2 * 4N >> levels digests -- 4 MiB for 2^20 rows at levels = 6 -- copied device to device before the proof is
+ * aborted, its root held against the recorded one).  r0h_session_finish then commits the segment again through
+ * r0h_proof_begin_committed_top: expansion, iNTT and the expanding NTT, no row hashing and no folds.  The comparison of the replayed
+ * root with the recorded one, which the hashing replay makes, is replaced by the subtree check at the 50 queries of
+ * r0h_proof_finish; the seals are the same.  0 = the default: off.  Every trace-circuit segment has at least 13 path digests, so
+ * every value up to 8 fits every segment.  Taken per session at r0h_session_begin; it matters only for segments that are evicted
+ * (r0h_ctx_set_session_device_limit).  The tops count in r0h_ctx_session_held_bytes, on top of the limit like the rows.
+ * r0h_last_session_tree_tops: of the last session finished on this context -- segments replayed from their top, the most bytes held
+ * in tops, the levels in force (0 for a session without a device limit: nothing is evicted, no top is kept). */
+const char* r0h_ctx_set_session_tree_tops(r0h_ctx* ctx, uint32_t levels);
+const char* r0h_last_session_tree_tops(r0h_ctx* ctx, uint64_t out[3]);
 const char* r0h_prove_elf(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t* elf, size_t elf_len, const uint32_t* input_words,
                           size_t n_input, uint32_t segment_po2, uint64_t max_cycles, r0h_receipt** receipt_out,
                           uint8_t image_id_out[32], uint64_t* cycles_out);

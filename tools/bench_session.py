@@ -59,6 +59,8 @@ def main():
     ap.add_argument("--resident-limit-gb", type=float, default=-1.0, help="r0h_ctx_set_session_resident_limit per session context (default: the library's, an eighth of the device)")
     ap.add_argument("--device-limit-gb", type=float, default=0.0, help="r0h_ctx_set_session_device_limit per session context: GiB the committed segments of a session keep on the device between "
                     "its phases; segments beyond it are evicted to their rows and committed again (default 0: no limit)")
+    ap.add_argument("--keep-tree-tops", type=int, default=0, help="r0h_ctx_set_session_tree_tops per session context: an evicted segment also keeps the top of its DATA tree, down to this many "
+                    "levels above the leaves (1..8), and is committed again without hashing (default 0: off)")
     ap.add_argument("--check-session", type=int, default=0, help="1: r0h_ctx_set_check_session -- the session balance of all segments is checked before the challenge is derived (single rank only)")
     args = ap.parse_args()
     world, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
@@ -99,6 +101,8 @@ def main():
         hal.set_session_resident_limit(int(args.resident_limit_gb * (1 << 30)))
     device_limit = max(1, int(args.device_limit_gb * (1 << 30))) if args.device_limit_gb > 0 else 0
     hal.set_session_device_limit(device_limit)
+    if args.keep_tree_tops:
+        hal.set_session_tree_tops(args.keep_tree_tops)
     others = []  # further sessions in flight beside this one: a context and a loaded circuit each
     if env is None and args.sessions > 1:
         import threading
@@ -107,6 +111,8 @@ def main():
             if args.resident_limit_gb >= 0:
                 h2.set_session_resident_limit(int(args.resident_limit_gb * (1 << 30)))
             h2.set_session_device_limit(device_limit)
+            if args.keep_tree_tops:
+                h2.set_session_tree_tops(args.keep_tree_tops)
             others.append((h2, h2.load_circuit(blob, entry.code_object_path("trace"))))
     peak_used = 0
     for _ in range(max(1, args.repeat)):
@@ -140,6 +146,7 @@ def main():
             env.barrier()
         wall = time.perf_counter() - t0
         st, dev = hal.last_session_stats(), hal.last_session_device()
+        tops = hal.last_session_tree_tops() if args.keep_tree_tops else {"replayed_from_top": 0, "tops_bytes": 0, "levels": 0}
     if env is not None and env.rank != 0:
         gc.free()
         hal.close()
@@ -164,6 +171,7 @@ def main():
     line = {"sessions_in_flight": args.sessions if env is None else 1, "lean_segments_of_the_reported_session": st["lean_segments"],
             "device_limit_GiB": args.device_limit_gb if device_limit else None, "evicted_segments_of_the_reported_session": dev["evicted"], "replayed_segments_of_the_reported_session": dev["replayed"],
             "peak_counted_bytes_of_the_reported_session": dev["peak_counted_bytes"], "rows_handle_bytes_of_the_reported_session": dev["rows_bytes"],
+            "tree_top_levels": tops["levels"] or None, "segments_replayed_from_their_tree_top": tops["replayed_from_top"], "tree_top_bytes_of_the_reported_session": tops["tops_bytes"],
             "peak_device_memory_used_GiB": round(peak_used / (1 << 30), 1) if peak_used else None, "metric": "segments/s of prove(env, elf) with the trace circuit: executor + device witgen + proof, all inside the timed region",
             "value": round(n / wall, 4), "unit": "segments/s", "n_gpus": world, "sharding": None if env is None else "segments rank, rank + %d, ... per rank (%s%s); receipts merged on rank 0" % (world, args.backend, ", all ranks on one GPU" if args.share_device else ""), "segment_po2": args.po2, "segments": len(seals), "cycles": cycles, "check_session": bool(args.check_session),
             "wall_s": round(wall, 4), "guest": what,
