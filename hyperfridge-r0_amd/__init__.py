@@ -61,6 +61,11 @@ _SIGNATURES = {
     "r0h_merkle_build": [_vp, _vp, _vp, _u32, _u32],
     "r0h_merkle_top": [_vp, _vp, _u32, _u32, _vp],
     "r0h_merkle_open_top": [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp],
+    "r0h_merkle_climb": [_vp, _vp, _vp, _u32, _u32, _u32, _vp],
+    "r0h_verify_seals_on": [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
+    "r0h_receipt_verify_elf_on": [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _c.POINTER(_c.c_int), _c.POINTER(_sz), _c.POINTER(_c.c_int)],
+    "r0h_receipt_verify_image_on": [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _c.POINTER(_c.c_int), _c.POINTER(_sz), _c.POINTER(_c.c_int)],
+    "r0h_recursor_set_verify_on_device": [_vp, _c.c_int],
     "r0h_batch_evaluate_any": [_vp, _vp, _u32, _vp, _vp, _u32, _vp],
     "r0h_mix_poly_coeffs": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32],
     "r0h_eltwise_add_elem": [_vp, _vp, _vp, _vp, _u32],
@@ -600,6 +605,29 @@ def verify_seal(blob, seal, poseidon2_consts=None, code_root=None, hashfn="posei
             raise R0HipError("verify_seal: a code root is 8 words")
     _check(lib().r0h_verify_seal_bound(pb, b.size, prc, pdg, ps, s_.size, proot, ctypes.byref(verdict), ctypes.byref(po2), None))
     return verdict.value, lib().r0h_verify_reason(verdict.value).decode(), po2.value
+
+
+def verify_seals(blob, seals, code_roots=None, hal=None):
+    """n seals of one circuit verified with their Merkle openings collected and hashed in one batch (r0h_verify_seals_on): on the
+    device of `hal` -- one upload, one launch, suite and Poseidon2 table the context's; every comparison and verdict stays the host's --
+    or, hal=None, on the host (Poseidon2; the same seam without a GPU).  code_roots: one control root per seal, or None.
+    -> [(verdict, reason, po2, data_root[8])], verdict and reason r0h_verify_seal_roots's for every input."""
+    b, pb = _u32arr(blob)
+    seals = [np.ascontiguousarray(s_, dtype=np.uint32) for s_ in seals]
+    n = len(seals)
+    flat = np.concatenate(seals) if n else np.zeros(0, dtype=np.uint32)
+    sizes = np.array([s_.size for s_ in seals], dtype=np.uintp)
+    proots = None
+    if code_roots is not None:
+        roots = np.ascontiguousarray(code_roots, dtype=np.uint32).reshape(-1)
+        if roots.size != 8 * n:
+            raise R0HipError("verify_seals: one control root of 8 words per seal")
+        proots = roots.ctypes.data_as(_vp)
+    verdicts, po2 = np.full(max(n, 1), -1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint32)
+    data_roots = np.zeros((max(n, 1), 8), dtype=np.uint32)
+    _check(lib().r0h_verify_seals_on(hal.ctx if hal is not None else None, pb, b.size, flat.ctypes.data_as(_vp), sizes.ctypes.data_as(_vp), n, proots,
+                                     verdicts.ctypes.data_as(_vp), po2.ctypes.data_as(_vp), data_roots.ctypes.data_as(_vp)))
+    return [(int(verdicts[i]), lib().r0h_verify_reason(int(verdicts[i])).decode(), int(po2[i]), data_roots[i].copy()) for i in range(n)]
 
 
 def seal_code_root(blob, seal):
@@ -1230,19 +1258,26 @@ class Receipt:
             out.append(c if has.value else None)
         return out
 
-    def verify(self, blob, control_roots, image_id, elf=None):
+    def verify(self, blob, control_roots, image_id, elf=None, hal=None):
         """`receipt.verify(image_id)` (r0h_receipt_verify): control_roots = {po2: root[8]}; image_id is required, as it is in the
         reference (None is passed through and yields verdict 12 "not tied to a program", never 0).  A receipt over the trace circuit
         binds its program through the session sum: give the ELF (r0h_receipt_verify_elf: its image id is derived, image_id is then
         ignored); with an image id alone the verdict is at best 15 "the program image was not given".  Returns (verdict, reason,
-        segment, seal verdict)."""
+        segment, seal verdict).  hal (with the ELF): the seals' Merkle openings are hashed on that context's device as one batch
+        (r0h_receipt_verify_elf_on); the verdicts are the same."""
         b, pb = _u32arr(blob)
         table = np.zeros(9 * max(len(control_roots), 1), dtype=np.uint32)
         for k, (po2, root) in enumerate(sorted(control_roots.items())):
             table[9 * k] = po2
             table[9 * k + 1:9 * k + 9] = root
         verdict, seg, sv = _c.c_int(-1), _sz(0), _c.c_int(0)
-        if elf is not None:
+        if hal is not None and elf is None:
+            raise R0HipError("Receipt.verify: hal= goes with the ELF form (or with verify_image)")
+        if elf is not None and hal is not None:
+            elf = bytes(elf)
+            _check(lib().r0h_receipt_verify_elf_on(hal.ctx, self.handle, pb, b.size, table.ctypes.data_as(_vp), len(control_roots), elf, len(elf),
+                                                   ctypes.byref(verdict), ctypes.byref(seg), ctypes.byref(sv)))
+        elif elf is not None:
             elf = bytes(elf)
             _check(lib().r0h_receipt_verify_elf(self.handle, pb, b.size, table.ctypes.data_as(_vp), len(control_roots), elf, len(elf),
                                                 ctypes.byref(verdict), ctypes.byref(seg), ctypes.byref(sv)))
@@ -1251,9 +1286,10 @@ class Receipt:
                                             ctypes.byref(verdict), ctypes.byref(seg), ctypes.byref(sv)))
         return verdict.value, lib().r0h_receipt_verify_reason(verdict.value).decode(), seg.value, sv.value
 
-    def verify_image(self, blob, control_roots, image_blob, image_id, image_control_root=None):
+    def verify_image(self, blob, control_roots, image_blob, image_id, image_control_root=None, hal=None):
         """`receipt.verify(image_id)` for a trace-circuit session WITHOUT the ELF (r0h_receipt_verify_image): the receipt's image proof
-        stands for the program image.  -> (verdict, reason, segment at fault, seal verdict)"""
+        stands for the program image.  -> (verdict, reason, segment at fault, seal verdict).  hal: the segment seals and the image
+        seal are verified as one batch with that context's device hashing their openings (r0h_receipt_verify_image_on)."""
         b, pb = _u32arr(blob)
         ib, pib = _u32arr(image_blob)
         table = np.zeros(max(1, len(control_roots)) * 9, dtype=np.uint32)
@@ -1264,8 +1300,12 @@ class Receipt:
         if image_control_root is not None:
             root, proot = _u32arr(image_control_root)
         verdict, seg, sv = _c.c_int(-1), _sz(0), _c.c_int(0)
-        _check(lib().r0h_receipt_verify_image(self.handle, pb, b.size, table.ctypes.data_as(_vp), len(control_roots), pib, ib.size, proot,
-                                              None if image_id is None else bytes(image_id), ctypes.byref(verdict), ctypes.byref(seg), ctypes.byref(sv)))
+        if hal is not None:
+            _check(lib().r0h_receipt_verify_image_on(hal.ctx, self.handle, pb, b.size, table.ctypes.data_as(_vp), len(control_roots), pib, ib.size, proot,
+                                                     None if image_id is None else bytes(image_id), ctypes.byref(verdict), ctypes.byref(seg), ctypes.byref(sv)))
+        else:
+            _check(lib().r0h_receipt_verify_image(self.handle, pb, b.size, table.ctypes.data_as(_vp), len(control_roots), pib, ib.size, proot,
+                                                  None if image_id is None else bytes(image_id), ctypes.byref(verdict), ctypes.byref(seg), ctypes.byref(sv)))
         return verdict.value, lib().r0h_receipt_verify_reason(verdict.value).decode(), seg.value, sv.value
 
     @property
@@ -1450,6 +1490,19 @@ class Hal:
         a, pa = _u32arr(idx)
         first = _u32(0)
         _check(lib().r0h_merkle_open_top(self.ctx, out.handle, matrix.handle, top.handle, levels, pa, a.size, rows, cols, ctypes.byref(first)))
+
+    def merkle_climb(self, openings, idx, rows, cols):
+        """The way back (r0h_merkle_climb): the packed openings in the Buf `openings` (merkle_open_top's layout) hashed from the row
+        upwards under the context's suite -> [n_q][8] words, entry q the digest at node (idx[q] + rows) >> path_digests.  The device
+        computes digests only; whether they are a tree's nodes is the caller's to say."""
+        a, pa = _u32arr(idx)
+        reached = np.zeros((a.size, 8), dtype=np.uint32)
+        _check(lib().r0h_merkle_climb(self.ctx, openings.handle, pa, a.size, rows, cols, reached.ctypes.data_as(_vp)))
+        return reached
+
+    def verify_seals(self, blob, seals, code_roots=None):
+        """verify_seals(...) with this context's device hashing the openings (and this context's suite and Poseidon2 table)"""
+        return verify_seals(blob, seals, code_roots, hal=self)
 
     def batch_evaluate_any(self, coeffs, po2, which, xs, out):
         w, pw = _u32arr(which)

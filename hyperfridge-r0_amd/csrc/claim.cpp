@@ -357,10 +357,24 @@ const char* r0h_receipt_verify_reason(int verdict) {
   return verdict >= 0 && verdict <= R0H_RECEIPT_V_IMAGE_PROOF ? names[verdict] : "unknown";
 }
 
+// What stands between the walk of a receipt and the verification of segment g's seal: R0H_RECEIPT_V_OK with the control root the seal
+// is verified against, or the verdict the walk ends with at this segment (one definition for the walk and for the batch the _on forms
+// verify ahead of it).  The seal names its trace size in its public part (globals, then po2): that size's control root is picked.
+static int segment_seal_root(const r0h_circuit& circ, const r0h_receipt::Segment& g, const uint32_t* control_roots, size_t n_roots, const uint32_t** root_out) {
+  *root_out = nullptr;
+  if (g.hashfn != "poseidon2") return R0H_RECEIPT_V_HASHFN;  // the only suite this prover and this verifier implement
+  if (g.seal.size() < (size_t)circ.n_global + 1 || g.seal[circ.n_global] >= P) return R0H_RECEIPT_V_SEAL;
+  const uint32_t po2 = dec(g.seal[circ.n_global]);
+  for (size_t k = 0; k < n_roots; k++)
+    if (control_roots[9 * k] == po2) *root_out = control_roots + 9 * k + 1;
+  return *root_out ? R0H_RECEIPT_V_OK : R0H_RECEIPT_V_NO_CONTROL_ROOT;
+}
+
 // risc0-zkvm receipt/composite.rs `verify_integrity_with_context` + receipt/mod.rs `Receipt::verify(image_id)`
 static const char* receipt_verify_impl(const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots,
                                        const uint8_t* image_id, const std::vector<std::pair<uint32_t, uint32_t>>* image, int* verdict_out, size_t* segment_out,
-                                       int* seal_verdict_out, const uint32_t* image_public = nullptr /* the verified image proof's 28 public inputs */) {
+                                       int* seal_verdict_out, const uint32_t* image_public = nullptr /* the verified image proof's 28 public inputs */,
+                                       std::vector<SealCheck>* verified = nullptr /* the _on forms: segment i's seal as receipt_seal_batch verified it */) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(rc && blob && verdict_out && (control_roots || !n_roots), "r0h_receipt_verify: NULL argument");
   if (segment_out) *segment_out = 0;
@@ -383,20 +397,21 @@ static const char* receipt_verify_impl(const r0h_receipt* rc, const uint32_t* bl
   std::vector<uint32_t> records(trace_circuit ? n * R0H_SESSION_RECORD_WORDS : 0);
   for (size_t i = 0; i < n; i++) {
     const r0h_receipt::Segment& g = rc->segments[i];
-    if (g.hashfn != "poseidon2") return done(R0H_RECEIPT_V_HASHFN, i);  // the only suite this prover and this verifier implement
-    // the seal names its trace size in its public part (globals, then po2): pick that size's control root, then verify bound to it
-    if (g.seal.size() < (size_t)circ.n_global + 1 || g.seal[circ.n_global] >= P) {
-      if (seal_verdict_out) *seal_verdict_out = R0H_VERIFY_TRUNCATED;
-      return done(R0H_RECEIPT_V_SEAL, i);
-    }
-    const uint32_t po2 = dec(g.seal[circ.n_global]);
+    // the seal is verified bound to the control root of the trace size it names
     const uint32_t* root = nullptr;
-    for (size_t k = 0; k < n_roots; k++)
-      if (control_roots[9 * k] == po2) root = control_roots + 9 * k + 1;
-    if (!root) return done(R0H_RECEIPT_V_NO_CONTROL_ROOT, i);
+    const int reach = segment_seal_root(circ, g, control_roots, n_roots, &root);
+    if (reach == R0H_RECEIPT_V_SEAL && seal_verdict_out) *seal_verdict_out = R0H_VERIFY_TRUNCATED;
+    if (reach != R0H_RECEIPT_V_OK) return done(reach, i);
     int sv = -1;
     uint32_t data_root[8];
-    R0H_TRY(r0h_verify_seal_roots(blob, blob_words, g.seal.data(), g.seal.size(), root, &sv, nullptr, data_root));
+    if (verified) {  // verified with the batch, against this very root
+      SealCheck& sc = (*verified)[i];
+      if (sc.err) { const char* err = sc.err; sc.err = nullptr; return err; }
+      sv = sc.verdict;
+      memcpy(data_root, sc.data_root, 32);
+    } else {
+      R0H_TRY(r0h_verify_seal_roots(blob, blob_words, g.seal.data(), g.seal.size(), root, &sv, nullptr, data_root));
+    }
     if (sv != R0H_VERIFY_OK) {
       if (seal_verdict_out) *seal_verdict_out = sv;
       return done(R0H_RECEIPT_V_SEAL, i);
@@ -464,6 +479,61 @@ static const char* receipt_verify_impl(const r0h_receipt* rc, const uint32_t* bl
   R0H_GUARD_END
 }
 
+// The _on forms: every segment seal receipt_verify_impl can come to verify -- the suite named, the seal long enough to name its trace
+// size, a control root known for it: the walk stops before any other -- and `extra` (the image seal; may be nullptr) verified as one
+// batch on `ctx`.  checks[i] is segment i's (a segment the walk cannot reach keeps verdict -1 and is never looked at), checks[n] the
+// extra one.  Anything the walk itself refuses first (no receipt, a malformed blob) leaves the batch empty and the refusal to the walk.
+static const char* receipt_seal_batch(r0h_ctx* ctx, const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots,
+                                      const SealCheck* extra, std::vector<SealCheck>& checks) {
+  R0H_TRY(require_poseidon2(ctx, "r0h_receipt_verify_on"));
+  std::vector<SealCheck> batch;
+  std::vector<size_t> slot;
+  r0h_circuit circ;
+  const bool walkable = rc && blob && (control_roots || !n_roots) && rc->kind == R0H_RECEIPT_COMPOSITE && !rc->segments.empty();
+  if (walkable) {
+    const char* err = parse_blob(&circ, blob, blob_words);
+    const bool parsed = !err;
+    if (err) r0h_free_error(err);  // (the walk parses it again and returns this)
+    checks.assign(rc->segments.size() + 1, SealCheck{nullptr, 0, nullptr, 0, nullptr});
+    for (size_t i = 0; parsed && circ.n_global >= 8 && i < rc->segments.size(); i++) {
+      const r0h_receipt::Segment& g = rc->segments[i];
+      const uint32_t* root = nullptr;
+      if (segment_seal_root(circ, g, control_roots, n_roots, &root) != R0H_RECEIPT_V_OK) continue;
+      batch.push_back(SealCheck{blob, blob_words, g.seal.data(), g.seal.size(), root});
+      slot.push_back(i);
+    }
+  } else {
+    checks.assign(1, SealCheck{nullptr, 0, nullptr, 0, nullptr});
+  }
+  if (extra) {
+    batch.push_back(*extra);
+    slot.push_back(checks.size() - 1);
+  }
+  R0H_TRY(verify_seals_batch(ctx, HASH_POSEIDON2, batch.data(), batch.size()));
+  for (size_t k = 0; k < batch.size(); k++) checks[slot[k]] = batch[k];
+  return nullptr;
+}
+static void free_check_errors(std::vector<SealCheck>& checks) {
+  for (SealCheck& sc : checks)
+    if (sc.err) { r0h_free_error(sc.err); sc.err = nullptr; }
+}
+
+const char* r0h_receipt_verify_elf_on(r0h_ctx* ctx, const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots,
+                                      const uint8_t* elf, size_t elf_len, int* verdict_out, size_t* segment_out, int* seal_verdict_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && elf, "r0h_receipt_verify_elf_on: NULL argument");
+  std::vector<std::pair<uint32_t, uint32_t>> image;
+  uint32_t entry = 0;
+  uint8_t image_id[32];
+  R0H_TRY(elf_image(elf, elf_len, image, &entry, image_id));
+  std::vector<SealCheck> checks;
+  R0H_TRY(receipt_seal_batch(ctx, rc, blob, blob_words, control_roots, n_roots, nullptr, checks));
+  const char* err = receipt_verify_impl(rc, blob, blob_words, control_roots, n_roots, image_id, &image, verdict_out, segment_out, seal_verdict_out, nullptr, &checks);
+  free_check_errors(checks);
+  return err;
+  R0H_GUARD_END
+}
+
 const char* r0h_receipt_verify(const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots,
                                const uint8_t* image_id, int* verdict_out, size_t* segment_out, int* seal_verdict_out) {
   return receipt_verify_impl(rc, blob, blob_words, control_roots, n_roots, image_id, nullptr, verdict_out, segment_out, seal_verdict_out);
@@ -473,9 +543,11 @@ const char* r0h_receipt_verify(const r0h_receipt* rc, const uint32_t* blob, size
 // Checked: the image seal verifies against the image circuit bound to its control root (derived from the blob when not given), its
 // digest is the root in the first claim's pre-state -- whose digest must be image_id --, its challenge is this session's; then
 // everything r0h_receipt_verify_elf checks, with the image proof's total as the image's side of the balance.
-const char* r0h_receipt_verify_image(const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots,
-                                     const uint32_t* image_blob, size_t image_blob_words, const uint32_t* image_control_root, const uint8_t* image_id, int* verdict_out,
-                                     size_t* segment_out, int* seal_verdict_out) {
+// One body for r0h_receipt_verify_image (on == nullptr: the image seal verified by the immediate verifier, then the walk) and
+// r0h_receipt_verify_image_on (the image seal rides in the batch of the segment seals on `on`).
+static const char* receipt_verify_image_impl(r0h_ctx* on, const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots,
+                                             const uint32_t* image_blob, size_t image_blob_words, const uint32_t* image_control_root, const uint8_t* image_id,
+                                             int* verdict_out, size_t* segment_out, int* seal_verdict_out) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(rc && blob && image_blob && verdict_out, "r0h_receipt_verify_image: NULL argument");
   if (segment_out) *segment_out = 0;
@@ -486,22 +558,58 @@ const char* r0h_receipt_verify_image(const r0h_receipt* rc, const uint32_t* blob
   if (rc->image_seal.size() <= R0H_IMAGE_GLOBALS) { *verdict_out = R0H_RECEIPT_V_IMAGE_PROOF; return nullptr; }
   int sv = -1;
   uint32_t po2 = 0, root[8];
-  if (!image_control_root) {  // a verifier with the blob derives the root of the size the seal names -- once the seal as such holds
-    R0H_TRY(r0h_verify_seal(image_blob, image_blob_words, nullptr, nullptr, rc->image_seal.data(), rc->image_seal.size(), &sv, &po2));
-    if (sv == R0H_VERIFY_OK) {
-      R0H_TRY(r0h_control_root_host(image_blob, image_blob_words, nullptr, nullptr, po2, root));
-      image_control_root = root;
+  std::vector<SealCheck> checks;  // the batch form's
+  if (on) {
+    // bound to the caller's control root if there is one; without one the root the seal commits to is held to the one derived from
+    // the blob once the seal as such holds -- what the two verifications below come to
+    const SealCheck image_check{image_blob, image_blob_words, rc->image_seal.data(), rc->image_seal.size(), image_control_root};
+    R0H_TRY(receipt_seal_batch(on, rc, blob, blob_words, control_roots, n_roots, &image_check, checks));
+    SealCheck& im = checks.back();
+    const char* err = im.err;
+    im.err = nullptr;
+    sv = im.verdict;
+    if (!err && sv == R0H_VERIFY_OK && !image_control_root) {
+      err = r0h_control_root_host(image_blob, image_blob_words, nullptr, nullptr, im.po2, root);
+      if (!err && memcmp(root, im.code_root, 32) != 0) sv = R0H_VERIFY_CODE_ROOT;
     }
+    if (err) { free_check_errors(checks); return err; }
+  } else {
+    if (!image_control_root) {  // a verifier with the blob derives the root of the size the seal names -- once the seal as such holds
+      R0H_TRY(r0h_verify_seal(image_blob, image_blob_words, nullptr, nullptr, rc->image_seal.data(), rc->image_seal.size(), &sv, &po2));
+      if (sv == R0H_VERIFY_OK) {
+        R0H_TRY(r0h_control_root_host(image_blob, image_blob_words, nullptr, nullptr, po2, root));
+        image_control_root = root;
+      }
+    }
+    if (image_control_root)
+      R0H_TRY(r0h_verify_seal_bound(image_blob, image_blob_words, nullptr, nullptr, rc->image_seal.data(), rc->image_seal.size(), image_control_root, &sv, &po2, nullptr));
   }
-  if (image_control_root)
-    R0H_TRY(r0h_verify_seal_bound(image_blob, image_blob_words, nullptr, nullptr, rc->image_seal.data(), rc->image_seal.size(), image_control_root, &sv, &po2, nullptr));
   if (sv != R0H_VERIFY_OK) {
+    free_check_errors(checks);
     if (seal_verdict_out) *seal_verdict_out = sv;
     *verdict_out = R0H_RECEIPT_V_IMAGE_PROOF;
     return nullptr;
   }
-  return receipt_verify_impl(rc, blob, blob_words, control_roots, n_roots, image_id, nullptr, verdict_out, segment_out, seal_verdict_out, rc->image_seal.data());
+  const char* err = receipt_verify_impl(rc, blob, blob_words, control_roots, n_roots, image_id, nullptr, verdict_out, segment_out, seal_verdict_out, rc->image_seal.data(),
+                                        on ? &checks : nullptr);
+  free_check_errors(checks);
+  return err;
   R0H_GUARD_END
+}
+
+const char* r0h_receipt_verify_image(const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots,
+                                     const uint32_t* image_blob, size_t image_blob_words, const uint32_t* image_control_root, const uint8_t* image_id, int* verdict_out,
+                                     size_t* segment_out, int* seal_verdict_out) {
+  return receipt_verify_image_impl(nullptr, rc, blob, blob_words, control_roots, n_roots, image_blob, image_blob_words, image_control_root, image_id, verdict_out, segment_out,
+                                   seal_verdict_out);
+}
+
+const char* r0h_receipt_verify_image_on(r0h_ctx* ctx, const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots,
+                                        const uint32_t* image_blob, size_t image_blob_words, const uint32_t* image_control_root, const uint8_t* image_id,
+                                        int* verdict_out, size_t* segment_out, int* seal_verdict_out) {
+  R0H_REQUIRE(ctx, "r0h_receipt_verify_image_on: NULL argument");
+  return receipt_verify_image_impl(ctx, rc, blob, blob_words, control_roots, n_roots, image_blob, image_blob_words, image_control_root, image_id, verdict_out, segment_out,
+                                   seal_verdict_out);
 }
 
 const char* r0h_receipt_verify_elf(const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots, size_t n_roots, const uint8_t* elf,

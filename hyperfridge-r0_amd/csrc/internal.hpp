@@ -313,6 +313,27 @@ const char* merkle_top_copy(r0h_ctx* ctx, const r0h_buf* nodes, uint32_t rows, u
 const char* merkle_open_top(r0h_ctx* ctx, uint32_t* out, const uint32_t* matrix, const uint32_t* top, uint32_t levels, const uint32_t* d_idx, uint32_t n_q, uint32_t rows,
                             uint32_t cols, uint32_t* report);
 const char* merkle_open_top_verdict(const char* caller, const uint32_t report[2], const uint32_t* idx_host);
+// merkle_climb.hip: packed openings (`cols` values, then `path` sibling digests) hashed from the row up to the node `path` levels above
+// it, under the context's suite.  A job names its opening by word offset into one buffer; reached_host[j][8] is the digest job j reaches.
+// merkle_climb: the openings are on the device already; merkle_climb_spans: they lie in host memory and go up back to back through the
+// staging helpers (offsets count from the first span's first word).  One launch on the context's stream; both block until the digests
+// are back.  upload_bytes_out (optional): what went to the device, openings and job table.
+struct ClimbJob { uint32_t offset, cols, path, row; };
+struct ClimbSpan { const uint32_t* w; size_t n; };
+const char* merkle_climb(r0h_ctx* ctx, const uint32_t* d_words, size_t n_words, const ClimbJob* jobs, size_t n_jobs, uint32_t* reached_host);
+const char* merkle_climb_spans(r0h_ctx* ctx, const ClimbSpan* spans, size_t n_spans, const ClimbJob* jobs, size_t n_jobs, uint32_t* reached_host, size_t* upload_bytes_out);
+// verify.cpp: a batch of seals verified with their Merkle openings collected and hashed together -- on `ctx` (one upload, one launch of
+// merkle_climb_kernel, suite and Poseidon2 table the context's) or, ctx == nullptr, on the host under `host_hashfn` with the compiled-in
+// table.  Every comparison and every verdict is the host's; verdict and reason are the immediate verifier's for every input.  Per seal:
+// `err` (a malformed blob, a non-canonical expected root: what the single-seal entry points return as their error; owned by the caller)
+// or verdict, po2, and the CODE / DATA roots the transcript recomputes.
+struct SealCheck {
+  const uint32_t* blob; size_t blob_words; const uint32_t* seal; size_t seal_words; const uint32_t* expected_code_root;  // in
+  const char* err = nullptr;
+  int verdict = -1;
+  uint32_t po2 = 0, code_root[8] = {0}, data_root[8] = {0};
+};
+const char* verify_seals_batch(r0h_ctx* ctx, int host_hashfn, SealCheck* seals, size_t n, size_t* upload_bytes_out = nullptr);
 // receipts, sessions, image proofs and recursion nodes name Poseidon2 only: their entry points refuse a context on another suite
 const char* require_poseidon2(const r0h_ctx* ctx, const char* caller);
 }  // namespace r0h

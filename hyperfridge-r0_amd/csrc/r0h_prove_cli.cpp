@@ -2,7 +2,7 @@
 // witness on the device, prove K segments, print throughput and a digest of the seal.
 // It stands where hyperfridge's `host prove-camt53` stands relative to risc0 (host/src/main.rs:420-423 obtains a prover and
 // calls prove once); everything risc0-specific above the segment prover (executor, receipts) is out of scope.
-//   usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--hashfn poseidon2|sha-256]
+//   usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--verify-device 1] [--hashfn poseidon2|sha-256]
 //                    [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]
 // --hashfn sha-256 proves (and with --verify 1 checks) the segments under the SHA-256 hash suite; receipts name Poseidon2 only, so it is
 // refused together with any of the receipt options and with --elf.
@@ -83,7 +83,7 @@ static void die(const char* what, const char* err) {
 
 int main(int argc, char** argv) {
   if (argc < 2 || !strcmp(argv[1], "--help") || !strcmp(argv[1], "-h")) {
-    printf("usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--hashfn poseidon2|sha-256] [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]\n"
+    printf("usage: r0h_prove <circuit.r0c> [--code-object file.hsaco] [--po2 N] [--segments K] [--seed S] [--device D] [--contexts C] [--seal-out file] [--verify 1] [--verify-device 1] [--hashfn poseidon2|sha-256] [--receipt-out file.json | --receipt-dir dir] [--journal text] [--receipts R]\n"
            "       r0h_prove <trace.r0c> --elf guest.elf --input words.bin [--code-object file.hsaco] [--po2 N] [--device D] --receipt-out file.json\n"
            "       ... --elf guest.elf --compress --recursion-circuit recursion.r0c [--recursion-code-object file.hsaco] [--recursion-po2 N] [--compress-lanes 1..4] --root-out root.bin: "
            "the receipt's segments lifted and joined into one root (wire form) for r0h_verify --root\n"
@@ -118,7 +118,7 @@ int main(int argc, char** argv) {
   std::string receipt_prefix;               // --receipt-prefix P: the reference's file name, P-Receipt-<image id>-latest.json (host/src/main.rs:312-316)
   std::string image_circuit_path, image_co_path, check_co_path, term_names_path, fraction_names_path;
   unsigned check_witness = 0, check_balance = 0, check_session = 0;
-  unsigned po2 = 16, segments = 1, device = 0, contexts = 1, verify = 0, receipts = 1;
+  unsigned po2 = 16, segments = 1, device = 0, contexts = 1, verify = 0, receipts = 1, verify_device = 0;
   unsigned long long seed = 1;
   double session_device_limit_gb = 0;  // --session-device-limit-gb: r0h_ctx_set_session_device_limit of every session context
   unsigned session_keep_tree_tops = 0;  // --session-keep-tree-tops: r0h_ctx_set_session_tree_tops of every session context
@@ -131,6 +131,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--contexts")) contexts = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--seal-out")) seal_out = argv[i + 1];
     else if (!strcmp(argv[i], "--verify")) verify = (unsigned)atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--verify-device")) verify_device = (unsigned)atoi(argv[i + 1]);  // the after-proof verification hashes its Merkle openings on the proving context
     else if (!strcmp(argv[i], "--hashfn")) hashfn = argv[i + 1];
     else if (!strcmp(argv[i], "--check-witness")) check_witness = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--check-code-object")) check_co_path = argv[i + 1];
@@ -351,13 +352,18 @@ int main(int argc, char** argv) {
     // every receipt verified the way the reference's verifier would (verifier/src/main.rs:124-126), with the ELF: host threads
     std::atomic<unsigned> next_check{0}, refused{0};
     const auto v0 = std::chrono::steady_clock::now();
-    auto check_worker = [&] {
+    // (--verify-device 1: thread k hashes the seals' Merkle openings on worker k's context, one batch per receipt; every verdict stays the host's)
+    auto check_worker = [&](unsigned k) {
+      r0h_ctx* on = verify_device ? workers[k].ctx : nullptr;
       for (unsigned u; (u = next_check.fetch_add(1)) < receipts;) {
         int verdict = -1;
-        const char* e = r0h_receipt_verify_elf(made[u], blob.data(), blob.size(), root_table.data(), root_table.size() / 9, elf.data(), elf.size(), &verdict, nullptr, nullptr);
+        const char* e = on ? r0h_receipt_verify_elf_on(on, made[u], blob.data(), blob.size(), root_table.data(), root_table.size() / 9, elf.data(), elf.size(), &verdict, nullptr, nullptr)
+                           : r0h_receipt_verify_elf(made[u], blob.data(), blob.size(), root_table.data(), root_table.size() / 9, elf.data(), elf.size(), &verdict, nullptr, nullptr);
         if (e) { r0h_free_error(e); verdict = -1; }
         if (verdict == R0H_RECEIPT_V_OK && !image_blob.empty()) {  // ... and the way the reference's verifier does: the image id's 32 bytes alone
-          e = r0h_receipt_verify_image(made[u], blob.data(), blob.size(), root_table.data(), root_table.size() / 9, image_blob.data(), image_blob.size(), nullptr, image_id, &verdict,
+          e = on ? r0h_receipt_verify_image_on(on, made[u], blob.data(), blob.size(), root_table.data(), root_table.size() / 9, image_blob.data(), image_blob.size(), nullptr, image_id,
+                                               &verdict, nullptr, nullptr)
+                 : r0h_receipt_verify_image(made[u], blob.data(), blob.size(), root_table.data(), root_table.size() / 9, image_blob.data(), image_blob.size(), nullptr, image_id, &verdict,
                                        nullptr, nullptr);
           if (e) { r0h_free_error(e); verdict = -1; }
         }
@@ -366,8 +372,8 @@ int main(int argc, char** argv) {
     };
     {
       std::vector<std::thread> threads;
-      for (unsigned k = 1; k < std::min(receipts, 8u); k++) threads.emplace_back(check_worker);
-      check_worker();
+      for (unsigned k = 1; k < std::min(receipts, verify_device ? contexts : 8u); k++) threads.emplace_back(check_worker, k);
+      check_worker(0);
       for (auto& t : threads) t.join();
     }
     const double verify_secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - v0).count();
@@ -537,7 +543,8 @@ int main(int argc, char** argv) {
     for (const Lane& ln : lanes) {
       if (!ln.proved) continue;
       int verdict = -1;
-      CHECK(r0h_verify_seal_hashfn(blob.data(), blob.size(), hashfn.c_str(), ln.seal.data(), ln.words, nullptr, &verdict, nullptr, nullptr));
+      if (verify_device) CHECK(r0h_verify_seals_on(ln.ctx, blob.data(), blob.size(), ln.seal.data(), &ln.words, 1, nullptr, &verdict, nullptr, nullptr));
+      else CHECK(r0h_verify_seal_hashfn(blob.data(), blob.size(), hashfn.c_str(), ln.seal.data(), ln.words, nullptr, &verdict, nullptr, nullptr));
       if (verdict != R0H_VERIFY_OK) { fprintf(stderr, "r0h_prove: the verifier rejects the seal: %s\n", r0h_verify_reason(verdict)); return 3; }
     }
     fprintf(stderr, "r0h_prove: seals verified\n");

@@ -43,6 +43,7 @@ struct r0h_recursor {
   uint32_t root[8] = {0};                  // control root of the recursion circuit at po2
   std::vector<uint32_t> recursion_blob, segment_blob;
   std::vector<uint32_t> segment_roots;     // n records of 9 words [po2, root[8]]: control roots of the segment circuit
+  bool verify_on_device = false;           // r0h_recursor_set_verify_on_device: consumed seals are verified as a batch on the lane's context
 };
 
 namespace {
@@ -87,10 +88,26 @@ struct Check {  // a seal this step consumes, verified on a host thread while th
   void run() { err = r0h_verify_seal_roots(blob, blob_words, seal, seal_words, root, &verdict, nullptr, data_root); }
 };
 
+// the checks as one batch of the collecting verifier on `ctx`: the openings of all of them hashed by one launch, every comparison and
+// verdict the host's (verify.cpp verify_seals_batch).  Blocks; leaves in every check what run() leaves.
+const char* run_checks_on(r0h_ctx* ctx, std::vector<Check>& checks) {
+  std::vector<SealCheck> batch;
+  for (const Check& c : checks) batch.push_back(SealCheck{c.blob, c.blob_words, c.seal, c.seal_words, c.root});
+  R0H_TRY(verify_seals_batch(ctx, HASH_POSEIDON2, batch.data(), batch.size()));
+  for (size_t i = 0; i < checks.size(); i++) {
+    checks[i].err = batch[i].err;
+    checks[i].verdict = batch[i].verdict;
+    memcpy(checks[i].data_root, batch[i].data_root, 32);
+  }
+  return nullptr;
+}
+
 const char* prove_checked(r0h_recursor* rc, r0h_ctx* ctx, std::vector<Check>& checks, const uint32_t publics[16], const std::vector<uint32_t>& states,
                           std::vector<uint32_t>& seal) {
   std::vector<std::thread> threads;
-  for (Check& c : checks) threads.emplace_back([&c] { c.run(); });
+  // on the device: the batch goes first, so that its one short launch does not wait behind the node's proof on the lane's stream
+  if (rc->verify_on_device) R0H_TRY(run_checks_on(ctx, checks));
+  else for (Check& c : checks) threads.emplace_back([&c] { c.run(); });
   const char* err = prove_node(rc, ctx, publics, states, seal);
   for (std::thread& t : threads) t.join();
   for (Check& c : checks) {
@@ -245,6 +262,12 @@ const char* r0h_recursor_free(r0h_recursor* rc) {
   return nullptr;
 }
 
+const char* r0h_recursor_set_verify_on_device(r0h_recursor* rc, int on) {
+  R0H_REQUIRE(rc, "r0h_recursor_set_verify_on_device: NULL argument");
+  rc->verify_on_device = on != 0;
+  return nullptr;
+}
+
 const char* r0h_recursor_control_root(const r0h_recursor* rc, uint32_t root_out[8]) {
   R0H_REQUIRE(rc && root_out, "r0h_recursor_control_root: NULL argument");
   memcpy(root_out, rc->root, 32);
@@ -304,7 +327,8 @@ const char* r0h_compress(r0h_recursor* rc, const r0h_receipt* receipt, uint32_t 
     }
     std::atomic<size_t> next(0);
     std::vector<std::thread> threads;
-    for (size_t t = 0; t < std::min<size_t>(n, 3 * (size_t)lanes); t++)
+    if (rc->verify_on_device) R0H_TRY(run_checks_on(rc->ctx, checks));  // all leaves in one batch
+    else for (size_t t = 0; t < std::min<size_t>(n, 3 * (size_t)lanes); t++)
       threads.emplace_back([&] { for (size_t i = next++; i < n; i = next++) checks[i].run(); });
     for (std::thread& t : threads) t.join();
     const char* err = nullptr;

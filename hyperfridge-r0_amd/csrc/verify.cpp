@@ -3,6 +3,9 @@
 // fold of the 50 queries.  Replaces risc0-zkp 3.0.4 verify/{mod.rs, merkle.rs, fri.rs, read_iop.rs} as reached from
 // `receipt.verify(image_id)` (host/src/main.rs:622-624, verifier/src/main.rs:124-126) -- SURVEY.md 8(f) rank 1.
 // Written against the seal layout the sequencer emits; the tests cross-check its verdicts with the CPU restatement's verifier.
+// One seam lets a device help the PROVING side's own checks (verify_seals_batch / r0h_verify_seals_on): a second instantiation of the
+// walk records the Merkle openings instead of hashing them, the batch is hashed by merkle_climb.hip (or here, without a context), and
+// every comparison and verdict stays on the host.  The entry points of a verifier proper do not come near it.
 #include "../../include/r0hip_circuit.h"
 #include "seal_layout.hpp"
 
@@ -68,6 +71,21 @@ class SealReader {
   size_t n_, pos_ = 0;
 };
 
+// An opening whose hashing is put off (the collecting verifier): where its packed words lie in the seal, its shape, the reject code of
+// its tree and the digest its path must reach.  A seal's walk leaves them in seal order, query by query, with each query's own verdict.
+struct Deferred {
+  const uint32_t* values;  // `cols` values, then `path` sibling digests
+  uint32_t cols, path, row;
+  int reject;
+  uint32_t want[8];
+};
+struct Collected {
+  std::vector<Deferred> jobs;
+  uint32_t first_job[R0H_QUERIES + 1] = {0};  // query q recorded jobs [first_job[q], first_job[q + 1])
+  int walk[R0H_QUERIES] = {0};                // what the walk of query q ended with, its openings taken as good
+  bool trailing = false;
+};
+
 // The verifier's view of one committed matrix: the elided top layer (read from the seal) folded down to the root.
 class TreeVerifier {
  public:
@@ -96,6 +114,26 @@ class TreeVerifier {
       memcpy(cur, parent, 32);
     }
     if (memcmp(&top_[node * 8], cur, 32) != 0) throw Reject{reject_};
+    return values;
+  }
+
+  // The collecting form: every host check of open() in its order -- the row bound, canonical values, every sibling present and
+  // (Poseidon2) canonical -- and no hashing.  The opening is recorded with this tree's reject code and the node of top_ its path must
+  // reach; whoever hashes the batch makes the comparison open() ends with.
+  const uint32_t* open_later(Cursor& io, const HashSuite& k, size_t row, std::vector<Deferred>& later) const {
+    if (row >= shape_.rows) throw Reject{reject_};
+    const uint32_t* values = io.take(shape_.cols);
+    for (size_t i = 0; i < shape_.cols; i++)
+      if (values[i] >= P) throw Reject{reject_};
+    size_t node = row + shape_.rows;
+    for (; node >= 2 * shape_.top_size; node >>= 1) {
+      const uint32_t* sibling = io.take(8);
+      for (int i = 0; i < 8 && k.digests_are_elems(); i++)
+        if (sibling[i] >= P) throw Reject{R0H_VERIFY_BAD_ELEM};
+    }
+    Deferred d{values, (uint32_t)shape_.cols, (uint32_t)shape_.path_digests(), (uint32_t)row, reject_, {0}};
+    memcpy(d.want, &top_[node * 8], 32);
+    later.push_back(d);
     return values;
   }
 
@@ -139,8 +177,13 @@ Fp4 constraint_at_z(const r0h_circuit& c, const Fp4& poly_mix, const std::vector
   return mx[c.ret].tot;
 }
 
+// COLLECT = false is the immediate verifier: every opening hashed where it is read, the queries on a few host threads, `collected`
+// unused.  COLLECT = true walks the same seal with open_later in place of open, the queries one after the other on the calling thread
+// (what is left of a query is a few hundred field operations), and returns with the openings in `collected` instead of a verdict on
+// them; a Reject thrown before the queries is final in either form (no opening precedes it).
+template <bool COLLECT>
 void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size_t seal_words, uint32_t* po2_out, const uint32_t* expected_code_root,
-            uint32_t* code_root_out, uint32_t* data_root_out = nullptr) {
+            uint32_t* code_root_out, uint32_t* data_root_out = nullptr, Collected* collected = nullptr) {
   SealReader io(k, seal, seal_words);
   const uint32_t* global = io.take_elems((size_t)c.n_global + 1);
   const uint32_t po2 = dec(global[c.n_global]);
@@ -261,12 +304,16 @@ void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size
   for (int g = 0; g < 4; g++) words_per_query += group[g]->opening_words();
   for (const Round& rd : rounds) words_per_query += rd.tree->opening_words();
   const Cursor base = io.cursor();
+  auto open = [&](const TreeVerifier& t, Cursor& cur, size_t row) {
+    if constexpr (COLLECT) return t.open_later(cur, k, row, collected->jobs);
+    else return t.open(cur, k, row);
+  };
   auto one_query = [&](uint32_t q) {
     Cursor cur{base.w, base.n, base.pos + (size_t)q * words_per_query < base.n ? base.pos + (size_t)q * words_per_query : base.n};
     std::vector<Fp4> combo_tot(n_combos + 1, fp4_zero());
     size_t pos = pos_of[q];
     const uint32_t* row[4];
-    for (int g = 0; g < 4; g++) row[g] = group[g]->open(cur, k, pos);
+    for (int g = 0; g < 4; g++) row[g] = open(*group[g], cur, pos);
     const Fp4 x = lift(fpow(w_domain, pos));
     for (uint32_t r = 0; r < n_regs; r++) {
       Fp4& t = combo_tot[c.regs[r].combo];
@@ -285,7 +332,7 @@ void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size
     size_t rows_above = domain;
     for (const Round& rd : rounds) {
       const size_t quot = pos / rd.rows, grp = pos % rd.rows;
-      const uint32_t* col = rd.tree->open(cur, k, grp);
+      const uint32_t* col = open(*rd.tree, cur, grp);
       Fp4 v[R0H_FRI_FOLD];
       for (uint32_t i = 0; i < R0H_FRI_FOLD; i++)
         for (int e = 0; e < 4; e++) v[i].e[e] = col[e * R0H_FRI_FOLD + i];
@@ -307,6 +354,17 @@ void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size
     }
     if (!(horner(final_poly.data(), degree, lift(fpow(w_final, pos))) == goal)) throw Reject{R0H_VERIFY_FRI_FINAL};
   };
+  if constexpr (COLLECT) {  // seal order: query by query, a query's openings in the order the walk reads them
+    for (uint32_t q = 0; q < R0H_QUERIES; q++) {
+      collected->first_job[q] = (uint32_t)collected->jobs.size();
+      try { one_query(q); collected->walk[q] = R0H_VERIFY_OK; }
+      catch (const Reject& r) { collected->walk[q] = r.code; }
+    }
+    collected->first_job[R0H_QUERIES] = (uint32_t)collected->jobs.size();
+    io.skip_to(base.pos + (size_t)R0H_QUERIES * words_per_query);
+    collected->trailing = !io.exhausted();
+    return;
+  }
   int verdict_of[R0H_QUERIES];
   std::atomic<uint32_t> next{0};
   auto worker = [&]() {
@@ -330,7 +388,100 @@ void verify(const r0h_circuit& c, const HashSuite& k, const uint32_t* seal, size
   if (!io.exhausted()) throw Reject{R0H_VERIFY_TRAILING};
 }
 
+// the verdict of a collected seal once its openings are hashed (reached[j][8] for job j): the reject code of the first job in seal
+// order that does not reach its node, a query's own verdict where all its jobs do -- every recorded job precedes the point where its
+// query's walk stopped, and the immediate verifier reports the first failing query -- then the trailing-words check
+int settle(const Collected& col, const uint32_t* reached) {
+  for (uint32_t q = 0; q < R0H_QUERIES; q++) {
+    for (uint32_t j = col.first_job[q]; j < col.first_job[q + 1]; j++)
+      if (memcmp(col.jobs[j].want, reached + 8 * (size_t)j, 32) != 0) return col.jobs[j].reject;
+    if (col.walk[q] != R0H_VERIFY_OK) return col.walk[q];
+  }
+  return col.trailing ? R0H_VERIFY_TRAILING : R0H_VERIFY_OK;
+}
+
 }  // namespace
+
+const char* verify_seals_batch(r0h_ctx* ctx, int host_hashfn, SealCheck* seals, size_t n, size_t* upload_bytes_out) {
+  const int hashfn = ctx ? ctx->hashfn : host_hashfn;
+  const std::unique_ptr<HashSuite> suite = make_suite(hashfn, ctx ? &ctx->p2_host : &p2_default());
+  if (upload_bytes_out) *upload_bytes_out = 0;
+  std::vector<Collected> walks(n);
+  std::vector<char> open_verdict(n, 0);  // the seal's verdict waits for its openings
+  // the walks, one after the other on the calling thread (what is left of a seal is about 1.5 ms: profiles/r16/verify_on_device.md)
+  auto walk = [&](size_t s) {
+    SealCheck& sc = seals[s];
+    sc.err = nullptr; sc.verdict = -1; sc.po2 = 0;
+    memset(sc.code_root, 0, 32);
+    memset(sc.data_root, 0, 32);
+    if (!sc.blob || (!sc.seal && sc.seal_words)) { sc.err = make_error("r0h_verify_seal: NULL argument"); return; }
+    for (int i = 0; i < 8 && sc.expected_code_root && hashfn == HASH_POSEIDON2; i++)
+      if (sc.expected_code_root[i] >= P) { sc.err = make_error("r0h_verify_seal: expected code root word %d not canonical", i); return; }
+    try {
+      r0h_circuit c;
+      if ((sc.err = parse_blob(&c, sc.blob, sc.blob_words))) return;
+      verify<true>(c, *suite, sc.seal, sc.seal_words, &sc.po2, sc.expected_code_root, sc.code_root, sc.data_root, &walks[s]);
+      open_verdict[s] = 1;
+    } catch (const Reject& r) {
+      sc.verdict = r.code;
+    } catch (const std::exception& ex) {
+      sc.err = make_error("exception: %s", ex.what());
+    } catch (...) {
+      sc.err = make_error("unknown exception");
+    }
+  };
+  for (size_t s = 0; s < n; s++) walk(s);
+  // an error of the batch as a whole takes the per-seal errors with it: the caller gets one string to free
+  auto failed = [&](const char* err) {
+    for (size_t s = 0; s < n; s++)
+      if (seals[s].err) { r0h_free_error(seals[s].err); seals[s].err = nullptr; }
+    return err;
+  };
+  size_t n_jobs = 0;
+  for (size_t s = 0; s < n; s++)
+    if (open_verdict[s]) n_jobs += walks[s].jobs.size();
+  std::vector<uint32_t> reached(8 * n_jobs);
+  if (ctx) {
+    // a seal's openings lie back to back behind its final polynomial: one span per seal, from its first recorded opening to the end
+    // of its last, goes up as it is
+    std::vector<ClimbSpan> spans;
+    std::vector<ClimbJob> jobs;
+    jobs.reserve(n_jobs);
+    size_t at = 0;
+    for (size_t s = 0; s < n; s++) {
+      const std::vector<Deferred>& dj = walks[s].jobs;
+      if (!open_verdict[s] || dj.empty()) continue;
+      const uint32_t* lo = dj.front().values;
+      const uint32_t* hi = dj.back().values + dj.back().cols + 8 * (size_t)dj.back().path;
+      for (const Deferred& d : dj) jobs.push_back(ClimbJob{(uint32_t)(at + (size_t)(d.values - lo)), d.cols, d.path, d.row});
+      spans.push_back(ClimbSpan{lo, (size_t)(hi - lo)});
+      at += (size_t)(hi - lo);
+      if (at >= ((size_t)1 << 32)) return failed(make_error("r0h_verify_seals_on: %zu words of openings in one batch", at));
+    }
+    if (const char* err = merkle_climb_spans(ctx, spans.data(), spans.size(), jobs.data(), jobs.size(), reached.data(), upload_bytes_out)) return failed(err);
+  } else {
+    size_t j = 0;
+    for (size_t s = 0; s < n; s++)
+      for (const Deferred& d : walks[s].jobs) {
+        if (!open_verdict[s]) break;
+        uint32_t* cur = &reached[8 * j++];
+        uint32_t parent[8];
+        suite->hash_elems(d.values, d.cols, cur);
+        for (uint32_t l = 0; l < d.path; l++) {
+          const uint32_t* sibling = d.values + d.cols + 8 * (size_t)l;
+          if ((d.row >> l) & 1) suite->hash_pair(sibling, cur, parent); else suite->hash_pair(cur, sibling, parent);
+          memcpy(cur, parent, 32);
+        }
+      }
+  }
+  size_t j = 0;
+  for (size_t s = 0; s < n; s++) {
+    if (!open_verdict[s]) continue;
+    seals[s].verdict = settle(walks[s], reached.data() + 8 * j);
+    j += walks[s].jobs.size();
+  }
+  return nullptr;
+}
 }  // namespace r0h
 
 namespace r0h {
@@ -401,7 +552,7 @@ static const char* verify_entry(int hashfn, const uint32_t* blob, size_t blob_wo
   if (po2_out) *po2_out = 0;
   if (code_root_out) memset(code_root_out, 0, 32);
   try {
-    verify(c, *make_suite(hashfn, own ? own.get() : &p2_default()), seal, seal_words, po2_out, expected_code_root, code_root_out, data_root_out);
+    verify<false>(c, *make_suite(hashfn, own ? own.get() : &p2_default()), seal, seal_words, po2_out, expected_code_root, code_root_out, data_root_out);
     *verdict_out = R0H_VERIFY_OK;
   } catch (const Reject& r) {
     *verdict_out = r.code;
@@ -436,6 +587,34 @@ const char* r0h_verify_seal_roots(const uint32_t* blob, size_t blob_words, const
   R0H_REQUIRE(data_root_out, "r0h_verify_seal_roots: NULL argument");
   memset(data_root_out, 0, 32);
   return verify_entry(HASH_POSEIDON2, blob, blob_words, nullptr, nullptr, seal, seal_words, expected_code_root, verdict_out, po2_out, nullptr, data_root_out);
+}
+
+// n seals of one circuit (back to back in `seals`), their Merkle openings hashed in one batch: on `ctx` (one upload, one launch; suite and Poseidon2 table the
+// context's) or, ctx == NULL, on the host (Poseidon2, the compiled-in table).  Verdicts are r0h_verify_seal_roots's.
+const char* r0h_verify_seals_on(r0h_ctx* ctx, const uint32_t* blob, size_t blob_words, const uint32_t* seals, const size_t* seal_words, size_t n,
+                                const uint32_t* expected_code_roots, int* verdicts_out, uint32_t* po2_out, uint32_t* data_roots_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(blob && ((seals && seal_words && verdicts_out) || !n), "r0h_verify_seals_on: NULL argument");
+  std::vector<SealCheck> checks(n);
+  size_t at = 0;
+  for (size_t s = 0; s < n; s++) {
+    checks[s] = SealCheck{blob, blob_words, seals + at, seal_words[s], expected_code_roots ? expected_code_roots + 8 * s : nullptr};
+    at += seal_words[s];
+    verdicts_out[s] = -1;
+  }
+  const char* err = verify_seals_batch(ctx, HASH_POSEIDON2, checks.data(), n);
+  for (SealCheck& sc : checks) {  // one circuit, one suite: a per-seal error is the call's
+    if (sc.err && !err) err = sc.err;
+    else if (sc.err) r0h_free_error(sc.err);
+  }
+  if (err) return err;
+  for (size_t s = 0; s < n; s++) {
+    verdicts_out[s] = checks[s].verdict;
+    if (po2_out) po2_out[s] = checks[s].po2;
+    if (data_roots_out) memcpy(data_roots_out + 8 * s, checks[s].data_root, 32);
+  }
+  return nullptr;
+  R0H_GUARD_END
 }
 
 // ---- the control root of a circuit's own CODE columns, on the host.  A verifier is handed control roots (risc0's has a table of

@@ -137,6 +137,12 @@ class Recursor:
         self.control_root = np.zeros(8, dtype=np.uint32)
         _check(lib().r0h_recursor_control_root(self.handle, self.control_root.ctypes.data_as(_vp)))
 
+    def set_verify_on_device(self, on=True):
+        """lift / join / compress verify the seals they consume as one batch with the lane's device hashing their Merkle openings
+        (r0h_recursor_set_verify_on_device), instead of on host threads beside the proof.  Off by default; refusals, messages and
+        nodes are the same either way."""
+        _check(lib().r0h_recursor_set_verify_on_device(self.handle, 1 if on else 0))
+
     def lift(self, segment_seal, claim):
         """risc0 `lift`: one recursion-circuit proof standing for one segment seal and its claim."""
         a, pa = _u32arr(segment_seal)

@@ -109,6 +109,15 @@ const char* r0h_merkle_build(r0h_ctx* ctx, r0h_buf* nodes, const r0h_buf* matrix
 const char* r0h_merkle_top(r0h_ctx* ctx, const r0h_buf* nodes, uint32_t rows, uint32_t levels, r0h_buf* top_out);
 const char* r0h_merkle_open_top(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* matrix, const r0h_buf* top, uint32_t levels,
                                 const uint32_t* idx_host, uint32_t n_q, uint32_t rows, uint32_t cols, uint32_t* first_mismatch_out);
+/* The way back: n_q packed openings in `openings` (device; what r0h_merkle_open_top and the sequencer pack: `cols` values, then the
+ * path_digests sibling digests l = 0 .. path_digests - 1) hashed from the row upwards under the context's hash suite -- the row sponge
+ * of r0h_hash_rows over the values, then per sibling H(cur || sib) when bit l of idx_host[q] is 0 and H(sib || cur) when it is 1.
+ * reached_host[q][8] is the digest at node (idx_host[q] + rows) >> path_digests of the tree the opening belongs to, i.e. in the
+ * layer a seal carries; path_digests = log2(rows) - top_layer as above, and path_digests == 0 is legal (the leaf digest is what is
+ * reached).  idx_host[q] < rows and cols >= 1 are checked here.  The device computes digests and compares nothing: whether they are the committed
+ * nodes is the caller's to say.  One launch on the context's stream; blocks until the digests are back. */
+const char* r0h_merkle_climb(r0h_ctx* ctx, const r0h_buf* openings, const uint32_t* idx_host, uint32_t n_q, uint32_t rows,
+                             uint32_t cols, uint32_t* reached_host);
 /* The SHA-256 suite (recalled from risc0-zkp core/hash/sha and risc0-sys sha256.h; unpinned: the reference vendors neither).
  * A digest is 8 words, word j = bswap32 of SHA-256 state word j, so its bytes in memory are the standard big-endian digest; message
  * word i of a compression = bswap32 of input word i.  Pair: one compression of the IV over the 16 words a || b, no padding, no
@@ -409,6 +418,19 @@ const char* r0h_verify_seal_hashfn(const uint32_t* blob, size_t blob_words, cons
  * circuit is derived from these roots: csrc/claim.cpp) */
 const char* r0h_verify_seal_roots(const uint32_t* blob, size_t blob_words, const uint32_t* seal, size_t seal_words,
                                   const uint32_t* expected_code_root, int* verdict_out, uint32_t* po2_out, uint32_t* data_root_out);
+/* n seals of one circuit, verified with the device hashing their Merkle openings.  `seals` holds the n seals back to back,
+ * seal_words[s] words each; expected_code_roots (optional) holds one control root of 8 words per seal (the seals of a batch may
+ * differ in po2); verdicts_out[n], po2_out[n] (optional) and data_roots_out[n][8] (optional) are what r0h_verify_seal_roots gives
+ * for each seal, verdict and reason equal for every input.  The verifier walks every seal on the host as ever -- transcript,
+ * constraint identity, DEEP, FRI folds, final polynomial, and of every opening the row bound and the canonical-word checks -- but puts
+ * the hashing of the openings off: the openings of all n seals go to the device in one upload and are hashed by one launch of
+ * r0h_merkle_climb's kernel on the context's stream, and the host compares each digest that comes back with the node of the top
+ * layer it read from the seal.  The verdict is the reject code of the first opening in seal order that fails, else the walk's own.
+ * The device decides nothing.  Suite and Poseidon2 table are the context's, so a SHA-256 context verifies SHA-256 seals.
+ * ctx == NULL hashes the collected openings on the host (Poseidon2, the compiled-in table): the same seam without a device. */
+const char* r0h_verify_seals_on(r0h_ctx* ctx, const uint32_t* blob, size_t blob_words, const uint32_t* seals, const size_t* seal_words,
+                                size_t n, const uint32_t* expected_code_roots, int* verdicts_out, uint32_t* po2_out,
+                                uint32_t* data_roots_out);
 /* The control root of a circuit's own CODE columns at trace size 2^po2, computed on the HOST from the blob alone (circuits with a
  * column program: the CODE columns r0h_witgen generates) -- the same 8 words as r0h_code_root / r0h_code_commit_root on the device.
  * A verifier that has the circuit need not be told its control roots (risc0's verifier has them compiled in).  Seconds at po2 = 20. */
@@ -541,6 +563,15 @@ const char* r0h_receipt_verify_image(const r0h_receipt* rc, const uint32_t* blob
                                      const uint8_t* image_id, int* verdict_out, size_t* segment_out, int* seal_verdict_out);
 const char* r0h_receipt_set_image_proof(r0h_receipt* rc, const uint32_t* seal, size_t seal_words);
 const char* r0h_receipt_image_proof(const r0h_receipt* rc, const uint32_t** seal_out, size_t* seal_words_out); /* NULL / 0 when there is none */
+/* r0h_receipt_verify_elf / _image with the seals' Merkle openings hashed on `ctx` (a Poseidon2 context; its table is the one the
+ * seals are held to): the segment seals that the walk can reach, and the image seal when there is one, are verified as one batch of
+ * r0h_verify_seals_on before the receipt is walked.  Same arguments otherwise, same verdict, segment and seal verdict for every input. */
+const char* r0h_receipt_verify_elf_on(r0h_ctx* ctx, const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots,
+                                      size_t n_roots, const uint8_t* elf, size_t elf_len, int* verdict_out, size_t* segment_out,
+                                      int* seal_verdict_out);
+const char* r0h_receipt_verify_image_on(r0h_ctx* ctx, const r0h_receipt* rc, const uint32_t* blob, size_t blob_words, const uint32_t* control_roots,
+                                        size_t n_roots, const uint32_t* image_blob, size_t image_blob_words, const uint32_t* image_control_root,
+                                        const uint8_t* image_id, int* verdict_out, size_t* segment_out, int* seal_verdict_out);
 const char* r0h_receipt_verify_reason(int verdict); /* static string, do not free */
 /* The image id as text, the reference's way (host/src/main.rs:445-449, verifier/src/main.rs:131-143, host/out/IMAGE_ID.hex): eight
  * u32 words printed `{:08x}`, each stored little-endian in the 32-byte digest (`Digest::from([u32; 8])`) -- NOT the digest's bytes
@@ -931,6 +962,10 @@ const char* r0h_recursor_new(r0h_ctx* ctx, const uint32_t* recursion_blob, size_
                              uint32_t po2, const uint32_t* segment_blob, size_t segment_words, const uint32_t* segment_control_roots,
                              size_t n_roots, r0h_recursor** out);
 const char* r0h_recursor_free(r0h_recursor* rc);
+/* on != 0: r0h_lift, r0h_join and r0h_compress verify the seals they consume through r0h_verify_seals_on's batch form on the lane's
+ * context, enqueued before the node's proof (r0h_compress: all leaves in one batch), instead of on host threads beside it.  Off by
+ * default; refusals and their messages are the same either way, and so is every node. */
+const char* r0h_recursor_set_verify_on_device(r0h_recursor* rc, int on);
 const char* r0h_recursor_control_root(const r0h_recursor* rc, uint32_t root_out[8]); /* of the recursion circuit at its po2 */
 const char* r0h_lift(r0h_recursor* rc, const uint32_t* seal, size_t seal_words, const r0h_receipt_claim* claim, r0h_node** out);
 const char* r0h_join(r0h_recursor* rc, const r0h_node* a, const r0h_node* b, r0h_node** out);
