@@ -101,6 +101,10 @@ _SIGNATURES = {
     "r0h_session_balance_report": [_vp, _vp, _sz, _c.POINTER(_sz)],
     "r0h_session_balance_message": [_vp, _c.POINTER(_vp)],
     "r0h_session_balance_stats": [_vp, _vp],
+    "r0h_session_balance_export": [_vp, _vp, _sz, _c.POINTER(_sz)],
+    "r0h_session_balance_merge": [_vp, _vp, _sz],
+    "r0h_session_balance_add_session": [_vp, _vp],
+    "r0h_session_journal": [_vp, _pp, _c.POINTER(_sz)],
     "r0h_ctx_set_check_session": [_vp, _c.c_int],
     "r0h_circuit_free": [_vp],
     "r0h_witgen": [_vp, _vp, _u32, _u64, _vp, _vp, _vp],
@@ -458,6 +462,16 @@ class SessionImbalance(ctypes.Structure):
         return (self.source, self.first_row, self.fraction, self.net, self.members, tuple(self.values[:self.n_values]))
 
 
+class SessionClass(ctypes.Structure):
+    """r0h_session_class: a class a handle holds, as it travels between handles -- its fingerprint `key`, the canonical residue `net`
+    of its numerators' sum (0: it balances), its `members` (saturating), its lowest member (source, first_row, fraction) and
+    values[:n_values], its per-identity sums; 64 bytes"""
+    _fields_ = [("key", _u64), ("net", _u32), ("members", _u32), ("source", _u32), ("first_row", _u32), ("fraction", _u32), ("n_values", _u32), ("values", _u32 * 8)]
+
+
+SESSION_CLASS_DTYPE = np.dtype([("key", "<u8"), ("net", "<u4"), ("members", "<u4"), ("source", "<u4"), ("first_row", "<u4"), ("fraction", "<u4"), ("n_values", "<u4"), ("values", "<u4", (8,))])
+assert SESSION_CLASS_DTYPE.itemsize == ctypes.sizeof(SessionClass) == 64
+
 SESSION_SOURCE_IMAGE, SESSION_SOURCE_JOURNAL = 0xFFFFFFFE, 0xFFFFFFFF
 
 
@@ -536,6 +550,34 @@ class SessionBalance:
         out = (_u64 * 4)()
         _check(lib().r0h_session_balance_stats(self.handle, out))
         return tuple(int(x) for x in out)
+
+    def export(self, capacity=None):
+        """every class held, balanced ones included, as a numpy structured array of 64-byte records (SESSION_CLASS_DTYPE) in ascending
+        key order; with `capacity`: (the `capacity` lowest keys, the number of classes held)"""
+        n = _sz(0)
+        cap = 0 if capacity is None else int(capacity)
+        if capacity is None:
+            _check(lib().r0h_session_balance_export(self.handle, None, 0, ctypes.byref(n)))
+            cap = n.value
+        out = np.zeros(cap, dtype=SESSION_CLASS_DTYPE)
+        _check(lib().r0h_session_balance_export(self.handle, out.ctypes.data_as(_vp) if cap else None, cap, ctypes.byref(n)))
+        out = out[:min(n.value, cap)]
+        return out if capacity is None else (out, n.value)
+
+    def merge(self, classes):
+        """the classes another handle of the same blob exported (a SESSION_CLASS_DTYPE array, or anything of 64 bytes per record)"""
+        a = np.ascontiguousarray(classes)
+        if a.dtype != SESSION_CLASS_DTYPE:
+            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+            if a.size % 64:
+                raise R0HipError("SessionBalance.merge: %d bytes are no whole number of 64-byte classes" % a.size)
+            a = a.view(SESSION_CLASS_DTYPE)
+        a = a.reshape(-1)
+        _check(lib().r0h_session_balance_merge(self.handle, a.ctypes.data_as(_vp) if a.size else None, a.size))
+
+    def add_session(self, session):
+        """the additions of a session's own pending segments (r0h_session_balance_add_session): not the verifier's side"""
+        _check(lib().r0h_session_balance_add_session(self.handle, session.handle))
 
     def free(self):
         if self.handle:
@@ -1374,6 +1416,13 @@ class Session:
         idx, rec, n = np.zeros(cap, np.uint32), np.zeros((cap, SESSION_RECORD_WORDS), np.uint32), _sz(0)
         _check(lib().r0h_session_records(self.handle, idx.ctypes.data_as(_vp), rec.ctypes.data_as(_vp), cap, ctypes.byref(n)))
         return idx[:n.value].copy(), rec[:n.value].copy()
+
+    @property
+    def journal(self):
+        """the run's journal (bytes): every rank has it"""
+        p, n = _vp(), _sz(0)
+        _check(lib().r0h_session_journal(self.handle, ctypes.byref(p), ctypes.byref(n)))
+        return ctypes.string_at(p, n.value) if n.value else b""
 
     def finish(self, all_records):
         """all_records: [n_segments, SESSION_RECORD_WORDS] in index order.  Returns (Receipt of this rank's segments, image id, cycles)."""

@@ -55,7 +55,9 @@ __device__ __forceinline__ void table_insert(Slot* __restrict__ table, uint32_t 
       }
     if (prev == 0ull || prev == key) {
       atomicAdd(&s->sum, sum);
-      atomicAdd(&s->members, members);
+      // the count saturates at 2^32 - 1 (a merged share may bring one that is there already): whoever wraps the word sets it to the
+      // maximum afterwards, and any addition after that wraps again and does the same, so the last word is the maximum iff any wrapped
+      if (atomicAdd(&s->members, members) > ~members) atomicMax(&s->members, 0xffffffffu);
       atomicMax(&s->first_inv, first_inv);
       return;
     }
@@ -296,6 +298,25 @@ __global__ __launch_bounds__(SES_THREADS) void session_rehash_kernel(SessionSlot
     table_insert(to, to_bits, ctr, s.key, s.sum % P, s.members, s.first_inv, s.values, nullptr);
   }
 }
+// every occupied slot into a dense list (r0h_session_balance_export): balance_compact_kernel with "occupied" for "does not balance"
+__global__ __launch_bounds__(SES_THREADS) void session_export_kernel(SessionSlot* __restrict__ list, unsigned long long room, const SessionSlot* __restrict__ table,
+                                                                     unsigned long long slots, unsigned long long* __restrict__ ctr) {
+  for (unsigned long long i = blockIdx.x * (unsigned long long)SES_THREADS + threadIdx.x; i < slots; i += gridDim.x * (unsigned long long)SES_THREADS) {
+    const SessionSlot s = table[i];
+    if (!s.key) continue;
+    const unsigned long long at = atomicAdd(&ctr[BAL_CURSOR], 1ull);
+    if (at < room) list[at] = s;
+  }
+}
+// classes from another handle (r0h_session_balance_merge; the host has checked every entry): one lane per entry, its own sum, members
+// and first member into its class, a class not held yet claimed with the entry's values.  No workgroup waits for another.
+__global__ __launch_bounds__(SES_THREADS) void session_merge_kernel(SessionSlot* __restrict__ table, uint32_t slot_bits, unsigned long long* __restrict__ ctr,
+                                                                    const r0h_session_class* __restrict__ classes, uint32_t n) {
+  const uint32_t i = blockIdx.x * SES_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const r0h_session_class e = classes[i];
+  table_insert(table, slot_bits, ctr, e.key, e.net, e.members, ~session_first(e.source, e.first_row, e.fraction), e.values, &ctr[SES_OCCUPIED]);
+}
 }  // namespace
 }  // namespace r0h
 
@@ -406,7 +427,8 @@ const char* session_table_ensure(r0h_session_balance* sb) {
   sb->table = t.release();
   return nullptr;
 }
-// slots >= 2 x the tuples there will be: the next power of two that holds them, every occupied slot re-inserted, the old table released
+// slots >= 2 x the classes there can be (`tuples`: sb->room and what is about to come): the next power of two that holds them, every
+// occupied slot re-inserted, the old table released
 const char* session_table_grow(r0h_session_balance* sb, uint64_t tuples) {
   SessionTable* t = sb->table;
   r0h_ctx* ctx = sb->ctx;
@@ -458,7 +480,7 @@ const char* r0h::session_table_add_list(r0h_session_balance* sb, uint32_t source
   R0H_TRY(session_table_ensure(sb));
   uint64_t tuples = 0;
   for (size_t i = 0; i < n; i++) tuples += numerators[i] != 0;
-  R0H_TRY(session_table_grow(sb, sb->tuples + tuples));
+  R0H_TRY(session_table_grow(sb, sb->room + tuples));
   const size_t k_bytes = n * 8, n_bytes = (n * 4 + 15) & ~(size_t)15, v_bytes = n * n_ids * 4;
   DevBuf list;  // keys, numerators, values
   R0H_TRY(list.alloc(ctx, k_bytes + n_bytes + v_bytes));
@@ -470,7 +492,61 @@ const char* r0h::session_table_add_list(r0h_session_balance* sb, uint32_t source
   hipLaunchKernelGGL(session_list_kernel, dim3((uint32_t)((n + SES_THREADS - 1) / SES_THREADS)), dim3(SES_THREADS), 0, ctx->stream, t->slots(), t->slot_bits, t->ctr(),
                      (const unsigned long long*)base, (const uint32_t*)(base + k_bytes), (const uint32_t*)(base + k_bytes + n_bytes), n_ids, source, (uint32_t)n);
   R0H_TRY(launch_ok("session_list_kernel"));
-  return session_table_settle(sb);  // (synchronises: the list goes back to the pool)
+  R0H_TRY(session_table_settle(sb));  // (synchronises: the list goes back to the pool)
+  sb->room += tuples;
+  return nullptr;
+}
+
+const char* r0h::session_table_export(r0h_session_balance* sb, std::vector<r0h_session_class>* out) {
+  r0h_ctx* ctx = sb->ctx;
+  out->clear();
+  if (!sb->table) return nullptr;  // nothing was added
+  SessionTable* t = sb->table;
+  const uint64_t slots = 1ull << t->slot_bits;
+  KScope ks(ctx, "session_balance", (double)slots * sizeof(SessionSlot));
+  unsigned long long occupied = 0;
+  R0H_TRY(r0h_buf_d2h(ctx, t->side.get(), SES_OCCUPIED * 8, &occupied, 8));
+  if (!occupied) return nullptr;
+  R0H_REQUIRE(occupied <= slots, "r0h_session_balance_export: %llu classes counted in %llu slots", occupied, (unsigned long long)slots);
+  DevBuf list;
+  R0H_TRY(list.alloc(ctx, occupied * sizeof(SessionSlot)));
+  R0H_TRY_HIP(hipMemsetAsync(t->ctr() + BAL_CURSOR, 0, 8, ctx->stream));
+  uint32_t grid;
+  R0H_TRY(scan_grid(ctx, slots, SES_THREADS, &grid));
+  hipLaunchKernelGGL(session_export_kernel, dim3(grid), dim3(SES_THREADS), 0, ctx->stream, (SessionSlot*)list->ptr, occupied, t->slots(), (unsigned long long)slots, t->ctr());
+  R0H_TRY(launch_ok("session_export_kernel"));
+  std::vector<SessionSlot> found(occupied);
+  R0H_TRY(r0h_buf_d2h(ctx, list.get(), 0, found.data(), occupied * sizeof(SessionSlot)));  // (synchronises: the list goes back to the pool)
+  unsigned long long copied = 0;
+  R0H_TRY(r0h_buf_d2h(ctx, t->side.get(), BAL_CURSOR * 8, &copied, 8));
+  R0H_REQUIRE(copied == occupied, "r0h_session_balance_export: %llu classes counted, %llu found", occupied, copied);
+  out->resize(occupied);
+  for (size_t k = 0; k < found.size(); k++) {
+    const SessionSlot& s = found[k];
+    const uint64_t first = ~s.first_inv;
+    r0h_session_class& e = (*out)[k];
+    e = r0h_session_class{s.key, (uint32_t)(s.sum % P), s.members, (uint32_t)(first >> 32), (uint32_t)(first >> 8) & 0xffffffu, (uint32_t)(first & 255u), (uint32_t)sb->ids.size(), {0, 0, 0, 0, 0, 0, 0, 0}};
+    memcpy(e.values, s.values, sizeof e.values);
+  }
+  return nullptr;
+}
+
+const char* r0h::session_table_merge(r0h_session_balance* sb, const r0h_session_class* classes, size_t n, uint64_t distinct) {
+  r0h_ctx* ctx = sb->ctx;
+  KScope ks(ctx, "session_balance", (double)n * sizeof(r0h_session_class));
+  R0H_TRY(session_table_ensure(sb));
+  if (!n) return nullptr;
+  R0H_TRY(session_table_grow(sb, sb->room + distinct));  // counted first: the load stays at 1/2 or below if every key is a class not held yet
+  DevBuf list;
+  R0H_TRY(list.alloc(ctx, n * sizeof(r0h_session_class)));
+  R0H_TRY(r0h_buf_h2d(ctx, list.get(), 0, classes, n * sizeof(r0h_session_class)));
+  SessionTable* t = sb->table;
+  hipLaunchKernelGGL(session_merge_kernel, dim3((uint32_t)((n + SES_THREADS - 1) / SES_THREADS)), dim3(SES_THREADS), 0, ctx->stream, t->slots(), t->slot_bits, t->ctr(),
+                     (const r0h_session_class*)list->ptr, (uint32_t)n);
+  R0H_TRY(launch_ok("session_merge_kernel"));
+  R0H_TRY(session_table_settle(sb));  // (synchronises: the list goes back to the pool)
+  sb->room += distinct;
+  return nullptr;
 }
 
 const char* r0h::session_table_report(r0h_session_balance* sb, r0h_session_imbalance* out, size_t capacity, size_t* n_out) {
@@ -527,13 +603,14 @@ extern "C" const char* r0h_session_balance_add(r0h_session_balance* sb, uint32_t
   R0H_TRY(r0h_buf_d2h(ctx, tb->side.get(), BAL_TUPLES * 8, &tuples, 8));
   R0H_REQUIRE(sb->tuples + tuples <= 0xffffffffull, "r0h_session_balance_add: more than 2^32 - 1 tuples in one handle");
   if (tuples) {
-    R0H_TRY(session_table_grow(sb, sb->tuples + tuples));
+    R0H_TRY(session_table_grow(sb, sb->room + tuples));
     hipLaunchKernelGGL(session_insert_kernel, dim3((n + SES_THREADS - 1) / SES_THREADS), dim3(SES_THREADS), 0, ctx->stream, tb->slots(), tb->slot_bits, tb->ctr(), d.words, d.cols, tb->weights(),
                        (const uint32_t*)map->ptr, n_ids, n_own, 4 * n_chain, source, po2);
     R0H_TRY(launch_ok("session_insert_kernel"));
   }
   R0H_TRY(session_table_settle(sb));  // (synchronises: the tape goes back to the pool, the caller's buffers are its own again)
   sb->tuples += tuples;
+  sb->room += tuples;
   return nullptr;
   R0H_GUARD_END
 }

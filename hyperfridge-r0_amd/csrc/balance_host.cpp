@@ -1,6 +1,7 @@
 // Host side of the balance checks (include/r0hip.h; the device's side is csrc/balance.hip): the chain links' check in plain loops
 // (r0h_logup_check_balance_host: the compiled form the device's is compared with), and the session balance's handle -- the
-// identities, a host handle's classes, the verifier's side, report and message; a device handle's table is balance.hip's, behind the
+// identities, a host handle's classes, the verifier's side, report and message, export and merge (every entry of a merged list is
+// checked here, for both kinds of handle); a device handle's table is balance.hip's, behind the
 // session_table_* functions.  The tuples come from logup_host.cpp's walk_tuples.
 #include <string.h>
 
@@ -253,6 +254,82 @@ const char* r0h_session_balance_stats(r0h_session_balance* sb, uint64_t stats_ou
   stats_out[2] = sb->grows;
   stats_out[3] = sb->classes.size();
   if (sb->ctx) R0H_TRY(session_table_stats(sb, &stats_out[1], &stats_out[3]));
+  return nullptr;
+  R0H_GUARD_END
+}
+
+const char* r0h_session_balance_export(r0h_session_balance* sb, r0h_session_class* out, size_t capacity, size_t* n_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(sb && n_out && (out || !capacity), "r0h_session_balance_export: NULL argument");
+  *n_out = 0;
+  std::vector<r0h_session_class> all;
+  if (sb->ctx) {
+    R0H_TRY(session_table_export(sb, &all));
+  } else {
+    all.reserve(sb->classes.size());
+    for (const auto& kv : sb->classes) {
+      const SessionClass& cl = kv.second;
+      r0h_session_class e = {kv.first, (uint32_t)(cl.sum % P), (uint32_t)std::min<uint64_t>(cl.members, 0xffffffffull), (uint32_t)(cl.first >> 32), (uint32_t)(cl.first >> 8) & 0xffffffu,
+                             (uint32_t)(cl.first & 255u), (uint32_t)sb->ids.size(), {0, 0, 0, 0, 0, 0, 0, 0}};
+      memcpy(e.values, cl.values, sizeof e.values);
+      all.push_back(e);
+    }
+  }
+  std::sort(all.begin(), all.end(), [](const r0h_session_class& a, const r0h_session_class& b) { return a.key < b.key; });  // (a key is held once)
+  *n_out = all.size();
+  if (!all.empty() && capacity) memcpy(out, all.data(), std::min(all.size(), capacity) * sizeof(r0h_session_class));
+  return nullptr;
+  R0H_GUARD_END
+}
+
+const char* r0h_session_balance_merge(r0h_session_balance* sb, const r0h_session_class* classes, size_t n) {
+  R0H_GUARD_BEGIN
+  static_assert(sizeof(r0h_session_class) == 64, "a class travels as one 64-byte record");
+  R0H_REQUIRE(sb && (classes || !n), "r0h_session_balance_merge: NULL argument");
+  R0H_REQUIRE(n <= SESSION_MAX_LIST, "r0h_session_balance_merge: %zu classes in one call: more than 2^24", n);
+  const size_t n_ids = sb->ids.size();
+  std::vector<r0h_session_class> list(classes, classes + n);  // what is taken in: the words behind n_values are zero whatever the caller left there
+  std::vector<uint64_t> keys(n);
+  uint64_t members = 0;
+  for (size_t i = 0; i < n; i++) {
+    r0h_session_class& e = list[i];
+    R0H_REQUIRE(e.n_values == n_ids, "r0h_session_balance_merge: entry %zu has %u values, the handle has %zu identities", i, e.n_values, n_ids);
+    R0H_REQUIRE(e.key, "r0h_session_balance_merge: entry %zu has key 0", i);
+    R0H_REQUIRE(e.net < P, "r0h_session_balance_merge: net of entry %zu is not canonical", i);
+    R0H_REQUIRE(e.fraction <= SESSION_OUTSIDE_FRACTION, "r0h_session_balance_merge: entry %zu has fraction %u: more than 255", i, e.fraction);
+    R0H_REQUIRE(e.first_row < (1u << 24), "r0h_session_balance_merge: entry %zu has first row %u: not below 2^24", i, e.first_row);
+    uint32_t h0 = 0, h1 = 0;
+    for (size_t k = 0; k < 8; k++) {
+      if (k >= n_ids) {
+        e.values[k] = 0;
+        continue;
+      }
+      R0H_REQUIRE(e.values[k] < P, "r0h_session_balance_merge: value %zu of entry %zu is not canonical", k, i);
+      h0 = add(h0, mul(sb->weights[k], enc(e.values[k])));
+      h1 = add(h1, mul(sb->weights[n_ids + k], enc(e.values[k])));
+    }
+    R0H_REQUIRE(e.key == balance_key(h0, h1), "r0h_session_balance_merge: the key of entry %zu is not the fingerprint of its values", i);
+    keys[i] = e.key;
+    members += e.members;
+  }
+  std::sort(keys.begin(), keys.end());
+  const uint64_t distinct = (uint64_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
+  if (sb->ctx) {
+    R0H_TRY(session_table_merge(sb, list.data(), n, distinct));
+  } else {
+    for (const r0h_session_class& e : list) {
+      auto it = sb->classes.find(e.key);
+      if (it == sb->classes.end()) {
+        it = sb->classes.emplace(e.key, SessionClass()).first;
+        memcpy(it->second.values, e.values, sizeof e.values);
+      }
+      SessionClass& cl = it->second;
+      cl.sum = (cl.sum + e.net) % P;
+      cl.members = std::min<uint64_t>(cl.members + e.members, 0xffffffffull);
+      cl.first = std::min(cl.first, session_first(e.source, e.first_row, e.fraction));
+    }
+  }
+  sb->tuples = std::min<uint64_t>(sb->tuples + members, 0xffffffffull);
   return nullptr;
   R0H_GUARD_END
 }

@@ -202,6 +202,7 @@ struct r0h_session_balance {
   std::vector<uint32_t> weights;      // [2][ids.size()]: balance_weight of each
   bool reads_global = false;          // some numerator or part reads an (early) public input
   uint64_t tuples = 0, grows = 0;
+  uint64_t room = 0;                  // device handle: no more classes than this are held (tuples added, entries merged): what the table is sized from
   std::unordered_map<uint64_t, r0h::SessionClass> classes;  // host handle: by balance_key
   r0h::SessionTable* table = nullptr;                       // device handle
 };
@@ -212,5 +213,8 @@ namespace r0h {
 const char* session_table_add_list(r0h_session_balance* sb, uint32_t source, const uint64_t* keys, const uint32_t* numerators, const uint32_t* values, size_t n);
 const char* session_table_report(r0h_session_balance* sb, r0h_session_imbalance* out, size_t capacity, size_t* n_out);
 const char* session_table_stats(r0h_session_balance* sb, uint64_t* slots_out, uint64_t* occupied_out);
+// every class held, in no order (the caller orders them), and a list of classes into the table (checked by the caller; `distinct` of its keys differ)
+const char* session_table_export(r0h_session_balance* sb, std::vector<r0h_session_class>* out);
+const char* session_table_merge(r0h_session_balance* sb, const r0h_session_class* classes, size_t n, uint64_t distinct);
 void session_table_free(r0h_session_balance* sb);
 }  // namespace r0h

@@ -636,16 +636,11 @@ const char* r0h_session_records(const r0h_session* s, uint32_t* indices_out, uin
 
 namespace {
 struct SessionBalanceFree { void operator()(r0h_session_balance* sb) const { r0h_session_balance_free(sb); } };
-// r0h_ctx_set_check_session: between the phases, before the challenge exists -- every segment's session tuples (their DATA witnesses
-// are still resident, lean segments included) and the verifier's side from the ELF and the run's journal must cancel class by class.
-// A session that does not balance is this call's error, by the name of its lowest class, and its proofs are aborted.
-const char* check_session(r0h_session* s) {
-  r0h_ctx* ctx = s->ctx;
-  profile_phase(ctx, "check_session");
-  r0h_session_balance* made = nullptr;
-  R0H_TRY(r0h_session_balance_new(ctx, s->c->blob.data(), s->c->blob.size(), &made));
-  std::unique_ptr<r0h_session_balance, SessionBalanceFree> sb(made);
-  bool own_proof = false;  // a proof of the caller's context is still to be finished: it closes the profile
+// The session's own share of the session balance: every pending segment's session tuples into `sb` (a device handle; `source` is the
+// segment's index), in index order -- what check_session below and r0h_session_balance_add_session both add.  *own_proof: a proof on
+// the handle's context is still to be finished.
+const char* add_pending_segments(r0h_session* s, r0h_session_balance* sb, bool* own_proof) {
+  r0h_ctx* ctx = sb->ctx;
   for (Pending& p : s->pending) {  // in index order
     // an evicted segment's witness is expanded again for its addition, into a block that goes back behind it.  The multiplicity
     // columns stay zero there: the addition walks the accumulators with a public total only, and those read no table column
@@ -656,11 +651,24 @@ const char* check_session(r0h_session* s) {
       R0H_TRY(r0h_trace_rows_expand(p.rows.get(), again.get()));
     }
     if (p.lctx != ctx) R0H_TRY(r0h_sync(p.lctx));
-    else own_proof = own_proof || !p.done;
+    else *own_proof = *own_proof || !p.done;
     const r0h_buf* code_cols = nullptr;
     R0H_TRY(r0h_code_commit_columns(p.cc, &code_cols));
-    R0H_TRY(r0h_session_balance_add(sb.get(), (uint32_t)p.index, s->c, p.po2, code_cols, p.evicted ? again.get() : p.data.get(), p.global.data()));
+    R0H_TRY(r0h_session_balance_add(sb, (uint32_t)p.index, s->c, p.po2, code_cols, p.evicted ? again.get() : p.data.get(), p.global.data()));
   }
+  return nullptr;
+}
+// r0h_ctx_set_check_session: between the phases, before the challenge exists -- every segment's session tuples (their DATA witnesses
+// are still resident, lean segments included) and the verifier's side from the ELF and the run's journal must cancel class by class.
+// A session that does not balance is this call's error, by the name of its lowest class, and its proofs are aborted.
+const char* check_session(r0h_session* s) {
+  r0h_ctx* ctx = s->ctx;
+  profile_phase(ctx, "check_session");
+  r0h_session_balance* made = nullptr;
+  R0H_TRY(r0h_session_balance_new(ctx, s->c->blob.data(), s->c->blob.size(), &made));
+  std::unique_ptr<r0h_session_balance, SessionBalanceFree> sb(made);
+  bool own_proof = false;  // a proof of the caller's context is still to be finished: it closes the profile
+  R0H_TRY(add_pending_segments(s, sb.get(), &own_proof));
   R0H_TRY(r0h_session_balance_add_verifier_side(sb.get(), s->elf.data(), s->elf.size(), s->journal.data(), s->journal.size()));
   char* text = nullptr;
   R0H_TRY(r0h_session_balance_message(sb.get(), &text));
@@ -785,6 +793,26 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
   *receipt_out = rc_guard.release();
   return nullptr;
   R0H_GUARD_END
+}
+
+// A rank's share of the gathered session balance (include/r0hip.h): the pending segments' additions and nothing else.
+const char* r0h_session_balance_add_session(r0h_session_balance* sb, r0h_session* s) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(sb && s, "r0h_session_balance_add_session: NULL argument");
+  R0H_REQUIRE(s->trace_mode, "r0h_session_balance_add_session: the session's circuit is not the trace circuit: its segments are proved at once and share no sum");
+  R0H_REQUIRE(sb->ctx, "r0h_session_balance_add_session: this handle was made without a context: a session's witnesses are on the device");
+  for (const Pending& p : s->pending)
+    R0H_REQUIRE(!p.done && (p.evicted ? (bool)p.rows : (bool)p.data), "r0h_session_balance_add_session: segment %zu is finished: a session is added between r0h_session_begin and r0h_session_finish", p.index);
+  bool own_proof = false;
+  return add_pending_segments(s, sb, &own_proof);
+  R0H_GUARD_END
+}
+
+const char* r0h_session_journal(const r0h_session* s, const uint8_t** bytes, size_t* n) {
+  R0H_REQUIRE(s && bytes && n, "r0h_session_journal: NULL argument");
+  *bytes = s->journal.data();
+  *n = s->journal.size();
+  return nullptr;
 }
 
 // both phases on one rank: the records this rank contributes are all there are

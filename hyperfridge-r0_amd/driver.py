@@ -81,6 +81,28 @@ class DistEnv:
         self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
         return t.cpu().numpy()
 
+    def all_gather_bytes(self, array):
+        """every rank's bytes on every rank, in rank order: [uint8 numpy array per rank] (the array's own bytes with one rank).  An
+        all-gather of one length per rank, then of the arrays padded to the longest, as uint8 tensors (host tensors under gloo, device
+        tensors under "nccl": RCCL)"""
+        import numpy as np
+        mine = np.frombuffer(np.ascontiguousarray(array).tobytes(), dtype=np.uint8)
+        if self.dist is None:
+            return [mine]
+        import torch
+        where = self.device if (self.device is not None and self.dist.get_backend() == "nccl") else "cpu"  # (gloo gathers host tensors only)
+        length = torch.tensor([mine.size], dtype=torch.int64, device=where)
+        lengths = [torch.zeros_like(length) for _ in range(self.world)]
+        self.dist.all_gather(lengths, length)
+        lengths = [int(x.item()) for x in lengths]
+        longest = max(max(lengths), 1)
+        padded = torch.zeros(longest, dtype=torch.uint8)
+        padded[:mine.size] = torch.from_numpy(mine.copy())
+        padded = padded.to(where)
+        parts = [torch.zeros_like(padded) for _ in range(self.world)]
+        self.dist.all_gather(parts, padded)
+        return [part.cpu().numpy()[:n] for part, n in zip(parts, lengths)]
+
     def close(self):
         if self.dist is not None and self.dist.is_initialized():
             self.dist.destroy_process_group()
@@ -111,17 +133,69 @@ def run_timed(env, step_fn, steps, warmup, device_sync=lambda: None, many_fn=Non
     return env.max(elapsed), env.sum(units)
 
 
-def prove_elf_sharded(env, hal, circuit, elf, input_words, segment_po2=20, max_cycles=0):
+def exchange_session_classes(env, balance, timings=None):
+    """The gathered session balance's collective step: every rank's classes (SessionBalance.export, 64 bytes a class) go to every rank,
+    each merges the others' in rank order and asks for the message -- merging is associative and commutative, so every rank ends with
+    the classes of one handle that had every rank's additions and with the same text (None: the session balances).  `timings`, when
+    given, receives exported_classes, exported_bytes and the milliseconds of export, exchange, merge and report."""
+    t0 = time.perf_counter()
+    mine = balance.export()
+    t1 = time.perf_counter()
+    parts = env.all_gather_bytes(mine)
+    t2 = time.perf_counter()
+    for rank, part in enumerate(parts):
+        if rank != env.rank:
+            balance.merge(part)
+    t3 = time.perf_counter()
+    text = balance.message()
+    t4 = time.perf_counter()
+    if timings is not None:
+        timings.update(exported_classes=int(len(mine)), exported_bytes=int(mine.nbytes), export_ms=1e3 * (t1 - t0), exchange_ms=1e3 * (t2 - t1), merge_ms=1e3 * (t3 - t2),
+                       report_ms=1e3 * (t4 - t3))
+    return text
+
+
+def check_sharded_session(env, hal, circuit, ses, elf, timings=None):
+    """The session balance of a session its ranks share, between its phases and before any challenge is derived: a device handle per
+    rank takes the rank's own segments (SessionBalance.add_session), rank 0 alone the verifier's side (every rank has the ELF and the
+    journal), then exchange_session_classes.  Returns the message, the same on every rank (None: the session balances)."""
+    import hyperfridge_r0_amd as r0
+    balance = r0.SessionBalance(circuit.blob, hal)
+    try:
+        t0 = time.perf_counter()
+        balance.add_session(ses)
+        if env.rank == 0:
+            balance.add_verifier_side(bytes(elf), ses.journal)
+        if timings is not None:
+            timings["add_ms"] = 1e3 * (time.perf_counter() - t0)
+        return exchange_session_classes(env, balance, timings)
+    finally:
+        balance.free()
+
+
+def prove_elf_sharded(env, hal, circuit, elf, input_words, segment_po2=20, max_cycles=0, check_session=False, timings=None):
     """`prove(env, elf)` on env.world GPUs: every rank executes the guest (deterministic, a tenth of a second per ten million cycles)
     and commits segments rank, rank + world, ... (r0h_session_begin); with the trace circuit the segments of a session share ONE
     challenge derived from all their DATA roots, so the ranks exchange their records -- 28 words per segment, one all-reduce of a
     table every rank fills its own rows of (RCCL under "nccl", gloo otherwise: the one collective of the path) -- and finish their
     proofs under it (r0h_session_finish).  The ranks' receipts travel to rank 0 as JSON over point-to-point send / recv
     (hyperfridge-r0_amd/recursion.py torch_transport) and are merged there (r0h_receipt_merge): the merged receipt is the one a single
-    GPU would have produced, seal for seal.  Returns (Receipt on rank 0 / None elsewhere, image id, cycles)."""
+    GPU would have produced, seal for seal.  Returns (Receipt on rank 0 / None elsewhere, image id, cycles).
+    check_session=True: the session balance in its gathered form (check_sharded_session) between the commitments and the records
+    exchange; a session that does not balance closes every rank's session and raises R0HipError("r0h_prove_elf: session fraction F
+    does not balance: ...") on every rank, the text r0h_ctx_set_check_session gives a single rank."""
     import numpy as np
     import hyperfridge_r0_amd as r0
     ses = hal.session_begin(circuit, elf, input_words, segment_po2=segment_po2, max_cycles=max_cycles, part=env.rank, parts=env.world)
+    if check_session:
+        try:
+            text = check_sharded_session(env, hal, circuit, ses, elf, timings)
+        except BaseException:
+            ses.close()
+            raise
+        if text is not None:
+            ses.close()
+            raise r0.R0HipError("r0h_prove_elf: " + text)
     idx, rec = ses.records()
     table = np.zeros((ses.n_segments, r0.SESSION_RECORD_WORDS), dtype=np.int64)
     if len(idx):

@@ -282,7 +282,26 @@ const char* r0h_ctx_set_check_balance(r0h_ctx* ctx, int on);
  * The weights are public and fixed: a diagnostic for honest mistakes, not a verifier -- r0h_receipt_verify_elf stays the judge.
  * The device keeps an open-addressed table of 64-byte slots that belongs to the handle, starts at 1,024 slots and is rehashed into
  * the next power of two whenever an addition would take the load above 1/2; "r0h_session_balance: table full" if a probe sequence
- * runs out all the same.  One handle is used from one thread at a time. */
+ * runs out all the same.  One handle is used from one thread at a time.
+ * EXPORT AND MERGE: a handle's classes leave it and enter another one, so that ranks which each hold a share of a session's additions
+ * reach the answer of one handle that had them all.  r0h_session_balance_export gives one 64-byte r0h_session_class per class HELD,
+ * those that already balance included (a class balanced here still adds its members and its lowest member to the merged answer, a
+ * class open here may be closed elsewhere): `key` the fingerprint, `net` the canonical residue of the numerators' sum in [0, p) (it
+ * may be 0), `members` saturating at 2^32 - 1, (source, first_row, fraction) the lowest member, values[0 .. n_values) the per-identity
+ * sums and zeros behind them.  Entries come in ascending `key` order, so two exports of the same content are the same bytes whatever
+ * the scheduling or the order of the additions; *n_out counts the classes held and `out` receives the `capacity` lowest keys; an empty
+ * handle gives 0.  Host and device handles alike.  The fingerprint of values v[0 .. n) under the handle's identities id[k] (kind << 32
+ * | index, 0 for "one") is key = (h0 << 31 | h1) + 1 with h_j = sum_k w_j(id[k]) v[k] mod p and w_j(id) = 1 + (((splitmix64(
+ * splitmix64(id) + 0xBA1A9CE (j + 1)) >> 32) (p - 1)) >> 32), splitmix64 the usual finaliser (add 0x9E3779B97F4A7C15; x ^= x >> 30,
+ * times 0xBF58476D1CE4E5B9; x ^= x >> 27, times 0x94D049BB133111EB; x ^= x >> 31), all in 64-bit words.
+ * r0h_session_balance_merge takes such a list from any handle made from the same blob and combines per class: the sums added mod p,
+ * the members added (saturating at 2^32 - 1), the lowest member by (source, row, fraction), the values from whoever holds the class
+ * first (the rule for colliding fingerprints above, unchanged).  Every one of these is associative and commutative: merging in any
+ * order, pairwise or tree-wise, gives the report, the message, the class count and the export of one handle with every addition.  The
+ * tuples counted by _stats grow by the merged members (saturating at 2^32 - 1, after which further additions are refused as above).
+ * The same key may come more than once in a list; n may be 0; n <= 2^24 a call.  Refused by entry index, before anything is taken in:
+ * n_values other than the handle's identity count, key 0, net or a value >= p, fraction > 255, first_row >= 2^24, a key that is not
+ * the fingerprint of the entry's values.  The device counts first and grows its table when the merged load would pass 1/2. */
 #define R0H_SESSION_SOURCE_IMAGE 0xfffffffeu
 #define R0H_SESSION_SOURCE_JOURNAL 0xffffffffu
 typedef struct { uint32_t source, fraction, first_row, net, members, n_values, values[8]; } r0h_session_imbalance;
@@ -303,12 +322,18 @@ const char* r0h_session_balance_add_verifier_side(r0h_session_balance* sb, const
 const char* r0h_session_balance_report(r0h_session_balance* sb, r0h_session_imbalance* out, size_t capacity, size_t* n_out);
 const char* r0h_session_balance_message(r0h_session_balance* sb, char** text_out);
 const char* r0h_session_balance_stats(r0h_session_balance* sb, uint64_t stats_out[4]);
+typedef struct { uint64_t key; uint32_t net, members, source, first_row, fraction, n_values; uint32_t values[8]; } r0h_session_class; /* 64 bytes */
+const char* r0h_session_balance_export(r0h_session_balance* sb, r0h_session_class* out, size_t capacity, size_t* n_out);
+const char* r0h_session_balance_merge(r0h_session_balance* sb, const r0h_session_class* classes, size_t n);
 /* on != 0: from now on r0h_session_finish (and so r0h_prove_elf) of a trace-circuit session on this context checks the session balance
  * of all its segments' DATA witnesses (still resident, lean segments included; an evicted segment's is expanded again from its rows) with the verifier's side from the ELF and the run's
  * journal BEFORE the session challenge is derived, and a session that does not balance returns "r0h_prove_elf: session fraction F
  * does not balance: ..." (the message above) with its proofs aborted; the phase is `check_session` in the profile.  Single-rank
  * sessions only: a rank sees its own segments alone, and r0h_session_begin with parts > 1 refuses the switch (a multi-rank driver
- * would gather the tuples through the handle above).  Off (the default): nothing is checked, seals, launches and timing are unchanged. */
+ * would gather the tuples through the handle above).  The switch stays single-rank; the gathered form is beside it: every rank adds
+ * its own share with r0h_session_balance_add_session (below, with the sessions), rank 0 the verifier's side, the ranks exchange their
+ * r0h_session_balance_export lists and r0h_session_balance_merge the others' -- every rank then holds the same classes and gives the
+ * same message (hyperfridge-r0_amd/driver.py: prove_elf_sharded(check_session=True)).  Off (the default): nothing is checked, seals, launches and timing are unchanged. */
 const char* r0h_ctx_set_check_session(r0h_ctx* ctx, int on);
 
 /* ---- the sequencer: risc0-circuit-rv32im `SegmentProver::prove` + risc0-zkp `Prover::{commit_group, finalize}` ---- */
@@ -887,6 +912,14 @@ const char* r0h_session_records(const r0h_session* s, uint32_t* indices_out, uin
 const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size_t n_records, r0h_receipt** receipt_out,
                                uint8_t image_id_out[32], uint64_t* cycles_out);
 const char* r0h_session_free(r0h_session* s);
+/* The session's own share of the session balance (above): the additions r0h_ctx_set_check_session's check makes for this rank's
+ * pending segments and nothing else -- `source` is the segment's index, a resident or lean DATA witness is used as it is, an evicted
+ * segment's is expanded again from its rows; the verifier's side is NOT added (one rank adds it: r0h_session_balance_add_verifier_side).
+ * Between r0h_session_begin and r0h_session_finish, any `parts`, a trace-circuit session and a device handle made from its circuit's
+ * blob on the session's device; anything else is an error that says so.  r0h_session_journal: the run's journal, which every rank has
+ * (the guest is executed in full on each); the bytes are the session's until it is freed. */
+const char* r0h_session_balance_add_session(r0h_session_balance* sb, r0h_session* s);
+const char* r0h_session_journal(const r0h_session* s, const uint8_t** bytes, size_t* n);
 /* composite receipts that each hold some segments of one session -> one receipt with all of them in index order.  Refused: a
  * segment index missing or present twice, journals that differ, a receipt that is not composite. */
 const char* r0h_receipt_merge(const r0h_receipt* const* parts, size_t n, r0h_receipt** out);

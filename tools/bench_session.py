@@ -61,7 +61,8 @@ def main():
                     "its phases; segments beyond it are evicted to their rows and committed again (default 0: no limit)")
     ap.add_argument("--keep-tree-tops", type=int, default=0, help="r0h_ctx_set_session_tree_tops per session context: an evicted segment also keeps the top of its DATA tree, down to this many "
                     "levels above the leaves (1..8), and is committed again without hashing (default 0: off)")
-    ap.add_argument("--check-session", type=int, default=0, help="1: r0h_ctx_set_check_session -- the session balance of all segments is checked before the challenge is derived (single rank only)")
+    ap.add_argument("--check-session", type=int, default=0, help="1: r0h_ctx_set_check_session -- the session balance of all segments is checked before the challenge is derived; "
+                    "under WORLD_SIZE > 1 in its gathered form (driver.prove_elf_sharded(check_session=True): every rank's classes exported, exchanged and merged), whose bytes and milliseconds the line reports")
     args = ap.parse_args()
     world, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     import __graft_entry__ as entry
@@ -95,8 +96,9 @@ def main():
     blob = np.fromfile(entry.circuit_blob_path("trace"), dtype=np.uint32)
     hal = r0.Hal(0 if (env is None or args.share_device) else local)
     gc = hal.load_circuit(blob, entry.code_object_path("trace"))
-    if args.check_session:
+    if args.check_session and env is None:  # (the context's switch stays single-rank: shared sessions are checked by the driver)
         hal.set_check_session(True)
+    gathered = {}
     if args.resident_limit_gb >= 0:
         hal.set_session_resident_limit(int(args.resident_limit_gb * (1 << 30)))
     device_limit = max(1, int(args.device_limit_gb * (1 << 30))) if args.device_limit_gb > 0 else 0
@@ -142,11 +144,15 @@ def main():
         elif env is None:
             receipt, image_id, cycles = hal.prove_elf(gc, elf, stream, segment_po2=args.po2)
         else:
-            receipt, image_id, cycles = driver.prove_elf_sharded(env, hal, gc, elf, stream, segment_po2=args.po2)
+            receipt, image_id, cycles = driver.prove_elf_sharded(env, hal, gc, elf, stream, segment_po2=args.po2, check_session=bool(args.check_session), timings=gathered)
             env.barrier()
         wall = time.perf_counter() - t0
         st, dev = hal.last_session_stats(), hal.last_session_device()
         tops = hal.last_session_tree_tops() if args.keep_tree_tops else {"replayed_from_top": 0, "tops_bytes": 0, "levels": 0}
+    if env is not None and args.check_session:  # every rank's exported bytes, in rank order
+        mine = np.zeros(world, dtype=np.int64)
+        mine[env.rank] = gathered["exported_bytes"]
+        gathered["exported_bytes_per_rank"] = [int(x) for x in env.sum_array(mine)]
     if env is not None and env.rank != 0:
         gc.free()
         hal.close()
@@ -175,6 +181,9 @@ def main():
             "peak_device_memory_used_GiB": round(peak_used / (1 << 30), 1) if peak_used else None, "metric": "segments/s of prove(env, elf) with the trace circuit: executor + device witgen + proof, all inside the timed region",
             "value": round(n / wall, 4), "unit": "segments/s", "n_gpus": world, "sharding": None if env is None else "segments rank, rank + %d, ... per rank (%s%s); receipts merged on rank 0" % (world, args.backend, ", all ranks on one GPU" if args.share_device else ""), "segment_po2": args.po2, "segments": len(seals), "cycles": cycles, "check_session": bool(args.check_session),
             "wall_s": round(wall, 4), "guest": what,
+            "gathered_session_check": None if not gathered else {"exported_bytes_per_rank": gathered["exported_bytes_per_rank"], "exported_classes_of_rank_0": gathered["exported_classes"],
+                                                                 "rank_0_ms": {k[:-3]: round(gathered[k], 3) for k in ("add_ms", "export_ms", "exchange_ms", "merge_ms", "report_ms")},
+                                                                 "note": "add = r0h_session_balance_add_session (+ the verifier's side on rank 0); export, all-gather, merge of the other ranks' lists, message"},
             "executor": {"host_s": round(st["executor_s"], 4), "MHz_with_trace_kept": round(cycles / st["executor_s"] / 1e6, 2), "host_ms_per_segment": round(1e3 * st["executor_s"] / max(1, st["segments"]), 3),
                          "note": "own host thread, overlaps the device work of the previous segment"},
             "device": {"witgen_ms_per_segment": round(st["witgen_ms"] / max(1, st["segments"]), 3), "prove_ms_per_segment": round(st["prove_ms"] / max(1, st["segments"]), 3),
