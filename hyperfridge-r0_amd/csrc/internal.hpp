@@ -302,13 +302,18 @@ std::unique_ptr<HashSuite> make_suite(int fn, const P2Consts* k);
 // SHA-256 suite on the host (hash_suite.cpp): digests are 8 words whose bytes in memory are the standard big-endian SHA-256 bytes
 void sha_hash_pair_host(const uint32_t* left, const uint32_t* right, uint32_t* out);
 void sha_hash_elems_host(const uint32_t* words, size_t n, uint32_t digest[8]);
-// ... and on the device (sha256.hip): what r0h_hash_rows / r0h_hash_fold run on a context whose suite is SHA-256 (arguments checked by the callers)
-const char* sha256_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix, uint32_t rows, uint32_t cols);
-const char* sha256_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size);
-// merkle_top.hip: a tree kept as its top (digests [0, 2 * rows >> levels)) and the openings made from it under the context's suite.
-// merkle_top_copy: r0h_merkle_top under the caller's name.  merkle_open_top: device pointers, stream-ordered; `report` (two device words,
-// reset here) receives the count of queries whose subtree does not hash to the top's node and the lowest such query;
+// The device side of both suites is hash_suite_device.hpp; r0h_hash_rows / r0h_hash_fold / r0h_merkle_build are in merkle.hip, with the
+// two shape checks the Merkle entry points share: "<caller>: rows n is not a power of two" and "<caller>: query q opens row r of an
+// n-row tree" for the first idx_host[q] >= rows.
+const char* require_pow2_rows(const char* caller, uint32_t rows);
+const char* require_rows_in_tree(const char* caller, const uint32_t* idx_host, uint32_t n_q, uint32_t rows);
+// merkle_top.hip: packed openings (device pointers, stream-ordered): per query the `cols` values of row d_idx[q], then the sibling
+// digests up to the layer a seal carries.  merkle_open: out of a tree held in full, all 2 * rows nodes (no hashing, no suite).
+// The rest: a tree kept as its top (digests [0, 2 * rows >> levels)) and the openings made from it under the context's suite.
+// merkle_top_copy: r0h_merkle_top under the caller's name.  merkle_open_top: `report` (two device words, reset here) receives
+// the count of queries whose subtree does not hash to the top's node and the lowest such query;
 // merkle_open_top_verdict makes the caller's error of it ("<caller>: tree top does not match the matrix under query q (row r)").
+const char* merkle_open(r0h_ctx* ctx, uint32_t* out, const uint32_t* matrix, const uint32_t* nodes, const uint32_t* d_idx, uint32_t n_q, uint32_t rows, uint32_t cols);
 const char* merkle_top_copy(r0h_ctx* ctx, const r0h_buf* nodes, uint32_t rows, uint32_t levels, r0h_buf* top_out, const char* caller);
 const char* merkle_open_top(r0h_ctx* ctx, uint32_t* out, const uint32_t* matrix, const uint32_t* top, uint32_t levels, const uint32_t* d_idx, uint32_t n_q, uint32_t rows,
                             uint32_t cols, uint32_t* report);

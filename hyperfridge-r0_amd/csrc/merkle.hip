@@ -1,51 +1,52 @@
-// Poseidon2 (BabyBear, t=24, rate 16, x^7, 4+21+4 rounds) row hashing and Merkle folding for gfx950.
-// Replaces risc0-zkp 3.0.4 hal `hash_rows` / `hash_fold` with the poseidon2 hash suite (CUDA side: risc0-sys 1.5.0
-// poseidon2 kernels) -- SURVEY.md 8(a) a6-a8.
+// Row hashing and Merkle folding for gfx950 under the context's hash suite (hash_suite_device.hpp): Poseidon2 (BabyBear, t=24, rate 16,
+// x^7, 4+21+4 rounds) or SHA-256.  Replaces risc0-zkp 3.0.4 hal `hash_rows` / `hash_fold` (CUDA side: risc0-sys 1.5.0 poseidon2 and
+// sha256 kernels) -- SURVEY.md 8(a) a6-a8.
 //
-// One lane owns one row (hash_rows) or one parent node (hash_fold): the 24-word state lives in VGPRs, the round
-// constants are wave-uniform and come in through scalar loads, and consecutive lanes read consecutive rows of each
-// column so every column access of a wave is one contiguous 256-byte run.  This kernel is VALU-integer bound
-// (about 1.36k Montgomery products per permutation), not HBM bound: see DESIGN.md for the arithmetic.
-#include "poseidon2_device.hpp"
+// One lane owns one row (hash_rows) or one parent node (hash_fold): the hash's state lives in VGPRs, the round constants are
+// wave-uniform (Poseidon2: scalar loads; SHA-256: literals), and consecutive lanes read consecutive rows of each column so every
+// column access of a wave is one contiguous 256-byte run.  Under Poseidon2 these kernels are VALU-integer bound (about 1.36k
+// Montgomery products per permutation), not HBM bound: see DESIGN.md for the arithmetic.
+#include "hash_suite_device.hpp"
 
 namespace r0h {
 
+template <class S>
 __global__ __launch_bounds__(256) void hash_rows_kernel(uint32_t* __restrict__ digests, const uint32_t* __restrict__ matrix,
-                                                         uint32_t rows, uint32_t cols, const P2Consts* __restrict__ k) {
+                                                         uint32_t rows, uint32_t cols, typename S::Consts k) {
   uint32_t row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
-  uint32_t c[P2_CELLS];
-  p2_hash_row(c, matrix + row, rows, cols, k);  // the row sponge (poseidon2_device.hpp)
+  uint32_t d[8];
+  S::row(d, matrix + row, rows, cols, k);
   uint4* dst = (uint4*)(digests + (size_t)row * 8);
-  dst[0] = make_uint4(c[0], c[1], c[2], c[3]);
-  dst[1] = make_uint4(c[4], c[5], c[6], c[7]);
+  dst[0] = make_uint4(d[0], d[1], d[2], d[3]);
+  dst[1] = make_uint4(d[4], d[5], d[6], d[7]);
 }
 
 // nodes[i] = H(nodes[2i] || nodes[2i+1]), output_size <= i < 2*output_size
-__global__ __launch_bounds__(256) void hash_fold_kernel(uint32_t* __restrict__ nodes, uint32_t output_size,
-                                                         const P2Consts* __restrict__ k) {
+template <class S>
+__global__ __launch_bounds__(256) void hash_fold_kernel(uint32_t* __restrict__ nodes, uint32_t output_size, typename S::Consts k) {
   uint32_t t = blockIdx.x * 256 + threadIdx.x;
   if (t >= output_size) return;
   uint32_t i = output_size + t;
   const uint4* src = (const uint4*)(nodes + (size_t)2 * i * 8);
-  uint32_t c[P2_CELLS];
+  uint32_t d[2][8];
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     uint4 v = src[q];
-    c[4 * q] = v.x; c[4 * q + 1] = v.y; c[4 * q + 2] = v.z; c[4 * q + 3] = v.w;
+    uint32_t* h = &d[q >> 1][4 * (q & 1)];
+    h[0] = v.x; h[1] = v.y; h[2] = v.z; h[3] = v.w;
   }
-#pragma unroll
-  for (int q = 16; q < P2_CELLS; q++) c[q] = 0;
-  p2_mix<P2_ZERO_CAP | P2_DIGEST_ONLY>(c, k);
+  S::pair(d[0], d[0], d[1], k);
   uint4* dst = (uint4*)(nodes + (size_t)i * 8);
-  dst[0] = make_uint4(c[0], c[1], c[2], c[3]);
-  dst[1] = make_uint4(c[4], c[5], c[6], c[7]);
+  dst[0] = make_uint4(d[0][0], d[0][1], d[0][2], d[0][3]);
+  dst[1] = make_uint4(d[0][4], d[0][5], d[0][6], d[0][7]);
 }
 
 // Upper Merkle levels have fewer parents than the chip has lanes: one permutation per lane then takes a full
 // single-wave latency (~26 us) per level, 17 levels per tree.  This variant spreads ONE permutation over 24 lanes of a
 // 32-lane half-wave (one state cell per lane): S-boxes run in parallel, the external layer exchanges within quads and
 // across the six quads by shuffles, the internal layer is a 5-step shuffle all-reduce.  Latency per level drops ~7x.
+// Poseidon2 only: a SHA-256 compression is a few microseconds of adds and rotates, there is nothing to gain from spreading one.
 __device__ __forceinline__ uint32_t half_shfl(uint32_t v, uint32_t src_in_half) {
   return __shfl(v, (int)((threadIdx.x & 32u) | src_in_half), 64);
 }
@@ -84,6 +85,16 @@ __global__ __launch_bounds__(256) void hash_fold_lanes_kernel(uint32_t* __restri
   if (live && l < 8u) nodes[(size_t)node * 8 + l] = c;
 }
 
+// the two shape checks every Merkle entry point makes, under the caller's name (internal.hpp)
+const char* require_pow2_rows(const char* caller, uint32_t rows) {
+  R0H_REQUIRE(rows && (rows & (rows - 1)) == 0, "%s: rows %u is not a power of two", caller, rows);
+  return nullptr;
+}
+const char* require_rows_in_tree(const char* caller, const uint32_t* idx_host, uint32_t n_q, uint32_t rows) {
+  for (uint32_t q = 0; q < n_q; q++) R0H_REQUIRE(idx_host[q] < rows, "%s: query %u opens row %u of a %u-row tree", caller, q, idx_host[q], rows);
+  return nullptr;
+}
+
 }  // namespace r0h
 
 using namespace r0h;
@@ -97,10 +108,12 @@ const char* r0h_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix,
   R0H_REQUIRE((size_t)rows * 32 <= digests->bytes, "r0h_hash_rows: %u digests exceed the output buffer", rows);
   R0H_REQUIRE(((uintptr_t)digests->ptr & 15) == 0, "r0h_hash_rows: digest buffer must be 16-byte aligned");
   if (!rows) return nullptr;
-  if (ctx->hashfn == HASH_SHA256) return sha256_hash_rows(ctx, digests, matrix, rows, cols);  // the context's suite (r0h_ctx_set_hashfn)
-  KScope ks(ctx, "hash_rows_kernel", (double)rows * cols * 4 + (double)rows * 32);
-  hipLaunchKernelGGL(hash_rows_kernel, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, u32(digests), u32(matrix), rows, cols, ctx->p2);
-  return launch_ok("hash_rows_kernel");
+  return with_suite(ctx, [&](auto suite) {
+    using S = decltype(suite);
+    KScope ks(ctx, S::rows_kernel, (double)rows * cols * 4 + (double)rows * 32);
+    hipLaunchKernelGGL(hash_rows_kernel<S>, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, u32(digests), u32(matrix), rows, cols, S::consts(ctx));
+    return launch_ok(S::rows_kernel);
+  });
   R0H_GUARD_END
 }
 
@@ -110,14 +123,16 @@ const char* r0h_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size) {
   R0H_REQUIRE((size_t)output_size * 4 * 32 <= nodes->bytes, "r0h_hash_fold: output_size %u needs %zu bytes of nodes", output_size, (size_t)output_size * 128);
   R0H_REQUIRE(((uintptr_t)nodes->ptr & 15) == 0, "r0h_hash_fold: node buffer must be 16-byte aligned");
   if (!output_size) return nullptr;
-  if (ctx->hashfn == HASH_SHA256) return sha256_hash_fold(ctx, nodes, output_size);
-  KScope ks(ctx, "hash_fold_kernel", (double)output_size * 96);
-  if (output_size <= 8192) {  // fewer parents than the chip has SIMD slots (measured up to 8 K: 1.47 vs 1.52 ms per tree) (32x the instructions per permutation, ~7x less latency): spread each permutation over 24 lanes (latency, not throughput)
-    hipLaunchKernelGGL(hash_fold_lanes_kernel, dim3((output_size * 32 + 255) / 256), dim3(256), 0, ctx->stream, u32(nodes), output_size, ctx->p2);
-    return launch_ok("hash_fold_lanes_kernel");
-  }
-  hipLaunchKernelGGL(hash_fold_kernel, dim3((output_size + 255) / 256), dim3(256), 0, ctx->stream, u32(nodes), output_size, ctx->p2);
-  return launch_ok("hash_fold_kernel");
+  return with_suite(ctx, [&](auto suite) {
+    using S = decltype(suite);
+    KScope ks(ctx, S::fold_kernel, (double)output_size * 96);
+    if (std::is_same<S, P2Device>::value && output_size <= 8192) {  // Poseidon2 with fewer parents than the chip has SIMD slots (measured up to 8 K: 1.47 vs 1.52 ms per tree) (32x the instructions per permutation, ~7x less latency): spread each permutation over 24 lanes (latency, not throughput)
+      hipLaunchKernelGGL(hash_fold_lanes_kernel, dim3((output_size * 32 + 255) / 256), dim3(256), 0, ctx->stream, u32(nodes), output_size, ctx->p2);
+      return launch_ok("hash_fold_lanes_kernel");
+    }
+    hipLaunchKernelGGL(hash_fold_kernel<S>, dim3((output_size + 255) / 256), dim3(256), 0, ctx->stream, u32(nodes), output_size, S::consts(ctx));
+    return launch_ok(S::fold_kernel);
+  });
   R0H_GUARD_END
 }
 
@@ -132,7 +147,7 @@ const char* r0h_hash_fold_io(r0h_ctx* ctx, r0h_buf* io, uint32_t input_size, uin
 const char* r0h_merkle_build(r0h_ctx* ctx, r0h_buf* nodes, const r0h_buf* matrix, uint32_t rows, uint32_t cols) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && nodes && matrix, "r0h_merkle_build: NULL argument");
-  R0H_REQUIRE(rows && (rows & (rows - 1)) == 0, "r0h_merkle_build: rows %u is not a power of two", rows);
+  R0H_TRY(require_pow2_rows("r0h_merkle_build", rows));
   R0H_REQUIRE((size_t)rows * 2 * 32 <= nodes->bytes, "r0h_merkle_build: node buffer too small for %u rows", rows);
   r0h_buf leaves = *nodes;
   leaves.ptr = (char*)nodes->ptr + (size_t)rows * 32;

@@ -12,82 +12,41 @@
 // loop of the sponge and the climb are wave-uniform, only the side a sibling goes to differs between lanes (a select, no branch).
 // A batch is at most 7 x 50 jobs per seal, each a chain of cols / 16 + path dependent permutations: a latency problem, so the
 // grid is one wave per (tree, seal) spread over as many compute units, and nothing is shared between lanes (no LDS).
-// One template, instantiated per hash suite (the leaf and pair functions of poseidon2_device.hpp / sha256_device.hpp).
+// One template, instantiated per hash suite (row and pair of hash_suite_device.hpp).
 #include <algorithm>
 #include <numeric>
 
-#include "poseidon2_device.hpp"
+#include "hash_suite_device.hpp"
 #include "seal_layout.hpp"
-#include "sha256_device.hpp"
 
 namespace r0h {
-
-struct P2Climb {
-  typedef const P2Consts* Consts;
-  static constexpr const char* kernel_name = "merkle_climb_kernel";
-  static __device__ __forceinline__ void leaf(uint32_t (&d)[8], const uint32_t* __restrict__ values, uint32_t cols, Consts k) {
-    uint32_t c[P2_CELLS];
-    p2_hash_row(c, values, 1, cols, k);
-#pragma unroll
-    for (int w = 0; w < 8; w++) d[w] = c[w];
-  }
-  // d = right_side ? H(sib || d) : H(d || sib): hash_fold_kernel's permutation
-  static __device__ __forceinline__ void pair(uint32_t (&d)[8], const uint32_t* __restrict__ sib, bool right_side, Consts k) {
-    uint32_t c[P2_CELLS];
-#pragma unroll
-    for (int w = 0; w < 8; w++) {
-      const uint32_t s = sib[w];
-      c[w] = right_side ? s : d[w];
-      c[8 + w] = right_side ? d[w] : s;
-    }
-#pragma unroll
-    for (int w = 16; w < P2_CELLS; w++) c[w] = 0;
-    p2_mix<P2_ZERO_CAP | P2_DIGEST_ONLY>(c, k);
-#pragma unroll
-    for (int w = 0; w < 8; w++) d[w] = c[w];
-  }
-};
-
-struct ShaClimb {
-  typedef int Consts;  // (none: the round constants are literals)
-  static constexpr const char* kernel_name = "sha256_merkle_climb_kernel";
-  static __device__ __forceinline__ void leaf(uint32_t (&d)[8], const uint32_t* __restrict__ values, uint32_t cols, Consts) {
-    uint32_t st[8];
-    sha_hash_row(st, values, 1, cols);
-#pragma unroll
-    for (int w = 0; w < 8; w++) d[w] = sha_bswap(st[w]);
-  }
-  // one compression of the IV over the 16 words left || right, no padding: sha256_hash_fold_kernel's
-  static __device__ __forceinline__ void pair(uint32_t (&d)[8], const uint32_t* __restrict__ sib, bool right_side, Consts) {
-    uint32_t st[8], m[16];
-    sha_init(st);
-#pragma unroll
-    for (int w = 0; w < 8; w++) {
-      const uint32_t s = sha_bswap(sib[w]), own = sha_bswap(d[w]);
-      m[w] = right_side ? s : own;
-      m[8 + w] = right_side ? own : s;
-    }
-    sha_compress(st, m);
-#pragma unroll
-    for (int w = 0; w < 8; w++) d[w] = sha_bswap(st[w]);
-  }
-};
 
 // jobs: {word offset, cols, path digests, row index} in the host's sorted order; waves: {first job, jobs (1..64)} per workgroup, all of
 // whose jobs have the cols and path of the first.  reached[j][8] for sorted job j.  Every offset + cols + 8 * path lies inside `words`
 // (the host has checked it against the buffer before the launch).
-template <class Suite>
+template <class S>
 __global__ __launch_bounds__(64) void merkle_climb_kernel(uint32_t* __restrict__ reached, const uint32_t* __restrict__ words, const uint4* __restrict__ jobs,
-                                                          const uint2* __restrict__ waves, typename Suite::Consts k) {
+                                                          const uint2* __restrict__ waves, typename S::Consts k) {
   const uint2 wave = waves[blockIdx.x];
   if (threadIdx.x >= wave.y) return;
   const uint32_t cols = __builtin_amdgcn_readfirstlane(jobs[wave.x].y), path = __builtin_amdgcn_readfirstlane(jobs[wave.x].z);
   const uint4 job = jobs[wave.x + threadIdx.x];
   const uint32_t* __restrict__ opening = words + job.x;
   uint32_t cur[8];
-  Suite::leaf(cur, opening, cols, k);
+  S::row(cur, opening, 1, cols, k);
 #pragma unroll 1
-  for (uint32_t l = 0; l < path; l++) Suite::pair(cur, opening + cols + 8 * l, (job.w >> l) & 1u, k);
+  for (uint32_t l = 0; l < path; l++) {  // cur = H(sib || cur) where the path comes up from the right, H(cur || sib) from the left
+    const uint32_t* __restrict__ sib = opening + cols + 8 * l;
+    const bool right_side = (job.w >> l) & 1u;
+    uint32_t left[8], right[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+      const uint32_t s = sib[w];
+      left[w] = right_side ? s : cur[w];
+      right[w] = right_side ? cur[w] : s;
+    }
+    S::pair(cur, left, right, k);
+  }
   uint32_t* dst = reached + (size_t)(wave.x + threadIdx.x) * 8;
 #pragma unroll
   for (int w = 0; w < 8; w++) dst[w] = cur[w];
@@ -129,16 +88,12 @@ const char* merkle_climb(r0h_ctx* ctx, const uint32_t* d_words, size_t n_words, 
   R0H_TRY(stage_h2d(ctx, d_table, table.data(), table_bytes));
   R0H_TRY(stage_h2d(ctx, d_waves, waves.data(), waves_bytes));
   const uint32_t n_waves = (uint32_t)(waves.size() / 2);
-  if (ctx->hashfn == HASH_SHA256) {
-    KScope ks(ctx, ShaClimb::kernel_name, (double)n_words * 4);
-    hipLaunchKernelGGL(merkle_climb_kernel<ShaClimb>, dim3(n_waves), dim3(64), 0, ctx->stream, d_reached, d_words, (const uint4*)d_table, (const uint2*)d_waves, 0);
-    R0H_TRY(launch_ok(ShaClimb::kernel_name));
-  } else {
-    KScope ks(ctx, P2Climb::kernel_name, (double)n_words * 4);
-    hipLaunchKernelGGL(merkle_climb_kernel<P2Climb>, dim3(n_waves), dim3(64), 0, ctx->stream, d_reached, d_words, (const uint4*)d_table, (const uint2*)d_waves,
-                       (const P2Consts*)ctx->p2);
-    R0H_TRY(launch_ok(P2Climb::kernel_name));
-  }
+  R0H_TRY(with_suite(ctx, [&](auto suite) {
+    using S = decltype(suite);
+    KScope ks(ctx, S::climb_kernel, (double)n_words * 4);
+    hipLaunchKernelGGL(merkle_climb_kernel<S>, dim3(n_waves), dim3(64), 0, ctx->stream, d_reached, d_words, (const uint4*)d_table, (const uint2*)d_waves, S::consts(ctx));
+    return launch_ok(S::climb_kernel);
+  }));
   std::vector<uint32_t> sorted(8 * n_jobs);
   R0H_TRY(r0h_buf_d2h(ctx, block.get(), table_bytes, sorted.data(), reached_bytes));
   for (size_t j = 0; j < n_jobs; j++) memcpy(reached_host + 8 * (size_t)order[j], &sorted[8 * j], 32);
@@ -173,16 +128,14 @@ extern "C" {
 const char* r0h_merkle_climb(r0h_ctx* ctx, const r0h_buf* openings, const uint32_t* idx_host, uint32_t n_q, uint32_t rows, uint32_t cols, uint32_t* reached_host) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && openings && ((idx_host && reached_host) || !n_q), "r0h_merkle_climb: NULL argument");
-  R0H_REQUIRE(rows && (rows & (rows - 1)) == 0, "r0h_merkle_climb: rows %u is not a power of two", rows);
+  R0H_TRY(require_pow2_rows("r0h_merkle_climb", rows));
   R0H_REQUIRE(cols >= 1, "r0h_merkle_climb: cols 0: an opening holds at least one value");
   const MerkleShape mp(rows, cols);
   R0H_REQUIRE((size_t)n_q * mp.opening_words() * 4 <= openings->bytes, "r0h_merkle_climb: %u openings of %zu words exceed the buffer", n_q, mp.opening_words());
   R0H_REQUIRE((size_t)n_q * mp.opening_words() < ((size_t)1 << 32), "r0h_merkle_climb: %u openings of %zu words in one call", n_q, mp.opening_words());
+  R0H_TRY(require_rows_in_tree("r0h_merkle_climb", idx_host, n_q, rows));
   std::vector<ClimbJob> jobs(n_q);
-  for (uint32_t q = 0; q < n_q; q++) {
-    R0H_REQUIRE(idx_host[q] < rows, "r0h_merkle_climb: query %u opens row %u of a %u-row tree", q, idx_host[q], rows);
-    jobs[q] = ClimbJob{(uint32_t)(q * mp.opening_words()), cols, (uint32_t)mp.path_digests(), idx_host[q]};
-  }
+  for (uint32_t q = 0; q < n_q; q++) jobs[q] = ClimbJob{(uint32_t)(q * mp.opening_words()), cols, (uint32_t)mp.path_digests(), idx_host[q]};
   return merkle_climb(ctx, u32(openings), (size_t)n_q * mp.opening_words(), jobs.data(), n_q, reached_host);
   R0H_GUARD_END
 }

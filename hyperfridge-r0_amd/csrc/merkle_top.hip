@@ -9,77 +9,56 @@
 // contiguous run of 4 * 2^levels bytes per column), the digests go to LDS word-major [8][2^levels], and `levels` rounds of pair hashing
 // follow -- before each, the sibling of the queried path at that level is written out.  The subtree's root must be the node the
 // kept top has there: that is the check that top and matrix belong together, made at every query (a mismatch is counted and the
-// lowest query number kept; the host reports it).  The levels above come from the top as merkle_open_kernel (prover.hip) takes them
-// from the full tree, and the packed opening is the same: `cols` column values, then path_digests sibling digests.
-// One template, instantiated per hash suite (the leaf and pair functions of poseidon2_device.hpp / sha256_device.hpp).
-#include "poseidon2_device.hpp"
+// lowest query number kept; the host reports it).  The levels above come from the top as merkle_open_kernel, the opening of a tree
+// held in full, takes them from its nodes (path_above, below), and the packed opening is the same: `cols` column values, then
+// path_digests sibling digests.  One template, instantiated per hash suite (row and pair of hash_suite_device.hpp).
+#include "hash_suite_device.hpp"
 #include "seal_layout.hpp"
-#include "sha256_device.hpp"
 
 namespace r0h {
 
-struct P2Merkle {
-  typedef const P2Consts* Consts;
-  static constexpr const char* kernel_name = "merkle_open_top_kernel";
-  static __device__ __forceinline__ void leaf(uint32_t (&d)[8], const uint32_t* __restrict__ src, uint32_t rows, uint32_t cols, Consts k) {
-    uint32_t c[P2_CELLS];
-    p2_hash_row(c, src, rows, cols, k);
-#pragma unroll
-    for (int w = 0; w < 8; w++) d[w] = c[w];
+// The sibling digests of `row`'s path from `first` levels above the leaves up to (excluding) level n_path, out of the node array of a
+// `rows`-leaf tree (node i at words [8i, 8i + 8), the root at 1), into path[8 * first, 8 * n_path): one word per lane and step
+__device__ __forceinline__ void path_above(uint32_t* path, const uint32_t* nodes, uint32_t row, uint32_t rows, uint32_t first, uint32_t n_path) {
+  for (uint32_t w = threadIdx.x + 8 * first; w < 8 * n_path; w += blockDim.x) {
+    const uint32_t sibling = ((row + rows) >> (w >> 3)) ^ 1u;
+    path[w] = nodes[(size_t)sibling * 8 + (w & 7)];
   }
-  // d = H(left || right), the digests of nodes 2p and 2p + 1 at lds[w * n + 2p], lds[w * n + 2p + 1]: hash_fold_kernel's permutation
-  static __device__ __forceinline__ void pair(uint32_t (&d)[8], const uint32_t* lds, uint32_t n, uint32_t p, Consts k) {
-    uint32_t c[P2_CELLS];
-#pragma unroll
-    for (int w = 0; w < 8; w++) { c[w] = lds[w * n + 2 * p]; c[8 + w] = lds[w * n + 2 * p + 1]; }
-#pragma unroll
-    for (int w = 16; w < P2_CELLS; w++) c[w] = 0;
-    p2_mix<P2_ZERO_CAP | P2_DIGEST_ONLY>(c, k);
-#pragma unroll
-    for (int w = 0; w < 8; w++) d[w] = c[w];
-  }
-};
+}
 
-struct ShaMerkle {
-  typedef int Consts;  // (none: the round constants are literals)
-  static constexpr const char* kernel_name = "sha256_merkle_open_top_kernel";
-  static __device__ __forceinline__ void leaf(uint32_t (&d)[8], const uint32_t* __restrict__ src, uint32_t rows, uint32_t cols, Consts) {
-    uint32_t st[8];
-    sha_hash_row(st, src, rows, cols);
-#pragma unroll
-    for (int w = 0; w < 8; w++) d[w] = sha_bswap(st[w]);
-  }
-  // one compression of the IV over the 16 words left || right, no padding: sha256_hash_fold_kernel's
-  static __device__ __forceinline__ void pair(uint32_t (&d)[8], const uint32_t* lds, uint32_t n, uint32_t p, Consts) {
-    uint32_t st[8], m[16];
-    sha_init(st);
-#pragma unroll
-    for (int w = 0; w < 8; w++) { m[w] = sha_bswap(lds[w * n + 2 * p]); m[8 + w] = sha_bswap(lds[w * n + 2 * p + 1]); }
-    sha_compress(st, m);
-#pragma unroll
-    for (int w = 0; w < 8; w++) d[w] = sha_bswap(st[w]);
-  }
-};
+// out[q] = column values at row idx[q] followed by the sibling digests up to (excluding) the top layer.  Does not depend on the suite.
+__global__ void merkle_open_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ matrix, const uint32_t* __restrict__ nodes,
+                                   const uint32_t* __restrict__ idx, uint32_t row_size, uint32_t col_size, uint32_t n_path) {
+  const uint32_t q = blockIdx.x, row = idx[q];
+  uint32_t* dst = out + (size_t)q * (col_size + 8 * n_path);
+  for (uint32_t i = threadIdx.x; i < col_size; i += blockDim.x) dst[i] = matrix[(size_t)i * row_size + row];
+  path_above(dst + col_size, nodes, row, row_size, 0, n_path);
+}
 
 // report[0]: queries whose subtree root is not the top's node; report[1]: the lowest such query number (0xffffffff: none)
-template <class Suite>
+template <class S>
 __global__ __launch_bounds__(256) void merkle_open_top_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ matrix, const uint32_t* __restrict__ top,
                                                                const uint32_t* __restrict__ idx, uint32_t rows, uint32_t cols, uint32_t n_path, uint32_t levels,
-                                                               uint32_t* __restrict__ report, typename Suite::Consts k) {
+                                                               uint32_t* __restrict__ report, typename S::Consts k) {
   extern __shared__ uint32_t lds[];  // [8][n]: word w of the node in slot s at lds[w * n + s]
   const uint32_t q = blockIdx.x, row = idx[q], n = 1u << levels, j = threadIdx.x;  // blockDim.x == n <= rows
   uint32_t* dst = out + (size_t)q * (cols + 8 * n_path);
   for (uint32_t i = j; i < cols; i += n) dst[i] = matrix[(size_t)i * rows + row];
   const uint32_t base = (row >> levels) << levels, local = row - base;  // the subtree's first leaf row; base + j < rows
   uint32_t d[8];
-  Suite::leaf(d, matrix + base + j, rows, cols, k);
+  S::row(d, matrix + base + j, rows, cols, k);
 #pragma unroll
   for (int w = 0; w < 8; w++) lds[w * n + j] = d[w];
   __syncthreads();
   for (uint32_t l = 0; l < levels; l++) {  // slots [0, n >> l) hold the subtree's nodes l levels above the leaves
     for (uint32_t w = j; w < 8; w += n) dst[cols + 8 * l + w] = lds[w * n + ((local >> l) ^ 1u)];
     const bool parent = j < (n >> (l + 1));
-    if (parent) Suite::pair(d, lds, n, j, k);
+    if (parent) {  // the nodes in slots 2j and 2j + 1
+      uint32_t right[8];
+#pragma unroll
+      for (int w = 0; w < 8; w++) { d[w] = lds[w * n + 2 * j]; right[w] = lds[w * n + 2 * j + 1]; }
+      S::pair(d, d, right, k);
+    }
     __syncthreads();  // every pair has been read before a slot is written
     if (parent) {
 #pragma unroll
@@ -97,17 +76,14 @@ __global__ __launch_bounds__(256) void merkle_open_top_kernel(uint32_t* __restri
       atomicMin(&report[1], q);
     }
   }
-  for (uint32_t w = j + 8 * levels; w < 8 * n_path; w += n) {  // the path above the subtree: out of the top
-    const uint32_t sibling = ((row + rows) >> (w >> 3)) ^ 1u;
-    dst[cols + w] = top[(size_t)sibling * 8 + (w & 7)];
-  }
+  path_above(dst + cols, top, row, rows, levels, n_path);  // the path above the subtree: out of the top
 }
 
 // how many digests the top of a `rows`-leaf tree kept to `levels` above the leaves holds (index 0 unused, the root at 1)
 static size_t top_digests(uint32_t rows, uint32_t levels) { return ((size_t)2 * rows) >> levels; }
 
 static const char* require_top_shape(const char* caller, uint32_t rows, uint32_t levels) {
-  R0H_REQUIRE(rows && (rows & (rows - 1)) == 0, "%s: rows %u is not a power of two", caller, rows);
+  R0H_TRY(require_pow2_rows(caller, rows));
   const uint32_t path = (uint32_t)MerkleShape(rows, 0).path_digests(), most = path < R0H_MERKLE_TOP_MAX_LEVELS ? path : R0H_MERKLE_TOP_MAX_LEVELS;
   R0H_REQUIRE(levels >= 1 && levels <= most, "%s: levels %u outside [1, %u] (at most %u, and at most the %u path digests of an opening in a tree of %u rows)", caller, levels,
               most, (unsigned)R0H_MERKLE_TOP_MAX_LEVELS, path, rows);
@@ -130,15 +106,17 @@ const char* merkle_open_top(r0h_ctx* ctx, uint32_t* out, const uint32_t* matrix,
   R0H_TRY(stage_h2d(ctx, report, clean, sizeof clean));
   const uint32_t n = 1u << levels, n_path = (uint32_t)MerkleShape(rows, cols).path_digests();
   const size_t lds_bytes = (size_t)8 * n * 4;
-  if (ctx->hashfn == HASH_SHA256) {
-    KScope ks(ctx, ShaMerkle::kernel_name, (double)n_q * n * cols * 4);
-    hipLaunchKernelGGL(merkle_open_top_kernel<ShaMerkle>, dim3(n_q), dim3(n), lds_bytes, ctx->stream, out, matrix, top, d_idx, rows, cols, n_path, levels, report, 0);
-    return launch_ok(ShaMerkle::kernel_name);
-  }
-  KScope ks(ctx, P2Merkle::kernel_name, (double)n_q * n * cols * 4);
-  hipLaunchKernelGGL(merkle_open_top_kernel<P2Merkle>, dim3(n_q), dim3(n), lds_bytes, ctx->stream, out, matrix, top, d_idx, rows, cols, n_path, levels, report,
-                     (const P2Consts*)ctx->p2);
-  return launch_ok(P2Merkle::kernel_name);
+  return with_suite(ctx, [&](auto suite) {
+    using S = decltype(suite);
+    KScope ks(ctx, S::open_top_kernel, (double)n_q * n * cols * 4);
+    hipLaunchKernelGGL(merkle_open_top_kernel<S>, dim3(n_q), dim3(n), lds_bytes, ctx->stream, out, matrix, top, d_idx, rows, cols, n_path, levels, report, S::consts(ctx));
+    return launch_ok(S::open_top_kernel);
+  });
+}
+
+const char* merkle_open(r0h_ctx* ctx, uint32_t* out, const uint32_t* matrix, const uint32_t* nodes, const uint32_t* d_idx, uint32_t n_q, uint32_t rows, uint32_t cols) {
+  hipLaunchKernelGGL(merkle_open_kernel, dim3(n_q), dim3(256), 0, ctx->stream, out, matrix, nodes, d_idx, rows, cols, (uint32_t)MerkleShape(rows, cols).path_digests());
+  return launch_ok("merkle_open_kernel");
 }
 
 const char* merkle_open_top_verdict(const char* caller, const uint32_t report[2], const uint32_t* idx_host) {
@@ -170,7 +148,7 @@ const char* r0h_merkle_open_top(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* matri
   R0H_REQUIRE(top_digests(rows, levels) * 32 <= top->bytes, "r0h_merkle_open_top: the top of a %u-row tree at %u levels is %zu bytes, the buffer holds %zu", rows, levels,
               top_digests(rows, levels) * 32, top->bytes);
   R0H_REQUIRE((size_t)n_q * mp.opening_words() * 4 <= out->bytes, "r0h_merkle_open_top: %u openings of %zu words exceed the output buffer", n_q, mp.opening_words());
-  for (uint32_t q = 0; q < n_q; q++) R0H_REQUIRE(idx_host[q] < rows, "r0h_merkle_open_top: query %u opens row %u of a %u-row tree", q, idx_host[q], rows);
+  R0H_TRY(require_rows_in_tree("r0h_merkle_open_top", idx_host, n_q, rows));
   if (first_mismatch_out) *first_mismatch_out = 0xffffffffu;
   if (!n_q) return nullptr;
   (void)hipSetDevice(ctx->device);

@@ -1,5 +1,5 @@
 // Device-side Poseidon2 permutation (BabyBear, t=24, x^7, 4+21+4 rounds) over a state held in 24 VGPRs of one lane.
-// Shared by poseidon2.hip (hash_rows / hash_fold) and tools/microbench/p2_rounds_bench.hip (per-round cycle counts).
+// Reached by the Merkle kernels through P2Device (hash_suite_device.hpp); shared with sponge.hip and tools/microbench/p2_rounds_bench.hip (per-round cycle counts).
 #pragma once
 #include "internal.hpp"
 
@@ -263,7 +263,8 @@ __device__ __forceinline__ void p2_mix(uint32_t (&c)[P2_CELLS], const P2Consts* 
 }
 
 // The row sponge: c[0..7] = digest of the `cols` words src[0], src[rows], src[2 * rows], .. (one row of a column-major matrix), absorbed
-// in rate blocks.  What hash_rows_kernel computes per lane (poseidon2.hip) and merkle_open_top_kernel per leaf (merkle_top.hip).
+// in rate blocks.  P2Device::row (hash_suite_device.hpp): what hash_rows_kernel computes per lane,
+// merkle_open_top_kernel per leaf and merkle_climb_kernel per opening.
 __device__ __forceinline__ void p2_hash_row(uint32_t (&c)[P2_CELLS], const uint32_t* src, uint32_t rows, uint32_t cols,
                                             const P2Consts* __restrict__ k) {
 #pragma unroll

@@ -33,17 +33,6 @@ struct WriteIop {
 };
 
 // ------------------------------------------------------------------ Merkle
-// out[q] = column values at row idx[q] followed by the sibling digests up to (excluding) the top layer
-__global__ void merkle_open_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ matrix, const uint32_t* __restrict__ nodes,
-                                   const uint32_t* __restrict__ idx, uint32_t row_size, uint32_t col_size, uint32_t n_path) {
-  const uint32_t q = blockIdx.x, row = idx[q];
-  uint32_t* dst = out + (size_t)q * (col_size + 8 * n_path);
-  for (uint32_t i = threadIdx.x; i < col_size; i += blockDim.x) dst[i] = matrix[(size_t)i * row_size + row];
-  for (uint32_t w = threadIdx.x; w < 8 * n_path; w += blockDim.x) {
-    uint32_t level = w >> 3, node = ((row + row_size) >> level) ^ 1u;
-    dst[col_size + w] = nodes[(size_t)node * 8 + (w & 7)];
-  }
-}
 // The full form holds all 2 * rows nodes.  The top form (top_levels != 0: r0h_proof_begin_committed_top) holds digests
 // [0, 2 * rows >> top_levels) only, and its openings hash the bottom top_levels levels again from the matrix (merkle_top.hip).
 struct Tree {
@@ -88,9 +77,7 @@ static const char* tree_open(r0h_ctx* ctx, const Tree& t, const r0h_buf* d_idx, 
     return merkle_open_top_verdict("r0h_proof_finish", report, idx_host);
   }
   R0H_TRY(packed.alloc(ctx, (size_t)n_q * words * 4));
-  hipLaunchKernelGGL(merkle_open_kernel, dim3(n_q), dim3(256), 0, ctx->stream, u32(packed.get()), u32(t.matrix), u32(t.nodes.get()), u32(d_idx),
-                     (uint32_t)t.mp.rows, (uint32_t)t.mp.cols, (uint32_t)t.mp.path_digests());
-  R0H_TRY(launch_ok("merkle_open_kernel"));
+  R0H_TRY(merkle_open(ctx, u32(packed.get()), u32(t.matrix), u32(t.nodes.get()), u32(d_idx), n_q, (uint32_t)t.mp.rows, (uint32_t)t.mp.cols));
   host.resize((size_t)n_q * words);
   return r0h_buf_d2h(ctx, packed.get(), 0, host.data(), host.size() * 4);
 }

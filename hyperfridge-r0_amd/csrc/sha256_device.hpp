@@ -52,8 +52,9 @@ __device__ __forceinline__ void sha_compress(uint32_t st[8], uint32_t w[16]) {
 }
 
 // The row sponge: st = state after the `cols` words src[0], src[rows], src[2 * rows], .. (one row of a column-major matrix), compressed in
-// 16-word blocks chained from the IV, the last partial block zero-filled; digest word j is sha_bswap(st[j]).  What
-// sha256_hash_rows_kernel computes per lane (sha256.hip) and merkle_open_top_kernel per leaf (merkle_top.hip).
+// 16-word blocks chained from the IV, the last partial block zero-filled, no length block (`hash_raw_data_slice`); cols = 0 gives the IV.
+// Digest word j is sha_bswap(st[j]): ShaDevice::row (hash_suite_device.hpp), what sha256_hash_rows_kernel computes per lane,
+// sha256_merkle_open_top_kernel per leaf and sha256_merkle_climb_kernel per opening.
 __device__ __forceinline__ void sha_hash_row(uint32_t st[8], const uint32_t* src, uint32_t rows, uint32_t cols) {
   uint32_t w[16];
   sha_init(st);

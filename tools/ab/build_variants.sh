@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build libr0hip variants that differ only in how ONE translation unit is compiled -- poseidon2.hip by default (A/B runs of hash_rows /
+# Build libr0hip variants that differ only in how ONE translation unit is compiled -- merkle.hip by default (A/B runs of hash_rows /
 # hash_fold in ONE process on ONE box: tools/ab/ab_hash.py), UNIT=ntt for ntt.hip (tools/ab/ab_ntt.py).
 # usage: [UNIT=ntt] tools/ab/build_variants.sh name1:"-Dflags" name2:"-Dflags" ...
 set -e
@@ -8,7 +8,7 @@ SRC=hyperfridge-r0_amd/csrc
 OUT=tools/ab/lib
 mkdir -p $OUT
 make -s -j8 -C $SRC
-UNIT=${UNIT:-poseidon2}
+UNIT=${UNIT:-merkle}
 OTHERS=$(ls $SRC/*.o | grep -v "/$UNIT.o")
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
