@@ -56,6 +56,7 @@ _SIGNATURES = {
     "r0h_zk_shift": [_vp, _vp, _u32, _u32],
     "r0h_batch_interpolate_ntt_zk_shift": [_vp, _vp, _u32, _u32],
     "r0h_poseidon2_set_consts": [_vp, _vp, _vp],
+    "r0h_poseidon2_dot_schedule": [_vp, _vp],
     "r0h_hash_rows": [_vp, _vp, _vp, _u32, _u32],
     "r0h_hash_fold": [_vp, _vp, _u32],
     "r0h_merkle_build": [_vp, _vp, _vp, _u32, _u32],
@@ -1510,6 +1511,13 @@ class Hal:
         b, pb = _u32arr(diag_m1)
         assert a.size == 24 * 29 and b.size == 24
         _check(lib().r0h_poseidon2_set_consts(self.ctx, pa, pb))
+
+    def poseidon2_dot_schedule(self):
+        """'tight' when the table the context holds is covered by the correction schedule derived from the compiled-in diagonal (the
+        default table is), 'safe' when its Poseidon2 kernels run the schedule that holds for any table.  Same digests either way."""
+        tight = ctypes.c_int(-1)
+        _check(lib().r0h_poseidon2_dot_schedule(self.ctx, ctypes.byref(tight)))
+        return "tight" if tight.value == 1 else "safe"
 
     def hash_rows(self, digests, matrix, rows, cols):
         _check(lib().r0h_hash_rows(self.ctx, digests.handle, matrix.handle, rows, cols))

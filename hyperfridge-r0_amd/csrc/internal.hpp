@@ -66,6 +66,9 @@ struct P2Consts {
   // kappa_k = sum_{i>=1} D_i^k, all in Montgomery form,
   //   part_sigma: for r = 1..20 the row [D_1^r .. D_23^r, kappa_{r-1}, kappa_{r-2}, .., kappa_0]   (23 + r words each)
   //   part_final: for i = 1..23 the row [D_i^21, D_i^20, .., D_i^0]
+  // The kernels' tight correction schedule for these 43 dot products is derived from the compiled-in diagonal
+  // (poseidon2_dot_schedule.hpp); whether it covers the words that stand here is found by fill_p2 and kept BESIDE the table
+  // (r0h_ctx::p2_tight), not in it: the bytes that are uploaded and compared (ctx_helper, ctx_code_commit) are the table alone.
   uint32_t part_sigma[P2_PART_SIGMA_WORDS];
   uint32_t part_final[(P2_CELLS - 1) * (P2_PARTIAL + 1)];
 };
@@ -108,7 +111,8 @@ struct r0h_ctx {
   uint32_t* pow3_top = nullptr; // 3^(i*2^22), i < 16 (exponents up to 2^26)
   r0h::P2Consts* p2 = nullptr;  // device
   r0h::P2Consts p2_host;
-  int hashfn = 0;               // r0h::HashFn: the suite hash_rows / hash_fold / the sequencer follow (r0h_ctx_set_hashfn)
+  bool p2_tight = false;        // the tight dot-product schedule covers p2_host (fill_p2): which Poseidon2 kernels with_suite launches
+  int hashfn = 0;              // r0h::HashFn: the suite hash_rows / hash_fold / the sequencer follow (r0h_ctx_set_hashfn)
   void* scratch = nullptr;      // small device scratch for scans / partial sums
   size_t scratch_bytes = 0;
   void* pinned = nullptr;       // pinned host staging ring for small parameter uploads
@@ -266,8 +270,10 @@ const char* run_lanes(const std::vector<r0h_ctx*>& lanes, Fn fn, OnError on_erro
 }
 // host Poseidon2 (transcript only): permutation over 24 Montgomery words with the context's table
 void p2_mix_host(const P2Consts& k, uint32_t* cells);
-// table from canonical round constants [29][24] and canonical (mu_i - 1) [24]; the compiled-in risc0 table, filled on first use
-void fill_p2(P2Consts& k, const uint32_t* rc, const uint32_t* diag_m1);
+// table from canonical round constants [29][24] and canonical (mu_i - 1) [24]; the compiled-in risc0 table, filled on first use.
+// Returns whether the kernels' tight dot-product schedule covers the table just filled (walked in exact integers): true for the
+// compiled-in diagonal, and for any other whose words keep every bound; otherwise the kernels of the safe schedule are launched.
+bool fill_p2(P2Consts& k, const uint32_t* rc, const uint32_t* diag_m1);
 const P2Consts& p2_default();
 void p2_hash_elems_host(const P2Consts& k, const uint32_t* elems, size_t n, uint32_t digest[8]);
 void p2_sponge_rows_host(const P2Consts& k, const uint32_t* words, size_t n_words, uint32_t* cols, size_t stride, size_t* rows_used);

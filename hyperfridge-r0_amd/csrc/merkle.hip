@@ -11,7 +11,7 @@
 namespace r0h {
 
 template <class S>
-__global__ __launch_bounds__(256) void hash_rows_kernel(uint32_t* __restrict__ digests, const uint32_t* __restrict__ matrix,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S::rows_waves))) void hash_rows_kernel(uint32_t* __restrict__ digests, const uint32_t* __restrict__ matrix,
                                                          uint32_t rows, uint32_t cols, typename S::Consts k) {
   uint32_t row = blockIdx.x * 256 + threadIdx.x;
   if (row >= rows) return;
@@ -126,7 +126,7 @@ const char* r0h_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size) {
   return with_suite(ctx, [&](auto suite) {
     using S = decltype(suite);
     KScope ks(ctx, S::fold_kernel, (double)output_size * 96);
-    if (std::is_same<S, P2Device>::value && output_size <= 8192) {  // Poseidon2 with fewer parents than the chip has SIMD slots (measured up to 8 K: 1.47 vs 1.52 ms per tree) (32x the instructions per permutation, ~7x less latency): spread each permutation over 24 lanes (latency, not throughput)
+    if (S::poseidon2 && output_size <= 8192) {  // Poseidon2 with fewer parents than the chip has SIMD slots (measured up to 8 K: 1.47 vs 1.52 ms per tree) (32x the instructions per permutation, ~7x less latency): spread each permutation over 24 lanes (latency, not throughput)
       hipLaunchKernelGGL(hash_fold_lanes_kernel, dim3((output_size * 32 + 255) / 256), dim3(256), 0, ctx->stream, u32(nodes), output_size, ctx->p2);
       return launch_ok("hash_fold_lanes_kernel");
     }

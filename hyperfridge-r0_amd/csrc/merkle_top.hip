@@ -107,7 +107,7 @@ const char* merkle_open_top(r0h_ctx* ctx, uint32_t* out, const uint32_t* matrix,
   const uint32_t n = 1u << levels, n_path = (uint32_t)MerkleShape(rows, cols).path_digests();
   const size_t lds_bytes = (size_t)8 * n * 4;
   return with_suite(ctx, [&](auto suite) {
-    using S = decltype(suite);
+    using S = typename decltype(suite)::OpenTop;
     KScope ks(ctx, S::open_top_kernel, (double)n_q * n * cols * 4);
     hipLaunchKernelGGL(merkle_open_top_kernel<S>, dim3(n_q), dim3(n), lds_bytes, ctx->stream, out, matrix, top, d_idx, rows, cols, n_path, levels, report, S::consts(ctx));
     return launch_ok(S::open_top_kernel);

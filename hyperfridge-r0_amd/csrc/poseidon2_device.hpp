@@ -1,7 +1,10 @@
 // Device-side Poseidon2 permutation (BabyBear, t=24, x^7, 4+21+4 rounds) over a state held in 24 VGPRs of one lane.
 // Reached by the Merkle kernels through P2Device (hash_suite_device.hpp); shared with sponge.hip and tools/microbench/p2_rounds_bench.hip (per-round cycle counts).
 #pragma once
+#include <utility>
+
 #include "internal.hpp"
+#include "poseidon2_dot_schedule.hpp"
 
 namespace r0h {
 
@@ -10,7 +13,7 @@ namespace r0h {
 //   x4' = x4 - p if that does not wrap (< 1.02)                               x7 = x3*x4' < 0.81 + 1, then one reduction
 // Two conditional subtractions fewer than four full products; the result is the same canonical word.  (A signed-Montgomery
 // chain -- v_mad_i64_i32 / v_mul_hi_i32, no corrections until the end -- measured 19 % slower: tools/microbench/p2_rounds_bench.)
-__device__ __forceinline__ uint32_t sbox7(uint32_t x) {
+R0H_HD uint32_t sbox7(uint32_t x) {
   uint32_t x2 = mul_lazy(x, x);
   uint32_t x3 = mul_lazy(x2, x);
   uint32_t x4 = reduce1(mul_lazy(x2, x2));
@@ -149,13 +152,13 @@ __device__ __forceinline__ void m_ext(uint32_t (&c)[P2_CELLS]) {
 #endif
 
 // c[1] + ... + c[23] mod p for reduced words, as a balanced tree
-__device__ __forceinline__ uint32_t sum_lanes_1_to_23(const uint32_t (&c)[P2_CELLS]) {
+R0H_HD uint32_t sum_lanes_1_to_23(const uint32_t (&c)[P2_CELLS]) {
   uint32_t s1[12];
-#pragma unroll
+R0H_UNROLL
   for (int i = 0; i < 11; i++) s1[i] = add(c[2 * i + 2], c[2 * i + 3]);
   s1[11] = c[1];
   uint32_t s2[6];
-#pragma unroll
+R0H_UNROLL
   for (int i = 0; i < 6; i++) s2[i] = add(s1[2 * i], s1[2 * i + 1]);
   return add(add(add(s2[0], s2[1]), add(s2[2], s2[3])), add(s2[4], s2[5]));
 }
@@ -168,33 +171,58 @@ __device__ __forceinline__ void p2_full_round(uint32_t (&c)[P2_CELLS], const uin
   else m_ext(c);
 }
 
-// Lazily accumulated dot product mod p: 64-bit accumulator, products of reduced words.  The first four products fit as they
-// are (4 p^2 < 2^64); from then on the high word is brought below p before every second product, which keeps the total
-// below p 2^32 + 2 p^2 < 2^64 and its high word below 2p.  ~11 SIMD cycles per term against ~34 for a reduced product plus a
-// modular add (tools/microbench/dot_bench.hip).  `idx` is the term's position: compile-time after unrolling.
-__device__ __forceinline__ void dot_fix(uint64_t& acc) {
+// Lazily accumulated dot product mod p: 64-bit accumulator, products of reduced words.  The accumulator's high word is brought
+// below p (dot_fix: one conditional subtraction, which needs it below 2p, i.e. the accumulator below 2p 2^32 < 2^64) where the
+// schedule S says so, and once more before reduce64 if S asks for it (poseidon2_dot_schedule.hpp).  Two schedules:
+//   P2DotSafe   holds for every canonical table: the first four products fit as they are (4 p^2 < 2^64), from then on a correction
+//               before every second product keeps the total below p 2^32 + 2 p^2, and one at the end: 550 per permutation.
+//   P2DotTight  from an exact bound over the words of the compiled-in table, which are about p/2 on average: 258 per permutation.
+//               Every correction subtracts p 2^32 from a value that is reduced mod p afterwards, so the words are the same.
+// fill_p2 (poseidon2_host.cpp) checks the tight schedule against the table a context loads, and the launches choose the instantiation from that.
+// ~11 SIMD cycles per term against ~34 for a reduced product plus a modular add (tools/microbench/dot_bench.hip).
+// ROW (the dot product, in the schedule's numbering) is a template argument, so a row's mask is an immediate; `idx` (the term's
+// position) is compile-time after unrolling.  (Masks looked up by a loop variable are loads from a table until the loops are
+// unrolled, and with them in the body the loops are not unrolled.)  The functions from here to p2_partial_rounds also compile for
+// the host (tools/fuzz/p2_dot_check.cpp); with R0H_DOT_CHECK defined there, every bound the schedule relies on is asserted in 128-bit
+// arithmetic as the code runs.
+#if defined(R0H_DOT_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+void r0h_dot_check_failed(const char* what, uint64_t acc);  // defined by the checking program
+#define R0H_DOT_REQUIRE(cond, what, acc) do { if (!(cond)) r0h_dot_check_failed(what, acc); } while (0)
+#else
+#define R0H_DOT_REQUIRE(cond, what, acc) do { } while (0)
+#endif
+R0H_HD void dot_fix(uint64_t& acc) {
   uint32_t hi = (uint32_t)(acc >> 32);
+  R0H_DOT_REQUIRE(hi < 2 * (uint64_t)P, "a correction finds the high word at or above 2p", acc);
 #if defined(__HIP_DEVICE_COMPILE__)
   // reduce1 on the high word IN PLACE: the word is a read-write operand and only the scratch is early-clobber, so the register
   // coalescer keeps it in the accumulator pair.  reduce1 itself returns an early-clobber output, which cost a v_mov_b32 back into
-  // the pair after every correction (550 per permutation); same two full-rate instructions, same word.
+  // the pair after every correction; same two full-rate instructions, same word.
   uint32_t x;
   asm("v_subrev_co_u32 %1, vcc, 0x78000001, %0\n\tv_cndmask_b32 %0, %1, %0, vcc" : "+v"(hi), "=&v"(x) : : "vcc");
 #else
   hi = reduce1(hi);
 #endif
   acc = ((uint64_t)hi << 32) | (uint32_t)acc;
+#if defined(__HIP_DEVICE_COMPILE__)
   // opaque re-pack: seen as (hi << 32) + lo, the optimiser re-associates the following multiply-adds into separate 64-bit
   // additions and moves instead of one v_mad_u64_u32 on the accumulator pair
   asm("" : "+v"(acc));
+#endif
 }
-__device__ __forceinline__ void dot_mac(uint64_t& acc, uint32_t a, uint32_t b, int idx) {
+template <class S, int ROW>
+R0H_HD void dot_mac(uint64_t& acc, uint32_t a, uint32_t b, int idx) {
+  constexpr uint64_t mask = S::mask(ROW);
   if (idx == 0) { acc = (uint64_t)a * b; return; }
-  if (idx >= 4 && (idx & 1) == 0) dot_fix(acc);
+  if ((mask >> idx) & 1) dot_fix(acc);
+  R0H_DOT_REQUIRE((((unsigned __int128)acc + (unsigned __int128)a * b) >> 64) == 0, "the accumulator reaches 2^64", acc);
   acc += (uint64_t)a * b;
 }
-__device__ __forceinline__ uint32_t dot_finish(uint64_t acc) {
-  dot_fix(acc);  // below p 2^32 + 2^32 < 4 p^2: what reduce64 asks for
+template <class S, int ROW>
+R0H_HD uint32_t dot_finish(uint64_t acc) {
+  constexpr uint64_t mask = S::mask(ROW);
+  if ((mask >> P2_DOT_END) & 1) dot_fix(acc);
+  R0H_DOT_REQUIRE(acc < P2_DOT_END_LIMIT, "reduce64 is handed 4 p^2 or more", acc);
   return reduce64(acc);
 }
 
@@ -204,40 +232,57 @@ __device__ __forceinline__ uint32_t dot_finish(uint64_t acc) {
 //   sigma_r = sum_i D_i^r u_i + sum_{j<r} kappa_{r-1-j} sum_j      (kappa_k = sum_i D_i^k),
 // and the lanes themselves are materialised once at the end (22 terms each): 1176 lazily accumulated terms in all, instead
 // of 21 x 24 reduced constant products and 21 x 48 modular adds.  Same canonical words as the round-by-round form.
-__device__ __forceinline__ void p2_partial_rounds(uint32_t (&c)[P2_CELLS], const P2Consts* __restrict__ k) {
+// Round R and lane I are template arguments for the schedule's sake (above); `row` walks part_sigma as the rounds go.
+template <class S, int R>
+R0H_HD void p2_partial_round(const uint32_t (&c)[P2_CELLS], uint32_t (&sums)[P2_PARTIAL], uint32_t& s0, uint32_t& sigma,
+                             const uint32_t*& row, const P2Consts* __restrict__ k) {
+  if (R > 0) {
+    constexpr int ROW = R > 0 ? R - 1 : 0;
+    uint64_t acc;
+R0H_UNROLL
+    for (int i = 0; i < P2_CELLS - 1; i++) dot_mac<S, ROW>(acc, c[i + 1], row[i], i);
+R0H_UNROLL
+    for (int j = 0; j < R; j++) dot_mac<S, ROW>(acc, sums[j], row[P2_CELLS - 1 + j], P2_CELLS - 1 + j);
+    sigma = dot_finish<S, ROW>(acc);
+    row += P2_CELLS - 1 + R;
+  }
+  const uint32_t y = sbox7(add(s0, k->rc_partial[R]));
+  sums[R] = add(y, sigma);
+  s0 = add(sums[R], mul_const(y, k->diag_canon[0], k->diag_shoup[0]));
+}
+template <class S, int I>
+R0H_HD void p2_partial_lane(uint32_t (&c)[P2_CELLS], const uint32_t (&sums)[P2_PARTIAL], const uint32_t* f) {
+  constexpr int ROW = P2_DOT_SIGMA_ROWS + I - 1;
+  uint64_t acc;
+  dot_mac<S, ROW>(acc, c[I], f[0], 0);
+R0H_UNROLL
+  for (int q = 0; q < P2_PARTIAL; q++) dot_mac<S, ROW>(acc, sums[q], f[1 + q], 1 + q);
+  c[I] = dot_finish<S, ROW>(acc);
+}
+template <class S, int... R, int... I>
+R0H_HD void p2_partial_rounds_seq(uint32_t (&c)[P2_CELLS], const P2Consts* __restrict__ k, std::integer_sequence<int, R...>,
+                                  std::integer_sequence<int, I...>) {
   // table offsets go through an opaque zero: with constant offsets, loop-invariant code motion precomputes one 64-bit address
   // per table row outside the caller's loop and spills hundreds of SGPRs
   uint32_t zero;
+#if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_mov_b32 %0, 0" : "=s"(zero));
+#else
+  zero = 0;
+#endif
   uint32_t sums[P2_PARTIAL];
   uint32_t s0 = c[0];
   uint32_t sigma = sum_lanes_1_to_23(c);
-  const uint32_t* __restrict__ row = k->part_sigma + zero;
-#pragma unroll
-  for (int r = 0; r < P2_PARTIAL; r++) {
-    if (r > 0) {
-      uint64_t acc;
-#pragma unroll
-      for (int i = 0; i < P2_CELLS - 1; i++) dot_mac(acc, c[i + 1], row[i], i);
-#pragma unroll
-      for (int j = 0; j < r; j++) dot_mac(acc, sums[j], row[P2_CELLS - 1 + j], P2_CELLS - 1 + j);
-      sigma = dot_finish(acc);
-      row += P2_CELLS - 1 + r;
-    }
-    const uint32_t y = sbox7(add(s0, k->rc_partial[r]));
-    sums[r] = add(y, sigma);
-    s0 = add(sums[r], mul_const(y, k->diag_canon[0], k->diag_shoup[0]));
-  }
+  const uint32_t* row = k->part_sigma + zero;
+  (p2_partial_round<S, R>(c, sums, s0, sigma, row, k), ...);
   c[0] = s0;
-#pragma unroll
-  for (int i = 1; i < P2_CELLS; i++) {
-    const uint32_t* __restrict__ f = k->part_final + zero + (i - 1) * (P2_PARTIAL + 1);
-    uint64_t acc;
-    dot_mac(acc, c[i], f[0], 0);
-#pragma unroll
-    for (int q = 0; q < P2_PARTIAL; q++) dot_mac(acc, sums[q], f[1 + q], 1 + q);
-    c[i] = dot_finish(acc);
-  }
+  (p2_partial_lane<S, I + 1>(c, sums, k->part_final + zero + I * (P2_PARTIAL + 1)), ...);
+}
+// S has no default, here and in p2_mix_ends, p2_mix, p2_hash_row: P2DotTight is valid only for a table fill_p2 has found it to cover,
+// so whoever takes it says so (with_suite does, by r0h_ctx::p2_tight).
+template <class S>
+R0H_HD void p2_partial_rounds(uint32_t (&c)[P2_CELLS], const P2Consts* __restrict__ k) {
+  p2_partial_rounds_seq<S>(c, k, std::make_integer_sequence<int, P2_PARTIAL>{}, std::make_integer_sequence<int, P2_CELLS - 1>{});
 }
 
 // The permutation, with what the sponge knows about its ends (both wave-uniform; compile-time constants fold away):
@@ -245,26 +290,28 @@ __device__ __forceinline__ void p2_partial_rounds(uint32_t (&c)[P2_CELLS], const
 //   digest_only  only c[0..7] are read afterwards (a hash's last block): the last linear layer leaves c[8..23] unfinished
 // The canonical words that are read are those of the plain permutation.  One body serves every block of hash_rows: the two
 // shorter layers sit beside the full ones behind scalar branches, the rounds themselves are not duplicated.
+template <class S>
 __device__ __forceinline__ void p2_mix_ends(uint32_t (&c)[P2_CELLS], const P2Consts* __restrict__ k, bool zero_cap, bool digest_only) {
   if (zero_cap) m_ext<true, false>(c);
   else m_ext(c);
 #pragma unroll 1
   for (int r = 0; r < P2_HALF_FULL; r++) p2_full_round(c, k->rc_full[r]);
-  p2_partial_rounds(c, k);
+  p2_partial_rounds<S>(c, k);
 #pragma unroll 1
   for (int r = P2_HALF_FULL; r < 2 * P2_HALF_FULL; r++) {
     p2_full_round(c, k->rc_full[r], digest_only && r == 2 * P2_HALF_FULL - 1);
   }
 }
 constexpr int P2_ZERO_CAP = 1, P2_DIGEST_ONLY = 2;
-template <int ENDS = 0>
+template <int ENDS, class S>
 __device__ __forceinline__ void p2_mix(uint32_t (&c)[P2_CELLS], const P2Consts* __restrict__ k) {
-  p2_mix_ends(c, k, (ENDS & P2_ZERO_CAP) != 0, (ENDS & P2_DIGEST_ONLY) != 0);
+  p2_mix_ends<S>(c, k, (ENDS & P2_ZERO_CAP) != 0, (ENDS & P2_DIGEST_ONLY) != 0);
 }
 
 // The row sponge: c[0..7] = digest of the `cols` words src[0], src[rows], src[2 * rows], .. (one row of a column-major matrix), absorbed
 // in rate blocks.  P2Device::row (hash_suite_device.hpp): what hash_rows_kernel computes per lane,
 // merkle_open_top_kernel per leaf and merkle_climb_kernel per opening.
+template <class S>
 __device__ __forceinline__ void p2_hash_row(uint32_t (&c)[P2_CELLS], const uint32_t* src, uint32_t rows, uint32_t cols,
                                             const P2Consts* __restrict__ k) {
 #pragma unroll
@@ -278,7 +325,7 @@ __device__ __forceinline__ void p2_hash_row(uint32_t (&c)[P2_CELLS], const uint3
     const uint32_t have = cols - blk * P2_RATE;  // columns left, this block's included
 #pragma unroll
     for (int i = 0; i < P2_RATE; i++) c[i] = (uint32_t)i < have ? src[(size_t)(blk * P2_RATE + i) * rows] : 0u;
-    p2_mix_ends(c, k, blk == 0, blk + 1 == blocks);
+    p2_mix_ends<S>(c, k, blk == 0, blk + 1 == blocks);
   }
 }
 

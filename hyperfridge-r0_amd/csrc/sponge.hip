@@ -1,6 +1,6 @@
 // The rows of the in-circuit Poseidon2 sponge (include/r0hip_circuit.h SPONGE, tools/sponge_component.py) made on the device: what
 // r0h_lift, r0h_join and the image proof plant into a witness.  The chain from one permutation to the next is sequential and stays on
-// the host (ctx.cpp p2_sponge_chain_host: one pass gives the digest and what every permutation starts from); a permutation's 30 rows
+// the host (poseidon2_host.cpp p2_sponge_chain_host: one pass gives the digest and what every permutation starts from); a permutation's 30 rows
 // depend only on those 24 words, so the expansion -- 65 columns x 30 rows per permutation, 32 MB for a 2^20-row segment seal -- is
 // one launch over the trace's rows instead of a host loop, a pageable staging vector and a 2-D copy.
 #include "circuit.hpp"

@@ -86,6 +86,10 @@ const char* r0h_batch_interpolate_ntt_zk_shift(r0h_ctx* ctx, r0h_buf* io, uint32
 /* ---- Hal: Poseidon2 Merkle commitment (`hash_rows`, `hash_fold`; prove/merkle.rs) ---- */
 /* rc: 24*29 canonical round constants, diag_m1: 24 canonical (mu_i - 1); the default table is compiled in */
 const char* r0h_poseidon2_set_consts(r0h_ctx* ctx, const uint32_t* rc, const uint32_t* diag_m1);
+/* The Poseidon2 kernels exist for two schedules of the conditional subtractions in the partial rounds' dot products: a tight one
+ * derived from the compiled-in diagonal, and a safe one for any canonical table.  *tight = 1 when the table the context holds is
+ * covered by the tight schedule (the default table is), 0 when its kernels run the safe one.  The digests are the same either way. */
+const char* r0h_poseidon2_dot_schedule(const r0h_ctx* ctx, int* tight);
 /* digests[r] = sponge(matrix[0][r], matrix[1][r], ..., matrix[cols-1][r]) for r < rows */
 const char* r0h_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix, uint32_t rows, uint32_t cols);
 /* nodes[i] = H(nodes[2i] || nodes[2i+1]) for output_size <= i < 2*output_size (digest units) */

@@ -18,13 +18,13 @@ __global__ __launch_bounds__(256) void rounds_kernel(uint32_t* out, const P2Cons
 #pragma unroll 1
   for (int it = 0; it < iters; it++) {
     if (MODE == 0) p2_full_round(c, k->rc_full[it & 7]);
-    if (MODE == 1) p2_partial_rounds(c, k);
-    if (MODE == 2) p2_mix(c, k);
+    if (MODE == 1) p2_partial_rounds<P2DotTight>(c, k);  // the schedule of the compiled-in table, which main() uploads
+    if (MODE == 2) p2_mix<0, P2DotTight>(c, k);
     if (MODE == 3) m_ext(c);
     if (MODE == 5) {  // a hash's only block: zero capacity in, digest out (hash_fold; cols <= 16 in hash_rows)
 #pragma unroll
       for (int i = P2_RATE; i < P2_CELLS; i++) c[i] = 0;
-      p2_mix<P2_ZERO_CAP | P2_DIGEST_ONLY>(c, k);
+      p2_mix<P2_ZERO_CAP | P2_DIGEST_ONLY, P2DotTight>(c, k);
     }
     if (MODE == 4) {
 #pragma unroll
