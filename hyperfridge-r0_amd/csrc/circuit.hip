@@ -167,14 +167,15 @@ const char* r0h_circuit_load_check(r0h_circuit* c, const char* code_object_path)
 }  // extern "C"
 namespace r0h {
 // one launch of witgen_fixed_kernel over the columns `kinds` describes; the parameter block (kinds, then the PERIODIC section in
-// Montgomery form) goes through the context's scratch, in stream order behind whatever read it last
+// Montgomery form) goes through a block from the pool, in stream order behind whatever read it last
 static const char* witgen_fixed(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, std::vector<uint32_t>& kinds, uint64_t seed_mixed, r0h_buf* buf) {
   const uint32_t n = 1u << po2, threads = n < 256 ? n : 256, cols = (uint32_t)(kinds.size() / 2);
   const size_t table_at = kinds.size();
   for (uint32_t v : c->periodic) kinds.push_back(enc(v));
-  R0H_TRY(ensure_scratch(ctx, kinds.size() * 4));
-  R0H_TRY(stage_h2d(ctx, ctx->scratch, kinds.data(), kinds.size() * 4));
-  const uint32_t* dk = (const uint32_t*)ctx->scratch;
+  DevBuf d_kinds;
+  R0H_TRY(d_kinds.alloc(ctx, kinds.size() * 4));
+  R0H_TRY(stage_h2d(ctx, d_kinds->ptr, kinds.data(), kinds.size() * 4));
+  const uint32_t* dk = u32(d_kinds.get());
   hipLaunchKernelGGL(witgen_fixed_kernel, dim3(n / threads, cols), dim3(threads), 0, ctx->stream, u32(buf), dk, po2, seed_mixed, dk + table_at, c->period);
   return launch_ok("r0h_witgen");
 }

@@ -23,19 +23,6 @@ const char* make_error(const char* fmt, ...) {
   return out;
 }
 
-const char* ensure_scratch(r0h_ctx* ctx, size_t bytes) {
-  if (ctx->scratch_bytes >= bytes) return nullptr;
-  if (ctx->scratch) {
-    R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
-    R0H_TRY_HIP(hipFree(ctx->scratch));
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-  }
-  R0H_TRY_HIP(hipMalloc(&ctx->scratch, bytes));
-  ctx->scratch_bytes = bytes;
-  return nullptr;
-}
-
 const char* stage_h2d(r0h_ctx* ctx, void* dst, const void* src, size_t bytes) {
   if (!bytes) return nullptr;
   if (bytes > ctx->pinned_bytes / 2) {  // too large for the ring: plain blocking copy
@@ -152,7 +139,7 @@ void ctx_release(r0h_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   for (int d = 0; d < 2; d++) { (void)hipFree(ctx->tw_lo[d]); (void)hipFree(ctx->tw_hi[d]); (void)hipFree(ctx->tw12[d]); }
   for (int d = 0; d < 2; d++) { (void)hipFree(ctx->twb_lo[d]); (void)hipFree(ctx->twb_hi[d]); }
-  (void)hipFree(ctx->pow3_lo); (void)hipFree(ctx->pow3_hi); (void)hipFree(ctx->pow3_top); (void)hipFree(ctx->p2); (void)hipFree(ctx->scratch);
+  (void)hipFree(ctx->pow3_lo); (void)hipFree(ctx->pow3_hi); (void)hipFree(ctx->pow3_top); (void)hipFree(ctx->p2);
   (void)hipHostFree(ctx->pinned);
   for (auto& kv : ctx->pool) (void)hipFree(kv.second);
   for (hipEvent_t e : ctx->prof.events) (void)hipEventDestroy(e);
@@ -208,7 +195,6 @@ const char* r0h_ctx_create(int device, r0h_ctx** out) {
   R0H_TRY_HIP(hipMemcpy(ctx->p2, &ctx->p2_host, sizeof(P2Consts), hipMemcpyHostToDevice));
   ctx->pinned_bytes = 8u << 20;
   R0H_TRY_HIP(hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault));
-  R0H_TRY(ensure_scratch(ctx, 4u << 20));
   *out = ctx;
   return nullptr;
   R0H_GUARD_END

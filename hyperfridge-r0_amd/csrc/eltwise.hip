@@ -1,8 +1,7 @@
 // Streaming operations of the prover for gfx950: polynomial evaluation at extension points, FRI batching mix,
-// FRI fold, extension-field scans (running products, synthetic division) and the small element-wise helpers.
+// FRI fold and the small element-wise helpers (the extension-field scans are scan.hip).
 // Replaces risc0-zkp 3.0.4 hal `batch_evaluate_any`, `mix_poly_coeffs`, `eltwise_{add,copy}_elem`,
-// `eltwise_sum_extelem`, `gather_sample`, `scatter`, `fri_fold`, `prefix_products` and core/poly.rs `poly_divide`
-// (which upstream runs on the host) -- SURVEY.md 8(a) a10, a12-a15.
+// `eltwise_sum_extelem`, `gather_sample`, `scatter`, `fri_fold` -- SURVEY.md 8(a) a12-a15.
 // All of these are HBM-bound streams: one pass over the operand, coalesced column reads, 16-byte extension accesses.
 #include <algorithm>
 #include <array>
@@ -200,194 +199,6 @@ __global__ void fri_fold_kernel(uint32_t* __restrict__ out, const uint32_t* __re
   for (int k = 0; k < 4; k++) out[(size_t)k * n_out + idx] = tot.e[k];
 }
 
-// ------------------------------------------------------------------ extension-field scans
-// Both scans use chunks of `threads * E` elements: per-chunk summary, a serial pass over the (few) chunk summaries,
-// then the in-chunk pass with a Hillis-Steele scan across the block's threads.
-struct ScanGeom {
-  uint32_t threads, E, chunk, n_chunks;
-};
-static ScanGeom scan_geom(uint32_t n) {
-  ScanGeom g;
-  g.threads = n < 256 ? n : 256;
-  g.chunk = n < 4096 ? n : 4096;
-  g.E = g.chunk / g.threads;
-  g.n_chunks = n / g.chunk;
-  return g;
-}
-
-// running product (SUM = false): io[i] = prod_{j<=i} io[j]; running sum (SUM = true): io[i] = sum_{j<=i} io[j]
-template <bool SUM> R0H_HD Fp4 scan_id() { return SUM ? fp4_zero() : fp4_one(); }
-template <bool SUM> R0H_HD Fp4 scan_op(const Fp4& a, const Fp4& b) { return SUM ? a + b : a * b; }
-template <bool SUM>
-__global__ void prefix_chunk_prod_kernel(uint32_t* __restrict__ chunk_prod, const uint32_t* __restrict__ io, uint32_t E) {
-  extern __shared__ uint32_t sh[];
-  const uint32_t t = threadIdx.x, nt = blockDim.x;
-  const uint32_t* p = io + 4 * ((size_t)blockIdx.x * nt * E + (size_t)t * E);
-  Fp4 v = scan_id<SUM>();
-  for (uint32_t k = 0; k < E; k++) v = scan_op<SUM>(v, ld4(p + 4 * k));
-  st4(sh + 4 * t, v);
-  __syncthreads();
-  for (uint32_t s = nt / 2; s >= 1; s >>= 1) {
-    if (t < s) st4(sh + 4 * t, scan_op<SUM>(ld4(sh + 4 * t), ld4(sh + 4 * (t + s))));
-    __syncthreads();
-  }
-  if (t == 0) st4(chunk_prod + 4 * (size_t)blockIdx.x, ld4(sh));
-}
-// exclusive scan over the chunk summaries, one block: serial per thread, Hillis-Steele across threads
-template <bool SUM>
-__global__ __launch_bounds__(256) void prefix_chunk_scan_kernel(uint32_t* chunk_prod, uint32_t n_chunks) {
-  __shared__ uint32_t sh[256 * 4];
-  const uint32_t t = threadIdx.x, per = (n_chunks + 255) / 256, b0 = t * per;
-  Fp4 v = scan_id<SUM>();
-  for (uint32_t k = 0; k < per && b0 + k < n_chunks; k++) v = scan_op<SUM>(v, ld4(chunk_prod + 4 * (size_t)(b0 + k)));
-  st4(sh + 4 * t, v);
-  __syncthreads();
-  for (uint32_t s = 1; s < 256; s <<= 1) {
-    Fp4 o = t >= s ? ld4(sh + 4 * (t - s)) : scan_id<SUM>();
-    __syncthreads();
-    if (t >= s) st4(sh + 4 * t, scan_op<SUM>(ld4(sh + 4 * t), o));
-    __syncthreads();
-  }
-  Fp4 cur = t ? ld4(sh + 4 * (t - 1)) : scan_id<SUM>();
-  for (uint32_t k = 0; k < per && b0 + k < n_chunks; k++) {
-    Fp4 x = ld4(chunk_prod + 4 * (size_t)(b0 + k));
-    st4(chunk_prod + 4 * (size_t)(b0 + k), cur);
-    cur = scan_op<SUM>(cur, x);
-  }
-}
-template <bool SUM>
-__global__ void prefix_apply_kernel(uint32_t* __restrict__ io, const uint32_t* __restrict__ chunk_excl, uint32_t E) {
-  extern __shared__ uint32_t sh[];
-  const uint32_t t = threadIdx.x, nt = blockDim.x;
-  uint32_t* p = io + 4 * ((size_t)blockIdx.x * nt * E + (size_t)t * E);
-  Fp4 v = scan_id<SUM>();
-  for (uint32_t k = 0; k < E; k++) v = scan_op<SUM>(v, ld4(p + 4 * k));
-  st4(sh + 4 * t, v);
-  __syncthreads();
-  for (uint32_t s = 1; s < nt; s <<= 1) {  // inclusive scan over threads
-    Fp4 o = t >= s ? ld4(sh + 4 * (t - s)) : scan_id<SUM>();
-    __syncthreads();
-    if (t >= s) st4(sh + 4 * t, scan_op<SUM>(ld4(sh + 4 * t), o));
-    __syncthreads();
-  }
-  Fp4 cur = ld4(chunk_excl + 4 * (size_t)blockIdx.x);
-  if (t > 0) cur = scan_op<SUM>(cur, ld4(sh + 4 * (t - 1)));
-  for (uint32_t k = 0; k < E; k++) {
-    cur = scan_op<SUM>(cur, ld4(p + 4 * k));
-    st4(p + 4 * k, cur);
-  }
-}
-
-// what a scan leaves, n = 2^po2 packed extension elements, as the four columns of 2^po2 words an ACCUM accumulator is stored in
-__global__ void ext_unpack_kernel(uint32_t* __restrict__ cols, const uint32_t* __restrict__ packed, uint32_t po2) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= (1u << po2)) return;
-  const uint4 v = *(const uint4*)(packed + 4 * (size_t)r);
-  cols[r] = v.x; cols[((size_t)1 << po2) + r] = v.y; cols[((size_t)2 << po2) + r] = v.z; cols[((size_t)3 << po2) + r] = v.w;
-}
-
-// synthetic division by (x - z): q[i] = sum_{j>i} p[j] z^(j-i-1), remainder = sum_j p[j] z^j
-struct DivPowers {
-  Fp4 z, zE, zChunk;  // z, z^E, z^chunk
-};
-// One division job = (polynomial index within a buffer of n-coefficient polynomials, point, slot of its chunk values).  The
-// kernels take a batch of jobs on blockIdx.y -- the DEEP step divides ~10 combos by one to three points each: one launch set
-// per "k-th point of every combo" instead of one per (combo, point), and the remainders are read back once at the end.
-struct DivJob {
-  DivPowers pw;
-  uint32_t poly, slot, pad0, pad1;
-};
-__global__ void divide_chunk_sum_kernel(uint32_t* __restrict__ chunk_vals, const uint32_t* __restrict__ polys, const DivJob* __restrict__ jobs, uint32_t E,
-                                        uint32_t n, uint32_t n_chunks) {
-  extern __shared__ uint32_t sh[];
-  const uint32_t t = threadIdx.x, nt = blockDim.x;
-  const DivJob job = jobs[blockIdx.y];
-  const DivPowers pw = job.pw;
-  uint32_t* chunk_val = chunk_vals + 4 * (size_t)job.slot * (n_chunks + 1);
-  const uint32_t* p = polys + 4 * ((size_t)job.poly * n + (size_t)blockIdx.x * nt * E + (size_t)t * E);
-  Fp4 v = fp4_zero();
-  for (uint32_t k = E; k-- > 0;) v = v * pw.z + ld4(p + 4 * k);  // sum_k p[k] z^k
-  st4(sh + 4 * t, v);
-  __syncthreads();
-  // V = sum_t v_t z^(E t): pairwise combine with growing powers
-  Fp4 step = pw.zE;
-  for (uint32_t s = 1; s < nt; s <<= 1) {
-    if ((t & (2 * s - 1)) == 0) st4(sh + 4 * t, ld4(sh + 4 * t) + ld4(sh + 4 * (t + s)) * step);
-    step = step * step;
-    __syncthreads();
-  }
-  if (t == 0) st4(chunk_val + 4 * (size_t)blockIdx.x, ld4(sh));
-}
-// carry[b] = sum_{b' > b} S_b' z^((b'-b-1)*chunk); remainder = sum_b S_b z^(b*chunk) -> chunk_val[n_chunks].
-// One block: each thread owns `per` consecutive chunks, a suffix scan with growing powers links the threads.
-__global__ __launch_bounds__(256) void divide_chunk_carry_kernel(uint32_t* chunk_vals, const DivJob* __restrict__ jobs, uint32_t n_chunks) {
-  __shared__ uint32_t sh[256 * 4];
-  const DivJob job = jobs[blockIdx.x];
-  const DivPowers pw = job.pw;
-  uint32_t* chunk_val = chunk_vals + 4 * (size_t)job.slot * (n_chunks + 1);
-  const uint32_t t = threadIdx.x, per = (n_chunks + 255) / 256, b0 = t * per;
-  Fp4 v = fp4_zero();  // sum_k S[b0+k] zc^k
-  for (uint32_t k = per; k-- > 0;)
-    if (b0 + k < n_chunks) v = v * pw.zChunk + ld4(chunk_val + 4 * (size_t)(b0 + k));
-    else v = v * pw.zChunk;
-  st4(sh + 4 * t, v);
-  __syncthreads();
-  Fp4 step = fp4_pow(pw.zChunk, per);
-  for (uint32_t s = 1; s < 256; s <<= 1) {  // sh[t] = sum_{t' >= t} v_t' step^(t'-t)
-    Fp4 o = t + s < 256 ? ld4(sh + 4 * (t + s)) : fp4_zero();
-    __syncthreads();
-    if (t + s < 256) st4(sh + 4 * t, ld4(sh + 4 * t) + o * step);
-    step = step * step;
-    __syncthreads();
-  }
-  if (t == 0) st4(chunk_val + 4 * (size_t)n_chunks, ld4(sh));  // remainder (slot past the carries)
-  // carry entering this thread's top chunk from the threads above
-  Fp4 cur = t + 1 < 256 ? ld4(sh + 4 * (t + 1)) : fp4_zero();
-  for (uint32_t k = per; k-- > 0;) {
-    if (b0 + k >= n_chunks) { cur = cur * pw.zChunk; continue; }
-    Fp4 sv = ld4(chunk_val + 4 * (size_t)(b0 + k));
-    st4(chunk_val + 4 * (size_t)(b0 + k), cur);
-    cur = cur * pw.zChunk + sv;
-  }
-}
-__global__ void divide_apply_kernel(uint32_t* __restrict__ polys, const uint32_t* __restrict__ chunk_vals, const DivJob* __restrict__ jobs, uint32_t E, uint32_t n,
-                                    uint32_t n_chunks) {
-  extern __shared__ uint32_t sh[];
-  const uint32_t t = threadIdx.x, nt = blockDim.x;
-  const DivJob job = jobs[blockIdx.y];
-  const DivPowers pw = job.pw;
-  const uint32_t* chunk_carry = chunk_vals + 4 * (size_t)job.slot * (n_chunks + 1);
-  uint32_t* p = polys + 4 * ((size_t)job.poly * n + (size_t)blockIdx.x * nt * E + (size_t)t * E);
-  Fp4 v = fp4_zero();
-  for (uint32_t k = E; k-- > 0;) v = v * pw.z + ld4(p + 4 * k);
-  st4(sh + 4 * t, v);
-  __syncthreads();
-  // suffix scan over threads: after it sh[t] = sum_{t' >= t} v_t' z^(E (t'-t))
-  Fp4 step = pw.zE;
-  for (uint32_t s = 1; s < nt; s <<= 1) {
-    Fp4 o = t + s < nt ? ld4(sh + 4 * (t + s)) : fp4_zero();
-    __syncthreads();
-    if (t + s < nt) st4(sh + 4 * t, ld4(sh + 4 * t) + o * step);
-    step = step * step;
-    __syncthreads();
-  }
-  // carry entering this thread's range from above: threads above it, then the chunks above the block
-  Fp4 zpow = fp4_pow(pw.zE, nt - 1 - t);
-  Fp4 cur = ld4(chunk_carry + 4 * (size_t)blockIdx.x) * zpow;
-  if (t + 1 < nt) cur = cur + ld4(sh + 4 * (t + 1));
-  for (uint32_t k = E; k-- > 0;) {
-    Fp4 next = cur * pw.z + ld4(p + 4 * k);
-    st4(p + 4 * k, cur);
-    cur = next;
-  }
-}
-
-// remainders of a batch, packed: out[job] = chunk_vals[slot(job)][n_chunks]
-__global__ void divide_remainders_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ chunk_vals, uint32_t n_jobs, uint32_t n_chunks) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n_jobs) st4(out + 4 * (size_t)j, ld4(chunk_vals + 4 * ((size_t)j * (n_chunks + 1) + n_chunks)));
-}
-
 static Fp4 host_fp4(const uint32_t v[4]) { return Fp4{{v[0], v[1], v[2], v[3]}}; }
 static bool canonical4(const uint32_t v[4]) { return v[0] < P && v[1] < P && v[2] < P && v[3] < P; }
 
@@ -441,8 +252,9 @@ const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, cons
   for (auto& g : groups) max_cols = std::max(max_cols, g.second.size());
   const size_t tab_words = 4 * (size_t)MAX_NP * (rl + rows), pt_words = 4 * MAX_NP, idx_words = (size_t)(1 + MAX_NP) * max_cols,
                part_words = 4 * (size_t)MAX_NP * max_cols * blocks;
-  R0H_TRY(ensure_scratch(ctx, (tab_words + pt_words + idx_words + part_words) * 4));
-  uint32_t* tab = (uint32_t*)ctx->scratch;
+  DevBuf tmp;  // [tables][points][indices][partial sums], sized for the largest group
+  R0H_TRY(tmp.alloc(ctx, (tab_words + pt_words + idx_words + part_words) * 4));
+  uint32_t* tab = u32(tmp.get());
   uint32_t* pts = tab + tab_words;
   uint32_t* idx = pts + pt_words;
   uint32_t* part = idx + idx_words;
@@ -464,7 +276,7 @@ const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, cons
     if (np == 1) hipLaunchKernelGGL(eval_rows_kernel<1>, dim3(gb, ng), dim3(256), 0, ctx->stream, part, u32(coeffs), idx, tab, po2, rl_log);
     else hipLaunchKernelGGL(eval_rows_kernel<2>, dim3(gb, ng), dim3(256), 0, ctx->stream, part, u32(coeffs), idx, tab, po2, rl_log);
     hipLaunchKernelGGL(eval_reduce_kernel, dim3((ng * np + 63) / 64), dim3(64), 0, ctx->stream, u32(out), part, idx + ng, gb, ng * np);
-    R0H_TRY(launch_ok("batch_evaluate_any kernels"));  // scratch reuse by the next group is ordered by the stream
+    R0H_TRY(launch_ok("batch_evaluate_any kernels"));  // reuse of the block by the next group is ordered by the stream
   }
   return nullptr;
   R0H_GUARD_END
@@ -501,11 +313,12 @@ const char* r0h_mix_poly_coeffs(r0h_ctx* ctx, r0h_buf* combos, const uint32_t mi
   params.insert(params.end(), ids.begin(), ids.end());
   for (uint32_t k = 0; k < input_count; k++)
     for (int q = 0; q < 4; q++) params.push_back(pw[order[k]].e[q]);
-  R0H_TRY(ensure_scratch(ctx, params.size() * 4));
-  R0H_TRY(stage_h2d(ctx, ctx->scratch, params.data(), params.size() * 4));
+  DevBuf d_params;
+  R0H_TRY(d_params.alloc(ctx, params.size() * 4));
+  R0H_TRY(stage_h2d(ctx, d_params->ptr, params.data(), params.size() * 4));
   uint32_t n = 1u << po2, threads = n < 256 ? n : 256;
   KScope ks(ctx, "mix_poly_kernel", 4.0 * input_count * (double)n + 32.0 * n_groups * (double)n);
-  hipLaunchKernelGGL(mix_poly_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(combos), u32(input), (const uint32_t*)ctx->scratch, n_groups, po2);
+  hipLaunchKernelGGL(mix_poly_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(combos), u32(input), u32(d_params.get()), n_groups, po2);
   return launch_ok("mix_poly_kernel");
   R0H_GUARD_END
 }
@@ -605,8 +418,9 @@ const char* r0h_scatter_slices(r0h_ctx* ctx, r0h_buf* into, const uint32_t* inde
     R0H_REQUIRE(values[k] < P, "r0h_scatter_slices: value %u is not a canonical field word", k);
   }
   const size_t bytes = (size_t)(end - begin) * 4;
-  R0H_TRY(ensure_scratch(ctx, 2 * bytes));
-  uint32_t* d_off = (uint32_t*)ctx->scratch;
+  DevBuf tmp;  // [offsets][values]
+  R0H_TRY(tmp.alloc(ctx, 2 * bytes));
+  uint32_t* d_off = u32(tmp.get());
   uint32_t* d_val = d_off + (end - begin);
   R0H_TRY(stage_h2d(ctx, d_off, offsets + begin, bytes));
   R0H_TRY(stage_h2d(ctx, d_val, values + begin, bytes));
@@ -625,94 +439,3 @@ const char* r0h_fri_fold(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* in, const ui
 }
 
 }  // extern "C"
-template <bool SUM>
-static const char* prefix_scan(r0h_ctx* ctx, r0h_buf* io, uint32_t n, const char* what) {
-  R0H_REQUIRE(ctx && io, "%s: NULL argument", what);
-  R0H_REQUIRE(n && (n & (n - 1)) == 0, "%s: n %u is not a power of two", what, n);
-  R0H_REQUIRE((size_t)n * 16 <= io->bytes, "%s: n %u exceeds the buffer", what, n);
-  const ScanGeom g = scan_geom(n);
-  R0H_TRY(ensure_scratch(ctx, (size_t)(g.n_chunks + 1) * 16));
-  uint32_t* cp = (uint32_t*)ctx->scratch;
-  hipLaunchKernelGGL(prefix_chunk_prod_kernel<SUM>, dim3(g.n_chunks), dim3(g.threads), g.threads * 16, ctx->stream, cp, u32(io), g.E);
-  hipLaunchKernelGGL(prefix_chunk_scan_kernel<SUM>, dim3(1), dim3(256), 0, ctx->stream, cp, g.n_chunks);
-  hipLaunchKernelGGL(prefix_apply_kernel<SUM>, dim3(g.n_chunks), dim3(g.threads), g.threads * 16, ctx->stream, u32(io), cp, g.E);
-  return launch_ok(what);
-}
-extern "C" {
-const char* r0h_prefix_products(r0h_ctx* ctx, r0h_buf* io, uint32_t n) { return prefix_scan<false>(ctx, io, n, "r0h_prefix_products"); }
-// the additive counterpart (the running sums of a log-derivative argument): io[i] = sum_{j <= i} io[j] over extension elements
-const char* r0h_prefix_sums(r0h_ctx* ctx, r0h_buf* io, uint32_t n) { return prefix_scan<true>(ctx, io, n, "r0h_prefix_sums"); }
-
-const char* r0h_poly_divide(r0h_ctx* ctx, r0h_buf* poly, uint32_t n, const uint32_t z[4], uint32_t remainder[4]) {
-  R0H_REQUIRE(ctx && poly && z, "r0h_poly_divide: NULL argument");
-  R0H_REQUIRE(canonical4(z), "r0h_poly_divide: z words must be canonical (< p)");
-  R0H_REQUIRE(n && (n & (n - 1)) == 0, "r0h_poly_divide: n %u is not a power of two", n);
-  R0H_REQUIRE((size_t)n * 16 <= poly->bytes, "r0h_poly_divide: n %u exceeds the buffer", n);
-  const uint32_t idx = 0;
-  return r0h::poly_divide_batch(ctx, poly, n, &idx, z, 1, remainder);
-}
-
-}  // extern "C"
-
-namespace r0h {
-const char* unpack_ext_columns(r0h_ctx* ctx, uint32_t* cols, const uint32_t* packed, uint32_t po2) {
-  const uint32_t n = 1u << po2, threads = n < 256 ? n : 256;
-  hipLaunchKernelGGL(ext_unpack_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, cols, packed, po2);
-  return launch_ok("ext_unpack_kernel");
-}
-
-// polys: a buffer of n-coefficient extension polynomials (AoS, natural order); job j divides polynomial poly_idx[j] in place by
-// (x - points[4j..4j+4)).  Jobs on the same polynomial are applied in the order given.  remainders_host (4 words per job, may be
-// NULL) is filled by ONE blocking copy after everything has been enqueued.
-const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* points, uint32_t n_jobs, uint32_t* remainders_host) {
-  R0H_GUARD_BEGIN
-  if (!n_jobs) return nullptr;
-  const ScanGeom g = scan_geom(n);
-  const size_t n_polys = polys->bytes / ((size_t)n * 16);
-  // pass k holds the k-th job of every polynomial: within a pass the jobs touch different polynomials and run side by side
-  std::vector<std::vector<uint32_t>> passes;
-  {
-    std::map<uint32_t, uint32_t> seen;
-    for (uint32_t j = 0; j < n_jobs; j++) {
-      R0H_REQUIRE(poly_idx[j] < n_polys, "poly_divide: polynomial %u outside a buffer of %zu", poly_idx[j], n_polys);
-      const uint32_t k = seen[poly_idx[j]]++;
-      if (passes.size() <= k) passes.emplace_back();
-      passes[k].push_back(j);
-    }
-  }
-  std::vector<DivJob> jobs;  // in launch order; slot = the job's index as given (remainders come back in the caller's order)
-  for (const auto& pass : passes)
-    for (uint32_t j : pass) {
-      DivJob d;
-      d.pw.z = host_fp4(points + 4 * (size_t)j);
-      d.pw.zE = fp4_pow(d.pw.z, g.E);
-      d.pw.zChunk = fp4_pow(d.pw.z, g.chunk);
-      d.poly = poly_idx[j]; d.slot = j; d.pad0 = d.pad1 = 0;
-      jobs.push_back(d);
-    }
-  const size_t cv_bytes = (size_t)n_jobs * (g.n_chunks + 1) * 16, job_bytes = jobs.size() * sizeof(DivJob), rem_bytes = (size_t)n_jobs * 16;
-  R0H_TRY(ensure_scratch(ctx, cv_bytes + job_bytes + rem_bytes));
-  uint32_t* cv = (uint32_t*)ctx->scratch;
-  DivJob* d_jobs = (DivJob*)((char*)ctx->scratch + cv_bytes);
-  uint32_t* d_rem = (uint32_t*)((char*)ctx->scratch + cv_bytes + job_bytes);
-  R0H_TRY(stage_h2d(ctx, d_jobs, jobs.data(), job_bytes));
-  KScope ks(ctx, "poly_divide", 48.0 * n * n_jobs);
-  size_t first = 0;
-  for (const auto& pass : passes) {
-    const uint32_t nj = (uint32_t)pass.size();
-    hipLaunchKernelGGL(divide_chunk_sum_kernel, dim3(g.n_chunks, nj), dim3(g.threads), g.threads * 16, ctx->stream, cv, u32(polys), d_jobs + first, g.E, n, g.n_chunks);
-    hipLaunchKernelGGL(divide_chunk_carry_kernel, dim3(nj), dim3(256), 0, ctx->stream, cv, d_jobs + first, g.n_chunks);
-    hipLaunchKernelGGL(divide_apply_kernel, dim3(g.n_chunks, nj), dim3(g.threads), g.threads * 16, ctx->stream, u32(polys), cv, d_jobs + first, g.E, n, g.n_chunks);
-    first += nj;
-  }
-  R0H_TRY(launch_ok("poly_divide kernels"));
-  if (remainders_host) {
-    hipLaunchKernelGGL(divide_remainders_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, ctx->stream, d_rem, cv, n_jobs, g.n_chunks);
-    R0H_TRY(launch_ok("divide_remainders_kernel"));
-    R0H_TRY_HIP(hipMemcpyAsync(remainders_host, d_rem, rem_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  return nullptr;
-  R0H_GUARD_END
-}
-}  // namespace r0h

@@ -1,7 +1,8 @@
 // BabyBear (p = 15*2^27 + 1) in Montgomery form and its quartic extension, for host and gfx950 device code.
 // Replaces risc0-sys 1.5.0 `fp.h` / `fpext.h` and risc0-zkp 3.0.4 `field/baby_bear.rs`.
 // 31-bit modular integer work on the VALU: one v_mad_u64_u32 for a*b, one v_mul_lo_u32 for the Montgomery
-// quotient, one v_mad_u64_u32 for the reduction, then a branch-free conditional subtract (v_sub + v_min).
+// quotient, one v_mad_u64_u32 for the reduction, then a branch-free conditional subtract through the carry flag
+// (v_sub_co + v_cndmask: reduce1).
 #pragma once
 #include <stdint.h>
 #if defined(__HIPCC__)

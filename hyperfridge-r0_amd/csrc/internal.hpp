@@ -113,8 +113,6 @@ struct r0h_ctx {
   r0h::P2Consts p2_host;
   bool p2_tight = false;        // the tight dot-product schedule covers p2_host (fill_p2): which Poseidon2 kernels with_suite launches
   int hashfn = 0;              // r0h::HashFn: the suite hash_rows / hash_fold / the sequencer follow (r0h_ctx_set_hashfn)
-  void* scratch = nullptr;      // small device scratch for scans / partial sums
-  size_t scratch_bytes = 0;
   void* pinned = nullptr;       // pinned host staging ring for small parameter uploads
   size_t pinned_bytes = 0, pinned_off = 0;
   std::multimap<size_t, void*> pool;  // cached device allocations of the sequencer, by size (stream-ordered reuse)
@@ -185,7 +183,6 @@ struct KScope {
     t->used += 2;
   }
 };
-const char* ensure_scratch(r0h_ctx* ctx, size_t bytes);
 // stream-ordered upload of a small host array through the pinned ring (the caller's memory may die on return)
 const char* stage_h2d(r0h_ctx* ctx, void* dst_device, const void* src_host, size_t bytes);
 // device buffer from the context's pool: no hipMalloc / hipFree (and no implicit device sync) in steady state

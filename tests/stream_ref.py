@@ -1,5 +1,5 @@
-"""Plain-Python reference of the DEEP-step streams of eltwise.hip: Python ints, Fp4 = Fp[x]/(x^4 - 11), nothing shared with the
-device code or the oracle but the definitions.  Words go in and come out in Montgomery form (a word w stands for w / 2^32 mod p),
+"""Plain-Python reference of the DEEP-step streams of eltwise.hip and of the division of scan.hip: Python ints,
+Fp4 = Fp[x]/(x^4 - 11), nothing shared with the device code or the oracle but the definitions.  Words go in and come out in Montgomery form (a word w stands for w / 2^32 mod p),
 as numpy uint32 arrays laid out as the C ABI lays them out (include/r0hip.h, oracle/orc.h):
   evaluate     natural-order base-field coefficients, one extension point
   mix_poly     combos: extension elements, array of structs [combo][i]; input: base-field columns [c][i]

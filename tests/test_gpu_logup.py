@@ -97,7 +97,7 @@ def test_device_accumulation_without_tables_at_every_scan_shape(hal, orc, seed, 
 
 @pytest.mark.parametrize("po2", [22, 24])
 def test_device_accumulation_beyond_256_chunks(hal, orc, po2):
-    """more than 256 chunks: every thread of prefix_chunk_scan_kernel takes 4 (2^22) or 16 (2^24) of them"""
+    """more than 256 chunks: every thread of scan_link_kernel takes 4 (2^22) or 16 (2^24) of them"""
     check_accum(hal, orc, SMALL, po2, reference=po2 == 22)
 
 

@@ -1,6 +1,6 @@
-"""The DEEP-step streams of eltwise.hip where the whole-proof tests cannot name a kernel: the running sums of the evaluation kernel in
-their steady state, the host grouping of the evaluation requests, tables narrower than a row, and the mix, fold, division and small
-element-wise kernels at corner operands and at every launch geometry.  Bit-exact against the CPU oracle, and against the plain-Python
+"""The DEEP-step streams of eltwise.hip and the division of scan.hip where the whole-proof tests cannot name a kernel: the running sums
+of the evaluation kernel in their steady state, the host grouping of the evaluation requests, tables narrower than a row, and the mix,
+fold, division and small element-wise kernels at corner operands and at every launch geometry.  Bit-exact against the CPU oracle, and against the plain-Python
 reference (stream_ref.py) as well wherever n <= 2^10.  Operand families and points: field_words.py."""
 import numpy as np
 import pytest
@@ -224,7 +224,7 @@ def test_fri_fold_tails_and_corner_mixes(hal, orc, n_out, kind):
 
 # ------------------------------------------------------------------ f. poly_divide
 # one element; two; fewer threads than a block; one block of one element per thread; two per thread; one full chunk; two chunks; 256
-# chunks (one per thread of the carry kernel); 512 (two per thread)
+# chunks (one per thread of the link kernel); 512 (two per thread)
 DIVIDE_SIZES = [1, 2, 128, 256, 512, 4096, 8192, 1 << 20, 1 << 21]
 
 
@@ -248,6 +248,27 @@ def test_poly_divide_at_corner_points_and_every_geometry(hal, orc, n, kind):
         if kz == "zero":  # division by x: the coefficients move down by one, the constant term is left over
             assert np.array_equal(q[:-4], v[4:]) and not q[-4:].any() and np.array_equal(rem, v[:4])
     buf.free()
+
+
+@pytest.mark.parametrize("kind", ["random", "top"])
+def test_three_scans_back_to_back_share_a_pooled_block(hal, orc, kind):
+    """At n = 8192 (two chunks) the temporaries of a prefix scan (48 bytes) and of a one-job division (128) fall into one size class of
+    the context's pool, so sums, products and division enqueued with nothing read in between take the same block one after the other:
+    only the stream orders them."""
+    n = 8192
+    rng = _rng(75, kind)
+    a, b, c = (family(rng, 4 * n, kind) for _ in range(3))
+    z = point(rng, "random")
+    ab, bb, cb = hal.copy_from(a), hal.copy_from(b), hal.copy_from(c)
+    hal.prefix_sums(ab, n)
+    hal.prefix_products(bb, n)
+    rem = hal.poly_divide(cb, n, z)
+    got_a, got_b, got_c = ab.to_host(), bb.to_host(), cb.to_host()
+    _free(ab, bb, cb)
+    assert np.array_equal(got_a, (np.cumsum(a.reshape(n, 4).astype(np.int64), axis=0) % P).astype(np.uint32).reshape(-1))
+    assert np.array_equal(got_b, orc.prefix_products(b, n))
+    want_q, want_rem = orc.poly_divide(c, n, z)
+    assert np.array_equal(got_c, want_q) and np.array_equal(rem, want_rem)
 
 
 # ------------------------------------------------------------------ g. the small helpers
