@@ -76,6 +76,17 @@ _SIGNATURES = {
     "r0h_gather_sample": [_vp, _vp, _vp, _u32, _u32, _u32],
     "r0h_scatter": [_vp, _vp, _vp, _vp, _vp, _u32],
     "r0h_fri_fold": [_vp, _vp, _vp, _vp, _u32],
+    "r0h_fri_fold_buf": [_vp, _vp, _vp, _vp, _sz, _u32],
+    "r0h_iop_new": [_vp, _pp],
+    "r0h_iop_free": [_vp],
+    "r0h_iop_set_state": [_vp, _vp, _sz],
+    "r0h_iop_state": [_vp, _vp, _sz, _c.POINTER(_sz)],
+    "r0h_iop_commit": [_vp, _vp, _sz],
+    "r0h_iop_commit_elems": [_vp, _vp, _sz, _sz],
+    "r0h_iop_draw_ext": [_vp, _vp, _sz, _sz],
+    "r0h_iop_draw_queries": [_vp, _u32, _vp, _u32, _u32, _vp, _sz],
+    "r0h_ctx_set_device_transcript": [_vp, _c.c_int],
+    "r0h_ctx_blocking_waits": [_vp, _c.POINTER(_u64)],
     "r0h_batch_evaluate_any_buf": [_vp, _vp, _u32, _vp, _vp, _u32, _vp],
     "r0h_mix_poly_coeffs_buf": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32],
     "r0h_scatter_slices": [_vp, _vp, _vp, _u32, _vp, _vp, _u32],
@@ -361,6 +372,52 @@ class Buf:
     def free(self):
         if self.handle:
             _check(lib().r0h_buf_free(self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Iop:
+    """The Fiat-Shamir generator of the context's hash suite over a state in device memory (r0h_iop_*): commits read their digests
+    from device buffers, draws write their challenges to device buffers, all in stream order; only set_state / state block.  Offsets
+    count words."""
+
+    def __init__(self, hal):
+        self.hal, self.handle = hal, _vp()
+        _check(lib().r0h_iop_new(hal.ctx, ctypes.byref(self.handle)))
+
+    def set_state(self, words):
+        """the generator's words as the host holds them, then pool_used: 25 words under Poseidon2, 17 under SHA-256"""
+        a, p = _u32arr(words)
+        _check(lib().r0h_iop_set_state(self.handle, p, a.size))
+
+    def state(self):
+        out = np.zeros(32, dtype=np.uint32)
+        n = _sz(0)
+        _check(lib().r0h_iop_state(self.handle, out.ctypes.data_as(_vp), out.size, ctypes.byref(n)))
+        return out[:n.value].copy()
+
+    def commit(self, buf, word_offset=0):
+        _check(lib().r0h_iop_commit(self.handle, buf.handle, word_offset))
+
+    def commit_elems(self, buf, word_offset, n):
+        _check(lib().r0h_iop_commit_elems(self.handle, buf.handle, word_offset, n))
+
+    def draw_ext(self, out, word_offset=0, count=1):
+        _check(lib().r0h_iop_draw_ext(self.handle, out.handle, word_offset, count))
+
+    def draw_queries(self, domain, tree_rows, n_queries, idx_out, word_offset=0):
+        """the sequencer's query loop: the table idx_out[word_offset + t * n_queries + q]"""
+        r, pr = _u32arr(tree_rows)
+        _check(lib().r0h_iop_draw_queries(self.handle, domain, pr, r.size, n_queries, idx_out.handle, word_offset))
+
+    def free(self):
+        if self.handle:
+            _check(lib().r0h_iop_free(self.handle))
             self.handle = None
 
     def __del__(self):
@@ -1614,6 +1671,14 @@ class Hal:
         m, pm = _u32arr(mix)
         _check(lib().r0h_fri_fold(self.ctx, out.handle, inp.handle, pm, n_out))
 
+    def fri_fold_buf(self, out, inp, mix_buf, mix_word_offset, n_out):
+        """fri_fold with the mix read from four words of a device buffer (r0h_fri_fold_buf)"""
+        _check(lib().r0h_fri_fold_buf(self.ctx, out.handle, inp.handle, mix_buf.handle, mix_word_offset, n_out))
+
+    def iop(self):
+        """a fresh transcript generator of this context's hash suite on the device (r0h_iop_new)"""
+        return Iop(self)
+
     def prefix_products(self, io, n):
         _check(lib().r0h_prefix_products(self.ctx, io.handle, n))
 
@@ -1795,6 +1860,17 @@ class Hal:
         """prove_segment, proof_finish and the sessions of this context check every segment's witness before its ACCUM group is
         committed and raise, naming the first violated term, instead of returning a seal that cannot verify (r0h_ctx_set_check_witness)"""
         _check(lib().r0h_ctx_set_check_witness(self.ctx, 1 if on else 0))
+
+    def set_device_transcript(self, on=True):
+        """proof_finish -- and so prove_segment, sessions and recursion on this context -- runs its FRI commitments and queries on a
+        transcript on the device, with one read-back for both steps (r0h_ctx_set_device_transcript); off by default, same seals"""
+        _check(lib().r0h_ctx_set_device_transcript(self.ctx, 1 if on else 0))
+
+    def blocking_waits(self):
+        """how many times the library has waited for this context's stream so far (r0h_ctx_blocking_waits)"""
+        n = _u64(0)
+        _check(lib().r0h_ctx_blocking_waits(self.ctx, ctypes.byref(n)))
+        return n.value
 
     def prove_segment(self, circuit, po2, code, data, glob, seal_capacity_words=1 << 20):
         """code: the CODE witness columns (Buf) or their commitment (CodeCommit, r0h_prove_segment_committed) -- same seal."""

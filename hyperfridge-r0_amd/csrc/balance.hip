@@ -443,7 +443,7 @@ const char* session_table_grow(r0h_session_balance* sb, uint64_t tuples) {
   R0H_TRY(scan_grid(ctx, from_slots, SES_THREADS, &grid));
   hipLaunchKernelGGL(session_rehash_kernel, dim3(grid), dim3(SES_THREADS), 0, ctx->stream, (SessionSlot*)bigger->ptr, bits, t->ctr(), t->slots(), from_slots);
   R0H_TRY(launch_ok("session_rehash_kernel"));
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the old table goes back to the pool
+  R0H_TRY_HIP(ctx_wait(ctx));  // the old table goes back to the pool
   t->table = std::move(bigger);
   t->slot_bits = bits;
   sb->grows++;

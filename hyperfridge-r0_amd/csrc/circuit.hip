@@ -136,7 +136,7 @@ const char* r0h_circuit_free(r0h_circuit* c) {
   if (!c) return nullptr;
   r0h_ctx* ctx = c->ctx;
   (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
+  (void)ctx_wait(ctx);
   ctx_code_commits_drop(ctx, c);  // the commitments of its CODE group go with the circuit
   CircuitUnload()(c);
   ctx_release(ctx);
@@ -265,7 +265,7 @@ static const char* witgen_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2,
     for (uint32_t k = 0; k < c->n_global; k++)
       R0H_TRY_HIP(hipMemcpyAsync(global_out + k, u32(data) + ((size_t)c->global_cols[k] << po2), 4, hipMemcpyDeviceToHost, ctx->stream));
   }
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   return nullptr;
   R0H_GUARD_END
 }
@@ -395,7 +395,7 @@ const char* r0h_check_witness(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, 
     }
   }
   R0H_TRY_HIP(hipMemcpyAsync(table.data(), d_table, table.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   size_t found = 0;
   for (uint32_t t = 0; t < n_terms; t++) {
     if (!table[2 * t]) continue;

@@ -27,12 +27,12 @@ const char* stage_h2d(r0h_ctx* ctx, void* dst, const void* src, size_t bytes) {
   if (!bytes) return nullptr;
   if (bytes > ctx->pinned_bytes / 2) {  // too large for the ring: plain blocking copy
     R0H_TRY_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    R0H_TRY_HIP(ctx_wait(ctx));
     return nullptr;
   }
   size_t need = (bytes + 255) & ~(size_t)255;
   if (ctx->pinned_off + need > ctx->pinned_bytes) {
-    R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // every earlier ring slot has been consumed
+    R0H_TRY_HIP(ctx_wait(ctx));  // every earlier ring slot has been consumed
     ctx->pinned_off = 0;
   }
   char* slot = (char*)ctx->pinned + ctx->pinned_off;
@@ -56,7 +56,7 @@ const char* buf_alloc_pooled(r0h_ctx* ctx, size_t bytes, r0h_buf** out) {
     if (e != hipSuccess && !ctx->pool.empty()) {
       // out of memory with blocks of other sizes parked: give them back and try once more
       (void)hipGetLastError();
-      (void)hipStreamSynchronize(ctx->stream);
+      (void)ctx_wait(ctx);
       for (auto& kv : ctx->pool) (void)hipFree(kv.second);
       ctx->pool.clear();
       ctx->pool_bytes = 0;
@@ -99,7 +99,7 @@ void profile_phase(r0h_ctx* ctx, const char* name) {
 }
 const char* profile_close(r0h_ctx* ctx) {
   profile_phase(ctx, "end");
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   Profile& p = ctx->prof;
   std::vector<float> ms(p.names.size() - 1, 0.f);
   for (size_t i = 0; i < ms.size(); i++) (void)hipEventElapsedTime(&ms[i], p.events[i], p.events[i + 1]);
@@ -119,12 +119,13 @@ const char* ctx_helper(r0h_ctx* ctx, size_t k, r0h_ctx** out) {
   h->check_witness = ctx->check_witness;
   h->check_balance = ctx->check_balance;
   h->check_session = ctx->check_session;
+  h->device_transcript = ctx->device_transcript;
   h->hashfn = ctx->hashfn;
   h->p2_tight = ctx->p2_tight;  // goes with the table below
   if (memcmp(&h->p2_host, &ctx->p2_host, sizeof(P2Consts)) != 0) {  // r0h_poseidon2_set_consts on the owner since the helper was made
     h->p2_host = ctx->p2_host;
     R0H_TRY_HIP(hipSetDevice(h->device));
-    R0H_TRY_HIP(hipStreamSynchronize(h->stream));
+    R0H_TRY_HIP(ctx_wait(h));
     R0H_TRY_HIP(hipMemcpy(h->p2, &h->p2_host, sizeof(P2Consts), hipMemcpyHostToDevice));
   }
   *out = h;
@@ -136,7 +137,7 @@ void ctx_release(r0h_ctx* ctx) {
   for (r0h_ctx* h : ctx->helpers) r0h_ctx_destroy(h);
   ctx->helpers.clear();
   (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
+  (void)ctx_wait(ctx);
   for (int d = 0; d < 2; d++) { (void)hipFree(ctx->tw_lo[d]); (void)hipFree(ctx->tw_hi[d]); (void)hipFree(ctx->tw12[d]); }
   for (int d = 0; d < 2; d++) { (void)hipFree(ctx->twb_lo[d]); (void)hipFree(ctx->twb_hi[d]); }
   (void)hipFree(ctx->pow3_lo); (void)hipFree(ctx->pow3_hi); (void)hipFree(ctx->pow3_top); (void)hipFree(ctx->p2);
@@ -203,7 +204,7 @@ const char* r0h_ctx_create(int device, r0h_ctx** out) {
 const char* r0h_ctx_destroy(r0h_ctx* ctx) {
   if (!ctx) return nullptr;
   (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
+  (void)ctx_wait(ctx);
   ctx_code_commits_drop(ctx, nullptr);  // cached CODE commitments hold references of their own: they go first, their buffers while the device state is whole
   ctx_release(ctx);  // buffers and circuits still alive keep the device state until they are freed
   return nullptr;
@@ -211,7 +212,19 @@ const char* r0h_ctx_destroy(r0h_ctx* ctx) {
 
 const char* r0h_sync(r0h_ctx* ctx) {
   R0H_REQUIRE(ctx, "r0h_sync: ctx is NULL");
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
+  return nullptr;
+}
+
+const char* r0h_ctx_set_device_transcript(r0h_ctx* ctx, int on) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_device_transcript: ctx is NULL");
+  ctx->device_transcript = on != 0;
+  for (r0h_ctx* h : ctx->helpers) h->device_transcript = ctx->device_transcript;
+  return nullptr;
+}
+const char* r0h_ctx_blocking_waits(const r0h_ctx* ctx, uint64_t* count_out) {
+  R0H_REQUIRE(ctx && count_out, "r0h_ctx_blocking_waits: NULL argument");
+  *count_out = ctx->blocking_waits.load();
   return nullptr;
 }
 
@@ -220,7 +233,7 @@ const char* r0h_poseidon2_set_consts(r0h_ctx* ctx, const uint32_t* rc, const uin
   for (int i = 0; i < P2_CELLS * P2_ROUNDS; i++) R0H_REQUIRE(rc[i] < P, "round constant %d not canonical", i);
   for (int i = 0; i < P2_CELLS; i++) R0H_REQUIRE(diag_m1[i] < P, "diagonal word %d not canonical", i);
   ctx->p2_tight = fill_p2(ctx->p2_host, rc, diag_m1);
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   R0H_TRY_HIP(hipMemcpy(ctx->p2, &ctx->p2_host, sizeof(P2Consts), hipMemcpyHostToDevice));
   return nullptr;
 }
@@ -281,7 +294,7 @@ const char* r0h_buf_free(r0h_buf* b) {
       // stream-ordered reuse: whoever takes this block next enqueues behind everything that used it
       const size_t sz = b->bytes ? (b->bytes + 255) & ~(size_t)255 : 256;
       if (b->ctx->pool_bytes + sz > POOL_LIMIT) {
-        (void)hipStreamSynchronize(b->ctx->stream);
+        (void)ctx_wait(b->ctx);
         (void)hipFree(b->ptr);
       } else {
         b->ctx->pool.emplace(sz, b->ptr);
@@ -289,7 +302,7 @@ const char* r0h_buf_free(r0h_buf* b) {
       }
     } else if (b->owned && b->ptr) {
       (void)hipSetDevice(b->ctx->device);  // best effort before the free: a failure here shows up as the free's error
-      (void)hipStreamSynchronize(b->ctx->stream);
+      (void)ctx_wait(b->ctx);
       hipError_t e = hipFree(b->ptr);
       if (e != hipSuccess) return make_error("r0h_buf_free: %s", hipGetErrorString(e));
     }
@@ -306,7 +319,7 @@ const char* r0h_buf_h2d(r0h_ctx* ctx, r0h_buf* dst, size_t off, const void* src,
   R0H_REQUIRE(off + bytes <= dst->bytes, "r0h_buf_h2d: [%zu, +%zu) outside a %zu-byte buffer", off, bytes, dst->bytes);
   if (!bytes) return nullptr;
   R0H_TRY_HIP(hipMemcpyAsync((char*)dst->ptr + off, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // src is pageable caller memory: do not outlive the call
+  R0H_TRY_HIP(ctx_wait(ctx));  // src is pageable caller memory: do not outlive the call
   return nullptr;
 }
 
@@ -315,7 +328,7 @@ const char* r0h_buf_d2h(r0h_ctx* ctx, const r0h_buf* src, size_t off, void* dst,
   R0H_REQUIRE(off + bytes <= src->bytes, "r0h_buf_d2h: [%zu, +%zu) outside a %zu-byte buffer", off, bytes, src->bytes);
   if (!bytes) return nullptr;
   R0H_TRY_HIP(hipMemcpyAsync(dst, (const char*)src->ptr + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   return nullptr;
 }
 
@@ -354,7 +367,7 @@ const char* r0h_last_session_tree_tops(r0h_ctx* ctx, uint64_t out[3]) {
 }
 const char* r0h_kernel_timing(r0h_ctx* ctx, int enable) {
   R0H_REQUIRE(ctx, "r0h_kernel_timing: ctx is NULL");
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   ctx->ktime_on = enable != 0;
   for (auto& kv : ctx->ktimers) { kv.second.used = 0; kv.second.alg_bytes = 0; }
   return nullptr;
@@ -363,7 +376,7 @@ const char* r0h_kernel_timing(r0h_ctx* ctx, int enable) {
 const char* r0h_kernel_stats(r0h_ctx* ctx, char* json_out, size_t capacity) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && json_out && capacity, "r0h_kernel_stats: NULL argument");
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   std::string js = "{";
   bool first = true;
   for (auto& kv : ctx->ktimers) {

@@ -183,9 +183,7 @@ __global__ void scatter_kernel(uint32_t* into, const uint32_t* offsets, const ui
 }
 
 // ------------------------------------------------------------------ fri_fold
-__global__ void fri_fold_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, Fp4 mix, uint32_t n_out) {
-  uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n_out) return;
+__device__ __forceinline__ void fri_fold_at(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, const Fp4& mix, uint32_t n_out, uint32_t idx) {
   const size_t n_in = (size_t)n_out * R0H_FRI_FOLD;
   Fp4 tot = fp4_zero(), cur = fp4_one();
 #pragma unroll
@@ -197,6 +195,17 @@ __global__ void fri_fold_kernel(uint32_t* __restrict__ out, const uint32_t* __re
   }
 #pragma unroll
   for (int k = 0; k < 4; k++) out[(size_t)k * n_out + idx] = tot.e[k];
+}
+__global__ void fri_fold_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, Fp4 mix, uint32_t n_out) {
+  uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_out) return;
+  fri_fold_at(out, in, mix, n_out, idx);
+}
+// the same with the mix read from device memory (four words a transcript on the device drew: r0h_iop_draw_ext)
+__global__ void fri_fold_buf_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, const uint32_t* __restrict__ mix, uint32_t n_out) {
+  uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_out) return;
+  fri_fold_at(out, in, Fp4{{mix[0], mix[1], mix[2], mix[3]}}, n_out, idx);
 }
 
 static Fp4 host_fp4(const uint32_t v[4]) { return Fp4{{v[0], v[1], v[2], v[3]}}; }
@@ -436,6 +445,17 @@ const char* r0h_fri_fold(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* in, const ui
   if (!n_out) return nullptr;
   hipLaunchKernelGGL(fri_fold_kernel, dim3((n_out + 255) / 256), dim3(256), 0, ctx->stream, u32(out), u32(in), host_fp4(mix), n_out);
   return launch_ok("fri_fold_kernel");
+}
+
+const char* r0h_fri_fold_buf(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* in, const r0h_buf* mix_buf, size_t mix_word_offset, uint32_t n_out) {
+  R0H_REQUIRE(ctx && out && in && mix_buf, "r0h_fri_fold_buf: NULL argument");
+  R0H_REQUIRE(mix_word_offset <= mix_buf->bytes / 4 && 4 <= mix_buf->bytes / 4 - mix_word_offset, "r0h_fri_fold_buf: the mix at words [%zu, +4) ends beyond a buffer of %zu words",
+              mix_word_offset, mix_buf->bytes / 4);
+  R0H_REQUIRE((size_t)n_out * 16 <= out->bytes && (size_t)n_out * 16 * R0H_FRI_FOLD <= in->bytes, "r0h_fri_fold_buf: n_out %u exceeds a buffer", n_out);
+  if (!n_out) return nullptr;
+  KScope ks(ctx, "fri_fold_buf_kernel", (double)n_out * 16 * (R0H_FRI_FOLD + 1));
+  hipLaunchKernelGGL(fri_fold_buf_kernel, dim3((n_out + 255) / 256), dim3(256), 0, ctx->stream, u32(out), u32(in), u32(mix_buf) + mix_word_offset, n_out);
+  return launch_ok("fri_fold_buf_kernel");
 }
 
 }  // extern "C"

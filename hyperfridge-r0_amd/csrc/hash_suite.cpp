@@ -46,6 +46,11 @@ struct P2Rng : SuiteRng {
     for (int i = 0; i < 3; i++) { uint32_t nv = dec(elem()); if (val == 0) val = nv; }
     return val & (uint32_t)(((uint64_t)1 << n) - 1);
   }
+  size_t state(uint32_t* out) const override {
+    memcpy(out, cells, sizeof cells);
+    out[P2_CELLS] = pool_used;
+    return P2_CELLS + 1;
+  }
 };
 struct P2Suite : HashSuite {
   const P2Consts* k;
@@ -89,6 +94,12 @@ struct ShaRng : SuiteRng {
     return enc((uint32_t)val);
   }
   uint32_t bits(uint32_t n) override { return random_u32() & (uint32_t)(((uint64_t)1 << n) - 1); }
+  size_t state(uint32_t* out) const override {
+    memcpy(out, pool0, 32);
+    memcpy(out + 8, pool1, 32);
+    out[16] = pool_used;
+    return 17;
+  }
 };
 struct ShaSuite : HashSuite {
   int fn() const override { return HASH_SHA256; }

@@ -132,6 +132,8 @@ struct r0h_ctx {
   bool check_balance = false;     // r0h_ctx_set_check_balance: the sequencer runs r0h_logup_check_balance on every segment before it commits DATA
   bool check_session = false;     // r0h_ctx_set_check_session: r0h_session_finish checks the session balance of all segments before it derives the challenge
   uint64_t balance_stats[3] = {0, 0, 0};  // the last r0h_logup_check_balance: tuples, inserts that reached the global table, its slots
+  bool device_transcript = false;  // r0h_ctx_set_device_transcript: fri_commit and queries run on the device generator (prover.hip), one read-back for both
+  std::atomic<uint64_t> blocking_waits{0};  // r0h_ctx_blocking_waits: the times the library has waited for this context's stream (ctx_wait)
   bool ktime_on = false;
   std::map<std::string, r0h::KTimer> ktimers;
   // The committed CODE groups of the circuits loaded on this context, by (circuit, po2, hash suite): CODE depends on nothing else, so
@@ -183,6 +185,11 @@ struct KScope {
     t->used += 2;
   }
 };
+// hipStreamSynchronize on the context's stream, counted: every place the library blocks on a context goes through here
+inline hipError_t ctx_wait(r0h_ctx* ctx) {
+  ctx->blocking_waits++;
+  return hipStreamSynchronize(ctx->stream);
+}
 // stream-ordered upload of a small host array through the pinned ring (the caller's memory may die on return)
 const char* stage_h2d(r0h_ctx* ctx, void* dst_device, const void* src_host, size_t bytes);
 // device buffer from the context's pool: no hipMalloc / hipFree (and no implicit device sync) in steady state
@@ -289,8 +296,12 @@ struct SuiteRng {
   virtual void mix(const uint32_t digest[8]) = 0;
   virtual uint32_t elem() = 0;            // a field element, Montgomery form
   virtual uint32_t bits(uint32_t n) = 0;  // an n-bit query index
+  // the generator's words as the device form holds them (r0h_iop_set_state): Poseidon2 the 24 cells and pool_used, SHA-256 pool0,
+  // pool1 and pool_used; at most SUITE_RNG_MAX_WORDS of them
+  virtual size_t state(uint32_t* words_out) const = 0;
   Fp4 ext() { Fp4 r; for (int i = 0; i < 4; i++) r.e[i] = elem(); return r; }
 };
+constexpr size_t SUITE_RNG_MAX_WORDS = 25;
 // the host side of a suite: hashing of pairs and of word slices (what the device kernels of the suite compute per node / per row)
 struct HashSuite {
   virtual ~HashSuite() {}
@@ -342,6 +353,8 @@ struct SealCheck {
   uint32_t po2 = 0, code_root[8] = {0}, data_root[8] = {0};
 };
 const char* verify_seals_batch(r0h_ctx* ctx, int host_hashfn, SealCheck* seals, size_t n, size_t* upload_bytes_out = nullptr);
+// iop.hip: a device transcript that starts from a host generator's state, uploaded in stream order (no wait, unlike r0h_iop_set_state)
+const char* iop_make(r0h_ctx* ctx, const SuiteRng& rng, r0h_iop** out);
 // receipts, sessions, image proofs and recursion nodes name Poseidon2 only: their entry points refuse a context on another suite
 const char* require_poseidon2(const r0h_ctx* ctx, const char* caller);
 }  // namespace r0h

@@ -303,7 +303,7 @@ const char* logup_accum_kept(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, c
   } else {
     R0H_TRY(own_accumulators(ctx, c, po2, d.words + t.acc_begin[n_chain], d, accum, nullptr));
   }
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the tape goes back to the pool
+  R0H_TRY_HIP(ctx_wait(ctx));  // the tape goes back to the pool
   return nullptr;
   R0H_GUARD_END
 }
@@ -352,7 +352,7 @@ const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_
                        (uint32_t)slots[k], n);
     R0H_TRY(launch_ok("logup_mult_kernel"));
   }
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   uint32_t err = 0;
   R0H_TRY(r0h_buf_d2h(ctx, hist.get(), hist_words * 4 + 16, &err, 4));
   R0H_REQUIRE(!(err & 1u), "r0h_logup_multiplicities: a lookup's numerator is neither 0 nor 1");

@@ -329,4 +329,47 @@ __device__ __forceinline__ void p2_hash_row(uint32_t (&c)[P2_CELLS], const uint3
   }
 }
 
+// One permutation spread over 24 lanes of a 32-lane half-wave, one state cell per lane (`c`: lane l's cell, l = lane within the half;
+// lanes 24..31 carry don't-cares): S-boxes run in parallel, the external layer exchanges within quads and across the six quads by
+// shuffles, the internal layer is a 5-step shuffle all-reduce.  32x the instructions of the one-lane form and about a seventh of its
+// latency: for chains of single permutations -- the upper Merkle levels (hash_fold_lanes_kernel, merkle.hip) and the transcript's
+// generator (P2Transcript, hash_suite_device.hpp).  Every lane of the half-wave must call it.  The plain round-by-round permutation, the
+// same canonical words as p2_mix.  (Cross-lane: compiled by hipcc only, not by the host builds of this header.)
+#if defined(__HIPCC__)
+__device__ __forceinline__ uint32_t half_shfl(uint32_t v, uint32_t src_in_half) {
+  return __shfl(v, (int)((threadIdx.x & 32u) | src_in_half), 64);
+}
+__device__ __forceinline__ uint32_t m_ext_lanes(uint32_t x, uint32_t l) {
+  const uint32_t q = l & ~3u;
+  uint32_t a = half_shfl(x, q), b = half_shfl(x, q | 1), d = half_shfl(x, q | 2), e = half_shfl(x, q | 3);
+  uint32_t t0 = add(a, b), t1 = add(d, e);
+  uint32_t t2 = add(add(b, b), t1), t3 = add(add(e, e), t0);
+  uint32_t t1x2 = add(t1, t1), t0x2 = add(t0, t0);
+  uint32_t t4 = add(add(t1x2, t1x2), t3), t5 = add(add(t0x2, t0x2), t2);
+  uint32_t t6 = add(t3, t5), t7 = add(t2, t4);
+  const uint32_t j = l & 3u;
+  uint32_t y = j == 0 ? t6 : (j == 1 ? t5 : (j == 2 ? t7 : t4));
+  // column sums over the six quads: pair neighbours, then add the two other pairs (lanes 24..31 carry don't-cares)
+  uint32_t t = add(y, half_shfl(y, l ^ 4u));
+  uint32_t s = add(t, add(half_shfl(t, (l + 8u) % 24u), half_shfl(t, (l + 16u) % 24u)));
+  return add(y, s);
+}
+__device__ __forceinline__ uint32_t p2_mix_lanes(uint32_t c, uint32_t l, const P2Consts* __restrict__ k) {
+  const bool cell = l < 24u;
+  const uint32_t li = cell ? l : 0u;
+  const uint32_t dg = k->diag_canon[li], ds = k->diag_shoup[li];
+  c = m_ext_lanes(c, l);
+  for (int r = 0; r < P2_HALF_FULL; r++) c = m_ext_lanes(sbox7(add(c, k->rc_full[r][li])), l);
+  for (int r = 0; r < P2_PARTIAL; r++) {
+    if (l == 0) c = sbox7(add(c, k->rc_partial[r]));
+    uint32_t sum = cell ? c : 0u;
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) sum = add(sum, half_shfl(sum, l ^ (uint32_t)off));
+    c = add(sum, mul_const(c, dg, ds));
+  }
+  for (int r = P2_HALF_FULL; r < 2 * P2_HALF_FULL; r++) c = m_ext_lanes(sbox7(add(c, k->rc_full[r][li])), l);
+  return c;
+}
+#endif
+
 }  // namespace r0h

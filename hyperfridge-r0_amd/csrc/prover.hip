@@ -155,6 +155,19 @@ __global__ void sub_head_kernel(uint32_t* __restrict__ combos, const uint32_t* _
 }
 struct Round { Tree tree; DevBuf evaluated; };  // a committed FRI round
 
+// Steps 7 and 8 with the transcript on the device (r0h_ctx_set_device_transcript): where the seal's words of the two steps stand in the
+// proof's tail block, in words.  The block is read back once, at the end of step 8.
+struct IopFree { void operator()(r0h_iop* iop) const { r0h_iop_free(iop); } };
+struct TailLayout {
+  std::vector<size_t> round_top;  // per FRI round: its tree's top layer, 8 * top_size words
+  size_t final_coeffs = 0;        // 4 * final_degree words
+  size_t idx = 0;                 // the query rows [n_trees][R0H_QUERIES]
+  std::vector<size_t> opened;     // per tree: R0H_QUERIES packed openings, and behind a top-form tree's the two report words of merkle_open_top
+  size_t seal_words = 0;          // everything above: what the read-back brings home
+  size_t fold_mix = 0;            // per FRI round the four words of its fold mix (the device's own: never read back)
+  size_t words = 0;
+};
+
 }  // namespace r0h
 
 // The committed CODE group of a program at one trace size: bit-reversed zk-shifted coefficients, evaluations on the 4N coset, Merkle
@@ -196,6 +209,10 @@ struct r0h_proof {
   std::vector<r0h::Fp4> coeff_u;   // per register the interpolant through its openings, then CHECK's sixteen openings
   r0h::DevBuf fri_coeffs;          // the FRI input; inside step 7 what the rounds so far have folded it to
   std::vector<r0h::Round> rounds;
+  // steps 7 and 8 under r0h_ctx_set_device_transcript: the generator the host's was handed over to, and the seal words of both steps
+  std::unique_ptr<r0h_iop, r0h::IopFree> iop;
+  r0h::DevBuf tail;
+  r0h::TailLayout tail_at;
   r0h_proof(r0h_ctx* c, const r0h_circuit* ci, uint32_t p, const r0h_buf* code_columns, const r0h_code_commit* cc)
       : ctx(c), circ(ci), po2(p), io(c->hashfn, &c->p2_host), own_code(ci->group_size[R0H_GROUP_CODE], p), code(cc ? cc : &own_code),
         g_accum(ci->group_size[R0H_GROUP_ACCUM], (size_t)4 << p), g_data(ci->group_size[R0H_GROUP_DATA], (size_t)4 << p),
@@ -508,6 +525,108 @@ static const char* queries(r0h_proof& st) {
   return nullptr;
 }
 
+// ---- steps 7 and 8 on the device transcript.  The host generator's state goes up once; roots are committed from the trees' nodes, the
+// fold mixes and the query rows are drawn into device words the next kernels read, and every word the two steps add to the seal is
+// copied, device to device, into the proof's tail block.  One read-back at the end of step 8 brings the block home; the host then
+// appends its parts to the seal in the order the host steps write them.
+static const char* copy_words(r0h_ctx* ctx, r0h_buf* dst, size_t dst_word, const r0h_buf* src, size_t src_word, size_t n) {
+  R0H_TRY_HIP(hipMemcpyAsync(u32(dst) + dst_word, u32(src) + src_word, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  return nullptr;
+}
+static std::vector<const Tree*> proof_trees(const r0h_proof& st) {  // in the order of the seal's openings
+  std::vector<const Tree*> trees;
+  for (int g = 0; g < 4; g++) trees.push_back(&st.group(g).tree);
+  for (const Round& rd : st.rounds) trees.push_back(&rd.tree);
+  return trees;
+}
+
+static const char* fri_commit_device(r0h_proof& st) {
+  r0h_ctx* ctx = st.ctx;
+  profile_phase(ctx, "fri_commit");
+  const FriSchedule fri((size_t)1 << st.po2);
+  TailLayout& at = st.tail_at;
+  at = TailLayout();
+  {
+    size_t w = 0;
+    for (const FriRound& fr : fri.rounds) { at.round_top.push_back(w); w += 8 * MerkleShape(fr.rows, R0H_FRI_FOLD * 4).top_size; }
+    at.final_coeffs = w;
+    w += 4 * fri.final_degree;
+    at.idx = w;
+    w += (4 + fri.rounds.size()) * R0H_QUERIES;
+    for (size_t t = 0; t < 4 + fri.rounds.size(); t++) {
+      const MerkleShape mp = t < 4 ? st.group((int)t).tree.mp : MerkleShape(fri.rounds[t - 4].rows, R0H_FRI_FOLD * 4);
+      at.opened.push_back(w);
+      w += (size_t)R0H_QUERIES * mp.opening_words() + (t < 4 && st.group((int)t).tree.top_levels ? 2 : 0);
+    }
+    at.seal_words = w;
+    at.fold_mix = w;
+    at.words = w + 4 * fri.rounds.size();
+  }
+  R0H_TRY(st.tail.alloc(ctx, at.words * 4));
+  r0h_iop* iop = nullptr;
+  R0H_TRY(iop_make(ctx, st.io.rng, &iop));
+  st.iop.reset(iop);
+  for (size_t r = 0; r < fri.rounds.size(); r++) {
+    const FriRound& fr = fri.rounds[r];
+    Round rd{Tree(fr.rows, R0H_FRI_FOLD * 4), DevBuf()};
+    R0H_TRY(rd.evaluated.alloc(ctx, fr.domain * 16));
+    R0H_TRY(r0h_batch_expand_into_evaluate_ntt(ctx, rd.evaluated.get(), st.fri_coeffs.get(), 4, log2u(fr.degree), 2));
+    R0H_TRY(tree_build(ctx, rd.tree, rd.evaluated.get()));
+    const size_t top_words = 8 * rd.tree.mp.top_size;  // nodes [top_size, 2 * top_size)
+    R0H_TRY(copy_words(ctx, st.tail.get(), at.round_top[r], rd.tree.nodes.get(), top_words, top_words));
+    R0H_TRY(r0h_iop_commit(iop, rd.tree.nodes.get(), 8));  // the root is node 1
+    R0H_TRY(r0h_iop_draw_ext(iop, st.tail.get(), at.fold_mix + 4 * r, 1));
+    DevBuf folded;
+    R0H_TRY(folded.alloc(ctx, fr.degree / R0H_FRI_FOLD * 16));
+    R0H_TRY(r0h_fri_fold_buf(ctx, folded.get(), st.fri_coeffs.get(), st.tail.get(), at.fold_mix + 4 * r, (uint32_t)(fr.degree / R0H_FRI_FOLD)));
+    st.fri_coeffs = std::move(folded);
+    st.rounds.push_back(std::move(rd));
+  }
+  R0H_TRY(r0h_batch_bit_reverse(ctx, st.fri_coeffs.get(), 4, log2u(fri.final_degree)));
+  R0H_TRY(copy_words(ctx, st.tail.get(), at.final_coeffs, st.fri_coeffs.get(), 0, 4 * fri.final_degree));
+  st.fri_coeffs.reset();
+  return r0h_iop_commit_elems(iop, st.tail.get(), at.final_coeffs, 4 * fri.final_degree);
+}
+
+static const char* queries_device(r0h_proof& st) {
+  r0h_ctx* ctx = st.ctx;
+  profile_phase(ctx, "queries");
+  const TailLayout& at = st.tail_at;
+  const size_t domain = (size_t)R0H_INV_RATE << st.po2;
+  const std::vector<const Tree*> trees = proof_trees(st);
+  const uint32_t nq = R0H_QUERIES, n_trees = (uint32_t)trees.size();
+  std::vector<uint32_t> rows;
+  for (const Tree* t : trees) rows.push_back((uint32_t)t->mp.rows);
+  R0H_TRY(r0h_iop_draw_queries(st.iop.get(), (uint32_t)domain, rows.data(), n_trees, nq, st.tail.get(), at.idx));
+  uint32_t* tail = u32(st.tail.get());
+  for (uint32_t t = 0; t < n_trees; t++) {
+    const Tree& tr = *trees[t];
+    const uint32_t* d_idx = tail + at.idx + (size_t)t * nq;
+    uint32_t* out = tail + at.opened[t];
+    if (tr.top_levels)
+      R0H_TRY(merkle_open_top(ctx, out, u32(tr.matrix), u32(tr.nodes.get()), tr.top_levels, d_idx, nq, (uint32_t)tr.mp.rows, (uint32_t)tr.mp.cols,
+                              out + (size_t)nq * tr.mp.opening_words()));
+    else
+      R0H_TRY(merkle_open(ctx, out, u32(tr.matrix), u32(tr.nodes.get()), d_idx, nq, (uint32_t)tr.mp.rows, (uint32_t)tr.mp.cols));
+  }
+  std::vector<uint32_t> host(at.seal_words);
+  R0H_TRY(r0h_buf_d2h(ctx, st.tail.get(), 0, host.data(), host.size() * 4));  // the one wait of the two steps
+  st.iop.reset();
+  st.tail.reset();
+  for (uint32_t t = 0; t < n_trees; t++)
+    if (trees[t]->top_levels)
+      R0H_TRY(merkle_open_top_verdict("r0h_proof_finish", host.data() + at.opened[t] + (size_t)nq * trees[t]->mp.opening_words(), host.data() + at.idx + (size_t)t * nq));
+  WriteIop& io = st.io;
+  for (size_t r = 0; r < st.rounds.size(); r++) io.write(host.data() + at.round_top[r], 8 * st.rounds[r].tree.mp.top_size);
+  io.write(host.data() + at.final_coeffs, at.idx - at.final_coeffs);
+  for (uint32_t q = 0; q < nq; q++)
+    for (uint32_t t = 0; t < n_trees; t++) {
+      const size_t w = trees[t]->mp.opening_words();
+      io.write(host.data() + at.opened[t] + (size_t)q * w, w);
+    }
+  return nullptr;
+}
+
 // steps 3-8 of DESIGN.md 2, each under its own phase marks; the seal is the transcript's written words
 static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector<uint32_t>& seal) {
   R0H_REQUIRE(st.mix_drawn, "r0h_proof_finish: this circuit has late public inputs: r0h_proof_late comes first");
@@ -517,8 +636,13 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
   R0H_TRY(commit_check(st));
   R0H_TRY(evaluate_at_z(st));
   R0H_TRY(deep(st));
-  R0H_TRY(fri_commit(st));
-  R0H_TRY(queries(st));
+  if (st.ctx->device_transcript) {  // the same two steps with the generator on the device: one wait instead of 2 R + 5
+    R0H_TRY(fri_commit_device(st));
+    R0H_TRY(queries_device(st));
+  } else {
+    R0H_TRY(fri_commit(st));
+    R0H_TRY(queries(st));
+  }
   R0H_TRY(profile_close(st.ctx));
   seal.swap(st.io.proof);
   return nullptr;
@@ -638,7 +762,7 @@ const char* r0h_code_commit_new(r0h_ctx* ctx, const r0h_buf* code, uint32_t coun
   cc->kept_columns.reset(copy);
   cc->witness = copy;
   R0H_TRY_HIP(hipMemcpyAsync(copy->ptr, code->ptr, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  R0H_TRY_HIP(ctx_wait(ctx));
   // Everything has succeeded: the group's three buffers leave the pool's ownership.  They are long-lived and read from other
   // contexts' streams, so on release they go back to the device (hipFree waits for every stream), not into this context's
   // stream-ordered pool
@@ -712,7 +836,7 @@ const char* r0h_proof_shrink(r0h_proof* proof, size_t* bytes_freed_out) {
   Group& g_data = proof->g_data;
   if (g_data.evaluated) {
     R0H_TRY_HIP(hipSetDevice(proof->ctx->device));
-    R0H_TRY_HIP(hipStreamSynchronize(proof->ctx->stream));  // the block goes back to the pool: nothing in flight may still read it
+    R0H_TRY_HIP(ctx_wait(proof->ctx));  // the block goes back to the pool: nothing in flight may still read it
     freed = g_data.evaluated->bytes;
     g_data.evaluated.reset();
     g_data.tree.matrix = nullptr;

@@ -269,7 +269,7 @@ const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const ui
     hipLaunchKernelGGL(divide_remainders_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, ctx->stream, d_rem, sums, n_jobs, g.n_chunks);
     R0H_TRY(launch_ok("divide_remainders_kernel"));
     R0H_TRY_HIP(hipMemcpyAsync(remainders_host, d_rem, rem_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+    R0H_TRY_HIP(ctx_wait(ctx));
   }
   return nullptr;
   R0H_GUARD_END

@@ -90,7 +90,7 @@ const char* rows_upload(const char* who, r0h_ctx* ctx, const r0h_preflight_row* 
   if (n_bounds) R0H_TRY_HIP(hipMemcpyAsync(base + h->row_bytes, bounds, bound_bytes, hipMemcpyHostToDevice, ctx->stream));
   R0H_TRY(stage_h2d(ctx, base + h->tab_off, &trace::trace_tables(), sizeof(trace::Tables)));
   trace::trace_globals(rows, n_rows, bounds, n_bounds, segment->number, segment->closing != 0, segment->idle_pc, globals_out);
-  if (wait) R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  if (wait) R0H_TRY_HIP(ctx_wait(ctx));
   *out = std::move(h);
   return nullptr;
 }
@@ -149,7 +149,7 @@ const char* r0h_trace_witgen(r0h_ctx* ctx, const r0h_preflight_row* rows, size_t
   std::unique_ptr<r0h_trace_rows> h;
   R0H_TRY(rows_upload("r0h_trace_witgen", ctx, rows, n_rows, bounds, n_bounds, po2, segment, false, &h, globals_out));
   R0H_TRY(rows_expand(h.get(), data));
-  R0H_TRY_HIP(hipStreamSynchronize(ctx->stream));  // the staging block goes back to the pool and the caller may free its rows
+  R0H_TRY_HIP(ctx_wait(ctx));  // the staging block goes back to the pool and the caller may free its rows
   return nullptr;
   R0H_GUARD_END
 }

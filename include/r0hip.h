@@ -160,6 +160,10 @@ const char* r0h_batch_evaluate_any_buf(r0h_ctx* ctx, const r0h_buf* coeffs, uint
                                        uint32_t n_eval, r0h_buf* out);
 const char* r0h_mix_poly_coeffs_buf(r0h_ctx* ctx, r0h_buf* combos, const uint32_t mix_start[4], const uint32_t mix[4],
                                     const r0h_buf* input, const r0h_buf* combo_of, uint32_t input_count, uint32_t po2);
+/* r0h_fri_fold with the mix read from device memory: the four words at mix_buf[mix_word_offset ..], e.g. where r0h_iop_draw_ext
+ * wrote them (canonical words, as every field word on the device).  Refused when those four words would end beyond the buffer. */
+const char* r0h_fri_fold_buf(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* in, const r0h_buf* mix_buf, size_t mix_word_offset,
+                             uint32_t n_out);
 /* values[k] goes to into[offsets[k]] for index[0] <= k < index[n_index - 1] (offsets / values hold n_values host words) */
 const char* r0h_scatter_slices(r0h_ctx* ctx, r0h_buf* into, const uint32_t* index, uint32_t n_index, const uint32_t* offsets,
                                const uint32_t* values, uint32_t n_values);
@@ -216,6 +220,37 @@ const char* r0h_check_witness(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, 
  * and its first row instead of a seal no verifier accepts.  Between r0h_proof_begin* and r0h_proof_finish the CODE and DATA
  * witness buffers must then stay as they were given.  Off (the default): nothing is checked, seals and timing are unchanged. */
 const char* r0h_ctx_set_check_witness(r0h_ctx* ctx, int on);
+/* ---- the transcript on the device: the Fiat-Shamir generator of the context's hash suite over a state in device memory (a block
+ * from the context's pool), driven in stream order.  What a sequencer does with a host transcript -- commit a root, hash and commit
+ * words of the seal, draw a challenge, draw the query rows -- without a round trip: digests are read from device buffers (a tree's
+ * root is its node 1, words [8, 16) of its nodes), challenges are written to device buffers where the next kernel reads them
+ * (r0h_fri_fold_buf).  A handle belongs to the suite its context was on when it was made and is refused once the context has changed
+ * suite.  r0h_iop_set_state / r0h_iop_state block: they are the hand-over between a host generator and this one.  The state is the
+ * generator's words as the host holds them, then pool_used -- Poseidon2: 24 cells (Montgomery form) + pool_used <= 16, 25 words;
+ * SHA-256: pool0[8], pool1[8] + pool_used <= 8, 17 words; a wrong count, a Poseidon2 cell >= p or a pool_used above that is refused.
+ * Everything else is stream-ordered and touches no host memory; offsets count 32-bit words.
+ *   r0h_iop_commit        mixes the digest at buf[word_offset .. +8)
+ *   r0h_iop_commit_elems  the suite's hash of the n words at buf[word_offset ..] (r0h_hash_elems_host's), then the mix
+ *   r0h_iop_draw_ext      `count` extension elements, 4 words each, to out[word_offset ..]
+ *   r0h_iop_draw_queries  per query pos = bits(log2 domain) % domain; for the trees from the fifth on pos %= tree_rows[t], carried on
+ *                         from tree to tree; the table idx_out[word_offset + t * n_queries + q].  domain a power of two, at most 16 trees.
+ * r0h_ctx_set_device_transcript(ctx, on != 0): r0h_proof_finish (and every entry point that runs it: r0h_prove_segment*, sessions,
+ * recursion) runs its last two steps, the FRI commitments and the queries, on such a transcript, with one read-back for both instead
+ * of 2 R + 5 (R FRI rounds).  Off (the default): the steps are what they always were.  The seal is the same words either way.
+ * r0h_ctx_blocking_waits: how many times the library has waited for this context's stream so far (every r0h_buf_d2h, r0h_sync and
+ * wait inside an entry point). ---- */
+typedef struct r0h_iop r0h_iop;
+const char* r0h_iop_new(r0h_ctx* ctx, r0h_iop** iop_out);
+const char* r0h_iop_free(r0h_iop* iop);
+const char* r0h_iop_set_state(r0h_iop* iop, const uint32_t* words, size_t n);
+const char* r0h_iop_state(r0h_iop* iop, uint32_t* words_out, size_t capacity, size_t* n_out);
+const char* r0h_iop_commit(r0h_iop* iop, const r0h_buf* buf, size_t word_offset);
+const char* r0h_iop_commit_elems(r0h_iop* iop, const r0h_buf* buf, size_t word_offset, size_t n);
+const char* r0h_iop_draw_ext(r0h_iop* iop, r0h_buf* out, size_t word_offset, size_t count);
+const char* r0h_iop_draw_queries(r0h_iop* iop, uint32_t domain, const uint32_t* tree_rows, uint32_t n_trees, uint32_t n_queries,
+                                 r0h_buf* idx_out, size_t word_offset);
+const char* r0h_ctx_set_device_transcript(r0h_ctx* ctx, int on);
+const char* r0h_ctx_blocking_waits(const r0h_ctx* ctx, uint64_t* count_out);
 /* ---- the balance check: which tuples a log-derivative argument (blob section LOGUP, r0hip_circuit.h) fails to cancel.  A witness
  * whose reads do not return what was written, whose boundary rows or multiplicities are off, still has running sums: the checker
  * above sees one chain-link term violated on the wrap row and nothing else.  This check names the fractions instead.
