@@ -87,6 +87,7 @@ _SIGNATURES = {
     "r0h_iop_draw_queries": [_vp, _u32, _vp, _u32, _u32, _vp, _sz],
     "r0h_ctx_set_device_transcript": [_vp, _c.c_int],
     "r0h_ctx_blocking_waits": [_vp, _c.POINTER(_u64)],
+    "r0h_ctx_set_device_finish": [_vp, _c.c_int],
     "r0h_batch_evaluate_any_buf": [_vp, _vp, _u32, _vp, _vp, _u32, _vp],
     "r0h_mix_poly_coeffs_buf": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32],
     "r0h_scatter_slices": [_vp, _vp, _vp, _u32, _vp, _vp, _u32],
@@ -138,6 +139,8 @@ _SIGNATURES = {
     "r0h_proof_begin": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _pp],
     "r0h_proof_finish": [_vp, _vp, _vp, _sz, _c.POINTER(_sz)],
     "r0h_proof_abort": [_vp],
+    "r0h_proof_finish_enqueue": [_vp, _vp],
+    "r0h_proof_finish_collect": [_vp, _vp, _sz, _c.POINTER(_sz)],
     "r0h_verify_seal": [_vp, _sz, _vp, _vp, _vp, _sz, _c.POINTER(_c.c_int), _c.POINTER(_u32)],
     "r0h_verify_seal_bound": [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _c.POINTER(_c.c_int), _c.POINTER(_u32), _vp],
     "r0h_code_root": [_vp, _vp, _u32, _u32, _vp],
@@ -1866,6 +1869,12 @@ class Hal:
         transcript on the device, with one read-back for both steps (r0h_ctx_set_device_transcript); off by default, same seals"""
         _check(lib().r0h_ctx_set_device_transcript(self.ctx, 1 if on else 0))
 
+    def set_device_finish(self, on=True):
+        """proof_finish -- and so prove_segment, sessions, image proofs and recursion on this context -- runs all its steps on a
+        transcript on the device, with one read-back for all of them, and can be split into proof_finish_enqueue / proof_finish_collect
+        (r0h_ctx_set_device_finish); off by default, same seals"""
+        _check(lib().r0h_ctx_set_device_finish(self.ctx, 1 if on else 0))
+
     def blocking_waits(self):
         """how many times the library has waited for this context's stream so far (r0h_ctx_blocking_waits)"""
         n = _u64(0)
@@ -2021,6 +2030,18 @@ class Hal:
         seal = np.empty(seal_capacity_words, dtype=np.uint32)
         n = _sz(0)
         _check(lib().r0h_proof_finish(proof, accum.handle, seal.ctypes.data_as(_vp), seal.size, ctypes.byref(n)))
+        return seal[:n.value].copy()
+
+    def proof_finish_enqueue(self, proof, accum):
+        """steps 3-8 enqueued on the proof's stream; returns without waiting for it (r0h_proof_finish_enqueue, set_device_finish on).
+        `accum` and what the proof was begun with stay as they are until proof_finish_collect."""
+        _check(lib().r0h_proof_finish_enqueue(proof, accum.handle))
+
+    def proof_finish_collect(self, proof, seal_capacity_words=1 << 20):
+        """the seal of an enqueued proof: one read-back (r0h_proof_finish_collect)"""
+        seal = np.empty(seal_capacity_words, dtype=np.uint32)
+        n = _sz(0)
+        _check(lib().r0h_proof_finish_collect(proof, seal.ctypes.data_as(_vp), seal.size, ctypes.byref(n)))
         return seal[:n.value].copy()
 
     def proof_abort(self, proof):

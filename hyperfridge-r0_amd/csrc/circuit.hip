@@ -309,13 +309,14 @@ const char* r0h_accum_public(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, c
   return logup_accum_kept(ctx, c, po2, code, data, global, mix, accum, nullptr);
 }
 
-const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code,
-                           const r0h_buf* eval_data, const uint32_t* global, const uint32_t* mix, const uint32_t poly_mix[4], r0h_buf* check) {
+// poly_mix: four host words (r0h_eval_check), or nullptr with d_poly_mix the four device words a transcript on the device drew (eval_check_dev)
+static const char* eval_check_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code, const r0h_buf* eval_data,
+                                   const uint32_t* global, const uint32_t* mix, const uint32_t* poly_mix, const uint32_t* d_poly_mix, r0h_buf* check) {
   R0H_GUARD_BEGIN
-  R0H_REQUIRE(ctx && c && eval_accum && eval_code && eval_data && check && poly_mix, "r0h_eval_check: NULL argument");
+  R0H_REQUIRE(ctx && c && eval_accum && eval_code && eval_data && check && (poly_mix || d_poly_mix), "r0h_eval_check: NULL argument");
   R0H_REQUIRE((global || !c->n_global) && (mix || !c->n_mix), "r0h_eval_check: NULL globals");
   R0H_REQUIRE(po2 >= 6 && po2 <= R0H_MAX_PO2, "r0h_eval_check: po2 %u outside [6, %u]", po2, R0H_MAX_PO2);
-  for (int q = 0; q < 4; q++) R0H_REQUIRE(poly_mix[q] < P, "r0h_eval_check: poly_mix words must be canonical (< p)");
+  for (int q = 0; q < 4 && poly_mix; q++) R0H_REQUIRE(poly_mix[q] < P, "r0h_eval_check: poly_mix words must be canonical (< p)");
   const size_t domain = (size_t)4 << po2;
   const r0h_buf* g[3] = {eval_accum, eval_code, eval_data};
   for (int k = 0; k < 3; k++) R0H_REQUIRE(domain * c->group_size[k] * 4 <= g[k]->bytes, "r0h_eval_check: group %d buffer too small", k);
@@ -325,8 +326,12 @@ const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, con
   uint32_t* p = params.data();
   for (uint32_t i = 0; i < c->n_global; i++) { R0H_REQUIRE(global[i] < P, "r0h_eval_check: global[%u] not canonical", i); *p++ = global[i]; }
   for (uint32_t i = 0; i < c->n_mix; i++) { R0H_REQUIRE(mix[i] < P, "r0h_eval_check: mix[%u] not canonical", i); *p++ = mix[i]; }
-  Fp4 pm{{poly_mix[0], poly_mix[1], poly_mix[2], poly_mix[3]}}, cur = fp4_one();
-  for (uint32_t k = 0; k < c->plan.n_pow; k++) { memcpy(p, cur.e, 16); p += 4; cur = cur * pm; }
+  if (poly_mix) {
+    Fp4 pm{{poly_mix[0], poly_mix[1], poly_mix[2], poly_mix[3]}}, cur = fp4_one();
+    for (uint32_t k = 0; k < c->plan.n_pow; k++) { memcpy(p, cur.e, 16); p += 4; cur = cur * pm; }
+  } else {
+    p += 4 * (size_t)c->plan.n_pow;  // filled on the device, below
+  }
   {
     uint32_t three_n = fpow(enc(3), (uint64_t)1 << po2), w4 = rou_fwd(2), w = ONE;
     for (int k = 0; k < 4; k++) { *p++ = inv(sub(mul(three_n, w), ONE)); w = mul(w, w4); }
@@ -339,6 +344,7 @@ const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, con
   uint32_t* d_check = u32(check);
   const uint32_t *g0 = u32(g[0]), *g1 = u32(g[1]), *g2 = u32(g[2]);
   const uint32_t *d_glob = u32(pbuf.get()), *d_mix = d_glob + c->n_global, *d_pow = d_mix + c->n_mix, *d_van = d_pow + 4 * (size_t)c->plan.n_pow;
+  if (!poly_mix) R0H_TRY(ext_powers(ctx, const_cast<uint32_t*>(d_pow), d_poly_mix, nullptr, c->plan.n_pow));
   double alg = (double)domain * 16;
   for (int k = 0; k < 3; k++) alg += (double)domain * c->group_size[k] * 4;
   KScope ks(ctx, "eval_check", alg);
@@ -351,6 +357,20 @@ const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, con
   return nullptr;
   R0H_GUARD_END
 }
+const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code,
+                           const r0h_buf* eval_data, const uint32_t* global, const uint32_t* mix, const uint32_t poly_mix[4], r0h_buf* check) {
+  R0H_REQUIRE(poly_mix, "r0h_eval_check: NULL argument");
+  return eval_check_impl(ctx, c, po2, eval_accum, eval_code, eval_data, global, mix, poly_mix, nullptr, check);
+}
+}  // extern "C"
+namespace r0h {
+const char* eval_check_dev(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code, const r0h_buf* eval_data,
+                           const uint32_t* global, const uint32_t* mix, const uint32_t* d_poly_mix, r0h_buf* check) {
+  R0H_REQUIRE(d_poly_mix, "r0h_eval_check: NULL argument");
+  return eval_check_impl(ctx, c, po2, eval_accum, eval_code, eval_data, global, mix, nullptr, d_poly_mix, check);
+}
+}  // namespace r0h
+extern "C" {
 
 const char* r0h_check_witness(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,
                               const uint32_t* global, const uint32_t* mix, r0h_violation* out, size_t capacity, size_t* n_out) {

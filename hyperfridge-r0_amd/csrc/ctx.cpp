@@ -97,8 +97,12 @@ void profile_phase(r0h_ctx* ctx, const char* name) {
   (void)hipEventRecord(p.events[i], ctx->stream);
   p.names.push_back(name);
 }
+void profile_end(r0h_ctx* ctx) { profile_phase(ctx, "end"); }
 const char* profile_close(r0h_ctx* ctx) {
-  profile_phase(ctx, "end");
+  profile_end(ctx);
+  return profile_collect(ctx);
+}
+const char* profile_collect(r0h_ctx* ctx) {
   R0H_TRY_HIP(ctx_wait(ctx));
   Profile& p = ctx->prof;
   std::vector<float> ms(p.names.size() - 1, 0.f);
@@ -120,6 +124,7 @@ const char* ctx_helper(r0h_ctx* ctx, size_t k, r0h_ctx** out) {
   h->check_balance = ctx->check_balance;
   h->check_session = ctx->check_session;
   h->device_transcript = ctx->device_transcript;
+  h->device_finish = ctx->device_finish;
   h->hashfn = ctx->hashfn;
   h->p2_tight = ctx->p2_tight;  // goes with the table below
   if (memcmp(&h->p2_host, &ctx->p2_host, sizeof(P2Consts)) != 0) {  // r0h_poseidon2_set_consts on the owner since the helper was made
@@ -220,6 +225,12 @@ const char* r0h_ctx_set_device_transcript(r0h_ctx* ctx, int on) {
   R0H_REQUIRE(ctx, "r0h_ctx_set_device_transcript: ctx is NULL");
   ctx->device_transcript = on != 0;
   for (r0h_ctx* h : ctx->helpers) h->device_transcript = ctx->device_transcript;
+  return nullptr;
+}
+const char* r0h_ctx_set_device_finish(r0h_ctx* ctx, int on) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_device_finish: ctx is NULL");
+  ctx->device_finish = on != 0;
+  for (r0h_ctx* h : ctx->helpers) h->device_finish = ctx->device_finish;
   return nullptr;
 }
 const char* r0h_ctx_blocking_waits(const r0h_ctx* ctx, uint64_t* count_out) {

@@ -151,6 +151,17 @@ __global__ __launch_bounds__(256) void mix_poly_kernel(uint32_t* __restrict__ co
   }
 }
 
+// out[k] = base^(exps ? exps[k] : k) for a base in device memory (a challenge the device's transcript drew): a lane per power by
+// square-and-multiply, at most 32 squarings deep.  Fills the power tables the host otherwise computes and uploads -- eval_check's
+// poly_mix powers, mix_poly_kernel's per-column powers, the DEEP head's.  (`out`, `base` need no alignment beyond a word.)
+__global__ __launch_bounds__(256) void ext_powers_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ base, const uint32_t* __restrict__ exps, uint32_t n) {
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= n) return;
+  const Fp4 r = fp4_pow(Fp4{{base[0], base[1], base[2], base[3]}}, exps ? exps[k] : k);
+#pragma unroll
+  for (int q = 0; q < 4; q++) out[4 * (size_t)k + q] = r.e[q];
+}
+
 // ------------------------------------------------------------------ small element-wise kernels
 __global__ void add_elem_kernel(uint32_t* out, const uint32_t* a, const uint32_t* b, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -225,10 +236,20 @@ const char* r0h_batch_evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t
 }  // extern "C"
 
 namespace r0h {
-const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which, const uint32_t* xs,
-                         uint32_t n_eval, r0h_buf* out, bool bitrev_coeffs) {
+const char* ext_powers(r0h_ctx* ctx, uint32_t* d_out, const uint32_t* d_base, const uint32_t* d_exps, uint32_t n) {
+  if (!n) return nullptr;
+  KScope ks(ctx, "ext_powers_kernel", 16.0 * n);
+  hipLaunchKernelGGL(ext_powers_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_out, d_base, d_exps, n);
+  return launch_ok("ext_powers_kernel");
+}
+
+// Request k evaluates column which[k] at a point given by its four words xs[4k ..) (host words: evaluate_any), or, xs == nullptr, by
+// its index pt_idx[k] in the device table d_points (evaluate_any_points).  Requests of one column are grouped by their list of points;
+// the list's key is the words in one form and the indices in the other, so distinct points with distinct indices group alike.
+static const char* evaluate_any_impl(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which, const uint32_t* xs, const uint32_t* pt_idx,
+                                     const uint32_t* d_points, uint32_t n_points, uint32_t n_eval, r0h_buf* out, bool bitrev_coeffs) {
   R0H_GUARD_BEGIN
-  R0H_REQUIRE(ctx && coeffs && out && (n_eval == 0 || (which && xs)), "r0h_batch_evaluate_any: NULL argument");
+  R0H_REQUIRE(ctx && coeffs && out && (n_eval == 0 || (which && (xs || (pt_idx && d_points)))), "r0h_batch_evaluate_any: NULL argument");
   R0H_REQUIRE(po2 <= MAX_DOMAIN_PO2, "r0h_batch_evaluate_any: po2 %u too large", po2);
   R0H_REQUIRE((size_t)n_eval * 16 <= out->bytes, "r0h_batch_evaluate_any: %u results exceed the output buffer", n_eval);
   if (!n_eval) return nullptr;
@@ -240,16 +261,19 @@ const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, cons
   std::map<uint32_t, std::vector<uint32_t>> by_col;  // column -> request indices
   for (uint32_t k = 0; k < n_eval; k++) {
     R0H_REQUIRE(which[k] < n_polys, "r0h_batch_evaluate_any: which[%u] = %u but the buffer holds %zu polynomials", k, which[k], n_polys);
-    for (int q = 0; q < 4; q++) R0H_REQUIRE(xs[4 * k + q] < P, "r0h_batch_evaluate_any: xs[%u] not canonical", k);
+    for (int q = 0; q < 4 && xs; q++) R0H_REQUIRE(xs[4 * k + q] < P, "r0h_batch_evaluate_any: xs[%u] not canonical", k);
+    R0H_REQUIRE(xs || pt_idx[k] < n_points, "r0h_batch_evaluate_any: request %u names point %u of a table of %u", k, xs ? 0u : pt_idx[k], n_points);
     by_col[which[k]].push_back(k);
   }
-  std::map<std::vector<uint32_t>, std::vector<ColJob>> groups;  // point list (4 words per point) -> columns
+  const size_t key_words = xs ? 4 : 1;
+  std::map<std::vector<uint32_t>, std::vector<ColJob>> groups;  // point list (4 words per point, or its index in the table) -> columns
   for (auto& c : by_col)
     for (size_t at = 0; at < c.second.size(); at += MAX_NP) {
       std::vector<uint32_t> key;
       ColJob job{c.first, {}};
       for (size_t i = at; i < c.second.size() && i < at + MAX_NP; i++) {
-        key.insert(key.end(), xs + 4 * (size_t)c.second[i], xs + 4 * (size_t)c.second[i] + 4);
+        if (xs) key.insert(key.end(), xs + 4 * (size_t)c.second[i], xs + 4 * (size_t)c.second[i] + 4);
+        else key.push_back(pt_idx[c.second[i]]);
         job.dest.push_back(c.second[i]);
       }
       groups[key].push_back(std::move(job));
@@ -268,14 +292,15 @@ const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, cons
   uint32_t* idx = pts + pt_words;
   uint32_t* part = idx + idx_words;
   for (auto& g : groups) {
-    const uint32_t np = (uint32_t)(g.first.size() / 4), ng = (uint32_t)g.second.size();
+    const uint32_t np = (uint32_t)(g.first.size() / key_words), ng = (uint32_t)g.second.size();
     std::vector<uint32_t> host((size_t)(1 + np) * ng);  // [column per job][destination per (job, point)]
     for (uint32_t j = 0; j < ng; j++) {
       host[j] = g.second[j].col;
       for (uint32_t p = 0; p < np; p++) host[ng + (size_t)j * np + p] = g.second[j].dest[p];
     }
     R0H_TRY(stage_h2d(ctx, idx, host.data(), host.size() * 4));
-    R0H_TRY(stage_h2d(ctx, pts, g.first.data(), g.first.size() * 4));
+    if (xs) R0H_TRY(stage_h2d(ctx, pts, g.first.data(), g.first.size() * 4));
+    for (uint32_t p = 0; p < np && !xs; p++) R0H_TRY_HIP(hipMemcpyAsync(pts + 4 * p, d_points + 4 * (size_t)g.first[p], 16, hipMemcpyDeviceToDevice, ctx->stream));
     KScope ks(ctx, "batch_evaluate_any", 4.0 * ng * (double)(1u << po2));  // algorithmic bytes: every column once
     // blocks per polynomial: enough workgroups overall (~2048) to fill the chip, but no more -- every block re-loads the power tables
     uint32_t gb = 2048 / ng;
@@ -290,16 +315,24 @@ const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, cons
   return nullptr;
   R0H_GUARD_END
 }
-}  // namespace r0h
+const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which, const uint32_t* xs, uint32_t n_eval, r0h_buf* out, bool bitrev_coeffs) {
+  R0H_REQUIRE(n_eval == 0 || xs, "r0h_batch_evaluate_any: NULL argument");
+  return evaluate_any_impl(ctx, coeffs, po2, which, xs, nullptr, nullptr, 0, n_eval, out, bitrev_coeffs);
+}
+const char* evaluate_any_points(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which, const uint32_t* pt_idx, uint32_t n_eval, const uint32_t* d_points,
+                                uint32_t n_points, r0h_buf* out, bool bitrev_coeffs) {
+  R0H_REQUIRE(n_eval == 0 || (pt_idx && d_points), "r0h_batch_evaluate_any: NULL argument");
+  return evaluate_any_impl(ctx, coeffs, po2, which, nullptr, pt_idx, d_points, n_points, n_eval, out, bitrev_coeffs);
+}
 
-extern "C" {
-
-const char* r0h_mix_poly_coeffs(r0h_ctx* ctx, r0h_buf* combos, const uint32_t mix_start[4], const uint32_t mix[4],
-                                const r0h_buf* input, const uint32_t* combo_of, uint32_t input_count, uint32_t po2) {
+// The per-column powers are mix_start * mix^c from host words (r0h_mix_poly_coeffs), or, mix == nullptr, mix^(first_exp + c) of the four
+// device words d_mix, filled into the parameter block by ext_powers (mix_poly_coeffs_dev)
+static const char* mix_poly_coeffs_impl(r0h_ctx* ctx, r0h_buf* combos, const uint32_t* mix_start, const uint32_t* mix, uint32_t first_exp, const uint32_t* d_mix,
+                                        const r0h_buf* input, const uint32_t* combo_of, uint32_t input_count, uint32_t po2) {
   R0H_GUARD_BEGIN
-  R0H_REQUIRE(ctx && combos && input && mix_start && mix && (combo_of || !input_count), "r0h_mix_poly_coeffs: NULL argument");
+  R0H_REQUIRE(ctx && combos && input && ((mix_start && mix) || d_mix) && (combo_of || !input_count), "r0h_mix_poly_coeffs: NULL argument");
   R0H_REQUIRE(po2 <= MAX_DOMAIN_PO2, "r0h_mix_poly_coeffs: po2 %u too large", po2);
-  R0H_REQUIRE(canonical4(mix_start) && canonical4(mix), "r0h_mix_poly_coeffs: mix words must be canonical (< p)");
+  R0H_REQUIRE(!mix || (canonical4(mix_start) && canonical4(mix)), "r0h_mix_poly_coeffs: mix words must be canonical (< p)");
   R0H_REQUIRE(((size_t)input_count << po2) * 4 <= input->bytes, "r0h_mix_poly_coeffs: %u columns exceed the input buffer", input_count);
   if (!input_count) return nullptr;
   std::vector<uint32_t> order(input_count);
@@ -309,8 +342,10 @@ const char* r0h_mix_poly_coeffs(r0h_ctx* ctx, r0h_buf* combos, const uint32_t mi
   }
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return combo_of[a] < combo_of[b]; });
   std::vector<Fp4> pw(input_count);
-  Fp4 cur = host_fp4(mix_start), m = host_fp4(mix);
-  for (uint32_t c = 0; c < input_count; c++) { pw[c] = cur; cur = cur * m; }
+  if (mix) {
+    Fp4 cur = host_fp4(mix_start), m = host_fp4(mix);
+    for (uint32_t c = 0; c < input_count; c++) { pw[c] = cur; cur = cur * m; }
+  }
   std::vector<uint32_t> starts, ids;
   for (uint32_t k = 0; k < input_count; k++)
     if (k == 0 || combo_of[order[k]] != combo_of[order[k - 1]]) { starts.push_back(k); ids.push_back(combo_of[order[k]]); }
@@ -321,15 +356,32 @@ const char* r0h_mix_poly_coeffs(r0h_ctx* ctx, r0h_buf* combos, const uint32_t mi
   params.insert(params.end(), order.begin(), order.end());
   params.insert(params.end(), ids.begin(), ids.end());
   for (uint32_t k = 0; k < input_count; k++)
-    for (int q = 0; q < 4; q++) params.push_back(pw[order[k]].e[q]);
+    for (int q = 0; q < 4; q++) params.push_back(mix ? pw[order[k]].e[q] : 0u);
+  const size_t pw_at = params.size() - 4 * (size_t)input_count, exps_at = params.size();
+  for (uint32_t k = 0; k < input_count && !mix; k++) params.push_back(first_exp + order[k]);  // behind everything the kernel reads: the exponent of each sorted column
   DevBuf d_params;
   R0H_TRY(d_params.alloc(ctx, params.size() * 4));
   R0H_TRY(stage_h2d(ctx, d_params->ptr, params.data(), params.size() * 4));
+  if (!mix) R0H_TRY(ext_powers(ctx, u32(d_params.get()) + pw_at, d_mix, u32(d_params.get()) + exps_at, input_count));
   uint32_t n = 1u << po2, threads = n < 256 ? n : 256;
   KScope ks(ctx, "mix_poly_kernel", 4.0 * input_count * (double)n + 32.0 * n_groups * (double)n);
   hipLaunchKernelGGL(mix_poly_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(combos), u32(input), u32(d_params.get()), n_groups, po2);
   return launch_ok("mix_poly_kernel");
   R0H_GUARD_END
+}
+const char* mix_poly_coeffs_dev(r0h_ctx* ctx, r0h_buf* combos, uint32_t first_exp, const uint32_t* d_mix, const r0h_buf* input, const uint32_t* combo_of, uint32_t input_count,
+                                uint32_t po2) {
+  R0H_REQUIRE(d_mix, "r0h_mix_poly_coeffs: NULL argument");
+  return mix_poly_coeffs_impl(ctx, combos, nullptr, nullptr, first_exp, d_mix, input, combo_of, input_count, po2);
+}
+}  // namespace r0h
+
+extern "C" {
+
+const char* r0h_mix_poly_coeffs(r0h_ctx* ctx, r0h_buf* combos, const uint32_t mix_start[4], const uint32_t mix[4],
+                                const r0h_buf* input, const uint32_t* combo_of, uint32_t input_count, uint32_t po2) {
+  R0H_REQUIRE(mix_start && mix, "r0h_mix_poly_coeffs: NULL argument");
+  return mix_poly_coeffs_impl(ctx, combos, mix_start, mix, 0, nullptr, input, combo_of, input_count, po2);
 }
 
 const char* r0h_eltwise_add_elem(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* a, const r0h_buf* b, uint32_t n) {

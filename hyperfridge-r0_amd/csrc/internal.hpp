@@ -133,6 +133,7 @@ struct r0h_ctx {
   bool check_session = false;     // r0h_ctx_set_check_session: r0h_session_finish checks the session balance of all segments before it derives the challenge
   uint64_t balance_stats[3] = {0, 0, 0};  // the last r0h_logup_check_balance: tuples, inserts that reached the global table, its slots
   bool device_transcript = false;  // r0h_ctx_set_device_transcript: fri_commit and queries run on the device generator (prover.hip), one read-back for both
+  bool device_finish = false;  // r0h_ctx_set_device_finish: steps 3-8 of proof_finish run on the device generator (prover.hip), one read-back for all of them
   std::atomic<uint64_t> blocking_waits{0};  // r0h_ctx_blocking_waits: the times the library has waited for this context's stream (ctx_wait)
   bool ktime_on = false;
   std::map<std::string, r0h::KTimer> ktimers;
@@ -211,6 +212,10 @@ r0h_buf buf_view(const r0h_buf* b, size_t offset_bytes, size_t bytes);
 // for the stream and makes the phases recorded since the last proof began what r0h_last_profile reports.  Host only.
 void profile_phase(r0h_ctx* ctx, const char* name);
 const char* profile_close(r0h_ctx* ctx);
+// profile_close in two halves, for a proof that is enqueued and collected later: profile_end marks the end of the last phase in stream
+// order (no wait); profile_collect waits for the stream and closes the profile.  profile_close is one after the other.
+void profile_end(r0h_ctx* ctx);
+const char* profile_collect(r0h_ctx* ctx);
 // after a kernel launch: the launch error, if any, as "<what>: launch failed: <hip text>"
 const char* launch_ok(const char* what);
 // inverse NTT with the coset shift f(x) -> f(3x) optionally fused into its last pass (sequencer path)
@@ -218,6 +223,24 @@ const char* interpolate_ntt(r0h_ctx* ctx, r0h_buf* io, const r0h_buf* src, uint3
 // batch_evaluate_any over coefficients stored in natural or bit-reversed order (the sequencer keeps them bit-reversed)
 const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which, const uint32_t* xs, uint32_t n_eval,
                          r0h_buf* out, bool bitrev_coeffs);
+// The forms of four launchers that take a challenge where the device's transcript left it (prover.hip, r0h_ctx_set_device_finish).  None
+// of them waits for the stream.  `d_points` is a table of extension points in device memory, four words each; requests and jobs name their
+// point by its index in it.
+//   ext_powers                out[4k .. 4k + 4) = base^(exps ? exps[k] : k), k < n: a lane per power, square-and-multiply (device pointers)
+//   eval_check_dev            r0h_eval_check with poly_mix read from four device words: the power words of the parameter block are filled by ext_powers
+//   evaluate_any_points       evaluate_any whose request k is (which[k], pt_idx[k]): grouped by point index, `pts` copied device to device
+//   mix_poly_coeffs_dev       r0h_mix_poly_coeffs whose column c is weighed by mix^(first_exp + c), mix read from four device words
+//   poly_divide_batch_points  poly_divide_batch whose job j divides by (x - point pt_idx[j]): the job table's w, w^E, w^chunk are filled on the
+//                             device, and d_report (one device word) becomes 0, or 1 + the first job, in the order given, whose remainder is not zero
+const char* ext_powers(r0h_ctx* ctx, uint32_t* d_out, const uint32_t* d_base, const uint32_t* d_exps, uint32_t n);
+const char* eval_check_dev(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code, const r0h_buf* eval_data,
+                           const uint32_t* global, const uint32_t* mix, const uint32_t* d_poly_mix, r0h_buf* check);
+const char* evaluate_any_points(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which, const uint32_t* pt_idx, uint32_t n_eval, const uint32_t* d_points,
+                                uint32_t n_points, r0h_buf* out, bool bitrev_coeffs);
+const char* mix_poly_coeffs_dev(r0h_ctx* ctx, r0h_buf* combos, uint32_t first_exp, const uint32_t* d_mix, const r0h_buf* input, const uint32_t* combo_of, uint32_t input_count,
+                                uint32_t po2);
+const char* poly_divide_batch_points(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* pt_idx, uint32_t n_jobs, const uint32_t* d_points,
+                                     uint32_t n_points, uint32_t* d_report);
 // in-place bit reversal of `count` columns of 2^po2 extension elements (16-byte units)
 const char* bit_reverse_ext(r0h_ctx* ctx, r0h_buf* io, uint32_t count, uint32_t po2);
 // per-device kernel attributes of the NTT family (LDS limits); called by r0h_ctx_create with the device current

@@ -3,6 +3,8 @@
 // draw the accumulation mix, accumulate, finalize) and risc0-zkp 3.0.4 prove/{prover.rs, poly_group.rs, merkle.rs,
 // fri.rs, write_iop.rs} + core/hash/{poseidon2,sha}/rng.rs behind the suite interface of hash_suite.cpp -- SURVEY.md 3.4 steps 3-13, 8(a) a8, a15-a17.
 // This is what host/src/main.rs:423 (`prover.prove(env, HYPERFRIDGE_ELF)`) spends its time in, once per segment.
+// The transcript is handed over to the device (iop.hip) for steps 7-8 under r0h_ctx_set_device_transcript and for steps 3-8 under
+// r0h_ctx_set_device_finish, where proof_finish also splits into an enqueue that waits for nothing and a collect that waits once.
 //
 // Device-resident throughout: witness, coefficients, evaluations, Merkle nodes, combos.  What crosses to the host per
 // segment: Merkle tops + roots (<= 2 KB each), ~500 tap evaluations, the FRI final polynomial (4 KB) and the 50
@@ -104,7 +106,8 @@ static const char* group_evaluate(r0h_ctx* ctx, Group& g, uint32_t po2) {
 // root on the host (a blocking read-back: the stream has drained when this returns).  CHECK comes with its coefficients made by its
 // own interpolation (witness == nullptr).
 // With `kept_top` (levels != 0) no tree is built: the group's tree takes its top form from a copy of those digests.
-static const char* group_commit(r0h_ctx* ctx, Group& g, const r0h_buf* witness, uint32_t po2, TreeTop& top, const r0h_buf* kept_top = nullptr, uint32_t levels = 0) {
+// group_build is the commit without the read-back: the tree stands in device memory, its top layer and root not yet anywhere else
+static const char* group_build(r0h_ctx* ctx, Group& g, const r0h_buf* witness, uint32_t po2, const r0h_buf* kept_top = nullptr, uint32_t levels = 0) {
   if (witness) {
     const size_t bytes = ((size_t)g.count << po2) * 4;
     R0H_REQUIRE(bytes <= witness->bytes, "prove_segment: witness buffer holds fewer than %u columns of 2^%u", g.count, po2);
@@ -122,6 +125,10 @@ static const char* group_commit(r0h_ctx* ctx, Group& g, const r0h_buf* witness, 
   } else {
     R0H_TRY(tree_build(ctx, g.tree, g.evaluated.get()));
   }
+  return nullptr;
+}
+static const char* group_commit(r0h_ctx* ctx, Group& g, const r0h_buf* witness, uint32_t po2, TreeTop& top, const r0h_buf* kept_top = nullptr, uint32_t levels = 0) {
+  R0H_TRY(group_build(ctx, g, witness, po2, kept_top, levels));
   return tree_top(ctx, g.tree, top);
 }
 
@@ -153,18 +160,98 @@ __global__ void sub_head_kernel(uint32_t* __restrict__ combos, const uint32_t* _
   uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < n) combos[fix[2 * k]] = sub(combos[fix[2 * k]], fix[2 * k + 1]);
 }
+
+// ---- the small kernels of steps 5 and 6 under r0h_ctx_set_device_finish: what the host computes from z and the DEEP mix when it has
+// them, computed where the device's transcript left them.  All latency-bound, a lane per item; extension words are read and written
+// word by word, so no table needs more than word alignment.
+__device__ __forceinline__ Fp4 ldw4(const uint32_t* p) { return Fp4{{p[0], p[1], p[2], p[3]}}; }
+__device__ __forceinline__ void stw4(uint32_t* p, const Fp4& v) { p[0] = v.e[0]; p[1] = v.e[1]; p[2] = v.e[2]; p[3] = v.e[3]; }
+
+// the point table: pts[i] = z * wpow[i] for the circuit's i-th distinct back (wpow[i] = omega^-back, host-known), pts[n_backs] = z^4
+__global__ __launch_bounds__(64) void deep_points_kernel(uint32_t* __restrict__ pts, const uint32_t* __restrict__ z, const uint32_t* __restrict__ wpow, uint32_t n_backs) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  const Fp4 zz = ldw4(z);
+  if (i < n_backs) stw4(pts + 4 * (size_t)i, scale(zz, wpow[i]));
+  else if (i == n_backs) stw4(pts + 4 * (size_t)i, fp4_pow(zz, 4));
+}
+
+// poly_interpolate on the device, a register per lane: regs[3r ..) = (first tap, taps, first work slot).  Register r's taps t have
+// x = pts[tap_pt[t]] and y = eval_u[t]; its interpolant goes to coeff_u[first tap ..).  M(x) = prod (x - x_j) is built once in the
+// register's taps + 1 work slots; per tap i the quotient M / (x - x_i) comes from synthetic division, twice: once for its value at x_i
+// (the Lagrange denominator), once to add it, scaled, into the interpolant.  Quadratic in the taps, and right for any count of them.
+// The lanes behind the registers copy CHECK's sixteen openings.
+__global__ __launch_bounds__(64) void interpolate_regs_kernel(uint32_t* __restrict__ coeff_u, const uint32_t* __restrict__ eval_u, const uint32_t* __restrict__ pts,
+                                                               const uint32_t* __restrict__ tap_pt, const uint32_t* __restrict__ regs, uint32_t n_regs, uint32_t n_taps,
+                                                               uint32_t* __restrict__ work) {
+  const uint32_t r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= n_regs) {
+    const uint32_t i = r - n_regs;
+    if (i < R0H_CHECK_SIZE) stw4(coeff_u + 4 * (size_t)(n_taps + i), ldw4(eval_u + 4 * (size_t)(n_taps + i)));
+    return;
+  }
+  const uint32_t first = regs[3 * r], n = regs[3 * r + 1];
+  uint32_t* M = work + 4 * (size_t)regs[3 * r + 2];
+  uint32_t* out = coeff_u + 4 * (size_t)first;
+  auto x = [&](uint32_t j) { return ldw4(pts + 4 * (size_t)tap_pt[first + j]); };
+  stw4(M, fp4_one());
+  for (uint32_t j = 0; j < n; j++) {  // M <- M * (x - x_j); j is M's degree going in
+    const Fp4 xj = x(j);
+    stw4(M + 4 * (j + 1), fp4_zero());
+    for (uint32_t k = j + 1; k-- > 0;) {
+      const Fp4 m = ldw4(M + 4 * k);
+      stw4(M + 4 * (k + 1), ldw4(M + 4 * (k + 1)) + m);
+      stw4(M + 4 * k, fp4_zero() - m * xj);
+    }
+  }
+  for (uint32_t k = 0; k < n; k++) stw4(out + 4 * k, fp4_zero());
+  for (uint32_t i = 0; i < n; i++) {
+    const Fp4 xi = x(i);
+    // q = M / (x - x_i): q[n-1] = M[n], q[k-1] = M[k] + x_i q[k]; its value at x_i by Horner's rule over the same descent
+    Fp4 q = ldw4(M + 4 * n), d = q;
+    for (uint32_t k = n - 1; k >= 1; k--) {
+      q = ldw4(M + 4 * k) + xi * q;
+      d = d * xi + q;
+    }
+    const Fp4 s = ldw4(eval_u + 4 * (size_t)(first + i)) * fp4_inv(d);
+    q = ldw4(M + 4 * n);
+    stw4(out + 4 * (n - 1), ldw4(out + 4 * (n - 1)) + q * s);
+    for (uint32_t k = n - 1; k >= 1; k--) {
+      q = ldw4(M + 4 * k) + xi * q;
+      stw4(out + 4 * (k - 1), ldw4(out + 4 * (k - 1)) + q * s);
+    }
+  }
+}
+
+// the values of sub_head_kernel's fix list: entry e covers the pairs [4e, 4e + 4) (an extension coefficient of a combo's head) and is
+// the sum over its terms t in [begin[e], begin[e + 1]) of pw[terms[2t]] * coeff_u[terms[2t + 1]], pw the powers of the DEEP mix
+__global__ __launch_bounds__(64) void deep_head_kernel(uint32_t* __restrict__ fix, const uint32_t* __restrict__ pw, const uint32_t* __restrict__ coeff_u,
+                                                        const uint32_t* __restrict__ begin, const uint32_t* __restrict__ terms, uint32_t n_entries) {
+  const uint32_t e = blockIdx.x * 64 + threadIdx.x;
+  if (e >= n_entries) return;
+  Fp4 h = fp4_zero();
+  for (uint32_t t = begin[e]; t < begin[e + 1]; t++) h = h + ldw4(pw + 4 * (size_t)terms[2 * t]) * ldw4(coeff_u + 4 * (size_t)terms[2 * t + 1]);
+#pragma unroll
+  for (int q = 0; q < 4; q++) fix[2 * (4 * (size_t)e + q) + 1] = h.e[q];
+}
+
 struct Round { Tree tree; DevBuf evaluated; };  // a committed FRI round
 
 // Steps 7 and 8 with the transcript on the device (r0h_ctx_set_device_transcript): where the seal's words of the two steps stand in the
 // proof's tail block, in words.  The block is read back once, at the end of step 8.
 struct IopFree { void operator()(r0h_iop* iop) const { r0h_iop_free(iop); } };
 struct TailLayout {
+  // the head, under r0h_ctx_set_device_finish only: what steps 3-6 add to the seal, and the verdict of the DEEP divisions
+  bool head = false;
+  size_t accum_top = 0, check_top = 0;  // the two groups' top layers, 8 * top_size words each
+  size_t coeff_u = 0;                   // 4 * n_u words: per register its interpolant, then CHECK's sixteen openings
+  size_t report = 0;                    // one word: 0, or 1 + the first DEEP division whose remainder is not zero
   std::vector<size_t> round_top;  // per FRI round: its tree's top layer, 8 * top_size words
   size_t final_coeffs = 0;        // 4 * final_degree words
   size_t idx = 0;                 // the query rows [n_trees][R0H_QUERIES]
   std::vector<size_t> opened;     // per tree: R0H_QUERIES packed openings, and behind a top-form tree's the two report words of merkle_open_top
   size_t seal_words = 0;          // everything above: what the read-back brings home
   size_t fold_mix = 0;            // per FRI round the four words of its fold mix (the device's own: never read back)
+  size_t poly_mix = 0, z = 0, deep_mix = 0;  // with the head: the challenges of steps 4-6, four words each (the device's own as well)
   size_t words = 0;
 };
 
@@ -213,6 +300,14 @@ struct r0h_proof {
   std::unique_ptr<r0h_iop, r0h::IopFree> iop;
   r0h::DevBuf tail;
   r0h::TailLayout tail_at;
+  // steps 3-8 under r0h_ctx_set_device_finish: the point table of steps 5 and 6 (a point per distinct back of the circuit's taps, then
+  // z^4; behind them the host-known omega^-back), the combo of every DEEP division in job order (whom the tail's report word names), and
+  // whether the steps have been enqueued (r0h_proof_finish_enqueue) and wait for r0h_proof_finish_collect
+  r0h::DevBuf points;
+  uint32_t n_points = 0;
+  uint32_t point_of_back[64] = {0};
+  std::vector<uint32_t> divide_combo;
+  bool enqueued = false;
   r0h_proof(r0h_ctx* c, const r0h_circuit* ci, uint32_t p, const r0h_buf* code_columns, const r0h_code_commit* cc)
       : ctx(c), circ(ci), po2(p), io(c->hashfn, &c->p2_host), own_code(ci->group_size[R0H_GROUP_CODE], p), code(cc ? cc : &own_code),
         g_accum(ci->group_size[R0H_GROUP_ACCUM], (size_t)4 << p), g_data(ci->group_size[R0H_GROUP_DATA], (size_t)4 << p),
@@ -540,14 +635,26 @@ static std::vector<const Tree*> proof_trees(const r0h_proof& st) {  // in the or
   return trees;
 }
 
-static const char* fri_commit_device(r0h_proof& st) {
+// The tail block laid out and taken from the pool, and the host generator handed over to the device (its state goes up in stream
+// order).  With `head` the block starts with what steps 3-6 add to the seal; every part of it keeps its offset modulo 8 words.
+static const char* tail_open(r0h_proof& st, bool head) {
   r0h_ctx* ctx = st.ctx;
-  profile_phase(ctx, "fri_commit");
   const FriSchedule fri((size_t)1 << st.po2);
   TailLayout& at = st.tail_at;
   at = TailLayout();
   {
     size_t w = 0;
+    if (head) {
+      at.head = true;
+      at.accum_top = w;
+      w += 8 * st.g_accum.tree.mp.top_size;
+      at.check_top = w;
+      w += 8 * st.g_check.tree.mp.top_size;
+      at.coeff_u = w;
+      w += 4 * (st.circ->taps.size() + R0H_CHECK_SIZE);
+      at.report = w;
+      w = (w + 1 + 7) & ~(size_t)7;
+    }
     for (const FriRound& fr : fri.rounds) { at.round_top.push_back(w); w += 8 * MerkleShape(fr.rows, R0H_FRI_FOLD * 4).top_size; }
     at.final_coeffs = w;
     w += 4 * fri.final_degree;
@@ -560,12 +667,216 @@ static const char* fri_commit_device(r0h_proof& st) {
     }
     at.seal_words = w;
     at.fold_mix = w;
-    at.words = w + 4 * fri.rounds.size();
+    w += 4 * fri.rounds.size();
+    if (head) {
+      w = (w + 3) & ~(size_t)3;
+      at.poly_mix = w;
+      at.z = w + 4;
+      at.deep_mix = w + 8;
+      w += 12;
+    }
+    at.words = w;
   }
   R0H_TRY(st.tail.alloc(ctx, at.words * 4));
   r0h_iop* iop = nullptr;
   R0H_TRY(iop_make(ctx, st.io.rng, &iop));
   st.iop.reset(iop);
+  return nullptr;
+}
+
+// a group committed on the device transcript: its top layer device to device into the tail, its root -- node 1 -- into the generator
+static const char* proof_commit_device(r0h_proof& st, Group& g, const r0h_buf* witness, size_t top_at) {
+  R0H_TRY(group_build(st.ctx, g, witness, st.po2));
+  const size_t top_words = 8 * g.tree.mp.top_size;  // nodes [top_size, 2 * top_size)
+  R0H_TRY(copy_words(st.ctx, st.tail.get(), top_at, g.tree.nodes.get(), top_words, top_words));
+  return r0h_iop_commit(st.iop.get(), g.tree.nodes.get(), 8);
+}
+
+// ---- steps 3-6 on the device transcript (r0h_ctx_set_device_finish).  The generator goes up before step 3; from there every challenge
+// is drawn into the tail's device-only words and the tables that depend on it are filled by kernels, so nothing waits for the stream
+// (but the witness checker, where it is on).  The seal words of the four steps stand in the tail's head.
+static const char* commit_accum_device(r0h_proof& st, const r0h_buf* accum) {
+  r0h_ctx* ctx = st.ctx;
+  if (!st.g_data.evaluated) {
+    profile_phase(ctx, "evaluate_data_again");
+    R0H_TRY(group_evaluate(ctx, st.g_data, st.po2));
+  }
+  if (st.check_data) {  // reads its table back: the one wait of an enqueue
+    profile_phase(ctx, "check_witness");
+    R0H_TRY(require_witness("prove_segment", ctx, st.circ, st.po2, accum, st.check_code, st.check_data, st.global.data(), st.mix.data()));
+  }
+  profile_phase(ctx, "commit_accum");
+  return proof_commit_device(st, st.g_accum, accum, st.tail_at.accum_top);
+}
+
+static const char* commit_check_device(r0h_proof& st) {
+  r0h_ctx* ctx = st.ctx;
+  Group& g_check = st.g_check;
+  profile_phase(ctx, "eval_check");
+  R0H_TRY(r0h_iop_draw_ext(st.iop.get(), st.tail.get(), st.tail_at.poly_mix, 1));
+  R0H_TRY(g_check.coeffs.alloc(ctx, ((size_t)R0H_INV_RATE << st.po2) * 16));
+  R0H_TRY(eval_check_dev(ctx, st.circ, st.po2, st.g_accum.evaluated.get(), st.code->g.evaluated.get(), st.g_data.evaluated.get(), st.global.data(), st.mix.data(),
+                         u32(st.tail.get()) + st.tail_at.poly_mix, g_check.coeffs.get()));
+  profile_phase(ctx, "commit_check");
+  R0H_TRY(r0h_batch_interpolate_ntt(ctx, g_check.coeffs.get(), 4, st.po2 + 2));
+  return proof_commit_device(st, g_check, nullptr, st.tail_at.check_top);
+}
+
+static const char* evaluate_at_z_device(r0h_proof& st) {
+  r0h_ctx* ctx = st.ctx;
+  const r0h_circuit* circ = st.circ;
+  profile_phase(ctx, "evaluate_at_z");
+  uint32_t* tail = u32(st.tail.get());
+  R0H_TRY(r0h_iop_draw_ext(st.iop.get(), st.tail.get(), st.tail_at.z, 1));
+  // the point table: a point per distinct back (the blob format admits backs below 64), then z^4
+  st.back_one = rou_rev(st.po2);
+  bool has_back[64] = {false};
+  for (const Tap& t : circ->taps) has_back[t.back] = true;
+  std::vector<uint32_t> wpow;
+  for (uint32_t b = 0; b < 64; b++)
+    if (has_back[b]) { st.point_of_back[b] = (uint32_t)wpow.size(); wpow.push_back(fpow(st.back_one, b)); }
+  const uint32_t n_backs = (uint32_t)wpow.size();
+  st.n_points = n_backs + 1;
+  R0H_TRY(st.points.alloc(ctx, (size_t)(4 * st.n_points + n_backs) * 4));
+  uint32_t* pts = u32(st.points.get());
+  R0H_TRY(stage_h2d(ctx, pts + 4 * st.n_points, wpow.data(), wpow.size() * 4));
+  {
+    KScope ks(ctx, "deep_points_kernel", 16.0 * st.n_points);
+    hipLaunchKernelGGL(deep_points_kernel, dim3((st.n_points + 63) / 64), dim3(64), 0, ctx->stream, pts, tail + st.tail_at.z, pts + 4 * st.n_points, n_backs);
+    R0H_TRY(launch_ok("deep_points_kernel"));
+  }
+  const uint32_t n_taps = (uint32_t)circ->taps.size(), n_u = n_taps + R0H_CHECK_SIZE, n_regs = (uint32_t)circ->regs.size();
+  std::vector<uint32_t> which(n_u), pt(n_u);
+  for (uint32_t t = 0; t < n_taps; t++) { which[t] = circ->taps[t].offset; pt[t] = st.point_of_back[circ->taps[t].back]; }
+  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) { which[n_taps + i] = i; pt[n_taps + i] = n_backs; }
+  DevBuf d_eval;
+  R0H_TRY(d_eval.alloc(ctx, (size_t)n_u * 16));
+  for (int g = 0; g < 4; g++) {
+    const uint32_t b = circ->group_tap_begin[g], e = g < 3 ? circ->group_tap_begin[g + 1] : n_u;
+    if (e == b) continue;
+    r0h_buf view = buf_view(d_eval.get(), (size_t)b * 16, (size_t)(e - b) * 16);
+    R0H_TRY(evaluate_any_points(ctx, st.group(g).coeffs.get(), st.po2, which.data() + b, pt.data() + b, e - b, pts, st.n_points, &view, true));
+  }
+  // the registers' table: [point of every tap][per register: first tap, taps, first work slot], then the work slots (taps + 1 a register)
+  std::vector<uint32_t> table(pt.begin(), pt.begin() + n_taps);
+  uint32_t work_slots = 0;
+  for (const Reg& reg : circ->regs) {
+    R0H_REQUIRE(reg.size >= 1 && reg.size <= 64, "prove_segment: register with %u taps", reg.size);
+    table.insert(table.end(), {reg.first_tap, reg.size, work_slots});
+    work_slots += reg.size + 1;
+  }
+  DevBuf d_regs;
+  R0H_TRY(d_regs.alloc(ctx, (table.size() + 4 * (size_t)work_slots) * 4));
+  R0H_TRY(stage_h2d(ctx, d_regs->ptr, table.data(), table.size() * 4));
+  {
+    KScope ks(ctx, "interpolate_regs_kernel", 32.0 * n_u);
+    const uint32_t* d_table = u32(d_regs.get());
+    hipLaunchKernelGGL(interpolate_regs_kernel, dim3((n_regs + R0H_CHECK_SIZE + 63) / 64), dim3(64), 0, ctx->stream, tail + st.tail_at.coeff_u, u32(d_eval.get()), pts, d_table,
+                       d_table + n_taps, n_regs, n_taps, u32(d_regs.get()) + table.size());
+    R0H_TRY(launch_ok("interpolate_regs_kernel"));
+  }
+  return r0h_iop_commit_elems(st.iop.get(), st.tail.get(), st.tail_at.coeff_u, 4 * (size_t)n_u);
+}
+
+// step 6, second part: the same fix list, its indices from the host and its values from deep_head_kernel
+static const char* subtract_interpolants_device(r0h_proof& st, r0h_buf* combos, uint32_t n_combos) {
+  r0h_ctx* ctx = st.ctx;
+  const uint32_t n_taps = (uint32_t)st.circ->taps.size(), n_regs = (uint32_t)st.circ->regs.size();
+  std::vector<uint32_t> head_len(n_combos + 1, 0);
+  for (const Reg& reg : st.circ->regs) {
+    R0H_REQUIRE(reg.size <= 64, "prove_segment: register with more than 64 taps");
+    if (reg.size > head_len[reg.combo]) head_len[reg.combo] = reg.size;
+  }
+  head_len[n_combos] = 1;
+  R0H_REQUIRE(((size_t)(n_combos + 1) << st.po2) * 4 < ((size_t)1 << 32), "prove_segment: combos buffer exceeds 32-bit word indexing");
+  // the running order of the mix: a power per register, then one per CHECK column
+  std::vector<uint32_t> fix, begin(1, 0u), terms;
+  for (uint32_t k = 0; k <= n_combos; k++)
+    for (uint32_t i = 0; i < head_len[k]; i++) {
+      for (uint32_t q = 0; q < 4; q++) {
+        fix.push_back((uint32_t)((((size_t)k << st.po2) + i) * 4 + q));
+        fix.push_back(0u);  // deep_head_kernel's
+      }
+      if (k < n_combos) {
+        for (uint32_t r = 0; r < n_regs; r++) {
+          const Reg& reg = st.circ->regs[r];
+          if (reg.combo == k && reg.size > i) terms.insert(terms.end(), {r, reg.first_tap + i});
+        }
+      } else {
+        for (uint32_t j = 0; j < R0H_CHECK_SIZE; j++) terms.insert(terms.end(), {n_regs + j, n_taps + j});
+      }
+      begin.push_back((uint32_t)(terms.size() / 2));
+    }
+  const uint32_t n_entries = (uint32_t)begin.size() - 1, n_pw = n_regs + R0H_CHECK_SIZE;
+  std::vector<uint32_t> table(fix);  // [fix pairs][begin][terms], then the powers of the mix
+  table.insert(table.end(), begin.begin(), begin.end());
+  table.insert(table.end(), terms.begin(), terms.end());
+  DevBuf d_fix;
+  R0H_TRY(d_fix.alloc(ctx, (table.size() + 4 * (size_t)n_pw) * 4));
+  R0H_TRY(stage_h2d(ctx, d_fix->ptr, table.data(), table.size() * 4));
+  uint32_t *d_table = u32(d_fix.get()), *d_pw = d_table + table.size();
+  const uint32_t* tail = u32(st.tail.get());
+  R0H_TRY(ext_powers(ctx, d_pw, tail + st.tail_at.deep_mix, nullptr, n_pw));
+  {
+    KScope ks(ctx, "deep_head_kernel", 32.0 * (double)(terms.size() / 2));
+    hipLaunchKernelGGL(deep_head_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, ctx->stream, d_table, d_pw, tail + st.tail_at.coeff_u, d_table + fix.size(),
+                       d_table + fix.size() + begin.size(), n_entries);
+    R0H_TRY(launch_ok("deep_head_kernel"));
+  }
+  const uint32_t nf = (uint32_t)(fix.size() / 2);
+  hipLaunchKernelGGL(sub_head_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, u32(combos), d_table, nf);
+  return launch_ok("sub_head_kernel");
+}
+
+static const char* deep_device(r0h_proof& st) {
+  r0h_ctx* ctx = st.ctx;
+  const r0h_circuit* circ = st.circ;
+  const uint32_t po2 = st.po2, n = 1u << po2;
+  profile_phase(ctx, "mix_combos");
+  uint32_t* tail = u32(st.tail.get());
+  R0H_TRY(r0h_iop_draw_ext(st.iop.get(), st.tail.get(), st.tail_at.deep_mix, 1));
+  const uint32_t n_combos = (uint32_t)circ->combo_begin.size() - 1;
+  DevBuf combos;
+  R0H_TRY(combos.alloc(ctx, (size_t)(n_combos + 1) * n * 16));
+  R0H_TRY(r0h_buf_zero(ctx, combos.get()));
+  uint32_t first_exp = 0;  // a column's exponent is its position in the running order over the four groups
+  for (int g = 0; g < 4; g++) {
+    const uint32_t gs = st.group(g).count;
+    std::vector<uint32_t> combo_of(gs, g < 3 ? 0u : n_combos);
+    for (const Reg& reg : circ->regs)
+      if (reg.group == (uint32_t)g) combo_of[reg.offset] = reg.combo;
+    R0H_TRY(mix_poly_coeffs_dev(ctx, combos.get(), first_exp, tail + st.tail_at.deep_mix, st.group(g).coeffs.get(), combo_of.data(), gs, po2));
+    first_exp += gs;
+  }
+  R0H_TRY(bit_reverse_ext(ctx, combos.get(), n_combos + 1, po2));
+  R0H_TRY(subtract_interpolants_device(st, combos.get(), n_combos));
+  profile_phase(ctx, "deep_divide");
+  std::vector<uint32_t> job_pt;
+  st.divide_combo.clear();
+  for (uint32_t k = 0; k <= n_combos; k++) {
+    if (k < n_combos) {
+      for (uint32_t b = circ->combo_begin[k]; b < circ->combo_begin[k + 1]; b++) {
+        st.divide_combo.push_back(k);
+        job_pt.push_back(st.point_of_back[circ->combo_backs[b]]);
+      }
+    } else {
+      st.divide_combo.push_back(k);
+      job_pt.push_back(st.n_points - 1);  // z^4
+    }
+  }
+  R0H_TRY(poly_divide_batch_points(ctx, combos.get(), n, st.divide_combo.data(), job_pt.data(), (uint32_t)job_pt.size(), u32(st.points.get()), st.n_points, tail + st.tail_at.report));
+  R0H_TRY(st.fri_coeffs.alloc(ctx, (size_t)n * 16));
+  R0H_TRY(r0h_eltwise_sum_extelem(ctx, st.fri_coeffs.get(), combos.get(), n_combos + 1, n));
+  return r0h_batch_bit_reverse(ctx, st.fri_coeffs.get(), 4, po2);
+}
+
+static const char* fri_commit_device(r0h_proof& st) {
+  r0h_ctx* ctx = st.ctx;
+  profile_phase(ctx, "fri_commit");
+  const FriSchedule fri((size_t)1 << st.po2);
+  if (!st.iop) R0H_TRY(tail_open(st, false));  // (under r0h_ctx_set_device_finish the generator went up before step 3)
+  const TailLayout& at = st.tail_at;
+  r0h_iop* iop = st.iop.get();
   for (size_t r = 0; r < fri.rounds.size(); r++) {
     const FriRound& fr = fri.rounds[r];
     Round rd{Tree(fr.rows, R0H_FRI_FOLD * 4), DevBuf()};
@@ -609,14 +920,32 @@ static const char* queries_device(r0h_proof& st) {
     else
       R0H_TRY(merkle_open(ctx, out, u32(tr.matrix), u32(tr.nodes.get()), d_idx, nq, (uint32_t)tr.mp.rows, (uint32_t)tr.mp.cols));
   }
+  return nullptr;
+}
+
+// The tail block read back -- the one wait of the steps that ran on the device transcript -- then the verdicts the host draws from
+// it, and its parts appended to the seal in the order the host steps write them
+static const char* tail_collect(r0h_proof& st) {
+  r0h_ctx* ctx = st.ctx;
+  const TailLayout& at = st.tail_at;
+  const std::vector<const Tree*> trees = proof_trees(st);
+  const uint32_t nq = R0H_QUERIES, n_trees = (uint32_t)trees.size();
   std::vector<uint32_t> host(at.seal_words);
-  R0H_TRY(r0h_buf_d2h(ctx, st.tail.get(), 0, host.data(), host.size() * 4));  // the one wait of the two steps
+  R0H_TRY(r0h_buf_d2h(ctx, st.tail.get(), 0, host.data(), host.size() * 4));
   st.iop.reset();
   st.tail.reset();
+  WriteIop& io = st.io;
+  if (at.head) {
+    const uint32_t report = host[at.report];
+    R0H_REQUIRE(report <= st.divide_combo.size(), "prove_segment: the DEEP report word %u names none of the %zu divisions", report, st.divide_combo.size());
+    R0H_REQUIRE(!report, "prove_segment: DEEP quotient of combo %u has a non-zero remainder (witness violates the taps?)", st.divide_combo[report ? report - 1 : 0]);
+    io.write(host.data() + at.accum_top, at.check_top - at.accum_top);
+    io.write(host.data() + at.check_top, at.coeff_u - at.check_top);
+    io.write(host.data() + at.coeff_u, at.report - at.coeff_u);
+  }
   for (uint32_t t = 0; t < n_trees; t++)
     if (trees[t]->top_levels)
       R0H_TRY(merkle_open_top_verdict("r0h_proof_finish", host.data() + at.opened[t] + (size_t)nq * trees[t]->mp.opening_words(), host.data() + at.idx + (size_t)t * nq));
-  WriteIop& io = st.io;
   for (size_t r = 0; r < st.rounds.size(); r++) io.write(host.data() + at.round_top[r], 8 * st.rounds[r].tree.mp.top_size);
   io.write(host.data() + at.final_coeffs, at.idx - at.final_coeffs);
   for (uint32_t q = 0; q < nq; q++)
@@ -627,11 +956,45 @@ static const char* queries_device(r0h_proof& st) {
   return nullptr;
 }
 
+static const char* require_finishable(const r0h_proof& st, const char* caller) {
+  R0H_REQUIRE(st.mix_drawn, "%s: this circuit has late public inputs: r0h_proof_late comes first", caller);
+  R0H_REQUIRE(st.io.suite->fn() == st.ctx->hashfn, "%s: the proof was begun under the %s hash suite, its context is now on %s", caller, hashfn_name(st.io.suite->fn()),
+              hashfn_name(st.ctx->hashfn));
+  return nullptr;
+}
+// r0h_ctx_set_device_finish: steps 3-8 enqueued on the proof's stream, the end of the last phase marked behind them.  Nothing here
+// waits for the stream (the witness checker does, where it is on): the host generator is not touched after the hand-over.
+static const char* proof_finish_enqueue(r0h_proof& st, const r0h_buf* accum) {
+  R0H_TRY(require_finishable(st, "r0h_proof_finish"));
+  R0H_REQUIRE(!st.enqueued, "r0h_proof_finish_enqueue: the proof has been enqueued already");
+  R0H_TRY(tail_open(st, true));
+  R0H_TRY(commit_accum_device(st, accum));
+  R0H_TRY(commit_check_device(st));
+  R0H_TRY(evaluate_at_z_device(st));
+  R0H_TRY(deep_device(st));
+  R0H_TRY(fri_commit_device(st));
+  R0H_TRY(queries_device(st));
+  profile_end(st.ctx);
+  st.enqueued = true;
+  return nullptr;
+}
+// the read-back (one wait), the host's verdicts, the seal; then the profile closes (a second wait, of a stream that has drained)
+static const char* proof_finish_collect(r0h_proof& st, std::vector<uint32_t>& seal) {
+  R0H_REQUIRE(st.enqueued, "r0h_proof_finish_collect: the proof has not been enqueued (r0h_proof_finish_enqueue comes first)");
+  st.enqueued = false;  // the stream has drained once the read-back returns, whatever it brings
+  R0H_TRY(tail_collect(st));
+  R0H_TRY(profile_collect(st.ctx));
+  seal.swap(st.io.proof);
+  return nullptr;
+}
+
 // steps 3-8 of DESIGN.md 2, each under its own phase marks; the seal is the transcript's written words
 static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector<uint32_t>& seal) {
-  R0H_REQUIRE(st.mix_drawn, "r0h_proof_finish: this circuit has late public inputs: r0h_proof_late comes first");
-  R0H_REQUIRE(st.io.suite->fn() == st.ctx->hashfn, "r0h_proof_finish: the proof was begun under the %s hash suite, its context is now on %s",
-              hashfn_name(st.io.suite->fn()), hashfn_name(st.ctx->hashfn));
+  R0H_TRY(require_finishable(st, "r0h_proof_finish"));
+  if (st.ctx->device_finish) {  // every step on the device generator: enqueue, then the one read-back and the profile's close
+    R0H_TRY(proof_finish_enqueue(st, accum));
+    return proof_finish_collect(st, seal);
+  }
   R0H_TRY(commit_accum(st, accum));
   R0H_TRY(commit_check(st));
   R0H_TRY(evaluate_at_z(st));
@@ -639,6 +1002,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
   if (st.ctx->device_transcript) {  // the same two steps with the generator on the device: one wait instead of 2 R + 5
     R0H_TRY(fri_commit_device(st));
     R0H_TRY(queries_device(st));
+    R0H_TRY(tail_collect(st));
   } else {
     R0H_TRY(fri_commit(st));
     R0H_TRY(queries(st));
@@ -797,7 +1161,7 @@ const char* r0h_proof_finish(r0h_proof* proof, const r0h_buf* accum, uint32_t* s
   R0H_TRY_HIP(hipSetDevice(proof->ctx->device));
   std::vector<uint32_t> seal;
   const char* err = proof_finish(*proof, accum, seal);
-  delete proof;  // consumed either way
+  r0h_proof_abort(proof);  // consumed either way (an error under r0h_ctx_set_device_finish may leave steps in flight: they run out first)
   return err ? err : seal_copy_out("r0h_proof_finish", seal, seal_out, seal_cap, seal_words_out);
   R0H_GUARD_END
 }
@@ -823,7 +1187,41 @@ const char* r0h_proof_globals(const r0h_proof* proof, uint32_t* globals_out) {
   return nullptr;
 }
 
+// The two halves of r0h_proof_finish under r0h_ctx_set_device_finish (include/r0hip.h)
+const char* r0h_proof_finish_enqueue(r0h_proof* proof, const r0h_buf* accum) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(proof && accum, "r0h_proof_finish_enqueue: NULL argument");
+  R0H_REQUIRE(!proof->enqueued, "r0h_proof_finish_enqueue: the proof has been enqueued already");
+  const char* err = nullptr;
+  if (!proof->ctx->device_finish) err = make_error("r0h_proof_finish_enqueue: the proof's context has r0h_ctx_set_device_finish off: only r0h_proof_finish takes this proof");
+  if (!err) {
+    R0H_TRY_HIP(hipSetDevice(proof->ctx->device));
+    err = proof_finish_enqueue(*proof, accum);
+  }
+  if (err) r0h_proof_abort(proof);  // consumed, as by r0h_proof_finish; what was enqueued before the error has run when the buffers go
+  return err;
+  R0H_GUARD_END
+}
+const char* r0h_proof_finish_collect(r0h_proof* proof, uint32_t* seal_out, size_t seal_cap, size_t* seal_words_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(proof && seal_words_out, "r0h_proof_finish_collect: NULL argument");
+  R0H_REQUIRE(proof->enqueued, "r0h_proof_finish_collect: the proof has not been enqueued (r0h_proof_finish_enqueue comes first)");
+  R0H_TRY_HIP(hipSetDevice(proof->ctx->device));
+  std::vector<uint32_t> seal;
+  const char* err = proof_finish_collect(*proof, seal);
+  r0h_proof_abort(proof);  // consumed either way
+  return err ? err : seal_copy_out("r0h_proof_finish_collect", seal, seal_out, seal_cap, seal_words_out);
+  R0H_GUARD_END
+}
+
 const char* r0h_proof_abort(r0h_proof* proof) {
+  if (!proof) return nullptr;
+  // steps may be in flight on its stream (enqueued and not collected, or an enqueue that ended in an error): they read the caller's
+  // buffers, so they have run before anything is released
+  if (proof->enqueued || proof->iop) {
+    (void)hipSetDevice(proof->ctx->device);
+    (void)ctx_wait(proof->ctx);
+  }
   delete proof;
   return nullptr;
 }

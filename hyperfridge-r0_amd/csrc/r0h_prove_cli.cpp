@@ -8,6 +8,8 @@
 // refused together with any of the receipt options and with --elf.
 // --device-transcript 1 (both modes) turns r0h_ctx_set_device_transcript on: the FRI commitments and the queries of every proof run on a transcript
 // on the device, one read-back for both steps; the seals and receipts are the same words.
+// --device-finish 1 (both modes) turns r0h_ctx_set_device_finish on: every step of a proof's second half runs on that transcript, one read-back
+// for all of them; the seals and receipts are the same words.
 // --check-witness 1 (both modes; [--check-code-object file.hsaco] [--term-names file.txt]) turns r0h_ctx_set_check_witness on: every segment's
 // witness is checked on the device before its ACCUM group is committed, and a violated segment ends the run with the term, its row count
 // and its first row -- and the term's name, from --term-names or <circuit>.terms.txt beside the blob (one name per line, in term
@@ -102,7 +104,9 @@ int main(int argc, char** argv) {
            "       --session-keep-tree-tops L: with it, an evicted segment also keeps the top of its DATA tree down to L levels above the leaves (1..8) and is committed again "
            "without hashing -- the same receipt; the run reports how many were replayed from their top (default 0: off)\n"
            "       --device-transcript 0|1: with 1 every proof runs its FRI commitments and its queries on a Fiat-Shamir transcript on the device, with one read-back for both steps "
-           "instead of one per commitment and per opened tree -- the same seals and receipts (default 0: the transcript stays on the host)\n%s\n", r0h_version());
+           "instead of one per commitment and per opened tree -- the same seals and receipts (default 0: the transcript stays on the host)\n"
+           "       --device-finish 0|1: with 1 every proof runs ALL the steps of its second half -- ACCUM, CHECK, the openings, DEEP, FRI, the queries -- on the transcript on the "
+           "device, with one read-back for all of them, whatever --device-transcript says -- the same seals and receipts (default 0)\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   // --compress takes no value: it is taken out of the arguments before the "--option value" pairs are read
@@ -127,6 +131,7 @@ int main(int argc, char** argv) {
   double session_device_limit_gb = 0;  // --session-device-limit-gb: r0h_ctx_set_session_device_limit of every session context
   unsigned session_keep_tree_tops = 0;  // --session-keep-tree-tops: r0h_ctx_set_session_tree_tops of every session context
   std::string device_transcript = "0";  // --device-transcript: r0h_ctx_set_device_transcript of every context
+  std::string device_finish = "0";      // --device-finish: r0h_ctx_set_device_finish of every context
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--code-object")) co_path = argv[i + 1];
     else if (!strcmp(argv[i], "--po2")) po2 = (unsigned)atoi(argv[i + 1]);
@@ -147,6 +152,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--session-device-limit-gb")) session_device_limit_gb = atof(argv[i + 1]);
     else if (!strcmp(argv[i], "--session-keep-tree-tops")) session_keep_tree_tops = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--device-transcript")) device_transcript = argv[i + 1];
+    else if (!strcmp(argv[i], "--device-finish")) device_finish = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
     else if (!strcmp(argv[i], "--journal")) journal_text = argv[i + 1];
@@ -182,6 +188,10 @@ int main(int argc, char** argv) {
   }
   if (device_transcript != "0" && device_transcript != "1") {
     fprintf(stderr, "r0h_prove: --device-transcript is 0 or 1, not %s\n", device_transcript.c_str());
+    return 2;
+  }
+  if (device_finish != "0" && device_finish != "1") {
+    fprintf(stderr, "r0h_prove: --device-finish is 0 or 1, not %s\n", device_finish.c_str());
     return 2;
   }
   if (hashfn != "poseidon2" && hashfn != "sha-256") { fprintf(stderr, "r0h_prove: --hashfn is poseidon2 or sha-256, not %s\n", hashfn.c_str()); return 1; }
@@ -227,6 +237,7 @@ int main(int argc, char** argv) {
     if (session_device_limit_gb > 0) CHECK(r0h_ctx_set_session_device_limit(ctx, std::max<uint64_t>(1, (uint64_t)(session_device_limit_gb * (double)(1ull << 30)))));
     if (session_keep_tree_tops) CHECK(r0h_ctx_set_session_tree_tops(ctx, session_keep_tree_tops));
     if (device_transcript == "1") CHECK(r0h_ctx_set_device_transcript(ctx, 1));
+    if (device_finish == "1") CHECK(r0h_ctx_set_device_finish(ctx, 1));
     if (check_balance) CHECK(r0h_ctx_set_check_balance(ctx, 1));
     if (check_session) CHECK(r0h_ctx_set_check_session(ctx, 1));
     if (!check_witness) return;

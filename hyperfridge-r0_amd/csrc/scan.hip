@@ -172,6 +172,32 @@ __global__ void divide_remainders_kernel(uint32_t* __restrict__ out, const uint3
   if (j < n_jobs) st4(out + 4 * (size_t)j, ld4(sums + 4 * ((size_t)j * (n_chunks + 1) + n_chunks)));
 }
 
+// The job table's weights filled on the device: job j divides by (x - points[pad0 of job j]), a point the device's transcript made
+// (poly_divide_batch_points).  A lane per job: w, w^E, w^chunk by square-and-multiply.
+__global__ __launch_bounds__(64) void divide_jobs_kernel(DivJob* __restrict__ jobs, const uint32_t* __restrict__ points, uint32_t E, uint32_t chunk, uint32_t n_jobs) {
+  const uint32_t j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= n_jobs) return;
+  const uint32_t* pt = points + 4 * (size_t)jobs[j].pad0;
+  const Fp4 w{{pt[0], pt[1], pt[2], pt[3]}};
+  jobs[j].w = w;
+  jobs[j].wE = fp4_pow(w, E);
+  jobs[j].wChunk = fp4_pow(w, chunk);
+}
+// report[0] = 0, or 1 + the lowest job whose remainder (divide_remainders_kernel's packed output) is not zero.  One wave.
+__global__ __launch_bounds__(64) void divide_report_kernel(uint32_t* __restrict__ report, const uint32_t* __restrict__ rem, uint32_t n_jobs) {
+  uint32_t first = 0xffffffffu;
+  for (uint32_t j = threadIdx.x; j < n_jobs; j += 64) {
+    const Fp4 r = ld4(rem + 4 * (size_t)j);
+    if ((r.e[0] | r.e[1] | r.e[2] | r.e[3]) && j < first) first = j;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const uint32_t o = __shfl_xor(first, off);
+    first = o < first ? o : first;
+  }
+  if (threadIdx.x == 0) report[0] = first == 0xffffffffu ? 0u : first + 1;
+}
+
 }  // namespace r0h
 
 using namespace r0h;
@@ -222,9 +248,15 @@ const char* unpack_ext_columns(r0h_ctx* ctx, uint32_t* cols, const uint32_t* pac
 // (x - points[4j..4j+4)).  Jobs on the same polynomial are applied in the order given.  remainders_host (4 words per job, may be
 // NULL) is filled by ONE blocking copy after everything has been enqueued.  The DEEP step divides ~10 combos by one to three points
 // each: one launch set per "k-th point of every combo" instead of one per (combo, point).
-const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* points, uint32_t n_jobs, uint32_t* remainders_host) {
+// points: four host words per job (poly_divide_batch), or nullptr with the job's point named by pt_idx[j] in the device table d_points and
+// the verdict left in the device word d_report instead of a read-back (poly_divide_batch_points)
+static const char* poly_divide_batch_impl(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* points, const uint32_t* pt_idx,
+                                          const uint32_t* d_points, uint32_t n_points, uint32_t n_jobs, uint32_t* remainders_host, uint32_t* d_report) {
   R0H_GUARD_BEGIN
-  if (!n_jobs) return nullptr;
+  if (!n_jobs) {
+    if (d_report) R0H_TRY_HIP(hipMemsetAsync(d_report, 0, 4, ctx->stream));
+    return nullptr;
+  }
   const ScanGeom g = scan_geom(n);
   const size_t n_polys = polys->bytes / ((size_t)n * 16);
   // pass k holds the k-th job of every polynomial: within a pass the jobs touch different polynomials and run side by side
@@ -242,10 +274,16 @@ const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const ui
   for (const auto& pass : passes)
     for (uint32_t j : pass) {
       DivJob d;
-      d.w = Fp4{{points[4 * (size_t)j], points[4 * (size_t)j + 1], points[4 * (size_t)j + 2], points[4 * (size_t)j + 3]}};
-      d.wE = fp4_pow(d.w, g.E);
-      d.wChunk = fp4_pow(d.w, g.chunk);
       d.poly = poly_idx[j]; d.slot = j; d.pad0 = d.pad1 = 0;
+      if (points) {
+        d.w = Fp4{{points[4 * (size_t)j], points[4 * (size_t)j + 1], points[4 * (size_t)j + 2], points[4 * (size_t)j + 3]}};
+        d.wE = fp4_pow(d.w, g.E);
+        d.wChunk = fp4_pow(d.w, g.chunk);
+      } else {
+        R0H_REQUIRE(pt_idx[j] < n_points, "poly_divide: job %u names point %u of a table of %u", j, pt_idx[j], n_points);
+        d.w = d.wE = d.wChunk = fp4_zero();  // divide_jobs_kernel's
+        d.pad0 = pt_idx[j];
+      }
       jobs.push_back(d);
     }
   const size_t sum_bytes = (size_t)n_jobs * (g.n_chunks + 1) * 16, job_bytes = jobs.size() * sizeof(DivJob), rem_bytes = (size_t)n_jobs * 16;
@@ -255,6 +293,11 @@ const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const ui
   DivJob* d_jobs = (DivJob*)((char*)tmp->ptr + sum_bytes);
   uint32_t* d_rem = (uint32_t*)((char*)tmp->ptr + sum_bytes + job_bytes);
   R0H_TRY(stage_h2d(ctx, d_jobs, jobs.data(), job_bytes));
+  if (!points) {
+    KScope kj(ctx, "divide_jobs_kernel", (double)job_bytes);
+    hipLaunchKernelGGL(divide_jobs_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, ctx->stream, d_jobs, d_points, g.E, g.chunk, n_jobs);
+    R0H_TRY(launch_ok("divide_jobs_kernel"));
+  }
   KScope ks(ctx, "poly_divide", 48.0 * n * n_jobs);
   size_t first = 0;
   for (const auto& pass : passes) {
@@ -265,13 +308,28 @@ const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const ui
     first += nj;
   }
   R0H_TRY(launch_ok("poly_divide kernels"));
-  if (remainders_host) {
+  if (remainders_host || d_report) {
     hipLaunchKernelGGL(divide_remainders_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, ctx->stream, d_rem, sums, n_jobs, g.n_chunks);
     R0H_TRY(launch_ok("divide_remainders_kernel"));
+  }
+  if (remainders_host) {
     R0H_TRY_HIP(hipMemcpyAsync(remainders_host, d_rem, rem_bytes, hipMemcpyDeviceToHost, ctx->stream));
     R0H_TRY_HIP(ctx_wait(ctx));
   }
+  if (d_report) {  // the remainders stay on the device: reduced to one word the caller reads back when it likes
+    KScope kr(ctx, "divide_report_kernel", (double)rem_bytes);
+    hipLaunchKernelGGL(divide_report_kernel, dim3(1), dim3(64), 0, ctx->stream, d_report, d_rem, n_jobs);
+    R0H_TRY(launch_ok("divide_report_kernel"));
+  }
   return nullptr;
   R0H_GUARD_END
+}
+const char* poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* points, uint32_t n_jobs, uint32_t* remainders_host) {
+  return poly_divide_batch_impl(ctx, polys, n, poly_idx, points, nullptr, nullptr, 0, n_jobs, remainders_host, nullptr);
+}
+const char* poly_divide_batch_points(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* pt_idx, uint32_t n_jobs, const uint32_t* d_points,
+                                     uint32_t n_points, uint32_t* d_report) {
+  R0H_REQUIRE(ctx && polys && d_report && (!n_jobs || (poly_idx && pt_idx && d_points)), "poly_divide: NULL argument");
+  return poly_divide_batch_impl(ctx, polys, n, poly_idx, nullptr, pt_idx, d_points, n_points, n_jobs, nullptr, d_report);
 }
 }  // namespace r0h

@@ -392,6 +392,31 @@ const char* r0h_proof_begin(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, co
 const char* r0h_proof_finish(r0h_proof* proof, const r0h_buf* accum, uint32_t* seal_out, size_t seal_capacity_words,
                              size_t* seal_words_out);
 const char* r0h_proof_abort(r0h_proof* proof);
+/* r0h_ctx_set_device_finish(ctx, on != 0), off by default: r0h_proof_finish (and every entry point that runs it: r0h_prove_segment*,
+ * sessions, image proofs, r0h_lift / r0h_join / r0h_compress) runs ALL its steps -- ACCUM, CHECK, the openings at z, DEEP, FRI, the
+ * queries -- on a transcript on the device, whatever r0h_ctx_set_device_transcript says.  The host generator is handed over once the
+ * accumulation mix has been drawn; poly_mix, z and the DEEP mix are drawn into device words, the tables that depend on them (the powers
+ * of poly_mix, the points z * omega^-back and z^4, the registers' interpolants, the per-column powers and the head of the DEEP mix, the
+ * division jobs) are filled by small kernels, and the remainders of the DEEP divisions are reduced to one word.  The seal is the same
+ * words.  r0h_proof_finish then waits twice instead of six times: for the one read-back of every seal word the steps made, and for
+ * the close of the per-phase profile (of a stream that has drained).  Helper contexts follow their owner's switch.
+ *
+ * With the switch on a proof can also be finished in two calls, so that one host thread keeps proofs in flight on several contexts:
+ *   r0h_proof_finish_enqueue  enqueues the steps on the proof's stream and returns without waiting for it.  Refused unless the proof's
+ *                             context has the switch on.  An error consumes the proof, as r0h_proof_finish's does.
+ *   r0h_proof_finish_collect  the read-back, the host's verdicts (a DEEP remainder that is not zero, a tree top that does not match:
+ *                             r0h_proof_finish's messages), the seal; consumes the proof either way.  Refused, and the proof left
+ *                             as it is, if it was not enqueued.
+ * r0h_proof_finish is one after the other.  Between the two calls `accum`, the CODE commitment (or the CODE columns) the proof was
+ * begun with and, under r0h_ctx_set_check_witness, the witness buffers must stay as they were given: the steps read them on the
+ * stream.  r0h_proof_abort of an enqueued proof waits for its stream before it releases anything.  With r0h_ctx_set_check_witness on,
+ * the checker still reads its table back between accumulation and the ACCUM commitment: the seal is the same, the enqueue waits once.
+ * The per-phase profile keeps its phase names and order: the phases' events are recorded at enqueue, the profile closes at collect (a
+ * context reports one proof at a time: begin the next on it after the collect).  r0h_kernel_timing adds events around the launches and
+ * no wait: the counts are the same with it on. */
+const char* r0h_ctx_set_device_finish(r0h_ctx* ctx, int on);
+const char* r0h_proof_finish_enqueue(r0h_proof* proof, const r0h_buf* accum);
+const char* r0h_proof_finish_collect(r0h_proof* proof, uint32_t* seal_out, size_t seal_capacity_words, size_t* seal_words_out);
 /* A proof waiting between its phases holds its DATA group three ways: coefficients, evaluations on the 4N coset (4/5 of the bytes:
  * 2 GiB for 128 columns of 2^20 rows) and Merkle nodes.  r0h_proof_shrink gives the evaluations back to the context's pool;
  * r0h_proof_finish computes them again from the coefficients (one expanding NTT, the same words: the seal does not change).  A

@@ -65,6 +65,8 @@ def main():
                     "under WORLD_SIZE > 1 in its gathered form (driver.prove_elf_sharded(check_session=True): every rank's classes exported, exchanged and merged), whose bytes and milliseconds the line reports")
     ap.add_argument("--device-transcript", type=int, default=0, choices=(0, 1), help="1: r0h_ctx_set_device_transcript per session context -- the FRI commitments and the queries of every "
                     "proof run on a transcript on the device, one read-back for both steps (default 0: off), the same receipt")
+    ap.add_argument("--device-finish", type=int, default=0, choices=(0, 1), help="1: r0h_ctx_set_device_finish per session context -- every step of a proof's second half runs on the "
+                    "transcript on the device, one read-back for all of them (default 0: off), the same receipt")
     args = ap.parse_args()
     world, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     import __graft_entry__ as entry
@@ -109,6 +111,8 @@ def main():
         hal.set_session_tree_tops(args.keep_tree_tops)
     if args.device_transcript:
         hal.set_device_transcript(True)
+    if args.device_finish:
+        hal.set_device_finish(True)
     others = []  # further sessions in flight beside this one: a context and a loaded circuit each
     if env is None and args.sessions > 1:
         import threading
@@ -121,6 +125,8 @@ def main():
                 h2.set_session_tree_tops(args.keep_tree_tops)
             if args.device_transcript:
                 h2.set_device_transcript(True)
+            if args.device_finish:
+                h2.set_device_finish(True)
             others.append((h2, h2.load_circuit(blob, entry.code_object_path("trace"))))
     peak_used = 0
     for _ in range(max(1, args.repeat)):
@@ -180,7 +186,7 @@ def main():
         for _, seal in seals[:args.oracle_check]:
             assert oc.verify(seal, code_root=roots[r0.verify_seal(blob, seal)[2]]) == (0, "ok")
     n = len(seals) * max(1, args.sessions if env is None else 1)
-    line = {"device_transcript": bool(args.device_transcript), "sessions_in_flight": args.sessions if env is None else 1, "lean_segments_of_the_reported_session": st["lean_segments"],
+    line = {"device_transcript": bool(args.device_transcript), "device_finish": bool(args.device_finish), "sessions_in_flight": args.sessions if env is None else 1, "lean_segments_of_the_reported_session": st["lean_segments"],
             "device_limit_GiB": args.device_limit_gb if device_limit else None, "evicted_segments_of_the_reported_session": dev["evicted"], "replayed_segments_of_the_reported_session": dev["replayed"],
             "peak_counted_bytes_of_the_reported_session": dev["peak_counted_bytes"], "rows_handle_bytes_of_the_reported_session": dev["rows_bytes"],
             "tree_top_levels": tops["levels"] or None, "segments_replayed_from_their_tree_top": tops["replayed_from_top"], "tree_top_bytes_of_the_reported_session": tops["tops_bytes"],
