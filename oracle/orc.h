@@ -115,6 +115,12 @@ void orc_poly_ext(const orc_circuit_t* c, const uint32_t poly_mix[4], const uint
 size_t orc_prove_segment(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
                          const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
                          size_t seal_cap);
+/* The same sequencer with the accumulation left to the caller: once the mix is drawn, accum_fn(mix, accum, user) fills the ACCUM
+ * group's columns ([column][row], group_size[ACCUM] * 2^po2 words) from the n_mix mix words; NULL = orc_accum_public. */
+typedef void (*orc_accum_fn)(const uint32_t* mix, uint32_t* accum, void* user);
+size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
+                              const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
+                              size_t seal_cap, orc_accum_fn accum_fn, void* user);
 /* 0 = accepted; otherwise a positive error code naming the first failed check. */
 int orc_verify_segment(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, const uint32_t* seal,
                        size_t seal_words);

@@ -399,9 +399,11 @@ void orc_poly_divide(uint32_t* poly, uint32_t n, const uint32_t z[4], uint32_t r
   st4(rem, cur);
 }
 
-/* Lagrange interpolation through (xs[i], ys[i]), i < n (n is at most a handful): coefficients low to high. */
+/* Lagrange interpolation through (xs[i], ys[i]), i < n: coefficients low to high.  n is a register's tap count -- up to 64, one tap
+ * per back the blob format admits -- and the work arrays are sized by it. */
 void orc_poly_interpolate(uint32_t* out, const uint32_t* xs, const uint32_t* ys, uint32_t n) {
-  fp4_t acc[16], basis[17];
+  fp4_t* acc = (fp4_t*)malloc(sizeof(fp4_t) * (2 * (size_t)n + 1));
+  fp4_t* basis = acc + n; /* n + 1 slots */
   for (uint32_t i = 0; i < n; i++) acc[i] = fp4_zero();
   for (uint32_t i = 0; i < n; i++) {
     /* basis = prod_{j != i} (x - xs[j]) */
@@ -423,6 +425,7 @@ void orc_poly_interpolate(uint32_t* out, const uint32_t* xs, const uint32_t* ys,
     for (uint32_t k = 0; k < n; k++) acc[k] = fp4_add(acc[k], fp4_mul(basis[k], scale));
   }
   for (uint32_t k = 0; k < n; k++) st4(out + 4 * k, acc[k]);
+  free(acc);
 }
 
 /* ------------------------------------------------------------------ transcript RNG */

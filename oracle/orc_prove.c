@@ -141,6 +141,13 @@ static void fri_prove(wiop_t* io, uint32_t* coeffs /* [4][n] bit-reversed, consu
 size_t orc_prove_segment(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
                          const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
                          size_t seal_cap) {
+  return orc_prove_segment_with(c, blob, blob_words, po2, code, data, global, seal, seal_cap, NULL, NULL);
+}
+
+/* the same with the ACCUM group the caller's: a circuit without an ACCUM section (tests/tap_circuits.py) has no other source of it */
+size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
+                              const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
+                              size_t seal_cap, orc_accum_fn accum_fn, void* user) {
   const size_t n = (size_t)1 << po2;
   wiop_t io;
   memset(&io, 0, sizeof io);
@@ -178,7 +185,8 @@ size_t orc_prove_segment(const orc_circuit_t* c, const uint32_t* blob, size_t bl
   for (uint32_t i = 0; i < c->n_mix; i++) mix[i] = orc_rng_elem(&io.rng);
   {
     uint32_t* accum = (uint32_t*)malloc((size_t)c->group_size[ORC_GROUP_ACCUM] * n * 4);
-    orc_accum_public(c, po2, code, data, global, mix, accum);
+    if (accum_fn) accum_fn(mix, accum, user);
+    else orc_accum_public(c, po2, code, data, global, mix, accum);
     group_from_witness(&grp[ORC_GROUP_ACCUM], accum, c->group_size[ORC_GROUP_ACCUM], po2);
     free(accum);
   }

@@ -9,6 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "oracle", "liborc.so")
 P = 2013265921
 _vp, _u32, _u64, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t
+ACCUM_FN = ctypes.CFUNCTYPE(None, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _vp)  # orc_accum_fn(mix, accum, user)
 
 
 def _ptr(a):
@@ -39,6 +40,8 @@ class Oracle:
             getattr(L, "orc_circuit_" + f).argtypes = [_vp]
         L.orc_prove_segment.restype = _sz
         L.orc_prove_segment.argtypes = [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _sz]
+        L.orc_prove_segment_with.restype = _sz
+        L.orc_prove_segment_with.argtypes = [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _sz, ACCUM_FN, _vp]
         L.orc_verify_segment.restype = ctypes.c_int
         L.orc_verify_segment.argtypes = [_vp, _vp, _sz, _vp, _sz]
         L.orc_verify_strerror.restype = ctypes.c_char_p
@@ -275,10 +278,32 @@ class OrcCircuit:
         self.o.L.orc_eval_check(self.h, po2, _ptr(ea), _ptr(ec), _ptr(ed), _ptr(glob), _ptr(mix), _ptr(poly_mix), _ptr(out))
         return out
 
-    def prove(self, po2, code, data, glob):
+    def prove(self, po2, code, data, glob, accum=None):
+        """accum: None for the circuit's own accumulation (its ACCUM section), or a callable mix -> the ACCUM group's words
+        ([column][row], flat or 2-D), called once the mix is drawn (orc_prove_segment_with); the mix it saw is kept in `last_mix`."""
         seal = np.zeros(1 << 21, np.uint32)
         code, data, glob = u32(code), u32(data), u32(glob)
-        n = self.o.L.orc_prove_segment(self.h, _ptr(self.blob), self.blob.size, po2, _ptr(code), _ptr(data), _ptr(glob), _ptr(seal), seal.size)
+        self.last_mix = None
+        if accum is None:
+            n = self.o.L.orc_prove_segment(self.h, _ptr(self.blob), self.blob.size, po2, _ptr(code), _ptr(data), _ptr(glob), _ptr(seal), seal.size)
+        else:
+            words, failed = self.group_size[0] << po2, []
+
+            def fill(mix_p, accum_p, _user):
+                try:  # an exception cannot cross the C frames: keep it, and raise it after the call
+                    mix = np.ctypeslib.as_array(mix_p, shape=(max(self.n_mix, 1),))[:self.n_mix].copy()
+                    got = u32(accum(mix)).reshape(-1)
+                    assert got.size == words, "accum gave %d words, the ACCUM group holds %d" % (got.size, words)
+                    np.ctypeslib.as_array(accum_p, shape=(words,))[:] = got
+                    self.last_mix = mix
+                except BaseException as e:
+                    failed.append(e)
+
+            fn = ACCUM_FN(fill)  # referenced until the call returns
+            n = self.o.L.orc_prove_segment_with(self.h, _ptr(self.blob), self.blob.size, po2, _ptr(code), _ptr(data), _ptr(glob), _ptr(seal), seal.size, fn, None)
+            del fn
+            if failed:
+                raise failed[0]
         assert n, "oracle prover failed (non-zero DEEP remainder?)"
         return seal[:n].copy()
 
