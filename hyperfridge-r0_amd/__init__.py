@@ -223,6 +223,11 @@ _SIGNATURES = {
     "r0h_prefix_sums": [_vp, _vp, _u32],
     "r0h_proof_data_root": [_vp, _vp],
     "r0h_proof_late": [_vp, _vp, _vp],
+    "r0h_proof_late_device": [_vp, _vp, _vp],
+    "r0h_logup_totals_device": [_vp, _vp, _u32, _vp, _vp, _vp],
+    "r0h_accum_public_device": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp],
+    "r0h_ctx_set_session_enqueue": [_vp, _c.c_int],
+    "r0h_last_session_phase2": [_vp, _vp],
     "r0h_proof_globals": [_vp, _vp],
     "r0h_code_commit_columns": [_vp, _pp],
     "r0h_verify_seal_roots": [_vp, _sz, _vp, _sz, _vp, _c.POINTER(_c.c_int), _c.POINTER(_u32), _vp],
@@ -1792,6 +1797,22 @@ class Hal:
         _check(lib().r0h_logup_totals(self.ctx, circuit.handle, po2, code.handle, data.handle, g.ctypes.data_as(_vp)))
         return g
 
+    def logup_totals_device(self, circuit, po2, code, data, globals_buf):
+        """logup_totals with the public inputs in a device Buf: every public total is left in the words of `globals_buf` the circuit
+        reads it from; nothing is read back and nothing waits (r0h_logup_totals_device)"""
+        _check(lib().r0h_logup_totals_device(self.ctx, circuit.handle, po2, code.handle if code is not None else None, data.handle, globals_buf.handle))
+
+    def accum_public_device(self, circuit, po2, code, data, globals_buf, mix_buf):
+        """accum_public with the public inputs and the mix in device Bufs (r0h_accum_public_device): no read-back, no wait"""
+        out = self.alloc(circuit.group_size[GROUP_ACCUM] << po2)
+        try:
+            _check(lib().r0h_accum_public_device(self.ctx, circuit.handle, po2, code.handle if code is not None else None, data.handle, globals_buf.handle,
+                                                 mix_buf.handle if mix_buf is not None else None, out.handle))
+        except R0HipError:
+            out.free()
+            raise
+        return out
+
     def logup_multiplicities(self, circuit, po2, data, glob):
         """fill the lookup tables' multiplicity columns of the DATA group `data` (Buf) from the lookups its rows make
         (r0h_logup_multiplicities)"""
@@ -1874,6 +1895,19 @@ class Hal:
         transcript on the device, with one read-back for all of them, and can be split into proof_finish_enqueue / proof_finish_collect
         (r0h_ctx_set_device_finish); off by default, same seals"""
         _check(lib().r0h_ctx_set_device_finish(self.ctx, 1 if on else 0))
+
+    def set_session_enqueue(self, on=True):
+        """the trace-circuit sessions begun on this context finish from the calling thread alone: every segment's second phase is
+        enqueued on its lane's stream and collected later (r0h_ctx_set_session_enqueue); off by default, same receipts"""
+        _check(lib().r0h_ctx_set_session_enqueue(self.ctx, 1 if on else 0))
+
+    def last_session_phase2(self):
+        """Of the last trace-circuit session finished on this context (r0h_last_session_phase2): the host threads its second phase ran
+        on, the blocking waits its lanes' contexts made in it, how many of those were the staging ring wrapping around, and how many
+        were made by replays of evicted segments and the image proof."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().r0h_last_session_phase2(self.ctx, out))
+        return dict(zip(("host_threads", "blocking_waits", "ring_waits", "replay_and_image_waits"), (int(v) for v in out)))
 
     def blocking_waits(self):
         """how many times the library has waited for this context's stream so far (r0h_ctx_blocking_waits)"""
@@ -2013,6 +2047,19 @@ class Hal:
         fn = lib().r0h_proof_begin_committed if isinstance(code, CodeCommit) else lib().r0h_proof_begin
         _check(fn(self.ctx, circuit.handle, po2, code.handle, data.handle, pg, mix.ctypes.data_as(_vp), ctypes.byref(h)))
         return h, mix[:circuit.n_mix]
+
+    def proof_late(self, proof, circuit, late):
+        """the late public inputs from host words; returns the accumulation mix words (r0h_proof_late)"""
+        words, pl = _u32arr(late)  # (`words` keeps the array alive over the call)
+        mix = np.zeros(max(circuit.n_mix, 1), dtype=np.uint32)
+        _check(lib().r0h_proof_late(proof, pl, mix.ctypes.data_as(_vp)))
+        del words
+        return mix[:circuit.n_mix]
+
+    def proof_late_device(self, proof, late_buf, mix_buf=None):
+        """the late public inputs from a device Buf of exactly n_late words (None for a circuit without any); the mix is drawn on the
+        device, into `mix_buf` if one is given (r0h_proof_late_device, set_device_finish on).  Waits for nothing."""
+        _check(lib().r0h_proof_late_device(proof, late_buf.handle if late_buf is not None else None, mix_buf.handle if mix_buf is not None else None))
 
     def proof_data_top(self, proof, po2, levels, top=None):
         """The top of a begun proof's DATA tree (r0h_proof_data_top): 2 * 4 * 2^po2 >> levels digests into `top` (allocated otherwise);

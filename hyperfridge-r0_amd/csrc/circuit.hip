@@ -311,7 +311,8 @@ const char* r0h_accum_public(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, c
 
 // poly_mix: four host words (r0h_eval_check), or nullptr with d_poly_mix the four device words a transcript on the device drew (eval_check_dev)
 static const char* eval_check_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code, const r0h_buf* eval_data,
-                                   const uint32_t* global, const uint32_t* mix, const uint32_t* poly_mix, const uint32_t* d_poly_mix, r0h_buf* check) {
+                                   const uint32_t* global, const uint32_t* mix, const uint32_t* poly_mix, const uint32_t* d_poly_mix, r0h_buf* check,
+                                   const uint32_t* d_late = nullptr, const uint32_t* d_mix_words = nullptr) {
   R0H_GUARD_BEGIN
   R0H_REQUIRE(ctx && c && eval_accum && eval_code && eval_data && check && (poly_mix || d_poly_mix), "r0h_eval_check: NULL argument");
   R0H_REQUIRE((global || !c->n_global) && (mix || !c->n_mix), "r0h_eval_check: NULL globals");
@@ -345,6 +346,9 @@ static const char* eval_check_impl(r0h_ctx* ctx, const r0h_circuit* c, uint32_t 
   const uint32_t *g0 = u32(g[0]), *g1 = u32(g[1]), *g2 = u32(g[2]);
   const uint32_t *d_glob = u32(pbuf.get()), *d_mix = d_glob + c->n_global, *d_pow = d_mix + c->n_mix, *d_van = d_pow + 4 * (size_t)c->plan.n_pow;
   if (!poly_mix) R0H_TRY(ext_powers(ctx, const_cast<uint32_t*>(d_pow), d_poly_mix, nullptr, c->plan.n_pow));
+  // the late public inputs and the mix where a device transcript left them: over the host's words, behind their upload in stream order
+  if (d_late && c->n_late) R0H_TRY_HIP(hipMemcpyAsync(const_cast<uint32_t*>(d_glob) + (c->n_global - c->n_late), d_late, (size_t)c->n_late * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  if (d_mix_words && c->n_mix) R0H_TRY_HIP(hipMemcpyAsync(const_cast<uint32_t*>(d_mix), d_mix_words, (size_t)c->n_mix * 4, hipMemcpyDeviceToDevice, ctx->stream));
   double alg = (double)domain * 16;
   for (int k = 0; k < 3; k++) alg += (double)domain * c->group_size[k] * 4;
   KScope ks(ctx, "eval_check", alg);
@@ -365,9 +369,9 @@ const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, con
 }  // extern "C"
 namespace r0h {
 const char* eval_check_dev(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code, const r0h_buf* eval_data,
-                           const uint32_t* global, const uint32_t* mix, const uint32_t* d_poly_mix, r0h_buf* check) {
+                           const uint32_t* global, const uint32_t* mix, const uint32_t* d_poly_mix, r0h_buf* check, const uint32_t* d_late, const uint32_t* d_mix) {
   R0H_REQUIRE(d_poly_mix, "r0h_eval_check: NULL argument");
-  return eval_check_impl(ctx, c, po2, eval_accum, eval_code, eval_data, global, mix, nullptr, d_poly_mix, check);
+  return eval_check_impl(ctx, c, po2, eval_accum, eval_code, eval_data, global, mix, nullptr, d_poly_mix, check, d_late, d_mix);
 }
 }  // namespace r0h
 extern "C" {

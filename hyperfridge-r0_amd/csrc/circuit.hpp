@@ -151,6 +151,11 @@ struct LogupKept {
 const char* logup_totals_keep(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io, LogupKept* keep);
 const char* logup_accum_kept(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum,
                              const LogupKept* kept);
+// the two with the public inputs (and the mix) in device buffers: challenges and coefficients are resolved by a kernel, the totals are
+// left in `globals`, nothing is read back and nothing waits for the stream (r0h_logup_totals_device, r0h_accum_public_device)
+const char* logup_totals_keep_device(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, r0h_buf* globals, LogupKept* keep);
+const char* logup_accum_kept_device(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const r0h_buf* globals, const r0h_buf* mix, r0h_buf* accum,
+                                    const LogupKept* kept);
 // The lookups of every table as a flat list (logup_host.cpp; what the device's counting kernel walks): per entry the numerator form
 // and the value form, form = n, (coefficient, DATA column + 1 or 0)..., coefficients in Montgomery form with the public inputs folded
 // in (absent public inputs count as 0).  Table k owns words [begin[k], begin[k + 1]) and `entries[k]` entries.

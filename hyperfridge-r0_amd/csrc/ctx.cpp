@@ -33,6 +33,7 @@ const char* stage_h2d(r0h_ctx* ctx, void* dst, const void* src, size_t bytes) {
   size_t need = (bytes + 255) & ~(size_t)255;
   if (ctx->pinned_off + need > ctx->pinned_bytes) {
     R0H_TRY_HIP(ctx_wait(ctx));  // every earlier ring slot has been consumed
+    ctx->ring_waits++;
     ctx->pinned_off = 0;
   }
   char* slot = (char*)ctx->pinned + ctx->pinned_off;
@@ -231,6 +232,11 @@ const char* r0h_ctx_set_device_finish(r0h_ctx* ctx, int on) {
   R0H_REQUIRE(ctx, "r0h_ctx_set_device_finish: ctx is NULL");
   ctx->device_finish = on != 0;
   for (r0h_ctx* h : ctx->helpers) h->device_finish = ctx->device_finish;
+  return nullptr;
+}
+const char* r0h_ctx_set_session_enqueue(r0h_ctx* ctx, int on) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_session_enqueue: ctx is NULL");
+  ctx->session_enqueue = on != 0 ? 1 : 0;
   return nullptr;
 }
 const char* r0h_ctx_blocking_waits(const r0h_ctx* ctx, uint64_t* count_out) {

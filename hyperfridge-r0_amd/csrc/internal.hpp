@@ -134,6 +134,9 @@ struct r0h_ctx {
   uint64_t balance_stats[3] = {0, 0, 0};  // the last r0h_logup_check_balance: tuples, inserts that reached the global table, its slots
   bool device_transcript = false;  // r0h_ctx_set_device_transcript: fri_commit and queries run on the device generator (prover.hip), one read-back for both
   bool device_finish = false;  // r0h_ctx_set_device_finish: steps 3-8 of proof_finish run on the device generator (prover.hip), one read-back for all of them
+  int session_enqueue = -1;    // r0h_ctx_set_session_enqueue: phase 2 of a session from the calling thread alone (session.cpp); -1: as R0H_SESSION_ENQUEUE says
+  uint64_t session_phase2[4] = {0, 0, 0, 0};  // r0h_last_session_phase2: host threads, blocking waits, of them ring wraps, of them replays + image proof
+  std::atomic<uint64_t> ring_waits{0};      // of blocking_waits: the times stage_h2d waited because the pinned ring had wrapped around
   std::atomic<uint64_t> blocking_waits{0};  // r0h_ctx_blocking_waits: the times the library has waited for this context's stream (ctx_wait)
   bool ktime_on = false;
   std::map<std::string, r0h::KTimer> ktimers;
@@ -227,14 +230,17 @@ const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, cons
 // of them waits for the stream.  `d_points` is a table of extension points in device memory, four words each; requests and jobs name their
 // point by its index in it.
 //   ext_powers                out[4k .. 4k + 4) = base^(exps ? exps[k] : k), k < n: a lane per power, square-and-multiply (device pointers)
-//   eval_check_dev            r0h_eval_check with poly_mix read from four device words: the power words of the parameter block are filled by ext_powers
+//   eval_check_dev            r0h_eval_check with poly_mix read from four device words: the power words of the parameter block are filled by ext_powers;
+//                             with d_late / d_mix the late public inputs and the mix words of the block are copied from there, device to device
+//                             (r0h_proof_late_device: the host words in their places are not read by the kernels)
 //   evaluate_any_points       evaluate_any whose request k is (which[k], pt_idx[k]): grouped by point index, `pts` copied device to device
 //   mix_poly_coeffs_dev       r0h_mix_poly_coeffs whose column c is weighed by mix^(first_exp + c), mix read from four device words
 //   poly_divide_batch_points  poly_divide_batch whose job j divides by (x - point pt_idx[j]): the job table's w, w^E, w^chunk are filled on the
 //                             device, and d_report (one device word) becomes 0, or 1 + the first job, in the order given, whose remainder is not zero
 const char* ext_powers(r0h_ctx* ctx, uint32_t* d_out, const uint32_t* d_base, const uint32_t* d_exps, uint32_t n);
 const char* eval_check_dev(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code, const r0h_buf* eval_data,
-                           const uint32_t* global, const uint32_t* mix, const uint32_t* d_poly_mix, r0h_buf* check);
+                           const uint32_t* global, const uint32_t* mix, const uint32_t* d_poly_mix, r0h_buf* check, const uint32_t* d_late = nullptr,
+                           const uint32_t* d_mix = nullptr);
 const char* evaluate_any_points(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which, const uint32_t* pt_idx, uint32_t n_eval, const uint32_t* d_points,
                                 uint32_t n_points, r0h_buf* out, bool bitrev_coeffs);
 const char* mix_poly_coeffs_dev(r0h_ctx* ctx, r0h_buf* combos, uint32_t first_exp, const uint32_t* d_mix, const r0h_buf* input, const uint32_t* combo_of, uint32_t input_count,
@@ -378,6 +384,8 @@ struct SealCheck {
 const char* verify_seals_batch(r0h_ctx* ctx, int host_hashfn, SealCheck* seals, size_t n, size_t* upload_bytes_out = nullptr);
 // iop.hip: a device transcript that starts from a host generator's state, uploaded in stream order (no wait, unlike r0h_iop_set_state)
 const char* iop_make(r0h_ctx* ctx, const SuiteRng& rng, r0h_iop** out);
+const char* iop_make_words(r0h_ctx* ctx, const uint32_t* state_words, size_t n, r0h_iop** out);  // from SuiteRng::state words kept earlier
+const char* iop_draw_words(r0h_iop* iop, r0h_buf* out, size_t word_offset, size_t n_words);        // r0h_iop_draw_ext by the word
 // receipts, sessions, image proofs and recursion nodes name Poseidon2 only: their entry points refuse a context on another suite
 const char* require_poseidon2(const r0h_ctx* ctx, const char* caller);
 }  // namespace r0h

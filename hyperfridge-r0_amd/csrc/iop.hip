@@ -99,16 +99,37 @@ static const char* iop_check_state(const char* caller, int hashfn, const uint32_
 // A transcript on `ctx` that starts from a host generator's state, which goes up in stream order (no wait): r0h_iop_new with a fresh
 // generator, the sequencer's hand-over with the proof's own (prover.hip)
 const char* iop_make(r0h_ctx* ctx, const SuiteRng& rng, r0h_iop** out) {
+  uint32_t words[SUITE_RNG_MAX_WORDS];
+  const size_t n = rng.state(words);
+  return iop_make_words(ctx, words, n, out);
+}
+// ... from the words of such a state, kept from an earlier moment of the host generator (SuiteRng::state)
+const char* iop_make_words(r0h_ctx* ctx, const uint32_t* words, size_t n, r0h_iop** out) {
   std::unique_ptr<r0h_iop> iop(new r0h_iop());
   iop->ctx = ctx;
   iop->hashfn = ctx->hashfn;
-  uint32_t words[SUITE_RNG_MAX_WORDS];
-  const size_t n = rng.state(words);
   R0H_TRY(iop_check_state("r0h_iop_new", iop->hashfn, words, n));
   R0H_TRY(iop->state.alloc(ctx, n * 4));
   R0H_TRY(stage_h2d(ctx, iop->state->ptr, words, n * 4));
   *out = iop.release();
   return nullptr;
+}
+
+// n_words field elements in a row into words [word_offset, +n_words) of `out` (an extension element is four of them; the accumulation
+// mix of a circuit is n_mix of them)
+const char* iop_draw_words(r0h_iop* iop, r0h_buf* out, size_t word_offset, size_t n_words) {
+  R0H_TRY(iop_usable(iop, "r0h_iop_draw_ext"));
+  R0H_REQUIRE(n_words < ((size_t)1 << 30), "r0h_iop_draw_ext: %zu words are more than one call draws", n_words);
+  const uint32_t* at = nullptr;
+  R0H_TRY(iop_window("r0h_iop_draw_ext", out, word_offset, n_words, &at));
+  if (!n_words) return nullptr;
+  r0h_ctx* ctx = iop->ctx;
+  return with_transcript(ctx, [&](auto t) {
+    using T = decltype(t);
+    KScope ks(ctx, T::draw_kernel, (double)n_words * 4);
+    hipLaunchKernelGGL(iop_draw_kernel<T>, dim3(1), dim3(64), 0, ctx->stream, u32(iop->state.get()), const_cast<uint32_t*>(at), (uint32_t)n_words, T::consts(ctx));
+    return launch_ok(T::draw_kernel);
+  });
 }
 
 }  // namespace r0h
@@ -183,16 +204,7 @@ const char* r0h_iop_draw_ext(r0h_iop* iop, r0h_buf* out, size_t word_offset, siz
   R0H_GUARD_BEGIN
   R0H_TRY(iop_usable(iop, "r0h_iop_draw_ext"));
   R0H_REQUIRE(count < ((size_t)1 << 28), "r0h_iop_draw_ext: %zu elements are more than one call draws", count);
-  const uint32_t* at = nullptr;
-  R0H_TRY(iop_window("r0h_iop_draw_ext", out, word_offset, 4 * count, &at));
-  if (!count) return nullptr;
-  r0h_ctx* ctx = iop->ctx;
-  return with_transcript(ctx, [&](auto t) {
-    using T = decltype(t);
-    KScope ks(ctx, T::draw_kernel, (double)count * 16);
-    hipLaunchKernelGGL(iop_draw_kernel<T>, dim3(1), dim3(64), 0, ctx->stream, u32(iop->state.get()), const_cast<uint32_t*>(at), (uint32_t)(4 * count), T::consts(ctx));
-    return launch_ok(T::draw_kernel);
-  });
+  return iop_draw_words(iop, out, word_offset, 4 * count);
   R0H_GUARD_END
 }
 

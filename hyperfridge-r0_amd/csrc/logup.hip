@@ -34,7 +34,10 @@ const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, 
     t->words.push_back((uint32_t)lf.terms.size());
     for (const LfTerm& term : lf.terms) {
       uint32_t coef = enc(term.coef);
-      if (term.global) {
+      if (term.global && want == Challenges::deferred) {
+        t->patch.push_back((uint32_t)t->words.size());  // (where the coefficient is pushed below)
+        t->patch.push_back(term.global - 1);
+      } else if (term.global) {
         R0H_REQUIRE(global, "log-derivative accumulation: a form reads a public input and none were given");
         coef = mul(coef, global[term.global - 1]);
       }
@@ -70,7 +73,7 @@ const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, 
           if (it == ch_index.end()) {
             const uint32_t* src = q.ch_kind == 1 ? mix : global;
             const size_t at = q.ch_kind == 1 ? 4 * (size_t)q.ch_idx : q.ch_idx;
-            R0H_REQUIRE(src || want == Challenges::identities, "log-derivative accumulation: a challenge is read from %s and none were given", q.ch_kind == 1 ? "the mix" : "the public inputs");
+            R0H_REQUIRE(src || want != Challenges::values, "log-derivative accumulation: a challenge is read from %s and none were given", q.ch_kind == 1 ? "the mix" : "the public inputs");
             it = ch_index.emplace(key, (uint32_t)t->ch.size()).first;
             t->ch.push_back(want == Challenges::values ? Fp4{{src[at], src[at + 1], src[at + 2], src[at + 3]}} : fp4_zero());
             t->ch_id.push_back(key);
@@ -97,6 +100,49 @@ const char* upload_tape(r0h_ctx* ctx, const Tape& t, DeviceTape* d) {
   d->cols = (const uint32_t* const*)(base + w_bytes);
   d->ch = (const Fp4*)(base + w_bytes + c_bytes);
   return nullptr;
+}
+
+// A deferred tape made whole where the public inputs and the mix are: lanes [0, n_patch) multiply a coefficient by its public input,
+// the n_ch lanes behind them copy a challenge's four words from the public inputs (kind 2) or the mix (kind 1) into the tape's
+// challenge block.  table = n_patch (tape word, public input) pairs, then n_ch (kind, index) pairs.  A few dozen lanes, once a tape:
+// the term kernel then reads the block exactly as it reads an uploaded one -- through scalar loads of a wave-uniform address (the compiler
+// emits s_load_dwordx4 for ch[ci] and s_load_dword for the tape words in both forms, for the term kernel is the same code object: 0
+// bytes of scratch and the same VGPR count by construction; profiles/r23/session_enqueue.md has the figures).
+__global__ __launch_bounds__(64) void logup_resolve_kernel(uint32_t* __restrict__ words, uint32_t* __restrict__ ch, const uint32_t* __restrict__ table, uint32_t n_patch, uint32_t n_ch,
+                                                            const uint32_t* __restrict__ globals, const uint32_t* __restrict__ mix) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i < n_patch) {
+    const uint32_t w = table[2 * i];
+    words[w] = mul(words[w], globals[table[2 * i + 1]]);
+  } else if (i - n_patch < n_ch) {
+    const uint32_t k = i - n_patch, kind = table[2 * (n_patch + k)], idx = table[2 * (n_patch + k) + 1];
+    const uint32_t* src = kind == 1 ? mix + 4 * (size_t)idx : globals + idx;
+#pragma unroll
+    for (int q = 0; q < 4; q++) ch[4 * (size_t)(k + 1) + q] = src[q];
+  }
+}
+
+const char* upload_tape_deferred(r0h_ctx* ctx, const r0h_circuit* c, const Tape& t, const r0h_buf* globals, const r0h_buf* mix, DeviceTape* d) {
+  R0H_REQUIRE(globals && globals->bytes >= (size_t)c->n_global * 4, "log-derivative accumulation: the device copy of the public inputs holds fewer than %u words", c->n_global);
+  R0H_REQUIRE(!mix || mix->bytes >= (size_t)c->n_mix * 4, "log-derivative accumulation: the device mix holds fewer than %u words", c->n_mix);
+  const uint32_t n_patch = (uint32_t)(t.patch.size() / 2), n_ch = (uint32_t)t.ch.size() - 1;
+  std::vector<uint32_t> table(t.patch);
+  for (uint32_t k = 0; k < n_patch; k++) R0H_REQUIRE(table[2 * k] < t.words.size() && table[2 * k + 1] < c->n_global, "log-derivative accumulation: a coefficient reads public input %u of %u", table[2 * k + 1], c->n_global);
+  for (uint32_t k = 1; k <= n_ch; k++) {  // (ch[0] is "one", uploaded with the tape)
+    const uint32_t kind = (uint32_t)(t.ch_id[k] >> 32), idx = (uint32_t)t.ch_id[k];
+    R0H_REQUIRE(kind == 1 ? (mix && 4 * (size_t)idx + 4 <= c->n_mix) : (kind == 2 && (size_t)idx + 4 <= c->n_global),
+                "log-derivative accumulation: challenge %u of kind %u lies outside %s", idx, kind, kind == 1 ? "the device mix (or none was given)" : "the public inputs");
+    table.insert(table.end(), {kind, idx});
+  }
+  R0H_TRY(upload_tape(ctx, t, d));
+  if (table.empty()) return nullptr;
+  DevBuf d_table;  // back to the pool behind the launch that reads it
+  R0H_TRY(d_table.alloc(ctx, table.size() * 4));
+  R0H_TRY(stage_h2d(ctx, d_table->ptr, table.data(), table.size() * 4));
+  KScope ks(ctx, "logup_resolve_kernel", 8.0 * (double)table.size());
+  hipLaunchKernelGGL(logup_resolve_kernel, dim3((n_patch + n_ch + 63) / 64), dim3(64), 0, ctx->stream, const_cast<uint32_t*>(d->words), (uint32_t*)const_cast<Fp4*>(d->ch), u32(d_table.get()),
+                     n_patch, n_ch, u32(globals), mix ? u32(mix) : nullptr);
+  return launch_ok("logup_resolve_kernel");
 }
 
 namespace {
@@ -249,8 +295,10 @@ __global__ void logup_chain_kernel(uint32_t* __restrict__ accum, const uint32_t*
 static_assert(sizeof(DevBuf) == sizeof(void*) && sizeof(LogupKept) == sizeof(void*) + 8 && alignof(LogupKept) == alignof(void*),
               "LogupKept is no longer {buffer pointer, po2, n_own}: tests/test_gpu_logup_kept.py builds one by hand");
 // standalone accumulators (`own_words`: where theirs begin on the device tape): terms -> running sums; totals_out (host, 4 words each)
-// if wanted, ACCUM columns if `accum`; `keep`: the scanned terms outlive the call (the accumulation of the same segment unpacks them: logup_accum_kept)
-static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const uint32_t* own_words, const DeviceTape& d, r0h_buf* accum, uint32_t* totals_out, LogupKept* keep = nullptr) {
+// if wanted, ACCUM columns if `accum`; `keep`: the scanned terms outlive the call (the accumulation of the same segment unpacks them: logup_accum_kept);
+// `d_globals`: every total copied, device to device, into the four words of a device copy of the public inputs where the circuit reads it
+static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const uint32_t* own_words, const DeviceTape& d, r0h_buf* accum, uint32_t* totals_out, LogupKept* keep = nullptr,
+                                    r0h_buf* d_globals = nullptr) {
   const uint32_t n = 1u << po2, n_chain = c->logup.n_chain, n_acc = (uint32_t)c->logup.accs.size(), n_own = n_acc - n_chain;
   if (!n_own) return nullptr;
   DevBuf terms;
@@ -263,6 +311,11 @@ static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t
     R0H_TRY(r0h_prefix_sums(ctx, &view, n));
     if (accum) R0H_TRY(unpack_ext_columns(ctx, u32(accum) + ((size_t)(4 * (n_chain + k)) << po2), (const uint32_t*)view.ptr, po2));
     if (totals_out) R0H_TRY(r0h_buf_d2h(ctx, &view, (size_t)(n - 1) * 16, totals_out + 4 * k, 16));
+    if (d_globals) {  // the scan's last element is the total
+      const uint32_t at = c->logup.accs[n_chain + k].final_global;
+      R0H_REQUIRE((size_t)at + 4 <= d_globals->bytes / 4, "r0h_logup_totals: a total goes to public inputs %u..%u, the device copy holds %zu words", at, at + 3, d_globals->bytes / 4);
+      R0H_TRY_HIP(hipMemcpyAsync(u32(d_globals) + at, (const uint32_t*)view.ptr + 4 * (size_t)(n - 1), 16, hipMemcpyDeviceToDevice, ctx->stream));
+    }
   }
   if (keep) {
     keep->terms = std::move(terms);
@@ -272,21 +325,18 @@ static const char* own_accumulators(r0h_ctx* ctx, const r0h_circuit* c, uint32_t
   return nullptr;
 }
 
-const char* logup_accum_kept(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum,
-                             const LogupKept* kept) {
-  R0H_GUARD_BEGIN
+// what both forms of the accumulation ask of their buffers
+static const char* accum_args(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const r0h_buf* accum) {
   R0H_REQUIRE(ctx && c && data && accum, "r0h_accum: NULL argument");
   R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_accum: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
-  const uint32_t n = 1u << po2, n_chain = c->logup.n_chain;
   R0H_REQUIRE(((size_t)c->group_size[R0H_GROUP_DATA] << po2) * 4 <= data->bytes && ((size_t)c->group_size[R0H_GROUP_ACCUM] << po2) * 4 <= accum->bytes &&
                   (!code || ((size_t)c->group_size[R0H_GROUP_CODE] << po2) * 4 <= code->bytes),
               "r0h_accum: buffers too small for 2^%u rows", po2);
-  for (uint32_t i = 0; i < c->n_mix; i++) R0H_REQUIRE(mix && mix[i] < P, "r0h_accum: mix[%u] missing or not canonical", i);
-  for (uint32_t i = 0; i < c->n_global; i++) R0H_REQUIRE(!global || global[i] < P, "r0h_accum: global[%u] not canonical", i);
-  Tape t;
-  R0H_TRY(build_tape(c, po2, code, data, global, mix, Challenges::values, 0, (uint32_t)c->logup.accs.size(), &t));
-  DeviceTape d;
-  R0H_TRY(upload_tape(ctx, t, &d));
+  return nullptr;
+}
+// the launches of the accumulation over a tape that stands on the device: terms, scan, chain, the public accumulators.  Waits for nothing.
+static const char* accum_launch(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const Tape& t, const DeviceTape& d, r0h_buf* accum, const LogupKept* kept) {
+  const uint32_t n = 1u << po2, n_chain = c->logup.n_chain;
   KScope ks(ctx, "logup_accum", ((double)t.cols.size() + 2.0 * c->group_size[R0H_GROUP_ACCUM]) * n * 4);
   DevBuf totals;
   R0H_TRY(totals.alloc(ctx, (size_t)n * 16));
@@ -303,8 +353,40 @@ const char* logup_accum_kept(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, c
   } else {
     R0H_TRY(own_accumulators(ctx, c, po2, d.words + t.acc_begin[n_chain], d, accum, nullptr));
   }
+  return nullptr;
+}
+
+const char* logup_accum_kept(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum,
+                             const LogupKept* kept) {
+  R0H_GUARD_BEGIN
+  R0H_TRY(accum_args(ctx, c, po2, code, data, accum));
+  for (uint32_t i = 0; i < c->n_mix; i++) R0H_REQUIRE(mix && mix[i] < P, "r0h_accum: mix[%u] missing or not canonical", i);
+  for (uint32_t i = 0; i < c->n_global; i++) R0H_REQUIRE(!global || global[i] < P, "r0h_accum: global[%u] not canonical", i);
+  Tape t;
+  R0H_TRY(build_tape(c, po2, code, data, global, mix, Challenges::values, 0, (uint32_t)c->logup.accs.size(), &t));
+  DeviceTape d;
+  R0H_TRY(upload_tape(ctx, t, &d));
+  R0H_TRY(accum_launch(ctx, c, po2, t, d, accum, kept));
   R0H_TRY_HIP(ctx_wait(ctx));  // the tape goes back to the pool
   return nullptr;
+  R0H_GUARD_END
+}
+
+// The same accumulation with the public inputs and the mix where the device's transcript left them: nothing of either is read on the
+// host, and nothing waits.  The tape, its table and every temporary are DevBufs of the context's pool, which hands a block out again in
+// stream order only; the host words of the uploads were copied into the pinned ring when they were staged (stage_h2d waits by itself in
+// the rare case that the ring wraps around).  That is all the wait of the host form stands for: it protects nothing the owners do not.
+const char* logup_accum_kept_device(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const r0h_buf* globals, const r0h_buf* mix, r0h_buf* accum,
+                                    const LogupKept* kept) {
+  R0H_GUARD_BEGIN
+  R0H_TRY(accum_args(ctx, c, po2, code, data, accum));
+  R0H_REQUIRE(globals && (mix || !c->n_mix), "r0h_accum: NULL argument");
+  R0H_REQUIRE(!c->logup.accs.empty(), "r0h_accum_public_device: the circuit has no log-derivative argument: its accumulation (r0h_accum) takes the mix from the host");
+  Tape t;
+  R0H_TRY(build_tape(c, po2, code, data, nullptr, nullptr, Challenges::deferred, 0, (uint32_t)c->logup.accs.size(), &t));
+  DeviceTape d;
+  R0H_TRY(upload_tape_deferred(ctx, c, t, globals, mix, &d));
+  return accum_launch(ctx, c, po2, t, d, accum, kept);
   R0H_GUARD_END
 }
 
@@ -367,7 +449,36 @@ const char* r0h_logup_totals(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, c
   return logup_totals_keep(ctx, c, po2, code, data, global_io, nullptr);
 }
 
+const char* r0h_logup_totals_device(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, r0h_buf* globals_io) {
+  return logup_totals_keep_device(ctx, c, po2, code, data, globals_io, nullptr);
+}
+const char* r0h_accum_public_device(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const r0h_buf* globals, const r0h_buf* mix, r0h_buf* accum) {
+  R0H_REQUIRE(ctx && c, "r0h_accum_public_device: NULL argument");
+  return logup_accum_kept_device(ctx, c, po2, code, data, globals, mix, accum, nullptr);
+}
+
 }  // extern "C"
+
+// r0h_logup_totals with the public inputs on the device: the challenges are read there and every total is left there, in the words of
+// `globals` the circuit reads it from.  Nothing crosses to the host and nothing waits.
+const char* r0h::logup_totals_keep_device(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, r0h_buf* globals, LogupKept* keep) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && c && data && globals, "r0h_logup_totals: NULL argument");
+  R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_logup_totals: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
+  R0H_REQUIRE(((size_t)c->group_size[R0H_GROUP_DATA] << po2) * 4 <= data->bytes && (!code || ((size_t)c->group_size[R0H_GROUP_CODE] << po2) * 4 <= code->bytes),
+              "r0h_logup_totals: buffers too small for 2^%u rows", po2);
+  const uint32_t n_chain = c->logup.n_chain, n_acc = (uint32_t)c->logup.accs.size();
+  if (n_acc == n_chain) return nullptr;
+  for (uint32_t j = n_chain; j < n_acc; j++)
+    for (const LogupFraction& f : c->logup.accs[j].fr)
+      for (const LogupPart& q : f.parts) R0H_REQUIRE(q.ch_kind != 1, "r0h_logup_totals: accumulator %u takes a challenge from the mix", j);
+  Tape t;
+  R0H_TRY(build_tape(c, po2, code ? code : data, data, nullptr, nullptr, Challenges::deferred, n_chain, n_acc - n_chain, &t));
+  DeviceTape d;
+  R0H_TRY(upload_tape_deferred(ctx, c, t, globals, nullptr, &d));
+  return own_accumulators(ctx, c, po2, d.words, d, nullptr, nullptr, keep, globals);
+  R0H_GUARD_END
+}
 
 const char* r0h::logup_totals_keep(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io, LogupKept* keep) {
   R0H_GUARD_BEGIN

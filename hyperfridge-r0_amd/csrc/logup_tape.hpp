@@ -14,10 +14,13 @@ struct Tape {
   std::vector<Fp4> ch;                      // challenges; index 0 is "one"
   std::vector<uint64_t> ch_id;              // their identities, kind << 32 | index (0: "one"): what the balance checks' weights are indexed by
   std::vector<uint32_t> acc_begin;          // word offset of every accumulator on the tape, and the tape's end
+  std::vector<uint32_t> patch;              // Challenges::deferred: (tape word, public input) pairs -- the coefficient there is still to be multiplied by that input
 };
 // The tape of accumulators [first, first + count).  `ch` holds the challenges' values (from `mix` and the public inputs: a missing
-// source is an error), or zeros beside their identities (the balance checks read `ch_id` alone: `mix` may be nullptr)
-enum class Challenges { values, identities };
+// source is an error), or zeros beside their identities (the balance checks read `ch_id` alone: `mix` may be nullptr).  `deferred`:
+// neither `global` nor `mix` is read -- the identities as above, and the public inputs a coefficient takes listed in `patch` instead of
+// folded in: upload_tape_deferred makes the tape whole on the device, from device copies of both
+enum class Challenges { values, identities, deferred };
 const char* build_tape(const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, Challenges want, uint32_t first,
                        uint32_t count, Tape* t);
 
@@ -28,6 +31,9 @@ struct DeviceTape {
   const Fp4* ch = nullptr;
 };
 const char* upload_tape(r0h_ctx* ctx, const Tape& t, DeviceTape* d);
+// a Challenges::deferred tape uploaded and resolved in stream order: the coefficients in `patch` multiplied by their public inputs and
+// the challenge block filled, both from `globals` (the circuit's n_global words) and `mix` (its n_mix words; nullptr if no identity is the mix's)
+const char* upload_tape_deferred(r0h_ctx* ctx, const r0h_circuit* c, const Tape& t, const r0h_buf* globals, const r0h_buf* mix, DeviceTape* d);
 
 // ---- grids.  The device's compute units, asked once a context
 inline const char* cu_count(r0h_ctx* ctx, uint32_t* n_cu) {

@@ -245,6 +245,10 @@ struct TailLayout {
   size_t accum_top = 0, check_top = 0;  // the two groups' top layers, 8 * top_size words each
   size_t coeff_u = 0;                   // 4 * n_u words: per register its interpolant, then CHECK's sixteen openings
   size_t report = 0;                    // one word: 0, or 1 + the first DEEP division whose remainder is not zero
+  // under r0h_proof_late_device as well: the late public inputs (seal words: tail_collect patches them into the opening block) and one
+  // word, 0 or 1 + the first of them that is not canonical; `mix` (below) is the accumulation mix, the device's own
+  bool late = false;
+  size_t late_report = 0, late_words = 0;
   std::vector<size_t> round_top;  // per FRI round: its tree's top layer, 8 * top_size words
   size_t final_coeffs = 0;        // 4 * final_degree words
   size_t idx = 0;                 // the query rows [n_trees][R0H_QUERIES]
@@ -252,6 +256,7 @@ struct TailLayout {
   size_t seal_words = 0;          // everything above: what the read-back brings home
   size_t fold_mix = 0;            // per FRI round the four words of its fold mix (the device's own: never read back)
   size_t poly_mix = 0, z = 0, deep_mix = 0;  // with the head: the challenges of steps 4-6, four words each (the device's own as well)
+  size_t mix = 0;                            // with `late`: the circuit's n_mix words
   size_t words = 0;
 };
 
@@ -308,6 +313,11 @@ struct r0h_proof {
   uint32_t point_of_back[64] = {0};
   std::vector<uint32_t> divide_combo;
   bool enqueued = false;
+  // r0h_proof_late_device: the late public inputs were absorbed and the mix drawn by the device generator (they stand in the tail; the
+  // host's `mix` and the late part of `global` are zeros until the collect).  A circuit without late inputs has drawn its mix on the
+  // host at proof_begin: `pre_mix_state` is the generator as it was before, which the device form starts from to draw the same words.
+  bool late_device = false;
+  std::vector<uint32_t> pre_mix_state;
   r0h_proof(r0h_ctx* c, const r0h_circuit* ci, uint32_t p, const r0h_buf* code_columns, const r0h_code_commit* cc)
       : ctx(c), circ(ci), po2(p), io(c->hashfn, &c->p2_host), own_code(ci->group_size[R0H_GROUP_CODE], p), code(cc ? cc : &own_code),
         g_accum(ci->group_size[R0H_GROUP_ACCUM], (size_t)4 << p), g_data(ci->group_size[R0H_GROUP_DATA], (size_t)4 << p),
@@ -382,7 +392,11 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_
   profile_phase(ctx, "commit_data");
   R0H_TRY(proof_commit(st, st.g_data, data, data_top, top_levels));
   R0H_TRY(r0h_buf_d2h(ctx, st.g_data.tree.nodes.get(), 32, st.data_root, 32));
-  if (!circ->n_late) return proof_late(st, nullptr);
+  if (!circ->n_late) {
+    st.pre_mix_state.resize(SUITE_RNG_MAX_WORDS);
+    st.pre_mix_state.resize(io.rng.state(st.pre_mix_state.data()));
+    return proof_late(st, nullptr);
+  }
   return nullptr;
 }
 
@@ -637,7 +651,7 @@ static std::vector<const Tree*> proof_trees(const r0h_proof& st) {  // in the or
 
 // The tail block laid out and taken from the pool, and the host generator handed over to the device (its state goes up in stream
 // order).  With `head` the block starts with what steps 3-6 add to the seal; every part of it keeps its offset modulo 8 words.
-static const char* tail_open(r0h_proof& st, bool head) {
+static const char* tail_open(r0h_proof& st, bool head, bool late = false) {
   r0h_ctx* ctx = st.ctx;
   const FriSchedule fri((size_t)1 << st.po2);
   TailLayout& at = st.tail_at;
@@ -653,7 +667,13 @@ static const char* tail_open(r0h_proof& st, bool head) {
       at.coeff_u = w;
       w += 4 * (st.circ->taps.size() + R0H_CHECK_SIZE);
       at.report = w;
-      w = (w + 1 + 7) & ~(size_t)7;
+      at.late_report = w + 1;
+      w = (w + (late ? 2 : 1) + 7) & ~(size_t)7;
+      if (late) {
+        at.late = true;
+        at.late_words = w;
+        w = (w + st.circ->n_late + 7) & ~(size_t)7;
+      }
     }
     for (const FriRound& fr : fri.rounds) { at.round_top.push_back(w); w += 8 * MerkleShape(fr.rows, R0H_FRI_FOLD * 4).top_size; }
     at.final_coeffs = w;
@@ -674,13 +694,62 @@ static const char* tail_open(r0h_proof& st, bool head) {
       at.z = w + 4;
       at.deep_mix = w + 8;
       w += 12;
+      if (late) { at.mix = w; w += st.circ->n_mix; }
     }
     at.words = w;
   }
   R0H_TRY(st.tail.alloc(ctx, at.words * 4));
   r0h_iop* iop = nullptr;
-  R0H_TRY(iop_make(ctx, st.io.rng, &iop));
+  if (late && !st.circ->n_late) R0H_TRY(iop_make_words(ctx, st.pre_mix_state.data(), st.pre_mix_state.size(), &iop));  // (the host has drawn the mix: from before it did)
+  else R0H_TRY(iop_make(ctx, st.io.rng, &iop));
   st.iop.reset(iop);
+  return nullptr;
+}
+
+// ---- the late public inputs on the device transcript (r0h_proof_late_device).  The generator goes up before them: they are absorbed
+// from device words and the accumulation mix is drawn into device words, so the host is out of the loop from the DATA commitment on.
+// 0, or 1 + the first word that is not canonical (a handful of words: one lane)
+__global__ __launch_bounds__(64) void late_check_kernel(uint32_t* __restrict__ report, const uint32_t* __restrict__ late, uint32_t n_late) {
+  if (blockIdx.x || threadIdx.x) return;
+  uint32_t bad = 0;
+  for (uint32_t k = n_late; k-- > 0;)
+    if (late[k] >= P) bad = k + 1;
+  *report = bad;
+}
+static const char* proof_late_device(r0h_proof& st, const r0h_buf* late, r0h_buf* mix_out) {
+  r0h_ctx* ctx = st.ctx;
+  const uint32_t n_late = st.circ->n_late, n_mix = st.circ->n_mix;
+  R0H_REQUIRE(!st.late_device && !(st.mix_drawn && n_late), "r0h_proof_late_device: the accumulation mix has been drawn already");
+  R0H_REQUIRE(st.io.suite->fn() == ctx->hashfn, "r0h_proof_late_device: the proof was begun under the %s hash suite, its context is now on %s", hashfn_name(st.io.suite->fn()),
+              hashfn_name(ctx->hashfn));
+  R0H_REQUIRE(ctx->device_finish, "r0h_proof_late_device: the proof's context has r0h_ctx_set_device_finish off: the steps behind the late inputs would ask the host generator");
+  R0H_REQUIRE(n_late ? late && late->bytes == (size_t)n_late * 4 : !late || !late->bytes, "r0h_proof_late_device: the late buffer holds %zu words, the circuit has %u late public inputs",
+              late ? late->bytes / 4 : (size_t)0, n_late);
+  R0H_REQUIRE(!mix_out || mix_out->bytes >= (size_t)n_mix * 4, "r0h_proof_late_device: mix_out holds %zu words, the circuit draws %u", mix_out ? mix_out->bytes / 4 : (size_t)0, n_mix);
+  // a step that fails after the hand-over takes it back: the tail and the device generator go (to the pool, behind what was launched),
+  // so the proof is as it was and r0h_proof_late, or this call again, finds it so
+  const char* err = [&]() -> const char* {
+    R0H_TRY(tail_open(st, true, true));
+    const TailLayout& at = st.tail_at;
+    uint32_t* tail = u32(st.tail.get());
+    if (n_late) R0H_TRY(copy_words(ctx, st.tail.get(), at.late_words, late, 0, n_late));
+    hipLaunchKernelGGL(late_check_kernel, dim3(1), dim3(64), 0, ctx->stream, tail + at.late_report, tail + at.late_words, n_late);
+    R0H_TRY(launch_ok("late_check_kernel"));
+    if (n_late) R0H_TRY(r0h_iop_commit_elems(st.iop.get(), st.tail.get(), at.late_words, n_late));
+    R0H_TRY(iop_draw_words(st.iop.get(), st.tail.get(), at.mix, n_mix));
+    if (mix_out && n_mix) R0H_TRY(copy_words(ctx, mix_out, 0, st.tail.get(), at.mix, n_mix));
+    return nullptr;
+  }();
+  if (err) {
+    st.iop.reset();
+    st.tail.reset();
+    st.tail_at = TailLayout();
+    return err;
+  }
+  st.mix.assign(n_mix, 0u);  // (canonical stand-ins: the kernels read the tail's words)
+  st.late_device = true;
+  if (!st.mix_drawn) profile_phase(ctx, "accum");
+  st.mix_drawn = true;
   return nullptr;
 }
 
@@ -703,6 +772,12 @@ static const char* commit_accum_device(r0h_proof& st, const r0h_buf* accum) {
   }
   if (st.check_data) {  // reads its table back: the one wait of an enqueue
     profile_phase(ctx, "check_witness");
+    if (st.late_device) {  // the checker takes host words: the late inputs and the mix come home for it (two more read-backs)
+      const uint32_t n_late = st.circ->n_late;
+      if (n_late) R0H_TRY(r0h_buf_d2h(ctx, st.tail.get(), st.tail_at.late_words * 4, st.global.data() + (st.circ->n_global - n_late), (size_t)n_late * 4));
+      if (st.circ->n_mix) R0H_TRY(r0h_buf_d2h(ctx, st.tail.get(), st.tail_at.mix * 4, st.mix.data(), (size_t)st.circ->n_mix * 4));
+      for (uint32_t i = 0; i < n_late; i++) R0H_REQUIRE(st.global[st.circ->n_global - n_late + i] < P, "r0h_proof_finish: late public input %u is not canonical", i);
+    }
     R0H_TRY(require_witness("prove_segment", ctx, st.circ, st.po2, accum, st.check_code, st.check_data, st.global.data(), st.mix.data()));
   }
   profile_phase(ctx, "commit_accum");
@@ -716,7 +791,8 @@ static const char* commit_check_device(r0h_proof& st) {
   R0H_TRY(r0h_iop_draw_ext(st.iop.get(), st.tail.get(), st.tail_at.poly_mix, 1));
   R0H_TRY(g_check.coeffs.alloc(ctx, ((size_t)R0H_INV_RATE << st.po2) * 16));
   R0H_TRY(eval_check_dev(ctx, st.circ, st.po2, st.g_accum.evaluated.get(), st.code->g.evaluated.get(), st.g_data.evaluated.get(), st.global.data(), st.mix.data(),
-                         u32(st.tail.get()) + st.tail_at.poly_mix, g_check.coeffs.get()));
+                         u32(st.tail.get()) + st.tail_at.poly_mix, g_check.coeffs.get(), st.late_device ? u32(st.tail.get()) + st.tail_at.late_words : nullptr,
+                         st.late_device ? u32(st.tail.get()) + st.tail_at.mix : nullptr));
   profile_phase(ctx, "commit_check");
   R0H_TRY(r0h_batch_interpolate_ntt(ctx, g_check.coeffs.get(), 4, st.po2 + 2));
   return proof_commit_device(st, g_check, nullptr, st.tail_at.check_top);
@@ -935,6 +1011,15 @@ static const char* tail_collect(r0h_proof& st) {
   st.iop.reset();
   st.tail.reset();
   WriteIop& io = st.io;
+  if (at.late) {  // before any other verdict: words that are no field elements make every later one meaningless
+    const uint32_t n_late = st.circ->n_late, n_early = st.circ->n_global - n_late, bad = host[at.late_report];
+    R0H_REQUIRE(bad <= n_late, "r0h_proof_finish_collect: the late report word %u names none of the %u late public inputs", bad, n_late);
+    R0H_REQUIRE(!bad, "r0h_proof_finish_collect: late public input %u is not canonical", bad ? bad - 1 : 0);
+    if (n_late) {
+      memcpy(st.global.data() + n_early, host.data() + at.late_words, (size_t)n_late * 4);
+      memcpy(io.proof.data() + st.seal_globals_at + n_early, host.data() + at.late_words, (size_t)n_late * 4);
+    }
+  }
   if (at.head) {
     const uint32_t report = host[at.report];
     R0H_REQUIRE(report <= st.divide_combo.size(), "prove_segment: the DEEP report word %u names none of the %zu divisions", report, st.divide_combo.size());
@@ -967,7 +1052,7 @@ static const char* require_finishable(const r0h_proof& st, const char* caller) {
 static const char* proof_finish_enqueue(r0h_proof& st, const r0h_buf* accum) {
   R0H_TRY(require_finishable(st, "r0h_proof_finish"));
   R0H_REQUIRE(!st.enqueued, "r0h_proof_finish_enqueue: the proof has been enqueued already");
-  R0H_TRY(tail_open(st, true));
+  if (!st.late_device) R0H_TRY(tail_open(st, true));  // (r0h_proof_late_device has handed the generator over already)
   R0H_TRY(commit_accum_device(st, accum));
   R0H_TRY(commit_check_device(st));
   R0H_TRY(evaluate_at_z_device(st));
@@ -995,6 +1080,7 @@ static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector
     R0H_TRY(proof_finish_enqueue(st, accum));
     return proof_finish_collect(st, seal);
   }
+  R0H_REQUIRE(!st.late_device, "r0h_proof_finish: the late public inputs went to the device generator (r0h_proof_late_device) and r0h_ctx_set_device_finish is off now");
   R0H_TRY(commit_accum(st, accum));
   R0H_TRY(commit_check(st));
   R0H_TRY(evaluate_at_z(st));
@@ -1179,6 +1265,14 @@ const char* r0h_proof_late(r0h_proof* proof, const uint32_t* late_globals, uint3
   R0H_TRY(proof_late(*proof, late_globals));
   if (proof->circ->n_mix) memcpy(mix_out, proof->mix.data(), (size_t)proof->circ->n_mix * 4);
   return nullptr;
+  R0H_GUARD_END
+}
+// r0h_proof_late with the late public inputs and the mix on the device (include/r0hip.h): nothing waits, nothing is read back
+const char* r0h_proof_late_device(r0h_proof* proof, const r0h_buf* late, r0h_buf* mix_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(proof, "r0h_proof_late_device: NULL argument");
+  R0H_TRY_HIP(hipSetDevice(proof->ctx->device));
+  return proof_late_device(*proof, late, mix_out);
   R0H_GUARD_END
 }
 const char* r0h_proof_globals(const r0h_proof* proof, uint32_t* globals_out) {

@@ -106,7 +106,9 @@ int main(int argc, char** argv) {
            "       --device-transcript 0|1: with 1 every proof runs its FRI commitments and its queries on a Fiat-Shamir transcript on the device, with one read-back for both steps "
            "instead of one per commitment and per opened tree -- the same seals and receipts (default 0: the transcript stays on the host)\n"
            "       --device-finish 0|1: with 1 every proof runs ALL the steps of its second half -- ACCUM, CHECK, the openings, DEEP, FRI, the queries -- on the transcript on the "
-           "device, with one read-back for all of them, whatever --device-transcript says -- the same seals and receipts (default 0)\n%s\n", r0h_version());
+           "device, with one read-back for all of them, whatever --device-transcript says -- the same seals and receipts (default 0)\n"
+           "       --session-enqueue 0|1: with --elf over the trace circuit; with 1 the second phase of every session is driven by the calling thread alone: each segment's session sum, "
+           "late inputs, accumulation and finish are enqueued on its lane's stream and collected one segment per lane later -- the same receipt (default: R0H_SESSION_ENQUEUE, else 0)\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   // --compress takes no value: it is taken out of the arguments before the "--option value" pairs are read
@@ -132,6 +134,7 @@ int main(int argc, char** argv) {
   unsigned session_keep_tree_tops = 0;  // --session-keep-tree-tops: r0h_ctx_set_session_tree_tops of every session context
   std::string device_transcript = "0";  // --device-transcript: r0h_ctx_set_device_transcript of every context
   std::string device_finish = "0";      // --device-finish: r0h_ctx_set_device_finish of every context
+  std::string session_enqueue;          // --session-enqueue: r0h_ctx_set_session_enqueue of every session context (not given: the library's default)
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--code-object")) co_path = argv[i + 1];
     else if (!strcmp(argv[i], "--po2")) po2 = (unsigned)atoi(argv[i + 1]);
@@ -153,6 +156,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--session-keep-tree-tops")) session_keep_tree_tops = (unsigned)atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--device-transcript")) device_transcript = argv[i + 1];
     else if (!strcmp(argv[i], "--device-finish")) device_finish = argv[i + 1];
+    else if (!strcmp(argv[i], "--session-enqueue")) session_enqueue = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
     else if (!strcmp(argv[i], "--journal")) journal_text = argv[i + 1];
@@ -192,6 +196,10 @@ int main(int argc, char** argv) {
   }
   if (device_finish != "0" && device_finish != "1") {
     fprintf(stderr, "r0h_prove: --device-finish is 0 or 1, not %s\n", device_finish.c_str());
+    return 2;
+  }
+  if (!session_enqueue.empty() && ((session_enqueue != "0" && session_enqueue != "1") || elf_path.empty())) {
+    fprintf(stderr, "r0h_prove: --session-enqueue is 0 or 1 and goes with --elf, not %s\n", session_enqueue.c_str());
     return 2;
   }
   if (hashfn != "poseidon2" && hashfn != "sha-256") { fprintf(stderr, "r0h_prove: --hashfn is poseidon2 or sha-256, not %s\n", hashfn.c_str()); return 1; }
@@ -238,6 +246,7 @@ int main(int argc, char** argv) {
     if (session_keep_tree_tops) CHECK(r0h_ctx_set_session_tree_tops(ctx, session_keep_tree_tops));
     if (device_transcript == "1") CHECK(r0h_ctx_set_device_transcript(ctx, 1));
     if (device_finish == "1") CHECK(r0h_ctx_set_device_finish(ctx, 1));
+    if (!session_enqueue.empty()) CHECK(r0h_ctx_set_session_enqueue(ctx, session_enqueue == "1"));
     if (check_balance) CHECK(r0h_ctx_set_check_balance(ctx, 1));
     if (check_session) CHECK(r0h_ctx_set_check_session(ctx, 1));
     if (!check_witness) return;
@@ -450,6 +459,9 @@ int main(int argc, char** argv) {
       printf("%s\"%u:%u,%u,%u,%u,%u,%u,%u,%u\"", k ? ", " : "", sizes[k], root[0], root[1], root[2], root[3], root[4], root[5], root[6], root[7]);
     }
     printf("]");
+    uint64_t phase2[4];  // of the first context's last session
+    CHECK(r0h_last_session_phase2(ctx, phase2));
+    printf(", \"phase2_host_threads\": %llu, \"phase2_blocking_waits\": %llu", (unsigned long long)phase2[0], (unsigned long long)phase2[1]);
     if (compress) printf(", \"root\": \"%s\", \"root_leaves\": %zu, \"compress_seconds\": %.4f", root_out.c_str(), root_leaves, compress_secs);
     printf("}\n");
     for (r0h_receipt* r : made) CHECK(r0h_receipt_free(r));

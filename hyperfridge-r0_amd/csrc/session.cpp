@@ -361,6 +361,7 @@ struct r0h_session {
   std::vector<uint8_t> journal;
   std::vector<uint8_t> elf;  // kept for the image proof (r0h_ctx_set_image_circuit) and for the session check's verifier side
   bool check_session = false;  // r0h_ctx_set_check_session was on when the session began
+  bool enqueue = false;        // r0h_ctx_set_session_enqueue (or R0H_SESSION_ENQUEUE=1) was on when the session began: phase 2 on the calling thread alone
   uint8_t image_id[32] = {0};
   uint64_t cycles = 0;
   r0h_session_stats stats = {0, 0, 0, 0, 0, 0, 0};
@@ -521,6 +522,10 @@ uint32_t lane_count() {  // two prover lanes by default
   if (const char* v = getenv("R0H_SESSION_LANES")) n = (uint32_t)strtoul(v, nullptr, 10);
   return n < 1 ? 1 : n > 4 ? 4 : n;
 }
+bool enqueue_default() {  // R0H_SESSION_ENQUEUE=1: sessions finish from one host thread unless their context says otherwise
+  const char* v = getenv("R0H_SESSION_ENQUEUE");
+  return v && strtoul(v, nullptr, 10) == 1;
+}
 }  // namespace
 
 extern "C" {
@@ -528,6 +533,12 @@ extern "C" {
 const char* r0h_last_session_stats(r0h_ctx* ctx, r0h_session_stats* out) {
   R0H_REQUIRE(ctx && out, "r0h_last_session_stats: NULL argument");
   *out = ctx->session;
+  return nullptr;
+}
+
+const char* r0h_last_session_phase2(r0h_ctx* ctx, uint64_t out[4]) {
+  R0H_REQUIRE(ctx && out, "r0h_last_session_phase2: NULL argument");
+  memcpy(out, ctx->session_phase2, sizeof ctx->session_phase2);
   return nullptr;
 }
 
@@ -567,6 +578,7 @@ const char* r0h_session_begin(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t*
   R0H_REQUIRE(!(trace_mode && ctx->check_session) || parts == 1,
               "r0h_session_begin: r0h_ctx_set_check_session is on and this is part %u of %u: a rank sees its own segments only, the session check covers single-rank sessions", part, parts);
   ses->check_session = trace_mode && ctx->check_session;
+  ses->enqueue = trace_mode && (ctx->session_enqueue < 0 ? enqueue_default() : ctx->session_enqueue > 0);
   if (trace_mode && ((ctx->image_circuit && part == 0) || ses->check_session)) ses->elf.assign(elf, elf + elf_len);
   ses->device.limit = trace_mode ? ctx->session_device_limit : 0;
   ses->device.tops_levels = ses->device.limit ? ctx->session_tree_tops : 0;  // (only an evicted segment keeps a top)
@@ -724,6 +736,163 @@ const char* replay_segment(r0h_session* s, Pending& p) {
   s->stats.prove_ms += 1e3 * seconds(t1, Clock::now());
   return nullptr;
 }
+
+// ---- phase 2 from one host thread (r0h_ctx_set_session_enqueue).  Once the challenge exists nothing a segment needs comes from the host:
+// its public inputs go up once, the session sum is left in their device copy (logup_totals_keep_device), the device generator absorbs
+// the late inputs and draws the mix (r0h_proof_late_device), the accumulation reads both where they are (logup_accum_kept_device) and
+// the finish is enqueued.  What the enqueued steps read stays with the segment's InFlight until it is collected.
+struct InFlight {
+  Pending* p = nullptr;
+  DevBuf data, globals, mix, accum;
+  Clock::time_point t0;
+};
+const char* enqueue_segment(r0h_session* s, Pending& p, const uint32_t challenge[16], InFlight& fl) {
+  const r0h_circuit* c = s->c;
+  r0h_ctx* lctx = p.lctx;
+  const uint32_t n_early = R0H_TRACE_GLOBALS - R0H_TRACE_LATE_GLOBALS;
+  fl.p = &p;
+  fl.t0 = Clock::now();
+  fl.data = std::move(p.data);
+  memcpy(p.global.data() + R0H_TRACE_GAMMA, challenge, 64);
+  const r0h_buf* code_cols = nullptr;
+  R0H_TRY(r0h_code_commit_columns(p.cc, &code_cols));
+  R0H_TRY(fl.globals.alloc(lctx, (size_t)c->n_global * 4));
+  R0H_TRY(stage_h2d(lctx, fl.globals->ptr, p.global.data(), (size_t)c->n_global * 4));
+  LogupKept kept;
+  R0H_TRY(logup_totals_keep_device(lctx, c, p.po2, code_cols, fl.data.get(), fl.globals.get(), &kept));
+  R0H_TRY(fl.mix.alloc(lctx, (size_t)(c->n_mix ? c->n_mix : 1) * 4));
+  const r0h_buf late = buf_view(fl.globals.get(), (size_t)n_early * 4, (size_t)R0H_TRACE_LATE_GLOBALS * 4);
+  R0H_TRY(r0h_proof_late_device(p.proof.get(), &late, fl.mix.get()));
+  R0H_TRY(fl.accum.alloc(lctx, ((size_t)c->group_size[R0H_GROUP_ACCUM] << p.po2) * 4));
+  R0H_TRY(logup_accum_kept_device(lctx, c, p.po2, code_cols, fl.data.get(), fl.globals.get(), fl.mix.get(), fl.accum.get(), &kept));
+  kept.terms.reset();  // (back to the lane's pool behind the launches that read it)
+  const char* err = r0h_proof_finish_enqueue(p.proof.get(), fl.accum.get());
+  if (err) (void)p.proof.release();  // consumed by the failed enqueue
+  return err;
+}
+// the read-back of an enqueued segment, its seal and the session's accounting; the buffers go back to the lane's pool behind the proof
+const char* collect_segment(r0h_session* s, InFlight& fl, std::vector<uint32_t>& seal) {
+  Pending& p = *fl.p;
+  size_t words = 0;
+  const char* err = r0h_proof_finish_collect(p.proof.release(), seal.data(), seal.size(), &words);  // consumed either way: the stream has drained
+  fl = InFlight();
+  if (p.rows) {
+    p.rows.reset();
+    std::lock_guard<std::mutex> lk(s->result_mu);
+    s->device.rows_held -= p.rows_bytes;
+  }
+  p.held.set(nullptr, 0);
+  R0H_TRY(err);
+  std::lock_guard<std::mutex> lk(s->result_mu);
+  p.seal.assign(seal.begin(), seal.begin() + words);
+  p.done = true;
+  return nullptr;
+}
+uint64_t lane_waits(const r0h_session* s) {
+  uint64_t n = 0;
+  for (const r0h_ctx* l : s->lane_ctx) n += l->blocking_waits.load();
+  return n;
+}
+uint64_t lane_ring_waits(const r0h_session* s) {
+  uint64_t n = 0;
+  for (const r0h_ctx* l : s->lane_ctx) n += l->ring_waits.load();
+  return n;
+}
+// The calling thread drives every lane's stream.  Phase 1 dealt the segments to the lanes as they came, so every lane context has a
+// queue of its own (in index order), and the thread goes round the lanes that still have one: on each it collects the segment that lane
+// has in flight -- the oldest enqueue of all, since every other lane was served after it -- and enqueues the lane's next.  A lane context
+// has at most one segment in flight (the ACCUM group and the finish temporaries of one segment per lane, what the blocking form holds
+// too; and a lane's 8 MiB pinned staging ring is never asked for more than one segment's tables between two collects), and while one
+// lane is being collected the others' streams have their segment to run.  After the first round -- every lane that holds a segment has
+// had its first enqueue -- the image proof is made; when no lane has anything left to enqueue, what is still in flight is collected,
+// oldest first.  An error ends the rounds: what is in flight is collected, then every other proof is aborted.
+const char* finish_enqueued(r0h_session* s, const uint32_t challenge[16], std::vector<uint32_t>& image_seal, uint64_t* other_waits) {
+  struct Lane { r0h_ctx* ctx; std::deque<Pending*> todo; InFlight flying; };
+  std::vector<Lane> lanes;  // in the order of their first segment
+  for (Pending& p : s->pending) {
+    if (p.done) continue;
+    auto it = std::find_if(lanes.begin(), lanes.end(), [&](const Lane& l) { return l.ctx == p.lctx; });
+    if (it == lanes.end()) { lanes.push_back(Lane{p.lctx, {}, InFlight()}); it = lanes.end() - 1; }
+    it->todo.push_back(&p);
+  }
+  std::vector<uint32_t> seal((size_t)1 << 20);
+  std::deque<Lane*> order;  // lanes with a segment in flight, oldest first
+  const char* first = nullptr;
+  auto note = [&](const char* err) {  // the first error is the session's; later ones are dropped
+    if (!err) return;
+    if (first) r0h_free_error(err);
+    else first = err;
+  };
+  auto collect = [&](Lane& l) {
+    const Clock::time_point t0 = l.flying.t0;
+    const char* err = collect_segment(s, l.flying, seal);
+    order.erase(std::find(order.begin(), order.end(), &l));
+    if (!err) {
+      std::lock_guard<std::mutex> lk(s->result_mu);
+      s->stats.prove_ms += 1e3 * seconds(t0, Clock::now());  // enqueue to collected
+      s->stats.segments++;
+    }
+    note(err);
+  };
+  // the blocking r0h_prove_image on the session's own context, whose stream and per-phase profile must be its alone meanwhile (a context
+  // reports one proof at a time): what flies there is collected first; the other lanes' segments run beside it
+  auto prove_image = [&]() {
+    for (Lane& l : lanes)
+      if (l.ctx == s->ctx && l.flying.p) collect(l);
+    if (first) return;
+    const uint64_t w0 = lane_waits(s);
+    size_t words = 0;
+    const char* err = r0h_prove_image(s->ctx, s->ctx->image_circuit, s->elf.data(), s->elf.size(), challenge, seal.data(), seal.size(), &words);
+    *other_waits += lane_waits(s) - w0;
+    if (!err) image_seal.assign(seal.begin(), seal.begin() + words);
+    note(err);
+  };
+  bool image_due = !s->elf.empty() && s->ctx->image_circuit;
+  for (bool any = true; any && !first;) {
+    any = false;
+    for (Lane& l : lanes) {
+      if (first) break;
+      if (l.todo.empty()) continue;
+      any = true;
+      if (l.flying.p) collect(l);
+      if (first) break;
+      Pending& p = *l.todo.front();
+      l.todo.pop_front();
+      if (p.evicted) {  // blocking, as in the lanes' form: its root comes to the host to be compared
+        const uint64_t w0 = lane_waits(s);
+        note(replay_segment(s, p));
+        *other_waits += lane_waits(s) - w0;
+        if (first) break;
+      }
+      const char* err = enqueue_segment(s, p, challenge, l.flying);
+      if (err) {  // the proof is aborted first (it waits for what the enqueue had launched), then its buffers go
+        p.proof.reset();
+        l.flying = InFlight();
+        note(err);
+        break;
+      }
+      order.push_back(&l);
+    }
+    if (image_due && !first) {
+      image_due = false;
+      prove_image();
+    }
+  }
+  while (!order.empty()) collect(*order.front());  // after an error too: what is in flight is collected, its seal kept or its error dropped
+  if (first)
+    for (Pending& p : s->pending) {  // the others' proofs are aborted, and what they held goes with them
+      if (p.done) continue;
+      p.proof.reset();
+      p.data.reset();
+      std::lock_guard<std::mutex> lk(s->result_mu);
+      if (p.rows) s->device.rows_held -= p.rows_bytes;
+      if (p.top) s->device.tops_held -= p.top->bytes;
+      p.rows.reset();
+      p.top.reset();
+      p.held.set(nullptr, 0);
+    }
+  return first;
+}
 }  // namespace
 
 // Phase 2: with the records of ALL segments of the session (in index order) the challenge is fixed; every proof of this rank receives
@@ -741,6 +910,18 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
     if (s->check_session) R0H_TRY(check_session(s));
     uint32_t challenge[16];
     session_challenge(all_records, n_records, challenge);
+    const uint64_t waits0 = lane_waits(s), ring0 = lane_ring_waits(s);
+    uint64_t other_waits = 0;
+    if (s->enqueue) {
+      // the lanes' contexts finish on the device generator for the length of the phase, whatever their switch says
+      std::vector<bool> was;
+      for (r0h_ctx* l : s->lane_ctx) { was.push_back(l->device_finish); l->device_finish = true; }
+      const char* err = finish_enqueued(s, challenge, image_seal, &other_waits);
+      for (size_t k = 0; k < s->lane_ctx.size(); k++) s->lane_ctx[k]->device_finish = was[k];
+      const uint64_t phase2[4] = {1, lane_waits(s) - waits0, lane_ring_waits(s) - ring0, other_waits};
+      memcpy(s->ctx->session_phase2, phase2, sizeof phase2);
+      R0H_TRY(err);
+    }
     std::atomic<bool> failed(false);  // a lane's error: the others leave before their next segment
     auto lane = [&](r0h_ctx* lctx) -> const char* {
       std::vector<uint32_t> seal((size_t)1 << 20), mix(s->c->n_mix);
@@ -771,7 +952,11 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
       }
       return nullptr;
     };
-    R0H_TRY(run_lanes(s->lane_ctx, lane, [&] { failed = true; }));
+    if (!s->enqueue) {
+      R0H_TRY(run_lanes(s->lane_ctx, lane, [&] { failed = true; }));
+      const uint64_t phase2[4] = {s->lane_ctx.size(), lane_waits(s) - waits0, lane_ring_waits(s) - ring0, 0};
+      memcpy(s->ctx->session_phase2, phase2, sizeof phase2);
+    }
   }
   r0h_receipt* rc = nullptr;
   R0H_TRY(r0h_receipt_new(R0H_RECEIPT_COMPOSITE, nullptr, 0, &rc));

@@ -431,6 +431,20 @@ size_t r0h_proof_resident_bytes(const r0h_proof* proof);
  * the proof holds them. */
 const char* r0h_proof_data_root(const r0h_proof* proof, uint32_t root_out[8]);
 const char* r0h_proof_late(r0h_proof* proof, const uint32_t* late_globals, uint32_t* mix_out);
+/* r0h_proof_late_device: r0h_proof_late with the late public inputs and the mix where the device has them, so that the host is out of
+ * the loop from the DATA commitment on.  The generator goes up BEFORE the late inputs (r0h_ctx_set_device_finish hands it over after
+ * the mix); `late` holds the circuit's n_late words on the device (exactly: a buffer of another size is refused), the generator absorbs
+ * them there, and the n_mix mix words are drawn into device words: copied into mix_out (NULL: not wanted) and kept by the proof,
+ * whose constraint check reads them there.  The call enqueues and returns: it waits for nothing and reads nothing back.  The late
+ * words are seal words; they come home with the one read-back of r0h_proof_finish_collect, which patches them into the seal's
+ * opening block -- the seal is word for word r0h_proof_late's -- and from then on r0h_proof_globals would have them.  Their
+ * canonicity is checked on the device and reported at the collect: "late public input k is not canonical".  With n_late == 0 the form
+ * is legal (`late` NULL or empty) and draws, on the device, the mix r0h_proof_begin has returned.  Refused: a second call, or one after
+ * r0h_proof_late; a context whose hash suite changed since the begin; a context with r0h_ctx_set_device_finish off (the steps behind
+ * the late inputs would ask the host generator).  A refusal leaves the proof as it was, and so does a step
+ * that fails after the hand-over (the tail and the device generator are given back).  With r0h_ctx_set_check_witness on, the
+ * checker takes host words: the enqueue reads the late inputs and the mix back for it (two more waits). */
+const char* r0h_proof_late_device(r0h_proof* proof, const r0h_buf* late, r0h_buf* mix_out);
 const char* r0h_proof_globals(const r0h_proof* proof, uint32_t* globals_out);
 /* Control root of a program at trace size 2^po2: Merkle root of the committed CODE group (count columns of 2^po2 words),
  * computed exactly as the sequencer commits it.  What a verifier passes to r0h_verify_seal_bound. */
@@ -900,6 +914,16 @@ const char* r0h_logup_multiplicities_host(const uint32_t* blob, size_t blob_word
 const char* r0h_logup_totals(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io);
 const char* r0h_accum_public(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data,
                              const uint32_t* global, const uint32_t* mix, r0h_buf* accum);
+/* The two with the public inputs (and the mix) in device buffers, for a caller whose challenges never reach the host
+ * (r0h_proof_late_device): `globals` holds the circuit's n_global words, `mix` its n_mix words.  A small kernel multiplies the tape's
+ * coefficients by the public inputs they take and fills the tape's challenge block from both buffers; the term kernel is the one of
+ * the host forms.  r0h_logup_totals_device leaves every total in the words of globals_io the circuit reads it from, device to device.
+ * Neither reads anything back nor waits for the stream: tape, tables and temporaries return to the context's pool in stream order.
+ * Canonicity of the device words is the producer's business (r0h_proof_late_device reports it).  r0h_accum_public_device is for
+ * circuits with a log-derivative argument; the synthetic circuits' r0h_accum takes its mix from the host. */
+const char* r0h_logup_totals_device(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, r0h_buf* globals_io);
+const char* r0h_accum_public_device(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data,
+                                    const r0h_buf* globals, const r0h_buf* mix, r0h_buf* accum);
 const char* r0h_vm_journal(const r0h_vm* vm, const uint8_t** bytes, size_t* n);
 /* the ReceiptClaim of segment i: system states and exit code from the run, Output{journal} on the last segment */
 const char* r0h_vm_segment_claim(const r0h_vm* vm, size_t i, r0h_receipt_claim* out);
@@ -988,6 +1012,29 @@ const char* r0h_session_journal(const r0h_session* s, const uint8_t** bytes, siz
  * segment index missing or present twice, journals that differ, a receipt that is not composite. */
 const char* r0h_receipt_merge(const r0h_receipt* const* parts, size_t n, r0h_receipt** out);
 /* per-stage timing of the last r0h_prove_elf on this context (for tools/bench_session.py): names are static strings */
+/* r0h_ctx_set_session_enqueue(ctx, on != 0): the trace-circuit sessions begun on this context finish (phase 2) from the thread that
+ * calls r0h_session_finish / r0h_prove_elf alone -- no lane threads.  Off by default; a context that was never told follows the
+ * environment (R0H_SESSION_ENQUEUE=1: on).  Taken per session at r0h_session_begin; the session's lane contexts run
+ * r0h_ctx_set_device_finish for the length of the phase.  Per segment the thread uploads the public inputs, then enqueues on the
+ * segment's lane context: the session sum (r0h_logup_totals_device), the late inputs and the mix (r0h_proof_late_device), the
+ * accumulation (r0h_accum_public_device) and r0h_proof_finish_enqueue -- none of which waits.  Every lane context keeps the segments phase 1 dealt it as a queue of
+ * its own, and the thread goes round the lanes that still have one: on each it collects the segment that lane has in flight
+ * (r0h_proof_finish_collect; the oldest enqueue of all, since every other lane was served after it) and enqueues the lane's next.  A
+ * lane context has at most one segment in flight, so the extra device memory is one ACCUM group and one set of finish temporaries
+ * per lane, as in the blocking form, and while one lane is collected the others' streams have a segment to run.  WHAT WAITS: per segment the
+ * collect's read-back and the close of the lane's profile (two waits of a stream); the blocking second commitment of an evicted
+ * segment, on the calling thread right before its enqueue; the image proof, which the calling thread proves with the blocking
+ * r0h_prove_image after the first round, when every lane that holds a segment has had its first enqueue (what is in flight on the session's own context is collected first);
+ * r0h_ctx_set_check_witness's read-backs.  The session check runs before the phase as always; phase 1 keeps its lanes.  An error at
+ * the enqueue or the collect of a segment is the session's error: what is in flight is collected, every other proof is aborted.  The
+ * seals, and so the receipt, are the ones of the lanes' form.  r0h_session_stats.prove_ms counts an enqueued segment from its enqueue
+ * to its collect (wall time, so segments in flight on several lanes overlap in it).
+ * r0h_last_session_phase2: of the last trace-circuit session finished on this context -- the host threads phase 2 ran on (1, or the
+ * session's lanes), the blocking waits the lanes' contexts made during it, how many of those were the staging ring wrapping around
+ * (stage uploads wait when the 8 MiB pinned ring of a context is used up), and how many were made by replays of evicted segments and
+ * the image proof. */
+const char* r0h_ctx_set_session_enqueue(r0h_ctx* ctx, int on);
+const char* r0h_last_session_phase2(r0h_ctx* ctx, uint64_t out[4]);
 typedef struct { uint32_t segments, lean_segments /* proved without resident evaluations: r0h_ctx_set_session_resident_limit */; uint64_t cycles; double executor_s, witgen_ms, prove_ms, wall_s; } r0h_session_stats;
 const char* r0h_last_session_stats(r0h_ctx* ctx, r0h_session_stats* out);
 

@@ -67,6 +67,8 @@ def main():
                     "proof run on a transcript on the device, one read-back for both steps (default 0: off), the same receipt")
     ap.add_argument("--device-finish", type=int, default=0, choices=(0, 1), help="1: r0h_ctx_set_device_finish per session context -- every step of a proof's second half runs on the "
                     "transcript on the device, one read-back for all of them (default 0: off), the same receipt")
+    ap.add_argument("--session-enqueue", type=int, default=None, choices=(0, 1), help="1: r0h_ctx_set_session_enqueue per session context -- the second phase of a session is driven by "
+                    "the calling thread alone, every segment's finish enqueued on its lane's stream and collected later (default: R0H_SESSION_ENQUEUE, else off), the same receipt")
     args = ap.parse_args()
     world, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
     import __graft_entry__ as entry
@@ -113,6 +115,8 @@ def main():
         hal.set_device_transcript(True)
     if args.device_finish:
         hal.set_device_finish(True)
+    if args.session_enqueue is not None:
+        hal.set_session_enqueue(bool(args.session_enqueue))
     others = []  # further sessions in flight beside this one: a context and a loaded circuit each
     if env is None and args.sessions > 1:
         import threading
@@ -127,6 +131,8 @@ def main():
                 h2.set_device_transcript(True)
             if args.device_finish:
                 h2.set_device_finish(True)
+            if args.session_enqueue is not None:
+                h2.set_session_enqueue(bool(args.session_enqueue))
             others.append((h2, h2.load_circuit(blob, entry.code_object_path("trace"))))
     peak_used = 0
     for _ in range(max(1, args.repeat)):
@@ -159,7 +165,7 @@ def main():
             receipt, image_id, cycles = driver.prove_elf_sharded(env, hal, gc, elf, stream, segment_po2=args.po2, check_session=bool(args.check_session), timings=gathered)
             env.barrier()
         wall = time.perf_counter() - t0
-        st, dev = hal.last_session_stats(), hal.last_session_device()
+        st, dev, phase2 = hal.last_session_stats(), hal.last_session_device(), hal.last_session_phase2()
         tops = hal.last_session_tree_tops() if args.keep_tree_tops else {"replayed_from_top": 0, "tops_bytes": 0, "levels": 0}
     if env is not None and args.check_session:  # every rank's exported bytes, in rank order
         mine = np.zeros(world, dtype=np.int64)
@@ -186,7 +192,8 @@ def main():
         for _, seal in seals[:args.oracle_check]:
             assert oc.verify(seal, code_root=roots[r0.verify_seal(blob, seal)[2]]) == (0, "ok")
     n = len(seals) * max(1, args.sessions if env is None else 1)
-    line = {"device_transcript": bool(args.device_transcript), "device_finish": bool(args.device_finish), "sessions_in_flight": args.sessions if env is None else 1, "lean_segments_of_the_reported_session": st["lean_segments"],
+    line = {"device_transcript": bool(args.device_transcript), "device_finish": bool(args.device_finish), "session_enqueue": bool(args.session_enqueue) if args.session_enqueue is not None else os.environ.get("R0H_SESSION_ENQUEUE") == "1",
+            "phase2_host_threads_of_the_reported_session": phase2["host_threads"], "phase2_blocking_waits_of_the_reported_session": phase2["blocking_waits"], "sessions_in_flight": args.sessions if env is None else 1, "lean_segments_of_the_reported_session": st["lean_segments"],
             "device_limit_GiB": args.device_limit_gb if device_limit else None, "evicted_segments_of_the_reported_session": dev["evicted"], "replayed_segments_of_the_reported_session": dev["replayed"],
             "peak_counted_bytes_of_the_reported_session": dev["peak_counted_bytes"], "rows_handle_bytes_of_the_reported_session": dev["rows_bytes"],
             "tree_top_levels": tops["levels"] or None, "segments_replayed_from_their_tree_top": tops["replayed_from_top"], "tree_top_bytes_of_the_reported_session": tops["tops_bytes"],
