@@ -60,6 +60,8 @@ _SIGNATURES = {
     "r0h_hash_rows": [_vp, _vp, _vp, _u32, _u32],
     "r0h_hash_fold": [_vp, _vp, _u32],
     "r0h_merkle_build": [_vp, _vp, _vp, _u32, _u32],
+    "r0h_hash_fold_top": [_vp, _vp, _u32],
+    "r0h_ctx_set_merkle_fused_tops": [_vp, _c.c_int],
     "r0h_merkle_top": [_vp, _vp, _u32, _u32, _vp],
     "r0h_merkle_open_top": [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _u32, _vp],
     "r0h_merkle_climb": [_vp, _vp, _vp, _u32, _u32, _u32, _vp],
@@ -1589,6 +1591,16 @@ class Hal:
 
     def hash_fold(self, nodes, output_size):
         _check(lib().r0h_hash_fold(self.ctx, nodes.handle, output_size))
+
+    def hash_fold_top(self, nodes, output_size):
+        """the levels output_size, output_size / 2, .., 1 of `nodes` from the level of 2 * output_size digests, in at most two launches
+        (r0h_hash_fold_top): the words the loop of hash_fold leaves; output_size is a power of two up to 8192"""
+        _check(lib().r0h_hash_fold_top(self.ctx, nodes.handle, output_size))
+
+    def set_merkle_fused_tops(self, on=True):
+        """merkle_build, and every tree a proof on this context commits, builds its levels of up to 8192 parents with hash_fold_top
+        instead of one hash_fold each (r0h_ctx_set_merkle_fused_tops); off by default, same nodes, seals and receipts"""
+        _check(lib().r0h_ctx_set_merkle_fused_tops(self.ctx, 1 if on else 0))
 
     def merkle_build(self, nodes, matrix, rows, cols):
         _check(lib().r0h_merkle_build(self.ctx, nodes.handle, matrix.handle, rows, cols))

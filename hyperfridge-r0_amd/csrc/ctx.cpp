@@ -127,6 +127,7 @@ const char* ctx_helper(r0h_ctx* ctx, size_t k, r0h_ctx** out) {
   h->device_transcript = ctx->device_transcript;
   h->device_finish = ctx->device_finish;
   h->hashfn = ctx->hashfn;
+  h->merkle_fused_tops = ctx->merkle_fused_tops;
   h->p2_tight = ctx->p2_tight;  // goes with the table below
   if (memcmp(&h->p2_host, &ctx->p2_host, sizeof(P2Consts)) != 0) {  // r0h_poseidon2_set_consts on the owner since the helper was made
     h->p2_host = ctx->p2_host;
@@ -237,6 +238,12 @@ const char* r0h_ctx_set_device_finish(r0h_ctx* ctx, int on) {
 const char* r0h_ctx_set_session_enqueue(r0h_ctx* ctx, int on) {
   R0H_REQUIRE(ctx, "r0h_ctx_set_session_enqueue: ctx is NULL");
   ctx->session_enqueue = on != 0 ? 1 : 0;
+  return nullptr;
+}
+const char* r0h_ctx_set_merkle_fused_tops(r0h_ctx* ctx, int on) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_merkle_fused_tops: ctx is NULL");
+  ctx->merkle_fused_tops = on != 0 ? 1 : 0;
+  for (r0h_ctx* h : ctx->helpers) h->merkle_fused_tops = ctx->merkle_fused_tops;
   return nullptr;
 }
 const char* r0h_ctx_blocking_waits(const r0h_ctx* ctx, uint64_t* count_out) {

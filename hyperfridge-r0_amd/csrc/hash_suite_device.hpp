@@ -16,6 +16,8 @@
 //   rows_waves        the waves per SIMD hash_rows_kernel is allocated for (amdgpu_waves_per_eu).  Poseidon2: the 7 the allocator
 //                     reached by itself (66 VGPRs) until the tight schedule of the partial rounds left the scheduler free to move more
 //                     of the multiply-adds (75 VGPRs, 6 waves); held to 7 it is at 66 again, without scratch.  SHA-256: what it has.
+//   Subtree           the suite merkle_subtree_kernel (merkle.hip) is instantiated for.  Poseidon2: it runs the lanes form alone, which has no
+//                     dot products, so one instantiation serves both schedules.
 //   OpenTop           the suite merkle_open_top_kernel is instantiated for.  Poseidon2: always the safe schedule -- under the tight
 //                     one the kernel (a row sponge and the pair hashes of a subtree in one body) takes 141 VGPRs instead of 118, 3 waves
 //                     instead of 4, and 44 bytes of scratch when held to 4.  The words are the same under either schedule.
@@ -82,11 +84,12 @@ struct P2DeviceT {
   static constexpr bool poseidon2 = true;
   static constexpr int rows_waves = 7;
   typedef P2DeviceT<P2DotSafe> OpenTop;
+  typedef P2DeviceT<P2DotSafe> Subtree;
   typedef P2Transcript Transcript;  // (no dot products in the lanes form: one for both schedules)
   typedef const P2Consts* __restrict__ Consts;  // (the qualifier is part of the kernels' signatures: without it hash_rows_kernel compiles to other code)
   static Consts consts(const r0h_ctx* ctx) { return ctx->p2; }
-  static constexpr const char *rows_kernel = "hash_rows_kernel", *fold_kernel = "hash_fold_kernel", *open_top_kernel = "merkle_open_top_kernel",
-                              *climb_kernel = "merkle_climb_kernel";
+  static constexpr const char *rows_kernel = "hash_rows_kernel", *fold_kernel = "hash_fold_kernel", *subtree_kernel = "merkle_subtree_kernel",
+                              *open_top_kernel = "merkle_open_top_kernel", *climb_kernel = "merkle_climb_kernel";
   static __device__ __forceinline__ void row(uint32_t (&d)[8], const uint32_t* src, uint32_t stride, uint32_t cols, Consts k) {
     uint32_t c[P2_CELLS];
     p2_hash_row<DOT>(c, src, stride, cols, k);
@@ -180,10 +183,11 @@ struct ShaDevice {
   static constexpr bool poseidon2 = false;
   static constexpr int rows_waves = 6;
   typedef ShaDevice OpenTop;
+  typedef ShaDevice Subtree;
   typedef ShaTranscript Transcript;
   typedef int Consts;  // (none: the round constants are literals)
   static Consts consts(const r0h_ctx*) { return 0; }
-  static constexpr const char *rows_kernel = "sha256_hash_rows_kernel", *fold_kernel = "sha256_hash_fold_kernel",
+  static constexpr const char *rows_kernel = "sha256_hash_rows_kernel", *fold_kernel = "sha256_hash_fold_kernel", *subtree_kernel = "sha256_merkle_subtree_kernel",
                               *open_top_kernel = "sha256_merkle_open_top_kernel", *climb_kernel = "sha256_merkle_climb_kernel";
   static __device__ __forceinline__ void row(uint32_t (&d)[8], const uint32_t* src, uint32_t stride, uint32_t cols, Consts) {
     uint32_t st[8];

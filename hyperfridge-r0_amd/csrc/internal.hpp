@@ -135,6 +135,7 @@ struct r0h_ctx {
   bool device_transcript = false;  // r0h_ctx_set_device_transcript: fri_commit and queries run on the device generator (prover.hip), one read-back for both
   bool device_finish = false;  // r0h_ctx_set_device_finish: steps 3-8 of proof_finish run on the device generator (prover.hip), one read-back for all of them
   int session_enqueue = -1;    // r0h_ctx_set_session_enqueue: phase 2 of a session from the calling thread alone (session.cpp); -1: as R0H_SESSION_ENQUEUE says
+  int merkle_fused_tops = -1;  // r0h_ctx_set_merkle_fused_tops: r0h_merkle_build ends in r0h_hash_fold_top (merkle.hip); -1: as R0H_MERKLE_FUSED_TOPS says
   uint64_t session_phase2[4] = {0, 0, 0, 0};  // r0h_last_session_phase2: host threads, blocking waits, of them ring wraps, of them replays + image proof
   std::atomic<uint64_t> ring_waits{0};      // of blocking_waits: the times stage_h2d waited because the pinned ring had wrapped around
   std::atomic<uint64_t> blocking_waits{0};  // r0h_ctx_blocking_waits: the times the library has waited for this context's stream (ctx_wait)
@@ -345,7 +346,7 @@ std::unique_ptr<HashSuite> make_suite(int fn, const P2Consts* k);
 // SHA-256 suite on the host (hash_suite.cpp): digests are 8 words whose bytes in memory are the standard big-endian SHA-256 bytes
 void sha_hash_pair_host(const uint32_t* left, const uint32_t* right, uint32_t* out);
 void sha_hash_elems_host(const uint32_t* words, size_t n, uint32_t digest[8]);
-// The device side of both suites is hash_suite_device.hpp; r0h_hash_rows / r0h_hash_fold / r0h_merkle_build are in merkle.hip, with the
+// The device side of both suites is hash_suite_device.hpp; r0h_hash_rows / r0h_hash_fold / r0h_hash_fold_top / r0h_merkle_build are in merkle.hip, with the
 // two shape checks the Merkle entry points share: "<caller>: rows n is not a power of two" and "<caller>: query q opens row r of an
 // n-row tree" for the first idx_host[q] >= rows.
 const char* require_pow2_rows(const char* caller, uint32_t rows);

@@ -7,6 +7,7 @@
 // column access of a wave is one contiguous 256-byte run.  Under Poseidon2 these kernels are VALU-integer bound (about 1.36k
 // Montgomery products per permutation), not HBM bound: see DESIGN.md for the arithmetic.
 #include "hash_suite_device.hpp"
+#include "merkle_fused_plan.hpp"
 
 namespace r0h {
 
@@ -54,6 +55,76 @@ __global__ __launch_bounds__(256) void hash_fold_lanes_kernel(uint32_t* __restri
   uint32_t c = (live && l < 16u) ? nodes[(size_t)2 * node * 8 + l] : 0u;
   c = p2_mix_lanes(c, l, k);
   if (live && l < 8u) nodes[(size_t)node * 8 + l] = c;
+}
+
+// The top of a tree without a launch per level (r0h_hash_fold_top; the plan is merkle_fused_plan.hpp).  Workgroup b owns node
+// r = G + b of the level of G nodes, reads the 2^d nodes d levels below it and folds them up to r.  The first level reads its children
+// from `nodes`; every later one reads them from LDS, where the workgroup keeps its subtree as a heap of 2^d digests (node 1 is r, the
+// children of h are 2h and 2h + 1, slot 0 is not used; a level only writes slots no earlier level wrote, so one barrier per level is
+// all the order it needs).  Every parent is also written to its place in `nodes`, for the openings, and never read from there: other
+// workgroups' stores are not visible inside a launch, and nothing here depends on them.
+// Poseidon2: one permutation per half-wave (p2_mix_lanes), as in hash_fold_lanes_kernel -- a workgroup has fewer parents than lanes
+// at every level.  Every lane runs every permutation of every level: the loop bounds are workgroup-uniform, `live` predicates loads
+// and stores only, and nothing returns before the last barrier.  SHA-256: one lane per parent.
+#ifndef R0H_MERKLE_FUSED_WG
+#define R0H_MERKLE_FUSED_WG 1024  // Poseidon2: 32 half-waves, two permutations deep at a level of 64 parents (profiles/r24/merkle_fused_tops.md)
+#endif
+constexpr uint32_t MERKLE_FUSED_WG = R0H_MERKLE_FUSED_WG;
+static_assert(MERKLE_FUSED_WG % 64 == 0 && MERKLE_FUSED_WG >= 64 && MERKLE_FUSED_WG <= 1024, "whole waves, one workgroup");
+template <class S>
+__global__ __launch_bounds__(MERKLE_FUSED_WG) void merkle_subtree_kernel(uint32_t* __restrict__ nodes, uint32_t G, uint32_t d, typename S::Consts k) {
+  extern __shared__ uint4 subtree[];
+  const uint32_t r = G + blockIdx.x;
+  for (uint32_t j = d; j-- > 0;) {
+    const uint32_t n = 1u << j;            // this level's parents: heap nodes n + p, tree nodes first + p, p < n
+    const size_t first = (size_t)r << j;
+    const bool from_nodes = j + 1 == d;
+    if constexpr (S::poseidon2) {
+      uint32_t* heap = (uint32_t*)subtree;
+      const uint32_t l = threadIdx.x & 31u, slot = threadIdx.x >> 5, slots = blockDim.x >> 5;
+      for (uint32_t p0 = 0; p0 < n; p0 += slots) {
+        const uint32_t p = p0 + slot;
+        const bool live = p < n;
+        const uint32_t h = n + (live ? p : 0u);
+        uint32_t c = 0u;
+        if (live && l < 16u) {
+          if (from_nodes) c = nodes[(first + p) * 16 + l];
+          else c = heap[h * 16 + l];
+        }
+        c = p2_mix_lanes(c, l, k);
+        if (live && l < 8u) {
+          heap[h * 8 + l] = c;
+          nodes[(first + p) * 8 + l] = c;
+        }
+      }
+    } else {
+      for (uint32_t p = threadIdx.x; p < n; p += blockDim.x) {
+        const uint32_t h = n + p;
+        const uint4* src = from_nodes ? (const uint4*)(nodes + (first + p) * 16) : subtree + 4 * h;
+        uint32_t dg[2][8];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          uint4 v = src[q];
+          uint32_t* w = &dg[q >> 1][4 * (q & 1)];
+          w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        }
+        S::pair(dg[0], dg[0], dg[1], k);
+        const uint4 lo = make_uint4(dg[0][0], dg[0][1], dg[0][2], dg[0][3]), hi = make_uint4(dg[0][4], dg[0][5], dg[0][6], dg[0][7]);
+        subtree[2 * h] = lo;
+        subtree[2 * h + 1] = hi;
+        uint4* dst = (uint4*)(nodes + (first + p) * 8);
+        dst[0] = lo;
+        dst[1] = hi;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// R0H_MERKLE_FUSED_TOPS=1: trees are built with r0h_hash_fold_top unless their context says otherwise (r0h_ctx_set_merkle_fused_tops)
+static bool merkle_fused_default() {
+  const char* v = getenv("R0H_MERKLE_FUSED_TOPS");
+  return v && strtoul(v, nullptr, 10) == 1;
 }
 
 // the two shape checks every Merkle entry point makes, under the caller's name (internal.hpp)
@@ -107,6 +178,32 @@ const char* r0h_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size) {
   R0H_GUARD_END
 }
 
+const char* r0h_hash_fold_top(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && nodes, "r0h_hash_fold_top: NULL argument");
+  R0H_REQUIRE((output_size & (output_size - 1)) == 0 && output_size <= MERKLE_FUSED_MAX_PARENTS, "r0h_hash_fold_top: output_size %u is not a power of two up to %u", output_size,
+              MERKLE_FUSED_MAX_PARENTS);
+  R0H_REQUIRE((size_t)output_size * 4 * 32 <= nodes->bytes, "r0h_hash_fold_top: output_size %u needs %zu bytes of nodes", output_size, (size_t)output_size * 128);
+  R0H_REQUIRE(((uintptr_t)nodes->ptr & 15) == 0, "r0h_hash_fold_top: node buffer must be 16-byte aligned");
+  MerkleFusedLaunch plan[2];
+  const int launches = merkle_fused_plan_top(output_size, MERKLE_FUSED_SPLIT, plan);
+  return with_suite(ctx, [&](auto suite) -> const char* {
+    using S = typename decltype(suite)::Subtree;
+    for (int i = 0; i < launches; i++) {
+      const uint32_t G = plan[i].G, d = plan[i].d;
+      R0H_REQUIRE(d >= 1 && d <= MERKLE_FUSED_MAX_D, "r0h_hash_fold_top: a launch of %u levels", d);
+      // Poseidon2: a half-wave per parent of the widest level, up to the workgroup's size; SHA-256: a lane per parent of it
+      const uint32_t want = S::poseidon2 ? 32u << (d - 1) : 1u << (d - 1);
+      const uint32_t wg = want >= MERKLE_FUSED_WG ? MERKLE_FUSED_WG : (want + 63u) & ~63u;
+      KScope ks(ctx, S::subtree_kernel, (double)G * (((size_t)2 << d) - 1) * 32);
+      hipLaunchKernelGGL(merkle_subtree_kernel<S>, dim3(G), dim3(wg), ((size_t)32 << d), ctx->stream, u32(nodes), G, d, S::consts(ctx));
+      R0H_TRY(launch_ok(S::subtree_kernel));
+    }
+    return nullptr;
+  });
+  R0H_GUARD_END
+}
+
 // Hal::hash_fold(io, input_size, output_size): the trait names both sizes (the fold halves a level, so input_size == 2 * output_size)
 const char* r0h_hash_fold_io(r0h_ctx* ctx, r0h_buf* io, uint32_t input_size, uint32_t output_size) {
   R0H_GUARD_BEGIN
@@ -124,6 +221,11 @@ const char* r0h_merkle_build(r0h_ctx* ctx, r0h_buf* nodes, const r0h_buf* matrix
   leaves.ptr = (char*)nodes->ptr + (size_t)rows * 32;
   leaves.bytes = (size_t)rows * 32;
   R0H_TRY(r0h_hash_rows(ctx, &leaves, matrix, rows, cols));
+  if (ctx->merkle_fused_tops < 0 ? merkle_fused_default() : ctx->merkle_fused_tops > 0) {  // r0h_ctx_set_merkle_fused_tops: the same nodes in fewer launches
+    uint32_t sz = rows / 2;
+    for (; sz > MERKLE_FUSED_MAX_PARENTS; sz /= 2) R0H_TRY(r0h_hash_fold(ctx, nodes, sz));
+    return r0h_hash_fold_top(ctx, nodes, sz);
+  }
   for (uint32_t sz = rows / 2; sz >= 1; sz /= 2) R0H_TRY(r0h_hash_fold(ctx, nodes, sz));
   return nullptr;
   R0H_GUARD_END

@@ -108,7 +108,9 @@ int main(int argc, char** argv) {
            "       --device-finish 0|1: with 1 every proof runs ALL the steps of its second half -- ACCUM, CHECK, the openings, DEEP, FRI, the queries -- on the transcript on the "
            "device, with one read-back for all of them, whatever --device-transcript says -- the same seals and receipts (default 0)\n"
            "       --session-enqueue 0|1: with --elf over the trace circuit; with 1 the second phase of every session is driven by the calling thread alone: each segment's session sum, "
-           "late inputs, accumulation and finish are enqueued on its lane's stream and collected one segment per lane later -- the same receipt (default: R0H_SESSION_ENQUEUE, else 0)\n%s\n", r0h_version());
+           "late inputs, accumulation and finish are enqueued on its lane's stream and collected one segment per lane later -- the same receipt (default: R0H_SESSION_ENQUEUE, else 0)\n"
+           "       --merkle-fused-tops 0|1: with 1 every Merkle tree is built with its levels of up to 8192 parents in two launches (r0h_hash_fold_top) instead of one launch per level "
+           "-- the same trees, seals and receipts (default: R0H_MERKLE_FUSED_TOPS, else 0)\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
   }
   // --compress takes no value: it is taken out of the arguments before the "--option value" pairs are read
@@ -135,6 +137,8 @@ int main(int argc, char** argv) {
   std::string device_transcript = "0";  // --device-transcript: r0h_ctx_set_device_transcript of every context
   std::string device_finish = "0";      // --device-finish: r0h_ctx_set_device_finish of every context
   std::string session_enqueue;          // --session-enqueue: r0h_ctx_set_session_enqueue of every session context (not given: the library's default)
+  bool merkle_fused_given = false;
+  std::string merkle_fused_tops;        // --merkle-fused-tops: r0h_ctx_set_merkle_fused_tops of every context (not given: the library's default)
   for (int i = 2; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--code-object")) co_path = argv[i + 1];
     else if (!strcmp(argv[i], "--po2")) po2 = (unsigned)atoi(argv[i + 1]);
@@ -157,6 +161,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--device-transcript")) device_transcript = argv[i + 1];
     else if (!strcmp(argv[i], "--device-finish")) device_finish = argv[i + 1];
     else if (!strcmp(argv[i], "--session-enqueue")) session_enqueue = argv[i + 1];
+    else if (!strcmp(argv[i], "--merkle-fused-tops")) { merkle_fused_tops = argv[i + 1]; merkle_fused_given = true; }
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
     else if (!strcmp(argv[i], "--journal")) journal_text = argv[i + 1];
@@ -201,6 +206,10 @@ int main(int argc, char** argv) {
   if (!session_enqueue.empty() && ((session_enqueue != "0" && session_enqueue != "1") || elf_path.empty())) {
     fprintf(stderr, "r0h_prove: --session-enqueue is 0 or 1 and goes with --elf, not %s\n", session_enqueue.c_str());
     return 2;
+  }
+  if (merkle_fused_given && merkle_fused_tops != "0" && merkle_fused_tops != "1") {
+    fprintf(stderr, "r0h_prove: --merkle-fused-tops is 0 or 1, not %s\n", merkle_fused_tops.c_str());
+    return 1;
   }
   if (hashfn != "poseidon2" && hashfn != "sha-256") { fprintf(stderr, "r0h_prove: --hashfn is poseidon2 or sha-256, not %s\n", hashfn.c_str()); return 1; }
   if (hashfn != "poseidon2" && (!elf_path.empty() || !receipt_out.empty() || !receipt_dir.empty() || !receipt_prefix.empty() || !camt.empty() || !image_circuit_path.empty())) {
@@ -247,6 +256,7 @@ int main(int argc, char** argv) {
     if (device_transcript == "1") CHECK(r0h_ctx_set_device_transcript(ctx, 1));
     if (device_finish == "1") CHECK(r0h_ctx_set_device_finish(ctx, 1));
     if (!session_enqueue.empty()) CHECK(r0h_ctx_set_session_enqueue(ctx, session_enqueue == "1"));
+    if (merkle_fused_given) CHECK(r0h_ctx_set_merkle_fused_tops(ctx, merkle_fused_tops == "1"));
     if (check_balance) CHECK(r0h_ctx_set_check_balance(ctx, 1));
     if (check_session) CHECK(r0h_ctx_set_check_session(ctx, 1));
     if (!check_witness) return;

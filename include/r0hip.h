@@ -94,6 +94,20 @@ const char* r0h_poseidon2_dot_schedule(const r0h_ctx* ctx, int* tight);
 const char* r0h_hash_rows(r0h_ctx* ctx, r0h_buf* digests, const r0h_buf* matrix, uint32_t rows, uint32_t cols);
 /* nodes[i] = H(nodes[2i] || nodes[2i+1]) for output_size <= i < 2*output_size (digest units) */
 const char* r0h_hash_fold(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size);
+/* The top of a tree in at most two launches.  With the level of 2 * output_size digests in place (output_size a power of two, at
+ * most 8192; anything else is refused, 0 does nothing) r0h_hash_fold_top fills the levels output_size, output_size / 2, .., 1 with the
+ * words the loop `for (sz = output_size; sz >= 1; sz /= 2) r0h_hash_fold(ctx, nodes, sz)` leaves there, under the context's hash
+ * suite: merkle_subtree_kernel folds a subtree per workgroup, a level handing its digests to the next through LDS, and workgroups
+ * hand nothing to one another inside a launch -- 128 workgroups fold down to the level of 128 nodes, one workgroup in a second
+ * launch folds from there to the root (one launch when output_size <= 64).  `nodes` as for r0h_hash_fold: 4 * output_size digests,
+ * 16-byte aligned.
+ * r0h_ctx_set_merkle_fused_tops(ctx, on != 0): r0h_merkle_build, and with it every tree the sequencer commits on this context,
+ * runs r0h_hash_fold down to the level of 16384 parents and then r0h_hash_fold_top once, instead of r0h_hash_fold for all levels.
+ * OFF BY DEFAULT; a context that was never told follows the environment (R0H_MERKLE_FUSED_TOPS=1: on).  The helper contexts of
+ * sessions and of r0h_compress follow their owner.  The same nodes word for word, so the same seals and receipts; what it saves is
+ * launches (profiles/r24/merkle_fused_tops.md).  r0h_hash_fold itself is the same with the switch on or off. */
+const char* r0h_hash_fold_top(r0h_ctx* ctx, r0h_buf* nodes, uint32_t output_size);
+const char* r0h_ctx_set_merkle_fused_tops(r0h_ctx* ctx, int on);
 /* nodes has 2*rows digests: leaves at [rows, 2rows), root at index 1 */
 const char* r0h_merkle_build(r0h_ctx* ctx, r0h_buf* nodes, const r0h_buf* matrix, uint32_t rows, uint32_t cols);
 /* A tree kept as its top.  A Merkle path needs the whole tree only because the sibling at level l covers 2^l leaves; kept from the

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-operation timing through the C ABI at bench sizes (po2 = 20): used to A/B kernel variants on the GPU box.
 usage: bench_ops.py [--hashfn poseidon2|sha-256] [--cols N] [op ...]   (--hashfn: the hash suite hash_rows / hash_fold run under;
---cols: the matrix's width, 192 by default)"""
+--cols: the matrix's width, 192 by default; hash_fold_top: the levels of 8192 .. 1 parents alone, as the fourteen launches of
+hash_fold and as r0h_hash_fold_top)"""
 import os
 import sys
 
@@ -21,7 +22,7 @@ def main():
         if o in args:
             opts[o] = args[args.index(o) + 1]
             del args[args.index(o):args.index(o) + 2]
-    ops = args or ["hash_rows", "hash_fold", "intt", "ntt", "bitrev", "zk", "evalany"]
+    ops = args or ["hash_rows", "hash_fold", "hash_fold_top", "intt", "ntt", "bitrev", "zk", "evalany"]
     hal = r0.Hal(0)
     hal.set_hashfn(opts["--hashfn"])
     po2, n, dom = 20, 1 << 20, 1 << 22
@@ -53,6 +54,14 @@ def main():
                 hal.hash_fold(nodes, sz)
                 sz //= 2
         timed("hash_fold", folds)
+    if "hash_fold_top" in ops:
+        def top_loop():
+            sz = 8192
+            while sz >= 1:
+                hal.hash_fold(nodes, sz)
+                sz //= 2
+        timed("top, loop", top_loop)
+        timed("top, fused", lambda: hal.hash_fold_top(nodes, 8192))
     if "intt" in ops:
         timed("intt", lambda: hal.batch_interpolate_ntt(src, cols, po2))
     if "ntt" in ops:

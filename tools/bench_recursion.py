@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--compress", type=int, default=None, metavar="LANES", help="one GPU: also time r0h_compress on LANES prover lanes (1..4, 0 = the default) against the sequential fold")
     ap.add_argument("--repeat", type=int, default=3, help="with --compress: timed repetitions of the fold and of compress, alternating; the minimum and all values are reported")
     ap.add_argument("--share-device", action="store_true", help="all ranks use GPU 0 (rehearsal on a one-GPU box; needs --backend gloo)")
+    ap.add_argument("--merkle-fused-tops", type=int, default=None, choices=(0, 1), help="1: r0h_ctx_set_merkle_fused_tops -- every tree's levels of up to 8192 parents in two launches "
+                    "(default: R0H_MERKLE_FUSED_TOPS, else off), the same nodes")
     args = ap.parse_args()
 
     import __graft_entry__ as entry
@@ -67,6 +69,8 @@ def main():
     from hyperfridge_r0_amd import driver, recursion
 
     hal = r0.Hal(device)
+    if args.merkle_fused_tops is not None:
+        hal.set_merkle_fused_tops(bool(args.merkle_fused_tops))
     seg_blob = np.fromfile(entry.circuit_blob_path(args.circuit), dtype=np.uint32)
     rec_blob = np.fromfile(entry.circuit_blob_path("recursion"), dtype=np.uint32)
     seg_co = entry.code_object_path(args.circuit)
