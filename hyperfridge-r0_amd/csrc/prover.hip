@@ -3,8 +3,15 @@
 // draw the accumulation mix, accumulate, finalize) and risc0-zkp 3.0.4 prove/{prover.rs, poly_group.rs, merkle.rs,
 // fri.rs, write_iop.rs} + core/hash/{poseidon2,sha}/rng.rs behind the suite interface of hash_suite.cpp -- SURVEY.md 3.4 steps 3-13, 8(a) a8, a15-a17.
 // This is what host/src/main.rs:423 (`prover.prove(env, HYPERFRIDGE_ELF)`) spends its time in, once per segment.
-// The transcript is handed over to the device (iop.hip) for steps 7-8 under r0h_ctx_set_device_transcript and for steps 3-8 under
-// r0h_ctx_set_device_finish, where proof_finish also splits into an enqueue that waits for nothing and a collect that waits once.
+//
+// One function per protocol step (proof_begin: steps 1-2; proof_steps: commit_accum, commit_check, evaluate_at_z, deep, fri_commit,
+// queries), one owner per buffer, and one question every step asks: where does the transcript live?  It starts on the host (WriteIop)
+// and may be handed over to the device generator (iop.hip; tail_open) at one of three places: before step 7
+// (r0h_ctx_set_device_transcript), before step 3 (r0h_ctx_set_device_finish) or before the late public inputs (r0h_proof_late_device).
+// After the hand-over `r0h_proof::iop` is set and the tail block exists, where the steps behind it leave their seal words for one
+// read-back (tail_collect); before it neither does.  draw_ext, commit_tree and commit_words are the transcript in either place, so a
+// step branches only where the two forms are different computations.  With the hand-over before step 3 nothing waits for the stream,
+// and proof_finish splits into an enqueue and a collect that waits once.
 //
 // Device-resident throughout: witness, coefficients, evaluations, Merkle nodes, combos.  What crosses to the host per
 // segment: Merkle tops + roots (<= 2 KB each), ~500 tap evaluations, the FRI final polynomial (4 KB) and the 50
@@ -63,25 +70,14 @@ static const char* tree_top(r0h_ctx* ctx, const Tree& t, TreeTop& top) {
   top.nodes.assign(2 * t.mp.top_size * 8, 0u);
   return r0h_buf_d2h(ctx, t.nodes.get(), 32, top.nodes.data() + 8, (2 * t.mp.top_size - 1) * 32);
 }
-// open `n_q` rows: returns packed openings on the host (their device block goes back to the pool behind the read-back).  A tree in
-// its top form reports, behind the openings in the same block, whether every queried subtree hashed to the top's node.
-static const char* tree_open(r0h_ctx* ctx, const Tree& t, const r0h_buf* d_idx, const uint32_t* idx_host, uint32_t n_q, std::vector<uint32_t>& host) {
-  DevBuf packed;
-  const size_t words = t.mp.opening_words();
-  if (t.top_levels) {
-    R0H_TRY(packed.alloc(ctx, ((size_t)n_q * words + 2) * 4));
-    R0H_TRY(merkle_open_top(ctx, u32(packed.get()), u32(t.matrix), u32(t.nodes.get()), t.top_levels, u32(d_idx), n_q, (uint32_t)t.mp.rows, (uint32_t)t.mp.cols,
-                            u32(packed.get()) + (size_t)n_q * words));
-    host.resize((size_t)n_q * words + 2);
-    R0H_TRY(r0h_buf_d2h(ctx, packed.get(), 0, host.data(), host.size() * 4));
-    const uint32_t report[2] = {host[host.size() - 2], host[host.size() - 1]};
-    host.resize((size_t)n_q * words);
-    return merkle_open_top_verdict("r0h_proof_finish", report, idx_host);
-  }
-  R0H_TRY(packed.alloc(ctx, (size_t)n_q * words * 4));
-  R0H_TRY(merkle_open(ctx, u32(packed.get()), u32(t.matrix), u32(t.nodes.get()), u32(d_idx), n_q, (uint32_t)t.mp.rows, (uint32_t)t.mp.cols));
-  host.resize((size_t)n_q * words);
-  return r0h_buf_d2h(ctx, packed.get(), 0, host.data(), host.size() * 4);
+// The rows d_idx[0 .. n_q) opened into `out`, packed (device pointers): opened_words() words.  A tree in its top form reports in the
+// last two of them whether every queried subtree hashed to the top's node (merkle_open_top_verdict reads them on the host).
+static size_t opened_words(const Tree& t, uint32_t n_q) { return (size_t)n_q * t.mp.opening_words() + (t.top_levels ? 2 : 0); }
+static const char* open_tree(r0h_ctx* ctx, const Tree& t, const uint32_t* d_idx, uint32_t n_q, uint32_t* out) {
+  if (t.top_levels)
+    return merkle_open_top(ctx, out, u32(t.matrix), u32(t.nodes.get()), t.top_levels, d_idx, n_q, (uint32_t)t.mp.rows, (uint32_t)t.mp.cols,
+                           out + (size_t)n_q * t.mp.opening_words());
+  return merkle_open(ctx, out, u32(t.matrix), u32(t.nodes.get()), d_idx, n_q, (uint32_t)t.mp.rows, (uint32_t)t.mp.cols);
 }
 
 // ------------------------------------------------------------------ poly groups
@@ -102,11 +98,10 @@ static const char* group_evaluate(r0h_ctx* ctx, Group& g, uint32_t po2) {
   g.tree.matrix = g.evaluated.get();
   return r0h_batch_expand_into_evaluate_ntt(ctx, g.evaluated.get(), g.coeffs.get(), g.count, po2, 2);
 }
-// The commit of a group: witness columns -> bit-reversed, zk-shifted coefficients -> evaluations on 4N -> tree -> its top layer and
-// root on the host (a blocking read-back: the stream has drained when this returns).  CHECK comes with its coefficients made by its
-// own interpolation (witness == nullptr).
+// A group up to its tree: witness columns -> bit-reversed, zk-shifted coefficients -> evaluations on 4N -> tree.  The tree stands in
+// device memory; its top layer and root go to the seal and the transcript by commit_tree (below), or to a CODE commitment by tree_top.
+// CHECK comes with its coefficients made by its own interpolation (witness == nullptr).
 // With `kept_top` (levels != 0) no tree is built: the group's tree takes its top form from a copy of those digests.
-// group_build is the commit without the read-back: the tree stands in device memory, its top layer and root not yet anywhere else
 static const char* group_build(r0h_ctx* ctx, Group& g, const r0h_buf* witness, uint32_t po2, const r0h_buf* kept_top = nullptr, uint32_t levels = 0) {
   if (witness) {
     const size_t bytes = ((size_t)g.count << po2) * 4;
@@ -126,10 +121,6 @@ static const char* group_build(r0h_ctx* ctx, Group& g, const r0h_buf* witness, u
     R0H_TRY(tree_build(ctx, g.tree, g.evaluated.get()));
   }
   return nullptr;
-}
-static const char* group_commit(r0h_ctx* ctx, Group& g, const r0h_buf* witness, uint32_t po2, TreeTop& top, const r0h_buf* kept_top = nullptr, uint32_t levels = 0) {
-  R0H_TRY(group_build(ctx, g, witness, po2, kept_top, levels));
-  return tree_top(ctx, g.tree, top);
 }
 
 // Lagrange interpolation of a handful of extension points (host; a register has at most a few taps)
@@ -236,8 +227,9 @@ __global__ __launch_bounds__(64) void deep_head_kernel(uint32_t* __restrict__ fi
 
 struct Round { Tree tree; DevBuf evaluated; };  // a committed FRI round
 
-// Steps 7 and 8 with the transcript on the device (r0h_ctx_set_device_transcript): where the seal's words of the two steps stand in the
-// proof's tail block, in words.  The block is read back once, at the end of step 8.
+// The steps behind the hand-over of the transcript to the device: where their seal words stand in the proof's tail block, in words.
+// Steps 7 and 8 always (r0h_ctx_set_device_transcript); the head with steps 3-6 in front of them.  The block is read back once, at
+// the end of step 8.
 struct IopFree { void operator()(r0h_iop* iop) const { r0h_iop_free(iop); } };
 struct TailLayout {
   // the head, under r0h_ctx_set_device_finish only: what steps 3-6 add to the seal, and the verdict of the DEEP divisions
@@ -296,23 +288,22 @@ struct r0h_proof {
   bool mix_drawn = false;
   const r0h_buf *check_code = nullptr, *check_data = nullptr;  // r0h_ctx_set_check_witness: the witness columns proof_finish checks (the caller's buffers)
   // what a step of proof_finish leaves for the steps after it
-  r0h::Fp4 z, z4;                  // the DEEP point and its fourth power, where CHECK is opened
-  uint32_t back_one = 0;           // omega^-1: a tap `back` rows behind is opened at z * back_one^back
-  std::vector<r0h::Fp4> coeff_u;   // per register the interpolant through its openings, then CHECK's sixteen openings
-  r0h::DevBuf fri_coeffs;          // the FRI input; inside step 7 what the rounds so far have folded it to
+  // the point table of steps 5 and 6: z * omega^-back for every distinct back of the circuit's taps, then z^4, where CHECK is opened.
+  // On the host (`points_host`) or, after the hand-over, on the device (`points`: behind the points the host-known omega^-back)
+  uint32_t n_points = 0;
+  uint32_t point_of_back[64] = {0};
+  std::vector<r0h::Fp4> points_host;
+  r0h::DevBuf points;
+  std::vector<r0h::Fp4> coeff_u;       // (host) per register the interpolant through its openings, then CHECK's sixteen openings
+  std::vector<uint32_t> divide_combo;  // the combo of every DEEP division in job order (whom the tail's report word names)
+  r0h::DevBuf fri_coeffs;              // the FRI input; inside step 7 what the rounds so far have folded it to
   std::vector<r0h::Round> rounds;
-  // steps 7 and 8 under r0h_ctx_set_device_transcript: the generator the host's was handed over to, and the seal words of both steps
+  // The hand-over: once the host generator has gone to the device, `iop` is that generator and `tail` the block the steps behind it
+  // write their seal words into (laid out by `tail_at`); before it, neither exists.  Every step asks `iop` where the transcript lives.
   std::unique_ptr<r0h_iop, r0h::IopFree> iop;
   r0h::DevBuf tail;
   r0h::TailLayout tail_at;
-  // steps 3-8 under r0h_ctx_set_device_finish: the point table of steps 5 and 6 (a point per distinct back of the circuit's taps, then
-  // z^4; behind them the host-known omega^-back), the combo of every DEEP division in job order (whom the tail's report word names), and
-  // whether the steps have been enqueued (r0h_proof_finish_enqueue) and wait for r0h_proof_finish_collect
-  r0h::DevBuf points;
-  uint32_t n_points = 0;
-  uint32_t point_of_back[64] = {0};
-  std::vector<uint32_t> divide_combo;
-  bool enqueued = false;
+  bool enqueued = false;  // the steps have been enqueued (r0h_proof_finish_enqueue) and wait for r0h_proof_finish_collect
   // r0h_proof_late_device: the late public inputs were absorbed and the mix drawn by the device generator (they stand in the tail; the
   // host's `mix` and the late part of `global` are zeros until the collect).  A circuit without late inputs has drawn its mix on the
   // host at proof_begin: `pre_mix_state` is the generator as it was before, which the device form starts from to draw the same words.
@@ -337,14 +328,56 @@ static const char* code_commit(r0h_ctx* ctx, r0h_code_commit& cc, const r0h_buf*
   cc.ctx = ctx;
   cc.hashfn = ctx->hashfn;
   cc.witness = columns;
-  return group_commit(ctx, cc.g, columns, cc.po2, cc.top);
+  R0H_TRY(group_build(ctx, cc.g, columns, cc.po2));
+  return tree_top(ctx, cc.g.tree, cc.top);  // (a blocking read-back: the stream has drained when this returns)
 }
-// a group of the proof committed: its top layer into the seal, its root into the transcript
-static const char* proof_commit(r0h_proof& st, Group& g, const r0h_buf* witness, const r0h_buf* kept_top = nullptr, uint32_t levels = 0) {
-  TreeTop top;
-  R0H_TRY(group_commit(st.ctx, g, witness, st.po2, top, kept_top, levels));
-  top.into(st.io);
+
+// ------------------------------------------------------------------ the transcript, wherever it lives
+// A proof's steps talk to the transcript through the three helpers below.  Each asks `st.iop`: null, and the generator is the host's
+// (`st.io.rng`), seal words are read back and appended to `st.io.proof` -- a wait each; set, and the generator is the device's, seal
+// words go device to device into their place in the tail block (a word offset, from `st.tail_at`), and nothing waits.
+static const char* copy_words(r0h_ctx* ctx, r0h_buf* dst, size_t dst_word, const r0h_buf* src, size_t src_word, size_t n) {
+  R0H_TRY_HIP(hipMemcpyAsync(u32(dst) + dst_word, u32(src) + src_word, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
   return nullptr;
+}
+// A challenge: in `host`, or in the four device words at `dev` (the tail's, which the next kernels read)
+struct Challenge {
+  Fp4 host;
+  const uint32_t* dev = nullptr;
+};
+static const char* draw_ext(r0h_proof& st, size_t tail_slot, Challenge& out) {
+  if (!st.iop) {
+    out.host = st.io.rng.ext();
+    return nullptr;
+  }
+  R0H_TRY(r0h_iop_draw_ext(st.iop.get(), st.tail.get(), tail_slot, 1));
+  out.dev = u32(st.tail.get()) + tail_slot;
+  return nullptr;
+}
+// A built tree committed: its top layer -- nodes [top_size, 2 * top_size) -- into the seal, its root -- node 1 -- into the transcript
+static const char* commit_tree(r0h_proof& st, const Tree& t, size_t tail_slot) {
+  if (!st.iop) {
+    TreeTop top;
+    R0H_TRY(tree_top(st.ctx, t, top));
+    top.into(st.io);
+    return nullptr;
+  }
+  const size_t top_words = 8 * t.mp.top_size;
+  R0H_TRY(copy_words(st.ctx, st.tail.get(), tail_slot, t.nodes.get(), top_words, top_words));
+  return r0h_iop_commit(st.iop.get(), t.nodes.get(), 8);
+}
+// `n` seal words that lie in device memory, at word `src_word` of `src`, written to the seal and committed as elements.  Words a
+// kernel has put into their tail slot itself need no copy (src == the tail).
+static const char* commit_words(r0h_proof& st, const r0h_buf* src, size_t src_word, size_t n, size_t tail_slot) {
+  if (!st.iop) {
+    std::vector<uint32_t> w(n);
+    R0H_TRY(r0h_buf_d2h(st.ctx, src, src_word * 4, w.data(), n * 4));
+    st.io.write(w.data(), n);
+    st.io.commit_elems(w.data(), n);
+    return nullptr;
+  }
+  if (src != st.tail.get()) R0H_TRY(copy_words(st.ctx, st.tail.get(), tail_slot, src, src_word, n));
+  return r0h_iop_commit_elems(st.iop.get(), st.tail.get(), tail_slot, n);
 }
 
 static const char* proof_late(r0h_proof& st, const uint32_t* late);
@@ -390,7 +423,8 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_
   R0H_REQUIRE(code.ctx->device == ctx->device, "prove_segment: the CODE commitment lives on device %d, this context on device %d", code.ctx->device, ctx->device);
   code.top.into(io);  // the same words whoever committed
   profile_phase(ctx, "commit_data");
-  R0H_TRY(proof_commit(st, st.g_data, data, data_top, top_levels));
+  R0H_TRY(group_build(ctx, st.g_data, data, po2, data_top, top_levels));
+  R0H_TRY(commit_tree(st, st.g_data.tree, 0));  // (on the host: the hand-over comes later, if at all)
   R0H_TRY(r0h_buf_d2h(ctx, st.g_data.tree.nodes.get(), 32, st.data_root, 32));
   if (!circ->n_late) {
     st.pre_mix_state.resize(SUITE_RNG_MAX_WORDS);
@@ -418,237 +452,7 @@ static const char* proof_late(r0h_proof& st, const uint32_t* late) {
   return nullptr;
 }
 
-// step 3: commit ACCUM -- behind the DATA evaluations made again where r0h_proof_shrink gave them back, and the witness check where it is on
-static const char* commit_accum(r0h_proof& st, const r0h_buf* accum) {
-  r0h_ctx* ctx = st.ctx;
-  if (!st.g_data.evaluated) {  // the same expanding NTT over the kept coefficients
-    profile_phase(ctx, "evaluate_data_again");
-    R0H_TRY(group_evaluate(ctx, st.g_data, st.po2));
-  }
-  if (st.check_data) {
-    profile_phase(ctx, "check_witness");
-    R0H_TRY(require_witness("prove_segment", ctx, st.circ, st.po2, accum, st.check_code, st.check_data, st.global.data(), st.mix.data()));
-  }
-  profile_phase(ctx, "commit_accum");
-  return proof_commit(st, st.g_accum, accum);
-}
-
-// step 4: the constraint check on the 4N coset, and CHECK committed
-static const char* commit_check(r0h_proof& st) {
-  r0h_ctx* ctx = st.ctx;
-  Group& g_check = st.g_check;
-  profile_phase(ctx, "eval_check");
-  const Fp4 poly_mix = st.io.rng.ext();
-  R0H_TRY(g_check.coeffs.alloc(ctx, ((size_t)R0H_INV_RATE << st.po2) * 16));
-  R0H_TRY(r0h_eval_check(ctx, st.circ, st.po2, st.g_accum.evaluated.get(), st.code->g.evaluated.get(), st.g_data.evaluated.get(), st.global.data(), st.mix.data(),
-                         poly_mix.e, g_check.coeffs.get()));
-  profile_phase(ctx, "commit_check");
-  R0H_TRY(r0h_batch_interpolate_ntt(ctx, g_check.coeffs.get(), 4, st.po2 + 2));  // 4 polys of 4N == 16 polys of N (bit-reversed)
-  return proof_commit(st, g_check, nullptr);
-}
-
-// step 5: every tap opened at z * omega^-back and CHECK at z^4; coeff_u into the seal and the transcript
-static const char* evaluate_at_z(r0h_proof& st) {
-  r0h_ctx* ctx = st.ctx;
-  const r0h_circuit* circ = st.circ;
-  profile_phase(ctx, "evaluate_at_z");
-  st.z = st.io.rng.ext();
-  st.z4 = fp4_pow(st.z, 4);
-  st.back_one = rou_rev(st.po2);
-  const uint32_t n_taps = (uint32_t)circ->taps.size(), n_u = n_taps + R0H_CHECK_SIZE;  // CHECK's columns stand behind the taps, as a fourth group
-  std::vector<Fp4> all_xs(n_u), eval_u(n_u);
-  std::vector<uint32_t> which(n_u);
-  DevBuf d_eval;
-  R0H_TRY(d_eval.alloc(ctx, (size_t)n_u * 16));
-  for (uint32_t t = 0; t < n_taps; t++) {
-    all_xs[t] = scale(st.z, fpow(st.back_one, circ->taps[t].back));
-    which[t] = circ->taps[t].offset;
-  }
-  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) { all_xs[n_taps + i] = st.z4; which[n_taps + i] = i; }
-  for (int g = 0; g < 4; g++) {
-    const uint32_t b = circ->group_tap_begin[g], e = g < 3 ? circ->group_tap_begin[g + 1] : n_u;
-    if (e == b) continue;
-    r0h_buf view = buf_view(d_eval.get(), (size_t)b * 16, (size_t)(e - b) * 16);
-    R0H_TRY(evaluate_any(ctx, st.group(g).coeffs.get(), st.po2, which.data() + b, (const uint32_t*)(all_xs.data() + b), e - b, &view, true));
-  }
-  R0H_TRY(r0h_buf_d2h(ctx, d_eval.get(), 0, eval_u.data(), (size_t)n_u * 16));
-  st.coeff_u.resize(n_u);
-  for (const Reg& reg : circ->regs) poly_interpolate(&st.coeff_u[reg.first_tap], &all_xs[reg.first_tap], &eval_u[reg.first_tap], reg.size);
-  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) st.coeff_u[n_taps + i] = eval_u[n_taps + i];
-  st.io.write((const uint32_t*)st.coeff_u.data(), 4 * (size_t)n_u);
-  st.io.commit_elems((const uint32_t*)st.coeff_u.data(), 4 * (size_t)n_u);
-  return nullptr;
-}
-
-// step 6, second part: subtract the interpolants from the mixed combos -- only the first few coefficients of each combo change
-static const char* subtract_interpolants(r0h_proof& st, r0h_buf* combos, const Fp4& mixv, uint32_t n_combos) {
-  const uint32_t n_taps = (uint32_t)st.circ->taps.size();
-  std::vector<Fp4> head((size_t)(n_combos + 1) * 64, fp4_zero());
-  std::vector<uint32_t> head_len(n_combos + 1, 0);
-  Fp4 cur = fp4_one();
-  for (const Reg& reg : st.circ->regs) {
-    R0H_REQUIRE(reg.size <= 64, "prove_segment: register with more than 64 taps");
-    for (uint32_t i = 0; i < reg.size; i++) {
-      Fp4& h = head[(size_t)reg.combo * 64 + i];
-      h = h + cur * st.coeff_u[reg.first_tap + i];
-    }
-    if (reg.size > head_len[reg.combo]) head_len[reg.combo] = reg.size;
-    cur = cur * mixv;
-  }
-  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) {
-    head[(size_t)n_combos * 64] = head[(size_t)n_combos * 64] + cur * st.coeff_u[n_taps + i];
-    cur = cur * mixv;
-  }
-  head_len[n_combos] = 1;
-  std::vector<uint32_t> fix;  // (word index, value) pairs
-  for (uint32_t k = 0; k <= n_combos; k++)
-    for (uint32_t i = 0; i < head_len[k]; i++)
-      for (uint32_t q = 0; q < 4; q++) {
-        fix.push_back((uint32_t)((((size_t)k << st.po2) + i) * 4 + q));
-        fix.push_back(head[(size_t)k * 64 + i].e[q]);
-      }
-  R0H_REQUIRE(((size_t)(n_combos + 1) << st.po2) * 4 < ((size_t)1 << 32), "prove_segment: combos buffer exceeds 32-bit word indexing");
-  DevBuf d_fix;  // back to the pool once the kernel that reads it is enqueued
-  R0H_TRY(d_fix.alloc(st.ctx, fix.size() * 4));
-  R0H_TRY(stage_h2d(st.ctx, d_fix->ptr, fix.data(), fix.size() * 4));
-  const uint32_t nf = (uint32_t)(fix.size() / 2);
-  hipLaunchKernelGGL(sub_head_kernel, dim3((nf + 255) / 256), dim3(256), 0, st.ctx->stream, u32(combos), u32(d_fix.get()), nf);
-  return launch_ok("sub_head_kernel");
-}
-
-// step 6, third part: every (combo, point) division of the DEEP step as one batch: a launch set per "k-th point of every combo", one
-// read-back of all remainders (upstream divides on the host; round 1 here ran one scan and one host sync per division)
-static const char* deep_divide(r0h_proof& st, r0h_buf* combos, uint32_t n_combos) {
-  const r0h_circuit* circ = st.circ;
-  std::vector<uint32_t> job_poly, job_pt;
-  for (uint32_t k = 0; k <= n_combos; k++) {
-    if (k < n_combos) {
-      for (uint32_t b = circ->combo_begin[k]; b < circ->combo_begin[k + 1]; b++) {
-        const Fp4 pt = scale(st.z, fpow(st.back_one, circ->combo_backs[b]));
-        job_poly.push_back(k);
-        job_pt.insert(job_pt.end(), pt.e, pt.e + 4);
-      }
-    } else {
-      job_poly.push_back(k);
-      job_pt.insert(job_pt.end(), st.z4.e, st.z4.e + 4);
-    }
-  }
-  std::vector<uint32_t> rem(4 * job_poly.size());
-  R0H_TRY(poly_divide_batch(st.ctx, combos, 1u << st.po2, job_poly.data(), job_pt.data(), (uint32_t)job_poly.size(), rem.data()));
-  for (size_t j = 0; j < job_poly.size(); j++)
-    R0H_REQUIRE(!(rem[4 * j] | rem[4 * j + 1] | rem[4 * j + 2] | rem[4 * j + 3]),
-                "prove_segment: DEEP quotient of combo %u has a non-zero remainder (witness violates the taps?)", job_poly[j]);
-  return nullptr;
-}
-
-// step 6: the columns of the four groups mixed into the combos, the interpolants subtracted, the divisions, the sum: the FRI input
-static const char* deep(r0h_proof& st) {
-  r0h_ctx* ctx = st.ctx;
-  const r0h_circuit* circ = st.circ;
-  const uint32_t po2 = st.po2, n = 1u << po2;
-  profile_phase(ctx, "mix_combos");
-  const Fp4 mixv = st.io.rng.ext();
-  const uint32_t n_combos = (uint32_t)circ->combo_begin.size() - 1;
-  DevBuf combos;  // back to the pool on return: before the first FRI round
-  R0H_TRY(combos.alloc(ctx, (size_t)(n_combos + 1) * n * 16));
-  R0H_TRY(r0h_buf_zero(ctx, combos.get()));
-  Fp4 cur = fp4_one();
-  for (int g = 0; g < 4; g++) {
-    const uint32_t gs = st.group(g).count;
-    std::vector<uint32_t> combo_of(gs, g < 3 ? 0u : n_combos);  // CHECK's columns all go into the last combo
-    for (const Reg& reg : circ->regs)
-      if (reg.group == (uint32_t)g) combo_of[reg.offset] = reg.combo;
-    R0H_TRY(r0h_mix_poly_coeffs(ctx, combos.get(), cur.e, mixv.e, st.group(g).coeffs.get(), combo_of.data(), gs, po2));
-    cur = cur * fp4_pow(mixv, gs);
-  }
-  R0H_TRY(bit_reverse_ext(ctx, combos.get(), n_combos + 1, po2));  // combos were mixed in bit-reversed order: natural from here on
-  R0H_TRY(subtract_interpolants(st, combos.get(), mixv, n_combos));
-  profile_phase(ctx, "deep_divide");
-  R0H_TRY(deep_divide(st, combos.get(), n_combos));
-  R0H_TRY(st.fri_coeffs.alloc(ctx, (size_t)n * 16));
-  R0H_TRY(r0h_eltwise_sum_extelem(ctx, st.fri_coeffs.get(), combos.get(), n_combos + 1, n));
-  return r0h_batch_bit_reverse(ctx, st.fri_coeffs.get(), 4, po2);
-}
-
-// step 7: per round evaluate, commit, draw the fold mix, fold by 16; what is left goes into the seal as it is
-static const char* fri_commit(r0h_proof& st) {
-  r0h_ctx* ctx = st.ctx;
-  WriteIop& io = st.io;
-  profile_phase(ctx, "fri_commit");
-  const FriSchedule fri((size_t)1 << st.po2);
-  for (const FriRound& fr : fri.rounds) {
-    Round rd{Tree(fr.rows, R0H_FRI_FOLD * 4), DevBuf()};
-    R0H_TRY(rd.evaluated.alloc(ctx, fr.domain * 16));
-    R0H_TRY(r0h_batch_expand_into_evaluate_ntt(ctx, rd.evaluated.get(), st.fri_coeffs.get(), 4, log2u(fr.degree), 2));
-    R0H_TRY(tree_build(ctx, rd.tree, rd.evaluated.get()));
-    TreeTop top;
-    R0H_TRY(tree_top(ctx, rd.tree, top));
-    top.into(io);
-    const Fp4 fold_mix = io.rng.ext();
-    DevBuf folded;
-    R0H_TRY(folded.alloc(ctx, fr.degree / R0H_FRI_FOLD * 16));
-    R0H_TRY(r0h_fri_fold(ctx, folded.get(), st.fri_coeffs.get(), fold_mix.e, (uint32_t)(fr.degree / R0H_FRI_FOLD)));
-    st.fri_coeffs = std::move(folded);  // the coefficients it was folded from go back to the pool
-    st.rounds.push_back(std::move(rd));
-  }
-  R0H_TRY(r0h_batch_bit_reverse(ctx, st.fri_coeffs.get(), 4, log2u(fri.final_degree)));
-  std::vector<uint32_t> fc(4 * fri.final_degree);
-  R0H_TRY(r0h_buf_d2h(ctx, st.fri_coeffs.get(), 0, fc.data(), fc.size() * 4));
-  st.fri_coeffs.reset();
-  io.write(fc.data(), fc.size());
-  io.commit_elems(fc.data(), fc.size());
-  return nullptr;
-}
-
-// step 8: the query positions depend only on the transcript state, not on the openings: draw all of them, then open each tree for
-// all queries in one kernel + one copy
-static const char* queries(r0h_proof& st) {
-  r0h_ctx* ctx = st.ctx;
-  profile_phase(ctx, "queries");
-  const size_t domain = (size_t)R0H_INV_RATE << st.po2;
-  std::vector<const Tree*> trees;
-  for (int g = 0; g < 4; g++) trees.push_back(&st.group(g).tree);
-  for (const Round& rd : st.rounds) trees.push_back(&rd.tree);
-  const uint32_t nq = R0H_QUERIES, n_trees = (uint32_t)trees.size();
-  std::vector<uint32_t> idx((size_t)n_trees * nq);
-  for (uint32_t q = 0; q < nq; q++) {
-    size_t pos = st.io.rng.bits(log2u(domain)) % domain;
-    for (uint32_t t = 0; t < n_trees; t++) {
-      if (t >= 4) pos = pos % trees[t]->mp.rows;
-      idx[(size_t)t * nq + q] = (uint32_t)pos;
-    }
-  }
-  DevBuf d_idx;
-  R0H_TRY(d_idx.alloc(ctx, idx.size() * 4));
-  R0H_TRY(stage_h2d(ctx, d_idx->ptr, idx.data(), idx.size() * 4));
-  std::vector<std::vector<uint32_t>> opened(n_trees);
-  for (uint32_t t = 0; t < n_trees; t++) {
-    r0h_buf view = buf_view(d_idx.get(), (size_t)t * nq * 4, (size_t)nq * 4);
-    R0H_TRY(tree_open(ctx, *trees[t], &view, idx.data() + (size_t)t * nq, nq, opened[t]));
-  }
-  for (uint32_t q = 0; q < nq; q++)
-    for (uint32_t t = 0; t < n_trees; t++) {
-      const size_t w = trees[t]->mp.opening_words();
-      st.io.write(opened[t].data() + (size_t)q * w, w);
-    }
-  return nullptr;
-}
-
-// ---- steps 7 and 8 on the device transcript.  The host generator's state goes up once; roots are committed from the trees' nodes, the
-// fold mixes and the query rows are drawn into device words the next kernels read, and every word the two steps add to the seal is
-// copied, device to device, into the proof's tail block.  One read-back at the end of step 8 brings the block home; the host then
-// appends its parts to the seal in the order the host steps write them.
-static const char* copy_words(r0h_ctx* ctx, r0h_buf* dst, size_t dst_word, const r0h_buf* src, size_t src_word, size_t n) {
-  R0H_TRY_HIP(hipMemcpyAsync(u32(dst) + dst_word, u32(src) + src_word, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  return nullptr;
-}
-static std::vector<const Tree*> proof_trees(const r0h_proof& st) {  // in the order of the seal's openings
-  std::vector<const Tree*> trees;
-  for (int g = 0; g < 4; g++) trees.push_back(&st.group(g).tree);
-  for (const Round& rd : st.rounds) trees.push_back(&rd.tree);
-  return trees;
-}
-
+// ------------------------------------------------------------------ the hand-over
 // The tail block laid out and taken from the pool, and the host generator handed over to the device (its state goes up in stream
 // order).  With `head` the block starts with what steps 3-6 add to the seal; every part of it keeps its offset modulo 8 words.
 static const char* tail_open(r0h_proof& st, bool head, bool late = false) {
@@ -753,20 +557,10 @@ static const char* proof_late_device(r0h_proof& st, const r0h_buf* late, r0h_buf
   return nullptr;
 }
 
-// a group committed on the device transcript: its top layer device to device into the tail, its root -- node 1 -- into the generator
-static const char* proof_commit_device(r0h_proof& st, Group& g, const r0h_buf* witness, size_t top_at) {
-  R0H_TRY(group_build(st.ctx, g, witness, st.po2));
-  const size_t top_words = 8 * g.tree.mp.top_size;  // nodes [top_size, 2 * top_size)
-  R0H_TRY(copy_words(st.ctx, st.tail.get(), top_at, g.tree.nodes.get(), top_words, top_words));
-  return r0h_iop_commit(st.iop.get(), g.tree.nodes.get(), 8);
-}
-
-// ---- steps 3-6 on the device transcript (r0h_ctx_set_device_finish).  The generator goes up before step 3; from there every challenge
-// is drawn into the tail's device-only words and the tables that depend on it are filled by kernels, so nothing waits for the stream
-// (but the witness checker, where it is on).  The seal words of the four steps stand in the tail's head.
-static const char* commit_accum_device(r0h_proof& st, const r0h_buf* accum) {
+// step 3: commit ACCUM -- behind the DATA evaluations made again where r0h_proof_shrink gave them back, and the witness check where it is on
+static const char* commit_accum(r0h_proof& st, const r0h_buf* accum) {
   r0h_ctx* ctx = st.ctx;
-  if (!st.g_data.evaluated) {
+  if (!st.g_data.evaluated) {  // the same expanding NTT over the kept coefficients
     profile_phase(ctx, "evaluate_data_again");
     R0H_TRY(group_evaluate(ctx, st.g_data, st.po2));
   }
@@ -781,98 +575,159 @@ static const char* commit_accum_device(r0h_proof& st, const r0h_buf* accum) {
     R0H_TRY(require_witness("prove_segment", ctx, st.circ, st.po2, accum, st.check_code, st.check_data, st.global.data(), st.mix.data()));
   }
   profile_phase(ctx, "commit_accum");
-  return proof_commit_device(st, st.g_accum, accum, st.tail_at.accum_top);
+  R0H_TRY(group_build(ctx, st.g_accum, accum, st.po2));
+  return commit_tree(st, st.g_accum.tree, st.tail_at.accum_top);
 }
 
-static const char* commit_check_device(r0h_proof& st) {
+// step 4: the constraint check on the 4N coset, and CHECK committed
+static const char* commit_check(r0h_proof& st) {
   r0h_ctx* ctx = st.ctx;
   Group& g_check = st.g_check;
   profile_phase(ctx, "eval_check");
-  R0H_TRY(r0h_iop_draw_ext(st.iop.get(), st.tail.get(), st.tail_at.poly_mix, 1));
+  Challenge poly_mix;
+  R0H_TRY(draw_ext(st, st.tail_at.poly_mix, poly_mix));
   R0H_TRY(g_check.coeffs.alloc(ctx, ((size_t)R0H_INV_RATE << st.po2) * 16));
-  R0H_TRY(eval_check_dev(ctx, st.circ, st.po2, st.g_accum.evaluated.get(), st.code->g.evaluated.get(), st.g_data.evaluated.get(), st.global.data(), st.mix.data(),
-                         u32(st.tail.get()) + st.tail_at.poly_mix, g_check.coeffs.get(), st.late_device ? u32(st.tail.get()) + st.tail_at.late_words : nullptr,
-                         st.late_device ? u32(st.tail.get()) + st.tail_at.mix : nullptr));
+  const r0h_buf *accum = st.g_accum.evaluated.get(), *code = st.code->g.evaluated.get(), *data = st.g_data.evaluated.get();
+  if (poly_mix.dev) {  // (r0h_proof_late_device: the late public inputs and the mix are the tail's words as well)
+    const uint32_t* tail = u32(st.tail.get());
+    R0H_TRY(eval_check_dev(ctx, st.circ, st.po2, accum, code, data, st.global.data(), st.mix.data(), poly_mix.dev, g_check.coeffs.get(),
+                           st.late_device ? tail + st.tail_at.late_words : nullptr, st.late_device ? tail + st.tail_at.mix : nullptr));
+  } else {
+    R0H_TRY(r0h_eval_check(ctx, st.circ, st.po2, accum, code, data, st.global.data(), st.mix.data(), poly_mix.host.e, g_check.coeffs.get()));
+  }
   profile_phase(ctx, "commit_check");
-  R0H_TRY(r0h_batch_interpolate_ntt(ctx, g_check.coeffs.get(), 4, st.po2 + 2));
-  return proof_commit_device(st, g_check, nullptr, st.tail_at.check_top);
+  R0H_TRY(r0h_batch_interpolate_ntt(ctx, g_check.coeffs.get(), 4, st.po2 + 2));  // 4 polys of 4N == 16 polys of N (bit-reversed)
+  R0H_TRY(group_build(ctx, g_check, nullptr, st.po2));
+  return commit_tree(st, g_check.tree, st.tail_at.check_top);
 }
 
-static const char* evaluate_at_z_device(r0h_proof& st) {
+// Steps 5 and 6 always run in the same form: the transcript is handed over before step 3, before step 7 or not at all, never between
+// them.  So step 6 finds the point table, and coeff_u, where step 5 left them -- on the host, or on the device and in the tail.
+//
+// the point table: a point per distinct back of the circuit's taps (the blob format admits backs below 64), then z^4
+static const char* deep_points(r0h_proof& st, const Challenge& z) {
   r0h_ctx* ctx = st.ctx;
-  const r0h_circuit* circ = st.circ;
-  profile_phase(ctx, "evaluate_at_z");
-  uint32_t* tail = u32(st.tail.get());
-  R0H_TRY(r0h_iop_draw_ext(st.iop.get(), st.tail.get(), st.tail_at.z, 1));
-  // the point table: a point per distinct back (the blob format admits backs below 64), then z^4
-  st.back_one = rou_rev(st.po2);
+  const uint32_t back_one = rou_rev(st.po2);  // omega^-1: a tap `back` rows behind is opened at z * back_one^back
   bool has_back[64] = {false};
-  for (const Tap& t : circ->taps) has_back[t.back] = true;
+  for (const Tap& t : st.circ->taps) has_back[t.back] = true;
   std::vector<uint32_t> wpow;
   for (uint32_t b = 0; b < 64; b++)
-    if (has_back[b]) { st.point_of_back[b] = (uint32_t)wpow.size(); wpow.push_back(fpow(st.back_one, b)); }
+    if (has_back[b]) { st.point_of_back[b] = (uint32_t)wpow.size(); wpow.push_back(fpow(back_one, b)); }
   const uint32_t n_backs = (uint32_t)wpow.size();
   st.n_points = n_backs + 1;
+  if (!z.dev) {
+    st.points_host.resize(st.n_points);
+    for (uint32_t i = 0; i < n_backs; i++) st.points_host[i] = scale(z.host, wpow[i]);
+    st.points_host[n_backs] = fp4_pow(z.host, 4);
+    return nullptr;
+  }
   R0H_TRY(st.points.alloc(ctx, (size_t)(4 * st.n_points + n_backs) * 4));
   uint32_t* pts = u32(st.points.get());
   R0H_TRY(stage_h2d(ctx, pts + 4 * st.n_points, wpow.data(), wpow.size() * 4));
-  {
-    KScope ks(ctx, "deep_points_kernel", 16.0 * st.n_points);
-    hipLaunchKernelGGL(deep_points_kernel, dim3((st.n_points + 63) / 64), dim3(64), 0, ctx->stream, pts, tail + st.tail_at.z, pts + 4 * st.n_points, n_backs);
-    R0H_TRY(launch_ok("deep_points_kernel"));
-  }
-  const uint32_t n_taps = (uint32_t)circ->taps.size(), n_u = n_taps + R0H_CHECK_SIZE, n_regs = (uint32_t)circ->regs.size();
-  std::vector<uint32_t> which(n_u), pt(n_u);
-  for (uint32_t t = 0; t < n_taps; t++) { which[t] = circ->taps[t].offset; pt[t] = st.point_of_back[circ->taps[t].back]; }
-  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) { which[n_taps + i] = i; pt[n_taps + i] = n_backs; }
-  DevBuf d_eval;
-  R0H_TRY(d_eval.alloc(ctx, (size_t)n_u * 16));
-  for (int g = 0; g < 4; g++) {
-    const uint32_t b = circ->group_tap_begin[g], e = g < 3 ? circ->group_tap_begin[g + 1] : n_u;
-    if (e == b) continue;
-    r0h_buf view = buf_view(d_eval.get(), (size_t)b * 16, (size_t)(e - b) * 16);
-    R0H_TRY(evaluate_any_points(ctx, st.group(g).coeffs.get(), st.po2, which.data() + b, pt.data() + b, e - b, pts, st.n_points, &view, true));
-  }
+  KScope ks(ctx, "deep_points_kernel", 16.0 * st.n_points);
+  hipLaunchKernelGGL(deep_points_kernel, dim3((st.n_points + 63) / 64), dim3(64), 0, ctx->stream, pts, z.dev, pts + 4 * st.n_points, n_backs);
+  return launch_ok("deep_points_kernel");
+}
+// step 5's middle on the host: the evaluations read back, every register's interpolant through its openings by poly_interpolate
+static const char* interpolate_host(r0h_proof& st, const r0h_buf* d_eval, const std::vector<Fp4>& xs) {
+  const uint32_t n_u = (uint32_t)xs.size(), n_taps = n_u - R0H_CHECK_SIZE;
+  std::vector<Fp4> eval_u(n_u);
+  R0H_TRY(r0h_buf_d2h(st.ctx, d_eval, 0, eval_u.data(), (size_t)n_u * 16));
+  st.coeff_u.resize(n_u);
+  for (const Reg& reg : st.circ->regs) poly_interpolate(&st.coeff_u[reg.first_tap], &xs[reg.first_tap], &eval_u[reg.first_tap], reg.size);
+  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) st.coeff_u[n_taps + i] = eval_u[n_taps + i];
+  return nullptr;
+}
+// and on the device: interpolate_regs_kernel writes coeff_u into its place in the tail
+static const char* interpolate_device(r0h_proof& st, const r0h_buf* d_eval, const std::vector<uint32_t>& pt) {
+  r0h_ctx* ctx = st.ctx;
+  const uint32_t n_u = (uint32_t)pt.size(), n_taps = n_u - R0H_CHECK_SIZE, n_regs = (uint32_t)st.circ->regs.size();
   // the registers' table: [point of every tap][per register: first tap, taps, first work slot], then the work slots (taps + 1 a register)
   std::vector<uint32_t> table(pt.begin(), pt.begin() + n_taps);
   uint32_t work_slots = 0;
-  for (const Reg& reg : circ->regs) {
-    R0H_REQUIRE(reg.size >= 1 && reg.size <= 64, "prove_segment: register with %u taps", reg.size);
+  for (const Reg& reg : st.circ->regs) {
     table.insert(table.end(), {reg.first_tap, reg.size, work_slots});
     work_slots += reg.size + 1;
   }
   DevBuf d_regs;
   R0H_TRY(d_regs.alloc(ctx, (table.size() + 4 * (size_t)work_slots) * 4));
   R0H_TRY(stage_h2d(ctx, d_regs->ptr, table.data(), table.size() * 4));
-  {
-    KScope ks(ctx, "interpolate_regs_kernel", 32.0 * n_u);
-    const uint32_t* d_table = u32(d_regs.get());
-    hipLaunchKernelGGL(interpolate_regs_kernel, dim3((n_regs + R0H_CHECK_SIZE + 63) / 64), dim3(64), 0, ctx->stream, tail + st.tail_at.coeff_u, u32(d_eval.get()), pts, d_table,
-                       d_table + n_taps, n_regs, n_taps, u32(d_regs.get()) + table.size());
-    R0H_TRY(launch_ok("interpolate_regs_kernel"));
-  }
-  return r0h_iop_commit_elems(st.iop.get(), st.tail.get(), st.tail_at.coeff_u, 4 * (size_t)n_u);
+  KScope ks(ctx, "interpolate_regs_kernel", 32.0 * n_u);
+  const uint32_t* d_table = u32(d_regs.get());
+  hipLaunchKernelGGL(interpolate_regs_kernel, dim3((n_regs + R0H_CHECK_SIZE + 63) / 64), dim3(64), 0, ctx->stream, u32(st.tail.get()) + st.tail_at.coeff_u, u32(d_eval),
+                     u32(st.points.get()), d_table, d_table + n_taps, n_regs, n_taps, u32(d_regs.get()) + table.size());
+  return launch_ok("interpolate_regs_kernel");
 }
 
-// step 6, second part: the same fix list, its indices from the host and its values from deep_head_kernel
-static const char* subtract_interpolants_device(r0h_proof& st, r0h_buf* combos, uint32_t n_combos) {
+// step 5: every tap opened at z * omega^-back and CHECK at z^4; coeff_u into the seal and the transcript
+static const char* evaluate_at_z(r0h_proof& st) {
   r0h_ctx* ctx = st.ctx;
-  const uint32_t n_taps = (uint32_t)st.circ->taps.size(), n_regs = (uint32_t)st.circ->regs.size();
-  std::vector<uint32_t> head_len(n_combos + 1, 0);
-  for (const Reg& reg : st.circ->regs) {
-    R0H_REQUIRE(reg.size <= 64, "prove_segment: register with more than 64 taps");
-    if (reg.size > head_len[reg.combo]) head_len[reg.combo] = reg.size;
+  const r0h_circuit* circ = st.circ;
+  profile_phase(ctx, "evaluate_at_z");
+  // (a register's taps are a run of the blob's: never none.  Step 6 keeps a combo's head in 64 slots.)
+  for (const Reg& reg : circ->regs) R0H_REQUIRE(reg.size >= 1 && reg.size <= 64, "prove_segment: register with more than 64 taps");
+  Challenge z;
+  R0H_TRY(draw_ext(st, st.tail_at.z, z));
+  R0H_TRY(deep_points(st, z));
+  const uint32_t n_taps = (uint32_t)circ->taps.size(), n_u = n_taps + R0H_CHECK_SIZE;  // CHECK's columns stand behind the taps, as a fourth group
+  std::vector<uint32_t> which(n_u), pt(n_u);  // request k: column which[k] of its group at point pt[k] of the table
+  for (uint32_t t = 0; t < n_taps; t++) { which[t] = circ->taps[t].offset; pt[t] = st.point_of_back[circ->taps[t].back]; }
+  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) { which[n_taps + i] = i; pt[n_taps + i] = st.n_points - 1; }
+  std::vector<Fp4> xs;  // on the host a request carries its point
+  if (!z.dev)
+    for (uint32_t p : pt) xs.push_back(st.points_host[p]);
+  DevBuf d_eval;
+  R0H_TRY(d_eval.alloc(ctx, (size_t)n_u * 16));
+  for (int g = 0; g < 4; g++) {
+    const uint32_t b = circ->group_tap_begin[g], e = g < 3 ? circ->group_tap_begin[g + 1] : n_u;
+    if (e == b) continue;
+    r0h_buf view = buf_view(d_eval.get(), (size_t)b * 16, (size_t)(e - b) * 16);
+    if (z.dev) R0H_TRY(evaluate_any_points(ctx, st.group(g).coeffs.get(), st.po2, which.data() + b, pt.data() + b, e - b, u32(st.points.get()), st.n_points, &view, true));
+    else R0H_TRY(evaluate_any(ctx, st.group(g).coeffs.get(), st.po2, which.data() + b, (const uint32_t*)(xs.data() + b), e - b, &view, true));
   }
-  head_len[n_combos] = 1;
-  R0H_REQUIRE(((size_t)(n_combos + 1) << st.po2) * 4 < ((size_t)1 << 32), "prove_segment: combos buffer exceeds 32-bit word indexing");
-  // the running order of the mix: a power per register, then one per CHECK column
-  std::vector<uint32_t> fix, begin(1, 0u), terms;
+  if (z.dev) {
+    R0H_TRY(interpolate_device(st, d_eval.get(), pt));
+    return commit_words(st, st.tail.get(), st.tail_at.coeff_u, 4 * (size_t)n_u, st.tail_at.coeff_u);
+  }
+  R0H_TRY(interpolate_host(st, d_eval.get(), xs));
+  st.io.write((const uint32_t*)st.coeff_u.data(), 4 * (size_t)n_u);
+  st.io.commit_elems((const uint32_t*)st.coeff_u.data(), 4 * (size_t)n_u);
+  return nullptr;
+}
+
+// step 6, second part: subtract the interpolants from the mixed combos -- only the first few coefficients of each combo change
+// The fix list is (word index, value) pairs, four to an entry; entry e is coefficient i of combo k's head, in the order of (k, i).  The
+// indices are the host's in both forms; the two routines below fill in the values and leave the list at the start of `d_fix`.
+// On the host: the heads summed from coeff_u and the running powers of the mix (a power per register, then one per CHECK column)
+static const char* head_values_host(r0h_proof& st, const Fp4& mixv, const std::vector<uint32_t>& head_len, std::vector<uint32_t>& fix, DevBuf& d_fix) {
+  const uint32_t n_taps = (uint32_t)st.circ->taps.size(), n_combos = (uint32_t)head_len.size() - 1;
+  std::vector<Fp4> head((size_t)(n_combos + 1) * 64, fp4_zero());
+  Fp4 cur = fp4_one();
+  for (const Reg& reg : st.circ->regs) {
+    for (uint32_t i = 0; i < reg.size; i++) {
+      Fp4& h = head[(size_t)reg.combo * 64 + i];
+      h = h + cur * st.coeff_u[reg.first_tap + i];
+    }
+    cur = cur * mixv;
+  }
+  for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) {
+    head[(size_t)n_combos * 64] = head[(size_t)n_combos * 64] + cur * st.coeff_u[n_taps + i];
+    cur = cur * mixv;
+  }
+  size_t e = 0;
+  for (uint32_t k = 0; k <= n_combos; k++)
+    for (uint32_t i = 0; i < head_len[k]; i++, e++)
+      for (uint32_t q = 0; q < 4; q++) fix[2 * (4 * e + q) + 1] = head[(size_t)k * 64 + i].e[q];
+  R0H_TRY(d_fix.alloc(st.ctx, fix.size() * 4));
+  return stage_h2d(st.ctx, d_fix->ptr, fix.data(), fix.size() * 4);
+}
+// On the device: per entry the terms of its sum, (power of the mix, word of coeff_u) in the same running order; deep_head_kernel adds them up
+static const char* head_values_device(r0h_proof& st, const uint32_t* d_mix, const std::vector<uint32_t>& head_len, const std::vector<uint32_t>& fix, DevBuf& d_fix) {
+  r0h_ctx* ctx = st.ctx;
+  const uint32_t n_taps = (uint32_t)st.circ->taps.size(), n_regs = (uint32_t)st.circ->regs.size(), n_combos = (uint32_t)head_len.size() - 1;
+  std::vector<uint32_t> begin(1, 0u), terms;
   for (uint32_t k = 0; k <= n_combos; k++)
     for (uint32_t i = 0; i < head_len[k]; i++) {
-      for (uint32_t q = 0; q < 4; q++) {
-        fix.push_back((uint32_t)((((size_t)k << st.po2) + i) * 4 + q));
-        fix.push_back(0u);  // deep_head_kernel's
-      }
       if (k < n_combos) {
         for (uint32_t r = 0; r < n_regs; r++) {
           const Reg& reg = st.circ->regs[r];
@@ -887,115 +742,178 @@ static const char* subtract_interpolants_device(r0h_proof& st, r0h_buf* combos, 
   std::vector<uint32_t> table(fix);  // [fix pairs][begin][terms], then the powers of the mix
   table.insert(table.end(), begin.begin(), begin.end());
   table.insert(table.end(), terms.begin(), terms.end());
-  DevBuf d_fix;
   R0H_TRY(d_fix.alloc(ctx, (table.size() + 4 * (size_t)n_pw) * 4));
   R0H_TRY(stage_h2d(ctx, d_fix->ptr, table.data(), table.size() * 4));
   uint32_t *d_table = u32(d_fix.get()), *d_pw = d_table + table.size();
-  const uint32_t* tail = u32(st.tail.get());
-  R0H_TRY(ext_powers(ctx, d_pw, tail + st.tail_at.deep_mix, nullptr, n_pw));
-  {
-    KScope ks(ctx, "deep_head_kernel", 32.0 * (double)(terms.size() / 2));
-    hipLaunchKernelGGL(deep_head_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, ctx->stream, d_table, d_pw, tail + st.tail_at.coeff_u, d_table + fix.size(),
-                       d_table + fix.size() + begin.size(), n_entries);
-    R0H_TRY(launch_ok("deep_head_kernel"));
-  }
+  R0H_TRY(ext_powers(ctx, d_pw, d_mix, nullptr, n_pw));
+  KScope ks(ctx, "deep_head_kernel", 32.0 * (double)(terms.size() / 2));
+  hipLaunchKernelGGL(deep_head_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, ctx->stream, d_table, d_pw, u32(st.tail.get()) + st.tail_at.coeff_u, d_table + fix.size(),
+                     d_table + fix.size() + begin.size(), n_entries);
+  return launch_ok("deep_head_kernel");
+}
+static const char* subtract_interpolants(r0h_proof& st, r0h_buf* combos, const Challenge& mix, uint32_t n_combos) {
+  std::vector<uint32_t> head_len(n_combos + 1, 0);  // (at most 64: evaluate_at_z has looked)
+  for (const Reg& reg : st.circ->regs)
+    if (reg.size > head_len[reg.combo]) head_len[reg.combo] = reg.size;
+  head_len[n_combos] = 1;
+  R0H_REQUIRE(((size_t)(n_combos + 1) << st.po2) * 4 < ((size_t)1 << 32), "prove_segment: combos buffer exceeds 32-bit word indexing");
+  std::vector<uint32_t> fix;
+  for (uint32_t k = 0; k <= n_combos; k++)
+    for (uint32_t i = 0; i < head_len[k]; i++)
+      for (uint32_t q = 0; q < 4; q++) {
+        fix.push_back((uint32_t)((((size_t)k << st.po2) + i) * 4 + q));
+        fix.push_back(0u);  // its value
+      }
+  DevBuf d_fix;  // back to the pool once the kernel that reads it is enqueued
+  if (mix.dev) R0H_TRY(head_values_device(st, mix.dev, head_len, fix, d_fix));
+  else R0H_TRY(head_values_host(st, mix.host, head_len, fix, d_fix));
   const uint32_t nf = (uint32_t)(fix.size() / 2);
-  hipLaunchKernelGGL(sub_head_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, u32(combos), d_table, nf);
+  hipLaunchKernelGGL(sub_head_kernel, dim3((nf + 255) / 256), dim3(256), 0, st.ctx->stream, u32(combos), u32(d_fix.get()), nf);
   return launch_ok("sub_head_kernel");
 }
 
-static const char* deep_device(r0h_proof& st) {
+// step 6, third part: every (combo, point) division of the DEEP step as one batch: a launch set per "k-th point of every combo", one
+// read-back of all remainders (upstream divides on the host; round 1 here ran one scan and one host sync per division)
+// A job is (combo, point of the table): a combo by every back of its registers, the last combo -- CHECK's -- by z^4.  On the host the
+// remainders come back and are looked at here; on the device the tail's report word names the first that is not zero (tail_collect).
+static const char* deep_divide(r0h_proof& st, r0h_buf* combos, uint32_t n_combos) {
+  const r0h_circuit* circ = st.circ;
+  std::vector<uint32_t>& job_poly = st.divide_combo;
+  std::vector<uint32_t> job_pt;
+  job_poly.clear();
+  for (uint32_t k = 0; k < n_combos; k++)
+    for (uint32_t b = circ->combo_begin[k]; b < circ->combo_begin[k + 1]; b++) {
+      job_poly.push_back(k);
+      job_pt.push_back(st.point_of_back[circ->combo_backs[b]]);
+    }
+  job_poly.push_back(n_combos);
+  job_pt.push_back(st.n_points - 1);
+  const uint32_t n = 1u << st.po2, n_jobs = (uint32_t)job_poly.size();
+  if (st.iop) return poly_divide_batch_points(st.ctx, combos, n, job_poly.data(), job_pt.data(), n_jobs, u32(st.points.get()), st.n_points, u32(st.tail.get()) + st.tail_at.report);
+  std::vector<uint32_t> points, rem(4 * (size_t)n_jobs);
+  for (uint32_t p : job_pt) points.insert(points.end(), st.points_host[p].e, st.points_host[p].e + 4);
+  R0H_TRY(poly_divide_batch(st.ctx, combos, n, job_poly.data(), points.data(), n_jobs, rem.data()));
+  for (uint32_t j = 0; j < n_jobs; j++)
+    R0H_REQUIRE(!(rem[4 * j] | rem[4 * j + 1] | rem[4 * j + 2] | rem[4 * j + 3]),
+                "prove_segment: DEEP quotient of combo %u has a non-zero remainder (witness violates the taps?)", job_poly[j]);
+  return nullptr;
+}
+
+// step 6: the columns of the four groups mixed into the combos, the interpolants subtracted, the divisions, the sum: the FRI input
+static const char* deep(r0h_proof& st) {
   r0h_ctx* ctx = st.ctx;
   const r0h_circuit* circ = st.circ;
   const uint32_t po2 = st.po2, n = 1u << po2;
   profile_phase(ctx, "mix_combos");
-  uint32_t* tail = u32(st.tail.get());
-  R0H_TRY(r0h_iop_draw_ext(st.iop.get(), st.tail.get(), st.tail_at.deep_mix, 1));
+  Challenge mix;
+  R0H_TRY(draw_ext(st, st.tail_at.deep_mix, mix));
   const uint32_t n_combos = (uint32_t)circ->combo_begin.size() - 1;
-  DevBuf combos;
+  DevBuf combos;  // back to the pool on return: before the first FRI round
   R0H_TRY(combos.alloc(ctx, (size_t)(n_combos + 1) * n * 16));
   R0H_TRY(r0h_buf_zero(ctx, combos.get()));
-  uint32_t first_exp = 0;  // a column's exponent is its position in the running order over the four groups
+  uint32_t first_exp = 0;  // a column is weighed by the mix to its position in the running order over the four groups
+  Fp4 cur = fp4_one();     // (host) mix^first_exp
   for (int g = 0; g < 4; g++) {
     const uint32_t gs = st.group(g).count;
-    std::vector<uint32_t> combo_of(gs, g < 3 ? 0u : n_combos);
+    std::vector<uint32_t> combo_of(gs, g < 3 ? 0u : n_combos);  // CHECK's columns all go into the last combo
     for (const Reg& reg : circ->regs)
       if (reg.group == (uint32_t)g) combo_of[reg.offset] = reg.combo;
-    R0H_TRY(mix_poly_coeffs_dev(ctx, combos.get(), first_exp, tail + st.tail_at.deep_mix, st.group(g).coeffs.get(), combo_of.data(), gs, po2));
+    if (mix.dev) {
+      R0H_TRY(mix_poly_coeffs_dev(ctx, combos.get(), first_exp, mix.dev, st.group(g).coeffs.get(), combo_of.data(), gs, po2));
+    } else {
+      R0H_TRY(r0h_mix_poly_coeffs(ctx, combos.get(), cur.e, mix.host.e, st.group(g).coeffs.get(), combo_of.data(), gs, po2));
+      cur = cur * fp4_pow(mix.host, gs);
+    }
     first_exp += gs;
   }
-  R0H_TRY(bit_reverse_ext(ctx, combos.get(), n_combos + 1, po2));
-  R0H_TRY(subtract_interpolants_device(st, combos.get(), n_combos));
+  R0H_TRY(bit_reverse_ext(ctx, combos.get(), n_combos + 1, po2));  // combos were mixed in bit-reversed order: natural from here on
+  R0H_TRY(subtract_interpolants(st, combos.get(), mix, n_combos));
   profile_phase(ctx, "deep_divide");
-  std::vector<uint32_t> job_pt;
-  st.divide_combo.clear();
-  for (uint32_t k = 0; k <= n_combos; k++) {
-    if (k < n_combos) {
-      for (uint32_t b = circ->combo_begin[k]; b < circ->combo_begin[k + 1]; b++) {
-        st.divide_combo.push_back(k);
-        job_pt.push_back(st.point_of_back[circ->combo_backs[b]]);
-      }
-    } else {
-      st.divide_combo.push_back(k);
-      job_pt.push_back(st.n_points - 1);  // z^4
-    }
-  }
-  R0H_TRY(poly_divide_batch_points(ctx, combos.get(), n, st.divide_combo.data(), job_pt.data(), (uint32_t)job_pt.size(), u32(st.points.get()), st.n_points, tail + st.tail_at.report));
+  R0H_TRY(deep_divide(st, combos.get(), n_combos));
   R0H_TRY(st.fri_coeffs.alloc(ctx, (size_t)n * 16));
   R0H_TRY(r0h_eltwise_sum_extelem(ctx, st.fri_coeffs.get(), combos.get(), n_combos + 1, n));
   return r0h_batch_bit_reverse(ctx, st.fri_coeffs.get(), 4, po2);
 }
 
-static const char* fri_commit_device(r0h_proof& st) {
+// step 7: per round evaluate, commit, draw the fold mix, fold by 16; what is left goes into the seal as it is
+static const char* fri_commit(r0h_proof& st) {
   r0h_ctx* ctx = st.ctx;
+  const TailLayout& at = st.tail_at;
   profile_phase(ctx, "fri_commit");
   const FriSchedule fri((size_t)1 << st.po2);
-  if (!st.iop) R0H_TRY(tail_open(st, false));  // (under r0h_ctx_set_device_finish the generator went up before step 3)
-  const TailLayout& at = st.tail_at;
-  r0h_iop* iop = st.iop.get();
   for (size_t r = 0; r < fri.rounds.size(); r++) {
     const FriRound& fr = fri.rounds[r];
     Round rd{Tree(fr.rows, R0H_FRI_FOLD * 4), DevBuf()};
     R0H_TRY(rd.evaluated.alloc(ctx, fr.domain * 16));
     R0H_TRY(r0h_batch_expand_into_evaluate_ntt(ctx, rd.evaluated.get(), st.fri_coeffs.get(), 4, log2u(fr.degree), 2));
     R0H_TRY(tree_build(ctx, rd.tree, rd.evaluated.get()));
-    const size_t top_words = 8 * rd.tree.mp.top_size;  // nodes [top_size, 2 * top_size)
-    R0H_TRY(copy_words(ctx, st.tail.get(), at.round_top[r], rd.tree.nodes.get(), top_words, top_words));
-    R0H_TRY(r0h_iop_commit(iop, rd.tree.nodes.get(), 8));  // the root is node 1
-    R0H_TRY(r0h_iop_draw_ext(iop, st.tail.get(), at.fold_mix + 4 * r, 1));
+    R0H_TRY(commit_tree(st, rd.tree, st.iop ? at.round_top[r] : 0));
+    Challenge fold_mix;
+    R0H_TRY(draw_ext(st, at.fold_mix + 4 * r, fold_mix));
     DevBuf folded;
     R0H_TRY(folded.alloc(ctx, fr.degree / R0H_FRI_FOLD * 16));
-    R0H_TRY(r0h_fri_fold_buf(ctx, folded.get(), st.fri_coeffs.get(), st.tail.get(), at.fold_mix + 4 * r, (uint32_t)(fr.degree / R0H_FRI_FOLD)));
-    st.fri_coeffs = std::move(folded);
+    const uint32_t n_folded = (uint32_t)(fr.degree / R0H_FRI_FOLD);
+    if (fold_mix.dev) R0H_TRY(r0h_fri_fold_buf(ctx, folded.get(), st.fri_coeffs.get(), st.tail.get(), at.fold_mix + 4 * r, n_folded));
+    else R0H_TRY(r0h_fri_fold(ctx, folded.get(), st.fri_coeffs.get(), fold_mix.host.e, n_folded));
+    st.fri_coeffs = std::move(folded);  // the coefficients it was folded from go back to the pool
     st.rounds.push_back(std::move(rd));
   }
   R0H_TRY(r0h_batch_bit_reverse(ctx, st.fri_coeffs.get(), 4, log2u(fri.final_degree)));
-  R0H_TRY(copy_words(ctx, st.tail.get(), at.final_coeffs, st.fri_coeffs.get(), 0, 4 * fri.final_degree));
+  R0H_TRY(commit_words(st, st.fri_coeffs.get(), 0, 4 * fri.final_degree, at.final_coeffs));
   st.fri_coeffs.reset();
-  return r0h_iop_commit_elems(iop, st.tail.get(), at.final_coeffs, 4 * fri.final_degree);
+  return nullptr;
 }
 
-static const char* queries_device(r0h_proof& st) {
+static std::vector<const Tree*> proof_trees(const r0h_proof& st) {  // in the order of the seal's openings
+  std::vector<const Tree*> trees;
+  for (int g = 0; g < 4; g++) trees.push_back(&st.group(g).tree);
+  for (const Round& rd : st.rounds) trees.push_back(&rd.tree);
+  return trees;
+}
+
+// step 8: the query positions depend only on the transcript state, not on the openings: draw all of them, then open each tree for
+// all queries in one kernel.  On the device both go into the tail, and the top-form trees' verdicts wait for tail_collect; on the host
+// the rows are drawn here and every tree's openings come back in a copy of their own.
+static const char* queries(r0h_proof& st) {
   r0h_ctx* ctx = st.ctx;
   profile_phase(ctx, "queries");
-  const TailLayout& at = st.tail_at;
   const size_t domain = (size_t)R0H_INV_RATE << st.po2;
   const std::vector<const Tree*> trees = proof_trees(st);
   const uint32_t nq = R0H_QUERIES, n_trees = (uint32_t)trees.size();
-  std::vector<uint32_t> rows;
-  for (const Tree* t : trees) rows.push_back((uint32_t)t->mp.rows);
-  R0H_TRY(r0h_iop_draw_queries(st.iop.get(), (uint32_t)domain, rows.data(), n_trees, nq, st.tail.get(), at.idx));
-  uint32_t* tail = u32(st.tail.get());
-  for (uint32_t t = 0; t < n_trees; t++) {
-    const Tree& tr = *trees[t];
-    const uint32_t* d_idx = tail + at.idx + (size_t)t * nq;
-    uint32_t* out = tail + at.opened[t];
-    if (tr.top_levels)
-      R0H_TRY(merkle_open_top(ctx, out, u32(tr.matrix), u32(tr.nodes.get()), tr.top_levels, d_idx, nq, (uint32_t)tr.mp.rows, (uint32_t)tr.mp.cols,
-                              out + (size_t)nq * tr.mp.opening_words()));
-    else
-      R0H_TRY(merkle_open(ctx, out, u32(tr.matrix), u32(tr.nodes.get()), d_idx, nq, (uint32_t)tr.mp.rows, (uint32_t)tr.mp.cols));
+  if (st.iop) {
+    const TailLayout& at = st.tail_at;
+    uint32_t* tail = u32(st.tail.get());
+    std::vector<uint32_t> rows;
+    for (const Tree* t : trees) rows.push_back((uint32_t)t->mp.rows);
+    R0H_TRY(r0h_iop_draw_queries(st.iop.get(), (uint32_t)domain, rows.data(), n_trees, nq, st.tail.get(), at.idx));
+    for (uint32_t t = 0; t < n_trees; t++) R0H_TRY(open_tree(ctx, *trees[t], tail + at.idx + (size_t)t * nq, nq, tail + at.opened[t]));
+    return nullptr;
   }
+  std::vector<uint32_t> idx((size_t)n_trees * nq);
+  for (uint32_t q = 0; q < nq; q++) {
+    size_t pos = st.io.rng.bits(log2u(domain)) % domain;
+    for (uint32_t t = 0; t < n_trees; t++) {
+      if (t >= 4) pos = pos % trees[t]->mp.rows;
+      idx[(size_t)t * nq + q] = (uint32_t)pos;
+    }
+  }
+  DevBuf d_idx;
+  R0H_TRY(d_idx.alloc(ctx, idx.size() * 4));
+  R0H_TRY(stage_h2d(ctx, d_idx->ptr, idx.data(), idx.size() * 4));
+  std::vector<std::vector<uint32_t>> opened(n_trees);
+  for (uint32_t t = 0; t < n_trees; t++) {
+    DevBuf packed;  // back to the pool behind the read-back
+    opened[t].resize(opened_words(*trees[t], nq));
+    R0H_TRY(packed.alloc(ctx, opened[t].size() * 4));
+    R0H_TRY(open_tree(ctx, *trees[t], u32(d_idx.get()) + (size_t)t * nq, nq, u32(packed.get())));
+    R0H_TRY(r0h_buf_d2h(ctx, packed.get(), 0, opened[t].data(), opened[t].size() * 4));
+    if (trees[t]->top_levels) R0H_TRY(merkle_open_top_verdict("r0h_proof_finish", opened[t].data() + opened[t].size() - 2, idx.data() + (size_t)t * nq));
+  }
+  for (uint32_t q = 0; q < nq; q++)
+    for (uint32_t t = 0; t < n_trees; t++) {
+      const size_t w = trees[t]->mp.opening_words();
+      st.io.write(opened[t].data() + (size_t)q * w, w);
+    }
   return nullptr;
 }
 
@@ -1047,23 +965,34 @@ static const char* require_finishable(const r0h_proof& st, const char* caller) {
               hashfn_name(st.ctx->hashfn));
   return nullptr;
 }
-// r0h_ctx_set_device_finish: steps 3-8 enqueued on the proof's stream, the end of the last phase marked behind them.  Nothing here
-// waits for the stream (the witness checker does, where it is on): the host generator is not touched after the hand-over.
+// Steps 3-8 of DESIGN.md 2, each under its own phase marks, and between them the hand-over of the transcript where the context asks
+// for one: before step 3 with the tail's head (r0h_ctx_set_device_finish; whatever it says goes, since what is handed over stays so),
+// before step 7 with the tail alone (r0h_ctx_set_device_transcript), earlier still by r0h_proof_late_device, or never.  Behind the
+// hand-over nothing waits for the stream (but the witness checker, where it is on) and the host generator is not touched again.
+static const char* proof_steps(r0h_proof& st, const r0h_buf* accum) {
+  const r0h_ctx* ctx = st.ctx;
+  R0H_REQUIRE(ctx->device_finish || !st.late_device,
+              "r0h_proof_finish: the late public inputs went to the device generator (r0h_proof_late_device) and r0h_ctx_set_device_finish is off now");
+  if (ctx->device_finish && !st.iop) R0H_TRY(tail_open(st, true));
+  R0H_TRY(commit_accum(st, accum));
+  R0H_TRY(commit_check(st));
+  R0H_TRY(evaluate_at_z(st));
+  R0H_TRY(deep(st));
+  if (ctx->device_transcript && !st.iop) R0H_TRY(tail_open(st, false));
+  R0H_TRY(fri_commit(st));
+  R0H_TRY(queries(st));
+  return nullptr;
+}
+// r0h_ctx_set_device_finish: the steps enqueued on the proof's stream, the end of the last phase marked behind them ...
 static const char* proof_finish_enqueue(r0h_proof& st, const r0h_buf* accum) {
   R0H_TRY(require_finishable(st, "r0h_proof_finish"));
   R0H_REQUIRE(!st.enqueued, "r0h_proof_finish_enqueue: the proof has been enqueued already");
-  if (!st.late_device) R0H_TRY(tail_open(st, true));  // (r0h_proof_late_device has handed the generator over already)
-  R0H_TRY(commit_accum_device(st, accum));
-  R0H_TRY(commit_check_device(st));
-  R0H_TRY(evaluate_at_z_device(st));
-  R0H_TRY(deep_device(st));
-  R0H_TRY(fri_commit_device(st));
-  R0H_TRY(queries_device(st));
+  R0H_TRY(proof_steps(st, accum));
   profile_end(st.ctx);
   st.enqueued = true;
   return nullptr;
 }
-// the read-back (one wait), the host's verdicts, the seal; then the profile closes (a second wait, of a stream that has drained)
+// ... then the read-back (one wait), the host's verdicts, the seal, and the profile closes (a second wait, of a stream that has drained)
 static const char* proof_finish_collect(r0h_proof& st, std::vector<uint32_t>& seal) {
   R0H_REQUIRE(st.enqueued, "r0h_proof_finish_collect: the proof has not been enqueued (r0h_proof_finish_enqueue comes first)");
   st.enqueued = false;  // the stream has drained once the read-back returns, whatever it brings
@@ -1073,26 +1002,16 @@ static const char* proof_finish_collect(r0h_proof& st, std::vector<uint32_t>& se
   return nullptr;
 }
 
-// steps 3-8 of DESIGN.md 2, each under its own phase marks; the seal is the transcript's written words
+// The seal is the transcript's written words.  Under r0h_ctx_set_device_finish the two halves above, one after the other (the last
+// phase ends before the read-back); otherwise the same steps, the tail brought home if there is one, and the profile closed.
 static const char* proof_finish(r0h_proof& st, const r0h_buf* accum, std::vector<uint32_t>& seal) {
   R0H_TRY(require_finishable(st, "r0h_proof_finish"));
-  if (st.ctx->device_finish) {  // every step on the device generator: enqueue, then the one read-back and the profile's close
+  if (st.ctx->device_finish) {
     R0H_TRY(proof_finish_enqueue(st, accum));
     return proof_finish_collect(st, seal);
   }
-  R0H_REQUIRE(!st.late_device, "r0h_proof_finish: the late public inputs went to the device generator (r0h_proof_late_device) and r0h_ctx_set_device_finish is off now");
-  R0H_TRY(commit_accum(st, accum));
-  R0H_TRY(commit_check(st));
-  R0H_TRY(evaluate_at_z(st));
-  R0H_TRY(deep(st));
-  if (st.ctx->device_transcript) {  // the same two steps with the generator on the device: one wait instead of 2 R + 5
-    R0H_TRY(fri_commit_device(st));
-    R0H_TRY(queries_device(st));
-    R0H_TRY(tail_collect(st));
-  } else {
-    R0H_TRY(fri_commit(st));
-    R0H_TRY(queries(st));
-  }
+  R0H_TRY(proof_steps(st, accum));
+  if (st.iop) R0H_TRY(tail_collect(st));
   R0H_TRY(profile_close(st.ctx));
   seal.swap(st.io.proof);
   return nullptr;

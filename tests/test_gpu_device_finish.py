@@ -272,6 +272,33 @@ def test_proof_finish_waits_four_times_less_than_with_the_device_transcript_alon
     h.close()
 
 
+@pytest.mark.parametrize("name,po2", [("tiny", 9), ("small", 13)])
+@pytest.mark.parametrize("suite", SUITES)
+def test_both_switches_on_is_the_device_finish(bench, suite, name, po2):
+    """r0h_ctx_set_device_transcript and r0h_ctx_set_device_finish together: the transcript is handed over once, before step 3 (whatever
+    the first switch says), so the seal is the host's and r0h_proof_finish waits for the read-back and the profile's close, twice.  A
+    context of its own, as in the test above: nothing near a wrap of the staging ring."""
+    want = bench.host_seal(suite, name, po2)
+    h = r0.Hal(0)
+    h.set_hashfn(suite)
+    gc = h.load_circuit(bench.blob[name], None if name == "tiny" else entry.code_object_path(name))
+    code, data, glob = h.witgen(gc, po2, 1)
+    cc = h.code_commit(gc, po2)
+    h.set_device_transcript(True)
+    h.set_device_finish(True)
+    proof, mix = h.proof_begin(gc, po2, cc, data, glob)
+    accum = h.accum(gc, po2, code, data, mix)
+    h.sync()
+    before = h.blocking_waits()
+    got = h.proof_finish(proof, accum)
+    waits = h.blocking_waits() - before
+    print("blocking waits of proof_finish with both switches on, %s at 2^%d under %s: %d" % (name, po2, suite, waits))
+    assert np.array_equal(got, want)
+    assert waits == 2
+    accum.free(), cc.free(), code.free(), data.free(), gc.free()
+    h.close()
+
+
 # ---- 7. enqueue / collect
 def test_one_thread_keeps_two_contexts_in_flight(bench):
     """begin A, begin B, enqueue A, enqueue B: neither context's count of blocking waits moves across the enqueues (fresh contexts, so
