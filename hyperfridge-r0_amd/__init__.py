@@ -79,6 +79,16 @@ _SIGNATURES = {
     "r0h_scatter": [_vp, _vp, _vp, _vp, _vp, _u32],
     "r0h_fri_fold": [_vp, _vp, _vp, _vp, _u32],
     "r0h_fri_fold_buf": [_vp, _vp, _vp, _vp, _sz, _u32],
+    "r0h_ext_powers_buf": [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _u32],
+    "r0h_batch_evaluate_any_points": [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _sz, _u32, _vp],
+    "r0h_mix_poly_coeffs_mixbuf": [_vp, _vp, _u32, _vp, _sz, _vp, _vp, _u32, _u32],
+    "r0h_poly_divide_batch": [_vp, _vp, _u32, _vp, _vp, _u32, _vp],
+    "r0h_poly_divide_batch_points": [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _sz, _u32, _vp, _sz],
+    "r0h_deep_points_buf": [_vp, _vp, _vp, _sz, _vp, _u32],
+    "r0h_poly_interpolate_host": [_vp, _vp, _u32, _vp],
+    "r0h_poly_interpolate_regs": [_vp, _vp, _vp, _vp, _sz, _u32, _vp, _vp, _u32, _u32],
+    "r0h_deep_subtract_heads": [_vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _sz, _vp, _vp, _sz],
+    "r0h_eval_check_mixbuf": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "r0h_iop_new": [_vp, _pp],
     "r0h_iop_free": [_vp],
     "r0h_iop_set_state": [_vp, _vp, _sz],
@@ -487,6 +497,15 @@ class CodeCommit:
             self.free()
         except Exception:
             pass
+
+
+def poly_interpolate_host(xs, ys):
+    """coefficients, low to high, of the polynomial through the extension points (xs[4i ..), ys[4i ..)) (pure host; needs no GPU)"""
+    (x, px), (y, py) = _u32arr(xs), _u32arr(ys)
+    assert x.size == y.size and x.size % 4 == 0
+    out = np.zeros(x.size, dtype=np.uint32)
+    _check(lib().r0h_poly_interpolate_host(px, py, x.size // 4, out.ctypes.data_as(_vp)))
+    return out
 
 
 def emit_eval_check_source(blob):
@@ -1694,6 +1713,66 @@ class Hal:
     def fri_fold_buf(self, out, inp, mix_buf, mix_word_offset, n_out):
         """fri_fold with the mix read from four words of a device buffer (r0h_fri_fold_buf)"""
         _check(lib().r0h_fri_fold_buf(self.ctx, out.handle, inp.handle, mix_buf.handle, mix_word_offset, n_out))
+
+    # ---- the device-challenge forms of steps 4-6: a challenge or a table is (Buf, word offset), index arrays are host arrays
+    def ext_powers_buf(self, out, out_word_offset, base_buf, base_word_offset, n, exps_buf=None, exps_word_offset=0):
+        """out[out_word_offset + 4k ..) = base^(exps[k], or k without a table) for k < n (r0h_ext_powers_buf)"""
+        _check(lib().r0h_ext_powers_buf(self.ctx, out.handle, out_word_offset, base_buf.handle, base_word_offset,
+                                        exps_buf.handle if exps_buf is not None else None, exps_word_offset, n))
+
+    def batch_evaluate_any_points(self, coeffs, po2, which, pt_idx, points_buf, points_word_offset, n_points, out):
+        w, pw = _u32arr(which)
+        i, pi = _u32arr(pt_idx)
+        assert i.size == w.size
+        _check(lib().r0h_batch_evaluate_any_points(self.ctx, coeffs.handle, po2, pw, pi, w.size, points_buf.handle, points_word_offset, n_points, out.handle))
+
+    def mix_poly_coeffs_mixbuf(self, combos, first_exp, mix_buf, mix_word_offset, inp, combo_of, po2):
+        co, pco = _u32arr(combo_of)
+        _check(lib().r0h_mix_poly_coeffs_mixbuf(self.ctx, combos.handle, first_exp, mix_buf.handle, mix_word_offset, inp.handle, pco, co.size, po2))
+
+    def poly_divide_batch(self, polys, n, poly_idx, points):
+        """job j divides polynomial poly_idx[j] of `polys` in place by (x - points[4j ..)) -> the remainders, 4 words per job in the order given"""
+        pi, ppi = _u32arr(poly_idx)
+        pt, ppt = _u32arr(points)
+        assert pt.size == 4 * pi.size
+        rem = np.zeros(4 * pi.size, dtype=np.uint32)
+        _check(lib().r0h_poly_divide_batch(self.ctx, polys.handle, n, ppi, ppt, pi.size, rem.ctypes.data_as(_vp)))
+        return rem
+
+    def poly_divide_batch_points(self, polys, n, poly_idx, pt_idx, points_buf, points_word_offset, n_points, report_buf, report_word_offset):
+        pi, ppi = _u32arr(poly_idx)
+        pt, ppt = _u32arr(pt_idx)
+        assert pt.size == pi.size
+        _check(lib().r0h_poly_divide_batch_points(self.ctx, polys.handle, n, ppi, ppt, pi.size, points_buf.handle, points_word_offset, n_points,
+                                                  report_buf.handle, report_word_offset))
+
+    def deep_points_buf(self, points_out, z_buf, z_word_offset, wpow):
+        w, pw = _u32arr(wpow)
+        _check(lib().r0h_deep_points_buf(self.ctx, points_out.handle, z_buf.handle, z_word_offset, pw, w.size))
+
+    def poly_interpolate_regs(self, coeff_u_out, eval_u, points_buf, points_word_offset, n_points, tap_pt, regs):
+        """regs: (first tap, taps) per register; the tables hold len(tap_pt) + 16 elements (r0h_poly_interpolate_regs)"""
+        t, pt = _u32arr(tap_pt)
+        r, pr = _u32arr(np.asarray(regs, dtype=np.uint32).reshape(-1, 2))
+        _check(lib().r0h_poly_interpolate_regs(self.ctx, coeff_u_out.handle, eval_u.handle, points_buf.handle, points_word_offset, n_points, pt, pr,
+                                               r.shape[0], t.size))
+
+    def deep_subtract_heads(self, combos, po2, n_combos, regs, n_taps, coeff_u, mix, coeff_u_word_offset=0, mix_word_offset=0):
+        """regs: (combo, first tap, taps) per register.  coeff_u and mix: both host words, or both Bufs (r0h_deep_subtract_heads)"""
+        r, pr = _u32arr(np.asarray(regs, dtype=np.uint32).reshape(-1, 3))
+        if isinstance(coeff_u, Buf) and isinstance(mix, Buf):
+            args = (None, coeff_u.handle, coeff_u_word_offset, None, mix.handle, mix_word_offset)
+        else:
+            (cu, pcu), (m, pm) = _u32arr(coeff_u), _u32arr(mix)
+            assert cu.size == 4 * (n_taps + CHECK_SIZE) and m.size == 4
+            args = (pcu, None, 0, pm, None, 0)
+        _check(lib().r0h_deep_subtract_heads(self.ctx, combos.handle, po2, n_combos, pr, r.shape[0], n_taps, *args))
+
+    def eval_check_mixbuf(self, circuit, po2, eval_accum, eval_code, eval_data, glob, mix, poly_mix_buf, poly_mix_word_offset, check):
+        g, pg = _u32arr(glob)
+        m, pm = _u32arr(mix)
+        _check(lib().r0h_eval_check_mixbuf(self.ctx, circuit.handle, po2, eval_accum.handle, eval_code.handle, eval_data.handle, pg, pm,
+                                           poly_mix_buf.handle, poly_mix_word_offset, check.handle))
 
     def iop(self):
         """a fresh transcript generator of this context's hash suite on the device (r0h_iop_new)"""

@@ -376,6 +376,13 @@ const char* eval_check_dev(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, con
 }  // namespace r0h
 extern "C" {
 
+const char* r0h_eval_check_mixbuf(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code, const r0h_buf* eval_data,
+                                  const uint32_t* global, const uint32_t* mix, const r0h_buf* poly_mix_buf, size_t poly_mix_word_offset, r0h_buf* check) {
+  R0H_REQUIRE(poly_mix_buf, "r0h_eval_check_mixbuf: NULL argument");
+  R0H_TRY(require_words_in("r0h_eval_check_mixbuf", "poly_mix", poly_mix_buf, poly_mix_word_offset, 4));
+  return r0h::eval_check_dev(ctx, c, po2, eval_accum, eval_code, eval_data, global, mix, u32(poly_mix_buf) + poly_mix_word_offset, check);
+}
+
 const char* r0h_check_witness(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* accum, const r0h_buf* code, const r0h_buf* data,
                               const uint32_t* global, const uint32_t* mix, r0h_violation* out, size_t capacity, size_t* n_out) {
   R0H_GUARD_BEGIN

@@ -510,4 +510,28 @@ const char* r0h_fri_fold_buf(r0h_ctx* ctx, r0h_buf* out, const r0h_buf* in, cons
   return launch_ok("fri_fold_buf_kernel");
 }
 
+// ---- the device-challenge forms of steps 4-6 (internal.hpp) on their own: every challenge or table is (buffer, word offset)
+const char* r0h_ext_powers_buf(r0h_ctx* ctx, r0h_buf* out, size_t out_word_offset, const r0h_buf* base_buf, size_t base_word_offset, const r0h_buf* exps_buf,
+                               size_t exps_word_offset, uint32_t n) {
+  R0H_REQUIRE(ctx && out && base_buf, "r0h_ext_powers_buf: NULL argument");
+  R0H_TRY(require_words_in("r0h_ext_powers_buf", "output", out, out_word_offset, 4 * (size_t)n));
+  R0H_TRY(require_words_in("r0h_ext_powers_buf", "base", base_buf, base_word_offset, 4));
+  if (exps_buf) R0H_TRY(require_words_in("r0h_ext_powers_buf", "exponent table", exps_buf, exps_word_offset, n));
+  return ext_powers(ctx, u32(out) + out_word_offset, u32(base_buf) + base_word_offset, exps_buf ? u32(exps_buf) + exps_word_offset : nullptr, n);
+}
+
+const char* r0h_batch_evaluate_any_points(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which, const uint32_t* pt_idx, uint32_t n_eval,
+                                          const r0h_buf* points_buf, size_t points_word_offset, uint32_t n_points, r0h_buf* out) {
+  R0H_REQUIRE(ctx && coeffs && out && points_buf && (n_eval == 0 || (which && pt_idx)), "r0h_batch_evaluate_any_points: NULL argument");
+  R0H_TRY(require_words_in("r0h_batch_evaluate_any_points", "point table", points_buf, points_word_offset, 4 * (size_t)n_points));
+  return evaluate_any_points(ctx, coeffs, po2, which, pt_idx, n_eval, u32(points_buf) + points_word_offset, n_points, out, false);
+}
+
+const char* r0h_mix_poly_coeffs_mixbuf(r0h_ctx* ctx, r0h_buf* combos, uint32_t first_exp, const r0h_buf* mix_buf, size_t mix_word_offset, const r0h_buf* input,
+                                       const uint32_t* combo_of, uint32_t input_count, uint32_t po2) {
+  R0H_REQUIRE(ctx && combos && input && mix_buf, "r0h_mix_poly_coeffs_mixbuf: NULL argument");
+  R0H_TRY(require_words_in("r0h_mix_poly_coeffs_mixbuf", "mix", mix_buf, mix_word_offset, 4));
+  return mix_poly_coeffs_dev(ctx, combos, first_exp, u32(mix_buf) + mix_word_offset, input, combo_of, input_count, po2);
+}
+
 }  // extern "C"

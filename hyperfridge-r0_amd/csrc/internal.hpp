@@ -164,6 +164,13 @@ struct r0h_buf {
 
 namespace r0h {
 inline uint32_t* u32(const r0h_buf* b) { return (uint32_t*)b->ptr; }
+// the refusal shared by the entry points that name device words as (buffer, word offset), r0h_fri_fold_buf's wording
+inline const char* require_words_in(const char* caller, const char* what, const r0h_buf* b, size_t word_offset, size_t n_words) {
+  const size_t have = b->bytes / 4;
+  R0H_REQUIRE(word_offset <= have && n_words <= have - word_offset, "%s: the %s at words [%zu, +%zu) ends beyond a buffer of %zu words", caller, what, word_offset, n_words,
+              have);
+  return nullptr;
+}
 // RAII bracket around the launches of one kernel family; no-op unless r0h_kernel_timing(ctx, 1) was called
 struct KScope {
   r0h_ctx* ctx;
@@ -238,6 +245,11 @@ const char* evaluate_any(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, cons
 //   mix_poly_coeffs_dev       r0h_mix_poly_coeffs whose column c is weighed by mix^(first_exp + c), mix read from four device words
 //   poly_divide_batch_points  poly_divide_batch whose job j divides by (x - point pt_idx[j]): the job table's w, w^E, w^chunk are filled on the
 //                             device, and d_report (one device word) becomes 0, or 1 + the first job, in the order given, whose remainder is not zero
+// Each is callable on its own through the C ABI, its device words named as (buffer, word offset) (include/r0hip.h, next to r0h_fri_fold_buf):
+//   ext_powers -> r0h_ext_powers_buf                 evaluate_any_points -> r0h_batch_evaluate_any_points (natural-order coefficients)
+//   eval_check_dev -> r0h_eval_check_mixbuf (without the late words)      mix_poly_coeffs_dev -> r0h_mix_poly_coeffs_mixbuf
+//   poly_divide_batch -> r0h_poly_divide_batch       poly_divide_batch_points -> r0h_poly_divide_batch_points
+// and so are the small kernels of steps 5 and 6 in prover.hip: r0h_deep_points_buf, r0h_poly_interpolate_regs, r0h_deep_subtract_heads.
 const char* ext_powers(r0h_ctx* ctx, uint32_t* d_out, const uint32_t* d_base, const uint32_t* d_exps, uint32_t n);
 const char* eval_check_dev(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum, const r0h_buf* eval_code, const r0h_buf* eval_data,
                            const uint32_t* global, const uint32_t* mix, const uint32_t* d_poly_mix, r0h_buf* check, const uint32_t* d_late = nullptr,

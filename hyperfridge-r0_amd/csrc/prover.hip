@@ -604,6 +604,13 @@ static const char* commit_check(r0h_proof& st) {
 // Steps 5 and 6 always run in the same form: the transcript is handed over before step 3, before step 7 or not at all, never between
 // them.  So step 6 finds the point table, and coeff_u, where step 5 left them -- on the host, or on the device and in the tail.
 //
+// deep_points_kernel over plain tables (the sequencer's, and r0h_deep_points_buf's): n_backs + 1 points to d_pts from z at d_z
+static const char* deep_points_table(r0h_ctx* ctx, uint32_t* d_pts, const uint32_t* d_z, uint32_t* d_wpow, const uint32_t* wpow, uint32_t n_backs) {
+  R0H_TRY(stage_h2d(ctx, d_wpow, wpow, (size_t)n_backs * 4));  // the kernel's: omega^-back, host-known, n_backs words
+  KScope ks(ctx, "deep_points_kernel", 16.0 * (n_backs + 1));
+  hipLaunchKernelGGL(deep_points_kernel, dim3((n_backs + 1 + 63) / 64), dim3(64), 0, ctx->stream, d_pts, d_z, d_wpow, n_backs);
+  return launch_ok("deep_points_kernel");
+}
 // the point table: a point per distinct back of the circuit's taps (the blob format admits backs below 64), then z^4
 static const char* deep_points(r0h_proof& st, const Challenge& z) {
   r0h_ctx* ctx = st.ctx;
@@ -623,10 +630,7 @@ static const char* deep_points(r0h_proof& st, const Challenge& z) {
   }
   R0H_TRY(st.points.alloc(ctx, (size_t)(4 * st.n_points + n_backs) * 4));
   uint32_t* pts = u32(st.points.get());
-  R0H_TRY(stage_h2d(ctx, pts + 4 * st.n_points, wpow.data(), wpow.size() * 4));
-  KScope ks(ctx, "deep_points_kernel", 16.0 * st.n_points);
-  hipLaunchKernelGGL(deep_points_kernel, dim3((st.n_points + 63) / 64), dim3(64), 0, ctx->stream, pts, z.dev, pts + 4 * st.n_points, n_backs);
-  return launch_ok("deep_points_kernel");
+  return deep_points_table(ctx, pts, z.dev, pts + 4 * st.n_points, wpow.data(), n_backs);
 }
 // step 5's middle on the host: the evaluations read back, every register's interpolant through its openings by poly_interpolate
 static const char* interpolate_host(r0h_proof& st, const r0h_buf* d_eval, const std::vector<Fp4>& xs) {
@@ -638,25 +642,31 @@ static const char* interpolate_host(r0h_proof& st, const r0h_buf* d_eval, const 
   for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) st.coeff_u[n_taps + i] = eval_u[n_taps + i];
   return nullptr;
 }
-// and on the device: interpolate_regs_kernel writes coeff_u into its place in the tail
-static const char* interpolate_device(r0h_proof& st, const r0h_buf* d_eval, const std::vector<uint32_t>& pt) {
-  r0h_ctx* ctx = st.ctx;
-  const uint32_t n_u = (uint32_t)pt.size(), n_taps = n_u - R0H_CHECK_SIZE, n_regs = (uint32_t)st.circ->regs.size();
+// and on the device: interpolate_regs_kernel writes coeff_u (n_taps + R0H_CHECK_SIZE elements) from the evaluations d_eval.  Tap t is opened
+// at point tap_pt[t] of the table d_points; register r is the taps [regs[2r], +regs[2r + 1]), one to 64 of them, no two registers sharing a tap.
+static const char* interpolate_regs(r0h_ctx* ctx, uint32_t* d_coeff_u, const uint32_t* d_eval, const uint32_t* d_points, const uint32_t* tap_pt, const uint32_t* regs,
+                                    uint32_t n_regs, uint32_t n_taps) {
   // the registers' table: [point of every tap][per register: first tap, taps, first work slot], then the work slots (taps + 1 a register)
-  std::vector<uint32_t> table(pt.begin(), pt.begin() + n_taps);
+  std::vector<uint32_t> table(tap_pt, tap_pt + n_taps);
   uint32_t work_slots = 0;
-  for (const Reg& reg : st.circ->regs) {
-    table.insert(table.end(), {reg.first_tap, reg.size, work_slots});
-    work_slots += reg.size + 1;
+  for (uint32_t r = 0; r < n_regs; r++) {
+    table.insert(table.end(), {regs[2 * r], regs[2 * r + 1], work_slots});
+    work_slots += regs[2 * r + 1] + 1;
   }
   DevBuf d_regs;
   R0H_TRY(d_regs.alloc(ctx, (table.size() + 4 * (size_t)work_slots) * 4));
   R0H_TRY(stage_h2d(ctx, d_regs->ptr, table.data(), table.size() * 4));
-  KScope ks(ctx, "interpolate_regs_kernel", 32.0 * n_u);
+  KScope ks(ctx, "interpolate_regs_kernel", 32.0 * (n_taps + R0H_CHECK_SIZE));
   const uint32_t* d_table = u32(d_regs.get());
-  hipLaunchKernelGGL(interpolate_regs_kernel, dim3((n_regs + R0H_CHECK_SIZE + 63) / 64), dim3(64), 0, ctx->stream, u32(st.tail.get()) + st.tail_at.coeff_u, u32(d_eval),
-                     u32(st.points.get()), d_table, d_table + n_taps, n_regs, n_taps, u32(d_regs.get()) + table.size());
+  hipLaunchKernelGGL(interpolate_regs_kernel, dim3((n_regs + R0H_CHECK_SIZE + 63) / 64), dim3(64), 0, ctx->stream, d_coeff_u, d_eval, d_points, d_table, d_table + n_taps, n_regs,
+                     n_taps, u32(d_regs.get()) + table.size());
   return launch_ok("interpolate_regs_kernel");
+}
+static const char* interpolate_device(r0h_proof& st, const r0h_buf* d_eval, const std::vector<uint32_t>& pt) {
+  const uint32_t n_taps = (uint32_t)pt.size() - R0H_CHECK_SIZE;
+  std::vector<uint32_t> regs;
+  for (const Reg& reg : st.circ->regs) regs.insert(regs.end(), {reg.first_tap, reg.size});
+  return interpolate_regs(st.ctx, u32(st.tail.get()) + st.tail_at.coeff_u, u32(d_eval), u32(st.points.get()), pt.data(), regs.data(), (uint32_t)st.circ->regs.size(), n_taps);
 }
 
 // step 5: every tap opened at z * omega^-back and CHECK at z^4; coeff_u into the seal and the transcript
@@ -699,40 +709,41 @@ static const char* evaluate_at_z(r0h_proof& st) {
 // The fix list is (word index, value) pairs, four to an entry; entry e is coefficient i of combo k's head, in the order of (k, i).  The
 // indices are the host's in both forms; the two routines below fill in the values and leave the list at the start of `d_fix`.
 // On the host: the heads summed from coeff_u and the running powers of the mix (a power per register, then one per CHECK column)
-static const char* head_values_host(r0h_proof& st, const Fp4& mixv, const std::vector<uint32_t>& head_len, std::vector<uint32_t>& fix, DevBuf& d_fix) {
-  const uint32_t n_taps = (uint32_t)st.circ->taps.size(), n_combos = (uint32_t)head_len.size() - 1;
+// Both take the registers as (combo, first tap, taps) triples and coeff_u as n_taps + R0H_CHECK_SIZE elements, CHECK's openings last.
+static const char* head_values_host(r0h_ctx* ctx, const uint32_t* regs, uint32_t n_regs, uint32_t n_taps, const Fp4* coeff_u, const Fp4& mixv,
+                                    const std::vector<uint32_t>& head_len, std::vector<uint32_t>& fix, DevBuf& d_fix) {
+  const uint32_t n_combos = (uint32_t)head_len.size() - 1;
   std::vector<Fp4> head((size_t)(n_combos + 1) * 64, fp4_zero());
   Fp4 cur = fp4_one();
-  for (const Reg& reg : st.circ->regs) {
-    for (uint32_t i = 0; i < reg.size; i++) {
-      Fp4& h = head[(size_t)reg.combo * 64 + i];
-      h = h + cur * st.coeff_u[reg.first_tap + i];
+  for (uint32_t r = 0; r < n_regs; r++) {
+    const uint32_t combo = regs[3 * r], first_tap = regs[3 * r + 1], size = regs[3 * r + 2];
+    for (uint32_t i = 0; i < size; i++) {
+      Fp4& h = head[(size_t)combo * 64 + i];
+      h = h + cur * coeff_u[first_tap + i];
     }
     cur = cur * mixv;
   }
   for (uint32_t i = 0; i < R0H_CHECK_SIZE; i++) {
-    head[(size_t)n_combos * 64] = head[(size_t)n_combos * 64] + cur * st.coeff_u[n_taps + i];
+    head[(size_t)n_combos * 64] = head[(size_t)n_combos * 64] + cur * coeff_u[n_taps + i];
     cur = cur * mixv;
   }
   size_t e = 0;
   for (uint32_t k = 0; k <= n_combos; k++)
     for (uint32_t i = 0; i < head_len[k]; i++, e++)
       for (uint32_t q = 0; q < 4; q++) fix[2 * (4 * e + q) + 1] = head[(size_t)k * 64 + i].e[q];
-  R0H_TRY(d_fix.alloc(st.ctx, fix.size() * 4));
-  return stage_h2d(st.ctx, d_fix->ptr, fix.data(), fix.size() * 4);
+  R0H_TRY(d_fix.alloc(ctx, fix.size() * 4));
+  return stage_h2d(ctx, d_fix->ptr, fix.data(), fix.size() * 4);
 }
 // On the device: per entry the terms of its sum, (power of the mix, word of coeff_u) in the same running order; deep_head_kernel adds them up
-static const char* head_values_device(r0h_proof& st, const uint32_t* d_mix, const std::vector<uint32_t>& head_len, const std::vector<uint32_t>& fix, DevBuf& d_fix) {
-  r0h_ctx* ctx = st.ctx;
-  const uint32_t n_taps = (uint32_t)st.circ->taps.size(), n_regs = (uint32_t)st.circ->regs.size(), n_combos = (uint32_t)head_len.size() - 1;
+static const char* head_values_device(r0h_ctx* ctx, const uint32_t* regs, uint32_t n_regs, uint32_t n_taps, const uint32_t* d_coeff_u, const uint32_t* d_mix,
+                                      const std::vector<uint32_t>& head_len, const std::vector<uint32_t>& fix, DevBuf& d_fix) {
+  const uint32_t n_combos = (uint32_t)head_len.size() - 1;
   std::vector<uint32_t> begin(1, 0u), terms;
   for (uint32_t k = 0; k <= n_combos; k++)
     for (uint32_t i = 0; i < head_len[k]; i++) {
       if (k < n_combos) {
-        for (uint32_t r = 0; r < n_regs; r++) {
-          const Reg& reg = st.circ->regs[r];
-          if (reg.combo == k && reg.size > i) terms.insert(terms.end(), {r, reg.first_tap + i});
-        }
+        for (uint32_t r = 0; r < n_regs; r++)
+          if (regs[3 * r] == k && regs[3 * r + 2] > i) terms.insert(terms.end(), {r, regs[3 * r + 1] + i});
       } else {
         for (uint32_t j = 0; j < R0H_CHECK_SIZE; j++) terms.insert(terms.end(), {n_regs + j, n_taps + j});
       }
@@ -747,29 +758,38 @@ static const char* head_values_device(r0h_proof& st, const uint32_t* d_mix, cons
   uint32_t *d_table = u32(d_fix.get()), *d_pw = d_table + table.size();
   R0H_TRY(ext_powers(ctx, d_pw, d_mix, nullptr, n_pw));
   KScope ks(ctx, "deep_head_kernel", 32.0 * (double)(terms.size() / 2));
-  hipLaunchKernelGGL(deep_head_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, ctx->stream, d_table, d_pw, u32(st.tail.get()) + st.tail_at.coeff_u, d_table + fix.size(),
+  hipLaunchKernelGGL(deep_head_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, ctx->stream, d_table, d_pw, d_coeff_u, d_table + fix.size(),
                      d_table + fix.size() + begin.size(), n_entries);
   return launch_ok("deep_head_kernel");
 }
-static const char* subtract_interpolants(r0h_proof& st, r0h_buf* combos, const Challenge& mix, uint32_t n_combos) {
+// `combos`: n_combos + 1 polynomials of 2^po2 extension coefficients, the last one CHECK's.  The device form (d_mix) reads coeff_u from
+// d_coeff_u, the host form from coeff_u_host.
+static const char* subtract_heads(r0h_ctx* ctx, r0h_buf* combos, uint32_t po2, uint32_t n_combos, const uint32_t* regs, uint32_t n_regs, uint32_t n_taps, const Fp4* coeff_u_host,
+                                  const uint32_t* d_coeff_u, const Fp4* mix_host, const uint32_t* d_mix) {
   std::vector<uint32_t> head_len(n_combos + 1, 0);  // (at most 64: evaluate_at_z has looked)
-  for (const Reg& reg : st.circ->regs)
-    if (reg.size > head_len[reg.combo]) head_len[reg.combo] = reg.size;
+  for (uint32_t r = 0; r < n_regs; r++)
+    if (regs[3 * r + 2] > head_len[regs[3 * r]]) head_len[regs[3 * r]] = regs[3 * r + 2];
   head_len[n_combos] = 1;
-  R0H_REQUIRE(((size_t)(n_combos + 1) << st.po2) * 4 < ((size_t)1 << 32), "prove_segment: combos buffer exceeds 32-bit word indexing");
+  R0H_REQUIRE(((size_t)(n_combos + 1) << po2) * 4 < ((size_t)1 << 32), "prove_segment: combos buffer exceeds 32-bit word indexing");
   std::vector<uint32_t> fix;
   for (uint32_t k = 0; k <= n_combos; k++)
     for (uint32_t i = 0; i < head_len[k]; i++)
       for (uint32_t q = 0; q < 4; q++) {
-        fix.push_back((uint32_t)((((size_t)k << st.po2) + i) * 4 + q));
+        fix.push_back((uint32_t)((((size_t)k << po2) + i) * 4 + q));
         fix.push_back(0u);  // its value
       }
   DevBuf d_fix;  // back to the pool once the kernel that reads it is enqueued
-  if (mix.dev) R0H_TRY(head_values_device(st, mix.dev, head_len, fix, d_fix));
-  else R0H_TRY(head_values_host(st, mix.host, head_len, fix, d_fix));
+  if (d_mix) R0H_TRY(head_values_device(ctx, regs, n_regs, n_taps, d_coeff_u, d_mix, head_len, fix, d_fix));
+  else R0H_TRY(head_values_host(ctx, regs, n_regs, n_taps, coeff_u_host, *mix_host, head_len, fix, d_fix));
   const uint32_t nf = (uint32_t)(fix.size() / 2);
-  hipLaunchKernelGGL(sub_head_kernel, dim3((nf + 255) / 256), dim3(256), 0, st.ctx->stream, u32(combos), u32(d_fix.get()), nf);
+  hipLaunchKernelGGL(sub_head_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, u32(combos), u32(d_fix.get()), nf);
   return launch_ok("sub_head_kernel");
+}
+static const char* subtract_interpolants(r0h_proof& st, r0h_buf* combos, const Challenge& mix, uint32_t n_combos) {
+  std::vector<uint32_t> regs;
+  for (const Reg& reg : st.circ->regs) regs.insert(regs.end(), {reg.combo, reg.first_tap, reg.size});
+  return subtract_heads(st.ctx, combos, st.po2, n_combos, regs.data(), (uint32_t)st.circ->regs.size(), (uint32_t)st.circ->taps.size(), st.coeff_u.data(),
+                        mix.dev ? u32(st.tail.get()) + st.tail_at.coeff_u : nullptr, &mix.host, mix.dev);
 }
 
 // step 6, third part: every (combo, point) division of the DEEP step as one batch: a launch set per "k-th point of every combo", one
@@ -1274,6 +1294,86 @@ const char* r0h_code_root(r0h_ctx* ctx, const r0h_buf* code, uint32_t count, uin
   R0H_TRY(code_commit(ctx, cc, code));
   memcpy(root_out, cc.top.root(), 32);
   return nullptr;
+  R0H_GUARD_END
+}
+
+// ---- the small kernels of steps 5 and 6 on their own (deep_points_table, interpolate_regs, subtract_heads): what the sequencer's inputs
+// are by construction -- register sizes, taps inside their tables -- is looked at here, before anything is launched
+const char* r0h_deep_points_buf(r0h_ctx* ctx, r0h_buf* points_out, const r0h_buf* z_buf, size_t z_word_offset, const uint32_t* wpow, uint32_t n_backs) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(n_backs >= 1 && n_backs <= 64, "r0h_deep_points_buf: %u backs (1 to 64)", n_backs);
+  R0H_REQUIRE(ctx && points_out && z_buf && wpow, "r0h_deep_points_buf: NULL argument");
+  for (uint32_t i = 0; i < n_backs; i++) R0H_REQUIRE(wpow[i] < P, "r0h_deep_points_buf: wpow[%u] not canonical", i);
+  R0H_TRY(require_words_in("r0h_deep_points_buf", "z", z_buf, z_word_offset, 4));
+  R0H_TRY(require_words_in("r0h_deep_points_buf", "point table", points_out, 0, 4 * (size_t)(n_backs + 1)));
+  DevBuf d_wpow;  // back to the pool once the kernel that reads it is enqueued
+  R0H_TRY(d_wpow.alloc(ctx, (size_t)n_backs * 4));
+  return deep_points_table(ctx, u32(points_out), u32(z_buf) + z_word_offset, u32(d_wpow.get()), wpow, n_backs);
+  R0H_GUARD_END
+}
+
+const char* r0h_poly_interpolate_host(const uint32_t* xs, const uint32_t* ys, uint32_t n, uint32_t* out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(xs && ys && out, "r0h_poly_interpolate_host: NULL argument");
+  R0H_REQUIRE(n >= 1 && n <= 64, "r0h_poly_interpolate_host: %u points (1 to 64)", n);
+  for (size_t k = 0; k < 4 * (size_t)n; k++) R0H_REQUIRE(xs[k] < P && ys[k] < P, "r0h_poly_interpolate_host: point %zu not canonical", k / 4);
+  for (uint32_t i = 0; i < n; i++)
+    for (uint32_t j = 0; j < i; j++) R0H_REQUIRE(memcmp(xs + 4 * i, xs + 4 * j, 16) != 0, "r0h_poly_interpolate_host: points %u and %u are equal", j, i);
+  poly_interpolate((Fp4*)out, (const Fp4*)xs, (const Fp4*)ys, n);
+  return nullptr;
+  R0H_GUARD_END
+}
+
+const char* r0h_poly_interpolate_regs(r0h_ctx* ctx, r0h_buf* coeff_u_out, const r0h_buf* eval_u, const r0h_buf* points_buf, size_t points_word_offset, uint32_t n_points,
+                                      const uint32_t* tap_pt, const uint32_t* regs, uint32_t n_regs, uint32_t n_taps) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && coeff_u_out && eval_u && points_buf && tap_pt && regs, "r0h_poly_interpolate_regs: NULL argument");
+  R0H_REQUIRE(n_regs >= 1 && n_regs <= n_taps && n_taps <= (1u << 24), "r0h_poly_interpolate_regs: %u registers over %u taps", n_regs, n_taps);
+  std::vector<uint32_t> owner(n_taps, 0u);  // 1 + the register a tap belongs to
+  for (uint32_t r = 0; r < n_regs; r++) {
+    const uint32_t first = regs[2 * r], size = regs[2 * r + 1];
+    R0H_REQUIRE(size >= 1 && size <= 64, "r0h_poly_interpolate_regs: register %u has %u taps (1 to 64)", r, size);
+    R0H_REQUIRE(first <= n_taps && size <= n_taps - first, "r0h_poly_interpolate_regs: register %u runs past the %u taps", r, n_taps);
+    for (uint32_t t = first; t < first + size; t++) {
+      R0H_REQUIRE(!owner[t], "r0h_poly_interpolate_regs: registers %u and %u overlap at tap %u", owner[t] - 1, r, t);
+      owner[t] = r + 1;
+    }
+  }
+  for (uint32_t t = 0; t < n_taps; t++) R0H_REQUIRE(tap_pt[t] < n_points, "r0h_poly_interpolate_regs: tap %u names point %u of a table of %u", t, tap_pt[t], n_points);
+  R0H_TRY(require_words_in("r0h_poly_interpolate_regs", "point table", points_buf, points_word_offset, 4 * (size_t)n_points));
+  R0H_TRY(require_words_in("r0h_poly_interpolate_regs", "evaluations", eval_u, 0, 4 * ((size_t)n_taps + R0H_CHECK_SIZE)));
+  R0H_TRY(require_words_in("r0h_poly_interpolate_regs", "interpolants", coeff_u_out, 0, 4 * ((size_t)n_taps + R0H_CHECK_SIZE)));
+  return interpolate_regs(ctx, u32(coeff_u_out), u32(eval_u), u32(points_buf) + points_word_offset, tap_pt, regs, n_regs, n_taps);
+  R0H_GUARD_END
+}
+
+const char* r0h_deep_subtract_heads(r0h_ctx* ctx, r0h_buf* combos, uint32_t po2, uint32_t n_combos, const uint32_t* regs, uint32_t n_regs, uint32_t n_taps,
+                                    const uint32_t* coeff_u_host, const r0h_buf* coeff_u_buf, size_t coeff_u_word_offset, const uint32_t* mix_host, const r0h_buf* mix_buf,
+                                    size_t mix_word_offset) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && combos && (regs || !n_regs), "r0h_deep_subtract_heads: NULL argument");
+  const bool host = coeff_u_host && mix_host && !coeff_u_buf && !mix_buf, dev = !coeff_u_host && !mix_host && coeff_u_buf && mix_buf;
+  R0H_REQUIRE(host || dev, "r0h_deep_subtract_heads: coeff_u and the mix are both host words or both device words");
+  R0H_REQUIRE(po2 <= MAX_DOMAIN_PO2, "r0h_deep_subtract_heads: po2 %u too large", po2);
+  R0H_REQUIRE(n_combos < (1u << 16) && n_taps <= (1u << 24), "r0h_deep_subtract_heads: %u combos over %u taps", n_combos, n_taps);
+  R0H_REQUIRE(((size_t)(n_combos + 1) << po2) * 4 < ((size_t)1 << 32), "r0h_deep_subtract_heads: combos buffer exceeds 32-bit word indexing");
+  R0H_REQUIRE(((size_t)(n_combos + 1) << po2) * 16 <= combos->bytes, "r0h_deep_subtract_heads: %u combos and CHECK's exceed the combos buffer", n_combos);
+  for (uint32_t r = 0; r < n_regs; r++) {
+    const uint32_t combo = regs[3 * r], first = regs[3 * r + 1], size = regs[3 * r + 2];
+    R0H_REQUIRE(combo < n_combos, "r0h_deep_subtract_heads: register %u names combo %u of %u", r, combo, n_combos);
+    R0H_REQUIRE(size >= 1 && size <= 64 && size <= ((uint64_t)1 << po2), "r0h_deep_subtract_heads: register %u has %u taps (1 to 64, and no more than the combo's coefficients)", r, size);
+    R0H_REQUIRE(first <= n_taps && size <= n_taps - first, "r0h_deep_subtract_heads: register %u runs past the %u taps", r, n_taps);
+  }
+  const size_t n_u = (size_t)n_taps + R0H_CHECK_SIZE;
+  if (dev) {
+    R0H_TRY(require_words_in("r0h_deep_subtract_heads", "interpolants", coeff_u_buf, coeff_u_word_offset, 4 * n_u));
+    R0H_TRY(require_words_in("r0h_deep_subtract_heads", "mix", mix_buf, mix_word_offset, 4));
+    return subtract_heads(ctx, combos, po2, n_combos, regs, n_regs, n_taps, nullptr, u32(coeff_u_buf) + coeff_u_word_offset, nullptr, u32(mix_buf) + mix_word_offset);
+  }
+  for (size_t k = 0; k < 4 * n_u; k++) R0H_REQUIRE(coeff_u_host[k] < P, "r0h_deep_subtract_heads: coeff_u word %zu not canonical", k);
+  for (int q = 0; q < 4; q++) R0H_REQUIRE(mix_host[q] < P, "r0h_deep_subtract_heads: mix words must be canonical (< p)");
+  const Fp4 mixv{{mix_host[0], mix_host[1], mix_host[2], mix_host[3]}};
+  return subtract_heads(ctx, combos, po2, n_combos, regs, n_regs, n_taps, (const Fp4*)coeff_u_host, nullptr, &mixv, nullptr);
   R0H_GUARD_END
 }
 

@@ -333,3 +333,23 @@ const char* poly_divide_batch_points(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, c
   return poly_divide_batch_impl(ctx, polys, n, poly_idx, nullptr, pt_idx, d_points, n_points, n_jobs, nullptr, d_report);
 }
 }  // namespace r0h
+
+extern "C" {
+
+const char* r0h_poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* points, uint32_t n_jobs, uint32_t* remainders_out) {
+  R0H_REQUIRE(ctx && polys && (!n_jobs || (poly_idx && points)), "r0h_poly_divide_batch: NULL argument");
+  R0H_REQUIRE(n && (n & (n - 1)) == 0, "r0h_poly_divide_batch: n %u is not a power of two", n);
+  for (size_t k = 0; k < 4 * (size_t)n_jobs; k++) R0H_REQUIRE(points[k] < P, "r0h_poly_divide_batch: the point of job %zu is not canonical (< p)", k / 4);
+  return r0h::poly_divide_batch(ctx, polys, n, poly_idx, points, n_jobs, remainders_out);
+}
+
+const char* r0h_poly_divide_batch_points(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx, const uint32_t* pt_idx, uint32_t n_jobs, const r0h_buf* points_buf,
+                                         size_t points_word_offset, uint32_t n_points, r0h_buf* report_buf, size_t report_word_offset) {
+  R0H_REQUIRE(ctx && polys && points_buf && report_buf && (!n_jobs || (poly_idx && pt_idx)), "r0h_poly_divide_batch_points: NULL argument");
+  R0H_REQUIRE(n && (n & (n - 1)) == 0, "r0h_poly_divide_batch_points: n %u is not a power of two", n);
+  R0H_TRY(require_words_in("r0h_poly_divide_batch_points", "point table", points_buf, points_word_offset, 4 * (size_t)n_points));
+  R0H_TRY(require_words_in("r0h_poly_divide_batch_points", "report word", report_buf, report_word_offset, 1));
+  return r0h::poly_divide_batch_points(ctx, polys, n, poly_idx, pt_idx, n_jobs, u32(points_buf) + points_word_offset, n_points, u32(report_buf) + report_word_offset);
+}
+
+}  // extern "C"

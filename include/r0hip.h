@@ -187,6 +187,56 @@ const char* r0h_prefix_sums(r0h_ctx* ctx, r0h_buf* io, uint32_t n); /* io[i] = s
 /* in-place synthetic division of an extension-coefficient polynomial (AoS, natural order) by (x - z) */
 const char* r0h_poly_divide(r0h_ctx* ctx, r0h_buf* poly, uint32_t n, const uint32_t z[4], uint32_t remainder[4]);
 
+/* ---- The device-challenge forms of steps 4-6 of a proof (what the sequencer runs under r0h_ctx_set_device_finish), callable on their
+ * own.  r0h_fri_fold_buf's conventions: a challenge or a table in device memory is a (buffer, word offset) pair, refused when it would
+ * end beyond the buffer and aligned to a word only; small index arrays are host arrays; no call waits for the stream unless it returns
+ * host words.  Every word is a canonical Montgomery word; extension elements are four words. */
+/* out[out_word_offset + 4k ..) = base^(exps ? exps[k] : k) for k < n; exps_buf may be NULL; x^0 = 1 for every x */
+const char* r0h_ext_powers_buf(r0h_ctx* ctx, r0h_buf* out, size_t out_word_offset, const r0h_buf* base_buf, size_t base_word_offset,
+                               const r0h_buf* exps_buf, size_t exps_word_offset, uint32_t n);
+/* r0h_batch_evaluate_any whose request k is evaluated at point pt_idx_host[k] of a table of n_points points in device memory */
+const char* r0h_batch_evaluate_any_points(r0h_ctx* ctx, const r0h_buf* coeffs, uint32_t po2, const uint32_t* which_host,
+                                          const uint32_t* pt_idx_host, uint32_t n_eval, const r0h_buf* points_buf,
+                                          size_t points_word_offset, uint32_t n_points, r0h_buf* out);
+/* r0h_mix_poly_coeffs whose column c is weighed by mix^(first_exp + c), the mix read from four device words */
+const char* r0h_mix_poly_coeffs_mixbuf(r0h_ctx* ctx, r0h_buf* combos, uint32_t first_exp, const r0h_buf* mix_buf,
+                                       size_t mix_word_offset, const r0h_buf* input, const uint32_t* combo_of_host,
+                                       uint32_t input_count, uint32_t po2);
+/* polys: n-coefficient extension polynomials (AoS, natural order, n a power of two).  Job j divides polynomial poly_idx_host[j] in
+ * place by (x - points_host[4j ..)); jobs on one polynomial are applied in the order given.  remainders_out (4 words per job, in the
+ * order given; may be NULL) is filled by one blocking copy. */
+const char* r0h_poly_divide_batch(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx_host,
+                                  const uint32_t* points_host, uint32_t n_jobs, uint32_t* remainders_out);
+/* The same with job j's point named by its index pt_idx_host[j] in a device table, and no read-back: the word at
+ * report_buf[report_word_offset] becomes 0, or 1 + the first job, in the order given, whose remainder is not zero (0 for no jobs) */
+const char* r0h_poly_divide_batch_points(r0h_ctx* ctx, r0h_buf* polys, uint32_t n, const uint32_t* poly_idx_host,
+                                         const uint32_t* pt_idx_host, uint32_t n_jobs, const r0h_buf* points_buf,
+                                         size_t points_word_offset, uint32_t n_points, r0h_buf* report_buf,
+                                         size_t report_word_offset);
+/* the DEEP point table: points_out[i] = z * wpow_host[i] (base-field words) for i < n_backs, points_out[n_backs] = z^4; 1 <= n_backs <= 64 */
+const char* r0h_deep_points_buf(r0h_ctx* ctx, r0h_buf* points_out, const r0h_buf* z_buf, size_t z_word_offset,
+                                const uint32_t* wpow_host, uint32_t n_backs);
+/* Pure host: the coefficients, low to high, of the polynomial of degree < n through n points (xs[4i ..), ys[4i ..)), 1 <= n <= 64,
+ * the xs distinct */
+const char* r0h_poly_interpolate_host(const uint32_t* xs, const uint32_t* ys, uint32_t n, uint32_t* out);
+/* Every register's interpolant on the device.  eval_u and coeff_u_out hold n_taps + 16 extension elements: tap t was opened at point
+ * tap_pt_host[t] of the table with the value eval_u[t]; register r is the taps [regs_host[2r], +regs_host[2r + 1]) and its interpolant
+ * goes to coeff_u_out at its first tap; the last sixteen elements (CHECK's openings) are copied.  Refused before any launch: a
+ * register of no or of more than 64 taps, registers that overlap or run past n_taps, a tap_pt outside the table.  The points of one
+ * register must be distinct (not looked at: they are device words). */
+const char* r0h_poly_interpolate_regs(r0h_ctx* ctx, r0h_buf* coeff_u_out, const r0h_buf* eval_u, const r0h_buf* points_buf,
+                                      size_t points_word_offset, uint32_t n_points, const uint32_t* tap_pt_host,
+                                      const uint32_t* regs_host, uint32_t n_regs, uint32_t n_taps);
+/* The head fix-up of the DEEP combos: combos holds n_combos + 1 polynomials of 2^po2 extension coefficients (natural order), the
+ * last one CHECK's.  With a running power of the mix per register in the order given, then one per CHECK column, coefficient i of
+ * combo k loses sum over the registers (k, first tap, taps > i) of power * coeff_u[first tap + i]; CHECK's combo loses, at coefficient
+ * 0, the sum over its sixteen columns.  regs_host: (combo, first tap, taps) per register.  coeff_u (n_taps + 16 elements) and the mix
+ * are both host words (the *_host pointers, buffers NULL) or both device words (the *_host pointers NULL). */
+const char* r0h_deep_subtract_heads(r0h_ctx* ctx, r0h_buf* combos, uint32_t po2, uint32_t n_combos, const uint32_t* regs_host,
+                                    uint32_t n_regs, uint32_t n_taps, const uint32_t* coeff_u_host, const r0h_buf* coeff_u_buf,
+                                    size_t coeff_u_word_offset, const uint32_t* mix_host, const r0h_buf* mix_buf,
+                                    size_t mix_word_offset);
+
 /* ---- CircuitHal: circuit blob (format: r0hip_circuit.h), witness generation, accumulation, eval_check ---- */
 /* Pure host: emit the HIP source of the circuit's eval_check kernels (caller frees with r0h_free_error). */
 const char* r0h_circuit_emit_hip(const uint32_t* blob, size_t n_words, char** source_out);
@@ -210,6 +260,12 @@ const char* r0h_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0
 const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum,
                            const r0h_buf* eval_code, const r0h_buf* eval_data, const uint32_t* global_host,
                            const uint32_t* mix_host, const uint32_t poly_mix[4], r0h_buf* check);
+/* r0h_eval_check with poly_mix read from device memory, the four words at poly_mix_buf[poly_mix_word_offset ..): its powers are made
+ * on the device (one of the device-challenge forms listed with r0h_ext_powers_buf) */
+const char* r0h_eval_check_mixbuf(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum,
+                                  const r0h_buf* eval_code, const r0h_buf* eval_data, const uint32_t* global_host,
+                                  const uint32_t* mix_host, const r0h_buf* poly_mix_buf, size_t poly_mix_word_offset,
+                                  r0h_buf* check);
 /* ---- the witness checker: which constraint a witness violates, and where.  Term t of a circuit is the t-th AndEqz of its
  * constraint program once the AndCond gates are flattened into their inner terms -- numbered by the power of poly_mix it is folded
  * with, 0 <= t < r0h_circuit_n_terms -- and its value on row r of a 2^po2-row trace is the AndEqz value times the product of its

@@ -7,6 +7,7 @@ import pytest
 
 import stream_ref as ref
 from field_words import FAMILIES, ONE, P, POINT_KINDS, family, point, rnd
+from stream_shapes import DIVIDE_SIZES, MIX_LAYOUTS
 
 pytestmark = pytest.mark.gpu
 GUARD = 0xA5A5A5A5  # no field word: above p
@@ -142,8 +143,7 @@ def test_evaluate_narrow_tables(hal, orc, po2, kind):
 
 
 # ------------------------------------------------------------------ d. mix_poly_coeffs, eltwise_sum_extelem
-# (combo of each column, combos in the buffer): unsorted with gaps -- combos 1, 3 and 4 come back as they went in; one column; 70 in one
-MIX_LAYOUTS = {"gaps": ([2, 0, 2, 5, 0], 6), "single": ([0], 1), "seventy": ([0] * 70, 1)}
+# the layouts: stream_shapes.MIX_LAYOUTS
 
 
 def _check_mix(hal, orc, init, start, mix, inp, ibuf, combo_of, po2):
@@ -223,9 +223,7 @@ def test_fri_fold_tails_and_corner_mixes(hal, orc, n_out, kind):
 
 
 # ------------------------------------------------------------------ f. poly_divide
-# one element; two; fewer threads than a block; one block of one element per thread; two per thread; one full chunk; two chunks; 256
-# chunks (one per thread of the link kernel); 512 (two per thread)
-DIVIDE_SIZES = [1, 2, 128, 256, 512, 4096, 8192, 1 << 20, 1 << 21]
+# the sizes: stream_shapes.DIVIDE_SIZES
 
 
 @pytest.mark.parametrize("kind,n", [(k, n) for n in DIVIDE_SIZES for k in FAMILIES if n <= 8192 or k != "random"])
