@@ -121,6 +121,26 @@ typedef void (*orc_accum_fn)(const uint32_t* mix, uint32_t* accum, void* user);
 size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
                               const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
                               size_t seal_cap, orc_accum_fn accum_fn, void* user);
+/* A cheating prover, for the tests of the verifiers: the same sequencer telling ONE lie, delta (a Montgomery word, 0 < delta < p)
+ * added in the field to every word the lie covers.  Transcript and Merkle trees of the seal are valid -- everything after the lie is
+ * made from what was committed -- so only the algebraic check that binds the lied-about words can refuse it.
+ *   COMMITTED  a = group (ORC_GROUP_*, CHECK included), b = column: the group's tree is built over, and opened from, a copy of its 4N
+ *              evaluations whose column b lies in every row; coefficients, eval_check, coeff_u, combos and FRI are honest
+ *   FLOWING    a = group (not CHECK), b = column: as COMMITTED, and eval_check reads the lying evaluations too, so CHECK is
+ *              consistent with the lie and the coefficients are not
+ *   COEFF_U    a = word of coeff_u, altered before it is written and committed; the DEEP mix, the subtracted interpolants and the
+ *              quotients (their remainders dropped) follow the lie
+ *   FRI        a = round, b = column 0..63 of that round's matrix, lied about in every row before its tree is built; the folds
+ *              come from the honest coefficients
+ *   FINAL      a = word of the final polynomial, altered after the last fold, before it is written and committed
+ * cheat == NULL or kind NONE is orc_prove_segment_with, word for word.  With a cheat, a non-zero DEEP remainder does not suppress
+ * the seal; 0 is returned for a descriptor that names no word of this proof. */
+#define ORC_GROUP_CHECK 3
+enum { ORC_CHEAT_NONE = 0, ORC_CHEAT_COMMITTED, ORC_CHEAT_FLOWING, ORC_CHEAT_COEFF_U, ORC_CHEAT_FRI, ORC_CHEAT_FINAL };
+typedef struct { uint32_t kind, a, b, delta; } orc_cheat_t;
+size_t orc_prove_segment_cheat(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
+                               const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
+                               size_t seal_cap, orc_accum_fn accum_fn, void* user, const orc_cheat_t* cheat);
 /* 0 = accepted; otherwise a positive error code naming the first failed check. */
 int orc_verify_segment(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, const uint32_t* seal,
                        size_t seal_words);

@@ -71,29 +71,52 @@ static void merkle_prove(merkle_t* m, wiop_t* io, size_t idx) {
 }
 
 /* ------------------------------------------------------------------ poly groups */
-typedef struct { uint32_t* coeffs; uint32_t* evaluated; uint32_t count; merkle_t merkle; } group_t;
-/* coeffs: bit-reversed, already in the shifted variable.  Evaluate on 4N, commit, then put coeffs in natural order. */
-static void group_finish(group_t* g, uint32_t po2) {
-  size_t n = (size_t)1 << po2;
-  g->evaluated = (uint32_t*)malloc((size_t)g->count * n * ORC_INV_RATE * 4);
+typedef struct { uint32_t* coeffs; uint32_t* evaluated; uint32_t* lying; uint32_t count; merkle_t merkle; } group_t;
+
+/* ---- the cheating prover (orc.h orc_cheat_t): every lie is delta added to each word it covers */
+static int cheats(const orc_cheat_t* cheat, uint32_t kind) { return cheat && cheat->kind == kind; }
+/* the descriptor if it lies about a column of group g (3 = CHECK), else NULL */
+static const orc_cheat_t* column_lie(const orc_cheat_t* cheat, uint32_t g) {
+  return (cheats(cheat, ORC_CHEAT_COMMITTED) || cheats(cheat, ORC_CHEAT_FLOWING)) && cheat->a == g ? cheat : NULL;
+}
+/* every row of one column of a [column][row] matrix */
+static void lie_about_column(uint32_t* matrix, size_t rows, uint32_t col, fp_t delta) {
+  for (size_t r = 0; r < rows; r++) matrix[col * rows + r] = fp_add(matrix[col * rows + r], delta);
+}
+
+/* coeffs: bit-reversed, already in the shifted variable.  Evaluate on 4N, commit, then put coeffs in natural order.
+ * lie (NULL = none): the tree is built over, and the openings come from, evaluations whose column lie->b lies in every row: a copy
+ * (COMMITTED: `evaluated`, which eval_check reads, stays honest) or `evaluated` itself (FLOWING).  The coefficients are honest. */
+static void group_finish(group_t* g, uint32_t po2, const orc_cheat_t* lie) {
+  size_t n = (size_t)1 << po2, rows = n * ORC_INV_RATE;
+  g->evaluated = (uint32_t*)malloc((size_t)g->count * rows * 4);
+  g->lying = NULL;
   orc_batch_expand_into_evaluate_ntt(g->evaluated, g->coeffs, g->count, po2, 2);
   orc_batch_bit_reverse(g->coeffs, g->count, po2);
-  merkle_new(&g->merkle, g->evaluated, n * ORC_INV_RATE, g->count);
+  const uint32_t* committed = g->evaluated;
+  if (lie && lie->kind == ORC_CHEAT_FLOWING) lie_about_column(g->evaluated, rows, lie->b, lie->delta);
+  else if (lie) {
+    g->lying = (uint32_t*)malloc((size_t)g->count * rows * 4);
+    memcpy(g->lying, g->evaluated, (size_t)g->count * rows * 4);
+    lie_about_column(g->lying, rows, lie->b, lie->delta);
+    committed = g->lying;
+  }
+  merkle_new(&g->merkle, committed, rows, g->count);
 }
-static void group_from_witness(group_t* g, const uint32_t* wit, uint32_t count, uint32_t po2) {
+static void group_from_witness(group_t* g, const uint32_t* wit, uint32_t count, uint32_t po2, const orc_cheat_t* lie) {
   size_t n = (size_t)1 << po2;
   g->count = count;
   g->coeffs = (uint32_t*)malloc((size_t)count * n * 4);
   memcpy(g->coeffs, wit, (size_t)count * n * 4);
   orc_batch_interpolate_ntt(g->coeffs, count, po2);
   orc_zk_shift(g->coeffs, count, po2);
-  group_finish(g, po2);
+  group_finish(g, po2, lie);
 }
-static void group_free(group_t* g) { free(g->coeffs); free(g->evaluated); free(g->merkle.nodes); }
+static void group_free(group_t* g) { free(g->coeffs); free(g->evaluated); free(g->lying); free(g->merkle.nodes); }
 
 void orc_code_root(const uint32_t* code, uint32_t count, uint32_t po2, uint32_t root[8]) {
   group_t g;
-  group_from_witness(&g, code, count, po2);
+  group_from_witness(&g, code, count, po2, NULL);
   memcpy(root, g.merkle.nodes + 8, 32);
   group_free(&g);
 }
@@ -101,7 +124,12 @@ void orc_code_root(const uint32_t* code, uint32_t count, uint32_t po2, uint32_t 
 /* ------------------------------------------------------------------ FRI prover */
 typedef struct { size_t domain; uint32_t* evaluated; merkle_t merkle; } fri_round_t;
 
-static void fri_prove(wiop_t* io, uint32_t* coeffs /* [4][n] bit-reversed, consumed */, size_t n, group_t** groups, int n_groups) {
+static int fri_rounds(size_t n) { int r = 0; for (; n > ORC_FRI_MIN_DEGREE; n /= ORC_FRI_FOLD) r++; return r; }
+
+/* cheat (NULL = none): FRI lies about column cheat->b of round cheat->a's matrix in every row, the folds made from the honest
+ * coefficients; FINAL about word cheat->a of the final polynomial, once the last fold is made */
+static void fri_prove(wiop_t* io, uint32_t* coeffs /* [4][n] bit-reversed, consumed */, size_t n, group_t** groups, int n_groups,
+                      const orc_cheat_t* cheat) {
   size_t orig_domain = n * ORC_INV_RATE;
   fri_round_t rounds[8];
   int n_rounds = 0;
@@ -110,6 +138,8 @@ static void fri_prove(wiop_t* io, uint32_t* coeffs /* [4][n] bit-reversed, consu
     r->domain = n * ORC_INV_RATE;
     r->evaluated = (uint32_t*)malloc(r->domain * 16);
     orc_batch_expand_into_evaluate_ntt(r->evaluated, coeffs, 4, log2u(n), 2);
+    if (cheats(cheat, ORC_CHEAT_FRI) && cheat->a == (uint32_t)(n_rounds - 1))
+      lie_about_column(r->evaluated, r->domain / ORC_FRI_FOLD, cheat->b, cheat->delta);
     merkle_new(&r->merkle, r->evaluated, r->domain / ORC_FRI_FOLD, ORC_FRI_FOLD * 4);
     merkle_commit(&r->merkle, io);
     fp4_t fold_mix = rng_ext(&io->rng);
@@ -120,6 +150,7 @@ static void fri_prove(wiop_t* io, uint32_t* coeffs /* [4][n] bit-reversed, consu
     n /= ORC_FRI_FOLD;
   }
   orc_batch_bit_reverse(coeffs, 4, log2u(n));
+  if (cheats(cheat, ORC_CHEAT_FINAL)) coeffs[cheat->a] = fp_add(coeffs[cheat->a], cheat->delta);
   wiop_write(io, coeffs, 4 * n);
   uint32_t d[8];
   orc_hash_elem_slice(coeffs, 4 * n, d);
@@ -141,14 +172,40 @@ static void fri_prove(wiop_t* io, uint32_t* coeffs /* [4][n] bit-reversed, consu
 size_t orc_prove_segment(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
                          const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
                          size_t seal_cap) {
-  return orc_prove_segment_with(c, blob, blob_words, po2, code, data, global, seal, seal_cap, NULL, NULL);
+  return orc_prove_segment_cheat(c, blob, blob_words, po2, code, data, global, seal, seal_cap, NULL, NULL, NULL);
 }
 
 /* the same with the ACCUM group the caller's: a circuit without an ACCUM section (tests/tap_circuits.py) has no other source of it */
 size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
                               const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
                               size_t seal_cap, orc_accum_fn accum_fn, void* user) {
+  return orc_prove_segment_cheat(c, blob, blob_words, po2, code, data, global, seal, seal_cap, accum_fn, user, NULL);
+}
+
+/* does the descriptor name a word or a column that a proof of 2^po2 rows has? */
+static int cheat_in_range(const orc_circuit_t* c, uint32_t po2, const orc_cheat_t* cheat) {
   const size_t n = (size_t)1 << po2;
+  if (cheat->delta == 0 || cheat->delta >= ORC_P) return 0;
+  switch (cheat->kind) {
+    case ORC_CHEAT_COMMITTED:
+      return cheat->a <= ORC_GROUP_CHECK && cheat->b < (cheat->a == ORC_GROUP_CHECK ? ORC_CHECK_SIZE : c->group_size[cheat->a]);
+    case ORC_CHEAT_FLOWING: return cheat->a < ORC_GROUP_CHECK && cheat->b < c->group_size[cheat->a];
+    case ORC_CHEAT_COEFF_U: return cheat->a < 4 * (c->n_taps + ORC_CHECK_SIZE);
+    case ORC_CHEAT_FRI: return (int)cheat->a < fri_rounds(n) && cheat->b < ORC_FRI_FOLD * 4;
+    case ORC_CHEAT_FINAL: return cheat->a < 4 * (n >> (4 * fri_rounds(n)));
+    default: return 0;
+  }
+}
+
+/* The sequencer.  cheat: NULL or kind ORC_CHEAT_NONE for the honest prover; otherwise the one lie of orc.h's orc_cheat_t is told
+ * where its kind says, and every commitment, challenge and opening after it is made from what was committed: the seal's transcript
+ * and Merkle paths are valid, its algebra is not. */
+size_t orc_prove_segment_cheat(const orc_circuit_t* c, const uint32_t* blob, size_t blob_words, uint32_t po2,
+                               const uint32_t* code, const uint32_t* data, const uint32_t* global, uint32_t* seal,
+                               size_t seal_cap, orc_accum_fn accum_fn, void* user, const orc_cheat_t* cheat) {
+  const size_t n = (size_t)1 << po2;
+  if (cheat && cheat->kind == ORC_CHEAT_NONE) cheat = NULL;
+  if (cheat && !cheat_in_range(c, po2, cheat)) return 0;
   wiop_t io;
   memset(&io, 0, sizeof io);
   orc_rng_init(&io.rng);
@@ -171,9 +228,9 @@ size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size
   }
 
   group_t grp[3], check;
-  group_from_witness(&grp[ORC_GROUP_CODE], code, c->group_size[ORC_GROUP_CODE], po2);
+  group_from_witness(&grp[ORC_GROUP_CODE], code, c->group_size[ORC_GROUP_CODE], po2, column_lie(cheat, ORC_GROUP_CODE));
   merkle_commit(&grp[ORC_GROUP_CODE].merkle, &io);
-  group_from_witness(&grp[ORC_GROUP_DATA], data, c->group_size[ORC_GROUP_DATA], po2);
+  group_from_witness(&grp[ORC_GROUP_DATA], data, c->group_size[ORC_GROUP_DATA], po2, column_lie(cheat, ORC_GROUP_DATA));
   merkle_commit(&grp[ORC_GROUP_DATA].merkle, &io);
   if (c->n_late) {
     uint32_t d[8];
@@ -187,7 +244,7 @@ size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size
     uint32_t* accum = (uint32_t*)malloc((size_t)c->group_size[ORC_GROUP_ACCUM] * n * 4);
     if (accum_fn) accum_fn(mix, accum, user);
     else orc_accum_public(c, po2, code, data, global, mix, accum);
-    group_from_witness(&grp[ORC_GROUP_ACCUM], accum, c->group_size[ORC_GROUP_ACCUM], po2);
+    group_from_witness(&grp[ORC_GROUP_ACCUM], accum, c->group_size[ORC_GROUP_ACCUM], po2, column_lie(cheat, ORC_GROUP_ACCUM));
     free(accum);
   }
   merkle_commit(&grp[ORC_GROUP_ACCUM].merkle, &io);
@@ -198,7 +255,7 @@ size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size
   check.coeffs = (uint32_t*)malloc(n * ORC_INV_RATE * 16);
   orc_eval_check(c, po2, grp[0].evaluated, grp[1].evaluated, grp[2].evaluated, global, mix, poly_mix.e, check.coeffs);
   orc_batch_interpolate_ntt(check.coeffs, 4, po2 + 2); /* 4 polys of 4N == 16 polys of N, bit-reversed */
-  group_finish(&check, po2);
+  group_finish(&check, po2, column_lie(cheat, ORC_GROUP_CHECK));
   merkle_commit(&check.merkle, &io);
 
   /* DEEP point and the tap evaluations */
@@ -224,6 +281,8 @@ size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size
   fp4_t z4 = fp4_pow(z, 4);
   for (uint32_t i = 0; i < ORC_CHECK_SIZE; i++) { which[c->n_taps + i] = i; st4(all_xs + 4 * (c->n_taps + i), z4); }
   orc_batch_evaluate_any(check.coeffs, po2, which + c->n_taps, all_xs + 4 * c->n_taps, ORC_CHECK_SIZE, coeff_u + 4 * c->n_taps);
+  /* a lying coeff_u word: what follows -- the DEEP mix, the subtracted interpolants, the quotients -- is made from the lie */
+  if (cheats(cheat, ORC_CHEAT_COEFF_U)) coeff_u[cheat->a] = fp_add(coeff_u[cheat->a], cheat->delta);
   wiop_write(&io, coeff_u, 4 * (size_t)n_u);
   {
     uint32_t d[8];
@@ -282,11 +341,12 @@ size_t orc_prove_segment_with(const orc_circuit_t* c, const uint32_t* blob, size
   free(combos); free(all_xs); free(eval_u); free(coeff_u); free(which); free(mix);
 
   group_t* order[4] = {&grp[0], &grp[1], &grp[2], &check};
-  fri_prove(&io, final_coeffs, n, order, 4);
+  fri_prove(&io, final_coeffs, n, order, 4, cheat);
   for (int g = 0; g < 3; g++) group_free(&grp[g]);
   group_free(&check);
 
-  size_t len = ok ? io.n : 0;
+  /* a non-zero DEEP remainder is a witness the honest prover refuses to seal; a cheat keeps the quotient and drops the remainder */
+  size_t len = ok || cheat ? io.n : 0;
   if (seal && len && len <= seal_cap) memcpy(seal, io.w, len * 4);
   free(io.w);
   return len;

@@ -10,6 +10,11 @@ LIB = os.path.join(ROOT, "oracle", "liborc.so")
 P = 2013265921
 _vp, _u32, _u64, _sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t
 ACCUM_FN = ctypes.CFUNCTYPE(None, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _vp)  # orc_accum_fn(mix, accum, user)
+CHEAT_KINDS = {"committed": 1, "flowing": 2, "coeff_u": 3, "fri": 4, "final": 5}  # orc.h ORC_CHEAT_*
+
+
+class Cheat(ctypes.Structure):  # orc_cheat_t
+    _fields_ = [("kind", _u32), ("a", _u32), ("b", _u32), ("delta", _u32)]
 
 
 def _ptr(a):
@@ -42,6 +47,8 @@ class Oracle:
         L.orc_prove_segment.argtypes = [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _sz]
         L.orc_prove_segment_with.restype = _sz
         L.orc_prove_segment_with.argtypes = [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _sz, ACCUM_FN, _vp]
+        L.orc_prove_segment_cheat.restype = _sz
+        L.orc_prove_segment_cheat.argtypes = [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _sz, ACCUM_FN, _vp, ctypes.POINTER(Cheat)]
         L.orc_verify_segment.restype = ctypes.c_int
         L.orc_verify_segment.argtypes = [_vp, _vp, _sz, _vp, _sz]
         L.orc_verify_strerror.restype = ctypes.c_char_p
@@ -278,13 +285,21 @@ class OrcCircuit:
         self.o.L.orc_eval_check(self.h, po2, _ptr(ea), _ptr(ec), _ptr(ed), _ptr(glob), _ptr(mix), _ptr(poly_mix), _ptr(out))
         return out
 
-    def prove(self, po2, code, data, glob, accum=None):
+    def prove(self, po2, code, data, glob, accum=None, cheat=None):
         """accum: None for the circuit's own accumulation (its ACCUM section), or a callable mix -> the ACCUM group's words
-        ([column][row], flat or 2-D), called once the mix is drawn (orc_prove_segment_with); the mix it saw is kept in `last_mix`."""
+        ([column][row], flat or 2-D), called once the mix is drawn (orc_prove_segment_with); the mix it saw is kept in `last_mix`.
+        cheat: None for the honest prover, or (kind, a, b, delta) -- kind a key of CHEAT_KINDS, the indices and the Montgomery word
+        delta as orc.h's orc_cheat_t states them -- for a seal with a valid transcript and valid trees that tells that one lie."""
         seal = np.zeros(1 << 21, np.uint32)
         code, data, glob = u32(code), u32(data), u32(glob)
         self.last_mix = None
-        if accum is None:
+        if cheat is not None:
+            kind, a, b, delta = cheat
+            lie = ctypes.byref(Cheat(CHEAT_KINDS[kind], a, b, delta))
+        if accum is None and cheat is not None:
+            n = self.o.L.orc_prove_segment_cheat(self.h, _ptr(self.blob), self.blob.size, po2, _ptr(code), _ptr(data), _ptr(glob), _ptr(seal), seal.size,
+                                                 ACCUM_FN(), None, lie)
+        elif accum is None:
             n = self.o.L.orc_prove_segment(self.h, _ptr(self.blob), self.blob.size, po2, _ptr(code), _ptr(data), _ptr(glob), _ptr(seal), seal.size)
         else:
             words, failed = self.group_size[0] << po2, []
@@ -300,11 +315,14 @@ class OrcCircuit:
                     failed.append(e)
 
             fn = ACCUM_FN(fill)  # referenced until the call returns
-            n = self.o.L.orc_prove_segment_with(self.h, _ptr(self.blob), self.blob.size, po2, _ptr(code), _ptr(data), _ptr(glob), _ptr(seal), seal.size, fn, None)
+            if cheat is None:
+                n = self.o.L.orc_prove_segment_with(self.h, _ptr(self.blob), self.blob.size, po2, _ptr(code), _ptr(data), _ptr(glob), _ptr(seal), seal.size, fn, None)
+            else:
+                n = self.o.L.orc_prove_segment_cheat(self.h, _ptr(self.blob), self.blob.size, po2, _ptr(code), _ptr(data), _ptr(glob), _ptr(seal), seal.size, fn, None, lie)
             del fn
             if failed:
                 raise failed[0]
-        assert n, "oracle prover failed (non-zero DEEP remainder?)"
+        assert n, "oracle prover failed (non-zero DEEP remainder?)" if cheat is None else "the cheat %r names no word of this proof" % (cheat,)
         return seal[:n].copy()
 
     def verify(self, seal, code_root=None):
