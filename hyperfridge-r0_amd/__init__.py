@@ -238,7 +238,18 @@ _SIGNATURES = {
     "r0h_proof_late_device": [_vp, _vp, _vp],
     "r0h_logup_totals_device": [_vp, _vp, _u32, _vp, _vp, _vp],
     "r0h_accum_public_device": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp],
+    "r0h_accum_mixbuf": [_vp, _vp, _u32, _vp, _vp, _vp, _sz, _vp],
+    "r0h_proof_begin_committed_enqueue": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _pp],
+    "r0h_proof_begin_committed_top_enqueue": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _pp],
+    "r0h_proof_data_root_device": [_vp, _vp, _sz],
+    "r0h_prove_segment_committed_enqueue": [_vp, _vp, _u32, _vp, _vp, _vp, _pp],
+    "r0h_prove_segment_collect": [_vp, _vp, _sz, _c.POINTER(_sz)],
+    "r0h_prove_image_enqueue": [_vp, _vp, _vp, _sz, _vp, _pp],
+    "r0h_prove_image_collect": [_vp, _vp, _sz, _c.POINTER(_sz)],
+    "r0h_prove_image_abort": [_vp],
     "r0h_ctx_set_session_enqueue": [_vp, _c.c_int],
+    "r0h_ctx_set_session_enqueue_begin": [_vp, _c.c_int],
+    "r0h_last_session_phase1": [_vp, _vp],
     "r0h_last_session_phase2": [_vp, _vp],
     "r0h_proof_globals": [_vp, _vp],
     "r0h_code_commit_columns": [_vp, _pp],
@@ -1873,6 +1884,16 @@ class Hal:
         _check(lib().r0h_accum(self.ctx, circuit.handle, po2, code.handle, data.handle, pm, out.handle))
         return out
 
+    def accum_mixbuf(self, circuit, po2, code, data, mix_buf, mix_word_offset=0):
+        """accum with the mix read from device words, n_mix of them at mix_buf[mix_word_offset ..) (r0h_accum_mixbuf): no wait"""
+        out = self.alloc(circuit.group_size[GROUP_ACCUM] << po2)
+        try:
+            _check(lib().r0h_accum_mixbuf(self.ctx, circuit.handle, po2, code.handle if code is not None else None, data.handle, mix_buf.handle, mix_word_offset, out.handle))
+        except R0HipError:
+            out.free()
+            raise
+        return out
+
     def accum_public(self, circuit, po2, code, data, glob, mix):
         """r0h_accum for a circuit whose accumulation reads public inputs (the log-derivative argument of the trace circuit)"""
         n = 1 << po2
@@ -1991,6 +2012,19 @@ class Hal:
         """the trace-circuit sessions begun on this context finish from the calling thread alone: every segment's second phase is
         enqueued on its lane's stream and collected later (r0h_ctx_set_session_enqueue); off by default, same receipts"""
         _check(lib().r0h_ctx_set_session_enqueue(self.ctx, 1 if on else 0))
+
+    def set_session_enqueue_begin(self, on=True):
+        """the trace-circuit sessions begun on this context are driven by the calling thread in both phases: no lane threads, the DATA
+        roots read back once per lane, the image proof enqueued (r0h_ctx_set_session_enqueue_begin; implies set_session_enqueue for
+        the session); off by default, same receipts"""
+        _check(lib().r0h_ctx_set_session_enqueue_begin(self.ctx, 1 if on else 0))
+
+    def last_session_phase1(self):
+        """Of the last trace-circuit session begun on this context (r0h_last_session_phase1): the host threads started for its first
+        phase, the blocking waits its lanes' contexts made in it, its segments and of them the evicted."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().r0h_last_session_phase1(self.ctx, out))
+        return dict(zip(("host_threads", "blocking_waits", "segments", "evictions"), (int(v) for v in out)))
 
     def last_session_phase2(self):
         """Of the last trace-circuit session finished on this context (r0h_last_session_phase2): the host threads its second phase ran
@@ -2184,6 +2218,74 @@ class Hal:
 
     def proof_abort(self, proof):
         _check(lib().r0h_proof_abort(proof))
+
+    @staticmethod
+    def _kept_code(code, what):
+        if not isinstance(code, CodeCommit):
+            raise R0HipError(f"{what}: the columns form commits CODE with a read-back that waits: commit it once with r0h_code_commit_new "
+                             "(Hal.code_commit) and pass the CodeCommit")
+        return code.handle
+
+    def proof_begin_enqueue(self, circuit, po2, code, data, glob, mix_buf=None, top=None):
+        """proof_begin without waiting for the stream: the transcript goes to the device before the DATA commitment
+        (r0h_proof_begin_committed_enqueue, or _top_enqueue with top=(Buf, levels); set_device_finish on, `code` a CodeCommit).  A
+        circuit without late inputs has its mix drawn on the device, into `mix_buf` if one is given.  Returns the proof handle."""
+        cc = Hal._kept_code(code, "proof_begin_enqueue")
+        g, pg = _u32arr(glob)
+        h = _vp()
+        pm = mix_buf.handle if mix_buf is not None else None
+        if top is not None:
+            _check(lib().r0h_proof_begin_committed_top_enqueue(self.ctx, circuit.handle, po2, cc, data.handle, pg, top[0].handle, top[1], pm, ctypes.byref(h)))
+        else:
+            _check(lib().r0h_proof_begin_committed_enqueue(self.ctx, circuit.handle, po2, cc, data.handle, pg, pm, ctypes.byref(h)))
+        return h
+
+    def proof_data_root(self, proof):
+        """the DATA root of a begun proof, eight words (r0h_proof_data_root; waits for a read-back on a proof begun by proof_begin_enqueue)"""
+        out = np.zeros(8, dtype=np.uint32)
+        _check(lib().r0h_proof_data_root(proof, out.ctypes.data_as(_vp)))
+        return out
+
+    def proof_data_root_device(self, proof, buf, word_offset=0):
+        """the same eight words copied to buf[word_offset ..) on the device, no wait (r0h_proof_data_root_device)"""
+        _check(lib().r0h_proof_data_root_device(proof, buf.handle, word_offset))
+
+    def prove_segment_enqueue(self, circuit, po2, code, data, glob):
+        """a whole proof submitted without waiting for the stream (r0h_prove_segment_committed_enqueue; set_device_finish on, `code` a
+        CodeCommit); `data` and `code` stay as they are until prove_segment_collect.  Returns the proof handle."""
+        cc = Hal._kept_code(code, "prove_segment_enqueue")
+        g, pg = _u32arr(glob)
+        h = _vp()
+        _check(lib().r0h_prove_segment_committed_enqueue(self.ctx, circuit.handle, po2, cc, data.handle, pg, ctypes.byref(h)))
+        return h
+
+    def prove_segment_collect(self, proof, seal_capacity_words=1 << 20):
+        """the seal of a proof submitted by prove_segment_enqueue: one read-back (r0h_prove_segment_collect)"""
+        seal = np.empty(seal_capacity_words, dtype=np.uint32)
+        n = _sz(0)
+        _check(lib().r0h_prove_segment_collect(proof, seal.ctypes.data_as(_vp), seal.size, ctypes.byref(n)))
+        return seal[:n.value].copy()
+
+    def prove_image_enqueue(self, image_circuit, elf, challenge):
+        """prove_image submitted without waiting for the stream (r0h_prove_image_enqueue, set_device_finish on); returns the handle
+        prove_image_collect takes"""
+        buf = (ctypes.c_uint8 * len(elf)).from_buffer_copy(elf)
+        ch, pch = _u32arr(challenge)
+        assert ch.size == 16
+        h = _vp()
+        _check(lib().r0h_prove_image_enqueue(self.ctx, image_circuit.handle, buf, len(elf), pch, ctypes.byref(h)))
+        return h
+
+    def prove_image_abort(self, handle):
+        """an enqueued image proof given up: waits for its stream, then releases what it held (r0h_prove_image_abort)"""
+        _check(lib().r0h_prove_image_abort(handle))
+
+    def prove_image_collect(self, handle):
+        """the seal of an enqueued image proof: one read-back (r0h_prove_image_collect)"""
+        seal = np.empty(1 << 18, dtype=np.uint32)
+        n = _sz(0)
+        _check(lib().r0h_prove_image_collect(handle, seal.ctypes.data_as(_vp), seal.size, ctypes.byref(n)))
+        return seal[:n.value].copy()
 
     def sponge_trace_device(self, words, po2, out=None):
         """sponge_trace made on the device (r0h_sponge_trace_device: host chain, sponge_rows_kernel): [65][2^po2] read back.  `out`: a

@@ -47,11 +47,19 @@ __global__ void witgen_derived_kernel(uint32_t* __restrict__ dst, const uint32_t
   if (kind == 2) prod = mul(prod, c[(r - bc) & mask]);
   dst[r] = add(prod, e[(r - be) & mask]);
 }
-__global__ void accum_term_kernel(uint32_t* __restrict__ term, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, Fp4 m0, Fp4 m1) {
+__device__ __forceinline__ void accum_term(uint32_t* __restrict__ term, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const Fp4& m0, const Fp4& m1) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   Fp4 t = m0 + scale(m1, b[r]);
   t.e[0] = add(t.e[0], a[r]);
   *(uint4*)(term + 4 * (size_t)r) = make_uint4(t.e[0], t.e[1], t.e[2], t.e[3]);
+}
+__global__ void accum_term_kernel(uint32_t* __restrict__ term, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, Fp4 m0, Fp4 m1) {
+  accum_term(term, a, b, m0, m1);
+}
+// the same term with the accumulator's two mix elements where a device transcript drew them: eight words at `mix` (r0h_accum_mixbuf)
+__global__ void accum_term_mixbuf_kernel(uint32_t* __restrict__ term, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ mix) {
+  const Fp4 m0{{mix[0], mix[1], mix[2], mix[3]}}, m1{{mix[4], mix[5], mix[6], mix[7]}};
+  accum_term(term, a, b, m0, m1);
 }
 // the checker's table before its kernels run: no row counted, no first row yet
 __global__ void check_table_init_kernel(uint32_t* __restrict__ table, uint32_t n_terms) {
@@ -279,28 +287,44 @@ const char* r0h_witgen_public(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, 
   return witgen_impl(ctx, c, po2, seed, global_in, code, data, nullptr);
 }
 
-const char* r0h_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* mix, r0h_buf* accum) {
+// mix: the circuit's n_mix host words (r0h_accum), or nullptr with d_mix the same words on the device (r0h_accum_mixbuf)
+static const char* accum_impl(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* data, const uint32_t* mix, const uint32_t* d_mix, r0h_buf* accum) {
   R0H_GUARD_BEGIN
-  (void)code;
-  R0H_REQUIRE(ctx && c && data && accum && (mix || c->n_mix == 0), "r0h_accum: NULL argument");
-  R0H_REQUIRE(c->has_column_program, "r0h_accum: this circuit carries no synthetic column program (WITGEN/ACCUM sections)");
-  R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "r0h_accum: po2 %u outside [4, %u]", po2, R0H_MAX_PO2);
+  R0H_REQUIRE(ctx && c && data && accum && (mix || d_mix || c->n_mix == 0), "%s: NULL argument", caller);
+  R0H_REQUIRE(c->has_column_program, "%s: this circuit carries no synthetic column program (WITGEN/ACCUM sections)", caller);
+  R0H_REQUIRE(po2 >= 4 && po2 <= R0H_MAX_PO2, "%s: po2 %u outside [4, %u]", caller, po2, R0H_MAX_PO2);
   const uint32_t n = 1u << po2, threads = n < 256 ? n : 256;
   R0H_REQUIRE(((size_t)c->data_cols.size() << po2) * 4 <= data->bytes && ((size_t)c->group_size[R0H_GROUP_ACCUM] << po2) * 4 <= accum->bytes,
-              "r0h_accum: buffers too small for 2^%u rows", po2);
-  for (uint32_t i = 0; i < c->n_mix; i++) R0H_REQUIRE(mix[i] < P, "r0h_accum: mix[%u] not canonical", i);
-  R0H_REQUIRE(c->logup.accs.empty(), "r0h_accum: this circuit accumulates a log-derivative argument that reads public inputs: use r0h_accum_public");
+              "%s: buffers too small for 2^%u rows", caller, po2);
+  for (uint32_t i = 0; i < c->n_mix && mix; i++) R0H_REQUIRE(mix[i] < P, "%s: mix[%u] not canonical", caller, i);
+  R0H_REQUIRE(c->logup.accs.empty(), "%s: this circuit accumulates a log-derivative argument that reads public inputs: use r0h_accum_public", caller);
   DevBuf term;
   R0H_TRY(term.alloc(ctx, (size_t)n * 16));
   for (uint32_t j = 0; j < c->acc_cols.size(); j++) {
-    Fp4 m0{{mix[8 * j], mix[8 * j + 1], mix[8 * j + 2], mix[8 * j + 3]}}, m1{{mix[8 * j + 4], mix[8 * j + 5], mix[8 * j + 6], mix[8 * j + 7]}};
-    hipLaunchKernelGGL(accum_term_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(term.get()), u32(data) + ((size_t)c->acc_cols[j].a << po2),
-                       u32(data) + ((size_t)c->acc_cols[j].b << po2), m0, m1);
+    const uint32_t *a = u32(data) + ((size_t)c->acc_cols[j].a << po2), *b = u32(data) + ((size_t)c->acc_cols[j].b << po2);
+    if (mix) {
+      Fp4 m0{{mix[8 * j], mix[8 * j + 1], mix[8 * j + 2], mix[8 * j + 3]}}, m1{{mix[8 * j + 4], mix[8 * j + 5], mix[8 * j + 6], mix[8 * j + 7]}};
+      hipLaunchKernelGGL(accum_term_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(term.get()), a, b, m0, m1);
+    } else {
+      hipLaunchKernelGGL(accum_term_mixbuf_kernel, dim3(n / threads), dim3(threads), 0, ctx->stream, u32(term.get()), a, b, d_mix + 8 * (size_t)j);
+    }
     R0H_TRY(r0h_prefix_products(ctx, term.get(), n));
     R0H_TRY(unpack_ext_columns(ctx, u32(accum) + ((size_t)(4 * j) << po2), u32(term.get()), po2));
   }
-  return launch_ok("r0h_accum");
+  return launch_ok(caller);
   R0H_GUARD_END
+}
+const char* r0h_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* mix, r0h_buf* accum) {
+  (void)code;
+  return accum_impl("r0h_accum", ctx, c, po2, data, mix, nullptr, accum);
+}
+// r0h_accum with the mix where a device transcript drew it: the circuit's n_mix words at word `mix_word_offset` of `mix_buf`.  Their
+// canonicity is the producer's business, as for the other device-challenge forms.  Waits for nothing.
+const char* r0h_accum_mixbuf(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const r0h_buf* mix_buf, size_t mix_word_offset, r0h_buf* accum) {
+  (void)code;
+  R0H_REQUIRE(c && mix_buf, "r0h_accum_mixbuf: NULL argument");
+  R0H_TRY(require_words_in("r0h_accum_mixbuf", "mix", mix_buf, mix_word_offset, c->n_mix));
+  return accum_impl("r0h_accum_mixbuf", ctx, c, po2, data, nullptr, u32(mix_buf) + mix_word_offset, accum);
 }
 
 const char* r0h_accum_public(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum) {

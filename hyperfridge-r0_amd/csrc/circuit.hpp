@@ -148,6 +148,9 @@ struct LogupKept {
   DevBuf terms;  // [n_own][2^po2] packed extension elements, inclusive prefix sums
   uint32_t po2 = 0, n_own = 0;
 };
+// r0h_logup_multiplicities without its wait (logup.hip), and what its error word means
+const char* logup_multiplicities_enqueue(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* data, const uint32_t* global, r0h_buf* err_out, size_t err_word_offset);
+const char* logup_multiplicities_verdict(uint32_t err);
 const char* logup_totals_keep(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, uint32_t* global_io, LogupKept* keep);
 const char* logup_accum_kept(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data, const uint32_t* global, const uint32_t* mix, r0h_buf* accum,
                              const LogupKept* kept);

@@ -240,6 +240,11 @@ const char* r0h_ctx_set_session_enqueue(r0h_ctx* ctx, int on) {
   ctx->session_enqueue = on != 0 ? 1 : 0;
   return nullptr;
 }
+const char* r0h_ctx_set_session_enqueue_begin(r0h_ctx* ctx, int on) {
+  R0H_REQUIRE(ctx, "r0h_ctx_set_session_enqueue_begin: ctx is NULL");
+  ctx->session_enqueue_begin = on != 0 ? 1 : 0;
+  return nullptr;
+}
 const char* r0h_ctx_set_merkle_fused_tops(r0h_ctx* ctx, int on) {
   R0H_REQUIRE(ctx, "r0h_ctx_set_merkle_fused_tops: ctx is NULL");
   ctx->merkle_fused_tops = on != 0 ? 1 : 0;

@@ -135,6 +135,8 @@ struct r0h_ctx {
   bool device_transcript = false;  // r0h_ctx_set_device_transcript: fri_commit and queries run on the device generator (prover.hip), one read-back for both
   bool device_finish = false;  // r0h_ctx_set_device_finish: steps 3-8 of proof_finish run on the device generator (prover.hip), one read-back for all of them
   int session_enqueue = -1;    // r0h_ctx_set_session_enqueue: phase 2 of a session from the calling thread alone (session.cpp); -1: as R0H_SESSION_ENQUEUE says
+  int session_enqueue_begin = -1;  // r0h_ctx_set_session_enqueue_begin: phase 1 from the calling thread as well, the image proof enqueued (session.cpp); -1: as R0H_SESSION_ENQUEUE_BEGIN says
+  uint64_t session_phase1[4] = {0, 0, 0, 0};  // r0h_last_session_phase1: host threads started for phase 1, blocking waits in it, segments, evictions
   int merkle_fused_tops = -1;  // r0h_ctx_set_merkle_fused_tops: r0h_merkle_build ends in r0h_hash_fold_top (merkle.hip); -1: as R0H_MERKLE_FUSED_TOPS says
   uint64_t session_phase2[4] = {0, 0, 0, 0};  // r0h_last_session_phase2: host threads, blocking waits, of them ring wraps, of them replays + image proof
   std::atomic<uint64_t> ring_waits{0};      // of blocking_waits: the times stage_h2d waited because the pinned ring had wrapped around
@@ -284,6 +286,9 @@ void ctx_code_commits_drop(r0h_ctx* ctx, const r0h_circuit* c);
 void vm_take_trace(r0h_vm* vm, size_t i, std::vector<r0h_preflight_row>& rows, std::vector<r0h_preflight_bound>& bounds);
 void vm_recycle_trace(r0h_vm* vm, std::vector<r0h_preflight_row>& rows, std::vector<r0h_preflight_bound>& bounds);
 void vm_take_spares(r0h_vm* vm, std::vector<std::vector<r0h_preflight_row>>& rows, std::vector<std::vector<r0h_preflight_bound>>& bounds);
+// trace.hip: r0h_trace_rows_upload without its wait: the caller keeps `rows` and `bounds` as they are until the copies have run
+const char* trace_rows_upload_enqueue(r0h_ctx* ctx, const r0h_preflight_row* rows, size_t n_rows, const r0h_preflight_bound* bounds, size_t n_bounds, uint32_t po2,
+                                      const r0h_trace_segment* segment, r0h_trace_rows** rows_out, uint32_t* globals_out);
 void session_rows_free(r0h_ctx* ctx);  // session.cpp: unpins and frees the row buffers a context kept (ctx teardown, device still alive)
 // the k-th helper context of `ctx` (same device, same Poseidon2 table), created on first use and kept until ctx goes
 const char* ctx_helper(r0h_ctx* ctx, size_t k, r0h_ctx** out);

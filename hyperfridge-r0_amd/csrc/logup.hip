@@ -396,11 +396,9 @@ using namespace r0h;
 
 extern "C" {
 
-// Fill the multiplicity columns of `data` from the lookups its rows make (before DATA is committed).
-const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* data, const uint32_t* global) {
-  R0H_GUARD_BEGIN
-  R0H_REQUIRE(ctx && c && data, "r0h_logup_multiplicities: NULL argument");
-  if (c->logup.tables.empty()) return nullptr;
+// The launches of r0h_logup_multiplicities; `hist` keeps the counters, and behind them the error word (*err_word_out: a device pointer
+// into it) the caller looks at once the stream has run: bit 0 a numerator that is neither 0 nor 1, bit 1 a value that is not in its table.
+static const char* multiplicities_launch(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* data, const uint32_t* global, DevBuf& hist, uint32_t** err_word_out) {
   R0H_REQUIRE(po2 >= 16 && po2 <= R0H_MAX_PO2, "r0h_logup_multiplicities: the tables have 2^16 rows: po2 %u outside [16, %u]", po2, R0H_MAX_PO2);
   R0H_REQUIRE(((size_t)c->group_size[R0H_GROUP_DATA] << po2) * 4 <= data->bytes, "r0h_logup_multiplicities: the DATA buffer is too small for 2^%u rows", po2);
   R0H_REQUIRE(c->logup.tables.size() <= 2, "r0h_logup_multiplicities: at most two tables");
@@ -414,7 +412,7 @@ const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_
   DevBuf dlist;
   R0H_TRY(dlist.alloc(ctx, list.words.size() * 4 + 16));
   R0H_TRY(stage_h2d(ctx, dlist->ptr, list.words.data(), list.words.size() * 4));
-  DevBuf hist;  // [n_tables][65536] counts, then per table the lookups binned and the slots gated off, then the error word
+  // hist: [n_tables][65536] counts, then per table the lookups binned and the slots gated off, then the error word
   const size_t hist_words = (size_t)n_tables * 65536;
   R0H_TRY(hist.alloc(ctx, hist_words * 4 + 32));
   R0H_TRY_HIP(hipMemsetAsync(hist->ptr, 0, hist_words * 4 + 32, ctx->stream));
@@ -434,12 +432,47 @@ const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_
                        (uint32_t)slots[k], n);
     R0H_TRY(launch_ok("logup_mult_kernel"));
   }
-  R0H_TRY_HIP(ctx_wait(ctx));
-  uint32_t err = 0;
-  R0H_TRY(r0h_buf_d2h(ctx, hist.get(), hist_words * 4 + 16, &err, 4));
+  *err_word_out = err_word;
+  return nullptr;
+}
+}  // extern "C"
+namespace r0h {
+const char* logup_multiplicities_verdict(uint32_t err) {
   R0H_REQUIRE(!(err & 1u), "r0h_logup_multiplicities: a lookup's numerator is neither 0 nor 1");
   R0H_REQUIRE(!(err & 2u), "r0h_logup_multiplicities: a row whose numerator is 1 looks up a value that is not in its table");
   return nullptr;
+}
+// r0h_logup_multiplicities without its wait: the error word goes device to device to err_out[err_word_offset], for the caller to read
+// back with whatever else it gathers and hand to logup_multiplicities_verdict (session.cpp: phase 1 from the calling thread)
+const char* logup_multiplicities_enqueue(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* data, const uint32_t* global, r0h_buf* err_out, size_t err_word_offset) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && c && data && err_out, "r0h_logup_multiplicities: NULL argument");
+  R0H_TRY(require_words_in("r0h_logup_multiplicities", "error word", err_out, err_word_offset, 1));
+  if (c->logup.tables.empty()) {
+    R0H_TRY_HIP(hipMemsetAsync(u32(err_out) + err_word_offset, 0, 4, ctx->stream));
+    return nullptr;
+  }
+  DevBuf hist;  // back to the pool behind the copy that reads it
+  uint32_t* err_word = nullptr;
+  R0H_TRY(multiplicities_launch(ctx, c, po2, data, global, hist, &err_word));
+  R0H_TRY_HIP(hipMemcpyAsync(u32(err_out) + err_word_offset, err_word, 4, hipMemcpyDeviceToDevice, ctx->stream));
+  return nullptr;
+  R0H_GUARD_END
+}
+}  // namespace r0h
+extern "C" {
+// Fill the multiplicity columns of `data` from the lookups its rows make (before DATA is committed).
+const char* r0h_logup_multiplicities(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, r0h_buf* data, const uint32_t* global) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && c && data, "r0h_logup_multiplicities: NULL argument");
+  if (c->logup.tables.empty()) return nullptr;
+  DevBuf hist;
+  uint32_t* err_word = nullptr;
+  R0H_TRY(multiplicities_launch(ctx, c, po2, data, global, hist, &err_word));
+  R0H_TRY_HIP(ctx_wait(ctx));
+  uint32_t err = 0;
+  R0H_TRY(r0h_buf_d2h(ctx, hist.get(), (size_t)((char*)err_word - (char*)hist->ptr), &err, 4));
+  return logup_multiplicities_verdict(err);
   R0H_GUARD_END
 }
 

@@ -6,8 +6,9 @@
 //
 // One function per protocol step (proof_begin: steps 1-2; proof_steps: commit_accum, commit_check, evaluate_at_z, deep, fri_commit,
 // queries), one owner per buffer, and one question every step asks: where does the transcript live?  It starts on the host (WriteIop)
-// and may be handed over to the device generator (iop.hip; tail_open) at one of three places: before step 7
-// (r0h_ctx_set_device_transcript), before step 3 (r0h_ctx_set_device_finish) or before the late public inputs (r0h_proof_late_device).
+// and may be handed over to the device generator (iop.hip; tail_open) at one of four places: before step 7
+// (r0h_ctx_set_device_transcript), before step 3 (r0h_ctx_set_device_finish), before the late public inputs (r0h_proof_late_device)
+// or before the DATA commitment (r0h_proof_begin_committed_enqueue: the first half of a proof waits for nothing either).
 // After the hand-over `r0h_proof::iop` is set and the tail block exists, where the steps behind it leave their seal words for one
 // read-back (tail_collect); before it neither does.  draw_ext, commit_tree and commit_words are the transcript in either place, so a
 // step branches only where the two forms are different computations.  With the hand-over before step 3 nothing waits for the stream,
@@ -241,6 +242,10 @@ struct TailLayout {
   // word, 0 or 1 + the first of them that is not canonical; `mix` (below) is the accumulation mix, the device's own
   bool late = false;
   size_t late_report = 0, late_words = 0;
+  // under r0h_proof_begin_committed[_top]_enqueue as well (the hand-over before the DATA commitment): in front of the head the DATA
+  // group's top layer, 8 * top_size words (seal words), and its root, eight words (what r0h_proof_data_root gives once they are home)
+  bool begin = false;
+  size_t data_top = 0, data_root = 0;
   std::vector<size_t> round_top;  // per FRI round: its tree's top layer, 8 * top_size words
   size_t final_coeffs = 0;        // 4 * final_degree words
   size_t idx = 0;                 // the query rows [n_trees][R0H_QUERIES]
@@ -284,7 +289,7 @@ struct r0h_proof {
   r0h::Group g_accum, g_data, g_check;
   std::vector<uint32_t> mix, global;
   size_t seal_globals_at = 0;   // where the seal's opening block of public inputs starts
-  uint32_t data_root[8] = {0};  // the DATA group's Merkle root (what a session's common challenge is derived from)
+  mutable uint32_t data_root[8] = {0};  // the DATA group's Merkle root (what a session's common challenge is derived from)
   bool mix_drawn = false;
   const r0h_buf *check_code = nullptr, *check_data = nullptr;  // r0h_ctx_set_check_witness: the witness columns proof_finish checks (the caller's buffers)
   // what a step of proof_finish leaves for the steps after it
@@ -309,6 +314,15 @@ struct r0h_proof {
   // host at proof_begin: `pre_mix_state` is the generator as it was before, which the device form starts from to draw the same words.
   bool late_device = false;
   std::vector<uint32_t> pre_mix_state;
+  // r0h_proof_begin_committed[_top]_enqueue: DATA was committed on the device generator, so `data_root` is on the host only once it
+  // has been read back (r0h_proof_data_root: eight words, a wait; or the collect)
+  mutable bool data_root_home = true;
+  // ... and a proof whose root was read back that way may be aborted right behind it (a session's eviction in phase 1): r0h_proof_abort
+  // then asks the stream whether anything is still queued on it, and waits only if so
+  mutable bool root_read_back = false;
+  // r0h_prove_segment_committed_enqueue: what the enqueued steps read until r0h_prove_segment_collect -- the ACCUM witness, and for a
+  // log-derivative accumulation the public inputs as device words
+  r0h::DevBuf own_accum, own_globals;
   r0h_proof(r0h_ctx* c, const r0h_circuit* ci, uint32_t p, const r0h_buf* code_columns, const r0h_code_commit* cc)
       : ctx(c), circ(ci), po2(p), io(c->hashfn, &c->p2_host), own_code(ci->group_size[R0H_GROUP_CODE], p), code(cc ? cc : &own_code),
         g_accum(ci->group_size[R0H_GROUP_ACCUM], (size_t)4 << p), g_data(ci->group_size[R0H_GROUP_DATA], (size_t)4 << p),
@@ -381,8 +395,13 @@ static const char* commit_words(r0h_proof& st, const r0h_buf* src, size_t src_wo
 }
 
 static const char* proof_late(r0h_proof& st, const uint32_t* late);
-// steps 1 and 2: the transcript opens, CODE and DATA are committed (DATA through its kept tree top where one is given)
-static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_t* global, const r0h_buf* data_top = nullptr, uint32_t top_levels = 0) {
+static const char* tail_open(r0h_proof& st, bool head, bool late = false, bool begin = false);
+static const char* late_enqueue(r0h_proof& st, const r0h_buf* late, const uint32_t* late_host, r0h_buf* mix_out);
+// steps 1 and 2: the transcript opens, CODE and DATA are committed (DATA through its kept tree top where one is given).  With `enqueue`
+// the generator goes to the device once CODE's top layer -- host words -- is in: DATA is committed there, the mix of a circuit without
+// late inputs is drawn there (into `mix_dev` too, if given), and nothing waits for the stream.
+static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_t* global, const r0h_buf* data_top = nullptr, uint32_t top_levels = 0, bool enqueue = false,
+                               r0h_buf* mix_dev = nullptr) {
   r0h_ctx* ctx = st.ctx;
   const r0h_circuit* circ = st.circ;
   const uint32_t po2 = st.po2;
@@ -424,6 +443,13 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_
   code.top.into(io);  // the same words whoever committed
   profile_phase(ctx, "commit_data");
   R0H_TRY(group_build(ctx, st.g_data, data, po2, data_top, top_levels));
+  if (enqueue) {  // the hand-over before the DATA commitment: top layer and root go device to device, the root into the generator
+    R0H_TRY(tail_open(st, true, true, true));
+    R0H_TRY(commit_tree(st, st.g_data.tree, st.tail_at.data_top));
+    R0H_TRY(copy_words(ctx, st.tail.get(), st.tail_at.data_root, st.g_data.tree.nodes.get(), 8, 8));
+    st.data_root_home = false;
+    return circ->n_late ? nullptr : late_enqueue(st, nullptr, nullptr, mix_dev);
+  }
   R0H_TRY(commit_tree(st, st.g_data.tree, 0));  // (on the host: the hand-over comes later, if at all)
   R0H_TRY(r0h_buf_d2h(ctx, st.g_data.tree.nodes.get(), 32, st.data_root, 32));
   if (!circ->n_late) {
@@ -438,6 +464,7 @@ static const char* proof_begin(r0h_proof& st, const r0h_buf* data, const uint32_
 static const char* proof_late(r0h_proof& st, const uint32_t* late) {
   const uint32_t n_late = st.circ->n_late, n_early = st.circ->n_global - n_late;
   R0H_REQUIRE(!st.mix_drawn, "r0h_proof_late: the accumulation mix has been drawn already");
+  R0H_REQUIRE(!st.iop, "r0h_proof_late: the proof's transcript went to the device before its DATA commitment (r0h_proof_begin_committed_enqueue): r0h_proof_late_device takes the late inputs");
   if (n_late) {
     R0H_REQUIRE(late, "r0h_proof_late: NULL argument");
     for (uint32_t i = 0; i < n_late; i++) R0H_REQUIRE(late[i] < P, "r0h_proof_late: word %u not canonical", i);
@@ -455,7 +482,7 @@ static const char* proof_late(r0h_proof& st, const uint32_t* late) {
 // ------------------------------------------------------------------ the hand-over
 // The tail block laid out and taken from the pool, and the host generator handed over to the device (its state goes up in stream
 // order).  With `head` the block starts with what steps 3-6 add to the seal; every part of it keeps its offset modulo 8 words.
-static const char* tail_open(r0h_proof& st, bool head, bool late = false) {
+static const char* tail_open(r0h_proof& st, bool head, bool late, bool begin) {
   r0h_ctx* ctx = st.ctx;
   const FriSchedule fri((size_t)1 << st.po2);
   TailLayout& at = st.tail_at;
@@ -464,6 +491,13 @@ static const char* tail_open(r0h_proof& st, bool head, bool late = false) {
     size_t w = 0;
     if (head) {
       at.head = true;
+      if (begin) {
+        at.begin = true;
+        at.data_top = w;
+        w += 8 * st.g_data.tree.mp.top_size;
+        at.data_root = w;
+        w += 8;
+      }
       at.accum_top = w;
       w += 8 * st.g_accum.tree.mp.top_size;
       at.check_top = w;
@@ -504,7 +538,7 @@ static const char* tail_open(r0h_proof& st, bool head, bool late = false) {
   }
   R0H_TRY(st.tail.alloc(ctx, at.words * 4));
   r0h_iop* iop = nullptr;
-  if (late && !st.circ->n_late) R0H_TRY(iop_make_words(ctx, st.pre_mix_state.data(), st.pre_mix_state.size(), &iop));  // (the host has drawn the mix: from before it did)
+  if (late && !begin && !st.circ->n_late) R0H_TRY(iop_make_words(ctx, st.pre_mix_state.data(), st.pre_mix_state.size(), &iop));  // (the host has drawn the mix: from before it did)
   else R0H_TRY(iop_make(ctx, st.io.rng, &iop));
   st.iop.reset(iop);
   return nullptr;
@@ -530,26 +564,33 @@ static const char* proof_late_device(r0h_proof& st, const r0h_buf* late, r0h_buf
   R0H_REQUIRE(n_late ? late && late->bytes == (size_t)n_late * 4 : !late || !late->bytes, "r0h_proof_late_device: the late buffer holds %zu words, the circuit has %u late public inputs",
               late ? late->bytes / 4 : (size_t)0, n_late);
   R0H_REQUIRE(!mix_out || mix_out->bytes >= (size_t)n_mix * 4, "r0h_proof_late_device: mix_out holds %zu words, the circuit draws %u", mix_out ? mix_out->bytes / 4 : (size_t)0, n_mix);
+  // A proof begun by r0h_proof_begin_committed_enqueue has handed its generator over already: the late inputs follow DATA's root there.
+  if (st.iop) return late_enqueue(st, late, nullptr, mix_out);
   // a step that fails after the hand-over takes it back: the tail and the device generator go (to the pool, behind what was launched),
   // so the proof is as it was and r0h_proof_late, or this call again, finds it so
-  const char* err = [&]() -> const char* {
-    R0H_TRY(tail_open(st, true, true));
-    const TailLayout& at = st.tail_at;
-    uint32_t* tail = u32(st.tail.get());
-    if (n_late) R0H_TRY(copy_words(ctx, st.tail.get(), at.late_words, late, 0, n_late));
-    hipLaunchKernelGGL(late_check_kernel, dim3(1), dim3(64), 0, ctx->stream, tail + at.late_report, tail + at.late_words, n_late);
-    R0H_TRY(launch_ok("late_check_kernel"));
-    if (n_late) R0H_TRY(r0h_iop_commit_elems(st.iop.get(), st.tail.get(), at.late_words, n_late));
-    R0H_TRY(iop_draw_words(st.iop.get(), st.tail.get(), at.mix, n_mix));
-    if (mix_out && n_mix) R0H_TRY(copy_words(ctx, mix_out, 0, st.tail.get(), at.mix, n_mix));
-    return nullptr;
-  }();
+  const char* err = tail_open(st, true, true);
+  if (!err) err = late_enqueue(st, late, nullptr, mix_out);
   if (err) {
     st.iop.reset();
     st.tail.reset();
     st.tail_at = TailLayout();
-    return err;
   }
+  return err;
+}
+// The late inputs -- device words at `late`, or host words at `late_host` -- into the tail, their canonicity into its report word, the
+// inputs into the device generator, and the mix drawn into the tail (and `mix_out`).  The generator has been handed over.
+static const char* late_enqueue(r0h_proof& st, const r0h_buf* late, const uint32_t* late_host, r0h_buf* mix_out) {
+  r0h_ctx* ctx = st.ctx;
+  const uint32_t n_late = st.circ->n_late, n_mix = st.circ->n_mix;
+  const TailLayout& at = st.tail_at;
+  uint32_t* tail = u32(st.tail.get());
+  if (n_late && late) R0H_TRY(copy_words(ctx, st.tail.get(), at.late_words, late, 0, n_late));
+  else if (n_late) R0H_TRY(stage_h2d(ctx, tail + at.late_words, late_host, (size_t)n_late * 4));
+  hipLaunchKernelGGL(late_check_kernel, dim3(1), dim3(64), 0, ctx->stream, tail + at.late_report, tail + at.late_words, n_late);
+  R0H_TRY(launch_ok("late_check_kernel"));
+  if (n_late) R0H_TRY(r0h_iop_commit_elems(st.iop.get(), st.tail.get(), at.late_words, n_late));
+  R0H_TRY(iop_draw_words(st.iop.get(), st.tail.get(), at.mix, n_mix));
+  if (mix_out && n_mix) R0H_TRY(copy_words(ctx, mix_out, 0, st.tail.get(), at.mix, n_mix));
   st.mix.assign(n_mix, 0u);  // (canonical stand-ins: the kernels read the tail's words)
   st.late_device = true;
   if (!st.mix_drawn) profile_phase(ctx, "accum");
@@ -962,6 +1003,11 @@ static const char* tail_collect(r0h_proof& st) {
     const uint32_t report = host[at.report];
     R0H_REQUIRE(report <= st.divide_combo.size(), "prove_segment: the DEEP report word %u names none of the %zu divisions", report, st.divide_combo.size());
     R0H_REQUIRE(!report, "prove_segment: DEEP quotient of combo %u has a non-zero remainder (witness violates the taps?)", st.divide_combo[report ? report - 1 : 0]);
+    if (at.begin) {  // DATA's top layer follows CODE's in the seal, as the host form writes it at the begin
+      io.write(host.data() + at.data_top, at.data_root - at.data_top);
+      memcpy(st.data_root, host.data() + at.data_root, 32);
+      st.data_root_home = true;
+    }
     io.write(host.data() + at.accum_top, at.check_top - at.accum_top);
     io.write(host.data() + at.check_top, at.coeff_u - at.check_top);
     io.write(host.data() + at.coeff_u, at.report - at.coeff_u);
@@ -1134,6 +1180,89 @@ const char* r0h_proof_begin_committed_top(r0h_ctx* ctx, const r0h_circuit* c, ui
   return proof_begin_impl(ctx, c, po2, nullptr, code, data, global, mix_out, out, top, levels);
 }
 
+// ---- a proof's first half enqueued (include/r0hip.h): the hand-over before the DATA commitment.  What is refused is refused before
+// anything is launched; an error behind that consumes the proof, once what was launched has run (it reads the caller's buffers).
+static const char* require_begin_enqueue(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data,
+                                         const uint32_t* global, const void* out) {
+  R0H_REQUIRE(ctx && c && data && out, "%s: NULL argument", caller);
+  R0H_REQUIRE(code, "%s: no CODE commitment: the columns forms commit CODE with a read-back that waits; commit it once with r0h_code_commit_new", caller);
+  R0H_REQUIRE(global || r0h_circuit_n_global(c) == 0, "%s: global is NULL", caller);
+  R0H_REQUIRE(ctx->device_finish, "%s: the context has r0h_ctx_set_device_finish off: the steps behind the DATA commitment would ask the host generator", caller);
+  return require_po2(caller, po2);
+}
+static const char* proof_begin_enqueue_impl(const char* caller, r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data,
+                                            const uint32_t* global, r0h_buf* mix_out, r0h_proof** out, const r0h_buf* top, uint32_t levels) {
+  R0H_GUARD_BEGIN
+  R0H_TRY(require_begin_enqueue(caller, ctx, c, po2, code, data, global, out));
+  R0H_REQUIRE(!mix_out || mix_out->bytes >= (size_t)c->n_mix * 4, "%s: mix_out holds %zu words, the circuit draws %u", caller, mix_out ? mix_out->bytes / 4 : (size_t)0, c->n_mix);
+  R0H_TRY_HIP(hipSetDevice(ctx->device));
+  std::unique_ptr<r0h_proof> st(new r0h_proof(ctx, c, po2, nullptr, code));
+  const char* err = proof_begin(*st, data, global, top, levels, true, mix_out);
+  if (err) {
+    (void)ctx_wait(ctx);
+    return err;
+  }
+  *out = st.release();
+  return nullptr;
+  R0H_GUARD_END
+}
+const char* r0h_proof_begin_committed_enqueue(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data, const uint32_t* global,
+                                              r0h_buf* mix_out, r0h_proof** out) {
+  return proof_begin_enqueue_impl("r0h_proof_begin_committed_enqueue", ctx, c, po2, code, data, global, mix_out, out, nullptr, 0);
+}
+const char* r0h_proof_begin_committed_top_enqueue(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data, const uint32_t* global,
+                                                  const r0h_buf* top, uint32_t levels, r0h_buf* mix_out, r0h_proof** out) {
+  R0H_REQUIRE(top, "r0h_proof_begin_committed_top_enqueue: NULL argument");
+  R0H_REQUIRE(levels >= 1 && levels <= R0H_MERKLE_TOP_MAX_LEVELS, "r0h_proof_begin_committed_top_enqueue: levels %u outside [1, %u]", levels, (unsigned)R0H_MERKLE_TOP_MAX_LEVELS);
+  return proof_begin_enqueue_impl("r0h_proof_begin_committed_top_enqueue", ctx, c, po2, code, data, global, mix_out, out, top, levels);
+}
+// begin-enqueue + the late inputs (host words: they go up through the pinned ring) + the accumulation from the tail's mix words +
+// r0h_proof_finish_enqueue.  The proof keeps the ACCUM witness (and a log-derivative circuit's public inputs on the device) until the collect.
+const char* r0h_prove_segment_committed_enqueue(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data, const uint32_t* global,
+                                                r0h_proof** out) {
+  R0H_GUARD_BEGIN
+  const char* const caller = "r0h_prove_segment_committed_enqueue";
+  R0H_TRY(require_begin_enqueue(caller, ctx, c, po2, code, data, global, out));
+  R0H_REQUIRE(c->has_column_program, "%s: the circuit has no accumulation program; drive the per-op entry points with your own accum step", caller);
+  const uint32_t n_early = c->n_global - c->n_late;
+  for (uint32_t i = 0; i < c->n_late; i++) R0H_REQUIRE(global[n_early + i] < P, "%s: late public input %u is not canonical", caller, i);
+  R0H_TRY_HIP(hipSetDevice(ctx->device));
+  std::unique_ptr<r0h_proof> st(new r0h_proof(ctx, c, po2, nullptr, code));
+  const char* err = [&]() -> const char* {
+    R0H_TRY(proof_begin(*st, data, global, nullptr, 0, true));
+    if (c->n_late) R0H_TRY(late_enqueue(*st, nullptr, global + n_early, nullptr));
+    R0H_TRY(st->own_accum.alloc(ctx, ((size_t)c->group_size[R0H_GROUP_ACCUM] << po2) * 4));
+    if (c->logup.accs.empty()) {
+      R0H_TRY(r0h_accum_mixbuf(ctx, c, po2, code->witness, data, st->tail.get(), st->tail_at.mix, st->own_accum.get()));
+    } else {
+      R0H_TRY(st->own_globals.alloc(ctx, (size_t)c->n_global * 4));
+      R0H_TRY(stage_h2d(ctx, st->own_globals->ptr, global, (size_t)c->n_global * 4));
+      const r0h_buf mix = buf_view(st->tail.get(), st->tail_at.mix * 4, (size_t)c->n_mix * 4);
+      R0H_TRY(r0h_accum_public_device(ctx, c, po2, code->witness, data, st->own_globals.get(), &mix, st->own_accum.get()));
+    }
+    return proof_finish_enqueue(*st, st->own_accum.get());
+  }();
+  if (err) {
+    (void)ctx_wait(ctx);
+    return err;
+  }
+  *out = st.release();
+  return nullptr;
+  R0H_GUARD_END
+}
+const char* r0h_prove_segment_collect(r0h_proof* proof, uint32_t* seal_out, size_t seal_cap, size_t* seal_words_out) {
+  return r0h_proof_finish_collect(proof, seal_out, seal_cap, seal_words_out);
+}
+// the DATA root where it stands on the device (node 1 of the group's tree): eight words to `out`, device to device, no wait
+const char* r0h_proof_data_root_device(const r0h_proof* proof, r0h_buf* out, size_t word_offset) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(proof && out, "r0h_proof_data_root_device: NULL argument");
+  R0H_TRY(require_words_in("r0h_proof_data_root_device", "root", out, word_offset, 8));
+  R0H_TRY_HIP(hipSetDevice(proof->ctx->device));
+  return copy_words(proof->ctx, out, word_offset, proof->g_data.tree.nodes.get(), 8, 8);
+  R0H_GUARD_END
+}
+
 // Commit the CODE group once (the sequencer's commit_code: code_commit above) and keep it, with a copy of the columns.
 const char* r0h_code_commit_new(r0h_ctx* ctx, const r0h_buf* code, uint32_t count, uint32_t po2, r0h_code_commit** out) {
   R0H_GUARD_BEGIN
@@ -1192,9 +1321,17 @@ const char* r0h_proof_finish(r0h_proof* proof, const r0h_buf* accum, uint32_t* s
 }
 
 const char* r0h_proof_data_root(const r0h_proof* proof, uint32_t root_out[8]) {
+  R0H_GUARD_BEGIN
   R0H_REQUIRE(proof && root_out, "r0h_proof_data_root: NULL argument");
+  if (!proof->data_root_home) {  // begun by r0h_proof_begin_committed[_top]_enqueue: node 1 comes home now, eight words and a wait
+    R0H_TRY_HIP(hipSetDevice(proof->ctx->device));
+    R0H_TRY(r0h_buf_d2h(proof->ctx, proof->g_data.tree.nodes.get(), 32, proof->data_root, 32));
+    proof->data_root_home = true;
+    proof->root_read_back = true;
+  }
   memcpy(root_out, proof->data_root, 32);
   return nullptr;
+  R0H_GUARD_END
 }
 const char* r0h_proof_late(r0h_proof* proof, const uint32_t* late_globals, uint32_t* mix_out) {
   R0H_GUARD_BEGIN
@@ -1253,7 +1390,12 @@ const char* r0h_proof_abort(r0h_proof* proof) {
   // buffers, so they have run before anything is released
   if (proof->enqueued || proof->iop) {
     (void)hipSetDevice(proof->ctx->device);
-    (void)ctx_wait(proof->ctx);
+    // (the stream's own answer: nothing an earlier call enqueued for this proof, or for another on its context, is missed)
+    const bool idle = proof->root_read_back && hipStreamQuery(proof->ctx->stream) == hipSuccess;
+    if (!idle) {
+      (void)hipGetLastError();
+      (void)ctx_wait(proof->ctx);
+    }
   }
   delete proof;
   return nullptr;
@@ -1276,10 +1418,13 @@ const char* r0h_proof_shrink(r0h_proof* proof, size_t* bytes_freed_out) {
   return nullptr;
   R0H_GUARD_END
 }
-// what the proof owns on the device: its groups, and CODE only where it committed the columns itself
+// what the proof owns on the device: its groups, CODE only where it committed the columns itself, and what a proof submitted whole
+// (r0h_prove_segment_committed_enqueue) keeps until its collect: the ACCUM witness and the device copy of the public inputs
 size_t r0h_proof_resident_bytes(const r0h_proof* proof) {
   if (!proof) return 0;
-  return proof->own_code.g.bytes() + proof->g_accum.bytes() + proof->g_data.bytes() + proof->g_check.bytes();
+  size_t kept = 0;
+  for (const r0h_buf* b : {proof->own_accum.get(), proof->own_globals.get()}) kept += b ? b->bytes : 0;
+  return proof->own_code.g.bytes() + proof->g_accum.bytes() + proof->g_data.bytes() + proof->g_check.bytes() + kept;
 }
 
 // The control root of a program at one trace size: the Merkle root of its committed CODE group (risc0 keeps one such root per

@@ -109,6 +109,9 @@ int main(int argc, char** argv) {
            "device, with one read-back for all of them, whatever --device-transcript says -- the same seals and receipts (default 0)\n"
            "       --session-enqueue 0|1: with --elf over the trace circuit; with 1 the second phase of every session is driven by the calling thread alone: each segment's session sum, "
            "late inputs, accumulation and finish are enqueued on its lane's stream and collected one segment per lane later -- the same receipt (default: R0H_SESSION_ENQUEUE, else 0)\n"
+           "       --session-enqueue-begin 0|1: with --elf over the trace circuit; with 1 the calling thread drives the first phase of every session as well -- no lane threads, the DATA "
+           "roots read back once per lane, evicted segments committed again without a wait, the image proof enqueued -- and --session-enqueue 1 is implied; the same receipt "
+           "(default: R0H_SESSION_ENQUEUE_BEGIN, else 0)\n"
            "       --merkle-fused-tops 0|1: with 1 every Merkle tree is built with its levels of up to 8192 parents in two launches (r0h_hash_fold_top) instead of one launch per level "
            "-- the same trees, seals and receipts (default: R0H_MERKLE_FUSED_TOPS, else 0)\n%s\n", r0h_version());
     return argc < 2 ? 1 : 0;
@@ -136,6 +139,7 @@ int main(int argc, char** argv) {
   unsigned session_keep_tree_tops = 0;  // --session-keep-tree-tops: r0h_ctx_set_session_tree_tops of every session context
   std::string device_transcript = "0";  // --device-transcript: r0h_ctx_set_device_transcript of every context
   std::string device_finish = "0";      // --device-finish: r0h_ctx_set_device_finish of every context
+  std::string session_enqueue_begin;    // --session-enqueue-begin: r0h_ctx_set_session_enqueue_begin of every session context (not given: the library's default)
   std::string session_enqueue;          // --session-enqueue: r0h_ctx_set_session_enqueue of every session context (not given: the library's default)
   bool merkle_fused_given = false;
   std::string merkle_fused_tops;        // --merkle-fused-tops: r0h_ctx_set_merkle_fused_tops of every context (not given: the library's default)
@@ -161,6 +165,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--device-transcript")) device_transcript = argv[i + 1];
     else if (!strcmp(argv[i], "--device-finish")) device_finish = argv[i + 1];
     else if (!strcmp(argv[i], "--session-enqueue")) session_enqueue = argv[i + 1];
+    else if (!strcmp(argv[i], "--session-enqueue-begin")) session_enqueue_begin = argv[i + 1];
     else if (!strcmp(argv[i], "--merkle-fused-tops")) { merkle_fused_tops = argv[i + 1]; merkle_fused_given = true; }
     else if (!strcmp(argv[i], "--receipt-out")) receipt_out = argv[i + 1];
     else if (!strcmp(argv[i], "--receipt-dir")) receipt_dir = argv[i + 1];
@@ -205,6 +210,10 @@ int main(int argc, char** argv) {
   }
   if (!session_enqueue.empty() && ((session_enqueue != "0" && session_enqueue != "1") || elf_path.empty())) {
     fprintf(stderr, "r0h_prove: --session-enqueue is 0 or 1 and goes with --elf, not %s\n", session_enqueue.c_str());
+    return 2;
+  }
+  if (!session_enqueue_begin.empty() && ((session_enqueue_begin != "0" && session_enqueue_begin != "1") || elf_path.empty())) {
+    fprintf(stderr, "r0h_prove: --session-enqueue-begin is 0 or 1 and goes with --elf, not %s\n", session_enqueue_begin.c_str());
     return 2;
   }
   if (merkle_fused_given && merkle_fused_tops != "0" && merkle_fused_tops != "1") {
@@ -256,6 +265,7 @@ int main(int argc, char** argv) {
     if (device_transcript == "1") CHECK(r0h_ctx_set_device_transcript(ctx, 1));
     if (device_finish == "1") CHECK(r0h_ctx_set_device_finish(ctx, 1));
     if (!session_enqueue.empty()) CHECK(r0h_ctx_set_session_enqueue(ctx, session_enqueue == "1"));
+    if (!session_enqueue_begin.empty()) CHECK(r0h_ctx_set_session_enqueue_begin(ctx, session_enqueue_begin == "1"));
     if (merkle_fused_given) CHECK(r0h_ctx_set_merkle_fused_tops(ctx, merkle_fused_tops == "1"));
     if (check_balance) CHECK(r0h_ctx_set_check_balance(ctx, 1));
     if (check_session) CHECK(r0h_ctx_set_check_session(ctx, 1));

@@ -361,6 +361,7 @@ struct r0h_session {
   std::vector<uint8_t> journal;
   std::vector<uint8_t> elf;  // kept for the image proof (r0h_ctx_set_image_circuit) and for the session check's verifier side
   bool check_session = false;  // r0h_ctx_set_check_session was on when the session began
+  bool enqueue_begin = false;  // r0h_ctx_set_session_enqueue_begin (or R0H_SESSION_ENQUEUE_BEGIN=1): phase 1 on the calling thread too, the image proof enqueued; implies `enqueue`
   bool enqueue = false;        // r0h_ctx_set_session_enqueue (or R0H_SESSION_ENQUEUE=1) was on when the session began: phase 2 on the calling thread alone
   uint8_t image_id[32] = {0};
   uint64_t cycles = 0;
@@ -522,6 +523,165 @@ uint32_t lane_count() {  // two prover lanes by default
   if (const char* v = getenv("R0H_SESSION_LANES")) n = (uint32_t)strtoul(v, nullptr, 10);
   return n < 1 ? 1 : n > 4 ? 4 : n;
 }
+bool enqueue_begin_default() {  // R0H_SESSION_ENQUEUE_BEGIN=1, unless the session's context says otherwise
+  const char* v = getenv("R0H_SESSION_ENQUEUE_BEGIN");
+  return v && strtoul(v, nullptr, 10) == 1;
+}
+uint64_t lane_waits(const r0h_session* s) {
+  uint64_t n = 0;
+  for (const r0h_ctx* l : s->lane_ctx) n += l->blocking_waits.load();
+  return n;
+}
+
+// ---- phase 1 from the calling thread (r0h_ctx_set_session_enqueue_begin).  The thread takes every segment from the executor's queue
+// and enqueues all of its phase 1 on the next lane's stream: the upload of its rows, the expansion, the multiplicity kernels and the
+// begin of its proof with the transcript on the device (r0h_proof_begin_committed_enqueue).  Nothing of that waits.  What the host needs
+// of a segment -- its DATA root for the session's records, and the multiplicity kernels' error word -- is gathered device to device
+// into one buffer per lane (GATHER_WORDS a segment) and read back once per lane when the executor has finished.  A segment's rows are
+// page-locked host memory the executor wants back: they stay with the lane until the event behind their copy has passed, which is
+// looked at, without waiting, at every segment (a lane that holds more than two such segments waits for its oldest copy, counted).  A segment beyond the device
+// limit needs its root before it gives up its proof: that read-back (r0h_proof_data_root) is the one wait of an eviction; the abort
+// behind it finds the stream idle.  A segment beyond the resident limit gives its evaluations back as it is begun (r0h_proof_shrink
+// waits, as ever: one wait each, counted).
+constexpr uint32_t GATHER_WORDS = 9, GATHER_SLOTS = 64;
+const char* begin_enqueued(r0h_session* ses, Feed& feed, RowBuffers& rows) {
+  const r0h_circuit* c = ses->c;
+  struct Upload { Feed::Segment seg; hipEvent_t done; };
+  struct Lane { r0h_ctx* ctx; bool was_finish; DevBuf gather; std::vector<size_t> slots; std::deque<Upload> uploads; };
+  std::vector<Lane> lanes;
+  for (r0h_ctx* l : ses->lane_ctx) {
+    lanes.push_back(Lane{l, l->device_finish, DevBuf(), {}, {}});
+    l->device_finish = true;  // for the length of the phase, as phase 2 does
+  }
+  std::vector<Pending> made;
+  r0h_session::Device& dev = ses->device;
+  const uint64_t waits0 = lane_waits(ses);
+  // the rows whose copies have run go back to the executor, oldest first; a lane keeps the rows of at most `keep` segments whose
+  // copies have not (72 MiB each at 2^20 rows): beyond that it waits for the oldest copy, and the wait is counted
+  auto release = [&](Lane& l, size_t keep) {
+    while (!l.uploads.empty()) {
+      Upload& u = l.uploads.front();
+      if (!u.done || hipEventQuery(u.done) != hipSuccess) {  // (no event: the segment's enqueue failed before it had one)
+        (void)hipGetLastError();
+        if (l.uploads.size() <= keep) return;
+        l.ctx->blocking_waits++;
+        if (u.done) (void)hipEventSynchronize(u.done);
+        else (void)hipStreamSynchronize(l.ctx->stream);
+      }
+      if (u.done) (void)hipEventDestroy(u.done);
+      l.uploads.pop_front();
+    }
+  };
+  auto flush = [&](Lane& l) -> const char* {  // the lane's gathered words come home: one read-back
+    if (l.slots.empty()) return nullptr;
+    std::vector<uint32_t> host(l.slots.size() * GATHER_WORDS);
+    R0H_TRY(r0h_buf_d2h(l.ctx, l.gather.get(), 0, host.data(), host.size() * 4));
+    for (size_t k = 0; k < l.slots.size(); k++) {
+      memcpy(made[l.slots[k]].root, host.data() + k * GATHER_WORDS, 32);
+      R0H_TRY(logup_multiplicities_verdict(host[k * GATHER_WORDS + 8]));
+    }
+    l.slots.clear();
+    return nullptr;
+  };
+  std::vector<uint32_t> global(c->n_global);
+  const char* err = [&]() -> const char* {
+    for (size_t k = 0;; k++) {
+      Feed::Segment taken;
+      R0H_TRY(feed.next(taken));
+      if (!taken) break;
+      Lane& l = lanes[k % lanes.size()];
+      r0h_ctx* lctx = l.ctx;
+      R0H_TRY_HIP(hipSetDevice(lctx->device));
+      for (Lane& other : lanes) release(other, 2);
+      // from here on the lane keeps the rows, whatever becomes of the segment: a copy that reads them may be queued when a later step fails
+      l.uploads.push_back(Upload{std::move(taken), nullptr});
+      const Produced* const seg = l.uploads.back().seg.get();
+      DevBuf data;  // (before `pend`: a proof that fails is aborted before its DATA block goes back)
+      Pending pend;
+      pend.index = seg->index;
+      pend.lctx = lctx;
+      pend.claim = seg->claim;
+      pend.po2 = trace_size(seg->rows.size() + seg->bounds.size());
+      if (pend.po2 < R0H_TRACE_MIN_PO2) pend.po2 = R0H_TRACE_MIN_PO2;
+      uint8_t cd[32];
+      claim_digest(seg->claim, cd);
+      std::fill(global.begin(), global.end(), 0u);
+      claim_globals(cd, global.data());
+      R0H_TRY(data.alloc(lctx, ((size_t)c->group_size[R0H_GROUP_DATA] << pend.po2) * 4));
+      R0H_TRY(ctx_code_commit(lctx, c, pend.po2, &pend.cc_held));  // (the first segment of a size on a context commits CODE, and waits for it)
+      pend.cc = pend.cc_held.get();
+      const Clock::time_point t0 = Clock::now();
+      rows.pin(seg->rows.data(), seg->rows.capacity() * sizeof(r0h_preflight_row));
+      const r0h_trace_segment ts = {seg->info.index + 1, seg->info.closing, seg->info.pre.pc, 0};
+      r0h_trace_rows* staged = nullptr;
+      R0H_TRY(trace_rows_upload_enqueue(lctx, seg->rows.data(), seg->rows.size(), seg->bounds.data(), seg->bounds.size(), pend.po2, &ts, &staged, global.data()));
+      pend.rows.reset(staged);
+      R0H_TRY_HIP(hipEventCreateWithFlags(&l.uploads.back().done, hipEventDisableTiming));
+      R0H_TRY_HIP(hipEventRecord(l.uploads.back().done, lctx->stream));
+      if (!l.gather) R0H_TRY(l.gather.alloc(lctx, (size_t)GATHER_SLOTS * GATHER_WORDS * 4));
+      if (l.slots.size() == GATHER_SLOTS) R0H_TRY(flush(l));
+      const size_t at = l.slots.size() * GATHER_WORDS;
+      R0H_TRY(r0h_trace_rows_expand(pend.rows.get(), data.get()));
+      R0H_TRY(logup_multiplicities_enqueue(lctx, c, pend.po2, data.get(), global.data(), l.gather.get(), at + 8));
+      const Clock::time_point t1 = Clock::now();
+      r0h_proof* proof = nullptr;
+      R0H_TRY(r0h_proof_begin_committed_enqueue(lctx, c, pend.po2, pend.cc, data.get(), global.data(), nullptr, &proof));
+      pend.proof.reset(proof);
+      R0H_TRY(r0h_proof_data_root_device(proof, l.gather.get(), at));
+      if (!dev.limit) pend.rows.reset();  // nothing will be committed twice (the block goes back to the lane's pool in stream order)
+      pend.rows_bytes = r0h_trace_rows_bytes(pend.rows.get());
+      const uint64_t cost = data->bytes + r0h_proof_resident_bytes(proof) + pend.rows_bytes;
+      pend.evicted = dev.limit && dev.counted + cost > dev.limit;
+      uint64_t top_bytes = 0;
+      if (pend.evicted) {
+        dev.evicted++;
+        if (dev.tops_levels) {  // the DATA tree's top stays, device to device (merkle_top_copy out of the nodes the root is read from)
+          top_bytes = ((((uint64_t)R0H_INV_RATE << pend.po2) * 2) >> dev.tops_levels) * 32;
+          R0H_TRY(pend.top.alloc(lctx, top_bytes));
+          R0H_TRY(r0h_proof_data_top(proof, dev.tops_levels, pend.top.get()));
+          dev.tops_held += top_bytes;
+          dev.tops_peak = std::max(dev.tops_peak, dev.tops_held);
+        }
+        R0H_TRY(r0h_proof_data_root(proof, pend.root));  // the wait of an eviction: everything the segment had on the stream has run
+        pend.proof.reset();                               // (aborted without a second wait)
+        data.reset();
+      } else {
+        dev.counted += cost;
+        dev.counted_peak = std::max(dev.counted_peak, dev.counted);
+        // beyond the session's resident limit a segment waits for the challenge without its evaluations: given back as it is begun, as
+        // in the lanes' form (r0h_proof_shrink waits for the lane's stream: one wait a lean segment, counted)
+        const uint64_t evaluations = ((uint64_t)c->group_size[R0H_GROUP_DATA] << pend.po2) * 16;
+        if (ses->resident_evaluations + evaluations > ses->resident_limit) {
+          ses->stats.lean_segments++;
+          R0H_TRY(r0h_proof_shrink(proof, nullptr));
+        } else {
+          ses->resident_evaluations += evaluations;
+        }
+      }
+      dev.rows_held += pend.rows_bytes;
+      dev.rows_peak = std::max(dev.rows_peak, dev.rows_held);
+      pend.held.set(ses->ctx, pend.evicted ? pend.rows_bytes + top_bytes : cost);
+      pend.global = global;
+      pend.data = std::move(data);
+      ses->stats.witgen_ms += 1e3 * seconds(t0, t1);
+      ses->stats.prove_ms += 1e3 * seconds(t1, Clock::now());
+      made.push_back(std::move(pend));
+      l.slots.push_back(made.size() - 1);
+    }
+    for (Lane& l : lanes) R0H_TRY(flush(l));
+    return nullptr;
+  }();
+  for (Lane& l : lanes) {
+    if (err) (void)ctx_wait(l.ctx);  // what was launched reads the rows: it runs out before they go back
+    release(l, 0);  // (behind the lane's read-back every copy has run)
+    l.ctx->device_finish = l.was_finish;
+  }
+  const uint64_t phase1[4] = {0, lane_waits(ses) - waits0, made.size(), dev.evicted};
+  memcpy(ses->ctx->session_phase1, phase1, sizeof phase1);
+  if (err) return err;  // (`made` goes: proofs aborted, buffers back)
+  for (Pending& p : made) ses->pending.push_back(std::move(p));
+  return nullptr;
+}
 bool enqueue_default() {  // R0H_SESSION_ENQUEUE=1: sessions finish from one host thread unless their context says otherwise
   const char* v = getenv("R0H_SESSION_ENQUEUE");
   return v && strtoul(v, nullptr, 10) == 1;
@@ -539,6 +699,12 @@ const char* r0h_last_session_stats(r0h_ctx* ctx, r0h_session_stats* out) {
 const char* r0h_last_session_phase2(r0h_ctx* ctx, uint64_t out[4]) {
   R0H_REQUIRE(ctx && out, "r0h_last_session_phase2: NULL argument");
   memcpy(out, ctx->session_phase2, sizeof ctx->session_phase2);
+  return nullptr;
+}
+
+const char* r0h_last_session_phase1(r0h_ctx* ctx, uint64_t out[4]) {
+  R0H_REQUIRE(ctx && out, "r0h_last_session_phase1: NULL argument");
+  memcpy(out, ctx->session_phase1, sizeof ctx->session_phase1);
   return nullptr;
 }
 
@@ -579,6 +745,10 @@ const char* r0h_session_begin(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t*
               "r0h_session_begin: r0h_ctx_set_check_session is on and this is part %u of %u: a rank sees its own segments only, the session check covers single-rank sessions", part, parts);
   ses->check_session = trace_mode && ctx->check_session;
   ses->enqueue = trace_mode && (ctx->session_enqueue < 0 ? enqueue_default() : ctx->session_enqueue > 0);
+  ses->enqueue_begin = trace_mode && (ctx->session_enqueue_begin < 0 ? enqueue_begin_default() : ctx->session_enqueue_begin > 0);
+  R0H_REQUIRE(!ses->enqueue_begin || parts == 1,
+              "r0h_session_begin: r0h_ctx_set_session_enqueue_begin is on and this is part %u of %u: a sharded session runs its first phase on lane threads (turn the switch off)", part, parts);
+  if (ses->enqueue_begin) ses->enqueue = true;  // phase 2 from the calling thread as well
   if (trace_mode && ((ctx->image_circuit && part == 0) || ses->check_session)) ses->elf.assign(elf, elf + elf_len);
   ses->device.limit = trace_mode ? ctx->session_device_limit : 0;
   ses->device.tops_levels = ses->device.limit ? ctx->session_tree_tops : 0;  // (only an evicted segment keeps a top)
@@ -606,7 +776,14 @@ const char* r0h_session_begin(r0h_ctx* ctx, const r0h_circuit* c, const uint8_t*
   ses->lane_ctx.assign(lane_count(), ctx);
   for (size_t k = 1; k < ses->lane_ctx.size(); k++) R0H_TRY(ctx_helper(ctx, k - 1, &ses->lane_ctx[k]));
   feed.set_lanes(ses->lane_ctx.size());
-  R0H_TRY(run_lanes(ses->lane_ctx, [&](r0h_ctx* lctx) { return take_segments(ses.get(), feed, rows, lctx); }, [&] { feed.stop(); }));
+  if (ses->enqueue_begin) {
+    R0H_TRY(begin_enqueued(ses.get(), feed, rows));
+  } else {
+    const uint64_t waits0 = lane_waits(ses.get());
+    R0H_TRY(run_lanes(ses->lane_ctx, [&](r0h_ctx* lctx) { return take_segments(ses.get(), feed, rows, lctx); }, [&] { feed.stop(); }));
+    const uint64_t phase1[4] = {ses->lane_ctx.size() - 1, lane_waits(ses.get()) - waits0, ses->pending.size(), ses->device.evicted};
+    memcpy(ctx->session_phase1, phase1, sizeof phase1);
+  }
 
   const Feed::Run& run = feed.join();
   R0H_REQUIRE(run.exit_kind != R0H_VM_LIMIT, "r0h_prove_elf: the guest did not halt within %llu cycles (session limit)", (unsigned long long)max_cycles);
@@ -737,12 +914,46 @@ const char* replay_segment(r0h_session* s, Pending& p) {
   return nullptr;
 }
 
+// Phase 2 of an evicted segment under r0h_ctx_set_session_enqueue_begin: committed again from its rows without a wait.  The root it
+// commits and the multiplicity kernels' error word go to `check`, which collect_segment reads back behind the seal and holds against
+// the recorded root.
+const char* replay_enqueued(r0h_session* s, Pending& p, DevBuf& check) {
+  const Clock::time_point t0 = Clock::now();
+  R0H_TRY(p.data.alloc(p.lctx, ((size_t)s->c->group_size[R0H_GROUP_DATA] << p.po2) * 4));
+  R0H_TRY(check.alloc(p.lctx, GATHER_WORDS * 4));
+  p.lctx->prof.continued = true;
+  const char* err = [&]() -> const char* {
+    R0H_TRY(r0h_trace_rows_expand(p.rows.get(), p.data.get()));
+    R0H_TRY(logup_multiplicities_enqueue(p.lctx, s->c, p.po2, p.data.get(), p.global.data(), check.get(), 8));
+    r0h_proof* proof = nullptr;
+    if (p.top) R0H_TRY(r0h_proof_begin_committed_top_enqueue(p.lctx, s->c, p.po2, p.cc, p.data.get(), p.global.data(), p.top.get(), s->device.tops_levels, nullptr, &proof));
+    else R0H_TRY(r0h_proof_begin_committed_enqueue(p.lctx, s->c, p.po2, p.cc, p.data.get(), p.global.data(), nullptr, &proof));
+    p.proof.reset(proof);
+    return r0h_proof_data_root_device(proof, check.get(), 0);
+  }();
+  p.lctx->prof.continued = false;
+  R0H_TRY(err);
+  p.evicted = false;
+  p.rows.reset();  // (back to the lane's pool in stream order, behind the expansion)
+  const uint64_t top_bytes = p.top ? p.top->bytes : 0;
+  p.top.reset();   // (the proof has its own copy)
+  p.held.set(s->ctx, p.data->bytes + r0h_proof_resident_bytes(p.proof.get()));
+  std::lock_guard<std::mutex> lk(s->result_mu);
+  s->device.replayed++;
+  if (top_bytes) s->device.replayed_from_top++;
+  s->device.tops_held -= top_bytes;
+  s->device.rows_held -= p.rows_bytes;
+  s->stats.prove_ms += 1e3 * seconds(t0, Clock::now());
+  return nullptr;
+}
+
 // ---- phase 2 from one host thread (r0h_ctx_set_session_enqueue).  Once the challenge exists nothing a segment needs comes from the host:
 // its public inputs go up once, the session sum is left in their device copy (logup_totals_keep_device), the device generator absorbs
 // the late inputs and draws the mix (r0h_proof_late_device), the accumulation reads both where they are (logup_accum_kept_device) and
 // the finish is enqueued.  What the enqueued steps read stays with the segment's InFlight until it is collected.
 struct InFlight {
   Pending* p = nullptr;
+  DevBuf check;  // of a segment replayed without a wait (replay_enqueued): its root and the multiplicity kernels' error word, read back behind the collect
   DevBuf data, globals, mix, accum;
   Clock::time_point t0;
 };
@@ -775,6 +986,12 @@ const char* collect_segment(r0h_session* s, InFlight& fl, std::vector<uint32_t>&
   Pending& p = *fl.p;
   size_t words = 0;
   const char* err = r0h_proof_finish_collect(p.proof.release(), seal.data(), seal.size(), &words);  // consumed either way: the stream has drained
+  if (!err && fl.check) {  // a segment replayed without a wait: what it committed is looked at now
+    uint32_t got[GATHER_WORDS];
+    err = r0h_buf_d2h(p.lctx, fl.check.get(), 0, got, sizeof got);
+    if (!err) err = logup_multiplicities_verdict(got[8]);
+    if (!err && memcmp(got, p.root, 32)) err = make_error("r0h_session_finish: segment %zu committed another root when it was replayed", p.index);
+  }
   fl = InFlight();
   if (p.rows) {
     p.rows.reset();
@@ -787,11 +1004,6 @@ const char* collect_segment(r0h_session* s, InFlight& fl, std::vector<uint32_t>&
   p.seal.assign(seal.begin(), seal.begin() + words);
   p.done = true;
   return nullptr;
-}
-uint64_t lane_waits(const r0h_session* s) {
-  uint64_t n = 0;
-  for (const r0h_ctx* l : s->lane_ctx) n += l->blocking_waits.load();
-  return n;
 }
 uint64_t lane_ring_waits(const r0h_session* s) {
   uint64_t n = 0;
@@ -806,7 +1018,7 @@ uint64_t lane_ring_waits(const r0h_session* s) {
 // lane is being collected the others' streams have their segment to run.  After the first round -- every lane that holds a segment has
 // had its first enqueue -- the image proof is made; when no lane has anything left to enqueue, what is still in flight is collected,
 // oldest first.  An error ends the rounds: what is in flight is collected, then every other proof is aborted.
-const char* finish_enqueued(r0h_session* s, const uint32_t challenge[16], std::vector<uint32_t>& image_seal, uint64_t* other_waits) {
+const char* finish_enqueued(r0h_session* s, const uint32_t challenge[16], std::vector<uint32_t>& image_seal, uint64_t* other_waits, uint64_t* off_lane_waits) {
   struct Lane { r0h_ctx* ctx; std::deque<Pending*> todo; InFlight flying; };
   std::vector<Lane> lanes;  // in the order of their first segment
   for (Pending& p : s->pending) {
@@ -825,6 +1037,7 @@ const char* finish_enqueued(r0h_session* s, const uint32_t challenge[16], std::v
   };
   auto collect = [&](Lane& l) {
     const Clock::time_point t0 = l.flying.t0;
+    if (l.flying.check) *other_waits += 1;  // a replayed segment's root comes home behind its seal
     const char* err = collect_segment(s, l.flying, seal);
     order.erase(std::find(order.begin(), order.end(), &l));
     if (!err) {
@@ -848,6 +1061,23 @@ const char* finish_enqueued(r0h_session* s, const uint32_t challenge[16], std::v
     note(err);
   };
   bool image_due = !s->elf.empty() && s->ctx->image_circuit;
+  // r0h_ctx_set_session_enqueue_begin: the image proof is enqueued now that the challenge exists, on a helper context of its own -- a
+  // context reports one proof at a time, and every lane's context has segments to report -- and collected behind the last segment
+  r0h_image_proof* image_flying = nullptr;
+  r0h_ctx* image_ctx = nullptr;
+  bool image_ctx_finish = false;
+  uint64_t image_waits0 = 0;
+  if (image_due && s->enqueue_begin) {
+    image_due = false;
+    const char* err = ctx_helper(s->ctx, s->lane_ctx.size() - 1, &image_ctx);
+    if (!err) {
+      image_ctx_finish = image_ctx->device_finish;
+      image_ctx->device_finish = true;
+      image_waits0 = image_ctx->blocking_waits.load();
+      err = r0h_prove_image_enqueue(image_ctx, s->ctx->image_circuit, s->elf.data(), s->elf.size(), challenge, &image_flying);
+    }
+    note(err);
+  }
   for (bool any = true; any && !first;) {
     any = false;
     for (Lane& l : lanes) {
@@ -858,7 +1088,10 @@ const char* finish_enqueued(r0h_session* s, const uint32_t challenge[16], std::v
       if (first) break;
       Pending& p = *l.todo.front();
       l.todo.pop_front();
-      if (p.evicted) {  // blocking, as in the lanes' form: its root comes to the host to be compared
+      if (p.evicted && s->enqueue_begin) {  // enqueued: its root is compared behind its collect (one read-back there)
+        note(replay_enqueued(s, p, l.flying.check));
+        if (first) { p.proof.reset(); l.flying = InFlight(); break; }
+      } else if (p.evicted) {  // blocking, as in the lanes' form: its root comes to the host to be compared
         const uint64_t w0 = lane_waits(s);
         note(replay_segment(s, p));
         *other_waits += lane_waits(s) - w0;
@@ -879,6 +1112,17 @@ const char* finish_enqueued(r0h_session* s, const uint32_t challenge[16], std::v
     }
   }
   while (!order.empty()) collect(*order.front());  // after an error too: what is in flight is collected, its seal kept or its error dropped
+  if (image_flying) {
+    size_t words = 0;
+    const char* err = first ? r0h_prove_image_abort(image_flying) : r0h_prove_image_collect(image_flying, seal.data(), seal.size(), &words);
+    if (!err && !first) image_seal.assign(seal.begin(), seal.begin() + words);
+    note(err);
+  }
+  if (image_ctx) {
+    *off_lane_waits = image_ctx->blocking_waits.load() - image_waits0;  // (no lane's context: counted beside the lanes')
+    *other_waits += *off_lane_waits;
+    image_ctx->device_finish = image_ctx_finish;
+  }
   if (first)
     for (Pending& p : s->pending) {  // the others' proofs are aborted, and what they held goes with them
       if (p.done) continue;
@@ -916,9 +1160,10 @@ const char* r0h_session_finish(r0h_session* s, const uint32_t* all_records, size
       // the lanes' contexts finish on the device generator for the length of the phase, whatever their switch says
       std::vector<bool> was;
       for (r0h_ctx* l : s->lane_ctx) { was.push_back(l->device_finish); l->device_finish = true; }
-      const char* err = finish_enqueued(s, challenge, image_seal, &other_waits);
+      uint64_t off_lane_waits = 0;
+      const char* err = finish_enqueued(s, challenge, image_seal, &other_waits, &off_lane_waits);
       for (size_t k = 0; k < s->lane_ctx.size(); k++) s->lane_ctx[k]->device_finish = was[k];
-      const uint64_t phase2[4] = {1, lane_waits(s) - waits0, lane_ring_waits(s) - ring0, other_waits};
+      const uint64_t phase2[4] = {1, lane_waits(s) - waits0 + off_lane_waits, lane_ring_waits(s) - ring0, other_waits};  // (with the waits of the image proof's helper context)
       memcpy(s->ctx->session_phase2, phase2, sizeof phase2);
       R0H_TRY(err);
     }

@@ -132,6 +132,19 @@ const char* r0h_trace_rows_expand(const r0h_trace_rows* h, r0h_buf* data) {
   R0H_GUARD_END
 }
 
+}  // extern "C"
+const char* r0h::trace_rows_upload_enqueue(r0h_ctx* ctx, const r0h_preflight_row* rows, size_t n_rows, const r0h_preflight_bound* bounds, size_t n_bounds, uint32_t po2,
+                                           const r0h_trace_segment* segment, r0h_trace_rows** rows_out, uint32_t* globals_out) {
+  R0H_GUARD_BEGIN
+  R0H_REQUIRE(ctx && (rows || !n_rows) && (bounds || !n_bounds) && globals_out && segment && rows_out, "r0h_trace_rows_upload: NULL argument");
+  KScope ks(ctx, "trace_rows_upload", (double)n_rows * sizeof(r0h_preflight_row) + (double)n_bounds * sizeof(r0h_preflight_bound) + (double)sizeof(trace::Tables));
+  std::unique_ptr<r0h_trace_rows> h;
+  R0H_TRY(rows_upload("r0h_trace_rows_upload", ctx, rows, n_rows, bounds, n_bounds, po2, segment, false, &h, globals_out));
+  *rows_out = h.release();
+  return nullptr;
+  R0H_GUARD_END
+}
+extern "C" {
 size_t r0h_trace_rows_bytes(const r0h_trace_rows* h) { return h ? h->block->bytes : 0; }
 
 const char* r0h_trace_rows_free(r0h_trace_rows* h) {

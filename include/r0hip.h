@@ -257,6 +257,11 @@ const char* r0h_witgen_public(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, 
                               r0h_buf* code, r0h_buf* data);
 const char* r0h_accum(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data,
                       const uint32_t* mix_host, r0h_buf* accum);
+/* r0h_accum with the mix read from device memory, the circuit's n_mix words at mix_buf[mix_word_offset ..) -- where a device transcript
+ * drew them (r0h_proof_begin_committed_enqueue, r0h_proof_late_device).  The same accumulation word for word; waits for nothing.
+ * Canonicity of the device words is the producer's business (one of the device-challenge forms listed with r0h_ext_powers_buf). */
+const char* r0h_accum_mixbuf(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* code, const r0h_buf* data,
+                             const r0h_buf* mix_buf, size_t mix_word_offset, r0h_buf* accum);
 const char* r0h_eval_check(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_buf* eval_accum,
                            const r0h_buf* eval_code, const r0h_buf* eval_data, const uint32_t* global_host,
                            const uint32_t* mix_host, const uint32_t poly_mix[4], r0h_buf* check);
@@ -548,6 +553,41 @@ const char* r0h_proof_data_top(const r0h_proof* proof, uint32_t levels, r0h_buf*
 const char* r0h_proof_begin_committed_top(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code,
                                           const r0h_buf* data, const uint32_t* global_host, const r0h_buf* top, uint32_t levels,
                                           uint32_t* mix_out, r0h_proof** out);
+/* A proof's FIRST half enqueued: the hand-over before the DATA commitment, the earliest there is.  The generator goes to the device
+ * once the seal's public block and CODE's top layer -- host words of a kept commitment -- are in; DATA is interpolated, evaluated and
+ * hashed as ever, its top layer and root go device to device (the root into the device generator), and the call returns without
+ * waiting for the stream.  The DATA top layer comes home with the one read-back of r0h_proof_finish_collect and stands in the seal
+ * where the host form writes it: the seal is the same words.
+ *   r0h_proof_begin_committed_enqueue      r0h_proof_begin_committed.  For a circuit without late inputs the mix is drawn on the device
+ *                                          at once: copied into mix_out (a device buffer of n_mix words or more; NULL: not wanted) and
+ *                                          kept by the proof; accumulate from it with r0h_accum_mixbuf / r0h_accum_public_device.
+ *                                          For a circuit with late inputs the proof stops after DATA as ever and r0h_proof_late_device
+ *                                          takes it from there (it finds the generator handed over; the host r0h_proof_late refuses).
+ *   r0h_proof_begin_committed_top_enqueue  the same from a kept DATA tree top (r0h_proof_begin_committed_top): no tree is built.
+ *   r0h_proof_data_root                    on such a proof WAITS: node 1 is read back, eight words, the first time it is asked for.
+ *   r0h_proof_data_root_device             the root's eight words to out[word_offset ..), device to device, no wait (any proof): gather
+ *                                          the roots of many proofs and read them back once.
+ *   r0h_prove_segment_committed_enqueue    begin-enqueue + the late inputs (from global_host) + the accumulation + r0h_proof_finish_enqueue:
+ *                                          a whole proof submitted.  The proof keeps its ACCUM witness until the collect.
+ *   r0h_prove_segment_collect              r0h_proof_finish_collect of it: the seal of r0h_prove_segment_committed, word for word.
+ * A whole proof then waits twice: the read-back and the close of its profile.  All of them need r0h_ctx_set_device_finish on and a
+ * kept CODE commitment (r0h_code_commit_new: the columns forms commit CODE with a read-back that waits, and there is no enqueue form
+ * of them); both are refused by name before anything is launched, and a refusal changes nothing.  An error behind that consumes the
+ * proof (what was launched runs out first).  r0h_proof_late_device on such a proof cannot take the hand-over back: a step of it that
+ * fails leaves the proof fit for r0h_proof_abort only.  Until the collect `data`, the CODE commitment, a kept top's matrix and
+ * mix_out stay as they were given.  r0h_proof_abort waits for the proof's stream first; r0h_proof_shrink and
+ * r0h_proof_resident_bytes work as on any proof (the shrink waits, as ever; the bytes include the ACCUM witness a proof submitted whole keeps).  A context whose hash suite changed since the begin is
+ * refused by r0h_proof_late_device and the finish, as for every proof.  With r0h_ctx_set_check_balance on, the begin runs the checker
+ * first, read-backs and all; with r0h_ctx_set_check_witness on, the finish-enqueue reads the mix, the late inputs (if any) and the
+ * checker's table back: up to three waits more.  Phase names and their order are those of the blocking forms. */
+const char* r0h_proof_begin_committed_enqueue(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data,
+                                              const uint32_t* global_host, r0h_buf* mix_out, r0h_proof** out);
+const char* r0h_proof_begin_committed_top_enqueue(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data,
+                                                  const uint32_t* global_host, const r0h_buf* top, uint32_t levels, r0h_buf* mix_out, r0h_proof** out);
+const char* r0h_proof_data_root_device(const r0h_proof* proof, r0h_buf* out, size_t word_offset);
+const char* r0h_prove_segment_committed_enqueue(r0h_ctx* ctx, const r0h_circuit* c, uint32_t po2, const r0h_code_commit* code, const r0h_buf* data,
+                                                const uint32_t* global_host, r0h_proof** out);
+const char* r0h_prove_segment_collect(r0h_proof* proof, uint32_t* seal_out, size_t seal_capacity_words, size_t* seal_words_out);
 /* Per-phase device time (ms) of the last proof on this context that came out -- r0h_prove_segment*, r0h_proof_finish, or the session check
  * that closes a profile; names are static strings, *n_out names and times, valid until the next one closes.  A proof in flight, aborted or failed
  * leaves the report as it was; a context that has closed none reports *n_out = 0. */
@@ -1105,6 +1145,28 @@ const char* r0h_receipt_merge(const r0h_receipt* const* parts, size_t n, r0h_rec
  * the image proof. */
 const char* r0h_ctx_set_session_enqueue(r0h_ctx* ctx, int on);
 const char* r0h_last_session_phase2(r0h_ctx* ctx, uint64_t out[4]);
+/* r0h_ctx_set_session_enqueue_begin(ctx, on != 0): a switch of its own beside the one above, off by default (a context that was never
+ * told follows R0H_SESSION_ENQUEUE_BEGIN=1), taken per session at r0h_session_begin; it implies r0h_ctx_set_session_enqueue for the
+ * session.  The trace-circuit session is then driven by its calling thread and its executor thread and nothing else:
+ *   phase 1   no lane threads.  The thread inside r0h_prove_elf / r0h_session_begin takes each segment from the executor's queue and
+ *             enqueues, on the next lane's stream, the upload of its rows, the expansion, the multiplicity kernels and
+ *             r0h_proof_begin_committed_enqueue.  The DATA roots (and the multiplicity kernels' error words) are gathered device to
+ *             device (r0h_proof_data_root_device) into one buffer per lane and read back once per lane at the phase's end: WHAT WAITS
+ *             is that read-back, once per lane that had a segment; per evicted segment (r0h_ctx_set_session_device_limit) the
+ *             read-back of its root before it gives up its proof; per lean segment r0h_proof_shrink, as ever; a lane that holds the
+ *             rows of more than two segments whose copies have not run (the rows go back to the executor behind their copy); and
+ *             the CODE commitment of a trace size a context has not seen.  A lookup outside its table is reported at the phase's end.
+ *   phase 2   as under r0h_ctx_set_session_enqueue, and: an evicted segment is committed again through the enqueue begin (or its
+ *             _top form), so a replay no longer blocks -- the root it commits comes home behind its seal and is held against the
+ *             recorded one there (one read-back); the image proof is enqueued as soon as the challenge exists
+ *             (r0h_prove_image_enqueue) on a helper context of its own -- a context reports one proof at a time -- and collected
+ *             behind the last segment.
+ * The records, r0h_session_challenge, the seals and the receipt are the default form's byte for byte.  Sharded sessions
+ * (r0h_session_begin with parts > 1) refuse the switch.
+ * r0h_last_session_phase1: of the last trace-circuit session begun on this context -- host threads started for phase 1 (0 under the
+ * switch, lanes - 1 otherwise), the blocking waits the lanes' contexts made in it, its segments, and of them the evicted. */
+const char* r0h_ctx_set_session_enqueue_begin(r0h_ctx* ctx, int on);
+const char* r0h_last_session_phase1(r0h_ctx* ctx, uint64_t out[4]);
 typedef struct { uint32_t segments, lean_segments /* proved without resident evaluations: r0h_ctx_set_session_resident_limit */; uint64_t cycles; double executor_s, witgen_ms, prove_ms, wall_s; } r0h_session_stats;
 const char* r0h_last_session_stats(r0h_ctx* ctx, r0h_session_stats* out);
 
@@ -1132,6 +1194,20 @@ const char* r0h_ctx_set_image_circuit(r0h_ctx* ctx, const r0h_circuit* image_cir
 /* device: one image proof under `challenge` (r0h_session_challenge); seal_out may be NULL to ask for the size */
 const char* r0h_prove_image(r0h_ctx* ctx, const r0h_circuit* image_circuit, const uint8_t* elf, size_t elf_len, const uint32_t challenge[16],
                             uint32_t* seal_out, size_t seal_capacity_words, size_t* seal_words_out);
+/* The same proof in two calls (r0h_ctx_set_device_finish on), so that the thread that makes it can go on enqueueing elsewhere.
+ * r0h_prove_image_enqueue plants the witness, adds up the total on the device (r0h_logup_totals_device) and submits the proof through
+ * r0h_proof_begin_committed_enqueue, r0h_proof_late_device (the challenge and the total are the circuit's late inputs),
+ * r0h_accum_public_device and r0h_proof_finish_enqueue; it waits for nothing, except on the first call for a (context, trace size,
+ * suite): the image circuit's CODE group is committed then, once, and kept by the circuit's context like a session's CODE commitment.
+ * r0h_prove_image_collect is the read-back: the seal of r0h_prove_image, word for word; it consumes the handle either way
+ * (r0h_prove_image_abort: the handle given up, after its stream has drained).  A challenge word that is not canonical, a circuit that
+ * is not the image circuit and a context with the switch off are refused at the enqueue.  The ELF's bytes are not read after the
+ * enqueue returns.  A context reports one proof at a time: begin the next proof on `ctx` after the collect. */
+typedef struct r0h_image_proof r0h_image_proof;
+const char* r0h_prove_image_enqueue(r0h_ctx* ctx, const r0h_circuit* image_circuit, const uint8_t* elf, size_t elf_len, const uint32_t challenge[16],
+                                    r0h_image_proof** out);
+const char* r0h_prove_image_collect(r0h_image_proof* handle, uint32_t* seal_out, size_t seal_capacity_words, size_t* seal_words_out);
+const char* r0h_prove_image_abort(r0h_image_proof* handle);
 
 /* ---- recursion: risc0-zkvm `ProverServer::{lift, join, compress}` (risc0-circuit-recursion 4.0.4, Cargo.lock:3050-3085; BASELINE.json
  * configs[4]).  `lift` stands one recursion-circuit proof for one segment seal and its claim; `join` folds two nodes into one whose

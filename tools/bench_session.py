@@ -69,6 +69,8 @@ def main():
                     "transcript on the device, one read-back for all of them (default 0: off), the same receipt")
     ap.add_argument("--session-enqueue", type=int, default=None, choices=(0, 1), help="1: r0h_ctx_set_session_enqueue per session context -- the second phase of a session is driven by "
                     "the calling thread alone, every segment's finish enqueued on its lane's stream and collected later (default: R0H_SESSION_ENQUEUE, else off), the same receipt")
+    ap.add_argument("--session-enqueue-begin", type=int, default=None, choices=(0, 1), help="1: r0h_ctx_set_session_enqueue_begin per session context -- both phases of a session are driven "
+                    "by the calling thread, no lane threads, the image proof enqueued; implies --session-enqueue 1 (default: R0H_SESSION_ENQUEUE_BEGIN, else off), the same receipt")
     ap.add_argument("--merkle-fused-tops", type=int, default=None, choices=(0, 1), help="1: r0h_ctx_set_merkle_fused_tops per session context -- every tree's levels of up to 8192 parents "
                     "in two launches instead of fourteen (default: R0H_MERKLE_FUSED_TOPS, else off), the same receipt")
     args = ap.parse_args()
@@ -119,6 +121,8 @@ def main():
         hal.set_device_finish(True)
     if args.session_enqueue is not None:
         hal.set_session_enqueue(bool(args.session_enqueue))
+    if args.session_enqueue_begin is not None:
+        hal.set_session_enqueue_begin(bool(args.session_enqueue_begin))
     if args.merkle_fused_tops is not None:
         hal.set_merkle_fused_tops(bool(args.merkle_fused_tops))
     others = []  # further sessions in flight beside this one: a context and a loaded circuit each
@@ -137,6 +141,8 @@ def main():
                 h2.set_device_finish(True)
             if args.session_enqueue is not None:
                 h2.set_session_enqueue(bool(args.session_enqueue))
+            if args.session_enqueue_begin is not None:
+                h2.set_session_enqueue_begin(bool(args.session_enqueue_begin))
             if args.merkle_fused_tops is not None:
                 h2.set_merkle_fused_tops(bool(args.merkle_fused_tops))
             others.append((h2, h2.load_circuit(blob, entry.code_object_path("trace"))))
@@ -172,6 +178,7 @@ def main():
             env.barrier()
         wall = time.perf_counter() - t0
         st, dev, phase2 = hal.last_session_stats(), hal.last_session_device(), hal.last_session_phase2()
+        phase1 = hal.last_session_phase1()
         tops = hal.last_session_tree_tops() if args.keep_tree_tops else {"replayed_from_top": 0, "tops_bytes": 0, "levels": 0}
     if env is not None and args.check_session:  # every rank's exported bytes, in rank order
         mine = np.zeros(world, dtype=np.int64)
@@ -200,6 +207,8 @@ def main():
     n = len(seals) * max(1, args.sessions if env is None else 1)
     line = {"device_transcript": bool(args.device_transcript), "device_finish": bool(args.device_finish), "session_enqueue": bool(args.session_enqueue) if args.session_enqueue is not None else os.environ.get("R0H_SESSION_ENQUEUE") == "1",
             "merkle_fused_tops": bool(args.merkle_fused_tops) if args.merkle_fused_tops is not None else os.environ.get("R0H_MERKLE_FUSED_TOPS") == "1",
+            "session_enqueue_begin": bool(args.session_enqueue_begin) if args.session_enqueue_begin is not None else os.environ.get("R0H_SESSION_ENQUEUE_BEGIN") == "1",
+            "phase1_host_threads_of_the_reported_session": phase1["host_threads"], "phase1_blocking_waits_of_the_reported_session": phase1["blocking_waits"],
             "phase2_host_threads_of_the_reported_session": phase2["host_threads"], "phase2_blocking_waits_of_the_reported_session": phase2["blocking_waits"], "sessions_in_flight": args.sessions if env is None else 1, "lean_segments_of_the_reported_session": st["lean_segments"],
             "device_limit_GiB": args.device_limit_gb if device_limit else None, "evicted_segments_of_the_reported_session": dev["evicted"], "replayed_segments_of_the_reported_session": dev["replayed"],
             "peak_counted_bytes_of_the_reported_session": dev["peak_counted_bytes"], "rows_handle_bytes_of_the_reported_session": dev["rows_bytes"],
